@@ -9,6 +9,11 @@ step each) followed by the VAE decode to uint8, for `--batch-per-gpu` images on 
 SURVEY.md §8d timed region). Inputs (prompt embeddings, packed hint latents, regional mask, initial noise) are resident
 in HBM before the timed region. Weights are random-init FLUX.1-dev / RepText shapes (no checkpoints offline).
 Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times `--steps` passes and prints the line. `--full` adds what takes runs of its own: the
+output check (pass 0 run again, `output_check`), the per-launch roofline pass (`roofline`) and the CPU baseline
+(`cpu_baseline`); `--no-roofline-pass` / `--no-cpu-baseline` drop one of them from a `--full` run.
+`--dump-outputs DIR` writes rank 0's decoded image of the last timed pass as DIR/image.npy (float32, the uint8 values).
 """
 import argparse
 import json
@@ -43,11 +48,35 @@ def parse():
                     help="bf16 = BASELINE config 2 (the headline); config 5's 'fp8 weights': fp8-ln = LayerNorm-fed projections on the e4m3 "
                          "MFMA path, fp8 = every projection of the blocks (per-row scales, quantise passes) + e4m3 attention, fp8-mx = the same with "
                          "MX block-scaled operands written by the attention / GELU epilogues (no quantise passes)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline-pass", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the output check, the roofline pass and the CPU baseline after the timed passes")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline-pass", action="store_true", help="with --full: skip the roofline pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write rank 0's decoded image of the last timed pass to DIR/image.npy (float32)")
     ap.add_argument("--no-graph", action="store_true", help="enqueue every kernel of the loop from the host each pass instead of replaying the captured hipGraph")
     ap.add_argument("--depth-scale", type=float, default=1.0, help="DEBUG ONLY: scale layer counts (result flagged invalid)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+DUMP_MAX_BYTES = 60_000_000                      # payload cap of --dump-outputs (the .npy headers stay well under the 64 MB budget)
+
+
+def dump_outputs(out_dir, image):
+    """--dump-outputs: the decoded uint8 image(s) of the last timed pass, [B, H, W, 3] as float32, to out_dir/image.npy.
+    Larger than DUMP_MAX_BYTES (batches of big images): a fixed sample instead, the sorted flat indices drawn by
+    numpy.random.default_rng(0) without replacement, as a 1-D array."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    a = image.detach().to("cpu", torch.float32).numpy()
+    if a.nbytes > DUMP_MAX_BYTES:
+        idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_BYTES // a.itemsize, replace=False))
+        a = a.reshape(-1)[idx]
+    np.save(os.path.join(out_dir, "image.npy"), a)
 
 
 # ----------------------------------------------------------------------------------------- work model (BASELINE.md §2)
@@ -426,7 +455,7 @@ def main():
     first_out = None
     for k in range(args.steps):
         out = one_pass(k)
-        if k == 0:
+        if k == 0 and args.full:
             first_out = out                      # a reference only (every pass returns a fresh tensor): checked AFTER the timed region
     torch.cuda.synchronize()
     mine_s = time.perf_counter() - t0            # this rank's own shard, before it waits for the others
@@ -441,6 +470,8 @@ def main():
         allr = [torch.zeros(1, device=cdev, dtype=torch.float64) for _ in range(world)]
         dist.all_gather(allr, torch.tensor([mine_s], device=cdev, dtype=torch.float64))
         per_rank = [float(t.item()) for t in allr]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
 
     # ---- the bench looks at what it computed (outside the timed region): pass 0 is run again with the same sample ids
     check = None
@@ -473,7 +504,7 @@ def main():
     e2e_peak = 5.0e15 if full8 else 2.5e15                    # dense MFMA peak of the dtype the projections run in
 
     roofline = None
-    if rank == 0 and not args.no_roofline_pass:
+    if rank == 0 and args.full and not args.no_roofline_pass:
         import reptext_amd.pipeline as _pl
         pipe.capture_graphs = False              # per-launch events need the eager loop ...
         _ov, _pl.OVERLAP_TOWER = _pl.OVERLAP_TOWER, False          # ... with every kernel alone on the chip (no tower beside the transformer)
@@ -506,7 +537,7 @@ def main():
             roofline["bf16_gemm_launches"] = {"launches": nb, "achieved": round(flb / secb / 1e12, 1), "peak": 2500.0,
                                               "frac": round(flb / secb / 2.5e15, 4), "share_of_gemm_time": round(secb / (sec + secb), 3)}
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         pipe.capture_graphs = False
         cpu = cpu_baseline(cfg_t, H, W, args.inference_steps, args.text_lines, cfg_c, pipe=pipe if args.depth_scale == 1.0 and args.precision == "bf16" else None)
 

@@ -34,7 +34,7 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert bound == set(syms), f"binding/header mismatch: {bound ^ set(syms)}"
 
 
-def test_gemm_group_struct_layout_matches_c():
+def test_gemm_group_struct_layout_matches_c(tmp_path):
     """Compile a tiny host program against the header and compare sizeof/offsetof with the ctypes mirror."""
     from reptext_amd import native
 
@@ -45,9 +45,7 @@ def test_gemm_group_struct_layout_matches_c():
 int main(){ printf("%zu %zu %zu %zu %zu %zu\n", sizeof(rt_gemm_group), offsetof(rt_gemm_group, lda), offsetof(rt_gemm_group, strideA),
   offsetof(rt_gemm_group, M), offsetof(rt_gemm_group, out_f32), offsetof(rt_gemm_group, alpha)); return 0; }
 '''
-    d = os.path.join(ROOT, "gpurun_out")
-    os.makedirs(d, exist_ok=True)
-    src, exe = os.path.join(d, "_layout.c"), os.path.join(d, "_layout")
+    src, exe = str(tmp_path / "_layout.c"), str(tmp_path / "_layout")
     open(src, "w").write(prog)
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
     out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()

@@ -2,12 +2,12 @@
 # Round evidence in one go (run on the GPU box from the repo root): tools/collect_profiles.sh <tag>   e.g. r02
 # Writes under gpurun_out/prof_<tag>/ ; copy what is to be judged into profiles/.
 TAG=${1:-r03}
-R=$GRAFT_REPO_ROOT
+R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 export RT_OVERLAP_TOWER=0    # rocprof passes: every kernel alone on the chip (the bench lines of step 6 run the default, tower beside the transformer)
-B="python3 $R/bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-graph"
+B="python3 $R/bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-graph"
 echo "[1] kernel trace + stats (bf16)"; rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_bf16 -- $B > $OUT/bench_under_rocprof_bf16.json 2> $OUT/stats_bf16.err
 echo "[2] kernel trace + stats (fp8)";  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_fp8 -- $B --precision fp8 > $OUT/bench_under_rocprof_fp8.json 2> $OUT/stats_fp8.err
 echo "[2b] kernel trace + stats (fp8-mx)";  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_fp8mx -- $B --precision fp8-mx > $OUT/bench_under_rocprof_fp8mx.json 2> $OUT/stats_fp8mx.err
@@ -53,13 +53,13 @@ done
 echo "[6] bench lines"
 cd $R
 unset RT_OVERLAP_TOWER
-python3 bench.py > $OUT/bench_c2_bf16.json 2> $OUT/bench_c2_bf16.err
-python3 bench.py --no-cpu-baseline --precision fp8 > $OUT/bench_c2_fp8.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --batch-per-gpu 4 --steps 2 --warmup 1 > $OUT/bench_c3_batch4_bf16.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --height 1536 --width 1536 --steps 2 --warmup 1 > $OUT/bench_c5shape_1536_bf16.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --height 1536 --width 1536 --steps 2 --warmup 1 --precision fp8 > $OUT/bench_c5_1536_fp8.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --precision fp8-mx > $OUT/bench_c2_fp8mx.json 2>/dev/null
-python3 bench.py --no-cpu-baseline --height 1536 --width 1536 --steps 2 --warmup 1 --precision fp8-mx > $OUT/bench_c5_1536_fp8mx.json 2>/dev/null
+python3 bench.py --full > $OUT/bench_c2_bf16.json 2> $OUT/bench_c2_bf16.err
+python3 bench.py --full --no-cpu-baseline --precision fp8 > $OUT/bench_c2_fp8.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --batch-per-gpu 4 --steps 2 --warmup 1 > $OUT/bench_c3_batch4_bf16.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --height 1536 --width 1536 --steps 2 --warmup 1 > $OUT/bench_c5shape_1536_bf16.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --height 1536 --width 1536 --steps 2 --warmup 1 --precision fp8 > $OUT/bench_c5_1536_fp8.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --precision fp8-mx > $OUT/bench_c2_fp8mx.json 2>/dev/null
+python3 bench.py --full --no-cpu-baseline --height 1536 --width 1536 --steps 2 --warmup 1 --precision fp8-mx > $OUT/bench_c5_1536_fp8mx.json 2>/dev/null
 python3 tools/bench_inpaint.py > $OUT/bench_c4_inpaint.json 2> $OUT/bench_c4_inpaint.err
 python3 tools/mx_dev/time_gemm.py > $OUT/mx_gemm_microbench.txt 2>/dev/null
 python3 tools/bench_kernels.py all > $OUT/kernel_microbench.txt 2>/dev/null
