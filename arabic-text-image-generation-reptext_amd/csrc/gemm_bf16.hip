@@ -17,8 +17,6 @@
 // Reference math: torch.nn.functional.linear as reached from controlnet_flux.py:277,280,292,386,391 and the
 // diffusers blocks; epilogue terms documented in include/reptext_hip.h.
 #include "rt_common.h"
-#include <stdlib.h>
-#include <initializer_list>
 #include <type_traits>
 
 namespace {
@@ -26,47 +24,37 @@ namespace {
 constexpr int BK = 64;
 constexpr int THREADS = 512;
 
-// Tile geometry. 8 waves as 2(M) x 4(N); a wave's output is (NI0+NI1) x (NJ0+NJ1) fragments of 16x16, consumed per K-tile in the
-// four quadrants (a0,b0) (a0,b1) (a1,b1) (a1,b0) of its "halves" (a0 = first NI0 row fragments, b0 = first NJ0 column fragments).
-//   Geo<4,4,2,2>  256x256  the general tile (128 accumulator registers per lane, 128 KiB of LDS)
-//   Geo<5,4,2,1>  288x192  M = 4608 x N = 3072 is EXACTLY 256 of these (16 x 16): the single blocks' out-projection fills all 256
-//                          CUs in one round instead of 216 tiles of 256x256 on 256 CUs (84 %); 108 accumulator registers, 136 KiB
-//   Geo<4,4,2,1>  256x192  } narrower tiles for the TAIL of a multi-round launch (gemm_mix_kernel): the columns that would form a
-//   Geo<4,4,1,1>  256x128  } partly filled last round of 256x256 tiles are cut into 3/4- or 1/2-width tiles instead
-// The K order of every output element is the same in all of them, so results are bit-identical whatever tile computed them.
-template <int NI0_, int NI1_, int NJ0_, int NJ1_>
+// Tile geometry. 8 waves as 2(M) x 4(N); a wave's output is NI x NJ fragments of 16x16, consumed per K-tile in the four quadrants
+// (a0,b0) (a0,b1) (a1,b1) (a1,b0) of its "halves" (a0 = first NIH row fragments, b0 = first NJH column fragments).
+//   Geo<8,4>  256x256  the general tile (128 accumulator registers per lane, 128 KiB of LDS)
+//   Geo<8,2>  256x128  the convolution form for N <= 128 (the decoder's 1024x1024 stages): no dead columns
+// The K order of every output element is the same in both, so results do not depend on the tile that computed them.
+template <int NI_, int NJ_>
 struct Geo {
-  static constexpr int NI0 = NI0_, NI1 = NI1_, NJ0 = NJ0_, NJ1 = NJ1_;
-  static constexpr int NI = NI0 + NI1, NJ = NJ0 + NJ1;
-  static constexpr int NIH = NI0 > NI1 ? NI0 : NI1, NJH = NJ0 > NJ1 ? NJ0 : NJ1;
+  static constexpr int NI = NI_, NJ = NJ_;
+  static constexpr int NIH = NI / 2, NJH = NJ / 2;            // fragments per half
+  static_assert(NI == 2 * NIH && NJ == 2 * NJH, "the two halves of a wave's rows / columns are equal");
   static constexpr int WMR = 16 * NI, WNC = 16 * NJ;          // rows / columns per wave
   static constexpr int BM = 2 * WMR, BN = 4 * WNC;
   static constexpr int A_BYTES = BM * 128, W_BYTES = BN * 128;
-  // LDS-DMA pieces (8 rows x 128 B = 1 KiB, one wave-instruction) per wave and operand part; an a-half of 4*NIh pieces that does
-  // not divide by 8 waves is padded with dummy pieces (landing in a scratch region) so that every wave issues the same count
-  static constexpr int PA0 = (4 * NI0 + 7) / 8, PA1 = (4 * NI1 + 7) / 8, PB0 = NJ0, PB1 = NJ1;
-  static constexpr bool DUMMY = (4 * NI0) % 8 != 0 || (4 * NI1) % 8 != 0;
-  static constexpr int DUMMY_BYTES = DUMMY ? 8 * 1024 : 0;
-  static constexpr int BUF_BYTES = A_BYTES + W_BYTES + DUMMY_BYTES;
+  // LDS-DMA pieces (8 rows x 128 B = 1 KiB, one wave-instruction) per wave and operand half: an a-half is 4*NIH pieces, a b-half
+  // 8*NJH, dealt over the 8 waves
+  static_assert((4 * NIH) % 8 == 0, "every wave issues the same number of pieces of an a-half");
+  static constexpr int PA = 4 * NIH / 8, PB = NJH;
+  static constexpr int BUF_BYTES = A_BYTES + W_BYTES;
   static constexpr int LDS_BYTES = 2 * BUF_BYTES;             // double buffered
 };
-using Geo256 = Geo<4, 4, 2, 2>;
-using Geo288 = Geo<5, 4, 2, 1>;
-using Geo192 = Geo<4, 4, 2, 1>;
-using Geo128 = Geo<4, 4, 1, 1>;
-constexpr int LDS_MAX = Geo288::LDS_BYTES > Geo256::LDS_BYTES ? Geo288::LDS_BYTES : Geo256::LDS_BYTES;
+using Geo256 = Geo<8, 4>;
+using Geo128 = Geo<8, 2>;
 
 struct GroupDev {
   rt_gemm_group g;
   int tiles_m, tiles_n, tile_begin;
   int wide_store;      // bf16 output rows are 16-byte addressable in 8-column steps (C 16-B aligned, ldc/strideC/N % 8 == 0)
-  // gemm_mix_kernel only: columns [0, n_split) are cut into 256-wide tiles, [n_split, N) into narrow ones
-  int n_split, tiles_n_narrow, narrow_begin;
 };
 struct Launch {
   GroupDev grp[RT_GEMM_MAX_GROUPS];
   int ngroups;
-  int wide_total, narrow_total;      // gemm_mix_kernel: tiles of each kind over all groups
 };
 
 // Epilogue for one wave: NI x NJ accumulator fragments -> C. Lane owns rows mrow + 16i and, per fragment column j,
@@ -257,10 +245,10 @@ __device__ __forceinline__ void epilogue_tile(const rt_gemm_group& g, int bidx, 
 // ---------------------------------------------------------------------------------------------------
 // gemm_tile: one output tile, the ping-pong schedule.
 //   * a K-tile is consumed in 4 phases, one quadrant of the wave's output each, in the order (a0,b0) (a0,b1) (a1,b1) (a1,b0)
-//     so only (NI0+NJ0) + NJ1 + NI1 + 0 fragment reads (x2 k-steps) are needed per K-tile;
+//     so only (NIH+NJH) + NJH + NIH + 0 fragment reads (x2 k-steps) are needed per K-tile;
 //   * waves 4-7 run one barrier behind waves 0-3, so of the two waves that share a SIMD one is in its MFMA cluster
 //     while the other reads fragments / issues LDS-DMA: the matrix pipe always has a wave feeding it;
-//   * the operand parts a0,b0,b1,a1 of tile t+1 are issued (PA0, PB0, PB1, PA1 LDS-DMA pieces per wave) in phases 1..4 of tile t
+//   * the operand parts a0,b0,b1,a1 of tile t+1 are issued (PA, PB, PB, PA LDS-DMA pieces per wave) in phases 1..4 of tile t
 //     and consumed in the same order one tile later; they stay in flight ACROSS the barriers behind counted s_waitcnt vmcnt
 //     (never 0 in steady state). Each wait sits before the barrier that precedes the MFMA cluster, i.e. one barrier earlier
 //     than the first read of that data by EITHER wave group (the staggered group reads one barrier later), which is what orders
@@ -324,18 +312,19 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
   using T = G_;
   static_assert(!MX || FP8, "block scales belong to the e4m3 form");
   static_assert(!CONV || !FP8, "the convolution form is bf16");
+  static_assert(!FP8 || T::NIH <= 4, "the e4m3 MFMA rows of a quadrant are spelled out for up to four fragments");
   constexpr int ESZ = FP8 ? 1 : 2;                   // bytes per operand element
   constexpr int BKE = 128 / ESZ;                     // elements per K-tile
-  constexpr int NPC = T::PA0 + T::PB0 + T::PB1 + T::PA1;          // pieces per wave and K-tile
+  constexpr int NPC = 2 * (T::PA + T::PB);                        // pieces per wave and K-tile
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;
 
-  // ---- staging. LDS image: A tile rows in tile order (wave row wm at wm*WMR, its half 1 at +16*NI0), W tile rows likewise
-  //      (wave column wn at wn*WNC, half 1 at +16*NJ0), 128 B per row, 16-byte chunk c of row r at c ^ ((r>>1)&7).
-  //      Part a-half h = rows of BOTH wave rows' half h (4*NIh pieces of 8 rows), part b-half h = rows of all four wave columns'
-  //      half h (8*NJh pieces); wave w issues pieces w, w+8, ... of every part.
+  // ---- staging. LDS image: A tile rows in tile order (wave row wm at wm*WMR, its half 1 at +16*NIH), W tile rows likewise
+  //      (wave column wn at wn*WNC, half 1 at +16*NJH), 128 B per row, 16-byte chunk c of row r at c ^ ((r>>1)&7).
+  //      Part a-half h = rows of BOTH wave rows' half h (4*NIH pieces of 8 rows), part b-half h = rows of all four wave columns'
+  //      half h (8*NJH pieces); wave w issues pieces w, w+8, ... of every part.
   const char* Ab = reinterpret_cast<const char*>(g.A) + (int64_t)bidx * g.strideA * ESZ;
   const char* Wb = reinterpret_cast<const char*>(g.W);
   uint32_t src[NPC];      // byte offsets from Ab / Wb (both tensors are < 2^32 bytes; checked on the host)
@@ -343,25 +332,20 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
   {
     int k = 0;
     auto a_piece = [&](int half, int q) {
-      constexpr int dummy_base = T::A_BYTES + T::W_BYTES;
-      const int nih = half ? T::NI1 : T::NI0;
-      const int p = wave + 8 * q;
-      const bool real = p < 4 * nih;
-      const int pp = real ? p : p - 8 * ((p - 4 * nih) / 8 + 1);          // a dummy piece re-reads one of this wave's earlier pieces
-      const int wmp = pp / (2 * nih), within = pp - wmp * 2 * nih;
-      const int rowbase = wmp * T::WMR + (half ? 16 * T::NI0 : 0) + within * 8;
+      const int p = wave + 8 * q;                                           // < 4*NIH always
+      const int wmp = p / (2 * T::NIH), within = p - wmp * 2 * T::NIH;
+      const int rowbase = wmp * T::WMR + half * 16 * T::NIH + within * 8;
       const int row = rowbase + (lane >> 3);
       const int lc = (lane & 7) ^ ((row >> 1) & 7);
       const int am = min(m0 + row, g.M - 1);
       src[k] = (uint32_t)(((int64_t)am * g.lda) * ESZ + lc * 16);
-      lds_off[k] = real ? rowbase * 128 : dummy_base + wave * 1024;
+      lds_off[k] = rowbase * 128;
       ++k;
     };
     auto b_piece = [&](int half, int q) {
-      const int njh = half ? T::NJ1 : T::NJ0;
-      const int p = wave + 8 * q;                                           // < 8*njh always
-      const int wnp = p / (2 * njh), within = p - wnp * 2 * njh;
-      const int rowbase = wnp * T::WNC + (half ? 16 * T::NJ0 : 0) + within * 8;
+      const int p = wave + 8 * q;                                           // < 8*NJH always
+      const int wnp = p / (2 * T::NJH), within = p - wnp * 2 * T::NJH;
+      const int rowbase = wnp * T::WNC + half * 16 * T::NJH + within * 8;
       const int row = rowbase + (lane >> 3);
       const int lc = (lane & 7) ^ ((row >> 1) & 7);
       const int wr = min(n0 + row, g.N - 1);
@@ -370,13 +354,13 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
       ++k;
     };
 #pragma unroll
-    for (int q = 0; q < T::PA0; ++q) a_piece(0, q);
+    for (int q = 0; q < T::PA; ++q) a_piece(0, q);
 #pragma unroll
-    for (int q = 0; q < T::PB0; ++q) b_piece(0, q);
+    for (int q = 0; q < T::PB; ++q) b_piece(0, q);
 #pragma unroll
-    for (int q = 0; q < T::PB1; ++q) b_piece(1, q);
+    for (int q = 0; q < T::PB; ++q) b_piece(1, q);
 #pragma unroll
-    for (int q = 0; q < T::PA1; ++q) a_piece(1, q);
+    for (int q = 0; q < T::PA; ++q) a_piece(1, q);
   }
   // LDS-DMA by buffer_load ... lds: 4-SGPR descriptor per operand + the lane's invariant 32-bit byte offset + the K offset in an
   // SGPR — no per-K-tile vector address arithmetic and half the address registers of the global_load form.
@@ -405,8 +389,8 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
   };
   auto issue = [&](auto part_c, int buf, int koff) {                     // koff in BYTES along the row
     constexpr int part = decltype(part_c)::value;
-    constexpr int first = part == 0 ? 0 : part == 1 ? T::PA0 : part == 2 ? T::PA0 + T::PB0 : T::PA0 + T::PB0 + T::PB1;
-    constexpr int cnt = part == 0 ? T::PA0 : part == 1 ? T::PB0 : part == 2 ? T::PB1 : T::PA1;
+    constexpr int first = part == 0 ? 0 : part == 1 ? T::PA : part == 2 ? T::PA + T::PB : T::PA + 2 * T::PB;
+    constexpr int cnt = part == 0 || part == 3 ? T::PA : T::PB;
     constexpr bool isA = part == 0 || part == 3;
 #pragma unroll
     for (int q = 0; q < cnt; ++q)
@@ -423,7 +407,7 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
   uint32_t sc_lo = 0, sc_hi = 0;
   int sc_plane = 0, sc_src = 0;
   if constexpr (MX) {
-    static_assert(T::BM == 256 && T::NI0 == 4 && T::NI1 == 4, "the scale chunk order is that of the 256-row tile");
+    static_assert(T::BM == 256 && T::NIH == 4, "the scale chunk order is that of the 256-row tile");
     sc_lo = (uint32_t)reinterpret_cast<uintptr_t>(g.a_bscale);
     sc_hi = (uint32_t)(reinterpret_cast<uintptr_t>(g.a_bscale) >> 32);
     sc_plane = (int)g.a_bscale_plane;
@@ -461,40 +445,38 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
   bf16x8 wf[2][T::NJH][2];     // both b-halves: [half][frag][kk]
   int sc = 0x7F7F7F7F;         // MX: block scale bytes of the current a-half's four fragments (byte i = fragment i) for this K-tile
 
-#define RT_NIH(ah) ((ah) ? T::NI1 : T::NI0)
-#define RT_NJH(bh) ((bh) ? T::NJ1 : T::NJ0)
 #define RT_READ_A(ah)                                                                                             \
-  _Pragma("unroll") for (int i = 0; i < RT_NIH(ah); ++i) {                                                        \
-    af[i][0] = *reinterpret_cast<const bf16x8*>(tb + a_base + ((ah)*T::NI0 + i) * 2048 + rd0);                     \
-    af[i][1] = *reinterpret_cast<const bf16x8*>(tb + a_base + ((ah)*T::NI0 + i) * 2048 + rd1);                     \
+  _Pragma("unroll") for (int i = 0; i < T::NIH; ++i) {                                                            \
+    af[i][0] = *reinterpret_cast<const bf16x8*>(tb + a_base + ((ah)*T::NIH + i) * 2048 + rd0);                    \
+    af[i][1] = *reinterpret_cast<const bf16x8*>(tb + a_base + ((ah)*T::NIH + i) * 2048 + rd1);                    \
   }
 #define RT_READ_S(ah, kt_)                                                                                        \
   if constexpr (MX) sc = *reinterpret_cast<const int*>(smem + sc_rd + (((kt_) & 15) << 10) + (ah)*256);
 #define RT_READ_B(bh)                                                                                             \
-  _Pragma("unroll") for (int j = 0; j < RT_NJH(bh); ++j) {                                                        \
-    wf[bh][j][0] = *reinterpret_cast<const bf16x8*>(tb + w_base + ((bh)*T::NJ0 + j) * 2048 + rd0);                 \
-    wf[bh][j][1] = *reinterpret_cast<const bf16x8*>(tb + w_base + ((bh)*T::NJ0 + j) * 2048 + rd1);                 \
+  _Pragma("unroll") for (int j = 0; j < T::NJH; ++j) {                                                            \
+    wf[bh][j][0] = *reinterpret_cast<const bf16x8*>(tb + w_base + ((bh)*T::NJH + j) * 2048 + rd0);                \
+    wf[bh][j][1] = *reinterpret_cast<const bf16x8*>(tb + w_base + ((bh)*T::NJH + j) * 2048 + rd1);                \
   }
 #define RT_CAT8(lo, hi) __builtin_shufflevector(__builtin_bit_cast(i32x4, lo), __builtin_bit_cast(i32x4, hi), 0, 1, 2, 3, 4, 5, 6, 7)
 /* one fragment row i of the quadrant; i is a literal: the scale byte of fragment i is picked by the op_sel IMMEDIATE */ \
 #define RT_MFMA8_ROW(ah, bh, i)                                                                                   \
-  if constexpr ((i) < RT_NIH(ah)) {                                                                               \
-    _Pragma("unroll") for (int j = 0; j < RT_NJH(bh); ++j)                                                        \
-      acc[(ah)*T::NI0 + (i)][(bh)*T::NJ0 + j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(                 \
-          RT_CAT8(wf[bh][j][0], wf[bh][j][1]), RT_CAT8(af[i][0], af[i][1]), acc[(ah)*T::NI0 + (i)][(bh)*T::NJ0 + j], \
+  if constexpr ((i) < T::NIH) {                                                                                   \
+    _Pragma("unroll") for (int j = 0; j < T::NJH; ++j)                                                            \
+      acc[(ah)*T::NIH + (i)][(bh)*T::NJH + j] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(                 \
+          RT_CAT8(wf[bh][j][0], wf[bh][j][1]), RT_CAT8(af[i][0], af[i][1]), acc[(ah)*T::NIH + (i)][(bh)*T::NJH + j], \
           0 /* A: e4m3 */, 0 /* B: e4m3 */, 0, 0x7F7F7F7F /* weights: 2^0 */, MX ? ((i) & 3) : 0, MX ? sc : 0x7F7F7F7F); \
   }
 #define RT_MFMA(ah, bh)                                                                                           \
   do {                                                                                                            \
     __builtin_amdgcn_s_setprio(1);                                                                                \
     if constexpr (FP8) {                                                                                          \
-      RT_MFMA8_ROW(ah, bh, 0); RT_MFMA8_ROW(ah, bh, 1); RT_MFMA8_ROW(ah, bh, 2); RT_MFMA8_ROW(ah, bh, 3); RT_MFMA8_ROW(ah, bh, 4); \
+      RT_MFMA8_ROW(ah, bh, 0); RT_MFMA8_ROW(ah, bh, 1); RT_MFMA8_ROW(ah, bh, 2); RT_MFMA8_ROW(ah, bh, 3);         \
     } else {                                                                                                      \
       _Pragma("unroll") for (int kk = 0; kk < 2; ++kk)                                                            \
-        _Pragma("unroll") for (int i = 0; i < RT_NIH(ah); ++i)                                                    \
-          _Pragma("unroll") for (int j = 0; j < RT_NJH(bh); ++j)                                                  \
-            acc[(ah)*T::NI0 + i][(bh)*T::NJ0 + j] =                                                               \
-                __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[bh][j][kk], af[i][kk], acc[(ah)*T::NI0 + i][(bh)*T::NJ0 + j], 0, 0, 0); \
+        _Pragma("unroll") for (int i = 0; i < T::NIH; ++i)                                                        \
+          _Pragma("unroll") for (int j = 0; j < T::NJH; ++j)                                                      \
+            acc[(ah)*T::NIH + i][(bh)*T::NJH + j] =                                                               \
+                __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[bh][j][kk], af[i][kk], acc[(ah)*T::NIH + i][(bh)*T::NJH + j], 0, 0, 0); \
     }                                                                                                             \
     __builtin_amdgcn_s_setprio(0);                                                                                \
   } while (0)
@@ -502,7 +484,7 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
   const int nk = g.K / BKE;
   conv_at(0);
   issue(P0{}, 0, 0); issue_scales(0); issue(P1{}, 0, 0); issue(P2{}, 0, 0); issue(P3{}, 0, 0);
-  rt_vmcnt<T::PB1 + T::PA1>();                 // a0 (+ scales), b0 of tile 0 landed (younger: b1, a1)
+  rt_vmcnt<T::PB + T::PA>();                   // a0 (+ scales), b0 of tile 0 landed (younger: b1, a1)
   RT_BAR();
   if (wm == 1) RT_BAR();                       // stagger waves 4-7 by one barrier
 
@@ -520,12 +502,12 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
     RT_READ_A(0); RT_READ_S(0, kt); RT_READ_B(0);
     issue(P0{}, nb, koff);
     if constexpr (MX) { if ((kt & 7) == 7) issue_scales((kt + 1) >> 3); }
-    rt_vmcnt<T::PA1 + T::PA0>();               // b1(kt) landed (younger: a1(kt), a0(kt+1))
+    rt_vmcnt<2 * T::PA>();                     // b1(kt) landed (younger: a1(kt), a0(kt+1))
     RT_BAR(); RT_MFMA(0, 0); RT_BAR();
     // ---- phase 2: (a0,b1)
     RT_READ_B(1);
     issue(P1{}, nb, koff);
-    rt_vmcnt<T::PA0 + T::PB0>();               // a1(kt) landed (younger: a0(kt+1), b0(kt+1))
+    rt_vmcnt<T::PA + T::PB>();                 // a1(kt) landed (younger: a0(kt+1), b0(kt+1))
     RT_BAR(); RT_MFMA(0, 1); RT_BAR();
     // ---- phase 3: (a1,b1)
     RT_READ_A(1); RT_READ_S(1, kt);
@@ -533,7 +515,7 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
     RT_BAR(); RT_MFMA(1, 1); RT_BAR();
     // ---- phase 4: (a1,b0)  (b0 still in registers)
     issue(P3{}, nb, koff);
-    rt_vmcnt<T::PB1 + T::PA1>();               // a0(kt+1) (+ scales), b0(kt+1) landed (younger: b1(kt+1), a1(kt+1))
+    rt_vmcnt<T::PB + T::PA>();                 // a0(kt+1) (+ scales), b0(kt+1) landed (younger: b1(kt+1), a1(kt+1))
     RT_BAR(); RT_MFMA(1, 0); RT_BAR();
   }
   {                                            // last K-tile: nothing left to issue, drain
@@ -555,8 +537,6 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
 #undef RT_MFMA
 #undef RT_MFMA8_ROW
 #undef RT_CAT8
-#undef RT_NIH
-#undef RT_NJH
 
   const int mrow = m0 + wm * T::WMR + l15;
   const int ncol = n0 + wn * T::WNC + 4 * (lane >> 4);
@@ -565,12 +545,11 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
 }
 
 // XCD-aware placement (speed only, never correctness): workgroups are dealt round-robin over the 8 XCDs, so blocks b and b+8
-// share an L2. `xcd_run` gives XCD group x a CONTIGUOUS run of an n-item order (bijective for any n): item index of slot s.
+// share an L2. `xcd_run_start` gives XCD group x a CONTIGUOUS run of an n-item order (bijective for any n): item index of slot s.
 __device__ __forceinline__ int xcd_run_start(int n, int xcd) {
   const int q8 = n >> 3, r8 = n & 7;
   return xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8;
 }
-__device__ __forceinline__ int xcd_run_count(int n, int xcd) { return (n >> 3) + (xcd < (n & 7) ? 1 : 0); }
 
 // Walk one problem in panels of 8 tile-columns, row by row: the 32 tiles an XCD runs at a time form a ~4x8 patch that shares
 // 4 A row-panels and 8 W row-panels in that XCD's L2 instead of ~9 and ~14.
@@ -585,7 +564,7 @@ __device__ __forceinline__ void panel_walk(int t, int tiles_m, int tiles_n, int&
 
 typedef const __attribute__((address_space(4))) Launch* LaunchPtr;
 
-// One geometry for the whole launch (G_ = Geo256: every ordinary launch; Geo288: M x N a whole number of 288x192 tiles).
+// One geometry for the whole launch: Geo256, or Geo128 for the convolution form with N <= 128.
 template <bool FP8, class G_, bool MX = false, bool CONV = false>
 __global__ __launch_bounds__(THREADS, 2) void gemm_pp_kernel(const Launch L) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -612,64 +591,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_pp_kernel(const Launch L) {
   gemm_tile<FP8, G_, MX, CONV>(G.g, bidx, tm * G_::BM, tn * G_::BN, G.wide_store != 0, smem);
 }
 
-// Two geometries in one launch: the 256-wide tiles of every group first, then the narrow tiles (GN_) of the columns the host
-// left over (GroupDev::n_split). Every XCD group owns a contiguous run of the wide order AND a contiguous run of the narrow
-// order and walks the wide ones first, so all eight switch to the short tiles together and the last round is (nearly) full.
-template <class GN_>
-__global__ __launch_bounds__(THREADS, 2) void gemm_mix_kernel(const Launch L) {
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  LaunchPtr Lp = (LaunchPtr)__builtin_amdgcn_kernarg_segment_ptr();
-  (void)L;
-  const int xcd = (int)blockIdx.x & 7, slot = (int)blockIdx.x >> 3;
-  const int nW = Lp->wide_total, nN = Lp->narrow_total;
-  const int cW = xcd_run_count(nW, xcd), cN = xcd_run_count(nN, xcd);
-  if (slot >= cW + cN) return;
-  const bool narrow = slot >= cW;
-  const int lin = narrow ? xcd_run_start(nN, xcd) + (slot - cW) : xcd_run_start(nW, xcd) + slot;
-  int gi = 0;
-#pragma unroll
-  for (int i = 1; i < RT_GEMM_MAX_GROUPS; ++i)
-    if (i < Lp->ngroups && lin >= (narrow ? Lp->grp[i].narrow_begin : Lp->grp[i].tile_begin)) gi = i;
-#if defined(__HIP_DEVICE_COMPILE__)
-  const GroupDev G = Lp->grp[gi];
-#else
-  const GroupDev G = L.grp[0];
-#endif
-  int t = lin - (narrow ? G.narrow_begin : G.tile_begin);
-  const int tn_cnt = narrow ? G.tiles_n_narrow : G.tiles_n;
-  const int tiles_per_batch = G.tiles_m * tn_cnt;
-  const int bidx = t / tiles_per_batch;
-  t -= bidx * tiles_per_batch;
-  int tm, tn;
-  panel_walk(t, G.tiles_m, tn_cnt, tm, tn);
-  if (narrow) gemm_tile<false, GN_>(G.g, bidx, tm * GN_::BM, G.n_split + tn * GN_::BN, G.wide_store != 0, smem);
-  else gemm_tile<false, Geo256>(G.g, bidx, tm * Geo256::BM, tn * Geo256::BN, G.wide_store != 0, smem);
-}
-
-// ---- host side: which geometry? --------------------------------------------------------------------------------
-int g_num_cus = 0;
-int num_cus() {
-  if (g_num_cus == 0) {
-    int dev = 0, v = 0;
-    g_num_cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) g_num_cus = v;
-  }
-  return g_num_cus;
-}
-int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
-// bit 0: 288x192 launches, bit 1: narrow tail tiles; -1 = not read yet (RT_GEMM_TILES). Default 0: measured on MI355X the fuller last
-// round buys nothing — interleaved A/B at the model's shapes: 4608x3072x15360 on 256 tiles of 288x192 348 us vs 342 us on 216 tiles of
-// 256x256; q|k|v -1.6 %, ff1 -0.8 %; in the model 1210 vs 1213 TFLOP/s. The chip is power-limited: CUs left idle in a last round give
-// their share of the clock to the busy ones, and the narrower tiles re-read more operand bytes per FLOP.
-int g_tile_mode = -1;
-int tile_mode_now() {
-  if (g_tile_mode < 0) g_tile_mode = env_int("RT_GEMM_TILES", 0) & 3;
-  return g_tile_mode;
-}
-
+// ---- host side ---------------------------------------------------------------------------------------------------
 template <class K>
 int set_lds(K kern, int bytes) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
@@ -687,8 +609,6 @@ static int launch_gemm(const rt_gemm_group* groups, int32_t ngroups, void* strea
   const int bke = fp8 ? 128 : BK;                     // elements per K-tile
   const int al = fp8 ? 16 : 8;                        // elements per 16 bytes
   const int64_t esz = fp8 ? 1 : 2;
-  static const bool wide_on = env_int("RT_GEMM_WIDE_STORE", 1) != 0;   // A/B switches (tests and tools)
-  const int tile_mode = tile_mode_now();
   for (int i = 0; i < ngroups; ++i) {
     const rt_gemm_group& g = groups[i];
     if (!g.A || !g.W || !g.C || g.M < 1 || g.N < 1 || g.K < 1 || g.batch < 1) return RT_E_BADARG;
@@ -730,7 +650,7 @@ static int launch_gemm(const rt_gemm_group* groups, int32_t ngroups, void* strea
     L.grp[i].g = g;
     L.grp[i].tiles_m = (g.M + Geo256::BM - 1) / Geo256::BM;
     L.grp[i].tiles_n = (g.N + Geo256::BN - 1) / Geo256::BN;
-    L.grp[i].wide_store = (wide_on && !g.out_f32 && RT_ALIGNED(g.C, 16) && g.ldc % 8 == 0 && g.strideC % 8 == 0 && g.N % 8 == 0) ? 1 : 0;
+    L.grp[i].wide_store = (!g.out_f32 && RT_ALIGNED(g.C, 16) && g.ldc % 8 == 0 && g.strideC % 8 == 0 && g.N % 8 == 0) ? 1 : 0;
     L.grp[i].tile_begin = total;
     total += L.grp[i].tiles_m * L.grp[i].tiles_n * g.batch;
   }
@@ -739,11 +659,8 @@ static int launch_gemm(const rt_gemm_group* groups, int32_t ngroups, void* strea
     int e = set_lds(gemm_pp_kernel<false, Geo256>, Geo256::LDS_BYTES);
     if (!e) e = set_lds(gemm_pp_kernel<true, Geo256>, Geo256::LDS_BYTES);
     if (!e) e = set_lds(gemm_pp_kernel<true, Geo256, true>, Geo256::LDS_BYTES + 16384);
-    if (!e) e = set_lds(gemm_pp_kernel<false, Geo288>, Geo288::LDS_BYTES);
     if (!e) e = set_lds(gemm_pp_kernel<false, Geo256, false, true>, Geo256::LDS_BYTES);
     if (!e) e = set_lds(gemm_pp_kernel<false, Geo128, false, true>, Geo128::LDS_BYTES);
-    if (!e) e = set_lds(gemm_mix_kernel<Geo192>, Geo256::LDS_BYTES);
-    if (!e) e = set_lds(gemm_mix_kernel<Geo128>, Geo256::LDS_BYTES);
     if (e) return e;
     attr_done = true;
   }
@@ -764,85 +681,8 @@ static int launch_gemm(const rt_gemm_group* groups, int32_t ngroups, void* strea
     }
     return rt_hip_status();
   }
-  const int cus = num_cus();
-  // (1) 288x192 tiles: one problem whose M x N is a whole number of them and whose 256x256 tiling leaves the last round of
-  //     workgroups emptier. Cost model: rounds x tile area, the 288x192 tile charged 4 % for its lower operand reuse.
-  if ((tile_mode & 1) && ngroups == 1 && groups[0].M % Geo288::BM == 0 && groups[0].N % Geo288::BN == 0) {
-    const rt_gemm_group& g = groups[0];
-    const int t288 = (g.M / Geo288::BM) * (g.N / Geo288::BN) * g.batch;
-    const double c256 = (double)((total + cus - 1) / cus) * Geo256::BM * Geo256::BN;
-    const double c288 = (double)((t288 + cus - 1) / cus) * Geo288::BM * Geo288::BN * 1.04;
-    if (c288 < c256) {
-      L.grp[0].tiles_m = g.M / Geo288::BM;
-      L.grp[0].tiles_n = g.N / Geo288::BN;
-      hipLaunchKernelGGL((gemm_pp_kernel<false, Geo288>), dim3(t288), dim3(THREADS), Geo288::LDS_BYTES, st, L);
-      return rt_hip_status();
-    }
-  }
-  // (2) narrow tail: a launch of several rounds whose last round is poorly filled gives up the columns of that round to 3/4- or
-  //     1/2-width tiles (same row panels). Every group is cut at the same fraction of its columns (they share N in practice).
-  if ((tile_mode & 2) && total > cus) {
-    const int rounds = (total + cus - 1) / cus;
-    const double base = (double)rounds;                                    // time in units of one 256x256 round
-    int best_w = 0, best_cols = 0;
-    double best = base * 0.985;                                            // must beat the plain tiling by 1.5 %
-    for (int w : {192, 128}) {
-      const double unit = w / 256.0 * (w == 192 ? 1.03 : 1.08);            // a narrow tile's time in 256x256 tiles (less operand reuse)
-      // give up c column-tiles (of 256) of every group to the narrow geometry
-      int min_tn = 1 << 30;
-      for (int i = 0; i < ngroups; ++i) min_tn = L.grp[i].tiles_n < min_tn ? L.grp[i].tiles_n : min_tn;
-      for (int c = 1; c < min_tn; ++c) {
-        bool ok = true;
-        int wide = 0, narrow = 0;
-        for (int i = 0; i < ngroups; ++i) {
-          const rt_gemm_group& g = groups[i];
-          const int n_split = (L.grp[i].tiles_n - c) * 256;
-          if (g.N % 256 != 0 || (g.N - n_split) % w != 0) { ok = false; break; }
-          wide += L.grp[i].tiles_m * (L.grp[i].tiles_n - c) * g.batch;
-          narrow += L.grp[i].tiles_m * ((g.N - n_split) / w) * g.batch;
-        }
-        if (!ok) continue;
-        // wide tiles run first; narrow tiles fill the CUs as they free up: list scheduling bound
-        const double tw = (double)wide / cus, tn_ = (double)narrow / cus * unit;
-        const double t = ((wide + cus - 1) / cus) + (double)((narrow + cus - 1) / cus) * unit;
-        const double lb = tw + tn_;
-        const double est = lb + (t - lb) * 0.5;                             // between the perfect and the round-by-round bound
-        if (est < best) { best = est; best_w = w; best_cols = c; }
-      }
-    }
-    if (best_w) {
-      int wide = 0, narrow = 0;
-      for (int i = 0; i < ngroups; ++i) {
-        const rt_gemm_group& g = groups[i];
-        GroupDev& G = L.grp[i];
-        G.tiles_n -= best_cols;
-        G.n_split = G.tiles_n * 256;
-        G.tiles_n_narrow = (g.N - G.n_split) / best_w;
-        G.tile_begin = wide;
-        G.narrow_begin = narrow;
-        wide += G.tiles_m * G.tiles_n * g.batch;
-        narrow += G.tiles_m * G.tiles_n_narrow * g.batch;
-      }
-      L.wide_total = wide;
-      L.narrow_total = narrow;
-      int per_xcd = 0;
-      for (int x = 0; x < 8; ++x) {
-        const int c = (wide >> 3) + (x < (wide & 7)) + (narrow >> 3) + (x < (narrow & 7));
-        per_xcd = c > per_xcd ? c : per_xcd;
-      }
-      if (best_w == 192) hipLaunchKernelGGL((gemm_mix_kernel<Geo192>), dim3(8 * per_xcd), dim3(THREADS), Geo256::LDS_BYTES, st, L);
-      else hipLaunchKernelGGL((gemm_mix_kernel<Geo128>), dim3(8 * per_xcd), dim3(THREADS), Geo256::LDS_BYTES, st, L);
-      return rt_hip_status();
-    }
-  }
   hipLaunchKernelGGL((gemm_pp_kernel<false, Geo256>), dim3(total), dim3(THREADS), Geo256::LDS_BYTES, st, L);
   return rt_hip_status();
-}
-
-extern "C" int rt_gemm_tile_mode(int32_t mode) {
-  const int prev = tile_mode_now();
-  if (mode >= 0) g_tile_mode = mode & 3;
-  return prev;
 }
 
 extern "C" int rt_gemm_bf16(const rt_gemm_group* groups, int32_t ngroups, void* stream) {

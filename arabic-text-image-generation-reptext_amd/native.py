@@ -15,7 +15,7 @@ LIB_NAME = "librt_reptext_hip.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 RT_GEMM_MAX_GROUPS = 4
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -59,7 +59,6 @@ SIGNATURES = {
     "rt_abi_version": [],
     "rt_gemm_bf16": [C.POINTER(GemmGroup), _i32, _vp],
     "rt_gemm_fp8": [C.POINTER(GemmGroup), _i32, _vp],
-    "rt_gemm_tile_mode": [_i32],
     "rt_quantize_rows_fp8": [_vp, _i64, _i32, _vp, _i64, _vp, _i32, _i32, _vp],
     "rt_quantize_mx_fp8": [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _i32, _vp],
     "rt_layernorm_modulate_fp8": [_vp, _i64, _i64, _i32, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _f32, _vp],

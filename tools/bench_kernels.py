@@ -1,5 +1,5 @@
 """Kernel micro-benchmarks at the C2 shapes (1024², S=4608, d=3072). Run on the GPU box:
-    python tools/bench_kernels.py [gemm|attn|all]
+    python tools/bench_kernels.py [gemm|shapes|fp8|attn|attn8|elem|all]
 Prints TFLOP/s from torch.cuda.Event timing on the current stream (same stream the kernels are enqueued on)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -42,10 +42,8 @@ def bench_gemm():
     print(f"grouped qkv (4096+512)x9216x3072: {t*1e6:9.1f} us  {2*(T+Ni)*3*d*d/t/1e12:8.1f} TF/s", flush=True)
 
 
-def bench_gemm_tiles():
-    """Interleaved A/B of rt_gemm_bf16's tile modes (0 = 256x256 only, 3 = 288x192 + narrow tails) on the model's launches."""
-    from reptext_amd import native
-    lib = native.load()
+def bench_gemm_shapes():
+    """rt_gemm_bf16 on the model's launches (single- and double-block projections with their epilogues), best of 3 x 10 calls."""
     T, Ni, d = 512, 4096, 3072
     x = torch.randn(T + Ni, 4 * d, device=dev).to(torch.bfloat16)
     x32 = torch.randn(T + Ni, d, device=dev)
@@ -61,23 +59,15 @@ def bench_gemm_tiles():
         wi = (torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16)
         wt = (torch.randn(N, K, device=dev) * 0.02).to(torch.bfloat16)
         o = x32 if f32 else torch.empty(T + Ni, N, device=dev, dtype=torch.bfloat16)
-        kw = dict(res=None)
         def run(wi=wi, wt=wt, o=o, K=K, f32=f32):
             if f32:
                 ops.linear_grouped([ops.LinearProblem(x[T:, :K], wi, o[T:], gate=gate, res=o[T:]), ops.LinearProblem(x[:T, :K], wt, o[:T], gate=gate, res=o[:T])])
             else:
                 ops.linear_grouped([ops.LinearProblem(x[T:, :K], wi, o[T:]), ops.LinearProblem(x[:T, :K], wt, o[:T])])
         launches.append((f"double {name} (4096+512)x{N}x{K}", 2 * (T + Ni) * N * K, run))
-    prev = lib.rt_gemm_tile_mode(-1)
     for name, fl, run in launches:
-        res = {}
-        for rnd in range(3):
-            for mode in (0, 3):
-                lib.rt_gemm_tile_mode(mode)
-                res.setdefault(mode, []).append(timeit(run, iters=10, warm=2))
-        t0, t3 = min(res[0]), min(res[3])
-        print(f"{name:42s} mode0 {t0*1e6:7.1f} us {fl/t0/1e12:7.1f} TF/s | mode3 {t3*1e6:7.1f} us {fl/t3/1e12:7.1f} TF/s | {100*(t3/t0-1):+.1f} %", flush=True)
-    lib.rt_gemm_tile_mode(prev)
+        t = min(timeit(run, iters=10, warm=2) for _ in range(3))
+        print(f"{name:42s} {t*1e6:7.1f} us {fl/t/1e12:7.1f} TF/s", flush=True)
 
 
 def bench_gemm_fp8():
@@ -159,8 +149,8 @@ if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     if what in ("gemm", "all"):
         bench_gemm()
-    if what in ("tiles", "all"):
-        bench_gemm_tiles()
+    if what in ("shapes", "all"):
+        bench_gemm_shapes()
     if what in ("fp8", "all"):
         bench_gemm_fp8()
     if what in ("attn", "all"):
