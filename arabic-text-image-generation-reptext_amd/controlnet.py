@@ -119,6 +119,12 @@ class FluxControlNetModel(_MMDiTBase):
             self._cx_pad = wpad
         return torch.nn.functional.pad(cond, (0, kp - kin)), self._cx_pad
 
+    def _lora_unsupported(self, path: str, lin):
+        why = super()._lora_unsupported(path, lin)
+        if why is None and lin is self.controlnet_x_embedder and lin.in_features % 64:
+            why = f"in-features {lin.in_features} are not a multiple of 64: the K-padded copy of _padded_hint would go stale"
+        return why
+
     def _invalidate_derived(self):
         self._cx_pad = None
 
@@ -146,8 +152,8 @@ class FluxControlNetModel(_MMDiTBase):
                 _accumulate_single_into: Optional[Sequence[torch.Tensor]] = None, _mods: Optional["mmdit.StepMods"] = None,
                 _overwrite: bool = False, _sample_events: Optional[Sequence["torch.cuda.Event"]] = None, _ws_tag: str = "",
                 _static: Optional[StaticEmbeds] = None, _blocks_needed: Optional[Tuple[int, int]] = None):
-        """Same contract as CN:216-413. ``joint_attention_kwargs`` is accepted and ignored (LoRA scale plumbing, no
-        PEFT on this path). The private ``_rowscale`` / ``_accumulate_into`` arguments let the pipeline fuse its
+        """Same contract as CN:216-413. ``joint_attention_kwargs["scale"]`` scales this call's LoRA adapters (CN:263-276; merged into
+        the weights, lora.py). The private ``_rowscale`` / ``_accumulate_into`` arguments let the pipeline fuse its
         regional mask (PIPE:1062) and the sum over text lines (PIPE:1076-1080) into the zero-linear epilogues; with
         ``_overwrite`` the ``_accumulate_into`` buffers are written, not added to (first text line into preallocated
         buffers). ``_sample_events[i]`` is recorded on the current stream once double-block sample i is complete and
@@ -157,6 +163,7 @@ class FluxControlNetModel(_MMDiTBase):
         the rest come back as None (the pipeline knows which samples the transformer consumes: with 6 samples against 19
         blocks the sixth is never read, quirk Q5)."""
         doubles, singles = self._ensure_plans()
+        self._apply_lora_scale(joint_attention_kwargs)
         cfg = self.config
         if self.union:
             # CN:294-301. RepText weights have num_mode=None; kept as an explicit error path rather than a silent skip.

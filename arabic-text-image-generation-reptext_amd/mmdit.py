@@ -174,6 +174,11 @@ def plan_single(blk, fp8=False, fp8_attention: bool = False) -> SinglePlan:
     return pl
 
 
+def fp8_copies(pl) -> list:
+    """(bf16 weight, e4m3 copy, per-row scales) of every projection of a plan that has an e4m3 copy (enable_fp8_linears)."""
+    names = ("qkv_img", "qkv_txt", "ff1_img", "ff1_txt", "out_img", "out_txt", "ff2_img", "ff2_txt") if isinstance(pl, DoublePlan) else ("fused", "out")
+    return [(getattr(pl, n + "_w"), getattr(pl, n + "_w8"), getattr(pl, n + "_ws")) for n in names if getattr(pl, n + "_w8") is not None]
+
 class Workspace:
     """Preallocated activations for one (B,T,N) shape; reused across blocks, steps and models on the same device."""
 

@@ -15,7 +15,8 @@ LIB_NAME = "librt_reptext_hip.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 RT_GEMM_MAX_GROUPS = 4
-ABI_VERSION = 9
+ABI_VERSION = 10
+RT_LORA_MAX_TERMS = 8
 
 
 class NativeLibraryMissing(RuntimeError):
@@ -50,6 +51,12 @@ class GemmGroup(C.Structure):
         ("conv_ks", C.c_int32), ("conv_cin", C.c_int32), ("conv_w2", C.c_int32), ("conv_h2", C.c_int32),
         ("conv_inv_w2", C.c_float), ("conv_inv_h2", C.c_float),
     ]
+
+
+class LoraTerm(C.Structure):
+    """Mirror of ``rt_lora_term`` (include/reptext_hip.h): one adapter term of rt_lora_merge_bf16."""
+
+    _fields_ = [("B", C.c_void_p), ("At", C.c_void_p), ("ldb", C.c_int64), ("lda", C.c_int64), ("r_pad", C.c_int32), ("scale", C.c_float)]
 
 
 _i32, _i64, _f32, _vp = C.c_int32, C.c_int64, C.c_float, C.c_void_p
@@ -111,6 +118,9 @@ SIGNATURES.update({
     "rt_canny_u8": [_vp, _i32, _i32, _i32, _f32, _f32, _vp, _i32, _i32, _vp, _i64, _vp],
     "rt_preprocess_u8": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
 })
+
+# LoRA weight merge (csrc/lora.hip)
+SIGNATURES["rt_lora_merge_bf16"] = [C.POINTER(LoraTerm), _i32, _vp, _i64, _vp, _i64, _i32, _i32, _vp]
 
 # entries that do not return a status code
 RESTYPES = {"rt_canny_ws_bytes": C.c_int64, "rt_groupnorm_ws_bytes": C.c_int64, "rt_attention_fp8_vt_bytes": C.c_int64, "rt_attention_ws_bytes": C.c_int64}

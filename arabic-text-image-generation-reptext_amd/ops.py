@@ -378,6 +378,32 @@ def dequantize_mx(q: torch.Tensor, scales: BlockScales) -> torch.Tensor:
     return (q.to(torch.float32).view(B, R, D // 32, 32) * torch.exp2(e).unsqueeze(-1)).view(B, R, D)
 
 
+def lora_merge_(w: torch.Tensor, w0: torch.Tensor, terms: Sequence[tuple]) -> torch.Tensor:
+    """w = bf16(w0 + Σ c·B·A) (rt_lora_merge_bf16): ``terms`` = (B [N, r_pad] bf16, At [K, r_pad] bf16, c) with the r columns
+    zero-padded to a multiple of 32 and A stored transposed. w / w0 [N, K] bf16 views with unit inner stride (rows of a fused
+    weight are fine); w may be w0. No terms: w0 is copied bit for bit. One launch on the current stream."""
+    N, K, ldw = _rowmajor2d(w, "w")
+    N0, K0, ld0 = _rowmajor2d(w0, "w0")
+    if (N0, K0) != (N, K):
+        raise ValueError(f"lora_merge_: w {tuple(w.shape)} and w0 {tuple(w0.shape)} differ")
+    if len(terms) > native.RT_LORA_MAX_TERMS:
+        raise ValueError(f"lora_merge_: at most {native.RT_LORA_MAX_TERMS} terms per weight, got {len(terms)}")
+    if K % 8 or ldw % 8 or ld0 % 8:
+        raise ValueError("lora_merge_: K and the row strides must be multiples of 8")
+    pw, p0 = _dev(w, "w", BF16), _dev(w0, "w0", BF16)
+    arr = (native.LoraTerm * max(1, len(terms)))()
+    for t, (b, at, c) in enumerate(terms):
+        rb, r_pad, ldb = _rowmajor2d(b, "B")
+        ka, ra, lda = _rowmajor2d(at, "At")
+        if rb != N or ka != K or ra != r_pad or r_pad % 32:
+            raise ValueError(f"lora_merge_: term {t}: B {tuple(b.shape)} / At {tuple(at.shape)} do not fit w [{N}, {K}] with r_pad % 32 == 0")
+        if b.device != w.device or at.device != w.device:
+            raise RuntimeError("lora_merge_: factors and weight must be on the same device")
+        arr[t] = native.LoraTerm(_dev(b, "B", BF16), _dev(at, "At", BF16), ldb, lda, r_pad, float(c))
+    native.check("rt_lora_merge_bf16", native.load().rt_lora_merge_bf16(arr, len(terms), p0, ld0, pw, ldw, N, K, _stream()))
+    return w
+
+
 def qk_rmsnorm_rope(buf: torch.Tensor, q_off: int, k_off: int, H: int, T: int, wq_txt, wk_txt, wq_img, wk_img,
                     cos: torch.Tensor, sin: torch.Tensor, eps: float = 1e-6) -> None:
     """In place on buf [B,S,ld] bf16: heads at columns q_off + h*128 / k_off + h*128."""

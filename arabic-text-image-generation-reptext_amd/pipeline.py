@@ -444,6 +444,58 @@ class FluxControlNetPipeline:
         return isinstance(t, torch.Tensor) and t.dim() == 3 and isinstance(cn, FluxControlNetModel) and \
             t.shape[-1] == cn.controlnet_x_embedder.weight.shape[1]
 
+    # ------------------------------------------------------------------ LoRA: the FluxLoraLoaderMixin subset (PIPE:15,163), routed to
+    # the transformer; adapters are merged into the bf16 weights on the device (lora.py), so the loop and its graph are unchanged
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, adapter_name: Optional[str] = None, weight_name: Optional[str] = None,
+                          **kwargs):
+        self.transformer.load_lora_adapter(pretrained_model_name_or_path_or_dict, adapter_name=adapter_name, weight_name=weight_name,
+                                           prefix="transformer")
+
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        self.transformer.set_adapters(adapter_names, adapter_weights)
+
+    def get_active_adapters(self) -> List[str]:
+        return self.transformer.active_adapters()
+
+    def get_list_adapters(self) -> Dict[str, List[str]]:
+        m = getattr(self.transformer, "_lora", None)
+        return {} if m is None or not m.state.adapters else {"transformer": sorted(m.state.adapters)}
+
+    def fuse_lora(self, lora_scale: float = 1.0, adapter_names=None, **kwargs):
+        self.transformer.fuse_lora(lora_scale, adapter_names)
+
+    def unfuse_lora(self, **kwargs):
+        self.transformer.unfuse_lora()
+
+    def unload_lora_weights(self):
+        self.transformer.unload_lora()
+
+    def delete_adapters(self, adapter_names):
+        self.transformer.delete_adapters(adapter_names)
+
+    def enable_lora(self):
+        self.transformer.enable_adapters()
+
+    def disable_lora(self):
+        self.transformer.disable_adapters()
+
+    def _lora_models(self) -> list:
+        cn = self.controlnet
+        nets = list(cn.nets) if isinstance(cn, FluxMultiControlNetModel) else [cn]
+        models = [self.transformer] + nets + [getattr(self, "controlnet_inpaint", None)]
+        return [m for m in models if m is not None and getattr(m, "_lora", None) is not None]
+
+    def _apply_lora_scale(self) -> None:
+        """PIPE:908-925: the call's joint_attention_kwargs["scale"] merged into every model that carries adapters, before the loop
+        and on the current stream (the tower's side stream waits on it). The models' own per-call check then finds nothing to do."""
+        for m in self._lora_models():
+            m._apply_lora_scale(self.joint_attention_kwargs)
+
+    def _graph_safe_kwargs(self) -> bool:
+        """No joint_attention_kwargs, or only a LoRA "scale" while adapters are loaded: that one is in the weights already."""
+        kw = self.joint_attention_kwargs
+        return kw is None or (set(kw) == {"scale"} and bool(self._lora_models()))
+
     # ------------------------------------------------------------------ the call
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
@@ -513,6 +565,7 @@ class FluxControlNetPipeline:
         self._num_timesteps = len(timesteps)
         masks = self._region_masks(control_mask, latents.device, latents.dtype)
 
+        self._apply_lora_scale()
         latents = self._denoise(latents, prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids, timesteps, hints, masks,
                                 guidance_scale, controlnet_conditioning_scale, controlnet_conditioning_step, control_mode,
                                 callback_on_step_end, callback_on_step_end_tensor_inputs, num_inference_steps)
@@ -556,7 +609,7 @@ class FluxControlNetPipeline:
         tvals = timesteps.to(torch.float32).cpu().tolist()                 # host copies: no per-step device sync
         use_graph = (GRAPH_CAPTURE and getattr(self, "capture_graphs", True) and callback is None and latents.is_cuda
                      and not self.interrupt and isinstance(self.controlnet, (FluxControlNetModel, type(None)))
-                     and (control_mode is None) and self.joint_attention_kwargs is None)
+                     and (control_mode is None) and self._graph_safe_kwargs())
         if not use_graph:
             return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
                                        cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps)

@@ -198,6 +198,7 @@ class FluxControlNetPipeline(_BasePipeline):
         self._num_timesteps = len(timesteps)
         masks = self._region_masks(control_mask, latents.device, latents.dtype)
 
+        self._apply_lora_scale()
         latents = self._denoise_inpaint(latents, pe, pooled, text_ids, image_ids, timesteps, hints, masks, hint_inp, guidance_scale,
                                         true_guidance_scale, cfg, controlnet_conditioning_scale, controlnet_conditioning_scale_inpaint,
                                         controlnet_conditioning_step, control_mode, callback_on_step_end,

@@ -12,7 +12,7 @@ from typing import Sequence, Any, Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from . import mmdit, ops
+from . import lora, mmdit, ops
 from .config import Config, flux_dev_transformer_config
 from .modules import DoubleBlockParams, Lin, SingleBlockParams, TimeTextEmbedParams, WeightsIO, _ada
 from .ops import LinearProblem as P
@@ -93,7 +93,10 @@ class _MMDiTBase(nn.Module, WeightsIO):
 
     def _apply(self, fn, *a, **k):
         self._plans = None
-        return super()._apply(fn, *a, **k)
+        out = super()._apply(fn, *a, **k)
+        if getattr(self, "_lora", None) is not None:
+            self._lora.to_device(self.device)          # factors and W0 copies follow the weights
+        return out
 
     def enable_fp8_attention(self, on: bool = True):
         """BASELINE config 5 ("CDNA4 fp8 MFMA attention"): joint attention with e4m3 q, k, v and softmax numerators
@@ -119,10 +122,119 @@ class _MMDiTBase(nn.Module, WeightsIO):
         return self
 
     def load_state_dict(self, sd, strict: bool = True, **kw):
+        if getattr(self, "_lora", None) is not None:
+            raise RuntimeError(f"{type(self).__name__}.load_state_dict: LoRA adapters are merged into the weights; unload_lora() first")
         out = super().load_state_dict(sd, strict=strict, **kw)
         if getattr(self, "_fp8_linears", False):
             self._plans = None          # the e4m3 copies of the weights are stale
         return out
+
+    # ---- LoRA adapters: the PeftAdapterMixin subset (CN:22,41), merged into the bf16 weights on the device (lora.py)
+    def _fp8_rows(self) -> Dict[str, tuple]:
+        """{module path: (bf16 plan weight, e4m3 copy, row scales, r0, r1)} for every Linear whose weight is rows r0:r1 of a plan tensor
+        with an e4m3 copy (enable_fp8_linears); built once per plan build."""
+        plans = self._ensure_plans()
+        cache = getattr(self, "_fp8_rows_cache", None)
+        if cache is not None and cache[0] is plans:
+            return cache[1]
+        by_storage = {}
+        for pl in list(plans[0]) + list(plans[1]):
+            for full, w8, ws in mmdit.fp8_copies(pl):
+                by_storage[full.untyped_storage().data_ptr()] = (full, w8, ws)
+        rows = {}
+        for name, mod in self.named_modules():
+            hit = by_storage.get(mod.weight.data.untyped_storage().data_ptr()) if isinstance(mod, Lin) else None
+            if hit is None:
+                continue
+            full, w8, ws = hit
+            w = mod.weight.data
+            r0, rem = divmod(w.data_ptr() - full.data_ptr(), full.stride(0) * full.element_size())
+            r1 = r0 + w.shape[0]
+            if rem or r0 < 0 or r1 > full.shape[0] or w.shape[1] != full.shape[1] or w.stride() != full.stride():
+                raise RuntimeError(f"{name}: weight is not a row range of its fp8 plan tensor")
+            rows[name] = (full, w8, ws, r0, r1)
+        self._fp8_rows_cache = (plans, rows)
+        return rows
+
+    def _lora_unsupported(self, path: str, lin) -> Optional[str]:
+        """Why a LoRA may not target this Linear (None: it may)."""
+        if lin.in_features % 8:
+            return f"in-features {lin.in_features} are not a multiple of 8"
+        return None
+
+    def state_dict(self, *args, **kwargs):
+        """The weights at call scale 1.0: a call with joint_attention_kwargs={"scale": s} leaves the adapters merged at s until the
+        next call or adapter change (lora.py), so a save between calls re-merges at 1.0 first."""
+        if getattr(self, "_lora", None) is not None:
+            self._lora.sync(1.0)
+        return super().state_dict(*args, **kwargs)
+
+    def _lora_manager(self) -> "lora.LoraManager":
+        if getattr(self, "_lora", None) is None:
+            raise ValueError(f"{type(self).__name__}: no LoRA adapter is loaded")
+        return self._lora
+
+    def load_lora_adapter(self, pretrained_model_name_or_path_or_dict, adapter_name: Optional[str] = None,
+                          weight_name: Optional[str] = None, prefix: str = "transformer", **unused):
+        """Read a diffusers/PEFT LoRA (dict, .safetensors file, directory or cached hub id), make it the only active adapter at
+        weight 1.0 and merge it. ``adapter_name`` defaults to ``default_<n>``."""
+        from . import lora
+
+        sd, meta = lora.read_lora_file(pretrained_model_name_or_path_or_dict, weight_name)
+        parsed = lora.parse_lora_state_dict(sd, meta, prefix)
+        m = getattr(self, "_lora", None) or lora.LoraManager(self)
+        m.load(adapter_name or f"default_{len(m.state.adapters)}", parsed)
+        self._lora = m
+        m.sync()
+        return self
+
+    def set_adapters(self, adapter_names, weights=None):
+        m = self._lora_manager()
+        m.state.set_adapters(adapter_names, weights)
+        m.sync()
+
+    def fuse_lora(self, lora_scale: float = 1.0, adapter_names=None, **unused):
+        m = self._lora_manager()
+        m.state.fuse(lora_scale, adapter_names)
+        m.sync()
+
+    def unfuse_lora(self):
+        if getattr(self, "_lora", None) is not None:
+            self._lora.state.unfuse()
+            self._lora.sync()
+
+    def unload_lora(self):
+        """Drop every adapter. Unfused ones leave the weights (bit for bit the pre-LoRA weights when nothing is fused); fused ones stay
+        baked in, as diffusers' fuse_lora() + unload_lora_weights() recipe expects. Factors and W0 copies are freed."""
+        if getattr(self, "_lora", None) is not None:
+            self._lora.unload()
+            self._lora = None
+
+    def delete_adapters(self, adapter_names):
+        m = self._lora_manager()
+        m.state.delete(adapter_names)
+        m.sync()
+
+    def disable_adapters(self):
+        m = self._lora_manager()
+        m.state.set_enabled(False)
+        m.sync()
+
+    def enable_adapters(self):
+        m = self._lora_manager()
+        m.state.set_enabled(True)
+        m.sync()
+
+    def active_adapters(self) -> List[str]:
+        m = getattr(self, "_lora", None)
+        return [] if m is None else [a for a, _ in m.state.active]
+
+    def _apply_lora_scale(self, joint_attention_kwargs: Optional[Dict[str, Any]]) -> None:
+        """CN:263-276: the call's LoRA scale (joint_attention_kwargs["scale"], 1.0 without one) merged before the call; nothing is
+        launched when the weights already hold that state (e.g. inside the pipeline's loop, which applies it once up front)."""
+        if getattr(self, "_lora", None) is not None:
+            s = float((joint_attention_kwargs or {}).get("scale", 1.0))
+            self._lora.sync(s)
 
     def _rope(self, txt_ids: torch.Tensor, img_ids: torch.Tensor):
         """cos/sin [S,128] fp32; constant over the denoising loop, so cached on the id tensors' identity."""
@@ -223,6 +335,7 @@ class FluxTransformer2DModel(_MMDiTBase):
         current stream waits for it right before the first block that consumes that sample. ``_static`` (optional): this
         model's loop-invariant embeddings (prepare_static) — the text rows are copied instead of recomputed."""
         doubles, singles = self._ensure_plans()
+        self._apply_lora_scale(joint_attention_kwargs)
         cfg = self.config
         B, N, _ = hidden_states.shape
         Bc = encoder_hidden_states.shape[0]       # conditioning batch may be a multiple of B (inpaint CFG, Q6)

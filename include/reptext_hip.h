@@ -222,6 +222,27 @@ int rt_attention_fp8_fwd_mx(const void* qk8, const void* vt8, void* o8, int64_t 
                             void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * LoRA adapters merged into the bf16 weights (ABI 10; csrc/lora.hip). The reference's pipeline is a FluxLoraLoaderMixin
+ * (PIPE:15,163) and scales the adapters per call from joint_attention_kwargs["scale"] (PIPE:908-925, CN:263-276); here the
+ * adapters are folded into the Linear weights in place, outside the denoising loop, from a kept pristine copy W0, so the loop
+ * (and a captured graph of it) runs the unchanged GEMMs on the same buffers. Bound by memory: W0 is read and W written once.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct rt_lora_term {
+  const void* B;    /* bf16 [N][ldb]: lora_B rows, r columns zero-padded to a multiple of 32 */
+  const void* At;   /* bf16 [K][lda]: lora_A TRANSPOSED, same padding */
+  int64_t ldb, lda;
+  int32_t r_pad;    /* % 32 == 0, >= 32 */
+  float scale;      /* fp32 coefficient c (adapter weight x call scale x alpha/r) */
+} rt_lora_term;
+#define RT_LORA_MAX_TERMS 8
+/* W[n][k] = bf16( W0[n][k] + sum_t scale_t * sum_j B_t[n][j] * At_t[k][j] ), fp32 accumulation, ONE rounding.
+ * nterms == 0 copies W0 to W bit for bit. W may alias W0. K % 8 == 0, N >= 1, 16-byte aligned rows.
+ * Rejected on the host: null pointers (RT_E_BADARG), nterms > RT_LORA_MAX_TERMS, r_pad % 32 or K % 8 (RT_E_SHAPE), W0 / W / B / At
+ * not 16-byte aligned or a leading dimension not a multiple of 8 (RT_E_ALIGN); ld0 / ldw < K, ldb / lda < r_pad (RT_E_BADARG). */
+int rt_lora_merge_bf16(const rt_lora_term* terms /* host */, int32_t nterms, const void* W0, int64_t ld0,
+                       void* W, int64_t ldw, int32_t N, int32_t K, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Prompt encoders (PIPE:232-347: T5-XXL encoder -> prompt_embeds [B,512,4096], CLIP-L text model ->
  * pooled_prompt_embeds [B,768]). Once per prompt, outside the loop. Matrix work is rt_gemm_bf16; attention (head dim 64)
  * is assembled per head from rt_gemm_bf16 / rt_softmax_rows_bias / rt_transpose_bf16 / rt_gemm_bf16.

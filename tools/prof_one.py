@@ -1,4 +1,5 @@
-"""Run ONE kernel family a few times (for rocprofv3 --pmc passes): python tools/prof_one.py attn|gemm|attn8|gemm8"""
+"""Run ONE kernel family a few times (for rocprofv3 --pmc passes): python tools/prof_one.py attn|gemm|attn8|gemm8|lora<K>
+(lora3072 / lora15360: rt_lora_merge_bf16 of a 3072 x K weight, rank 64, out of place)"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -35,6 +36,14 @@ elif what == "attn8":
     out = torch.empty(B, S, d, device=dev, dtype=torch.bfloat16)
     for _ in range(5):
         ops.attention_fp8(qk8, vt8, out, H)
+elif what.startswith("lora"):
+    N, K, r = 3072, int(what[4:]), 64
+    w0 = torch.randn(N, K, device=dev).to(torch.bfloat16)
+    w = torch.empty_like(w0)
+    B = (torch.randn(N, r, device=dev) * 0.02).to(torch.bfloat16)
+    At = (torch.randn(K, r, device=dev) * 0.02).to(torch.bfloat16)
+    for _ in range(5):
+        ops.lora_merge_(w, w0, [(B, At, 0.5)])
 else:
     M, N, K = 4608, 21504, 3072
     a = torch.randn(M, K, device=dev).to(torch.bfloat16)
