@@ -1,0 +1,234 @@
+"""FLUX IP-Adapter (image prompt) for the transformer's double blocks: checkpoint reader, adapter state, loop-invariant set-up.
+
+With C = joint_attention_dim, d = inner_dim, H heads of 128, E = image embedding width, n = tokens per image prompt:
+
+  1. tok  = LayerNorm_C(reshape(Linear_{E -> n·C}(embeds), [B, n, C]))      affine, eps 1e-5             once per call
+  2. K_i  = to_k_ip_i(tok), V_i = to_v_ip_i(tok)   Linear_{C -> d} + bias, no norm, no RoPE               once per call
+  3. ip_i = s_i · softmax(q_i K_iᵀ / √128) V_i     q_i = the block's image query after norm_q, before RoPE  per step (rt_ip_attention)
+  4. h   <- h + ip_i  after the block's feed-forward residual (image stream only; no to_out, no gate)
+
+Rules recalled from diffusers (FluxIPAdapterMixin, FluxIPAdapterJointAttnProcessor2_0, ImageProjection, FluxTransformerBlock) and the
+XLabs-AI checkpoint layout; parity with them is unpinned (nothing can be checked offline). Single adapter, single image per sample.
+
+The adapter is held on the transformer as ``_ip_adapter`` — plain tensors, NOT registered parameters: ``state_dict()``,
+``load_state_dict(strict=True)`` and ``save_pretrained()`` are unchanged; ``_apply`` moves it with the model.
+
+Two key layouts, one table each (``_LAYOUTS``):
+  diffusers  image_proj.proj.* / image_proj.norm.* / ip_adapter.{i}.to_k_ip.* / ip_adapter.{i}.to_v_ip.*
+  XLabs      ip_adapter_proj_model.proj.* / .norm.* / double_blocks.{i}.processor.ip_adapter_double_stream_k_proj.* / _v_proj.*
+Refused with a ValueError naming the key: unknown keys, keys of single blocks (the InstantX layout), a block count other than
+num_layers, norm width != C, K/V out-features != d or in-features != C, a non-integer or > 128 token count, missing biases.
+"""
+from __future__ import annotations
+
+import itertools
+import os
+import re
+from dataclasses import dataclass
+from typing import Dict, List, Optional, Sequence, Tuple, Union
+
+import torch
+
+from . import ops
+
+_VERSIONS = itertools.count(1)     # IPAdapter.version: one number per set of device tensors (a captured graph holds their pointers)
+MAX_TOKENS = 128                   # rt_ip_attention: 1 <= n_ip <= 128
+DEFAULT_WEIGHT_NAME = "ip_adapter.safetensors"
+
+# layout name -> (projection prefix, norm prefix, regex of a block key -> (block index, "k" | "v", "weight" | "bias"))
+_LAYOUTS = {
+    "diffusers": ("image_proj.proj", "image_proj.norm", re.compile(r"^ip_adapter\.(\d+)\.to_(k|v)_ip\.(weight|bias)$")),
+    "xlabs": ("ip_adapter_proj_model.proj", "ip_adapter_proj_model.norm",
+              re.compile(r"^double_blocks\.(\d+)\.processor\.ip_adapter_double_stream_(k|v)_proj\.(weight|bias)$")),
+}
+_SINGLE_BLOCK_KEYS = re.compile(r"(^|\.)single_(transformer_)?blocks\.|ip_adapter_single_stream")
+
+
+@dataclass
+class IPAdapterWeights:
+    """Parsed checkpoint: tensors as stored in the file (any float dtype), one entry per double block."""
+
+    proj_w: torch.Tensor            # [n·C, E]
+    proj_b: torch.Tensor            # [n·C]
+    norm_w: torch.Tensor            # [C]
+    norm_b: torch.Tensor            # [C]
+    k_w: List[torch.Tensor]         # [d, C] each
+    k_b: List[torch.Tensor]
+    v_w: List[torch.Tensor]
+    v_b: List[torch.Tensor]
+    num_tokens: int
+
+
+def read_ip_adapter_file(path_or_dict, subfolder: Optional[str] = None, weight_name: Optional[str] = None) -> Dict[str, torch.Tensor]:
+    """State dict from a dict, a ``.safetensors`` file, or a directory / cached hub id (+ ``subfolder``) with ``weight_name``
+    (lora.read_lora_file's resolution; nothing is fetched)."""
+    from . import lora
+
+    if isinstance(path_or_dict, dict):
+        return dict(path_or_dict)
+    path = str(path_or_dict)
+    if not os.path.isfile(path):
+        from .modules import resolve_model_path
+
+        path = resolve_model_path(path)
+        if subfolder:
+            path = os.path.join(path, subfolder)
+        if weight_name is None:
+            files = sorted(f for f in os.listdir(path) if f.endswith(".safetensors")) if os.path.isdir(path) else []
+            if DEFAULT_WEIGHT_NAME in files:
+                weight_name = DEFAULT_WEIGHT_NAME
+            elif len(files) == 1:
+                weight_name = files[0]
+            else:
+                raise ValueError(f"{path}: pass weight_name= (no {DEFAULT_WEIGHT_NAME} and {len(files)} .safetensors files to choose from)")
+        if not os.path.isfile(os.path.join(path, weight_name)):
+            raise OSError(f"IP-Adapter file {os.path.join(path, weight_name)} not found")
+    return lora.read_lora_file(path, weight_name)[0]
+
+
+def parse_ip_adapter_state_dict(sd: Dict[str, torch.Tensor], num_layers: int, joint_attention_dim: int, inner_dim: int) -> IPAdapterWeights:
+    """Either key layout -> IPAdapterWeights; every refusal names the offending key."""
+    keys = list(sd)
+    bad = [k for k in keys if _SINGLE_BLOCK_KEYS.search(k)]
+    if bad:
+        raise ValueError(f"IP-Adapter keys of single blocks (the InstantX layout) are not supported: {sorted(bad)[0]}")
+    layout = next((name for name, (pp, _, rx) in _LAYOUTS.items() if any(k.startswith(pp + ".") or rx.match(k) for k in keys)), None)
+    if layout is None:
+        raise ValueError(f"no IP-Adapter keys found (expected image_proj.* / ip_adapter.* or ip_adapter_proj_model.* / double_blocks.*): "
+                         f"{sorted(keys)[0] if keys else '<empty state dict>'}")
+    pp, npfx, rx = _LAYOUTS[layout]
+    head = {f"{pp}.weight", f"{pp}.bias", f"{npfx}.weight", f"{npfx}.bias"}
+    blocks: Dict[int, Dict[Tuple[str, str], torch.Tensor]] = {}
+    for k in keys:
+        if k in head:
+            continue
+        m = rx.match(k)
+        if m is None:
+            raise ValueError(f"unrecognised IP-Adapter key: {k}")
+        blocks.setdefault(int(m.group(1)), {})[(m.group(2), m.group(3))] = sd[k]
+    for k in sorted(head):
+        if k not in sd:
+            raise ValueError(f"IP-Adapter state dict lacks {k}")
+
+    def block_key(i, kv, part):
+        return (f"ip_adapter.{i}.to_{kv}_ip.{part}" if layout == "diffusers"
+                else f"double_blocks.{i}.processor.ip_adapter_double_stream_{kv}_proj.{part}")
+
+    if sorted(blocks) != list(range(num_layers)):
+        odd = next((i for i in sorted(blocks) if i >= num_layers), None)
+        name = block_key(odd, "k", "weight") if odd is not None else block_key(next(i for i in range(num_layers) if i not in blocks), "k", "weight")
+        raise ValueError(f"IP-Adapter has {len(blocks)} blocks, the transformer {num_layers} double blocks: {name}")
+    C, d = joint_attention_dim, inner_dim
+    norm_w, norm_b, proj_w, proj_b = sd[f"{npfx}.weight"], sd[f"{npfx}.bias"], sd[f"{pp}.weight"], sd[f"{pp}.bias"]
+    if norm_w.dim() != 1 or norm_w.shape[0] != C or norm_b.shape != norm_w.shape:
+        raise ValueError(f"{npfx}.weight: width {tuple(norm_w.shape)} != joint_attention_dim {C}")
+    if proj_w.dim() != 2 or proj_w.shape[0] % C or not 1 <= proj_w.shape[0] // C <= MAX_TOKENS:
+        raise ValueError(f"{pp}.weight: {proj_w.shape[0]} output features are not 1..{MAX_TOKENS} tokens of width {C}")
+    if proj_b.shape != (proj_w.shape[0],):
+        raise ValueError(f"{pp}.bias: shape {tuple(proj_b.shape)} does not match {pp}.weight")
+    if proj_w.shape[1] % 8:
+        raise ValueError(f"{pp}.weight: image embedding width {proj_w.shape[1]} is not a multiple of 8")
+    out = IPAdapterWeights(proj_w, proj_b, norm_w, norm_b, [], [], [], [], proj_w.shape[0] // C)
+    for i in range(num_layers):
+        for kv, ws, bs in (("k", out.k_w, out.k_b), ("v", out.v_w, out.v_b)):
+            w, b = blocks[i].get((kv, "weight")), blocks[i].get((kv, "bias"))
+            if w is None:
+                raise ValueError(f"IP-Adapter state dict lacks {block_key(i, kv, 'weight')}")
+            if b is None:
+                raise ValueError(f"IP-Adapter state dict lacks {block_key(i, kv, 'bias')}")
+            if w.shape != (d, C):
+                raise ValueError(f"{block_key(i, kv, 'weight')}: shape {tuple(w.shape)} != (inner_dim {d}, joint_attention_dim {C})")
+            if b.shape != (d,):
+                raise ValueError(f"{block_key(i, kv, 'bias')}: shape {tuple(b.shape)} != ({d},)")
+            ws.append(w)
+            bs.append(b)
+    return out
+
+
+def normalize_scales(scale: Union[float, Sequence[float]], num_layers: int) -> List[float]:
+    """set_ip_adapter_scale's argument -> one float per double block."""
+    if isinstance(scale, (int, float)):
+        return [float(scale)] * num_layers
+    s = [float(x) for x in scale]
+    if len(s) != num_layers:
+        raise ValueError(f"set_ip_adapter_scale: expected a float or {num_layers} floats (one per double block), got {len(s)}")
+    return s
+
+
+def normalize_embeds(embeds) -> torch.Tensor:
+    """``ip_adapter_image_embeds`` as given (tensor or one-element list; [B,1,E], [1,1,E], [B,E] or [1,E]) -> [B or 1, E]."""
+    if isinstance(embeds, (list, tuple)):
+        if len(embeds) != 1:
+            raise ValueError(f"ip_adapter_image_embeds: one IP-Adapter is supported, got a list of {len(embeds)}")
+        embeds = embeds[0]
+    if not isinstance(embeds, torch.Tensor):
+        raise TypeError(f"ip_adapter_image_embeds: expected a tensor or a one-element list, got {type(embeds)}")
+    if embeds.dim() == 3:
+        if embeds.shape[1] != 1:
+            raise ValueError(f"ip_adapter_image_embeds: one image per sample is supported, got {embeds.shape[1]}")
+        embeds = embeds[:, 0]
+    if embeds.dim() != 2:
+        raise ValueError(f"ip_adapter_image_embeds: expected [B,1,E] or [B,E], got {tuple(embeds.shape)}")
+    return embeds
+
+
+@dataclass
+class PreparedIP:
+    """Loop-invariant K/V of one call: per double block (K_i, V_i) [B or 1, n, d] bf16 views of one GEMM output, and the scales."""
+
+    kv: List[Tuple[torch.Tensor, torch.Tensor]]
+    scales: List[float]
+    buf: torch.Tensor               # the storage the views point into
+
+
+class IPAdapter:
+    """Adapter state of one transformer: bf16 weights on the model's device, stacked [to_k_ip_0; to_v_ip_0; to_k_ip_1; ...] so that
+    the K/V of every block come from ONE GEMM per call (M = B·n rows), and the per-block scales (default 1.0)."""
+
+    def __init__(self, w: IPAdapterWeights, device):
+        bf = lambda t: t.to(device=device, dtype=torch.bfloat16).contiguous()
+        self.num_tokens, self.num_layers = w.num_tokens, len(w.k_w)
+        self.C, self.d, self.E = w.norm_w.shape[0], w.k_w[0].shape[0], w.proj_w.shape[1]
+        self.proj_w, self.proj_b = bf(w.proj_w), bf(w.proj_b)
+        # affine LayerNorm through rt_layernorm_modulate: LN(x)·(1 + scale) + shift with scale = weight - 1 (exact in fp32), shift = bias
+        self.norm_scale = (bf(w.norm_w).to(torch.float32) - 1.0).contiguous()
+        self.norm_shift = bf(w.norm_b).to(torch.float32).contiguous()
+        self.kv_w = torch.cat([bf(t) for pair in zip(w.k_w, w.v_w) for t in pair], dim=0).contiguous()        # [L·2d, C]
+        self.kv_b = torch.cat([bf(t) for pair in zip(w.k_b, w.v_b) for t in pair], dim=0).contiguous()
+        self.scales = [1.0] * self.num_layers
+        self.version = next(_VERSIONS)
+
+    def to_device(self, device) -> None:
+        moved = False
+        for name in ("proj_w", "proj_b", "norm_scale", "norm_shift", "kv_w", "kv_b"):
+            old = getattr(self, name)
+            new = old.to(device)
+            moved |= new is not old
+            setattr(self, name, new)
+        if moved:
+            self.version = next(_VERSIONS)
+
+    def set_scale(self, scale) -> None:
+        self.scales = normalize_scales(scale, self.num_layers)
+
+    @property
+    def active(self) -> bool:
+        return any(s != 0.0 for s in self.scales)
+
+    def prepare(self, embeds) -> PreparedIP:
+        """Steps 1-2 for one call: three launches (projection GEMM, LayerNorm, stacked K/V GEMM)."""
+        e = normalize_embeds(embeds)
+        if e.shape[1] != self.E:
+            raise ValueError(f"ip_adapter_image_embeds: width {e.shape[1]} != the adapter's image embedding width {self.E}")
+        if not self.proj_w.is_cuda:
+            raise RuntimeError("the IP-Adapter is on the CPU; move the transformer to the GPU (there is no CPU fallback)")
+        e = e.to(device=self.proj_w.device, dtype=torch.bfloat16).contiguous()
+        B, n, C, d, L = e.shape[0], self.num_tokens, self.C, self.d, self.num_layers
+        t32 = torch.empty(B, n * C, device=e.device, dtype=torch.float32)
+        ops.linear(e, self.proj_w, t32, bias=self.proj_b)
+        tok = torch.empty(B, n, C, device=e.device, dtype=torch.bfloat16)
+        ops.layernorm_modulate(t32.view(B, n, C), tok, self.norm_shift.repeat(B, 1), self.norm_scale.repeat(B, 1), eps=1e-5)
+        kv = torch.empty(B, n, L * 2 * d, device=e.device, dtype=torch.bfloat16)
+        ops.linear(tok, self.kv_w, kv, bias=self.kv_b)
+        views = [(kv[..., 2 * i * d : (2 * i + 1) * d], kv[..., (2 * i + 1) * d : (2 * i + 2) * d]) for i in range(L)]
+        return PreparedIP(views, list(self.scales), kv)

@@ -199,6 +199,12 @@ class Workspace:
         self.xn8 = None                            # fp8 path (allocated on first use): e4m3 LayerNorm output + row scales
         self.xs_t = self.xs_i = self.xs_all = None
 
+    def ip_buffer(self) -> torch.Tensor:
+        """[B,N,d] bf16: the IP-Adapter term of the running double block (allocated on first use)."""
+        if getattr(self, "_ip", None) is None:
+            self._ip = torch.empty(self.B, self.N, self.d, device=self._device, dtype=BF16)
+        return self._ip
+
     def fp8_buffers(self):
         if self.xn8 is None:
             B, T, N, S, d = self.B, self.T, self.N, self.S, self.d
@@ -321,10 +327,12 @@ class ModulationTable:
 
 
 def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: int, inject: Optional[torch.Tensor] = None,
-               mods: Optional[tuple] = None) -> None:
+               mods: Optional[tuple] = None, ip: Optional[tuple] = None) -> None:
     """One FluxTransformerBlock on ws.x in place (A.1). ``inject`` [B,N,d] bf16 is added to the image rows after the
     block (A.3 ControlNet residual), fused into the last GEMM's epilogue. ``mods`` = precomputed (image, text) adaLN
-    vectors for this step (ModulationTable); computed here from ``temb`` when absent."""
+    vectors for this step (ModulationTable); computed here from ``temb`` when absent. ``ip`` = (K, V, scale) of an IP-Adapter
+    (ip_adapter.py): scale · softmax(q Kᵀ/√128) V from the image query after norm_q and before RoPE, added to the image rows after the
+    feed-forward residual. With ``ip=None`` the launch sequence is unchanged."""
     T, d = ws.T, ws.d
     x_t, x_i = ws.x[:, :T], ws.x[:, T:]
     xn_t, xn_i = ws.xn[:, :T], ws.xn[:, T:]
@@ -351,6 +359,12 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         ops.layernorm_modulate(x_t, xn_t, ch(mt, 0), ch(mt, 1))
         ops.linear_grouped([P(xn_i, pl.qkv_img_w, ws.qkv[:, T:], bias=pl.qkv_img_b), P(xn_t, pl.qkv_txt_w, ws.qkv[:, :T], bias=pl.qkv_txt_b)])
     q, k, v = ws.qkv[..., :d], ws.qkv[..., d : 2 * d], ws.qkv[..., 2 * d :]
+    if ip is not None:
+        # the raw image query is only here: qk_rmsnorm_rope works in place and the attention output overwrites q
+        ip_out = ws.ip_buffer()
+        ops.ip_attention(q[:, T:], pl.nq_img, ip[0], ip[1], ip_out, H, ip_scale=ip[2])
+        if inject is None:
+            inject, ip = ip_out, None                # no ControlNet sample: the term rides the add2 slot of the ff2 epilogue
     if pl.fp8_attention:
         # 4.-6. RMSNorm(q,k) + RoPE -> e4m3 q|k and permuted Vᵀ, e4m3 joint attention; output over q ("mx": straight into the
         # out-projections' e4m3 operand with its block scales)
@@ -405,6 +419,9 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
     else:
         ops.linear_grouped([P(ws.ffh[:, T:], pl.ff2_img_w, x_i, bias=pl.ff2_img_b, gate=ch(mi, 5), res=x_i, add2=inject),
                             P(ws.ffh[:, :T], pl.ff2_txt_w, x_t, bias=pl.ff2_txt_b, gate=ch(mt, 5), res=x_t)])
+    if ip is not None:                               # the add2 slot holds the ControlNet sample: one accumulate pass per image
+        for b in range(ws.B):
+            ops.masked_accumulate_(ws.x[b, T:].unsqueeze(0), ip_out[b : b + 1], None, 1.0, True)
 
 
 def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: int, inject: Optional[torch.Tensor] = None,

@@ -463,6 +463,34 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     return out
 
 
+def ip_attention(q: torch.Tensor, wq: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, ip_scale: float = 1.0,
+                 accumulate: bool = False, scale: Optional[float] = None, eps: float = 1e-6) -> torch.Tensor:
+    """out (+)= ip_scale · softmax(bf16(rmsnorm(q)·wq) Kᵀ · scale) V (rt_ip_attention): the IP-Adapter term of a double block.
+    q [B,N,H·128] bf16 view of the RAW query projection (unit inner stride, e.g. columns :d of the fused q|k|v buffer; not modified);
+    wq bf16 [128] (norm_q.weight); k, v [B or 1, n, H·128] bf16 views sharing strides, 1 <= n <= 128 (batch 1: one image prompt for
+    every batch entry); out [B,N,H·128] bf16 or f32 view."""
+    d = H * 128
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] != d:
+            raise ValueError(f"{name}: need [B,rows,{d}] with unit inner stride, got {tuple(t.shape)} / {t.stride()}")
+    B, N, _ = q.shape
+    if out.shape != q.shape or out.dtype not in (BF16, F32):
+        raise ValueError("out must match q in shape and be bf16 or f32")
+    if k.shape != v.shape or k.stride() != v.stride() or k.shape[0] not in (1, B):
+        raise ValueError("k and v must share shape and strides, with batch 1 or B")
+    n = k.shape[1]
+    if not 1 <= n <= 128:
+        raise ValueError(f"ip_attention: 1..128 image-prompt tokens, got {n}")
+    if wq.numel() != 128 or not wq.is_contiguous():
+        raise ValueError("wq must be contiguous with 128 elements")
+    sc = (128 ** -0.5) if scale is None else float(scale)
+    native.check("rt_ip_attention", native.load().rt_ip_attention(
+        _dev(q, "q", BF16), q.stride(1), q.stride(0), _dev(wq, "wq", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), k.stride(1),
+        k.stride(0) if k.shape[0] == B and B > 1 else 0, _dev(out, "out"), out.stride(1), out.stride(0), int(out.dtype == F32),
+        int(accumulate), B, N, H, n, sc, float(ip_scale), float(eps), _stream()))
+    return out
+
+
 def attention_fp8_prep(buf: torch.Tensor, q_off: int, k_off: int, v_off: int, H: int, T: int, wq_txt, wk_txt, wq_img, wk_img,
                        cos: torch.Tensor, sin: torch.Tensor, qk8: torch.Tensor, vt8: torch.Tensor, eps: float = 1e-6) -> None:
     """From the fused projection buffer buf [B,S,ld] bf16 (not modified): qk8 [B,S,2·H·128] e4m3 = 16 · RoPE(RMSNorm(q | k)),

@@ -14,6 +14,7 @@ into the ControlNet's zero-linear epilogues.
 from __future__ import annotations
 
 import contextlib
+import functools
 import inspect
 import json
 import os
@@ -109,6 +110,21 @@ GRAPH_CAPTURE = os.environ.get("RT_GRAPH", "1") == "1"
 GRAPH_CACHE_MAX = 2
 
 
+def accepts_ip_adapter_arguments(call):
+    """``__call__`` keeps the reference's parameter list (PIPE:751-781, which ``inspect.signature`` still reports); the IP-Adapter's two
+    arguments, ``ip_adapter_image`` and ``ip_adapter_image_embeds``, are keyword-only extensions taken off here and left on the pipeline
+    as ``_ip_call_args`` for the duration of the call. What the call derives from them (``_ip_embeds``, read by ``_denoise``) is cleared
+    with them, so a later direct ``_denoise`` never sees a previous call's image prompt. Not re-entrant, like the rest of the call state."""
+    @functools.wraps(call)
+    def wrapper(self, *args, ip_adapter_image=None, ip_adapter_image_embeds=None, **kwargs):
+        self._ip_call_args = (ip_adapter_image, ip_adapter_image_embeds)
+        try:
+            return call(self, *args, **kwargs)
+        finally:
+            self._ip_call_args, self._ip_embeds = (None, None), None
+    return wrapper
+
+
 class FluxControlNetPipeline:
     model_cpu_offload_seq = "text_encoder->text_encoder_2->transformer->vae"
     _optional_components: List[str] = []
@@ -126,6 +142,7 @@ class FluxControlNetPipeline:
         self.default_sample_size = 64
         self._guidance_scale, self._joint_attention_kwargs, self._interrupt, self._num_timesteps = 1.0, None, False, 0
         self._progress_disabled = False
+        self._ip_call_args, self._ip_embeds = (None, None), None
 
     # ------------------------------------------------------------------ component plumbing
     @property
@@ -479,6 +496,50 @@ class FluxControlNetPipeline:
     def disable_lora(self):
         self.transformer.disable_adapters()
 
+    # ------------------------------------------------------------------ IP-Adapter (image prompt): the FluxIPAdapterMixin subset, routed
+    # to the transformer (ip_adapter.py). No image encoder is built here: callers pass `ip_adapter_image_embeds`.
+    def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder: Optional[str] = None, weight_name: Optional[str] = None,
+                        image_encoder_pretrained_model_name_or_path: Optional[str] = None, **kwargs):
+        """``image_encoder_pretrained_model_name_or_path`` is accepted for interface parity and ignored (no CLIP vision encoder)."""
+        self.transformer.load_ip_adapter(pretrained_model_name_or_path_or_dict, subfolder=subfolder, weight_name=weight_name)
+
+    def set_ip_adapter_scale(self, scale):
+        self.transformer.set_ip_adapter_scale(scale)
+
+    def unload_ip_adapter(self):
+        self.transformer.unload_ip_adapter()
+
+    def _resolve_ip_embeds(self, ip_adapter_image, ip_adapter_image_embeds, joint_attention_kwargs, batch_size, num_images_per_prompt, device):
+        """(embeds [total or 1, E] bf16 on the device, or None when the adapter has nothing to add; joint_attention_kwargs without the
+        embeds). The embeds may also arrive as joint_attention_kwargs["ip_adapter_image_embeds"], where diffusers' pipeline puts them."""
+        from . import ip_adapter as _ipa
+
+        if ip_adapter_image is not None:
+            raise NotImplementedError("ip_adapter_image needs an image encoder, which this pipeline does not have: encode the image "
+                                      "yourself and pass ip_adapter_image_embeds")
+        kw = joint_attention_kwargs
+        if kw is not None and "ip_adapter_image_embeds" in kw:
+            if ip_adapter_image_embeds is not None:
+                raise ValueError("ip_adapter_image_embeds were passed both as an argument and inside joint_attention_kwargs")
+            ip_adapter_image_embeds = kw["ip_adapter_image_embeds"]
+            kw = {k: v for k, v in kw.items() if k != "ip_adapter_image_embeds"} or None
+        if ip_adapter_image_embeds is None:
+            return None, kw
+        adapter = getattr(self.transformer, "_ip_adapter", None)
+        if adapter is None:
+            raise ValueError("ip_adapter_image_embeds were passed but no IP-Adapter is loaded (load_ip_adapter)")
+        e = _ipa.normalize_embeds(ip_adapter_image_embeds)
+        total = batch_size * num_images_per_prompt
+        if e.shape[0] == batch_size and total != batch_size:
+            e = e.repeat_interleave(num_images_per_prompt, dim=0)
+        if e.shape[0] not in (1, total):
+            raise ValueError(f"ip_adapter_image_embeds: batch {e.shape[0]} is neither 1 nor the number of images {total}")
+        if e.shape[1] != adapter.E:
+            raise ValueError(f"ip_adapter_image_embeds: width {e.shape[1]} != the adapter's image embedding width {adapter.E}")
+        if not adapter.active:
+            return None, kw
+        return e.to(device=device, dtype=torch.bfloat16).contiguous(), kw
+
     def _lora_models(self) -> list:
         cn = self.controlnet
         nets = list(cn.nets) if isinstance(cn, FluxMultiControlNetModel) else [cn]
@@ -497,6 +558,7 @@ class FluxControlNetPipeline:
         return kw is None or (set(kw) == {"scale"} and bool(self._lora_models()))
 
     # ------------------------------------------------------------------ the call
+    @accepts_ip_adapter_arguments
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 28,
@@ -528,6 +590,8 @@ class FluxControlNetPipeline:
             batch_size = prompt_embeds.shape[0]
         device, dtype = self._execution_device, self.transformer.dtype
         total = batch_size * num_images_per_prompt
+        self._ip_embeds, self._joint_attention_kwargs = self._resolve_ip_embeds(*self._ip_call_args, joint_attention_kwargs, batch_size,
+                                                                                num_images_per_prompt, device)
 
         prompt_embeds, pooled_prompt_embeds, text_ids = self.encode_prompt(
             prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds, device=device,
@@ -607,12 +671,13 @@ class FluxControlNetPipeline:
                  cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps):
         """Eager loop, or the replay of its captured hipGraph when this exact call signature has been seen before (GRAPH_CAPTURE)."""
         tvals = timesteps.to(torch.float32).cpu().tolist()                 # host copies: no per-step device sync
+        ipe = getattr(self, "_ip_embeds", None)                             # image prompt of this call (None: nothing to add)
         use_graph = (GRAPH_CAPTURE and getattr(self, "capture_graphs", True) and callback is None and latents.is_cuda
                      and not self.interrupt and isinstance(self.controlnet, (FluxControlNetModel, type(None)))
                      and (control_mode is None) and self._graph_safe_kwargs())
         if not use_graph:
             return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
-                                       cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps)
+                                       cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe)
         from . import mmdit as _mm
         _mm.reference_bf16_scalars(self.reference_bf16_scalars)      # the module switch follows THIS pipeline before the key is built
         sig = lambda t: (tuple(t.shape), str(t.dtype), tuple(t.stride()))
@@ -621,6 +686,10 @@ class FluxControlNetPipeline:
         key = (sig(latents), sig(prompt_embeds), sig(pooled), sig(text_ids), sig(image_ids), tuple(sig(h) for h in hints), tuple(sig(m) for m in masks),
                tuple(tvals), tuple(self.scheduler.sigmas.tolist()), float(guidance_scale), repr(cn_scale), int(cn_steps), int(num_inference_steps),
                str(latents.device), models, bool(self.reference_bf16_scalars), bool(_mm.RESIDUAL_F32), bool(OVERLAP_TOWER))
+        if ipe is not None:
+            # the embeds are one more static input of the graph; the per-block scales are kernel scalars baked into the capture
+            adapter = self.transformer._ip_adapter
+            key += (sig(ipe), adapter.version, tuple(adapter.scales))
         cache = self.__dict__.setdefault("_graph_cache", {})
         ent = cache.get(key)
         if ent is None:                                      # first sight of this signature: eager (and warm), remember it
@@ -628,15 +697,16 @@ class FluxControlNetPipeline:
                 cache.pop(next(iter(cache)))
             cache[key] = "seen"
             return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
-                                       cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps)
+                                       cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe)
         if ent == "failed":
             return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
-                                       cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps)
-        ins = [latents, prompt_embeds, pooled, text_ids, image_ids] + list(hints) + list(masks)
+                                       cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe)
+        ins = [latents, prompt_embeds, pooled, text_ids, image_ids] + list(hints) + list(masks) + ([ipe] if ipe is not None else [])
         if ent == "seen":                                    # second call: capture
             static = [t.clone() for t in ins]
-            nh = len(hints)
+            nh, nm = len(hints), len(masks)
             keep = [m._ensure_plans() for m in (self.transformer, self.controlnet) if m is not None] + [getattr(self.controlnet, "_cx_pad", None)]
+            keep.append(getattr(self.transformer, "_ip_adapter", None) if ipe is not None else None)     # its weights are read by the graph
             graph = torch.cuda.CUDAGraph()
             step_index = self.scheduler._step_index
             # The graph bakes in the device pointers of every buffer the loop touches. Buffers that live in caches which may evict or
@@ -648,9 +718,9 @@ class FluxControlNetPipeline:
             try:
                 # thread-local capture mode: calls made by OTHER threads (RCCL's watchdog polling its events) do not invalidate the capture
                 with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    out = self._denoise_eager(static[0], static[1], static[2], static[3], static[4], tvals, static[5 : 5 + nh], static[5 + nh :],
+                    out = self._denoise_eager(static[0], static[1], static[2], static[3], static[4], tvals, static[5 : 5 + nh], static[5 + nh : 5 + nh + nm],
                                               guidance_scale, cn_scale, cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps,
-                                              _quiet=True)
+                                              _quiet=True, _ip_embeds=static[-1] if ipe is not None else None)
                     out32 = self._master_latents
             except Exception as e:                           # capture is an optimisation, never a requirement
                 import sys
@@ -661,7 +731,7 @@ class FluxControlNetPipeline:
                 torch.cuda.synchronize()
                 self.scheduler._step_index = step_index
                 return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
-                                           cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps)
+                                           cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe)
             _mm.CAPTURE_KEEP = ops.CAPTURE_KEEP = None
             keep.append(getattr(self, "_sample_cache", None))
             keep.extend(dict(m._rope_cache) for m in (self.transformer, self.controlnet) if m is not None and hasattr(m, "_rope_cache"))
@@ -678,7 +748,8 @@ class FluxControlNetPipeline:
         return ent["out"].clone()
 
     def _denoise_eager(self, latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale,
-                       cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _quiet=False):
+                       cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _quiet=False,
+                       _ip_embeds=None):
         device = latents.device
         B = latents.shape[0]
         guidance = torch.full((B,), float(guidance_scale), device=device, dtype=torch.float32) if self.transformer.config.guidance_embeds else None
@@ -695,6 +766,8 @@ class FluxControlNetPipeline:
         # prompt_embeds invalidates them (recomputed below).
         static_t = self.transformer.prepare_static(prompt_embeds)
         static_c = [self.controlnet.prepare_static(prompt_embeds, h) for h in hints] if fused_cn and cn_steps > 0 else []
+        # the image prompt's tokens and every block's K/V of them: loop-invariant too (ip_adapter.py steps 1-2)
+        ip_prep = self.transformer._ip_adapter.prepare(_ip_embeds) if _ip_embeds is not None else None
         # Which tower samples does the transformer read? Block i takes sample i // ceil(n_blocks / n_samples) (A.3): with 6
         # samples against 19 double blocks the sixth is never consumed (Q5), so its block and zero-linear are not evaluated.
         blocks_needed, sample_buf, single_buf = None, None, None
@@ -777,7 +850,7 @@ class FluxControlNetPipeline:
                     hidden_states=latents, timestep=timestep, guidance=guidance, pooled_projections=pooled,
                     encoder_hidden_states=prompt_embeds, controlnet_block_samples=merged, controlnet_single_block_samples=merged_single,
                     txt_ids=text_ids, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs, return_dict=False,
-                    _mods=tab_t.step(i), _sample_events=events, _static=static_t)[0]
+                    _mods=tab_t.step(i), _sample_events=events, _static=static_t, _ip=ip_prep)[0]
                 if events is not None:
                     torch.cuda.current_stream().wait_stream(side)     # the tower has finished reading `latents` (its last sample is unused, Q5)
                 self.scheduler.step_master_(noise_pred, lat32, latents)

@@ -21,7 +21,7 @@ from . import ops
 from .controlnet import FluxControlNetModel
 from .image_processor import PipelineImageInput, VaeImageProcessor
 from .pipeline import FluxControlNetPipeline as _BasePipeline
-from .pipeline import FluxPipelineOutput, calculate_shift, retrieve_timesteps
+from .pipeline import FluxPipelineOutput, accepts_ip_adapter_arguments, calculate_shift, retrieve_timesteps
 from .utils import randn_tensor
 
 DEFAULT_NEGATIVE_PROMPT = "bad quality, worst quality, text, signature, watermark, extra words"     # INP:416
@@ -111,6 +111,7 @@ class FluxControlNetPipeline(_BasePipeline):
             t.shape[-1] == cn.controlnet_x_embedder.weight.shape[1]
 
     # ------------------------------------------------------------------ INP:846-1313
+    @accepts_ip_adapter_arguments
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  true_guidance_scale: float = 3.5, negative_prompt: Optional[Union[str, List[str]]] = None,
@@ -136,6 +137,9 @@ class FluxControlNetPipeline(_BasePipeline):
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, prompt_2, height, width, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
                           callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, max_sequence_length=max_sequence_length)
+        if any(a is not None for a in self._ip_call_args) or "ip_adapter_image_embeds" in (joint_attention_kwargs or {}):
+            # the conditioning batch is 2B under true CFG: the unconditional half would need a negative image prompt
+            raise ValueError("the inpaint pipeline does not support IP-Adapter image prompts (ip_adapter_image / ip_adapter_image_embeds)")
         self._guidance_scale, self._joint_attention_kwargs, self._interrupt = guidance_scale, joint_attention_kwargs, False
         cfg = self.do_classifier_free_guidance                          # enabled by guidance_scale > 1, scaled by true_guidance_scale (Q8)
 

@@ -12,7 +12,7 @@ from typing import Sequence, Any, Dict, List, Optional
 import torch
 import torch.nn as nn
 
-from . import lora, mmdit, ops
+from . import ip_adapter, lora, mmdit, ops
 from .config import Config, flux_dev_transformer_config
 from .modules import DoubleBlockParams, Lin, SingleBlockParams, TimeTextEmbedParams, WeightsIO, _ada
 from .ops import LinearProblem as P
@@ -96,6 +96,8 @@ class _MMDiTBase(nn.Module, WeightsIO):
         out = super()._apply(fn, *a, **k)
         if getattr(self, "_lora", None) is not None:
             self._lora.to_device(self.device)          # factors and W0 copies follow the weights
+        if getattr(self, "_ip_adapter", None) is not None:
+            self._ip_adapter.to_device(self.device)
         return out
 
     def enable_fp8_attention(self, on: bool = True):
@@ -322,6 +324,25 @@ class FluxTransformer2DModel(_MMDiTBase):
         d = self.inner_dim
         self.norm_out = _ada(d, 2, device=device, dtype=dtype)
         self.proj_out = Lin(d, patch_size * patch_size * self.out_channels, device=device, dtype=dtype)
+        self._ip_adapter: Optional["ip_adapter.IPAdapter"] = None
+
+    # ---- IP-Adapter (image prompt): the FluxIPAdapterMixin subset; state in ip_adapter.py, not in the parameters
+    def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder: Optional[str] = None, weight_name: Optional[str] = None):
+        """Read an IP-Adapter (dict, .safetensors file, directory + weight_name, or cached hub id; diffusers or XLabs key layout) and
+        make it this model's adapter at scale 1.0 in every double block. Replaces a loaded one."""
+        sd = ip_adapter.read_ip_adapter_file(pretrained_model_name_or_path_or_dict, subfolder, weight_name)
+        w = ip_adapter.parse_ip_adapter_state_dict(sd, self.config.num_layers, self.config.joint_attention_dim, self.inner_dim)
+        self._ip_adapter = ip_adapter.IPAdapter(w, self.device)
+        return self
+
+    def set_ip_adapter_scale(self, scale):
+        """One float for every double block, or a list of num_layers floats. A block at 0.0 launches nothing for the adapter."""
+        if self._ip_adapter is None:
+            raise ValueError(f"{type(self).__name__}: no IP-Adapter is loaded")
+        self._ip_adapter.set_scale(scale)
+
+    def unload_ip_adapter(self):
+        self._ip_adapter = None
 
     @torch.no_grad()
     def forward(self, hidden_states: torch.Tensor, encoder_hidden_states: torch.Tensor = None,
@@ -330,11 +351,16 @@ class FluxTransformer2DModel(_MMDiTBase):
                 joint_attention_kwargs: Optional[Dict[str, Any]] = None, controlnet_block_samples=None,
                 controlnet_single_block_samples=None, return_dict: bool = True, controlnet_blocks_repeat: bool = False,
                 _mods: Optional["mmdit.StepMods"] = None, _sample_events: Optional[Sequence["torch.cuda.Event"]] = None,
-                _static: Optional[StaticEmbeds] = None):
-        """``_sample_events[k]`` (optional): event another stream records when controlnet_block_samples[k] is complete; the
+                _static: Optional[StaticEmbeds] = None, _ip: Optional["ip_adapter.PreparedIP"] = None):
+        """``joint_attention_kwargs["ip_adapter_image_embeds"]`` (as in diffusers): the image prompt of a loaded IP-Adapter, projected
+        and applied in every double block (ip_adapter.py); ``_ip`` (optional) = the same already prepared (``_ip_adapter.prepare``), so
+        that a loop does not redo the projection per step.
+        ``_sample_events[k]`` (optional): event another stream records when controlnet_block_samples[k] is complete; the
         current stream waits for it right before the first block that consumes that sample. ``_static`` (optional): this
         model's loop-invariant embeddings (prepare_static) — the text rows are copied instead of recomputed."""
         doubles, singles = self._ensure_plans()
+        joint_attention_kwargs = dict(joint_attention_kwargs or {})          # a copy: the image prompt is popped below, as diffusers does
+        ip_embeds = joint_attention_kwargs.pop("ip_adapter_image_embeds", None)
         self._apply_lora_scale(joint_attention_kwargs)
         cfg = self.config
         B, N, _ = hidden_states.shape
@@ -357,6 +383,10 @@ class FluxTransformer2DModel(_MMDiTBase):
         temb = None if _mods is not None else self._temb(ws, timestep, guidance, pooled_projections)
         cos, sin = self._rope(txt_ids, img_ids)
         nl, ns = len(doubles), len(singles)
+        if _ip is None and ip_embeds is not None:
+            if getattr(self, "_ip_adapter", None) is None:
+                raise ValueError("ip_adapter_image_embeds were passed but no IP-Adapter is loaded (load_ip_adapter)")
+            _ip = self._ip_adapter.prepare(ip_embeds) if self._ip_adapter.active else None
         waited = set()
         for i, pl in enumerate(doubles):
             inj = None
@@ -367,7 +397,8 @@ class FluxTransformer2DModel(_MMDiTBase):
                 if _sample_events is not None and k not in waited:
                     torch.cuda.current_stream().wait_event(_sample_events[k])
                     waited.add(k)
-            mmdit.run_double(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.double[i])
+            ip = None if _ip is None or _ip.scales[i] == 0.0 else (*_ip.kv[i], _ip.scales[i])
+            mmdit.run_double(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.double[i], ip=ip)
         for i, pl in enumerate(singles):
             inj = None
             if controlnet_single_block_samples is not None:

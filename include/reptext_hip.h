@@ -243,6 +243,22 @@ int rt_lora_merge_bf16(const rt_lora_term* terms /* host */, int32_t nterms, con
                        void* W, int64_t ldw, int32_t N, int32_t K, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * IP-Adapter image prompt (csrc/ip_attention.hip): the cross-attention term a FLUX double block adds to its image stream,
+ *   o (+)= ip_scale * softmax( bf16(rmsnorm(q) * wq) * K^T * sm_scale ) * V          (heads of 128, concatenated along columns)
+ * q: the block's RAW image-stream query projection, bf16 rows of ldq elements (e.g. the fused q|k|v buffer: ldq = 3*H*128), head h at
+ * column h*128; it is NOT modified. The RMSNorm (eps, weight wq = norm_q.weight bf16[128]) is computed in fp32 from the raw row and
+ * rounded to bf16 as the MFMA operand. k, v: bf16 [B|1][n_ip][ldkv], head h at column h*128; stride_kvb = 0 shares one image prompt
+ * between the batch entries. o: bf16 or f32 (o_f32) rows of ldo elements; accumulate != 0 adds to what o holds. Only the first N rows
+ * and H*128 columns of each batch entry of o are touched. One pass, no online softmax: keys are padded to a multiple of 32 inside
+ * the kernel and the padding is masked. Any N >= 1.
+ * Rejected on the host: null pointers, B / N / H / n_ip < 1, sm_scale <= 0, a leading dimension < H*128 (RT_E_BADARG); n_ip > 128 (RT_E_SHAPE);
+ * pointers not 16-byte aligned, ldq / ldkv / the bf16 ldo or a batch stride not a multiple of 8 (f32 o: of 4) (RT_E_ALIGN). */
+int rt_ip_attention(const void* q, int64_t ldq, int64_t stride_qb, const void* wq,
+                    const void* k, const void* v, int64_t ldkv, int64_t stride_kvb,
+                    void* o, int64_t ldo, int64_t stride_ob, int32_t o_f32, int32_t accumulate,
+                    int32_t B, int32_t N, int32_t H, int32_t n_ip, float sm_scale, float ip_scale, float eps, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Prompt encoders (PIPE:232-347: T5-XXL encoder -> prompt_embeds [B,512,4096], CLIP-L text model ->
  * pooled_prompt_embeds [B,768]). Once per prompt, outside the loop. Matrix work is rt_gemm_bf16; attention (head dim 64)
  * is assembled per head from rt_gemm_bf16 / rt_softmax_rows_bias / rt_transpose_bf16 / rt_gemm_bf16.
