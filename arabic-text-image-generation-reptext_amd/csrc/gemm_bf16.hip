@@ -242,6 +242,61 @@ __device__ __forceinline__ void epilogue_tile(const rt_gemm_group& g, int bidx, 
   }
 }
 
+// q/k RMSNorm + RoPE of one 256x256 tile through the LDS ring, which is idle after the K loop (rt_gemm_group::rope_*; ROPE
+// instantiation only, tiles whose columns are q or k). Nothing is kept beside the accumulators: after the first phase they are dead.
+//   1. barrier (every wave is past its last fragment read), then each lane stores pack_bf16x2(acc + bias) — the value epilogue_tile
+//      stores for these columns — of its fragments to an LDS image of the tile with 520-byte rows: the 16 rows a 16-lane group
+//      writes at one column (8 bytes each) fall on 16 distinct 8-byte slots of the 128-byte bank row of ds_write_b64;
+//   2. barrier, then 16 lanes per row read the two heads of the row (8 elements per lane and head, as two ds_read_b64: rows are
+//      8-byte aligned, and the two rows of a 32-lane half interleave on the 256-byte bank row), run rt_qk_norm_rope8 — the
+//      stand-alone kernel's arithmetic — and store 16 bytes per lane (256 contiguous bytes per head row). cos/sin of the row are
+//      loaded once for both heads. 8 passes of 32 rows.
+constexpr int ROPE_RS = 520;                                   // LDS row stride in bytes
+constexpr int ROPE_LDS_BYTES = 256 * ROPE_RS;
+template <int NI, int NJ>
+__device__ __forceinline__ void rope_epilogue(const rt_gemm_group& g, int bidx, int m0, int n0, int lrow, int lcol, f32x4 (&acc)[NI][NJ], char* smem) {
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    f32x4 b4 = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (g.bias) {
+      const u32x2 b = *reinterpret_cast<const u32x2*>(reinterpret_cast<const bf16_t*>(g.bias) + n0 + lcol + 16 * j);
+      b4 = f32x4{bf16lo(b[0]), bf16hi(b[0]), bf16lo(b[1]), bf16hi(b[1])};
+    }
+#pragma unroll
+    for (int i = 0; i < NI; ++i) {
+      const f32x4 v = acc[i][j] + b4;
+      *reinterpret_cast<u32x2*>(smem + (lrow + 16 * i) * ROPE_RS + (lcol + 16 * j) * 2) = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+    }
+  }
+  __syncthreads();
+  const int grp = threadIdx.x >> 4, sub = threadIdx.x & 15;
+  const bool isk = n0 >= g.rope_k0 && n0 < g.rope_k0 + g.rope_w;
+  const u32x4 wu = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(isk ? g.rope_wk : g.rope_wq) + sub * 8);
+  const int rpb = g.rows_per_batch > 0 ? g.rows_per_batch : g.M;
+  bf16_t* cb = reinterpret_cast<bf16_t*>(g.C) + (int64_t)bidx * g.strideC + n0 + sub * 8;
+#pragma unroll 2
+  for (int it = 0; it < 8; ++it) {
+    const int row = it * 32 + grp;
+    const int m = m0 + row;
+    if (m >= g.M) continue;              // whole 16-lane groups skip together; the butterfly stays inside the group
+    const int64_t s = g.rope_pos0 + m % rpb;
+    const float* cp = g.rope_cos + s * 128 + sub * 8;
+    const float* sp = g.rope_sin + s * 128 + sub * 8;
+    const f32x4 c0 = *reinterpret_cast<const f32x4*>(cp), c1 = *reinterpret_cast<const f32x4*>(cp + 4);
+    const f32x4 s0 = *reinterpret_cast<const f32x4*>(sp), s1 = *reinterpret_cast<const f32x4*>(sp + 4);
+    const float cs[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
+    const float sn[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const char* lp = smem + row * ROPE_RS + h * 256 + sub * 16;
+      const u32x2 lo = *reinterpret_cast<const u32x2*>(lp), hi = *reinterpret_cast<const u32x2*>(lp + 8);
+      const u32x4 o = rt_qk_norm_rope8(u32x4{lo[0], lo[1], hi[0], hi[1]}, wu, cs, sn, g.rope_eps);
+      *reinterpret_cast<u32x4*>(cb + (int64_t)m * g.ldc + h * 128) = o;
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------
 // gemm_tile: one output tile, the ping-pong schedule.
 //   * a K-tile is consumed in 4 phases, one quadrant of the wave's output each, in the order (a0,b0) (a0,b1) (a1,b1) (a1,b0)
@@ -307,7 +362,7 @@ typedef __attribute__((ext_vector_type(8))) int i32x8;
 //              behind the image, which only halo rows make, into zeros) — and c0 in the scalar offset. Halo rows are computed and
 //              dropped in the epilogue (0.4-3 % of the rows). Everything else — tile, LDS image, ping-pong schedule, counted waits —
 //              is the GEMM's; the K order of an output element is that of csrc/vae.hip's conv_nhwc_kernel (bit-identical results).
-template <bool FP8, class G_, bool MX = false, bool CONV = false>
+template <bool FP8, class G_, bool MX = false, bool CONV = false, bool ROPE = false>
 __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int m0, int n0, bool wide_store, char* smem) {
   using T = G_;
   static_assert(!MX || FP8, "block scales belong to the e4m3 form");
@@ -538,6 +593,13 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
 #undef RT_MFMA8_ROW
 #undef RT_CAT8
 
+  if constexpr (ROPE) {                        // q / k tiles of a group that carries the fused step (tile-uniform: the ranges are tile-aligned)
+    static_assert(!FP8 && !CONV && T::BM == 256 && T::BN == 256, "the fused q/k step belongs to the bf16 256x256 tile");
+    if (g.rope_cos && ((n0 >= g.rope_q0 && n0 < g.rope_q0 + g.rope_w) || (n0 >= g.rope_k0 && n0 < g.rope_k0 + g.rope_w))) {
+      rope_epilogue<T::NI, T::NJ>(g, bidx, m0, n0, wm * T::WMR + l15, wn * T::WNC + 4 * (lane >> 4), acc, smem);
+      return;
+    }
+  }
   const int mrow = m0 + wm * T::WMR + l15;
   const int ncol = n0 + wn * T::WNC + 4 * (lane >> 4);
   if (g.out_f32) epilogue_tile<true, FP8, T::NI, T::NJ, CONV>(g, bidx, mrow, ncol, acc);
@@ -565,7 +627,7 @@ __device__ __forceinline__ void panel_walk(int t, int tiles_m, int tiles_n, int&
 typedef const __attribute__((address_space(4))) Launch* LaunchPtr;
 
 // One geometry for the whole launch: Geo256, or Geo128 for the convolution form with N <= 128.
-template <bool FP8, class G_, bool MX = false, bool CONV = false>
+template <bool FP8, class G_, bool MX = false, bool CONV = false, bool ROPE = false>
 __global__ __launch_bounds__(THREADS, 2) void gemm_pp_kernel(const Launch L) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   LaunchPtr Lp = (LaunchPtr)__builtin_amdgcn_kernarg_segment_ptr();
@@ -588,10 +650,12 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_pp_kernel(const Launch L) {
   t -= bidx * tiles_per_batch;
   int tm, tn;
   panel_walk(t, G.tiles_m, G.tiles_n, tm, tn);
-  gemm_tile<FP8, G_, MX, CONV>(G.g, bidx, tm * G_::BM, tn * G_::BN, G.wide_store != 0, smem);
+  gemm_tile<FP8, G_, MX, CONV, ROPE>(G.g, bidx, tm * G_::BM, tn * G_::BN, G.wide_store != 0, smem);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
+constexpr int ROPE_LDS = ROPE_LDS_BYTES > Geo256::LDS_BYTES ? ROPE_LDS_BYTES : Geo256::LDS_BYTES;    // 130 KiB of the CU's 160
+
 template <class K>
 int set_lds(K kern, int bytes) {
   hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
@@ -605,7 +669,7 @@ static int launch_gemm(const rt_gemm_group* groups, int32_t ngroups, void* strea
   Launch L{};
   L.ngroups = ngroups;
   int total = 0;
-  bool mx = false, conv = false;
+  bool mx = false, conv = false, rope = false;
   const int bke = fp8 ? 128 : BK;                     // elements per K-tile
   const int al = fp8 ? 16 : 8;                        // elements per 16 bytes
   const int64_t esz = fp8 ? 1 : 2;
@@ -641,6 +705,18 @@ static int launch_gemm(const rt_gemm_group* groups, int32_t ngroups, void* strea
         if (!RT_ALIGNED(g.c8, 8) || g.ldc8 % 8 || g.stride_c8 % 8 || !RT_ALIGNED(g.c_bscale, 16)) return RT_E_ALIGN;
       }
     }
+    if (g.rope_cos) {                                   // fused q/k RMSNorm + RoPE (rope_epilogue)
+      if (fp8 || g.out_f32 || g.conv_ks != 0 || !g.rope_sin || !g.rope_wq || !g.rope_wk) return RT_E_BADARG;
+      if (g.gate || g.res || g.add2 || g.rowscale || g.alpha != 1.0f) return RT_E_BADARG;
+      const int q0 = g.rope_q0, k0 = g.rope_k0, w = g.rope_w;
+      if (q0 < 0 || k0 < 0 || w < 256 || q0 % 256 || k0 % 256 || w % 256 || q0 + w > g.N || k0 + w > g.N || (q0 < k0 + w && k0 < q0 + w) ||
+          g.gelu_from < q0 + w || g.gelu_from < k0 + w || g.rope_pos0 < 0)
+        return RT_E_SHAPE;
+      if (!RT_ALIGNED(g.C, 16) || g.ldc % 8 || g.strideC % 8 || !RT_ALIGNED(g.rope_cos, 16) || !RT_ALIGNED(g.rope_sin, 16) ||
+          !RT_ALIGNED(g.rope_wq, 16) || !RT_ALIGNED(g.rope_wk, 16))
+        return RT_E_ALIGN;
+      rope = true;
+    }
     if (g.conv_ks != 0) {                               // convolution form (see gemm_tile): one bf16 problem, rows = haloed pixels
       if (fp8 || ngroups != 1 || g.batch != 1 || (g.conv_ks != 1 && g.conv_ks != 3)) return RT_E_BADARG;
       if (g.conv_cin < 64 || g.conv_cin % 64 != 0 || g.lda != g.conv_cin || g.K != g.conv_ks * g.conv_ks * g.conv_cin) return RT_E_SHAPE;
@@ -661,6 +737,7 @@ static int launch_gemm(const rt_gemm_group* groups, int32_t ngroups, void* strea
     if (!e) e = set_lds(gemm_pp_kernel<true, Geo256, true>, Geo256::LDS_BYTES + 16384);
     if (!e) e = set_lds(gemm_pp_kernel<false, Geo256, false, true>, Geo256::LDS_BYTES);
     if (!e) e = set_lds(gemm_pp_kernel<false, Geo128, false, true>, Geo128::LDS_BYTES);
+    if (!e) e = set_lds(gemm_pp_kernel<false, Geo256, false, false, true>, ROPE_LDS);
     if (e) return e;
     attr_done = true;
   }
@@ -681,7 +758,9 @@ static int launch_gemm(const rt_gemm_group* groups, int32_t ngroups, void* strea
     }
     return rt_hip_status();
   }
-  hipLaunchKernelGGL((gemm_pp_kernel<false, Geo256>), dim3(total), dim3(THREADS), Geo256::LDS_BYTES, st, L);
+  // a launch in which some group carries the fused q/k step runs its own instantiation: every other launch keeps its code object
+  if (rope) hipLaunchKernelGGL((gemm_pp_kernel<false, Geo256, false, false, true>), dim3(total), dim3(THREADS), ROPE_LDS, st, L);
+  else hipLaunchKernelGGL((gemm_pp_kernel<false, Geo256>), dim3(total), dim3(THREADS), Geo256::LDS_BYTES, st, L);
   return rt_hip_status();
 }
 

@@ -21,15 +21,29 @@ __device__ __forceinline__ u32x2 pack_e4m3x8(const float (&y)[8]) {
 
 constexpr float E4M3_MAX = 448.f;
 
+// A launch covers one or two row segments (rt_layernorm_modulate_pair: image rows + text rows of a double block), each with its own
+// tensors, leading dimensions and adaLN vectors; a wave picks its segment from its row index and then works as before.
+struct LnLaunch {
+  rt_ln_segment seg[2];
+  int rows0;            // rows of segment 0; rows >= rows0 belong to segment 1
+  int rows;             // all rows
+};
+
 template <bool X_F32, int NCH, bool OUT_FP8 = false>   // NCH = chunks of 8 elements per lane  (D <= 64*8*NCH)
-__global__ __launch_bounds__(256) void layernorm_mod_kernel(
-    const void* __restrict__ x, int64_t ldx, int64_t stride_xb, bf16_t* __restrict__ out, int64_t ldo,
-    int64_t stride_ob, const float* __restrict__ shift, const float* __restrict__ scale, int64_t mod_ld,
-    int batch, int rows_per_batch, int D, float eps, float* __restrict__ row_scale = nullptr) {
+__global__ __launch_bounds__(256) void layernorm_mod_kernel(const LnLaunch L, int D, float eps, float* __restrict__ row_scale = nullptr) {
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= batch * rows_per_batch) return;
-  const int b = row / rows_per_batch, r = row - b * rows_per_batch;
+  if (row >= L.rows) return;
+  const bool second = row >= L.rows0;                  // wave-uniform
+  const rt_ln_segment& sg = L.seg[second ? 1 : 0];
+  const void* __restrict__ x = sg.x;
+  bf16_t* __restrict__ out = reinterpret_cast<bf16_t*>(sg.out);
+  const float* __restrict__ shift = sg.shift;
+  const float* __restrict__ scale = sg.scale;
+  const int64_t ldx = sg.ldx, stride_xb = sg.stride_xb, ldo = sg.ldo, stride_ob = sg.stride_ob, mod_ld = sg.mod_ld;
+  const int rows_per_batch = sg.rows_per_batch;
+  const int srow = second ? row - L.rows0 : row;
+  const int b = srow / rows_per_batch, r = srow - b * rows_per_batch;
   float v[NCH][8];
   float s = 0.f;
 #pragma unroll
@@ -271,23 +285,7 @@ __global__ __launch_bounds__(256) void qk_rmsnorm_rope_kernel(
 #pragma unroll
   for (int v = 0; v < 2 * QK_HC; ++v) {
     const int h = hc * QK_HC + (v >> 1);
-    const u32x4 wu = (v & 1) ? wuk : wuq;
-    float x[8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { x[2 * i] = bf16lo(u[v][i]); x[2 * i + 1] = bf16hi(u[v][i]); }
-    float ss = 0.f;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ss += x[i] * x[i];
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-    const float r = rsqrtf(ss * (1.0f / 128.0f) + eps);
-    u32x4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const float a = x[2 * i] * r * bf16lo(wu[i]);
-      const float bq = x[2 * i + 1] * r * bf16hi(wu[i]);
-      o[i] = pack_bf16x2(a * cs[2 * i] - bq * sn[2 * i], bq * cs[2 * i + 1] + a * sn[2 * i + 1]);
-    }
+    const u32x4 o = rt_qk_norm_rope8(u[v], (v & 1) ? wuk : wuq, cs, sn, eps);
     if (h < H) *reinterpret_cast<u32x4*>(base + ((v & 1) ? k_off : q_off) + h * 128) = o;
   }
 }
@@ -506,9 +504,37 @@ __global__ void silu_split_kernel(const float* __restrict__ x, bf16_t* __restric
   }
 }
 
+// y[r][:] = (y[r][:] + a[r % B][:]) + b[r % B][:], 4 floats per thread (time_text_embed for all steps: (t + g) + p)
+__global__ void add_rows_f32_kernel(float* __restrict__ y, const float* __restrict__ a, const float* __restrict__ b, int rows, int B, int D4) {
+  const int64_t n = (int64_t)rows * D4;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / D4), c = (int)(i - (int64_t)r * D4);
+    const int64_t j = (int64_t)(r % B) * D4 + c;
+    f32x4 v = reinterpret_cast<const f32x4*>(y)[i] + reinterpret_cast<const f32x4*>(a)[j];
+    if (b) v += reinterpret_cast<const f32x4*>(b)[j];
+    reinterpret_cast<f32x4*>(y)[i] = v;
+  }
+}
+
 inline int grid_for(int64_t n, int block) {
   int64_t g = (n + block - 1) / block;
   return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
+
+int launch_layernorm(const LnLaunch& L, int x_f32, int D, float eps, void* stream) {
+  const dim3 grid((L.rows + 3) / 4), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const int nch = (D + 511) / 512;
+#define LN_LAUNCH(F32, N) hipLaunchKernelGGL((layernorm_mod_kernel<F32, N>), grid, block, 0, st, L, D, eps)
+  if (x_f32) {
+    if (nch <= 1) LN_LAUNCH(true, 1); else if (nch <= 2) LN_LAUNCH(true, 2); else if (nch <= 4) LN_LAUNCH(true, 4);
+    else if (nch <= 6) LN_LAUNCH(true, 6); else if (nch <= 8) LN_LAUNCH(true, 8); else LN_LAUNCH(true, 16);
+  } else {
+    if (nch <= 1) LN_LAUNCH(false, 1); else if (nch <= 2) LN_LAUNCH(false, 2); else if (nch <= 4) LN_LAUNCH(false, 4);
+    else if (nch <= 6) LN_LAUNCH(false, 6); else if (nch <= 8) LN_LAUNCH(false, 8); else LN_LAUNCH(false, 16);
+  }
+#undef LN_LAUNCH
+  return rt_hip_status();
 }
 
 }  // namespace
@@ -524,22 +550,27 @@ int rt_layernorm_modulate(const void* x, int64_t ldx, int64_t stride_xb, int32_t
   if (!RT_ALIGNED(x, 16) || !RT_ALIGNED(out, 16) || ldx % 8 || ldo % 8 || stride_xb % 8 || stride_ob % 8)
     return RT_E_ALIGN;
   if (scale && (!RT_ALIGNED(scale, 16) || !RT_ALIGNED(shift, 16) || mod_ld % 4)) return RT_E_ALIGN;
-  const int rows = batch * rows_per_batch;
-  const dim3 grid((rows + 3) / 4), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const int nch = (D + 511) / 512;
-#define LN_LAUNCH(F32, N)                                                                                         \
-  hipLaunchKernelGGL((layernorm_mod_kernel<F32, N>), grid, block, 0, st, x, ldx, stride_xb, (bf16_t*)out, ldo,   \
-                     stride_ob, shift, scale, mod_ld, batch, rows_per_batch, D, eps)
-  if (x_f32) {
-    if (nch <= 1) LN_LAUNCH(true, 1); else if (nch <= 2) LN_LAUNCH(true, 2); else if (nch <= 4) LN_LAUNCH(true, 4);
-    else if (nch <= 6) LN_LAUNCH(true, 6); else if (nch <= 8) LN_LAUNCH(true, 8); else LN_LAUNCH(true, 16);
-  } else {
-    if (nch <= 1) LN_LAUNCH(false, 1); else if (nch <= 2) LN_LAUNCH(false, 2); else if (nch <= 4) LN_LAUNCH(false, 4);
-    else if (nch <= 6) LN_LAUNCH(false, 6); else if (nch <= 8) LN_LAUNCH(false, 8); else LN_LAUNCH(false, 16);
+  LnLaunch L{};
+  L.seg[0] = rt_ln_segment{x, out, shift, scale, ldx, stride_xb, ldo, stride_ob, mod_ld, batch, rows_per_batch};
+  L.rows0 = L.rows = batch * rows_per_batch;
+  return launch_layernorm(L, x_f32, D, eps, stream);
+}
+
+int rt_layernorm_modulate_pair(const rt_ln_segment* segs, int32_t x_f32, int32_t D, float eps, void* stream) {
+  if (!segs || D < 8) return RT_E_BADARG;
+  if (D % 8 || D > 8192) return RT_E_SHAPE;
+  LnLaunch L{};
+  for (int i = 0; i < 2; ++i) {
+    const rt_ln_segment& g = segs[i];
+    if (!g.x || !g.out || g.batch < 1 || g.rows_per_batch < 1) return RT_E_BADARG;
+    if ((g.shift == nullptr) != (g.scale == nullptr)) return RT_E_BADARG;
+    if (!RT_ALIGNED(g.x, 16) || !RT_ALIGNED(g.out, 16) || g.ldx % 8 || g.ldo % 8 || g.stride_xb % 8 || g.stride_ob % 8) return RT_E_ALIGN;
+    if (g.scale && (!RT_ALIGNED(g.scale, 16) || !RT_ALIGNED(g.shift, 16) || g.mod_ld % 4)) return RT_E_ALIGN;
+    L.seg[i] = g;
   }
-#undef LN_LAUNCH
-  return rt_hip_status();
+  L.rows0 = segs[0].batch * segs[0].rows_per_batch;
+  L.rows = L.rows0 + segs[1].batch * segs[1].rows_per_batch;
+  return launch_layernorm(L, x_f32, D, eps, stream);
 }
 
 int rt_layernorm_modulate_fp8(const void* x, int64_t ldx, int64_t stride_xb, int32_t x_f32, void* out, int64_t ldo,
@@ -554,9 +585,11 @@ int rt_layernorm_modulate_fp8(const void* x, int64_t ldx, int64_t stride_xb, int
   const dim3 grid((rows + 3) / 4), block(256);
   hipStream_t st = (hipStream_t)stream;
   const int nch = (D + 511) / 512;
+  LnLaunch L{};
+  L.seg[0] = rt_ln_segment{x, out, shift, scale, ldx, stride_xb, ldo, stride_ob, mod_ld, batch, rows_per_batch};
+  L.rows0 = L.rows = rows;
 #define LN8_LAUNCH(F32, N)                                                                                        \
-  hipLaunchKernelGGL((layernorm_mod_kernel<F32, N, true>), grid, block, 0, st, x, ldx, stride_xb, (bf16_t*)out, ldo, \
-                     stride_ob, shift, scale, mod_ld, batch, rows_per_batch, D, eps, row_scale)
+  hipLaunchKernelGGL((layernorm_mod_kernel<F32, N, true>), grid, block, 0, st, L, D, eps, row_scale)
   if (x_f32) {
     if (nch <= 2) LN8_LAUNCH(true, 2); else if (nch <= 6) LN8_LAUNCH(true, 6); else LN8_LAUNCH(true, 16);
   } else {
@@ -625,6 +658,14 @@ int rt_gemv_bf16w(const float* x, int64_t ldx, const void* W, int64_t ldw, const
   hipLaunchKernelGGL(gemv_bf16w_kernel, dim3((N + rows_per_block - 1) / rows_per_block), dim3(256),
                      (size_t)B * K * 4, (hipStream_t)stream, x, ldx, (const bf16_t*)W, ldw, (const bf16_t*)bias, y,
                      ldy, B, N, K, silu_in, silu_out, accumulate);
+  return rt_hip_status();
+}
+
+int rt_add_rows_f32(float* y, const float* a, const float* b, int32_t rows, int32_t B, int32_t D, void* stream) {
+  if (!y || !a || rows < 1 || B < 1 || D < 4) return RT_E_BADARG;
+  if (D % 4) return RT_E_SHAPE;
+  if (!RT_ALIGNED(y, 16) || !RT_ALIGNED(a, 16) || (b && !RT_ALIGNED(b, 16))) return RT_E_ALIGN;
+  hipLaunchKernelGGL(add_rows_f32_kernel, dim3(grid_for((int64_t)rows * (D / 4), 256)), dim3(256), 0, (hipStream_t)stream, y, a, b, rows, B, D / 4);
   return rt_hip_status();
 }
 

@@ -53,6 +53,34 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// q/k RMSNorm(128) + interleaved-pair RoPE of the 8 elements one lane of a 16-lane group holds (elements 8·sub .. +7 of a head
+// vector; the group's 16 lanes are consecutive lanes of a wave). ONE definition for the stand-alone pass (norm_elem.hip,
+// qk_rmsnorm_rope_kernel) and the QKV GEMM's fused epilogue (gemm_bf16.hip), so the two give the same bits: per-lane sum of squares
+// in element order, xor 8,4,2,1 butterfly over the group, then scale, weight and rotate.
+// Which products are fused is spelled out (contraction off, explicit fma) instead of left to the compiler, which decides per call
+// site: the rotation is fma(a, cos, -(b·sin)) and fma(a, sin, b·cos) with the inner product rounded — what qk_rmsnorm_rope_kernel
+// has always computed — so results depend neither on the kernel the function is inlined into nor on the compiler's mood.
+__device__ __forceinline__ u32x4 rt_qk_norm_rope8(const u32x4 u, const u32x4 wu, const float (&cs)[8], const float (&sn)[8], float eps) {
+#pragma clang fp contract(off)
+  float x[8];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { x[2 * i] = bf16lo(u[i]); x[2 * i + 1] = bf16hi(u[i]); }
+  float ss = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ss += x[i] * x[i];
+#pragma unroll
+  for (int o = 8; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+  const float r = rsqrtf(__builtin_fmaf(ss, 1.0f / 128.0f, eps));
+  u32x4 o;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const float a = x[2 * i] * r * bf16lo(wu[i]);
+    const float bq = x[2 * i + 1] * r * bf16hi(wu[i]);
+    o[i] = pack_bf16x2(__builtin_fmaf(a, cs[2 * i], -(bq * sn[2 * i])), __builtin_fmaf(a, sn[2 * i + 1], bq * cs[2 * i + 1]));
+  }
+  return o;
+}
+
 static inline int rt_hip_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? RT_OK : (int)e;

@@ -31,6 +31,10 @@ BF16, F32 = torch.bfloat16, torch.float32
 # +1.9 % time per image (the GEMM epilogue and LayerNorm kernels take either dtype). RT_RESIDUAL_F32=0 selects bf16.
 RESIDUAL_F32 = os.environ.get("RT_RESIDUAL_F32", "1") == "1"
 
+# q/k RMSNorm + RoPE inside the QKV GEMM's epilogue (ops.QKRope) instead of a pass of its own over q and k: bf16 path, inner width a
+# multiple of 256, no IP-Adapter on the block (rt_ip_attention reads the raw q). Same bits either way; RT_FUSED_QK_ROPE=0 keeps the pass.
+FUSED_QK_ROPE = os.environ.get("RT_FUSED_QK_ROPE", "1") == "1"
+
 # The reference's bf16 run rounds the SCALARS that feed the sinusoidal embeddings: PIPE:1025 casts t to the latents' dtype,
 # PIPE:1048/1094 divide by 1000 in bf16 and CN:282-284 multiply by 1000 in bf16 again — t = 967.3 enters the embedding as 968,
 # guidance 3.5 as 3504. The default here (and in the oracle) is the exact fp32 value, i.e. the fp32 CPU run the parity target
@@ -269,13 +273,29 @@ def time_text_embed(tte, ws: Workspace, t1000: torch.Tensor, g1000: Optional[tor
     return ws.temb
 
 
-class EmbedScratch:
-    """The two [B,d] fp32 buffers time_text_embed needs, without a full Workspace."""
+def time_text_embed_all(tte, t1000_all: torch.Tensor, g1000: Optional[torch.Tensor], pooled: torch.Tensor, B: int) -> torch.Tensor:
+    """time_text_embed for every step of a schedule: fp32 [n·B, d], row i·B + b = step i, image b. t1000_all [n·B] in that order;
+    g1000 [B] / pooled [B,P] are the same at every step, so their MLPs run once and only the timestep MLP runs per step — all steps
+    in one batch of GEMV rows (a row's result does not depend on the rows it is launched with). Each row is (t + g) + p in fp32, the
+    order in which time_text_embed accumulates: the same bits."""
+    dev = pooled.device
+    d = tte.timestep_embedder.linear_2.weight.shape[0]
 
-    def __init__(self, B: int, d: int, device):
-        self.B = B
-        self.temb = torch.empty(B, d, device=device, dtype=F32)
-        self.tmp = torch.empty(B, d, device=device, dtype=F32)
+    def mlp(m, x_f32):
+        h = torch.empty(x_f32.shape[0], m.linear_1.weight.shape[0], device=dev, dtype=F32)
+        y = torch.empty(x_f32.shape[0], d, device=dev, dtype=F32)
+        ops.gemv(x_f32, m.linear_1.weight.data, m.linear_1.bias.data, h, silu_out=True)
+        ops.gemv(h, m.linear_2.weight.data, m.linear_2.bias.data, y)
+        return y
+
+    temb_all = mlp(tte.timestep_embedder, ops.timestep_embedding(t1000_all, 256))
+    pooled_f32 = pooled if pooled.dtype == F32 else ops.to_f32(pooled)
+    p = mlp(tte.text_embedder, pooled_f32.contiguous())
+    if g1000 is not None:
+        ops.add_rows_(temb_all, mlp(tte.guidance_embedder, ops.timestep_embedding(g1000, 256)), p)
+    else:
+        ops.add_rows_(temb_all, p)
+    return temb_all
 
 
 @dataclass
@@ -305,21 +325,33 @@ class ModulationTable:
             return torch.empty(M, w.shape[0], device=dev, dtype=F32)
 
         self.double, self.single, self.out = [], [], None
+        # M <= 32 rows with K % 256 == 0 (28 steps at batch 1): the skinny kernel streams each weight once for both terms, one launch
+        # per block; otherwise the general GEMM, two launches (hi, then lo accumulated onto it). The two give the same bits.
+        skinny = M <= 32 and temb_all.shape[1] % 256 == 0 and all(w.shape[0] % 16 == 0 for w in self._widths(doubles, singles, out_lin))
+
+        def table(problems):
+            if skinny:
+                ops.linear_skinny(hi, lo, problems)
+            else:
+                ops.linear_grouped([P(hi, w, o, bias=b) for w, b, o in problems])
+                ops.linear_grouped([P(lo, w, o, res=o) for w, b, o in problems])
+
         for pl in doubles:
             oi, ot = out_buf(pl.ada_img_w), out_buf(pl.ada_txt_w)
-            ops.linear_grouped([P(hi, pl.ada_img_w, oi, bias=pl.ada_img_b), P(hi, pl.ada_txt_w, ot, bias=pl.ada_txt_b)])
-            ops.linear_grouped([P(lo, pl.ada_img_w, oi, res=oi), P(lo, pl.ada_txt_w, ot, res=ot)])
+            table([(pl.ada_img_w, pl.ada_img_b, oi), (pl.ada_txt_w, pl.ada_txt_b, ot)])
             self.double.append((oi, ot))
         for pl in singles:
             o = out_buf(pl.ada_w)
-            ops.linear(hi, pl.ada_w, o, bias=pl.ada_b)
-            ops.linear(lo, pl.ada_w, o, res=o)
+            table([(pl.ada_w, pl.ada_b, o)])
             self.single.append(o)
         if out_lin is not None:
             o = out_buf(out_lin.weight.data)
-            ops.linear(hi, out_lin.weight.data, o, bias=out_lin.bias.data)
-            ops.linear(lo, out_lin.weight.data, o, res=o)
+            table([(out_lin.weight.data, out_lin.bias.data, o)])
             self.out = o
+
+    @staticmethod
+    def _widths(doubles, singles, out_lin):
+        return [w for pl in doubles for w in (pl.ada_img_w, pl.ada_txt_w)] + [pl.ada_w for pl in singles] + ([out_lin.weight.data] if out_lin is not None else [])
 
     def step(self, i: int) -> StepMods:
         r = slice(i * self.B, (i + 1) * self.B)
@@ -345,6 +377,7 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         ops.gemv(temb, pl.ada_txt_w, pl.ada_txt_b, mt, silu_in=True)
     ch = lambda m, i: m[:, i * d : (i + 1) * d]
     fp8 = pl.qkv_img_w8 is not None
+    fused_rope = False
     if fp8:
         xn8 = ws.fp8_buffers()
         xn8_t, xn8_i = xn8[:, :T], xn8[:, T:]
@@ -355,9 +388,11 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         ops.linear_grouped([P(xn8_i, pl.qkv_img_w8, ws.qkv[:, T:], bias=pl.qkv_img_b, a_scale=ws.xs_i, w_scale=pl.qkv_img_ws),
                             P(xn8_t, pl.qkv_txt_w8, ws.qkv[:, :T], bias=pl.qkv_txt_b, a_scale=ws.xs_t, w_scale=pl.qkv_txt_ws)])
     else:
-        ops.layernorm_modulate(x_i, xn_i, ch(mi, 0), ch(mi, 1))
-        ops.layernorm_modulate(x_t, xn_t, ch(mt, 0), ch(mt, 1))
-        ops.linear_grouped([P(xn_i, pl.qkv_img_w, ws.qkv[:, T:], bias=pl.qkv_img_b), P(xn_t, pl.qkv_txt_w, ws.qkv[:, :T], bias=pl.qkv_txt_b)])
+        ops.layernorm_modulate_pair(x_i, xn_i, ch(mi, 0), ch(mi, 1), x_t, xn_t, ch(mt, 0), ch(mt, 1))
+        fused_rope = FUSED_QK_ROPE and ip is None and not pl.fp8_attention and ops.QKRope.covers(d)
+        ri = ops.QKRope(0, d, d, pl.nq_img, pl.nk_img, cos, sin, pos0=T) if fused_rope else None
+        rt = ops.QKRope(0, d, d, pl.nq_txt, pl.nk_txt, cos, sin, pos0=0) if fused_rope else None
+        ops.linear_grouped([P(xn_i, pl.qkv_img_w, ws.qkv[:, T:], bias=pl.qkv_img_b, rope=ri), P(xn_t, pl.qkv_txt_w, ws.qkv[:, :T], bias=pl.qkv_txt_b, rope=rt)])
     q, k, v = ws.qkv[..., :d], ws.qkv[..., d : 2 * d], ws.qkv[..., 2 * d :]
     if ip is not None:
         # the raw image query is only here: qk_rmsnorm_rope works in place and the attention output overwrites q
@@ -376,7 +411,8 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
             ops.attention_fp8(qk8, vt8, q, H)
     else:
         # 4.-5. RMSNorm(q,k) + RoPE in place; 6. joint attention; output over q
-        ops.qk_rmsnorm_rope(ws.qkv, 0, d, H, T, pl.nq_txt, pl.nk_txt, pl.nq_img, pl.nk_img, cos, sin)
+        if not fused_rope:
+            ops.qk_rmsnorm_rope(ws.qkv, 0, d, H, T, pl.nq_txt, pl.nk_txt, pl.nq_img, pl.nk_img, cos, sin)
         ops.attention(q, k, v, q, H)
     # 7./8. x += gate_msa * out_proj(attn)
     if pl.mx:
@@ -403,8 +439,7 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         ops.linear_grouped([P(xn8_i, pl.ff1_img_w8, ws.ffh[:, T:], bias=pl.ff1_img_b, gelu_from=0, a_scale=ws.xs_i, w_scale=pl.ff1_img_ws, **o8(T, ws.S)),
                             P(xn8_t, pl.ff1_txt_w8, ws.ffh[:, :T], bias=pl.ff1_txt_b, gelu_from=0, a_scale=ws.xs_t, w_scale=pl.ff1_txt_ws, **o8(0, T))])
     else:
-        ops.layernorm_modulate(x_i, xn_i, ch(mi, 3), ch(mi, 4))
-        ops.layernorm_modulate(x_t, xn_t, ch(mt, 3), ch(mt, 4))
+        ops.layernorm_modulate_pair(x_i, xn_i, ch(mi, 3), ch(mi, 4), x_t, xn_t, ch(mt, 3), ch(mt, 4))
         ops.linear_grouped([P(xn_i, pl.ff1_img_w, ws.ffh[:, T:], bias=pl.ff1_img_b, gelu_from=0),
                             P(xn_t, pl.ff1_txt_w, ws.ffh[:, :T], bias=pl.ff1_txt_b, gelu_from=0)])
     if pl.mx:
@@ -434,6 +469,7 @@ def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         m = ws.mod_a[:, : 3 * d]
         ops.gemv(temb, pl.ada_w, pl.ada_b, m, silu_in=True)                   # shift, scale, gate
     big = ws.big
+    fused_rope = False
     if pl.fused_w8 is not None:
         xn8 = ws.fp8_buffers()
         ops.layernorm_modulate_fp8(ws.x, xn8, ws.xs_all, m[:, :d], m[:, d : 2 * d])
@@ -442,7 +478,9 @@ def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         ops.linear(xn8, pl.fused_w8, big, bias=pl.fused_b, gelu_from=3 * d, a_scale=ws.xs_all, w_scale=pl.fused_ws, **o8)
     else:
         ops.layernorm_modulate(ws.x, ws.xn, m[:, :d], m[:, d : 2 * d])
-        ops.linear(ws.xn, pl.fused_w, big, bias=pl.fused_b, gelu_from=3 * d)    # [k|v|q|gelu(mlp)]
+        fused_rope = FUSED_QK_ROPE and not pl.fp8_attention and ops.QKRope.covers(d)
+        ops.linear(ws.xn, pl.fused_w, big, bias=pl.fused_b, gelu_from=3 * d,    # [k|v|q|gelu(mlp)]
+                   rope=ops.QKRope(2 * d, 0, d, pl.nq, pl.nk, cos, sin) if fused_rope else None)
     q = big[..., 2 * d : 3 * d]
     if pl.fp8_attention:
         qk8, vt8 = ws.fp8_attn_buffers(H)
@@ -452,7 +490,8 @@ def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         else:
             ops.attention_fp8(qk8, vt8, q, H)
     else:
-        ops.qk_rmsnorm_rope(big, 2 * d, 0, H, 0, None, None, pl.nq, pl.nk, cos, sin)
+        if not fused_rope:
+            ops.qk_rmsnorm_rope(big, 2 * d, 0, H, 0, None, None, pl.nq, pl.nk, cos, sin)
         ops.attention(q, big[..., :d], big[..., d : 2 * d], q, H)
     if pl.mx:
         a8, sc = ws.fp8_wide(5 * d), ws.mx_scales()

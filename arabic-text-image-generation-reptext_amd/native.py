@@ -15,7 +15,7 @@ LIB_NAME = "librt_reptext_hip.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 RT_GEMM_MAX_GROUPS = 4
-ABI_VERSION = 11
+ABI_VERSION = 12
 RT_LORA_MAX_TERMS = 8
 
 
@@ -50,7 +50,24 @@ class GemmGroup(C.Structure):
         ("c8_from", C.c_int32), ("c_bscale_k0", C.c_int32),
         ("conv_ks", C.c_int32), ("conv_cin", C.c_int32), ("conv_w2", C.c_int32), ("conv_h2", C.c_int32),
         ("conv_inv_w2", C.c_float), ("conv_inv_h2", C.c_float),
+        ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p), ("rope_wq", C.c_void_p), ("rope_wk", C.c_void_p),
+        ("rope_q0", C.c_int32), ("rope_k0", C.c_int32), ("rope_w", C.c_int32), ("rope_pos0", C.c_int32),
+        ("rope_eps", C.c_float), ("rope_reserved", C.c_int32),
     ]
+
+
+class SkinnyGroup(C.Structure):
+    """Mirror of ``rt_skinny_group`` (include/reptext_hip.h): one problem of rt_gemm_skinny_bf16."""
+
+    _fields_ = [("W", C.c_void_p), ("bias", C.c_void_p), ("C", C.c_void_p), ("ldw", C.c_int64), ("ldc", C.c_int64), ("N", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LnSegment(C.Structure):
+    """Mirror of ``rt_ln_segment`` (include/reptext_hip.h): one row segment of rt_layernorm_modulate_pair."""
+
+    _fields_ = [("x", C.c_void_p), ("out", C.c_void_p), ("shift", C.c_void_p), ("scale", C.c_void_p),
+                ("ldx", C.c_int64), ("stride_xb", C.c_int64), ("ldo", C.c_int64), ("stride_ob", C.c_int64), ("mod_ld", C.c_int64),
+                ("batch", C.c_int32), ("rows_per_batch", C.c_int32)]
 
 
 class LoraTerm(C.Structure):
@@ -124,6 +141,11 @@ SIGNATURES["rt_lora_merge_bf16"] = [C.POINTER(LoraTerm), _i32, _vp, _i64, _vp, _
 
 # IP-Adapter cross-attention (csrc/ip_attention.hip)
 SIGNATURES["rt_ip_attention"] = [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp]
+
+# loop passes that moved out of the 256x256-tile GEMM / were merged (csrc/gemm_skinny.hip, csrc/norm_elem.hip)
+SIGNATURES["rt_gemm_skinny_bf16"] = [_vp, _vp, _i64, _i32, _i32, C.POINTER(SkinnyGroup), _i32, _vp]
+SIGNATURES["rt_layernorm_modulate_pair"] = [C.POINTER(LnSegment), _i32, _i32, _f32, _vp]
+SIGNATURES["rt_add_rows_f32"] = [_vp, _vp, _vp, _i32, _i32, _i32, _vp]
 
 # entries that do not return a status code
 RESTYPES = {"rt_canny_ws_bytes": C.c_int64, "rt_groupnorm_ws_bytes": C.c_int64, "rt_attention_fp8_vt_bytes": C.c_int64, "rt_attention_ws_bytes": C.c_int64}

@@ -116,6 +116,27 @@ class BlockScales:
 
 
 @dataclass
+class QKRope:
+    """Fused q/k RMSNorm + RoPE of a bf16 LinearProblem (rt_gemm_group::rope_*): columns [q0, q0+width) and [k0, k0+width) of out
+    leave the GEMM as qk_rmsnorm_rope would rewrite them. wq / wk bf16 [128] = the norm weights of this problem's rows; cos / sin f32
+    [positions,128]; pos0 = table row of the problem's row 0 in a batch entry. q0, k0, width % 256 == 0."""
+
+    q0: int
+    k0: int
+    width: int
+    wq: torch.Tensor
+    wk: torch.Tensor
+    cos: torch.Tensor
+    sin: torch.Tensor
+    pos0: int = 0
+    eps: float = 1e-6
+
+    @staticmethod
+    def covers(width: int) -> bool:
+        return width % 256 == 0
+
+
+@dataclass
 class LinearProblem:
     """One group of rt_gemm_bf16: out = epilogue(a @ w.T + bias).
 
@@ -144,6 +165,7 @@ class LinearProblem:
     out8: Optional[torch.Tensor] = None
     out8_scales: Optional[BlockScales] = None
     out8_from: int = 0
+    rope: Optional[QKRope] = None       # bf16 problems: fused q/k RMSNorm + RoPE
 
     @property
     def is_fp8(self) -> bool:
@@ -218,6 +240,18 @@ class LinearProblem:
             elif rsc.numel() != rows or not rsc.is_contiguous():
                 raise ValueError("rowscale must be contiguous with rows_per_batch (or M) elements, or [batch, rows]")
             g.rowscale = _dev(rsc, "rowscale", F32)
+        if self.rope is not None:
+            r = self.rope
+            if self.is_fp8:
+                raise TypeError("the fused q/k RMSNorm + RoPE belongs to bf16 problems")
+            if r.cos.shape != r.sin.shape or r.cos.dim() != 2 or r.cos.shape[1] != 128 or not r.cos.is_contiguous() or not r.sin.is_contiguous() \
+                    or r.cos.shape[0] < r.pos0 + (rpb if rpb > 0 else M):
+                raise ValueError("rope: cos/sin must be contiguous [positions,128] covering pos0 + rows")
+            if r.wq.numel() != 128 or r.wk.numel() != 128:
+                raise ValueError("rope: norm weights must have 128 elements")
+            g.rope_cos, g.rope_sin = _dev(r.cos, "cos", F32), _dev(r.sin, "sin", F32)
+            g.rope_wq, g.rope_wk = _dev(r.wq, "wq", BF16), _dev(r.wk, "wk", BF16)
+            g.rope_q0, g.rope_k0, g.rope_w, g.rope_pos0, g.rope_eps = int(r.q0), int(r.k0), int(r.width), int(r.pos0), float(r.eps)
         g.rows_per_batch = rpb
         g.gelu_from = N if self.gelu_from is None else int(self.gelu_from)
         g.alpha = float(self.alpha)
@@ -244,6 +278,36 @@ def linear(a, w, out, **kw) -> torch.Tensor:
     return out
 
 
+def linear_skinny(hi: torch.Tensor, lo: torch.Tensor, problems: Sequence[tuple]) -> None:
+    """out = lo @ w.T + (hi @ w.T + bias) for up to two (w, bias, out) problems that share hi / lo [M,K] bf16 (M <= 32), out f32
+    [M,N]: ONE launch that streams every weight once; bit-identical to linear(hi, w, out, bias=bias); linear(lo, w, out, res=out)."""
+    M, K, lda = _rowmajor2d(hi, "hi")
+    if lo.shape != hi.shape or lo.stride() != hi.stride():
+        raise ValueError("hi / lo must have the same shape and strides")
+    n = len(problems)
+    if not 1 <= n <= 2:
+        raise ValueError("1..2 problems per launch")
+    arr = (native.SkinnyGroup * n)()
+    for g, (w, bias, out) in zip(arr, problems):
+        N, Kw, ldw = _rowmajor2d(w, "w")
+        Mo, No, ldc = _rowmajor2d(out, "out")
+        if Kw != K or Mo != M or No != N or (bias is not None and bias.numel() != N):
+            raise ValueError(f"linear_skinny shapes mismatch: hi{tuple(hi.shape)} w{tuple(w.shape)} out{tuple(out.shape)}")
+        g.W, g.bias, g.C = _dev(w, "w", BF16), _opt(bias, "bias", BF16), _dev(out, "out", F32)
+        g.ldw, g.ldc, g.N = ldw, ldc, N
+    native.check("rt_gemm_skinny_bf16", native.load().rt_gemm_skinny_bf16(_dev(hi, "hi", BF16), _dev(lo, "lo", BF16), lda, M, K, arr, n, _stream()))
+
+
+def add_rows_(y: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """y[r] = (y[r] + a[r % B]) + b[r % B] in place; y f32 [rows,D], a / b f32 [B,D], all contiguous."""
+    rows, D = y.shape
+    B = a.shape[0]
+    if not y.is_contiguous() or not a.is_contiguous() or a.shape[1] != D or (b is not None and (b.shape != a.shape or not b.is_contiguous())):
+        raise ValueError("add_rows_: y [rows,D], a / b [B,D], contiguous")
+    native.check("rt_add_rows_f32", native.load().rt_add_rows_f32(_dev(y, "y", F32), _dev(a, "a", F32), _opt(b, "b", F32), rows, B, D, _stream()))
+    return y
+
+
 def gemv(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, *, silu_in=False,
          silu_out=False, accumulate=False) -> torch.Tensor:
     """out[b,n] (+)= post(sum_k pre(x[b,k]) w[n,k] + bias[n]); x,out f32, w,bias bf16."""
@@ -253,7 +317,7 @@ def gemv(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: to
     if Kw != K or Bo != B or No != N:
         raise ValueError("gemv shapes mismatch")
     lib = native.load()
-    step = 4
+    step = max(1, min(8, 16384 // K))      # rt_gemv_bf16w: at most 8 rows and 64 KiB of staged fp32 activations per launch; rows are independent
     for b0 in range(0, B, step):
         nb = min(step, B - b0)
         native.check("rt_gemv_bf16w", lib.rt_gemv_bf16w(
@@ -297,6 +361,26 @@ def layernorm_modulate(x: torch.Tensor, out: torch.Tensor, shift: Optional[torch
         _dev(x, "x"), x.stride(1), x.stride(0), int(x.dtype == F32), _dev(out, "out", BF16), out.stride(1), out.stride(0),
         _opt(shift, "shift", F32), _opt(scale, "scale", F32), mod_ld, B, R, D, float(eps), _stream()))
     return out
+
+
+def layernorm_modulate_pair(x0, out0, shift0, scale0, x1, out1, shift1, scale1, eps: float = 1e-6) -> None:
+    """layernorm_modulate(x0, out0, shift0, scale0) and layernorm_modulate(x1, out1, shift1, scale1) as ONE launch (the image rows and
+    the text rows of a double block): same dtype of x and same D, everything else per segment. Bit-identical to the two calls."""
+    segs = (native.LnSegment * 2)()
+    D = x0.shape[2]
+    for g, (x, out, shift, scale) in zip(segs, ((x0, out0, shift0, scale0), (x1, out1, shift1, scale1))):
+        if x.dim() != 3 or out.dim() != 3 or x.shape != out.shape or x.stride(2) != 1 or out.stride(2) != 1 or x.shape[2] != D or x.dtype != x0.dtype:
+            raise ValueError("layernorm_modulate_pair: x/out must be [B,R,D] with unit inner stride, one D and one dtype of x")
+        B, R, _ = x.shape
+        if scale is not None:
+            if scale.shape != (B, D) or shift.shape != (B, D) or scale.stride(1) != 1 or shift.stride(1) != 1 or scale.stride(0) != shift.stride(0):
+                raise ValueError("shift/scale must be [B,D] views with equal row stride")
+            g.mod_ld = scale.stride(0)
+        g.x, g.out, g.shift, g.scale = _dev(x, "x"), _dev(out, "out", BF16), _opt(shift, "shift", F32), _opt(scale, "scale", F32)
+        g.ldx, g.stride_xb, g.ldo, g.stride_ob, g.batch, g.rows_per_batch = x.stride(1), x.stride(0), out.stride(1), out.stride(0), B, R
+    if x0.dtype not in (BF16, F32):
+        raise TypeError("x must be bf16 or f32")
+    native.check("rt_layernorm_modulate_pair", native.load().rt_layernorm_modulate_pair(segs, int(x0.dtype == F32), D, float(eps), _stream()))
 
 
 def layernorm_modulate_fp8(x: torch.Tensor, out: torch.Tensor, row_scale: torch.Tensor, shift: Optional[torch.Tensor],

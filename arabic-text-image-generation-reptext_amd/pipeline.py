@@ -685,7 +685,7 @@ class FluxControlNetPipeline:
                         bool(getattr(m, "_fp8_attention", False))) for m in (self.transformer, self.controlnet) if m is not None)
         key = (sig(latents), sig(prompt_embeds), sig(pooled), sig(text_ids), sig(image_ids), tuple(sig(h) for h in hints), tuple(sig(m) for m in masks),
                tuple(tvals), tuple(self.scheduler.sigmas.tolist()), float(guidance_scale), repr(cn_scale), int(cn_steps), int(num_inference_steps),
-               str(latents.device), models, bool(self.reference_bf16_scalars), bool(_mm.RESIDUAL_F32), bool(OVERLAP_TOWER))
+               str(latents.device), models, bool(self.reference_bf16_scalars), bool(_mm.RESIDUAL_F32), bool(OVERLAP_TOWER), bool(_mm.FUSED_QK_ROPE))
         if ipe is not None:
             # the embeds are one more static input of the graph; the per-block scales are kernel scalars baked into the capture
             adapter = self.transformer._ip_adapter

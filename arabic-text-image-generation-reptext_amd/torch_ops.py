@@ -72,10 +72,15 @@ def enable_dispatch(on: bool = True) -> None:
     """Route the model code's calls of the registered kernels through torch.ops.reptext_amd.* (True) or straight to ctypes."""
     t = torch.ops.reptext_amd
     if on:
-        ops.linear = lambda a, w, out, bias=None, gate=None, res=None, add2=None, rowscale=None, rows_per_batch=0, gelu_from=None, alpha=1.0, **kw: \
-            (_direct["linear"](a, w, out, bias=bias, gate=gate, res=res, add2=add2, rowscale=rowscale, rows_per_batch=rows_per_batch,
-                               gelu_from=gelu_from, alpha=alpha, **kw) if (rows_per_batch or kw) else
-             t.linear(a, w, out, bias, gate, res, add2, rowscale, -1 if gelu_from is None else int(gelu_from), float(alpha))) or out
+        def linear(a, w, out, bias=None, gate=None, res=None, add2=None, rowscale=None, rows_per_batch=0, gelu_from=None, alpha=1.0, **kw):
+            if rows_per_batch or any(v is not None for v in kw.values()):
+                # forms the registered operator's schema does not carry (e4m3 scales, the fused q/k step): straight to ctypes
+                return _direct["linear"](a, w, out, bias=bias, gate=gate, res=res, add2=add2, rowscale=rowscale, rows_per_batch=rows_per_batch,
+                                         gelu_from=gelu_from, alpha=alpha, **kw)
+            t.linear(a, w, out, bias, gate, res, add2, rowscale, -1 if gelu_from is None else int(gelu_from), float(alpha))
+            return out
+
+        ops.linear = linear
         ops.attention = lambda q, k, v, out, H, scale=None, split=True: (t.attention(q, k, v, out, H, 0.0 if scale is None else float(scale)) if split
                                                                           else _direct["attention"](q, k, v, out, H, scale, split=False)) or out
         ops.layernorm_modulate = lambda x, out, shift, scale, eps=1e-6: t.layernorm_modulate(x, out, shift, scale, eps) or out

@@ -254,19 +254,24 @@ class _MMDiTBase(nn.Module, WeightsIO):
             self._rope_cache[key] = hit + (txt_ids, img_ids)   # keep the id tensors alive so data_ptr stays unique
         return hit[0], hit[1]
 
-    def _temb(self, ws, timestep, guidance, pooled):
+    def _embed_scalars(self, B, timestep, guidance):
+        """(t·1000 [len(timestep) or B], g·1000 [B] or None) as fp32, the inputs of the sinusoidal embeddings (CN:282-284)."""
         ref16 = mmdit.REF_BF16_SCALARS
         t1000 = mmdit.bf16_round_trip_x1000(timestep.reshape(-1)) if ref16 else timestep.to(torch.float32).reshape(-1) * 1000.0
-        if t1000.numel() == 1 and ws.B > 1:
-            t1000 = t1000.expand(ws.B)
+        if t1000.numel() == 1 and B > 1:
+            t1000 = t1000.expand(B)
         g1000 = None
         if self.config.guidance_embeds:
             if guidance is None:
                 raise ValueError("guidance_embeds=True requires `guidance`")
             g1000 = (mmdit.bf16_round_trip_x1000(guidance.reshape(-1)) if ref16 else guidance.to(torch.float32).reshape(-1) * 1000.0).contiguous()
-            if g1000.numel() == 1 and ws.B > 1:
-                g1000 = g1000.expand(ws.B).contiguous()
-        return mmdit.time_text_embed(self.time_text_embed, ws, t1000.contiguous(), g1000, pooled)
+            if g1000.numel() == 1 and B > 1:
+                g1000 = g1000.expand(B).contiguous()
+        return t1000.contiguous(), g1000
+
+    def _temb(self, ws, timestep, guidance, pooled):
+        t1000, g1000 = self._embed_scalars(ws.B, timestep, guidance)
+        return mmdit.time_text_embed(self.time_text_embed, ws, t1000, g1000, pooled)
 
     def prepare_static(self, encoder_hidden_states: torch.Tensor, controlnet_cond: Optional[torch.Tensor] = None) -> StaticEmbeds:
         """See StaticEmbeds. ``controlnet_cond`` [Bc,N,in+extra] only for models that own a ``controlnet_x_embedder``."""
@@ -291,11 +296,12 @@ class _MMDiTBase(nn.Module, WeightsIO):
         doubles, singles = self._ensure_plans()
         B, d = pooled.shape[0], self.inner_dim
         dev = pooled.device
-        sc = mmdit.EmbedScratch(B, d, dev)
-        temb_all = torch.empty(len(timesteps) * B, d, device=dev, dtype=torch.float32)
-        for i, t in enumerate(timesteps):
-            ts = torch.full((B,), float(t), device=dev, dtype=torch.float32)
-            temb_all[i * B : (i + 1) * B].copy_(self._temb(sc, ts, guidance, pooled))
+        # guidance and pooled text are the same at every step: their MLPs run once, the timestep MLP for all steps at once
+        ts = torch.empty(len(timesteps) * B, device=dev, dtype=torch.float32)
+        for i, t in enumerate(timesteps):                    # device fills (no host copy: this runs inside the loop's graph capture)
+            ts[i * B : (i + 1) * B].fill_(float(t))
+        t1000, g1000 = self._embed_scalars(B, ts, guidance)
+        temb_all = mmdit.time_text_embed_all(self.time_text_embed, t1000, g1000, pooled, B)
         return mmdit.ModulationTable(temb_all, len(timesteps), B, doubles, singles, getattr(self, "norm_out", None) and self.norm_out.linear)
 
     @classmethod

@@ -109,9 +109,44 @@ typedef struct rt_gemm_group {
    * conv_inv_w2 / conv_inv_h2 are filled in by the library. */
   int32_t conv_ks, conv_cin, conv_w2, conv_h2;
   float conv_inv_w2, conv_inv_h2;
+  /* Fused q/k RMSNorm + RoPE (ABI 12; rt_gemm_bf16, bf16 C): rope_cos != NULL makes the tiles whose columns lie in
+   * [rope_q0, rope_q0 + rope_w) or [rope_k0, rope_k0 + rope_w) leave the epilogue as rt_qk_rmsnorm_rope would rewrite them:
+   * the bf16 value bf16(acc + bias) of a 256x256 tile goes through LDS, then every 128-column head of a row is RMS-normalised with
+   * rope_wq / rope_wk (bf16 [128], the norm weights of THIS group's rows) and rotated with cos/sin row rope_pos0 + m (m = row in the
+   * batch entry; rope_pos0 = 0 for text rows and single blocks, T for the image rows of a double block). Bit-identical to the GEMM
+   * followed by rt_qk_rmsnorm_rope (one shared device function); saves that pass's read and write of q and k (A.1 steps 3,5; A.2).
+   * rope_q0 / rope_k0 / rope_w % 256 == 0, ranges inside N and disjoint, gelu_from >= their ends, no gate / res / add2 / rowscale,
+   * alpha == 1, C 16-byte aligned with ldc, strideC % 8 == 0; cos / sin / weights 16-byte aligned. All-zero = no fused step. */
+  const float* rope_cos;  /* f32 [positions][128] */
+  const float* rope_sin;
+  const void* rope_wq;    /* bf16 [128] */
+  const void* rope_wk;
+  int32_t rope_q0, rope_k0, rope_w, rope_pos0;
+  float rope_eps;
+  int32_t rope_reserved;  /* 0 */
 } rt_gemm_group;
 
 int rt_gemm_bf16(const rt_gemm_group* groups /* host */, int32_t ngroups, void* stream);
+
+/* Skinny linear for the adaLN tables (ABI 12; csrc/gemm_skinny.hip): M <= 32 activation rows given as the two-term bf16 split
+ * hi + lo of an fp32 vector (rt_silu_split_bf16), up to two problems that share them:
+ *   C[m][n] = lo[m]·W[n] + (hi[m]·W[n] + bias[n])        C f32 [M][ldc], W bf16 [N][ldw], bias bf16 [N] or NULL
+ * Every W fragment is loaded once and used for both products; one wave per 16 output columns, so N is spread over all CUs.
+ * Bit-identical to rt_gemm_bf16 {A = hi, bias, out_f32} followed by rt_gemm_bf16 {A = lo, res = C, out_f32}: same MFMA, operand
+ * roles and K order, one accumulator chain per product, the same epilogue operations. Replaces those pairs in
+ * mmdit.ModulationTable (AdaLayerNormZero/ZeroSingle/Continuous `linear(silu(temb))` for all steps at once; A.1 step 1, A.2, A.3).
+ * Rejected on the host: null hi / lo / groups / W / C, ngroups outside 1..2, M < 1 (RT_E_BADARG); M > 32, K % 256, N % 16,
+ * lda / ldw < K, ldc < N (RT_E_SHAPE); hi / lo / W / C not 16-byte aligned, bias not 8-byte aligned, lda / ldw % 8, ldc % 4 (RT_E_ALIGN). */
+typedef struct rt_skinny_group {
+  const void* W;        /* bf16 [N][ldw]   */
+  const void* bias;     /* bf16 [N] or NULL */
+  float* C;             /* f32 [M][ldc]    */
+  int64_t ldw, ldc;
+  int32_t N;
+  int32_t reserved;     /* 0 */
+} rt_skinny_group;
+int rt_gemm_skinny_bf16(const void* hi, const void* lo, int64_t lda, int32_t M, int32_t K,
+                        const rt_skinny_group* groups /* host */, int32_t ngroups, void* stream);
 
 /* Same contraction and epilogue on v_mfma_scale_f32_16x16x128_f8f6f4 (e4m3 x e4m3, fp32 accumulate, block scales fixed to
  * 1.0): BASELINE config 5 ("fp8 weights"), the projections fed by LayerNorm (to_q/k/v, add_*_proj, ff.net.0, proj_mlp).
@@ -140,6 +175,11 @@ int rt_gemv_bf16w(const float* x, int64_t ldx, const void* W, int64_t ldw, const
                   float* y, int64_t ldy, int32_t B, int32_t N, int32_t K,
                   int32_t silu_in, int32_t silu_out, int32_t accumulate, void* stream);
 
+/* y[r][:] = (y[r][:] + a[r % B][:]) + b[r % B][:] in fp32, rows r < rows, D % 4 == 0 (ABI 12). b may be NULL (one term). Adds the
+ * step-invariant guidance and pooled-text embeddings (B rows each, computed once) to the timestep embeddings of every step in the
+ * order CombinedTimestepGuidanceTextProjEmbeddings adds them (A.5: (t + g) + p). y / a / b contiguous rows of D, 16-byte aligned. */
+int rt_add_rows_f32(float* y, const float* a, const float* b, int32_t rows, int32_t B, int32_t D, void* stream);
+
 /* Timesteps(256, flip_sin_to_cos=True, shift 0): out[b] = [cos(t·f_j) | sin(t·f_j)], f_j = exp(-ln(1e4)·j/half).
  * A.5; feeds CN:287-291. t is already multiplied by 1000 by the caller (CN:282-284). */
 int rt_timestep_embedding(const float* t, float* out, int32_t B, int32_t dim, void* stream);
@@ -157,6 +197,19 @@ int rt_layernorm_modulate(const void* x, int64_t ldx, int64_t stride_xb, int32_t
                           void* out, int64_t ldo, int64_t stride_ob,
                           const float* shift, const float* scale, int64_t mod_ld,
                           int32_t batch, int32_t rows_per_batch, int32_t D, float eps, void* stream);
+/* Two row segments in ONE launch (ABI 12): segment i is what rt_layernorm_modulate computes for its own x / out / shift / scale,
+ * leading dimensions and row count; a row's arithmetic is the same, so the result is bit-identical to two calls. Both segments
+ * share x_f32, D and eps. Serves the image rows + text rows of a double block's norm1 / norm2 (A.1 steps 2, 7), whose text-row
+ * launch alone is at the kernel's latency floor. */
+typedef struct rt_ln_segment {
+  const void* x;        /* bf16|f32 [batch][rows_per_batch][ldx] */
+  void* out;            /* bf16 [batch][rows_per_batch][ldo]     */
+  const float* shift;   /* f32 [batch][mod_ld] or NULL (then scale NULL too) */
+  const float* scale;
+  int64_t ldx, stride_xb, ldo, stride_ob, mod_ld;
+  int32_t batch, rows_per_batch;
+} rt_ln_segment;
+int rt_layernorm_modulate_pair(const rt_ln_segment* segs /* host[2] */, int32_t x_f32, int32_t D, float eps, void* stream);
 /* Same, quantising the modulated row to e4m3 on the way out: out bytes [rows][ldo] and row_scale f32 [batch*rows_per_batch]
  * (= max|y| / 448 of that row), the A operand and a_scale of rt_gemm_fp8. One HBM read of x, half the write bytes. */
 int rt_layernorm_modulate_fp8(const void* x, int64_t ldx, int64_t stride_xb, int32_t x_f32,

@@ -1,5 +1,5 @@
 """Kernel micro-benchmarks at the C2 shapes (1024², S=4608, d=3072). Run on the GPU box:
-    python tools/bench_kernels.py [gemm|shapes|fp8|attn|attn8|elem|all]
+    python tools/bench_kernels.py [gemm|shapes|fp8|attn|attn8|elem|passes|all]
 Prints TFLOP/s from torch.cuda.Event timing on the current stream (same stream the kernels are enqueued on)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -145,6 +145,81 @@ def bench_elem():
     print(f"qk_rmsnorm_rope {S}x{2*d}: {t*1e6:8.1f} us  {2*S*2*d*2/t/1e9:8.1f} GB/s", flush=True)
 
 
+def bench_loop_passes(rounds=5):
+    """The loop's small passes, new form against the launches it replaces, alternating in one process. The adaLN weights rotate over
+    enough distinct copies (> 256 MiB) that every launch streams them from HBM, as in the model (one weight per block)."""
+    d, M = 3072, 28
+    hi, lo = ops.silu_split(torch.randn(M, d, device=dev), apply_silu=True)
+    mk = lambda n: ((torch.randn(n, d, device=dev) * 0.02).to(torch.bfloat16), torch.randn(n, device=dev).to(torch.bfloat16), torch.empty(M, n, device=dev))
+    for name, N, ngrp, copies in (("adaLN table 28x9216x3072", 3 * d, 1, 6), ("adaLN table 28x18432x3072 x2", 6 * d, 2, 3)):
+        sets = [[mk(N) for _ in range(ngrp)] for _ in range(copies)]
+        it = [0]
+
+        def pair():
+            pr = sets[it[0] % copies]; it[0] += 1
+            ops.linear_grouped([ops.LinearProblem(hi, w, o, bias=b) for w, b, o in pr])
+            ops.linear_grouped([ops.LinearProblem(lo, w, o, res=o) for w, b, o in pr])
+
+        def skinny():
+            pr = sets[it[0] % copies]; it[0] += 1
+            ops.linear_skinny(hi, lo, pr)
+
+        for r in range(rounds):
+            t0, t1 = timeit(pair, iters=copies * 4), timeit(skinny, iters=copies * 4)
+            print(f"{name}: two launches {t0*1e6:7.1f} us | skinny {t1*1e6:7.1f} us  {ngrp*N*d*2/t1/1e9:7.0f} GB/s of W", flush=True)
+        del sets
+    T, Ni = 512, 4096
+    x = torch.randn(1, T + Ni, d, device=dev)
+    out = torch.empty(1, T + Ni, d, device=dev, dtype=torch.bfloat16)
+    mi, mt = torch.randn(1, 6 * d, device=dev), torch.randn(1, 6 * d, device=dev)
+    ch = lambda m, i: m[:, i * d : (i + 1) * d]
+
+    def two():
+        ops.layernorm_modulate(x[:, T:], out[:, T:], ch(mi, 0), ch(mi, 1))
+        ops.layernorm_modulate(x[:, :T], out[:, :T], ch(mt, 0), ch(mt, 1))
+
+    one = lambda: ops.layernorm_modulate_pair(x[:, T:], out[:, T:], ch(mi, 0), ch(mi, 1), x[:, :T], out[:, :T], ch(mt, 0), ch(mt, 1))
+    for r in range(rounds):
+        t0, t1 = timeit(two, iters=50), timeit(one, iters=50)
+        print(f"layernorm_mod 4096+512 rows x {d} (f32 in): two launches {t0*1e6:6.1f} us | one launch {t1*1e6:6.1f} us", flush=True)
+
+
+def bench_fused_qkv(rounds=5):
+    """QKV launches with the q/k RMSNorm + RoPE fused into the epilogue (ops.QKRope) beside GEMM + qk_rmsnorm_rope, alternating."""
+    d, T, Ni, H = 3072, 512, 4096, 24
+    S = T + Ni
+    x = torch.randn(1, S, d, device=dev).to(torch.bfloat16)
+    wn = [(1 + 0.1 * torch.randn(128, device=dev)).to(torch.bfloat16) for _ in range(4)]
+    cos, sin = torch.randn(S, 128, device=dev), torch.randn(S, 128, device=dev)
+    P = ops.LinearProblem
+    # single block: [k|v|q|mlp]
+    w = (torch.randn(7 * d, d, device=dev) * 0.02).to(torch.bfloat16)
+    b = torch.zeros(7 * d, device=dev, dtype=torch.bfloat16)
+    big = torch.empty(1, S, 7 * d, device=dev, dtype=torch.bfloat16)
+
+    def two_s():
+        ops.linear(x, w, big, bias=b, gelu_from=3 * d)
+        ops.qk_rmsnorm_rope(big, 2 * d, 0, H, 0, None, None, wn[0], wn[1], cos, sin)
+
+    rope_s = ops.QKRope(2 * d, 0, d, wn[0], wn[1], cos, sin)
+    one_s = lambda: ops.linear(x, w, big, bias=b, gelu_from=3 * d, rope=rope_s)
+    # double block: image + text groups, [q|k|v]
+    wi, wt = [(torch.randn(3 * d, d, device=dev) * 0.02).to(torch.bfloat16) for _ in range(2)]
+    b3 = torch.zeros(3 * d, device=dev, dtype=torch.bfloat16)
+    qkv = torch.empty(1, S, 3 * d, device=dev, dtype=torch.bfloat16)
+
+    def two_d():
+        ops.linear_grouped([P(x[:, T:], wi, qkv[:, T:], bias=b3), P(x[:, :T], wt, qkv[:, :T], bias=b3)])
+        ops.qk_rmsnorm_rope(qkv, 0, d, H, T, wn[2], wn[3], wn[0], wn[1], cos, sin)
+
+    ri, rt = ops.QKRope(0, d, d, wn[0], wn[1], cos, sin, pos0=T), ops.QKRope(0, d, d, wn[2], wn[3], cos, sin, pos0=0)
+    one_d = lambda: ops.linear_grouped([P(x[:, T:], wi, qkv[:, T:], bias=b3, rope=ri), P(x[:, :T], wt, qkv[:, :T], bias=b3, rope=rt)])
+    for r in range(rounds):
+        t0, t1, t2, t3 = timeit(two_s), timeit(one_s), timeit(two_d), timeit(one_d)
+        print(f"qkv single 4608x21504x3072: gemm + rope {t0*1e6:7.1f} us | fused {t1*1e6:7.1f} us   "
+              f"double (4096+512)x9216x3072: gemm + rope {t2*1e6:7.1f} us | fused {t3*1e6:7.1f} us", flush=True)
+
+
 if __name__ == "__main__":
     what = sys.argv[1] if len(sys.argv) > 1 else "all"
     if what in ("gemm", "all"):
@@ -159,3 +234,6 @@ if __name__ == "__main__":
         bench_attn_fp8()
     if what in ("elem", "all"):
         bench_elem()
+    if what in ("passes", "all"):
+        bench_loop_passes()
+        bench_fused_qkv()
