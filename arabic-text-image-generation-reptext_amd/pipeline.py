@@ -18,8 +18,8 @@ import functools
 import inspect
 import json
 import os
-from dataclasses import dataclass, field
-from typing import Any, Callable, Dict, List, Optional, Sequence, Tuple, Union
+from dataclasses import dataclass
+from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
 import torch
@@ -400,9 +400,13 @@ class FluxControlNetPipeline:
         m = F.interpolate(m, size=noise.shape[-2:], mode="bilinear", align_corners=False) > 0
         return torch.where(m, 0.10 * image_latents + noise, noise)
 
+    glyph_blend_is_initial_latents = False     # Q1; the inpaint pipeline's reference returns the blend (INP:645-647)
+
     def prepare_latents_reptext(self, image, batch_size, num_channels_latents, height, width, dtype, device, generator, latents=None):
-        """PIPE:608-660 including quirk Q1: the glyph image IS VAE-encoded with `generator` (advancing its stream by one
-        [B,16,h,w] normal draw) and the blended result is computed, but the returned latents are the plain noise."""
+        """PIPE:608-660 / INP:598-653. The glyph image is VAE-encoded with `generator` (advancing its stream by one [B,16,h,w]
+        normal draw) before the noise is drawn, and 0.10·glyph latent + noise is computed where the down-sampled glyph mask is
+        positive. Quirk Q1: this pipeline's reference then drops that blend and returns the plain noise; under
+        `glyph_blend_is_initial_latents` the blend is what is returned."""
         h2 = 2 * (int(height) // self.vae_scale_factor)
         w2 = 2 * (int(width) // self.vae_scale_factor)
         image = image.to(device=device, dtype=dtype)
@@ -416,12 +420,13 @@ class FluxControlNetPipeline:
         if latents is not None:
             return latents.to(device=device, dtype=dtype), ids
         noise = randn_tensor((batch_size, num_channels_latents, h2, w2), generator=generator, device=device, dtype=dtype)
-        _unused_blend = self._glyph_blend(image, image_latents, noise)   # computed and dropped, as in the reference (Q1)
-        return self._pack_latents(noise, batch_size, num_channels_latents, h2, w2), ids
+        blend = self._glyph_blend(image, image_latents, noise)            # computed even where it is dropped, as in the reference (Q1)
+        start = blend.to(dtype) if self.glyph_blend_is_initial_latents else noise
+        return self._pack_latents(start, batch_size, num_channels_latents, h2, w2), ids
 
-    def _prep_pixels(self, image, width, height, batch_size, num_images_per_prompt, device, dtype):
+    def _prep_pixels(self, image, width, height, batch_size, num_images_per_prompt, device, dtype, processor=None):
         if not isinstance(image, torch.Tensor):
-            image = self.image_processor.preprocess(image, height=height, width=width)
+            image = (processor or self.image_processor).preprocess(image, height=height, width=width)
         repeat_by = batch_size if image.shape[0] == 1 else num_images_per_prompt
         return image.repeat_interleave(repeat_by, dim=0).to(device=device, dtype=dtype)
 
@@ -456,8 +461,8 @@ class FluxControlNetPipeline:
                 out.append(t.to(device=device, dtype=dtype))
         return out
 
-    def _is_packed_hint(self, t) -> bool:
-        cn = self.controlnet
+    def _is_packed_hint(self, t, tower=None) -> bool:
+        cn = tower if tower is not None else self.controlnet
         return isinstance(t, torch.Tensor) and t.dim() == 3 and isinstance(cn, FluxControlNetModel) and \
             t.shape[-1] == cn.controlnet_x_embedder.weight.shape[1]
 
@@ -581,13 +586,7 @@ class FluxControlNetPipeline:
         self.check_inputs(prompt, prompt_2, height, width, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
                           callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, max_sequence_length=max_sequence_length)
         self._guidance_scale, self._joint_attention_kwargs, self._interrupt = guidance_scale, joint_attention_kwargs, False
-
-        if isinstance(prompt, str):
-            batch_size = 1
-        elif isinstance(prompt, list):
-            batch_size = len(prompt)
-        else:
-            batch_size = prompt_embeds.shape[0]
+        batch_size = self._batch_size(prompt, prompt_embeds)
         device, dtype = self._execution_device, self.transformer.dtype
         total = batch_size * num_images_per_prompt
         self._ip_embeds, self._joint_attention_kwargs = self._resolve_ip_embeds(*self._ip_call_args, joint_attention_kwargs, batch_size,
@@ -599,41 +598,61 @@ class FluxControlNetPipeline:
         prompt_embeds = prompt_embeds.to(device=device)
         pooled_prompt_embeds = pooled_prompt_embeds.to(device=device)
 
-        # hints: one packed [B,N,128] tensor per text line (PIPE:928-942). Tensors that are already packed hint latents
-        # ([B,N,in+extra]) are taken as they are — an extension used by the benchmarks and the multi-GPU broadcast.
-        hints: List[torch.Tensor] = []
-        if isinstance(self.controlnet, FluxControlNetModel) and control_image is not None:
-            positions = control_position if control_position is not None else [None] * len(control_image)
-            for img, pos in zip(control_image, positions):
-                if self._is_packed_hint(img):
-                    hints.append(img.to(device=device, dtype=dtype))
-                else:
-                    h, height, width = self.prepare_image(image=img, image_position=pos, width=width, height=height, batch_size=total,
-                                                          num_images_per_prompt=num_images_per_prompt, device=device, dtype=dtype)
-                    hints.append(h)
-
-        num_channels_latents = self.transformer.config.in_channels // 4
-        sigmas = np.linspace(1.0, 1 / num_inference_steps, num_inference_steps)
-        image_seq_len = (int(height) // self.vae_scale_factor) * (int(width) // self.vae_scale_factor)
-        sc = self.scheduler.config
-        mu = calculate_shift(image_seq_len, sc.base_image_seq_len, sc.max_image_seq_len, sc.base_shift, sc.max_shift)
-        timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, timesteps, sigmas, mu=mu)
-
-        if control_glyph is not None:
-            init_image = self.image_processor.preprocess(control_glyph, height=height, width=width).to(dtype=torch.float32)
-            latents, latent_image_ids = self.prepare_latents_reptext(init_image, total, num_channels_latents, height, width,
-                                                                     prompt_embeds.dtype, device, generator, None)
-        else:
-            latents, latent_image_ids = self.prepare_latents(total, num_channels_latents, height, width, prompt_embeds.dtype, device,
-                                                             generator, latents)
-        self._num_timesteps = len(timesteps)
+        hints, height, width = self._collect_hints(control_image, control_position, height, width, total, num_images_per_prompt, device, dtype)
+        timesteps, num_inference_steps = self._schedule(height, width, num_inference_steps, timesteps, device)
+        latents, latent_image_ids = self._initial_latents(control_glyph, total, height, width, prompt_embeds.dtype, device, generator, latents)
         masks = self._region_masks(control_mask, latents.device, latents.dtype)
 
         self._apply_lora_scale()
         latents = self._denoise(latents, prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids, timesteps, hints, masks,
                                 guidance_scale, controlnet_conditioning_scale, controlnet_conditioning_step, control_mode,
                                 callback_on_step_end, callback_on_step_end_tensor_inputs, num_inference_steps)
+        return self._finish(latents, height, width, output_type, return_dict)
 
+    # ------------------------------------------------------------------ stages of the call (shared with pipeline_inpaint.py)
+    @staticmethod
+    def _batch_size(prompt, prompt_embeds) -> int:
+        if isinstance(prompt, str):
+            return 1
+        return len(prompt) if isinstance(prompt, list) else prompt_embeds.shape[0]
+
+    def _collect_hints(self, control_image, control_position, height, width, total, num_images_per_prompt, device, dtype, cfg=False):
+        """One packed [B,N,128] hint per text line (PIPE:928-942), doubled under true CFG; returns (hints, height, width) as
+        ``prepare_image`` leaves the size. Tensors that are already packed hint latents ([B,N,in+extra]) are taken as they are —
+        an extension used by the benchmarks and the multi-GPU broadcast. Only a single ``FluxControlNetModel`` is fed."""
+        hints: List[torch.Tensor] = []
+        if isinstance(self.controlnet, FluxControlNetModel) and control_image is not None:
+            positions = control_position if control_position is not None else [None] * len(control_image)
+            for img, pos in zip(control_image, positions):
+                if self._is_packed_hint(img):
+                    h = img.to(device=device, dtype=dtype)
+                    hints.append(torch.cat([h] * 2) if (cfg and h.shape[0] == total) else h)
+                else:
+                    h, height, width = self.prepare_image(image=img, image_position=pos, width=width, height=height, batch_size=total,
+                                                          num_images_per_prompt=num_images_per_prompt, device=device, dtype=dtype,
+                                                          do_classifier_free_guidance=cfg)
+                    hints.append(h)
+        return hints, height, width
+
+    def _schedule(self, height, width, num_inference_steps, timesteps, device):
+        """Linear sigmas shifted by the resolution's mu (PIPE:960-981) -> (timesteps, number of steps)."""
+        sigmas = np.linspace(1.0, 1 / num_inference_steps, num_inference_steps)
+        image_seq_len = (int(height) // self.vae_scale_factor) * (int(width) // self.vae_scale_factor)
+        sc = self.scheduler.config
+        mu = calculate_shift(image_seq_len, sc.base_image_seq_len, sc.max_image_seq_len, sc.base_shift, sc.max_shift)
+        timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, timesteps, sigmas, mu=mu)
+        self._num_timesteps = len(timesteps)
+        return timesteps, num_inference_steps
+
+    def _initial_latents(self, control_glyph, total, height, width, dtype, device, generator, latents):
+        """(packed latents, image ids): from the glyph image when one is given (``latents`` is then ignored, as in the reference)."""
+        num_channels_latents = self.transformer.config.in_channels // 4
+        if control_glyph is None:
+            return self.prepare_latents(total, num_channels_latents, height, width, dtype, device, generator, latents)
+        init_image = self.image_processor.preprocess(control_glyph, height=height, width=width).to(dtype=torch.float32)
+        return self.prepare_latents_reptext(init_image, total, num_channels_latents, height, width, dtype, device, generator, None)
+
+    def _finish(self, latents, height, width, output_type, return_dict):
         if output_type == "latent":
             # The parity tap (PIPE:1132-1133). The loop's state is kept in fp32 (A.6: the scheduler steps in fp32), and that state
             # is what is returned: rounding it to bf16 here would by itself cost 1.8e-3 rel-L2, twice the whole loop's error.
@@ -672,12 +691,16 @@ class FluxControlNetPipeline:
         """Eager loop, or the replay of its captured hipGraph when this exact call signature has been seen before (GRAPH_CAPTURE)."""
         tvals = timesteps.to(torch.float32).cpu().tolist()                 # host copies: no per-step device sync
         ipe = getattr(self, "_ip_embeds", None)                             # image prompt of this call (None: nothing to add)
+
+        def eager(callback=None):
+            return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
+                                       cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe)
+
         use_graph = (GRAPH_CAPTURE and getattr(self, "capture_graphs", True) and callback is None and latents.is_cuda
                      and not self.interrupt and isinstance(self.controlnet, (FluxControlNetModel, type(None)))
                      and (control_mode is None) and self._graph_safe_kwargs())
         if not use_graph:
-            return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
-                                       cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe)
+            return eager(callback)
         from . import mmdit as _mm
         _mm.reference_bf16_scalars(self.reference_bf16_scalars)      # the module switch follows THIS pipeline before the key is built
         sig = lambda t: (tuple(t.shape), str(t.dtype), tuple(t.stride()))
@@ -696,11 +719,9 @@ class FluxControlNetPipeline:
             if len(cache) >= GRAPH_CACHE_MAX:
                 cache.pop(next(iter(cache)))
             cache[key] = "seen"
-            return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
-                                       cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe)
+            return eager()
         if ent == "failed":
-            return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
-                                       cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe)
+            return eager()
         ins = [latents, prompt_embeds, pooled, text_ids, image_ids] + list(hints) + list(masks) + ([ipe] if ipe is not None else [])
         if ent == "seen":                                    # second call: capture
             static = [t.clone() for t in ins]
@@ -730,8 +751,7 @@ class FluxControlNetPipeline:
                 ops.drop_attention_workspaces(set(ops._ATTN_WS) - attn_keys)     # their zero fill was recorded, never executed
                 torch.cuda.synchronize()
                 self.scheduler._step_index = step_index
-                return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
-                                           cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe)
+                return eager()
             _mm.CAPTURE_KEEP = ops.CAPTURE_KEEP = None
             keep.append(getattr(self, "_sample_cache", None))
             keep.extend(dict(m._rope_cache) for m in (self.transformer, self.controlnet) if m is not None and hasattr(m, "_rope_cache"))
@@ -749,35 +769,56 @@ class FluxControlNetPipeline:
 
     def _denoise_eager(self, latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale,
                        cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _quiet=False,
-                       _ip_embeds=None):
+                       _ip_embeds=None, _extra_towers=(), _velocity=None):
+        """The one loop over timesteps, for both pipelines. ``_extra_towers``: (FluxControlNetModel, hint, conditioning scale) of
+        towers evaluated after the text-line towers into the same sample buffers, unmasked (the inpaint tower). ``_velocity(i,
+        noise_pred)``: what the scheduler steps with instead of the transformer's output (true CFG). With extra towers the loop stays
+        on one stream."""
         device = latents.device
         B = latents.shape[0]
         guidance = torch.full((B,), float(guidance_scale), device=device, dtype=torch.float32) if self.transformer.config.guidance_embeds else None
         # one regional mask per text line, shared by the batch ([1,N,1], the reference's form) or one per image ([B,N,1])
         rowscales = [m.to(torch.float32).reshape(-1).contiguous() if m.shape[0] == 1 else m.to(torch.float32).reshape(m.shape[0], -1).contiguous() for m in masks]
         num_warmup = max(len(timesteps) - num_inference_steps * self.scheduler.order, 0)
-        # adaLN vectors of every block for every step, once per image (timesteps/guidance/pooled are loop-invariant inputs)
+        # adaLN vectors of every block for every step, once per image (timesteps/guidance/pooled are loop-invariant inputs); under
+        # true CFG the conditioning batch is 2B against the latents' B (Q6) and the tables take guidance at that batch
         model_ts = [self._model_timestep(t) for t in tvals]
-        tab_t = self.transformer.build_modulation_table(model_ts, guidance, pooled)
+        g_tab = guidance if guidance is None or pooled.shape[0] == B else guidance.expand(pooled.shape[0]).contiguous()
+        tab_t = self.transformer.build_modulation_table(model_ts, g_tab, pooled)
         fused_cn = isinstance(self.controlnet, FluxControlNetModel) and len(hints) > 0
-        tab_c = self.controlnet.build_modulation_table(model_ts[: max(0, min(len(model_ts), cn_steps))], guidance, pooled) if fused_cn and cn_steps > 0 else None
+        # The towers of a step, in evaluation order: (model, hint, conditioning scale, row scale, modulation table). One entry per
+        # text line (masked; the first one writes the sample buffers, PIPE:1076-1087) and then the extra towers, whose residuals are
+        # ADDED to the text towers' and dropped when those are absent (INP:1231-1245: both sums are guarded by `control_block_samples
+        # is not None`) — they are therefore only evaluated when they can matter. Past `cn_steps` no tower runs (Q3).
+        towers = []
+        if fused_cn and cn_steps > 0:
+            ts_c = model_ts[: min(len(model_ts), cn_steps)]
+            tab_c = self.controlnet.build_modulation_table(ts_c, g_tab, pooled)
+            towers = [(self.controlnet, h, cn_scale, rowscales[line] if rowscales else None, tab_c) for line, h in enumerate(hints)]
+            towers += [(m, h, s, None, m.build_modulation_table(ts_c, g_tab, pooled)) for m, h, s in _extra_towers]
+
         # Loop-invariant work, once per image instead of once per step (the prompt and the hint latents do not change inside the
-        # loop): context_embedder(prompt) of both models, controlnet_x_embedder(hint) per text line. A callback that replaces
+        # loop): context_embedder(prompt) of every model, controlnet_x_embedder(hint) per tower. A callback that replaces
         # prompt_embeds invalidates them (recomputed below).
-        static_t = self.transformer.prepare_static(prompt_embeds)
-        static_c = [self.controlnet.prepare_static(prompt_embeds, h) for h in hints] if fused_cn and cn_steps > 0 else []
+        def prepare_static(pe):
+            return self.transformer.prepare_static(pe), [tw[0].prepare_static(pe, tw[1]) for tw in towers]
+
+        static_t, static_c = prepare_static(prompt_embeds)
         # the image prompt's tokens and every block's K/V of them: loop-invariant too (ip_adapter.py steps 1-2)
         ip_prep = self.transformer._ip_adapter.prepare(_ip_embeds) if _ip_embeds is not None else None
         # Which tower samples does the transformer read? Block i takes sample i // ceil(n_blocks / n_samples) (A.3): with 6
         # samples against 19 double blocks the sixth is never consumed (Q5), so its block and zero-linear are not evaluated.
+        # An extra tower of another depth adds into the first tower's buffers (it must not be deeper: there is one buffer per block
+        # of the first tower) and every block of every tower is then evaluated.
         blocks_needed, sample_buf, single_buf = None, None, None
         if fused_cn:
             cnet = self.controlnet
             n_cd, n_cs = len(cnet.transformer_blocks), len(cnet.single_transformer_blocks)
             n_td, n_ts = len(self.transformer.transformer_blocks), len(self.transformer.single_transformer_blocks)
-            need_d = 0 if n_cd == 0 else (n_td - 1) // int(np.ceil(n_td / n_cd)) + 1
-            need_s = 0 if n_cs == 0 or n_ts == 0 else (n_ts - 1) // int(np.ceil(n_ts / n_cs)) + 1
-            blocks_needed = (min(need_d, n_cd), min(need_s, n_cs))
+            if all((len(m.transformer_blocks), len(m.single_transformer_blocks)) == (n_cd, n_cs) for m, _, _ in _extra_towers):
+                need_d = 0 if n_cd == 0 else (n_td - 1) // int(np.ceil(n_td / n_cd)) + 1
+                need_s = 0 if n_cs == 0 or n_ts == 0 else (n_ts - 1) // int(np.ceil(n_ts / n_cs)) + 1
+                blocks_needed = (min(need_d, n_cd), min(need_s, n_cs))
             # sample buffers: allocated once per shape, written by the zero-linear epilogues every step (no per-step allocation)
             Bc, N_, d_ = prompt_embeds.shape[0], latents.shape[1], cnet.inner_dim
             key = (Bc, N_, d_, n_cd, n_cs, str(device))
@@ -795,8 +836,11 @@ class FluxControlNetPipeline:
         # launches fill only 27/32 of their last round of workgroups (216 GEMM tiles on 256 CUs, 864 attention workgroups on
         # 512 slots); two independent chains in flight fill some of those holes. Results are bitwise those of the serial order.
         # On by default (OVERLAP_TOWER; RT_OVERLAP_TOWER=0 turns it off): -0.5 % eager, -1.1 % inside the captured graph.
-        overlap = (OVERLAP_TOWER and fused_cn and tab_c is not None and device.type == "cuda"
+        # `not _extra_towers`: the inpaint flow is serial by decision (its second tower has no side stream or "tower" workspace of its
+        # own yet); an extra tower added to the BASE flow would switch the overlap off here too — extend this rule then, not the call.
+        overlap = (OVERLAP_TOWER and bool(towers) and not _extra_towers and device.type == "cuda"
                    and len(self.controlnet.single_transformer_blocks) == 0)
+        side = sample_ev = None
         if overlap:
             if getattr(self, "_side_stream", None) is None or self._side_stream.device != device:
                 self._side_stream = torch.cuda.Stream(device=device)
@@ -807,45 +851,23 @@ class FluxControlNetPipeline:
                 if self.interrupt:
                     continue
                 timestep = torch.full((B,), self._model_timestep(t), device=device, dtype=torch.float32)      # PIPE:1025,1048 (Q4)
-                merged = merged_single = None
-                events = None
-                if overlap and i < cn_steps:
-                    main = torch.cuda.current_stream()
-                    side.wait_stream(main)                       # latents of this step (and, at i = 0, tables and hints) are ready
-                    with torch.cuda.stream(side):
-                        for line, hint in enumerate(hints):
-                            self.controlnet(
-                                hidden_states=latents, controlnet_cond=hint, controlnet_mode=control_mode, conditioning_scale=cn_scale,
+                merged = merged_single = events = None
+                if towers and i < cn_steps:
+                    if overlap:
+                        side.wait_stream(torch.cuda.current_stream())    # latents of this step (and, at i = 0, tables and hints) are ready
+                        events = sample_ev                               # recorded by the last tower, once the sums are complete
+                    with torch.cuda.stream(side) if overlap else contextlib.nullcontext():
+                        for k, ((model, hint, scale, rowscale, table), static) in enumerate(zip(towers, static_c)):
+                            # zero-linear epilogues write (first tower) or add to (later ones) the preallocated buffers
+                            samples = model(
+                                hidden_states=latents, controlnet_cond=hint, controlnet_mode=control_mode, conditioning_scale=scale,
                                 timestep=timestep, guidance=guidance, pooled_projections=pooled, encoder_hidden_states=prompt_embeds,
                                 txt_ids=text_ids, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs,
-                                return_dict=False, _rowscale=rowscales[line] if rowscales else None, _accumulate_into=sample_buf,
-                                _overwrite=(line == 0), _sample_events=sample_ev if line == len(hints) - 1 else None,
-                                _mods=tab_c.step(i), _ws_tag="tower", _static=static_c[line], _blocks_needed=blocks_needed)
-                    merged, events = [b if k < blocks_needed[0] else None for k, b in enumerate(sample_buf)], sample_ev
-                for line, hint in enumerate(hints if events is None else ()):
-                    if i >= cn_steps:                                                             # Q3
-                        samples = single_samples = None
-                    elif fused_cn:
-                        # zero-linear epilogues write (line 0) or add to (later lines: PIPE:1076-1087) the preallocated buffers
-                        samples, single_samples = self.controlnet(
-                            hidden_states=latents, controlnet_cond=hint, controlnet_mode=control_mode, conditioning_scale=cn_scale,
-                            timestep=timestep, guidance=guidance, pooled_projections=pooled, encoder_hidden_states=prompt_embeds,
-                            txt_ids=text_ids, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs,
-                            return_dict=False, _rowscale=rowscales[line] if rowscales else None, _accumulate_into=sample_buf,
-                            _accumulate_single_into=single_buf, _overwrite=(line == 0), _mods=None if tab_c is None else tab_c.step(i),
-                            _static=static_c[line] if static_c else None, _blocks_needed=blocks_needed)
-                    else:
-                        rs = rowscales[line] if rowscales else None
-                        samples, single_samples = self.controlnet(
-                            hidden_states=latents, controlnet_cond=hint, controlnet_mode=control_mode, conditioning_scale=cn_scale,
-                            timestep=timestep, guidance=guidance, pooled_projections=pooled, encoder_hidden_states=prompt_embeds,
-                            txt_ids=text_ids, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs,
-                            return_dict=False, _rowscale=rs, _accumulate_into=merged if line > 0 else None,
-                            _accumulate_single_into=merged_single if line > 0 else None,
-                            _mods=None if tab_c is None else tab_c.step(i))
-                    if line == 0:
-                        merged, merged_single = samples, single_samples
-                    # line > 0: the zero-linear epilogues already summed into `merged` (PIPE:1076-1087)
+                                return_dict=False, _rowscale=rowscale, _accumulate_into=sample_buf, _accumulate_single_into=single_buf,
+                                _overwrite=(k == 0), _sample_events=events if k == len(towers) - 1 else None, _mods=table.step(i),
+                                _ws_tag="tower" if overlap else "", _static=static, _blocks_needed=blocks_needed)
+                            if k == 0:
+                                merged, merged_single = samples          # the buffers, None where a block was skipped
                 noise_pred = self.transformer(
                     hidden_states=latents, timestep=timestep, guidance=guidance, pooled_projections=pooled,
                     encoder_hidden_states=prompt_embeds, controlnet_block_samples=merged, controlnet_single_block_samples=merged_single,
@@ -853,6 +875,8 @@ class FluxControlNetPipeline:
                     _mods=tab_t.step(i), _sample_events=events, _static=static_t, _ip=ip_prep)[0]
                 if events is not None:
                     torch.cuda.current_stream().wait_stream(side)     # the tower has finished reading `latents` (its last sample is unused, Q5)
+                if _velocity is not None:
+                    noise_pred = _velocity(i, noise_pred)
                 self.scheduler.step_master_(noise_pred, lat32, latents)
                 if callback is not None:
                     env = {"latents": latents, "prompt_embeds": prompt_embeds}
@@ -862,8 +886,7 @@ class FluxControlNetPipeline:
                         lat32 = latents.to(torch.float32)
                     if "prompt_embeds" in out:                       # the loop-invariant embeddings are no longer valid
                         prompt_embeds = out.pop("prompt_embeds")
-                        static_t = self.transformer.prepare_static(prompt_embeds)
-                        static_c = [self.controlnet.prepare_static(prompt_embeds, h) for h in hints] if static_c else []
+                        static_t, static_c = prepare_static(prompt_embeds)
                 if i == len(tvals) - 1 or ((i + 1) > num_warmup and (i + 1) % self.scheduler.order == 0):
                     bar.update()
         self._master_latents = lat32          # fp32 state of the loop; `latents` is its bf16 copy

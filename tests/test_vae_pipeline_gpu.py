@@ -242,6 +242,44 @@ def test_inpaint_pipeline_cfg_and_second_tower(vae_pair, gpu):
     assert torch.equal(one, b16(lat0).float())
 
 
+def test_inpaint_pipeline_with_a_zero_second_tower_is_the_base_pipeline(vae_pair, gpu):
+    """Both pipelines run ONE denoising loop (pipeline._denoise_eager). With true CFG off (guidance_scale <= 1) and a
+    zero-initialised inpaint tower, whose samples add exact zeros to the text towers', the inpaint pipeline must return, bit for
+    bit, what the base pipeline returns for the same transformer, tower, embeddings, hints, masks and latents: two masked text
+    lines, tower active for 2 of 3 steps."""
+    from PIL import Image
+
+    from reptext_amd.controlnet import FluxControlNetModel
+    from reptext_amd.pipeline import FluxControlNetPipeline as Base
+    from reptext_amd.pipeline_inpaint import FluxControlNetPipeline as Inpaint
+    from reptext_amd.scheduler import FlowMatchEulerDiscreteScheduler
+    from reptext_amd.transformer import FluxTransformer2DModel
+
+    _, vae = vae_pair
+    tr = FluxTransformer2DModel(**SMALL_T, device=gpu, dtype=torch.bfloat16).random_init_(91)
+    cn = FluxControlNetModel(**SMALL_CN, device=gpu, dtype=torch.bfloat16).random_init_(92)
+    cni = FluxControlNetModel(**dict(SMALL_CN, extra_condition_channels=4), device=gpu, dtype=torch.bfloat16).random_init_(93)
+    cni.zero_init_controlnet_()
+    base = Base(FlowMatchEulerDiscreteScheduler(), vae, None, None, None, None, tr, cn)
+    inpaint = Inpaint(FlowMatchEulerDiscreteScheduler(), vae, None, None, None, None, tr, cn, cni)
+    base.capture_graphs = False
+    g = torch.Generator().manual_seed(12)
+    r = lambda *s: torch.randn(*s, generator=g).to(gpu, torch.bfloat16)
+    masks = []
+    for box in ((40, 120, 30, 200), (140, 220, 60, 240)):
+        m = np.zeros([256, 256], dtype=np.uint8); m[box[0]:box[1], box[2]:box[3]] = 255
+        masks.append(Image.fromarray(m))
+    kw = dict(prompt_embeds=r(1, 64, 256), pooled_prompt_embeds=r(1, 64), height=256, width=256, num_inference_steps=3, guidance_scale=1.0,
+              control_image=[r(1, 256, 128), r(1, 256, 128)], control_mask=masks, controlnet_conditioning_step=2, latents=r(1, 256, 64),
+              output_type="latent")
+    for p in (base, inpaint):
+        p.set_progress_bar_config(disable=True)
+    want = base(**kw).images.clone()
+    got = inpaint(**kw, control_image_inpaint=r(1, 256, 68)).images
+    assert not torch.equal(want, kw["latents"].float())
+    assert torch.equal(got, want)
+
+
 def test_pipeline_many_steps_error_growth(vae_pair, gpu):
     """28 steps (the BASELINE step count) at the C1 resolution with reduced-depth weights: the latent error vs the fp32 oracle
     must not grow with the step count (fp32 master latents + fp32 residual stream)."""
