@@ -25,19 +25,15 @@
 // round-robin over the 8 XCDs, so blockIdx.x & 7 labels the XCD group; each group owns a CONTIGUOUS run of the
 // (head, query block) items, i.e. whole heads (3 of 24 per XCD): K/V of a head are fetched into one XCD's L2 only.
 //
-// Key-split tail: with NI items per XCD group on `spx` workgroup slots (2 per CU), the last NI mod spx items would
-// occupy a partial round of full-length workgroups (864 items on 512 slots: 1.69 rounds run as 2). Instead those
-// `rem` items × ntiles key tiles are dealt to `spx` workgroups in equal contiguous runs of tiles; a run covers the
-// tail of one item and/or the head of the next. A workgroup that covers only part of an item writes its unnormalised
-// (m, l, Oᵀ) to a workspace record (write-through stores) and takes a ticket on the item's counter; the workgroup that
-// draws the last ticket combines the item's records IN RUN ORDER (not arrival order: bitwise reproducible) and
-// stores the output. Nobody waits on anybody, so no dispatch-order assumption exists. The decomposition depends on
-// (S, H, CU count) only — every batch entry is cut identically, so results do not depend on the batch size.
+// Key-split tail (attention_split.h, shared with attention_v3.hip): the items of the last, partly filled round of an XCD
+// group are not run by full-length workgroups; their key tiles are dealt to all `spx` workgroup slots (2 per CU) in equal
+// runs. A workgroup that covers only part of an item writes its unnormalised (m, l, Oᵀ) to a workspace record; the last
+// one to finish an item combines its records in run order.
 //
 // LDS image of a K or V tile: 64 rows × 256 B; 16-B chunk c of row r lives at 256·r + 16·(c ^ f(r)),
 // f(r) = ((r&3)<<2) | ((r>>2)&3): conflict-free for the row reads (K) and the transposed reads (V).
 // LDS-DMA writes lane-linear, so the XOR is applied to each lane's source address.
-#include "rt_common.h"
+#include "attention_split.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -51,63 +47,15 @@ constexpr int ATT_THREADS = 256;
 constexpr float RESCALE_THR = 6.0f;   // log2 units: P <= 64 between rescales
 constexpr int REC_WAVE_B = 64 * 64 * 4 + 64 * 8;   // one wave's partial: Oᵀ (64 registers × 64 lanes, fp32) + (m, l) per lane
 constexpr int REC_B = 4 * REC_WAVE_B;              // 67 584 B per (workgroup, segment)
-constexpr int CNT_ALIGN = 256;
-constexpr int SPLIT_MIN_TILES = 8;                 // do not split runs shorter than this many key tiles
 
-struct AttnGeom {
-  int S, H, nqb, ntiles, NI;   // NI = H * nqb work items per batch entry
-  int spx;                     // workgroup slots per XCD group (2 per CU)
-  int split;                   // key-split tail enabled (workspace present and it pays)
-};
-
-// Wave-uniform conditions that are almost never true (ragged last tile, a row maximum that outgrew the running one): tell the
-// block placement so, so that the rare code sits out of line and the common path falls through.
-#define RT_RARE(c) __builtin_expect(!!(c), 0)
-#define RT_USUAL(c) __builtin_expect(!!(c), 1)
-
-__device__ __forceinline__ int swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-
-// 3-input max. Plain fmaxf so the compiler inserts the MFMA->VALU wait states itself: an inline-asm v_max3 here read the
-// accumulators before the MFMA had retired them (run-to-run differences in the running max; csrc/Makefile builds this file
-// with -fno-honor-nans so no canonicalising v_max is emitted in front and the pair folds to one v_max3_f32).
-__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-
-typedef const __attribute__((address_space(3))) char* lds_cptr;
-__device__ __forceinline__ s16x4 tr_read(lds_cptr p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-
-// How the items of one XCD group are cut (identical on host and device; scalar arithmetic only).
-struct GroupCut {
-  int start, cnt;   // first item and number of items of this group
-  int nfull;        // items run by one full-length workgroup each
-  int rem;          // items whose key tiles are dealt to `spx` workgroups (0: no split)
-};
-__host__ __device__ inline GroupCut group_cut(const AttnGeom& G, int xcd) {
-  GroupCut c;
-  const int base = G.NI >> 3, extra = G.NI & 7;
-  c.cnt = base + (xcd < extra ? 1 : 0);
-  c.start = xcd * base + (xcd < extra ? xcd : extra);
-  c.nfull = c.cnt;
-  c.rem = 0;
-  if (G.split) {
-    const int nf = (c.cnt / G.spx) * G.spx, rem = c.cnt - nf;
-    // split when the partial round is less than 15/16 full and every run keeps >= SPLIT_MIN_TILES tiles
-    if (rem > 0 && rem * 16 < G.spx * 15 && (int64_t)rem * G.ntiles >= (int64_t)G.spx * SPLIT_MIN_TILES) {
-      c.nfull = nf;
-      c.rem = rem;
-    }
-  }
-  return c;
-}
-__host__ __device__ inline int group_slots(const AttnGeom& G, int xcd) {
+__host__ __device__ inline int group_slots(const SplitGeom& G, int xcd) {
   const GroupCut c = group_cut(G, xcd);
   return c.nfull + (c.rem ? G.spx : 0);
 }
 
 __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V, bf16_t* O,
-    int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob, float scale_log2, const AttnGeom G,
+    int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob, float scale_log2, const SplitGeom G,
     int* counters, char* records) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE_B];   // [slot][K|V]
   const int tid = threadIdx.x;
@@ -130,12 +78,10 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
   } else {
     jpart = slot - cut.nfull;
     if (cut.rem == 0 || jpart >= G.spx) return;
-    const unsigned U = (unsigned)cut.rem * (unsigned)ntiles;      // host checks rem * ntiles * spx < 2^31
-    const int lo = (int)((unsigned)jpart * U / (unsigned)G.spx), hi = (int)((unsigned)(jpart + 1) * U / (unsigned)G.spx);
-    const int i0 = lo / ntiles;
-    item0 = cut.start + cut.nfull + i0;
-    run_lo = lo - i0 * ntiles;
-    run_hi = hi - i0 * ntiles;   // may exceed ntiles: the run continues into item0 + 1
+    const SplitRun run = split_run(G, cut, jpart);
+    item0 = cut.start + cut.nfull + run.i0;
+    run_lo = run.lo - run.i0 * ntiles;
+    run_hi = run.hi - run.i0 * ntiles;   // may exceed ntiles: the run continues into item0 + 1
   }
 
   // ---- per-lane constants that do not depend on the item
@@ -290,9 +236,6 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
       l_run += ps;
     };
 
-#define RT_SB() __builtin_amdgcn_sched_barrier(0)
-// Opaque use+def: the value must exist HERE (keeps the optimiser from sinking a step's vector work below a later branch)
-#define RT_PIN(v) asm volatile("" : "+v"(v))
 // n groups of { 1 MFMA, nds LDS reads, nva vector/transcendental ops }
 #define RT_WEAVE(n, nds, nva)                                          \
   _Pragma("unroll") for (int w_ = 0; w_ < (n); ++w_) {                 \
@@ -422,7 +365,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
     if (!whole) {
       // ---- partial: write (Oᵀ, m, l) of this run through to memory, take a ticket, last ticket combines the item
       const int ritem = item - (cut.start + cut.nfull);            // index among the split items of this group
-      char* rec = records + ((((int64_t)b * 8 + xcd) * G.spx + jpart) * 2 + seg) * (int64_t)REC_B + wave * REC_WAVE_B;
+      char* rec = records + split_rec_index(G, b, xcd, jpart, seg) * (int64_t)REC_B + wave * REC_WAVE_B;
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(rec, 0, REC_WAVE_B, 0x00020000);
 #pragma unroll
       for (int i = 0; i < 4; ++i)
@@ -437,38 +380,16 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
         const u32x2 ml = __builtin_bit_cast(u32x2, mlf);
         __builtin_amdgcn_raw_buffer_store_b64(ml, rs, 16384 + lane * 8, 0, 16);
       }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // every storing wave drains its write-through stores
-      __syncthreads();
       int* cnt = counters + (int64_t)b * G.NI + item;
-      // which splitting workgroups cover this item (same closed forms on every workgroup; 32-bit scalar arithmetic)
-      const unsigned U = (unsigned)cut.rem * (unsigned)ntiles, spx = (unsigned)G.spx;
-      const unsigned a = (unsigned)ritem * (unsigned)ntiles, bnd = a + (unsigned)ntiles;
-      const int j_first = (int)(((a + 1) * spx + U - 1) / U) - 1;
-      const int j_last = min(G.spx - 1, (int)((bnd * spx + U - 1) / U) - 1);
-      const int nparts = j_last - j_first + 1;
-      volatile int* flag = reinterpret_cast<volatile int*>(smem);
-      if (tid == 0) {
-        const int old = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const int last = (old == nparts - 1) ? 1 : 0;
-        if (last) {
-          __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-          __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                         // drop this CU's stale lines
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        }
-        *flag = last;
-      }
-      __syncthreads();
-      const int last = __builtin_amdgcn_readfirstlane(*flag);
+      const SplitParts parts = split_parts(G, cut, ritem);
+      const bool last = split_ticket(cnt, parts.nparts, reinterpret_cast<volatile int*>(smem), tid);
       if (last) {
-        // record of splitting workgroup j for this item: its second segment when the item starts after the run does
         auto rec_of = [&](int j) -> const char* {
-          const unsigned lo_j = (unsigned)j * U / spx;
-          const int sj = (a > lo_j) ? 1 : 0;
-          return records + ((((int64_t)b * 8 + xcd) * G.spx + j) * 2 + sj) * (int64_t)REC_B + wave * REC_WAVE_B;
+          return records + split_rec_index(G, b, xcd, j, split_seg_of(G, parts, j)) * (int64_t)REC_B + wave * REC_WAVE_B;
         };
         // pass 1: common max; pass 2: weighted sum in run order
         float M = -INFINITY;
-        for (int j = j_first; j <= j_last; ++j) {
+        for (int j = parts.j_first; j <= parts.j_last; ++j) {
           const char* rj = rec_of(__builtin_amdgcn_readfirstlane(j));
           M = fmaxf(M, *reinterpret_cast<const float*>(rj + 16384 + lane * 8));
         }
@@ -477,7 +398,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
         for (int i = 0; i < 4; ++i)
 #pragma unroll
           for (int r = 0; r < 16; ++r) o_acc[i][r] = 0.f;
-        for (int j = j_first; j <= j_last; ++j) {
+        for (int j = parts.j_first; j <= parts.j_last; ++j) {
           const char* rj = rec_of(__builtin_amdgcn_readfirstlane(j));
           const float2 ml = *reinterpret_cast<const float2*>(rj + 16384 + lane * 8);
           const float wgt = __builtin_amdgcn_exp2f(ml.x - M);
@@ -521,53 +442,30 @@ int g_slots_per_xcd = 0;   // 2 workgroups per CU, CUs / 8 per XCD group (querie
 
 int slots_per_xcd() {
   if (g_slots_per_xcd == 0) {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-      int v = 0;
-      if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
     const char* e = getenv("RT_ATTN_SLOTS_PER_XCD");   // A/B and tests only
-    g_slots_per_xcd = e ? atoi(e) : (cus / 8) * 2;
+    g_slots_per_xcd = e ? atoi(e) : (split_cu_count() / 8) * 2;
     if (g_slots_per_xcd < 1) g_slots_per_xcd = 1;
   }
   return g_slots_per_xcd;
 }
 
-AttnGeom make_geom(int S, int H, bool want_split) {
-  AttnGeom G;
-  G.S = S;
-  G.H = H;
-  G.nqb = (S + BQ - 1) / BQ;
-  G.ntiles = (S + BKV - 1) / BKV;
-  G.NI = H * G.nqb;
-  G.spx = slots_per_xcd();
-  G.split = want_split ? 1 : 0;
-  return G;
-}
+SplitGeom make_geom(int S, int H, bool want_split) { return split_geom(S, H, BQ, BKV, slots_per_xcd(), want_split); }
 
 }  // namespace
 
 // Workspace of the key-split tail for (B, S, H) on the current device: item counters (zero before first use; the kernel
-// leaves them zero) followed by the partial records. 0 when no item of this shape would be split.
-int64_t rt_attention_v3_ws_bytes(int32_t B, int32_t S, int32_t H);
+// leaves them zero) followed by the partial records. 0 when no item of this shape would be split. The larger of the two
+// kernels' needs: either may serve the call.
 extern "C" int64_t rt_attention_ws_bytes(int32_t B, int32_t S, int32_t H) {
   if (B < 1 || S < 1 || H < 1) return 0;
   static const bool off = getenv("RT_ATTN_SPLIT") && getenv("RT_ATTN_SPLIT")[0] == '0';
   if (off) return 0;
-  const int64_t need3 = rt_attention_v3_ws_bytes(B, S, H);     // the larger of the two kernels' needs: either may serve the call
-  const AttnGeom G = make_geom(S, H, true);
-  bool any = false;
-  for (int x = 0; x < 8; ++x) any = any || group_cut(G, x).rem > 0;
-  if (!any) return need3;
-  const int64_t cnt_b = (((int64_t)B * G.NI * 4 + CNT_ALIGN - 1) / CNT_ALIGN) * CNT_ALIGN;
-  const int64_t need = cnt_b + (int64_t)B * 8 * G.spx * 2 * REC_B;
+  const int64_t need3 = rt_attention_v3_ws_bytes(B, S, H);
+  const int64_t need = split_ws_bytes(B, make_geom(S, H, true), REC_B);
   return need > need3 ? need : need3;
 }
 
 // csrc/attention_v3.hip: the one-wave-per-SIMD kernel (64 query rows per wave); takes the launch when S % 256 == 0
-int rt_attention_v3_try(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob,
-                        int32_t B, int32_t S, int32_t H, float scale, void* ws, int64_t ws_bytes, void* stream);
-int rt_attention_v3_mode(int mode);
 extern "C" int rt_attention_variant(int32_t mode) { return rt_attention_v3_mode(mode); }
 
 extern "C" int rt_attention_fwd(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b,
@@ -579,21 +477,22 @@ extern "C" int rt_attention_fwd(const void* q, const void* k, const void* v, voi
     return RT_E_ALIGN;
   if (ld < (int64_t)H * DH || ldo < (int64_t)H * DH) return RT_E_SHAPE;
   if ((int64_t)(S + BKV) * ld * 2 >= (int64_t)1 << 31) return RT_E_SHAPE;      // per-tile byte offsets are 32-bit
-  if ((int64_t)((S + BQ - 1) / BQ) * H * ((S + BKV - 1) / BKV + 1) * slots_per_xcd() >= ((int64_t)1 << 31)) return RT_E_SHAPE;   // 32-bit run arithmetic
+  if (!split_fits_32bit(make_geom(S, H, true))) return RT_E_SHAPE;
   {
-    const int r = rt_attention_v3_try(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, ws, ws_bytes, stream);
-    if (r != 0) return r == 1 ? RT_OK : r;
+    int taken = 0;
+    const int st = rt_attention_v3_try(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, ws, ws_bytes, stream, &taken);
+    if (taken || st != RT_OK) return st;
   }
   const int64_t need = rt_attention_ws_bytes(B, S, H);
   const bool split = ws != nullptr && need > 0;
   if (split && (ws_bytes < need || !RT_ALIGNED(ws, 256))) return RT_E_BADARG;
-  const AttnGeom G = make_geom(S, H, split);
+  const SplitGeom G = make_geom(S, H, split);
   int wmax = 0;
   for (int x = 0; x < 8; ++x) wmax = group_slots(G, x) > wmax ? group_slots(G, x) : wmax;
-  const int64_t cnt_b = (((int64_t)B * G.NI * 4 + CNT_ALIGN - 1) / CNT_ALIGN) * CNT_ALIGN;
   const dim3 grid(8 * wmax, B);
   hipLaunchKernelGGL(attention_fwd_kernel, grid, dim3(ATT_THREADS), 0, (hipStream_t)stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ld, stride_b, ldo, stride_ob,
-                     scale * 1.4426950408889634f, G, split ? (int*)ws : nullptr, split ? (char*)ws + cnt_b : nullptr);
+                     scale * 1.4426950408889634f, G, split ? (int*)ws : nullptr,
+                     split ? (char*)ws + split_cnt_bytes(B, S, H) : nullptr);
   return rt_hip_status();
 }

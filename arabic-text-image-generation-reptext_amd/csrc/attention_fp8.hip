@@ -32,9 +32,6 @@ constexpr float E4M3_MAX = 448.f;
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
-typedef const __attribute__((address_space(3))) char* lds_cptr;
-
-__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }   // see attention.hip
 
 __device__ __forceinline__ i32x8 lds_read32(lds_cptr p0, lds_cptr p1) {
   const i32x4 a = *(const __attribute__((address_space(3))) i32x4*)p0;

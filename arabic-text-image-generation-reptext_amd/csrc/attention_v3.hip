@@ -29,7 +29,7 @@
 // against attention.hip, interleaved in one process: S = 4608 x 24 heads 247 vs 264 us (-6.6 %), 4096 x 32 heads 244 vs 265,
 // batch 4 -5 %, S = 9728 986 vs 1065 us (1179 TFLOP/s); S = 768 25 vs 19 us (left to attention.hip). DESIGN.md §5 has the
 // ablation table (MFMA-only floor of this structure at S = 4096 x 32: 183 us = the chip holding ~1.6 GHz under back-to-back MFMAs).
-#include "rt_common.h"
+#include "attention_split.h"
 #include <cstdlib>
 #include <type_traits>
 
@@ -43,9 +43,6 @@ constexpr int STAGE_B = 2 * TILE_B;  // K | V
 constexpr int NSTAGE = 3;
 constexpr int V3_THREADS = 256;
 constexpr float RESCALE_THR = 6.0f;
-
-__device__ __forceinline__ int swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 
 // ---- the accumulator half of the register file is OWNED by the asm statements of this file -------------------------------------
 // O fragment f = d block * 2 + query block lives in a[16f : 16f+15], Q fragment i = query block * 8 + k-step in a[128+4i : 131+4i]
@@ -126,50 +123,13 @@ __device__ __forceinline__ f32x16 o_read(int f) {
   }
   return f32x16{x0, x1, x2, x3, x4, x5, x6, x7, x8, x9, x10, x11, x12, x13, x14, x15};
 }
-#define V3_SB() __builtin_amdgcn_sched_barrier(0)
-// an opaque use+def: nothing that reads x can be scheduled above this point (MFMA results need 12 wait states before a VALU read;
-// the asm MFMAs are invisible to hipcc's hazard recogniser, so the distance is kept by ORDER: two MFMAs always sit in between)
-#define V3_PIN(x) asm volatile("" : "+v"(x))
-
-typedef const __attribute__((address_space(3))) char* lds_cptr;
-__device__ __forceinline__ s16x4 tr_read(lds_cptr p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
 
 constexpr int REC3_WAVE_B = 8 * 16 * 64 * 4 + 64 * 16;   // one wave's partial: 8 O fragments (16 registers x 64 lanes, fp32) + (mA, lA, mB, lB) per lane
 constexpr int REC3_B = 4 * REC3_WAVE_B;                 // 135 168 B per (workgroup, segment)
-constexpr int CNT_ALIGN = 256;
-constexpr int SPLIT_MIN_TILES = 8;
-
-struct V3Geom {
-  int S, H, nqb, ntiles, NI;   // NI = H * nqb work items per batch entry
-  int spx;                     // workgroups per XCD group (one per CU)
-  int split;                   // key-split tail enabled (workspace present)
-};
-// How the items of one XCD group are cut (identical on host and device): `nfull` items run whole, one per workgroup and round;
-// the key tiles of the `rem` items of the last, partly filled round are dealt to all `spx` workgroups in equal contiguous runs
-// (csrc/attention.hip: the same scheme at 256-row items).
-struct V3Cut { int start, cnt, nfull, rem; };
-__host__ __device__ inline V3Cut v3_cut(const V3Geom& G, int xcd) {
-  V3Cut c;
-  const int base = G.NI >> 3, extra = G.NI & 7;
-  c.cnt = base + (xcd < extra ? 1 : 0);
-  c.start = xcd * base + (xcd < extra ? xcd : extra);
-  c.nfull = c.cnt;
-  c.rem = 0;
-  if (G.split) {
-    const int nf = (c.cnt / G.spx) * G.spx, rem = c.cnt - nf;
-    if (rem > 0 && rem * 16 < G.spx * 15 && (int64_t)rem * G.ntiles >= (int64_t)G.spx * SPLIT_MIN_TILES) {
-      c.nfull = nf;
-      c.rem = rem;
-    }
-  }
-  return c;
-}
 
 __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                                      const bf16_t* __restrict__ V, bf16_t* O, int64_t ld, int64_t stride_b,
-                                                                     int64_t ldo, int64_t stride_ob, float scale_log2, const V3Geom G,
+                                                                     int64_t ldo, int64_t stride_ob, float scale_log2, const SplitGeom G,
                                                                      int* counters, char* records) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [3 stages][K|V]
   const int tid = threadIdx.x;
@@ -178,7 +138,7 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
   const int l31 = lane & 31, hh = lane >> 5;
   const int ntiles = G.ntiles;
   const int xcd = (int)blockIdx.x & 7, slot = (int)blockIdx.x >> 3, b = (int)blockIdx.y;
-  const V3Cut cut = v3_cut(G, xcd);
+  const GroupCut cut = group_cut(G, xcd);   // attention_split.h: the key-split tail shared with attention.hip
   const uint32_t lds0 = (uint32_t)(uintptr_t)LDS_PTR(smem);
 
   // ---- per-lane constants
@@ -193,13 +153,8 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
 
   // ---- this workgroup's segments: its whole items (one per round), then the one or two pieces of its run of the split items
   const int nwhole = slot < cut.nfull ? (cut.nfull - slot + G.spx - 1) / G.spx : 0;
-  int run_lo = 0, run_hi = 0, run_i0 = 0;
-  if (cut.rem && slot < G.spx) {
-    const unsigned U = (unsigned)cut.rem * (unsigned)ntiles;
-    run_lo = (int)((unsigned)slot * U / (unsigned)G.spx);
-    run_hi = (int)((unsigned)(slot + 1) * U / (unsigned)G.spx);
-    run_i0 = run_lo / ntiles;
-  }
+  SplitRun run = {0, 0, 0};
+  if (cut.rem && slot < G.spx) run = split_run(G, cut, slot);
   const int nseg = nwhole + (cut.rem && slot < G.spx ? 2 : 0);
 
   for (int si = 0; si < nseg; ++si) {
@@ -210,9 +165,9 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
       te = ntiles;
     } else {
       seg = si - nwhole;
-      item = cut.start + cut.nfull + run_i0 + seg;
-      tb = seg == 0 ? run_lo - run_i0 * ntiles : 0;
-      te = seg == 0 ? min(run_hi - run_i0 * ntiles, ntiles) : run_hi - (run_i0 + 1) * ntiles;
+      item = cut.start + cut.nfull + run.i0 + seg;
+      tb = seg == 0 ? run.lo - run.i0 * ntiles : 0;
+      te = seg == 0 ? min(run.hi - run.i0 * ntiles, ntiles) : run.hi - (run.i0 + 1) * ntiles;
       if (te <= tb) continue;
     }
     const int head = item / G.nqb;
@@ -249,7 +204,6 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
       asm volatile("s_nop 7" ::: "memory");               // accvgpr writes settle before the first MFMA reads them
     }
     float mA = -INFINITY, mB = -INFINITY;                // running max (log2 domain) per query block; the row sums live in L fragments
-
 
     f32x16 sAa, sAb, sBa, sBb;          // scores: key half k0 (A) / k1 (B) x query block a / b
     bf16x8 pA[2][2], pB[2][2];          // numerators [query block][k-step of 16 keys]
@@ -364,7 +318,7 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
         else if (g & 1) mfma_s(Sb, kf[ks], 8 + ks);
         else mfma_s(Sa, kf[ks], ks);
         filler(g);
-        V3_SB();
+        RT_SB();
       }
     };
     // Oᵀ += Vᵀ·Pᵀ for one 32-key half (16 MFMAs: k-step x d block x query block)
@@ -377,7 +331,7 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
         if (h < 8) mfma_o((h >> 1) * 2 + (h & 1), vf[s2 * 4 + (h >> 1)], P[h & 1][s2]);
         else mfma_l(h & 1, P[h & 1][s2]);
         filler(g);
-        V3_SB();
+        RT_SB();
       }
     };
     // fillers of a group that finishes a half: max exchange (gaps 0, 1), decision (gap 2), numerators 16..31 (gaps 3..15)
@@ -392,8 +346,8 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
     };
     // fillers of a PV group that starts the next half: speculative numerators 0..15, its max chains
     auto first_half = [&](int g, f32x16& Sa, f32x16& Sb, bf16x8 (&P)[2][2]) __attribute__((always_inline)) {
-      if (g == 0) V3_PIN(Sa);                      // two MFMAs behind its last accumulation: safe to read from here on
-      if (g == 1) V3_PIN(Sb);
+      if (g == 0) RT_PIN(Sa);                      // two MFMAs behind its last accumulation: safe to read from here on
+      if (g == 1) RT_PIN(Sb);
       if (g >= 2 && g <= 17) elem(g - 2, Sa, Sb, P);     // elements 0..15, one per gap
       if (g == 18) elem_flush(P);
       if (g >= 1 && g <= 8) maxstep(g - 1, Sa, mxa0, mxa1);
@@ -425,14 +379,14 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
       } else {
         // first tile: no PV to overlap with; the scores of k0 need their 12 wait states before the VALU reads them
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");
-        V3_PIN(sAa); V3_PIN(sAb);
+        RT_PIN(sAa); RT_PIN(sAb);
 #pragma unroll
         for (int g = 0; g < 8; ++g) { maxstep(g, sAa, mxa0, mxa1); maxstep(g, sAb, mxb0, mxb1); }
 #pragma unroll
         for (int ks = 0; ks < 8; ++ks) kf[ks] = kread(1, ks);      // va already points at the segment's first stage
       }
       rka = mxa0; rkb = mxb0;                          // maxstep 7 leaves a chain's result in its first variable
-      V3_SB();
+      RT_SB();
       // ---- G3: Sᵀ(k1,t) ∥ exchange + decision for k0(t), numerators 16..31 (first tile: all 32) of k0(t), Vᵀ(k0,t) fragments
       qk_group(sBa, sBb, [&](int g) __attribute__((always_inline)) {
         if constexpr (first) {
@@ -450,7 +404,7 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
       if constexpr (!last) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        V3_SB();
+        RT_SB();
       }
       // ---- G4: PV(k0,t) ∥ speculative numerators 0..15 of k1(t), max chains of k1(t), K(k0,t+1) fragments, DMA of tile t+2
       pv_group(pA, [&](int g) __attribute__((always_inline)) {
@@ -464,7 +418,7 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
       rka = mxa0; rkb = mxb0;
       if constexpr (last) {
         // ---- drain: decision + numerators 16..31 of k1(t), then PV(k1,t)
-        V3_SB();
+        RT_SB();
         const float ea2 = exchange(rka), eb2 = exchange(rkb);
         decide(ea2, eb2, sBa, sBb, pB);
 #pragma unroll
@@ -472,7 +426,7 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
         elem_flush(pB);
 #pragma unroll
         for (int i = 0; i < 8; ++i) vf[(i >> 2) * 4 + (i & 3)] = vread(1, i >> 2, i & 3);
-        V3_SB();
+        RT_SB();
         pv_group(pB, [&](int) __attribute__((always_inline)) {});
       }
     };
@@ -509,7 +463,7 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
     const int jpart = slot;
     const int ritem = item - (cut.start + cut.nfull);            // index among the split items of this group
     {
-      char* rec = records + ((((int64_t)b * 8 + xcd) * G.spx + jpart) * 2 + seg) * (int64_t)REC3_B + wave * REC3_WAVE_B;
+      char* rec = records + split_rec_index(G, b, xcd, jpart, seg) * (int64_t)REC3_B + wave * REC3_WAVE_B;
       const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(rec, 0, REC3_WAVE_B, 0x00020000);
 #pragma unroll
       for (int f = 0; f < 8; ++f) {
@@ -523,43 +477,22 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
       const f32x4 ml = {mA, lA, mB, lB};
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ml), rs, 32768 + lane * 16, 0, 16);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");              // every storing wave drains its write-through stores
-    __syncthreads();
     int* cnt = counters + (int64_t)b * G.NI + item;
-    const unsigned U = (unsigned)cut.rem * (unsigned)ntiles, spx = (unsigned)G.spx;
-    const unsigned a = (unsigned)ritem * (unsigned)ntiles, bnd = a + (unsigned)ntiles;
-    const int j_first = (int)(((a + 1) * spx + U - 1) / U) - 1;
-    const int j_last = min(G.spx - 1, (int)((bnd * spx + U - 1) / U) - 1);
-    const int nparts = j_last - j_first + 1;
-    volatile int* flag = reinterpret_cast<volatile int*>(smem);
-    if (tid == 0) {
-      const int old = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      const int lastp = (old == nparts - 1) ? 1 : 0;
-      if (lastp) {
-        __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");                         // drop this CU's stale lines
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      *flag = lastp;
-    }
-    __syncthreads();
-    if (!__builtin_amdgcn_readfirstlane(*flag)) continue;
-    // record of splitting workgroup j for this item: its second segment when the item starts after the run does
+    const SplitParts parts = split_parts(G, cut, ritem);
+    if (!split_ticket(cnt, parts.nparts, reinterpret_cast<volatile int*>(smem), tid)) continue;
     auto rec_of = [&](int j) -> const char* {
-      const unsigned lo_j = (unsigned)j * U / spx;
-      const int sj = (a > lo_j) ? 1 : 0;
-      return records + ((((int64_t)b * 8 + xcd) * G.spx + j) * 2 + sj) * (int64_t)REC3_B + wave * REC3_WAVE_B;
+      return records + split_rec_index(G, b, xcd, j, split_seg_of(G, parts, j)) * (int64_t)REC3_B + wave * REC3_WAVE_B;
     };
     // pass 1: common maxima and the combined row sums; pass 2: per query block, weighted sums of the records IN RUN ORDER
     // (bitwise reproducible whatever the arrival order was). One query block's four fragments at a time: 64 accumulators.
     float MA = -INFINITY, MB = -INFINITY;
-    for (int j = j_first; j <= j_last; ++j) {
+    for (int j = parts.j_first; j <= parts.j_last; ++j) {
       const f32x4 ml = *reinterpret_cast<const f32x4*>(rec_of(__builtin_amdgcn_readfirstlane(j)) + 32768 + lane * 16);
       MA = fmaxf(MA, ml[0]);
       MB = fmaxf(MB, ml[2]);
     }
     float LA = 0.f, LB = 0.f;
-    for (int j = j_first; j <= j_last; ++j) {
+    for (int j = parts.j_first; j <= parts.j_last; ++j) {
       const f32x4 ml = *reinterpret_cast<const f32x4*>(rec_of(__builtin_amdgcn_readfirstlane(j)) + 32768 + lane * 16);
       LA = __builtin_fmaf(ml[1], __builtin_amdgcn_exp2f(ml[0] - MA), LA);
       LB = __builtin_fmaf(ml[3], __builtin_amdgcn_exp2f(ml[2] - MB), LB);
@@ -571,7 +504,7 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
       for (int dt = 0; dt < 4; ++dt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) t4[dt][r] = 0.f;
-      for (int j = j_first; j <= j_last; ++j) {
+      for (int j = parts.j_first; j <= parts.j_last; ++j) {
         const char* rj = rec_of(__builtin_amdgcn_readfirstlane(j));
         const f32x4 ml = *reinterpret_cast<const f32x4*>(rj + 32768 + lane * 16);
         const float w = __builtin_amdgcn_exp2f(qb ? ml[2] - MB : ml[0] - MA);
@@ -597,48 +530,30 @@ int v3_mode_now() {
   }
   return g_v3_mode;
 }
-V3Geom v3_geom(int S, int H, bool split) {
-  int dev = 0, cus = 256;
-  if (hipGetDevice(&dev) == hipSuccess) {
-    int x = 0;
-    if (hipDeviceGetAttribute(&x, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && x > 0) cus = x;
-  }
-  V3Geom G;
-  G.S = S; G.H = H; G.nqb = S / BQ3; G.ntiles = S / BKV; G.NI = H * G.nqb;
-  G.spx = cus / 8 > 0 ? cus / 8 : 1;
-  G.split = split ? 1 : 0;
-  return G;
-}
+SplitGeom v3_geom(int S, int H, bool split) { return split_geom(S, H, BQ3, BKV, split_cu_count() / 8, split); }   // one workgroup per CU
 
 }  // namespace
 
-// The counter region is laid out for attention.hip's item count (128-row items: twice ours), so one workspace serves either
-// kernel: both keep their counters inside it (zero at rest) and their records behind it.
-static int64_t v3_cnt_bytes(int32_t B, int32_t S, int32_t H) {
-  return (((int64_t)B * H * ((S + 127) / 128) * 4 + CNT_ALIGN - 1) / CNT_ALIGN) * CNT_ALIGN;
-}
 // Workspace attention_v3 wants for (B, S, H): ticket counters + partial records of the key-split tail; 0 when nothing would be split
 // or the shape is not taken. rt_attention_ws_bytes (attention.hip) returns the larger of the two kernels' needs.
 int64_t rt_attention_v3_ws_bytes(int32_t B, int32_t S, int32_t H) {
   if (S % BQ3 != 0) return 0;
-  const V3Geom G = v3_geom(S, H, true);
-  bool any = false;
-  for (int x = 0; x < 8; ++x) any = any || v3_cut(G, x).rem > 0;
-  if (!any) return 0;
-  return v3_cnt_bytes(B, S, H) + (int64_t)B * 8 * G.spx * 2 * REC3_B;
+  return split_ws_bytes(B, v3_geom(S, H, true), REC3_B);
 }
 
-// Called by rt_attention_fwd: returns 1 when the launch was taken over, 0 when the shape is left to attention.hip, < 0 / hipError on failure.
+// Called by rt_attention_fwd (declared, with its contract, in attention_split.h)
 int rt_attention_v3_try(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob,
-                        int32_t B, int32_t S, int32_t H, float scale, void* ws, int64_t ws_bytes, void* stream) {
-  if (!v3_mode_now() || S % BQ3 != 0 || (ldo % 8) || (stride_ob % 8) || !RT_ALIGNED(o, 16)) return 0;
+                        int32_t B, int32_t S, int32_t H, float scale, void* ws, int64_t ws_bytes, void* stream, int* taken) {
+  *taken = 0;
+  if (!v3_mode_now() || S % BQ3 != 0 || (ldo % 8) || (stride_ob % 8) || !RT_ALIGNED(o, 16)) return RT_OK;
   // short sequences (config 1's S = 768: 25 vs 19 us) stay with attention.hip, whose two workgroups per CU hide each other's
   // prologues; from ~1.5 k keys on the 64-rows-per-wave loop wins (S = 4608: 247 vs 264 us, S = 9728: 986 vs 1065 us)
-  if (v3_mode_now() == 1 && S < 1536) return 0;
+  if (v3_mode_now() == 1 && S < 1536) return RT_OK;
   const int64_t need = rt_attention_v3_ws_bytes(B, S, H);
-  const bool split = ws != nullptr && need > 0 && ws_bytes >= need && RT_ALIGNED(ws, 256);
-  const V3Geom G = v3_geom(S, H, split);
-  if ((int64_t)G.NI * (G.ntiles + 1) * G.spx >= ((int64_t)1 << 31)) return 0;
+  const bool split = ws != nullptr && need > 0 && ws_bytes >= need && RT_ALIGNED(ws, 256);   // unfit workspace: run unsplit
+  const SplitGeom G = v3_geom(S, H, split);
+  if (!split_fits_32bit(G)) return RT_OK;
+  *taken = 1;
   const int lds = NSTAGE * STAGE_B;
   static bool attr_done = false;
   if (!attr_done) {
@@ -648,16 +563,14 @@ int rt_attention_v3_try(const void* q, const void* k, const void* v, void* o, in
   }
   int slots = 0;
   for (int x = 0; x < 8; ++x) {
-    const V3Cut c = v3_cut(G, x);
+    const GroupCut c = group_cut(G, x);
     const int s = c.rem ? G.spx : (c.nfull < G.spx ? c.nfull : G.spx);
     slots = s > slots ? s : slots;
   }
-  const int64_t cnt_b = v3_cnt_bytes(B, S, H);
   hipLaunchKernelGGL(attention_v3_kernel, dim3(8 * slots, B), dim3(V3_THREADS), lds, (hipStream_t)stream, (const bf16_t*)q, (const bf16_t*)k,
                      (const bf16_t*)v, (bf16_t*)o, ld, stride_b, ldo, stride_ob, scale * 1.4426950408889634f, G, split ? (int*)ws : nullptr,
-                     split ? (char*)ws + cnt_b : nullptr);
-  const int st = rt_hip_status();
-  return st == RT_OK ? 1 : st;
+                     split ? (char*)ws + split_cnt_bytes(B, S, H) : nullptr);
+  return rt_hip_status();
 }
 
 int rt_attention_v3_mode(int mode) {

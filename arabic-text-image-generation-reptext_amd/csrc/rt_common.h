@@ -18,6 +18,34 @@ typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 #define LDS_PTR(p) ((__attribute__((address_space(3))) void*)(p))
 #define GLB_PTR(p) ((const __attribute__((address_space(1))) void*)(p))
 
+// Wave-uniform conditions that are almost never true (ragged last tile, a row maximum that outgrew the running one): tell the
+// block placement so, so that the rare code sits out of line and the common path falls through.
+#define RT_RARE(c) __builtin_expect(!!(c), 0)
+#define RT_USUAL(c) __builtin_expect(!!(c), 1)
+// Nothing is scheduled across this point.
+#define RT_SB() __builtin_amdgcn_sched_barrier(0)
+// Opaque use+def: the value must exist HERE. Keeps the optimiser from sinking a step's vector work below a later branch, and
+// nothing that reads v can be scheduled above it (attention_v3.hip keeps the 12 wait states between an asm MFMA, invisible to
+// hipcc's hazard recogniser, and a VALU read of its result by ORDER: two MFMAs always sit in between).
+#define RT_PIN(v) asm volatile("" : "+v"(v))
+
+// ---- pieces the attention kernels share (attention.hip, attention_v3.hip, attention_fp8.hip, vae_attention.hip) ------------------
+// LDS image of a 64-row × 256-B tile: 16-B chunk c of row r lives at 256·r + 16·(c ^ swz(r)) — conflict-free for row reads and
+// for the transposed reads. swz depends on r & 15 only.
+__device__ __forceinline__ int swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
+
+// 3-input max. Plain fmaxf so the compiler inserts the MFMA->VALU wait states itself: an inline-asm v_max3 here read the
+// accumulators before the MFMA had retired them (run-to-run differences in the running max). csrc/Makefile builds the attention
+// files with -fno-honor-nans (the `EXTRA :=` lines) so no canonicalising v_max is emitted in front and the pair folds to one
+// v_max3_f32.
+__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
+
+typedef const __attribute__((address_space(3))) char* lds_cptr;
+// ds_read_b64_tr_b16: the hardware-transposed LDS read that feeds Vᵀ fragments
+__device__ __forceinline__ s16x4 tr_read(lds_cptr p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
+}
+
 __device__ __forceinline__ float bf16_to_f32(bf16_t b) { return __uint_as_float(((uint32_t)b) << 16); }
 // round-to-nearest-even; plain cast keeps NaN a NaN (v_cvt_pk_bf16_f32 at -O3).
 __device__ __forceinline__ bf16_t f32_to_bf16(float f) {
@@ -133,7 +161,8 @@ __device__ __forceinline__ void rt_lds_barrier() {
 // ds_read_b64_tr_b16 of every attention tile, a third of the way into the tile: the copy for the NEXT tile was being waited for
 // there). An asm statement is invisible to that bookkeeping, so the copy stays in flight until OUR wait: every barrier that
 // publishes DMA-staged rows must be rt_dma_barrier() (s_waitcnt vmcnt(0) + barrier) or a counted wait. M0 (the LDS base of the
-// copy) is written in the same statement that uses it; nothing else in these kernels depends on M0.
+// copy) is written in the same statement that uses it; nothing else in these kernels depends on M0. (No "m0" clobber: it costs an
+// s_nop 0 behind every statement of the tile loops — DESIGN.md §3.)
 typedef __attribute__((ext_vector_type(4))) uint32_t rt_srd_t;
 __device__ __forceinline__ rt_srd_t rt_make_srd(const void* base) {
   const uint64_t a = reinterpret_cast<uint64_t>(base);

@@ -25,14 +25,6 @@ constexpr int SLICE_B = BKV * 256;      // one wave's K (or V) slice of a tile: 
 constexpr int XCH_WAVE_B = 64 * 64;     // one wave's partial scores: 16 fp32 per lane = 4 KiB
 constexpr float RESCALE_THR = 6.0f;     // log2 units, as in attention.hip
 
-__device__ __forceinline__ int swz(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
-__device__ __forceinline__ float max3f(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
-
-typedef const __attribute__((address_space(3))) char* lds_cptr;
-__device__ __forceinline__ s16x4 tr_read(lds_cptr p) {
-  return __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(p));
-}
-
 template <int NW>
 __global__ __launch_bounds__(NW * 64) void vae_attention_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                                 const bf16_t* __restrict__ V, bf16_t* __restrict__ O, int HW, int64_t ld,

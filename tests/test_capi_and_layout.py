@@ -113,3 +113,40 @@ def test_attention_v3_code_object_keeps_out_of_the_asm_owned_registers():
     r = subprocess.run(["make", "-C", os.path.join(PKG, "csrc"), "audit_v3"], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     assert "OK " in r.stdout
+
+
+# (B, S, H) -> rt_attention_ws_bytes on a 256-CU device, recorded from the library as it was BEFORE the key-split geometry of
+# csrc/attention.hip and csrc/attention_v3.hip moved into csrc/attention_split.h. The larger of the two kernels' needs: counters
+# for 128-row items + two records per splitting workgroup (67 584-B records on 64 workgroups per XCD group in attention.hip,
+# 135 168-B records on 32 in attention_v3: the same record bytes; S = 4500 is attention.hip's alone). 0: nothing splits.
+ATTENTION_WS_BYTES_256CU = {
+    (1, 4608, 24): 69209600,
+    (3, 4608, 24): 207628544,
+    (1, 4500, 24): 69209600,
+    (1, 4608, 2): 69206528,
+    (1, 4608, 4): 69206784,
+    (1, 2304, 8): 69206784,
+    (2, 2304, 7): 138413056,
+    (1, 2048, 8): 69206528,
+    (1, 9728, 24): 69213440,
+    (1, 1536, 24): 69207296,
+    (1, 768, 3): 0,
+    (1, 1024, 24): 0,
+    (1, 128, 1): 0,
+    (1, 200, 2): 0,
+    (0, 4608, 24): 0,
+}
+
+
+def test_attention_workspace_bytes_are_the_same_function_of_the_shape():
+    """The split geometry (cut rule, counter region, records per workgroup) decides the workspace size; it is a function of
+    (B, S, H, CU count) only. Without a device the CU query falls back to 256, the MI355X count."""
+    import torch
+
+    from reptext_amd import native
+
+    if torch.cuda.is_available() and torch.cuda.get_device_properties(0).multi_processor_count != 256:
+        pytest.skip("the recorded sizes are those of a 256-CU device")
+    lib = native.load()
+    got = {shape: lib.rt_attention_ws_bytes(*shape) for shape in ATTENTION_WS_BYTES_256CU}
+    assert got == ATTENTION_WS_BYTES_256CU

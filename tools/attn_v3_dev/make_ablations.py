@@ -10,14 +10,14 @@ src = open(os.path.join(csrc, "attention_v3.hip")).read()
 
 
 def rep(s, old, new):
-    assert s.count(old) >= 1, old[:70]
+    assert s.count(old) == 1, old[:70]
     return s.replace(old, new)
 
 
 VARIANTS = {
     "BASE": lambda s: s,
     "NODMA": lambda s: rep(s, "if (g >= 2 && g < 18 && (g & 1) == 0) dma_piece(sbp, so2, (g - 2) >> 1);", "(void)so2;"),
-    "NOBAR": lambda s: rep(s, '        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");\n        __builtin_amdgcn_s_barrier();\n        V3_SB();', "        V3_SB();"),
+    "NOBAR": lambda s: rep(s, '        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");\n        __builtin_amdgcn_s_barrier();\n        RT_SB();', "        RT_SB();"),
     "NOEXP": lambda s: rep(s, "float p = __builtin_amdgcn_exp2f(tf[o & 1]);", "float p = tf[o & 1];"),
     "NOL": lambda s: rep(s, "        else mfma_l(h & 1, P[h & 1][s2]);", "        else { }"),
     "NOSOFT": lambda s: rep(rep(s, "      if (pend2 >= 0) elem_c(pend2, P);\n      if (pend1 >= 0) elem_x(pend1);\n      elem_f(o, Sa, Sb);\n      pend2 = pend1;\n      pend1 = o;", "      (void)o;"),
@@ -27,8 +27,10 @@ VARIANTS = {
                            "      const s16x4 lo = tr_read((lds_cptr)(uintptr_t)(uint32_t)(va[dt] + kb * 8192 + s2 * 4096));\n      const s16x4 hi = tr_read((lds_cptr)(uintptr_t)(uint32_t)(va[4 + dt] + kb * 8192 + s2 * 4096));\n      return __builtin_shufflevector(__builtin_bit_cast(bf16x4, lo), __builtin_bit_cast(bf16x4, hi), 0, 1, 2, 3, 4, 5, 6, 7);",
                            "      return __builtin_bit_cast(bf16x8, i32x4v{va[dt], kb, s2, 2});"),
 }
-VARIANTS["NOPARTIAL"] = lambda s: rep(s, "    if (whole) {\n#pragma unroll\n      for (int f = 0; f < 8; ++f) oc[f] = o_read(f);\n    } else {", "    if (!whole) continue;\n    if (whole) {\n#pragma unroll\n      for (int f = 0; f < 8; ++f) oc[f] = o_read(f);\n    } else {")
-VARIANTS["NOCOMBINE"] = lambda s: rep(s, "      if (!lastp) continue;", "      if (true) continue;")
+# NOPARTIAL: a partial segment stores nothing (no record, no ticket, no combine); NOCOMBINE: records and tickets, but nobody combines
+VARIANTS["NOPARTIAL"] = lambda s: rep(s, "    if (whole) {\n      // ---- epilogue:", "    if (!whole) continue;\n    if (whole) {\n      // ---- epilogue:")
+VARIANTS["NOCOMBINE"] = lambda s: rep(s, "    if (!split_ticket(cnt, parts.nparts, reinterpret_cast<volatile int*>(smem), tid)) continue;",
+                                      "    split_ticket(cnt, parts.nparts, reinterpret_cast<volatile int*>(smem), tid);\n    if (true) continue;")
 VARIANTS["MFMAONLY"] = lambda s: VARIANTS["NOLDS"](VARIANTS["NOSOFT"](VARIANTS["NODMA"](VARIANTS["NOBAR"](s))))
 VARIANTS["NOSOFT_NOLDS"] = lambda s: VARIANTS["NOLDS"](VARIANTS["NOSOFT"](s))
 objs = [os.path.join(csrc, "build", f) for f in os.listdir(os.path.join(csrc, "build")) if f.endswith(".o") and f != "attention_v3.o"]
