@@ -15,7 +15,7 @@ LIB_NAME = "librt_reptext_hip.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 RT_GEMM_MAX_GROUPS = 4
-ABI_VERSION = 12
+ABI_VERSION = 13
 RT_LORA_MAX_TERMS = 8
 
 
@@ -141,6 +141,11 @@ SIGNATURES["rt_lora_merge_bf16"] = [C.POINTER(LoraTerm), _i32, _vp, _i64, _vp, _
 
 # IP-Adapter cross-attention (csrc/ip_attention.hip)
 SIGNATURES["rt_ip_attention"] = [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp]
+
+# CLIP vision encoder (csrc/attention_hd64.hip, csrc/image_encoder.hip)
+RT_ATTENTION_HD64_MAX_S = 4096
+SIGNATURES["rt_attention_hd64"] = [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _f32, _vp]
+SIGNATURES["rt_patchify_nchw"] = [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]
 
 # loop passes that moved out of the 256x256-tile GEMM / were merged (csrc/gemm_skinny.hip, csrc/norm_elem.hip)
 SIGNATURES["rt_gemm_skinny_bf16"] = [_vp, _vp, _i64, _i32, _i32, C.POINTER(SkinnyGroup), _i32, _vp]

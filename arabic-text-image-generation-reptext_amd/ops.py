@@ -575,6 +575,38 @@ def ip_attention(q: torch.Tensor, wq: torch.Tensor, k: torch.Tensor, v: torch.Te
     return out
 
 
+def attention_hd64(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, scale: Optional[float] = None) -> torch.Tensor:
+    """out[b, s, h·64:(h+1)·64] = softmax(scale · q_h k_hᵀ) v_h (rt_attention_hd64): non-causal self-attention with heads of 64, one
+    launch. q, k, v [B,S,H·64] bf16 views of one buffer sharing strides (the fused q|k|v projection); out [B,S,H·64] bf16 view with its
+    own strides; 1 <= S <= native.RT_ATTENTION_HD64_MAX_S."""
+    d = H * 64
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] != d:
+            raise ValueError(f"{name}: need [B,S,{d}] with unit inner stride, got {tuple(t.shape)} / {t.stride()}")
+    B, S, _ = q.shape
+    if not (q.stride() == k.stride() == v.stride()) or k.shape != q.shape or v.shape != q.shape or out.shape != q.shape:
+        raise ValueError("q,k,v must share shape and strides; out must have their shape")
+    if not 1 <= S <= native.RT_ATTENTION_HD64_MAX_S:
+        raise ValueError(f"attention_hd64: 1..{native.RT_ATTENTION_HD64_MAX_S} rows, got {S}")
+    native.check("rt_attention_hd64", native.load().rt_attention_hd64(
+        _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), q.stride(1), q.stride(0), _dev(out, "out", BF16), out.stride(1),
+        out.stride(0), B, S, H, float(scale if scale is not None else 64 ** -0.5), _stream()))
+    return out
+
+
+def patchify_nchw(x: torch.Tensor, patch: int, Kp: Optional[int] = None) -> torch.Tensor:
+    """im2col of a stride-p, kernel-p convolution (rt_patchify_nchw): x [B,3,G·p,G·p] f32 or bf16 -> bf16 [B, G², Kp] with
+    row[gy·G + gx][c·p² + dy·p + dx] = x[b, c, gy·p + dy, gx·p + dx] and zero columns from 3p² up to Kp (default: 3p² rounded up to 64)."""
+    if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] != x.shape[3] or x.shape[2] % patch or x.dtype not in (BF16, F32):
+        raise ValueError(f"patchify_nchw: need a square f32 or bf16 [B,3,G*{patch},G*{patch}] image, got {tuple(x.shape)} {x.dtype}")
+    x = x.contiguous()
+    B, G = x.shape[0], x.shape[2] // patch
+    Kp = (3 * patch * patch + 63) // 64 * 64 if Kp is None else int(Kp)
+    out = torch.empty(B, G * G, Kp, device=x.device, dtype=BF16)
+    native.check("rt_patchify_nchw", native.load().rt_patchify_nchw(_dev(x, "x"), int(x.dtype == F32), out.data_ptr(), B, G, patch, Kp, _stream()))
+    return out
+
+
 def attention_fp8_prep(buf: torch.Tensor, q_off: int, k_off: int, v_off: int, H: int, T: int, wq_txt, wk_txt, wq_img, wk_img,
                        cos: torch.Tensor, sin: torch.Tensor, qk8: torch.Tensor, vt8: torch.Tensor, eps: float = 1e-6) -> None:
     """From the fused projection buffer buf [B,S,ld] bf16 (not modified): qk8 [B,S,2·H·128] e4m3 = 16 · RoPE(RMSNorm(q | k)),

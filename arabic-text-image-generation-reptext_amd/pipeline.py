@@ -143,6 +143,8 @@ class FluxControlNetPipeline:
         self._guidance_scale, self._joint_attention_kwargs, self._interrupt, self._num_timesteps = 1.0, None, False, 0
         self._progress_disabled = False
         self._ip_call_args, self._ip_embeds = (None, None), None
+        # the IP-Adapter's image side (image_encoder.py); set by from_pretrained / load_ip_adapter or assigned, not components
+        self.image_encoder, self.feature_extractor = None, None
 
     # ------------------------------------------------------------------ component plumbing
     @property
@@ -183,6 +185,11 @@ class FluxControlNetPipeline:
         vae = kwargs.pop("vae", None) or AutoencoderKL.from_pretrained(root, torch_dtype=dt, subfolder="vae")
         te, te2 = kwargs.pop("text_encoder", None), kwargs.pop("text_encoder_2", None)
         tok, tok2 = kwargs.pop("tokenizer", None), kwargs.pop("tokenizer_2", None)
+        image_encoder, feature_extractor = kwargs.pop("image_encoder", None), kwargs.pop("feature_extractor", None)
+        if image_encoder is None and index.get("image_encoder") not in (None, [None, None]) and os.path.isdir(os.path.join(root, "image_encoder")):
+            from .image_encoder import CLIPVisionModelWithProjection
+
+            image_encoder = CLIPVisionModelWithProjection.from_pretrained(root, subfolder="image_encoder", torch_dtype=dt)
         try:
             if te is None and listed("text_encoder") and os.path.isdir(os.path.join(root, "text_encoder")):
                 from .text_encoders import CLIPTextModel                 # the encoders themselves run on the HIP kernels
@@ -205,8 +212,10 @@ class FluxControlNetPipeline:
         if isinstance(controlnet, str):
             controlnet = FluxControlNetModel.from_pretrained(controlnet, torch_dtype=dt)
         extra = {k: kwargs[k] for k in ("controlnet_inpaint",) if k in kwargs}
-        return cls(scheduler=scheduler, vae=vae, text_encoder=te, tokenizer=tok, text_encoder_2=te2, tokenizer_2=tok2,
+        pipe = cls(scheduler=scheduler, vae=vae, text_encoder=te, tokenizer=tok, text_encoder_2=te2, tokenizer_2=tok2,
                    transformer=transformer, controlnet=controlnet, **extra)
+        pipe.image_encoder, pipe.feature_extractor = image_encoder, feature_extractor
+        return pipe
 
     def save_pretrained(self, root: str, max_shard_bytes: int = 10 << 30) -> None:
         """Write the diffusers layout this class loads: model_index.json, scheduler/scheduler_config.json and one folder per
@@ -235,7 +244,7 @@ class FluxControlNetPipeline:
             json.dump(index, f, indent=2)
 
     def to(self, device=None, dtype=None):
-        for m in self.components.values():
+        for m in list(self.components.values()) + [self.image_encoder]:
             if isinstance(m, torch.nn.Module):
                 m.to(device=device, dtype=dtype) if dtype is not None else m.to(device)
         return self
@@ -502,11 +511,33 @@ class FluxControlNetPipeline:
         self.transformer.disable_adapters()
 
     # ------------------------------------------------------------------ IP-Adapter (image prompt): the FluxIPAdapterMixin subset, routed
-    # to the transformer (ip_adapter.py). No image encoder is built here: callers pass `ip_adapter_image_embeds`.
+    # to the transformer (ip_adapter.py); the image side is image_encoder.CLIPVisionModelWithProjection.
     def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder: Optional[str] = None, weight_name: Optional[str] = None,
-                        image_encoder_pretrained_model_name_or_path: Optional[str] = None, **kwargs):
-        """``image_encoder_pretrained_model_name_or_path`` is accepted for interface parity and ignored (no CLIP vision encoder)."""
+                        image_encoder_pretrained_model_name_or_path: Optional[str] = None, image_encoder_subfolder: Optional[str] = None,
+                        **kwargs):
+        """``image_encoder_pretrained_model_name_or_path`` (+ ``image_encoder_subfolder``): a local directory, or a hub id in the local
+        hub cache, that holds a CLIP vision ``config.json`` — loaded as ``self.image_encoder``. A name that does not resolve to one
+        leaves the pipeline's encoder as it is (one log line): nothing is fetched, and ``ip_adapter_image_embeds`` need no encoder."""
         self.transformer.load_ip_adapter(pretrained_model_name_or_path_or_dict, subfolder=subfolder, weight_name=weight_name)
+        name = image_encoder_pretrained_model_name_or_path
+        if name is None:
+            return
+        from .modules import resolve_model_path
+
+        try:
+            d = resolve_model_path(name)
+            d = os.path.join(d, image_encoder_subfolder) if image_encoder_subfolder else d
+        except OSError:
+            d = None
+        if d is None or not os.path.isfile(os.path.join(d, "config.json")):
+            import sys
+            print(f"[reptext_amd] load_ip_adapter: image encoder '{name}' is not a local directory with a config.json; keeping "
+                  f"image_encoder = {type(self.image_encoder).__name__}", file=sys.stderr, flush=True)
+            return
+        from .image_encoder import CLIPVisionModelWithProjection
+
+        enc = CLIPVisionModelWithProjection.from_pretrained(d, torch_dtype=torch.bfloat16)
+        self.image_encoder = enc.to(self.transformer.device)
 
     def set_ip_adapter_scale(self, scale):
         self.transformer.set_ip_adapter_scale(scale)
@@ -519,10 +550,20 @@ class FluxControlNetPipeline:
         embeds). The embeds may also arrive as joint_attention_kwargs["ip_adapter_image_embeds"], where diffusers' pipeline puts them."""
         from . import ip_adapter as _ipa
 
-        if ip_adapter_image is not None:
-            raise NotImplementedError("ip_adapter_image needs an image encoder, which this pipeline does not have: encode the image "
-                                      "yourself and pass ip_adapter_image_embeds")
         kw = joint_attention_kwargs
+        if ip_adapter_image is not None:
+            if ip_adapter_image_embeds is not None or (kw is not None and "ip_adapter_image_embeds" in kw):
+                raise ValueError("pass either ip_adapter_image or ip_adapter_image_embeds, not both")
+            if self.image_encoder is None:
+                raise NotImplementedError("ip_adapter_image needs an image encoder, which this pipeline does not have: encode the image "
+                                          "yourself and pass ip_adapter_image_embeds")
+            if isinstance(ip_adapter_image, torch.Tensor):
+                n = ip_adapter_image.shape[0] if ip_adapter_image.dim() == 4 else 1
+            else:
+                n = len(ip_adapter_image) if isinstance(ip_adapter_image, (list, tuple)) else 1
+            if n not in (1, batch_size):
+                raise ValueError(f"ip_adapter_image: {n} images for a batch of {batch_size} (one image per sample, or one for all)")
+            ip_adapter_image_embeds = self.encode_image(ip_adapter_image, device)      # from here on as if the caller had passed them
         if kw is not None and "ip_adapter_image_embeds" in kw:
             if ip_adapter_image_embeds is not None:
                 raise ValueError("ip_adapter_image_embeds were passed both as an argument and inside joint_attention_kwargs")
@@ -544,6 +585,24 @@ class FluxControlNetPipeline:
         if not adapter.active:
             return None, kw
         return e.to(device=device, dtype=torch.bfloat16).contiguous(), kw
+
+    def encode_image(self, image, device=None, num_images_per_prompt: int = 1) -> torch.Tensor:
+        """[B·num_images_per_prompt, projection_dim] bf16 image embeddings of ``self.image_encoder``. A tensor is taken as
+        ``pixel_values`` (diffusers' rule); anything else goes through ``self.feature_extractor(images=..., return_tensors="pt")``
+        when one is set, else ``image_encoder.clip_preprocess`` at the encoder's image size. One encoder run on the current stream."""
+        if self.image_encoder is None:
+            raise ValueError("encode_image: this pipeline has no image_encoder")
+        device = device or self._execution_device
+        if isinstance(image, torch.Tensor):
+            pixel_values = image if image.dim() == 4 else image[None]
+        elif self.feature_extractor is not None:
+            pixel_values = self.feature_extractor(images=image, return_tensors="pt").pixel_values
+        else:
+            from .image_encoder import clip_preprocess
+
+            pixel_values = clip_preprocess(image, size=self.image_encoder.config.image_size)
+        embeds = self.image_encoder(pixel_values.to(device)).image_embeds
+        return embeds.repeat_interleave(num_images_per_prompt, dim=0) if num_images_per_prompt != 1 else embeds
 
     def _lora_models(self) -> list:
         cn = self.controlnet

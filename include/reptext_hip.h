@@ -332,6 +332,34 @@ int rt_gated_mul(const void* x, int64_t ldx, void* out, int64_t ldo, int32_t row
 /* CLIP quick_gelu in place on n bf16 values: x · sigmoid(1.702 x). */
 int rt_quick_gelu(void* x, int64_t n, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * CLIP vision encoder (ABI 13; image_encoder.py: `CLIPVisionModelWithProjection`, the image encoder behind the pipeline's
+ * ip_adapter_image=). Once per image prompt, outside the loop. Matrix work is rt_gemm_bf16, norms rt_layernorm_modulate.
+ * ---------------------------------------------------------------------------------------- */
+/* Self-attention with heads of 64, non-causal, no bias (csrc/attention_hd64.hip):
+ *   o[b][s][h*64 .. h*64+63] = softmax(scale * q_h k_h^T) v_h        for every batch entry b, head h and row s < S
+ * q / k / v: bf16 views of one fused [B][S][ld] buffer (common row stride ld and batch stride stride_b, in elements; ld = 3*H*64 for
+ * the fused q|k|v projection), head h at column h*64; o: bf16 [B][S][ldo]. Both products on v_mfma_f32_16x16x32_bf16; scores, row
+ * maximum, row sum and accumulators fp32; P rounded to bf16 as the second product's operand; online softmax over key tiles of 64,
+ * o normalised once at the end; keys past S are padded inside the kernel and masked. Only rows < S and columns < H*64 of each batch
+ * entry of o are written; no atomics: two runs give the same bits. Any 1 <= S <= RT_ATTENTION_HD64_MAX_S. Replaces, with one
+ * launch, the per-(batch, head) rt_gemm_bf16 -> rt_softmax_rows_bias -> rt_transpose_bf16 -> rt_gemm_bf16 chain and its
+ * [S][S] fp32 score matrix (1536 launches per image for ViT-L/14's 24 layers x 16 heads).
+ * Rejected on the host: null pointers, B / S / H < 1, scale <= 0, ld or ldo < H*64, a negative batch stride (RT_E_BADARG);
+ * S > RT_ATTENTION_HD64_MAX_S, B or H > 65535 (RT_E_SHAPE); pointers not 16-byte aligned, ld / ldo / a batch stride not a multiple of
+ * 8 (RT_E_ALIGN). */
+#define RT_ATTENTION_HD64_MAX_S 4096
+int rt_attention_hd64(const void* q, const void* k, const void* v, int64_t ld, int64_t stride_b,
+                      void* o, int64_t ldo, int64_t stride_ob,
+                      int32_t B, int32_t S, int32_t H, float scale, void* stream);
+/* im2col of CLIPVisionEmbeddings.patch_embedding (Conv2d(3, d, kernel p, stride p, no bias)), feeding rt_gemm_bf16:
+ *   out[b*G*G + gy*G + gx][c*p*p + dy*p + dx] = bf16(x[b][c][gy*p + dy][gx*p + dx]),   columns 3*p*p .. Kp-1 = 0
+ * x: f32 (x_f32) or bf16 NCHW [B][3][G*p][G*p], contiguous; out: bf16 [B*G*G][Kp], Kp = 3*p*p rounded up to the GEMM's K % 64
+ * (588 -> 640 for p = 14); the weight [d][3][p][p] is reshaped and zero-padded to [d][Kp] once by the caller.
+ * Rejected on the host: null pointers, B / G / p < 1, Kp < 3*p*p (RT_E_BADARG); p > 1024, G > 4096, more than 2^31 - 256 16-byte
+ * chunks of output (RT_E_SHAPE); Kp % 64, out not 16-byte aligned, x not aligned to its element (RT_E_ALIGN). */
+int rt_patchify_nchw(const void* x, int32_t x_f32, void* out, int32_t B, int32_t G, int32_t p, int32_t Kp, void* stream);
+
 /* FlowMatchEulerDiscreteScheduler.step (PIPE:1109; A.6): x = bf16(f32(x) + dsigma·f32(v)), in place. */
 int rt_euler_step(void* x, const void* v, float dsigma, int64_t n, void* stream);
 
