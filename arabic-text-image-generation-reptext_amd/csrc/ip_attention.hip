@@ -1,4 +1,7 @@
 // rt_ip_attention — o (+)= ip_scale · softmax(bf16(rmsnorm(q)·wq) · Kᵀ · sm_scale) · V: the IP-Adapter term of a double block.
+// rt_ip_attention_gated — the same body with an optional fp32 column gate multiplied into ip_scale · acc before the write or
+// accumulate (GATED instantiations; the ungated ones are the code rt_ip_attention has always run): the InstantX form, whose term of a
+// double block goes through the adaLN gate_msa straight onto the residual rows, and whose single blocks query with all S rows.
 //
 // Rectangular attention of many query rows (N image tokens) against a handful of image-prompt keys (1 <= n_ip <= 128), one pass,
 // no online softmax. Bound by memory: q is read once and o written once; K and V of a head (<= 64 KiB) are staged in LDS once per
@@ -29,12 +32,14 @@ struct IpArgs {
   const bf16_t* k;
   const bf16_t* v;
   void* o;
+  const float* gate;           // GATED only: [B][>= H·128] fp32, batch stride stride_gb
+  int64_t stride_gb;
   int64_t ldq, stride_qb, ldkv, stride_kvb, ldo, stride_ob;
   int32_t N, n_ip, o_f32, accumulate;
   float sm_scale_log2, ip_scale, eps;
 };
 
-template <int KB, int TILES>   // key blocks of 32; 16-row tiles per wave
+template <int KB, int TILES, bool GATED>   // key blocks of 32; 16-row tiles per wave; an fp32 gate per output column
 __global__ __launch_bounds__(256) void ip_attention_kernel(const IpArgs a) {
   // Vᵀ row stride (elements): NP + 8 puts the 16 rows x 2 lane groups of a half-wave's 8-byte reads on 64 distinct banks
   constexpr int NP = KB * 32, VLD = NP + 8;
@@ -95,6 +100,9 @@ __global__ __launch_bounds__(256) void ip_attention_kernel(const IpArgs a) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) dst[s] = *reinterpret_cast<const u32x4*>(qr + 32 * s);
   };
+  // the lane's output columns are h·128 + 32cp + 8g + 0..7, cp = 0..3: their gate values are read per tile (L1/L2 hits; 12 KiB per
+  // batch entry) instead of held in 32 more registers
+  const float* grow = GATED ? a.gate + (int64_t)b * a.stride_gb + h * 128 + 8 * g : nullptr;
   u32x4 qnext[4];
   load_q(0, qnext);
   __syncthreads();                                // K / Vᵀ staged (the q loads above are already in flight)
@@ -187,6 +195,7 @@ __global__ __launch_bounds__(256) void ip_attention_kernel(const IpArgs a) {
       for (int c = 0; c < 8; ++c) {
         f32x4* p = reinterpret_cast<f32x4*>(orow + 32 * (c >> 1) + 4 * (c & 1));
         f32x4 x = ot[c] * inv;
+        if (GATED) x *= *reinterpret_cast<const f32x4*>(grow + 32 * (c >> 1) + 4 * (c & 1));
         if (a.accumulate) x += *p;
         *p = x;
       }
@@ -200,6 +209,14 @@ __global__ __launch_bounds__(256) void ip_attention_kernel(const IpArgs a) {
         for (int e = 0; e < 4; ++e) {
           x[e] = ot[2 * cp][e] * inv;
           x[4 + e] = ot[2 * cp + 1][e] * inv;
+        }
+        if (GATED) {
+          const f32x4 g0 = *reinterpret_cast<const f32x4*>(grow + 32 * cp), g1 = *reinterpret_cast<const f32x4*>(grow + 32 * cp + 4);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            x[e] *= g0[e];
+            x[4 + e] *= g1[e];
+          }
         }
         if (a.accumulate) {
           const u32x4 old = *p;
@@ -215,20 +232,32 @@ __global__ __launch_bounds__(256) void ip_attention_kernel(const IpArgs a) {
   }
 }
 
+template <bool GATED>
+void launch_ip(const IpArgs& a, int B, int H, hipStream_t st) {
+  const int kb = (a.n_ip + 31) / 32, rows_per_wg = kb == 4 ? 256 : 128;
+  const dim3 grid(H, (a.N + rows_per_wg - 1) / rows_per_wg, B), block(256);
+  switch (kb) {
+    case 1: hipLaunchKernelGGL((ip_attention_kernel<1, 2, GATED>), grid, block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((ip_attention_kernel<2, 2, GATED>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((ip_attention_kernel<3, 2, GATED>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((ip_attention_kernel<4, 4, GATED>), grid, block, 0, st, a); break;
+  }
+}
+
 }  // namespace
 
-extern "C" int rt_ip_attention(const void* q, int64_t ldq, int64_t stride_qb, const void* wq, const void* k, const void* v,
-                               int64_t ldkv, int64_t stride_kvb, void* o, int64_t ldo, int64_t stride_ob, int32_t o_f32,
-                               int32_t accumulate, int32_t B, int32_t N, int32_t H, int32_t n_ip, float sm_scale, float ip_scale,
-                               float eps, void* stream) {
+extern "C" int rt_ip_attention_gated(const void* q, int64_t ldq, int64_t stride_qb, const void* wq, const void* k, const void* v,
+                                     int64_t ldkv, int64_t stride_kvb, const float* gate, int64_t stride_gb, void* o, int64_t ldo,
+                                     int64_t stride_ob, int32_t o_f32, int32_t accumulate, int32_t B, int32_t N, int32_t H, int32_t n_ip,
+                                     float sm_scale, float ip_scale, float eps, void* stream) {
   if (!q || !wq || !k || !v || !o || B < 1 || N < 1 || H < 1 || n_ip < 1) return RT_E_BADARG;
   if (!(sm_scale > 0.0f)) return RT_E_BADARG;     // the row maximum is taken before the scale is applied
   if (n_ip > 128 || (N + 127) / 128 > 65535 || B > 65535) return RT_E_SHAPE;
   const int64_t d = (int64_t)H * 128;
-  if (ldq < d || ldkv < d || ldo < d || stride_qb < 0 || stride_kvb < 0 || stride_ob < 0) return RT_E_BADARG;
+  if (ldq < d || ldkv < d || ldo < d || stride_qb < 0 || stride_kvb < 0 || stride_ob < 0 || (gate && stride_gb < 0)) return RT_E_BADARG;
   const int o_align = o_f32 ? 4 : 8;     // elements per 16 bytes
   if (!RT_ALIGNED(q, 16) || !RT_ALIGNED(wq, 16) || !RT_ALIGNED(k, 16) || !RT_ALIGNED(v, 16) || !RT_ALIGNED(o, 16) || ldq % 8 ||
-      stride_qb % 8 || ldkv % 8 || stride_kvb % 8 || ldo % o_align || stride_ob % o_align)
+      stride_qb % 8 || ldkv % 8 || stride_kvb % 8 || ldo % o_align || stride_ob % o_align || (gate && (!RT_ALIGNED(gate, 16) || stride_gb % 4)))
     return RT_E_ALIGN;
   IpArgs a;
   a.q = (const bf16_t*)q;
@@ -236,6 +265,8 @@ extern "C" int rt_ip_attention(const void* q, int64_t ldq, int64_t stride_qb, co
   a.k = (const bf16_t*)k;
   a.v = (const bf16_t*)v;
   a.o = o;
+  a.gate = gate;
+  a.stride_gb = gate ? stride_gb : 0;
   a.ldq = ldq;
   a.stride_qb = stride_qb;
   a.ldkv = ldkv;
@@ -249,14 +280,15 @@ extern "C" int rt_ip_attention(const void* q, int64_t ldq, int64_t stride_qb, co
   a.sm_scale_log2 = sm_scale * 1.4426950408889634f;
   a.ip_scale = ip_scale;
   a.eps = eps;
-  const int kb = (n_ip + 31) / 32, rows_per_wg = kb == 4 ? 256 : 128;
-  const dim3 grid(H, (N + rows_per_wg - 1) / rows_per_wg, B), block(256);
-  const hipStream_t st = (hipStream_t)stream;
-  switch (kb) {
-    case 1: hipLaunchKernelGGL((ip_attention_kernel<1, 2>), grid, block, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((ip_attention_kernel<2, 2>), grid, block, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((ip_attention_kernel<3, 2>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((ip_attention_kernel<4, 4>), grid, block, 0, st, a); break;
-  }
+  if (gate) launch_ip<true>(a, B, H, (hipStream_t)stream);
+  else launch_ip<false>(a, B, H, (hipStream_t)stream);
   return rt_hip_status();
+}
+
+extern "C" int rt_ip_attention(const void* q, int64_t ldq, int64_t stride_qb, const void* wq, const void* k, const void* v,
+                               int64_t ldkv, int64_t stride_kvb, void* o, int64_t ldo, int64_t stride_ob, int32_t o_f32,
+                               int32_t accumulate, int32_t B, int32_t N, int32_t H, int32_t n_ip, float sm_scale, float ip_scale,
+                               float eps, void* stream) {
+  return rt_ip_attention_gated(q, ldq, stride_qb, wq, k, v, ldkv, stride_kvb, nullptr, 0, o, ldo, stride_ob, o_f32, accumulate, B, N, H,
+                               n_ip, sm_scale, ip_scale, eps, stream);
 }

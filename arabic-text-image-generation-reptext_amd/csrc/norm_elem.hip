@@ -537,6 +537,33 @@ int launch_layernorm(const LnLaunch& L, int x_f32, int D, float eps, void* strea
   return rt_hip_status();
 }
 
+// y = bf16(gelu(x)), the exact (erf) form 0.5 x (1 + erf(x / sqrt 2)): the InstantX image projection's activation (the GEMM epilogue
+// has the tanh form only). x fp32 as the GEMM wrote it, so the hidden is rounded once.
+__global__ void gelu_erf_kernel(const float* __restrict__ x, bf16_t* __restrict__ y, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float v = x[i];
+    y[i] = f32_to_bf16(0.5f * v * (1.0f + erff(v * 0.70710678118654752f)));
+  }
+}
+
+// y[b][r][:] = bf16(y[b][r][:] + x[b][r][:]) on bf16 views with their own row and batch strides, 8 elements per lane
+__global__ void add_bf16_2d_kernel(const bf16_t* __restrict__ x, int64_t ldx, int64_t stride_xb, bf16_t* __restrict__ y, int64_t ldy,
+                                   int64_t stride_yb, int batch, int rows, int D8) {
+  const int64_t n = (int64_t)batch * rows * D8;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(i % D8);
+    const int64_t br = i / D8;
+    const int r = (int)(br % rows), b = (int)(br / rows);
+    const u32x4 a = *reinterpret_cast<const u32x4*>(x + b * stride_xb + r * ldx + 8 * c);
+    u32x4* yp = reinterpret_cast<u32x4*>(y + b * stride_yb + r * ldy + 8 * c);
+    const u32x4 o = *yp;
+    u32x4 w;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) w[j] = pack_bf16x2(bf16lo(o[j]) + bf16lo(a[j]), bf16hi(o[j]) + bf16hi(a[j]));
+    *yp = w;
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -762,6 +789,22 @@ int rt_masked_accumulate(const void* x, void* y, const float* rowscale, float al
   }
   hipLaunchKernelGGL(masked_accumulate_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
                      (const bf16_t*)x, (bf16_t*)y, rowscale, alpha, batch, rows, D / 8, accumulate);
+  return rt_hip_status();
+}
+
+int rt_gelu_erf_bf16(const float* x, void* y, int64_t n, void* stream) {
+  if (!x || !y || n < 1) return RT_E_BADARG;
+  hipLaunchKernelGGL(gelu_erf_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)y, n);
+  return rt_hip_status();
+}
+
+int rt_add_bf16_2d(const void* x, int64_t ldx, int64_t stride_xb, void* y, int64_t ldy, int64_t stride_yb, int32_t batch, int32_t rows,
+                   int32_t D, void* stream) {
+  if (!x || !y || batch < 1 || rows < 1 || D < 8 || ldx < D || ldy < D || stride_xb < 0 || stride_yb < 0) return RT_E_BADARG;
+  if (D % 8) return RT_E_SHAPE;
+  if (!RT_ALIGNED(x, 16) || !RT_ALIGNED(y, 16) || ldx % 8 || ldy % 8 || stride_xb % 8 || stride_yb % 8) return RT_E_ALIGN;
+  hipLaunchKernelGGL(add_bf16_2d_kernel, dim3(grid_for((int64_t)batch * rows * (D / 8), 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)x, ldx, stride_xb, (bf16_t*)y, ldy, stride_yb, batch, rows, D / 8);
   return rt_hip_status();
 }
 

@@ -1,4 +1,5 @@
-"""FLUX IP-Adapter (image prompt) for the transformer's double blocks: checkpoint reader, adapter state, loop-invariant set-up.
+"""FLUX IP-Adapter (image prompt): checkpoint reader, adapter state, loop-invariant set-up. Two forms: the diffusers / XLabs one (one
+ungated term per double block, below) and the InstantX one (a term inside every block, double and single; further below).
 
 With C = joint_attention_dim, d = inner_dim, H heads of 128, E = image embedding width, n = tokens per image prompt:
 
@@ -16,8 +17,29 @@ The adapter is held on the transformer as ``_ip_adapter`` — plain tensors, NOT
 Two key layouts, one table each (``_LAYOUTS``):
   diffusers  image_proj.proj.* / image_proj.norm.* / ip_adapter.{i}.to_k_ip.* / ip_adapter.{i}.to_v_ip.*
   XLabs      ip_adapter_proj_model.proj.* / .norm.* / double_blocks.{i}.processor.ip_adapter_double_stream_k_proj.* / _v_proj.*
-Refused with a ValueError naming the key: unknown keys, keys of single blocks (the InstantX layout), a block count other than
+Refused with a ValueError naming the key: unknown keys, keys that name single blocks, a block count other than
 num_layers, norm width != C, K/V out-features != d or in-features != C, a non-integer or > 128 token count, missing biases.
+
+The InstantX form (``InstantX/FLUX.1-dev-IP-Adapter``; layout "instantx", recognised by ``image_proj.proj.0.weight``), with
+L2 = num_layers, L1 = num_single_layers and j over all L2 + L1 blocks, double blocks first:
+
+  1. tok  = LayerNorm_C(reshape(Linear_{2E -> n·C}(GELU(Linear_{E -> 2E}(embeds))), [B, n, C]))   biases, exact (erf) GELU, eps 1e-5
+  2. K_j  = rmsnorm_128(to_k_ip_j(tok)), V_j = to_v_ip_j(tok)    Linear_{C -> d} WITHOUT bias; the norm per head, eps 1e-5, no weight,
+                                                                  on K only; K rounded to bf16 after the norm; no RoPE
+  3. ip_j = softmax(q̂ K_jᵀ / √128) V_j      q̂ = the block's query after norm_q, before RoPE: the image rows of a double block, ALL
+                                              S = T + N rows (text rows included) of a single block   (rt_ip_attention_gated)
+  4. double block: h <- h + gate_msa · (to_out(attn_img) + s_j · ip_j)     (gated; the text stream is untouched)
+     single block: x <- x + gate · proj_out([attn + s_j · ip_j | gelu(mlp)])
+  5. s_j: one float per block, default 1.0.
+
+Rules recalled from InstantX's IPAFluxAttnProcessor2_0, MLPProjModel and transformer_flux.py; neither they nor diffusers can be read
+offline, so parity with upstream is unpinned here too. What the tests pin is parity with an fp32 restatement of exactly these rules
+(tests/instantx_reference.py). Keys: image_proj.proj.{0,2}.{weight,bias}, image_proj.norm.{weight,bias}, ip_adapter.{j}.to_{k,v}_ip.weight
+— as a flat dict, a flat .safetensors file, or the upstream ``ip-adapter.bin`` (torch.save of {"image_proj": {...}, "ip_adapter": {...}},
+read with weights_only=True). Refused, naming the key: a block count other than L2 + L1, biases on to_k_ip / to_v_ip, wrong shapes,
+n outside 1..128, E not a multiple of 64 (rt_gemm_bf16 needs K % 64 == 0, and 2E is the second projection's K), unknown keys.
+The image encoder this adapter is trained with (SigLIP-so400m) is not here: the 1152-wide embedding comes in through
+``ip_adapter_image_embeds=``.
 """
 from __future__ import annotations
 
@@ -41,15 +63,20 @@ _LAYOUTS = {
     "xlabs": ("ip_adapter_proj_model.proj", "ip_adapter_proj_model.norm",
               re.compile(r"^double_blocks\.(\d+)\.processor\.ip_adapter_double_stream_(k|v)_proj\.(weight|bias)$")),
 }
+_INSTANTX_MARK = "image_proj.proj.0.weight"
+_INSTANTX_BLOCK = re.compile(r"^ip_adapter\.(\d+)\.to_(k|v)_ip\.(weight|bias)$")
+GEMM_K = 64                        # rt_gemm_bf16: K % 64 == 0
 _SINGLE_BLOCK_KEYS = re.compile(r"(^|\.)single_(transformer_)?blocks\.|ip_adapter_single_stream")
 
 
 @dataclass
 class IPAdapterWeights:
-    """Parsed checkpoint: tensors as stored in the file (any float dtype), one entry per double block."""
+    """Parsed checkpoint: tensors as stored in the file (any float dtype), one entry per double block — per block, double blocks
+    first, for the "instantx" layout, whose projection has two layers (proj_w/proj_b the first, proj2_w/proj2_b the second) and
+    whose K/V linears have no bias (k_b / v_b stay empty)."""
 
-    proj_w: torch.Tensor            # [n·C, E]
-    proj_b: torch.Tensor            # [n·C]
+    proj_w: torch.Tensor            # [n·C, E]                       instantx: [2E, E]
+    proj_b: torch.Tensor            # [n·C]                          instantx: [2E]
     norm_w: torch.Tensor            # [C]
     norm_b: torch.Tensor            # [C]
     k_w: List[torch.Tensor]         # [d, C] each
@@ -57,15 +84,25 @@ class IPAdapterWeights:
     v_w: List[torch.Tensor]
     v_b: List[torch.Tensor]
     num_tokens: int
+    layout: str = "diffusers"       # "diffusers" | "xlabs" | "instantx"
+    proj2_w: Optional[torch.Tensor] = None      # instantx: [n·C, 2E]
+    proj2_b: Optional[torch.Tensor] = None
+    num_double: int = 0             # instantx: blocks [0, num_double) are double blocks
 
 
 def read_ip_adapter_file(path_or_dict, subfolder: Optional[str] = None, weight_name: Optional[str] = None) -> Dict[str, torch.Tensor]:
-    """State dict from a dict, a ``.safetensors`` file, or a directory / cached hub id (+ ``subfolder``) with ``weight_name``
-    (lora.read_lora_file's resolution; nothing is fetched)."""
+    """State dict from a dict, a ``.safetensors`` file, a ``torch.save``d ``.bin`` / ``.pt`` file (read with weights_only=True), or a
+    directory / cached hub id (+ ``subfolder``) with ``weight_name`` (lora.read_lora_file's resolution; nothing is fetched). The
+    nested upstream form {"image_proj": {...}, "ip_adapter": {...}} is flattened with those two prefixes."""
     from . import lora
 
+    def flat(sd):
+        if sd and all(isinstance(v, dict) for v in sd.values()):
+            return {f"{pre}.{k}": v for pre, inner in sd.items() for k, v in inner.items()}
+        return dict(sd)
+
     if isinstance(path_or_dict, dict):
-        return dict(path_or_dict)
+        return flat(path_or_dict)
     path = str(path_or_dict)
     if not os.path.isfile(path):
         from .modules import resolve_model_path
@@ -83,15 +120,74 @@ def read_ip_adapter_file(path_or_dict, subfolder: Optional[str] = None, weight_n
                 raise ValueError(f"{path}: pass weight_name= (no {DEFAULT_WEIGHT_NAME} and {len(files)} .safetensors files to choose from)")
         if not os.path.isfile(os.path.join(path, weight_name)):
             raise OSError(f"IP-Adapter file {os.path.join(path, weight_name)} not found")
-    return lora.read_lora_file(path, weight_name)[0]
+        path = os.path.join(path, weight_name)
+    if path.endswith((".bin", ".pt", ".pth")):
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(sd, dict):
+            raise ValueError(f"{path}: expected a state dict, got {type(sd).__name__}")
+        return flat(sd)
+    return lora.read_lora_file(path)[0]
 
 
-def parse_ip_adapter_state_dict(sd: Dict[str, torch.Tensor], num_layers: int, joint_attention_dim: int, inner_dim: int) -> IPAdapterWeights:
-    """Either key layout -> IPAdapterWeights; every refusal names the offending key."""
+def _parse_instantx(sd: Dict[str, torch.Tensor], num_layers: int, num_single_layers: int, C: int, d: int) -> IPAdapterWeights:
+    pp, npfx = "image_proj.proj", "image_proj.norm"
+    head = [f"{pp}.0.weight", f"{pp}.0.bias", f"{pp}.2.weight", f"{pp}.2.bias", f"{npfx}.weight", f"{npfx}.bias"]
+    L = num_layers + num_single_layers
+    blocks: Dict[int, Dict[str, torch.Tensor]] = {}
+    for k in sd:
+        if k in head:
+            continue
+        m = _INSTANTX_BLOCK.match(k)
+        if m is None:
+            raise ValueError(f"unrecognised IP-Adapter key: {k}")
+        if m.group(3) == "bias":
+            raise ValueError(f"the InstantX layout has no bias on to_k_ip / to_v_ip: {k}")
+        blocks.setdefault(int(m.group(1)), {})[m.group(2)] = sd[k]
+    for k in head:
+        if k not in sd:
+            raise ValueError(f"IP-Adapter state dict lacks {k}")
+    if sorted(blocks) != list(range(L)):
+        odd = next((i for i in sorted(blocks) if i >= L), None)
+        i = odd if odd is not None else next(i for i in range(L) if i not in blocks)
+        raise ValueError(f"IP-Adapter has {len(blocks)} blocks, the transformer {num_layers} double + {num_single_layers} single = {L} "
+                         f"blocks: ip_adapter.{i}.to_k_ip.weight")
+    w0, b0, w2, b2, norm_w, norm_b = (sd[k] for k in head)
+    if norm_w.dim() != 1 or norm_w.shape[0] != C or norm_b.shape != norm_w.shape:
+        raise ValueError(f"{npfx}.weight: width {tuple(norm_w.shape)} != joint_attention_dim {C}")
+    if w0.dim() != 2 or w0.shape[0] != 2 * w0.shape[1]:
+        raise ValueError(f"{pp}.0.weight: shape {tuple(w0.shape)} is not [2E, E]")
+    E = w0.shape[1]
+    if E % GEMM_K:
+        raise ValueError(f"{pp}.0.weight: image embedding width {E} is not a multiple of {GEMM_K} (rt_gemm_bf16 needs K % {GEMM_K} == 0; "
+                         f"E and 2E are the K of the two projections)")
+    if b0.shape != (2 * E,):
+        raise ValueError(f"{pp}.0.bias: shape {tuple(b0.shape)} does not match {pp}.0.weight")
+    if w2.dim() != 2 or w2.shape[1] != 2 * E or w2.shape[0] % C or not 1 <= w2.shape[0] // C <= MAX_TOKENS:
+        raise ValueError(f"{pp}.2.weight: shape {tuple(w2.shape)} is not 1..{MAX_TOKENS} tokens of width {C} from {2 * E} features")
+    if b2.shape != (w2.shape[0],):
+        raise ValueError(f"{pp}.2.bias: shape {tuple(b2.shape)} does not match {pp}.2.weight")
+    out = IPAdapterWeights(w0, b0, norm_w, norm_b, [], [], [], [], w2.shape[0] // C, "instantx", w2, b2, num_layers)
+    for i in range(L):
+        for kv, ws in (("k", out.k_w), ("v", out.v_w)):
+            w = blocks[i].get(kv)
+            if w is None:
+                raise ValueError(f"IP-Adapter state dict lacks ip_adapter.{i}.to_{kv}_ip.weight")
+            if w.shape != (d, C):
+                raise ValueError(f"ip_adapter.{i}.to_{kv}_ip.weight: shape {tuple(w.shape)} != (inner_dim {d}, joint_attention_dim {C})")
+            ws.append(w)
+    return out
+
+
+def parse_ip_adapter_state_dict(sd: Dict[str, torch.Tensor], num_layers: int, joint_attention_dim: int, inner_dim: int,
+                                num_single_layers: int = 0) -> IPAdapterWeights:
+    """Any key layout -> IPAdapterWeights; every refusal names the offending key."""
     keys = list(sd)
+    if _INSTANTX_MARK in sd:
+        return _parse_instantx(sd, num_layers, num_single_layers, joint_attention_dim, inner_dim)
     bad = [k for k in keys if _SINGLE_BLOCK_KEYS.search(k)]
     if bad:
-        raise ValueError(f"IP-Adapter keys of single blocks (the InstantX layout) are not supported: {sorted(bad)[0]}")
+        raise ValueError(f"IP-Adapter keys that name single blocks are not supported (the InstantX file numbers all its blocks "
+                         f"ip_adapter.{{j}}): {sorted(bad)[0]}")
     layout = next((name for name, (pp, _, rx) in _LAYOUTS.items() if any(k.startswith(pp + ".") or rx.match(k) for k in keys)), None)
     if layout is None:
         raise ValueError(f"no IP-Adapter keys found (expected image_proj.* / ip_adapter.* or ip_adapter_proj_model.* / double_blocks.*): "
@@ -128,7 +224,7 @@ def parse_ip_adapter_state_dict(sd: Dict[str, torch.Tensor], num_layers: int, jo
         raise ValueError(f"{pp}.bias: shape {tuple(proj_b.shape)} does not match {pp}.weight")
     if proj_w.shape[1] % 8:
         raise ValueError(f"{pp}.weight: image embedding width {proj_w.shape[1]} is not a multiple of 8")
-    out = IPAdapterWeights(proj_w, proj_b, norm_w, norm_b, [], [], [], [], proj_w.shape[0] // C)
+    out = IPAdapterWeights(proj_w, proj_b, norm_w, norm_b, [], [], [], [], proj_w.shape[0] // C, layout)
     for i in range(num_layers):
         for kv, ws, bs in (("k", out.k_w, out.k_b), ("v", out.v_w, out.v_b)):
             w, b = blocks[i].get((kv, "weight")), blocks[i].get((kv, "bias"))
@@ -145,13 +241,13 @@ def parse_ip_adapter_state_dict(sd: Dict[str, torch.Tensor], num_layers: int, jo
     return out
 
 
-def normalize_scales(scale: Union[float, Sequence[float]], num_layers: int) -> List[float]:
-    """set_ip_adapter_scale's argument -> one float per double block."""
+def normalize_scales(scale: Union[float, Sequence[float]], num_layers: int, per: str = "one per double block") -> List[float]:
+    """set_ip_adapter_scale's argument -> one float per block the adapter has a term in."""
     if isinstance(scale, (int, float)):
         return [float(scale)] * num_layers
     s = [float(x) for x in scale]
     if len(s) != num_layers:
-        raise ValueError(f"set_ip_adapter_scale: expected a float or {num_layers} floats (one per double block), got {len(s)}")
+        raise ValueError(f"set_ip_adapter_scale: expected a float or {num_layers} floats ({per}), got {len(s)}")
     return s
 
 
@@ -174,34 +270,54 @@ def normalize_embeds(embeds) -> torch.Tensor:
 
 @dataclass
 class PreparedIP:
-    """Loop-invariant K/V of one call: per double block (K_i, V_i) [B or 1, n, d] bf16 views of one GEMM output, and the scales."""
+    """Loop-invariant K/V of one call: per double block (K_i, V_i) [B or 1, n, d] bf16 views of one GEMM output, and the scales.
+    ``inside`` = the InstantX form: one entry per block (``num_double`` double blocks, then the single blocks), the term goes inside
+    the block (mmdit.run_double / run_single, ``ip_inside``)."""
 
     kv: List[Tuple[torch.Tensor, torch.Tensor]]
     scales: List[float]
     buf: torch.Tensor               # the storage the views point into
+    inside: bool = False
+    num_double: int = 0
+    tok: Optional[torch.Tensor] = None   # InstantX form: the image tokens [B or 1, n, C] K/V were made from
 
 
 class IPAdapter:
     """Adapter state of one transformer: bf16 weights on the model's device, stacked [to_k_ip_0; to_v_ip_0; to_k_ip_1; ...] so that
     the K/V of every block come from ONE GEMM per call (M = B·n rows), and the per-block scales (default 1.0)."""
 
+    _TENSORS = ("proj_w", "proj_b", "norm_scale", "norm_shift", "kv_w", "kv_b", "proj2_w", "proj2_b", "k_w", "v_w", "ones")
+
     def __init__(self, w: IPAdapterWeights, device):
         bf = lambda t: t.to(device=device, dtype=torch.bfloat16).contiguous()
+        self.layout, self.num_double = w.layout, w.num_double
         self.num_tokens, self.num_layers = w.num_tokens, len(w.k_w)
         self.C, self.d, self.E = w.norm_w.shape[0], w.k_w[0].shape[0], w.proj_w.shape[1]
         self.proj_w, self.proj_b = bf(w.proj_w), bf(w.proj_b)
+        self.scales = [1.0] * self.num_layers
+        self.version = next(_VERSIONS)
+        if w.layout == "instantx":
+            # K and V of all L2 + L1 blocks come from ONE grouped launch: [to_k_ip_0; to_k_ip_1; ...] -> fp32 (normalised, then rounded)
+            # and [to_v_ip_0; ...] -> bf16
+            self.proj2_w, self.proj2_b = bf(w.proj2_w), bf(w.proj2_b)
+            self.norm_scale = (bf(w.norm_w).to(torch.float32) - 1.0).contiguous()
+            self.norm_shift = bf(w.norm_b).to(torch.float32).contiguous()
+            self.k_w = torch.cat([bf(t) for t in w.k_w], dim=0).contiguous()          # [L·d, C]
+            self.v_w = torch.cat([bf(t) for t in w.v_w], dim=0).contiguous()
+            self.ones = torch.ones(128, device=device, dtype=torch.bfloat16)           # the weightless K norm through rt_rmsnorm_rows
+            return
         # affine LayerNorm through rt_layernorm_modulate: LN(x)·(1 + scale) + shift with scale = weight - 1 (exact in fp32), shift = bias
         self.norm_scale = (bf(w.norm_w).to(torch.float32) - 1.0).contiguous()
         self.norm_shift = bf(w.norm_b).to(torch.float32).contiguous()
         self.kv_w = torch.cat([bf(t) for pair in zip(w.k_w, w.v_w) for t in pair], dim=0).contiguous()        # [L·2d, C]
         self.kv_b = torch.cat([bf(t) for pair in zip(w.k_b, w.v_b) for t in pair], dim=0).contiguous()
-        self.scales = [1.0] * self.num_layers
-        self.version = next(_VERSIONS)
 
     def to_device(self, device) -> None:
         moved = False
-        for name in ("proj_w", "proj_b", "norm_scale", "norm_shift", "kv_w", "kv_b"):
-            old = getattr(self, name)
+        for name in self._TENSORS:
+            old = getattr(self, name, None)
+            if old is None:
+                continue
             new = old.to(device)
             moved |= new is not old
             setattr(self, name, new)
@@ -209,14 +325,19 @@ class IPAdapter:
             self.version = next(_VERSIONS)
 
     def set_scale(self, scale) -> None:
-        self.scales = normalize_scales(scale, self.num_layers)
+        if self.layout == "instantx":
+            per = f"one per block: {self.num_double} double, then {self.num_layers - self.num_double} single"
+            self.scales = normalize_scales(scale, self.num_layers, per)
+        else:
+            self.scales = normalize_scales(scale, self.num_layers)
 
     @property
     def active(self) -> bool:
         return any(s != 0.0 for s in self.scales)
 
     def prepare(self, embeds) -> PreparedIP:
-        """Steps 1-2 for one call: three launches (projection GEMM, LayerNorm, stacked K/V GEMM)."""
+        """Steps 1-2 for one call: three launches (projection GEMM, LayerNorm, stacked K/V GEMM); six for the InstantX form (two
+        projection GEMMs with the exact GELU between them, LayerNorm, the stacked K and V GEMMs as one grouped launch, the K norm)."""
         e = normalize_embeds(embeds)
         if e.shape[1] != self.E:
             raise ValueError(f"ip_adapter_image_embeds: width {e.shape[1]} != the adapter's image embedding width {self.E}")
@@ -224,6 +345,18 @@ class IPAdapter:
             raise RuntimeError("the IP-Adapter is on the CPU; move the transformer to the GPU (there is no CPU fallback)")
         e = e.to(device=self.proj_w.device, dtype=torch.bfloat16).contiguous()
         B, n, C, d, L = e.shape[0], self.num_tokens, self.C, self.d, self.num_layers
+        if self.layout == "instantx":
+            f32 = lambda *shape: torch.empty(*shape, device=e.device, dtype=torch.float32)
+            hid = ops.gelu_erf(ops.linear(e, self.proj_w, f32(B, 2 * self.E), bias=self.proj_b))
+            t32 = ops.linear(hid, self.proj2_w, f32(B, n * C), bias=self.proj2_b)
+            tok = torch.empty(B, n, C, device=e.device, dtype=torch.bfloat16)
+            ops.layernorm_modulate(t32.view(B, n, C), tok, self.norm_shift.repeat(B, 1), self.norm_scale.repeat(B, 1), eps=1e-5)
+            k32 = f32(B, n, L * d)
+            kv = torch.empty(2, B, n, L * d, device=e.device, dtype=torch.bfloat16)
+            ops.linear_grouped([ops.LinearProblem(tok, self.k_w, k32), ops.LinearProblem(tok, self.v_w, kv[1])])
+            ops.rmsnorm_heads_(k32, kv[0], self.ones, eps=1e-5)
+            views = [(kv[0][..., j * d : (j + 1) * d], kv[1][..., j * d : (j + 1) * d]) for j in range(L)]
+            return PreparedIP(views, list(self.scales), kv, True, self.num_double, tok)
         t32 = torch.empty(B, n * C, device=e.device, dtype=torch.float32)
         ops.linear(e, self.proj_w, t32, bias=self.proj_b)
         tok = torch.empty(B, n, C, device=e.device, dtype=torch.bfloat16)

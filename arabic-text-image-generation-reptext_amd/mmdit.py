@@ -209,6 +209,12 @@ class Workspace:
             self._ip = torch.empty(self.B, self.N, self.d, device=self._device, dtype=BF16)
         return self._ip
 
+    def ip_buffer_joint(self) -> torch.Tensor:
+        """[B,S,d] bf16: the IP-Adapter term of the running single block, all S rows (the InstantX form; allocated on first use)."""
+        if getattr(self, "_ip_s", None) is None:
+            self._ip_s = torch.empty(self.B, self.S, self.d, device=self._device, dtype=BF16)
+        return self._ip_s
+
     def fp8_buffers(self):
         if self.xn8 is None:
             B, T, N, S, d = self.B, self.T, self.N, self.S, self.d
@@ -359,12 +365,15 @@ class ModulationTable:
 
 
 def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: int, inject: Optional[torch.Tensor] = None,
-               mods: Optional[tuple] = None, ip: Optional[tuple] = None) -> None:
+               mods: Optional[tuple] = None, ip: Optional[tuple] = None, ip_inside: bool = False) -> None:
     """One FluxTransformerBlock on ws.x in place (A.1). ``inject`` [B,N,d] bf16 is added to the image rows after the
     block (A.3 ControlNet residual), fused into the last GEMM's epilogue. ``mods`` = precomputed (image, text) adaLN
     vectors for this step (ModulationTable); computed here from ``temb`` when absent. ``ip`` = (K, V, scale) of an IP-Adapter
     (ip_adapter.py): scale · softmax(q Kᵀ/√128) V from the image query after norm_q and before RoPE, added to the image rows after the
-    feed-forward residual. With ``ip=None`` the launch sequence is unchanged."""
+    feed-forward residual. ``ip_inside`` = the InstantX form of the same tuple: gate_msa · scale · softmax(q Kᵀ/√128) V, K used as given,
+    accumulated straight onto the residual image rows by ONE launch placed where the raw query exists (before attention); the later
+    x += gate_msa · to_out(attn) epilogue adds onto it, so h <- h + gate_msa · (to_out(attn) + scale · ip) up to the order of two
+    fp32 additions. With ``ip=None`` the launch sequence is unchanged."""
     T, d = ws.T, ws.d
     x_t, x_i = ws.x[:, :T], ws.x[:, T:]
     xn_t, xn_i = ws.xn[:, :T], ws.xn[:, T:]
@@ -394,6 +403,9 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         rt = ops.QKRope(0, d, d, pl.nq_txt, pl.nk_txt, cos, sin, pos0=0) if fused_rope else None
         ops.linear_grouped([P(xn_i, pl.qkv_img_w, ws.qkv[:, T:], bias=pl.qkv_img_b, rope=ri), P(xn_t, pl.qkv_txt_w, ws.qkv[:, :T], bias=pl.qkv_txt_b, rope=rt)])
     q, k, v = ws.qkv[..., :d], ws.qkv[..., d : 2 * d], ws.qkv[..., 2 * d :]
+    if ip is not None and ip_inside:
+        ops.ip_attention_gated(q[:, T:], pl.nq_img, ip[0], ip[1], x_i, H, ip_scale=ip[2], gate=ch(mi, 2), accumulate=True)
+        ip = None
     if ip is not None:
         # the raw image query is only here: qk_rmsnorm_rope works in place and the attention output overwrites q
         ip_out = ws.ip_buffer()
@@ -460,8 +472,13 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
 
 
 def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: int, inject: Optional[torch.Tensor] = None,
-               mods: Optional[torch.Tensor] = None) -> None:
-    """One FluxSingleTransformerBlock on ws.x in place (A.2)."""
+               mods: Optional[torch.Tensor] = None, ip: Optional[tuple] = None) -> None:
+    """One FluxSingleTransformerBlock on ws.x in place (A.2). ``ip`` = (K, V, scale) of an InstantX IP-Adapter (ip_adapter.py):
+    scale · softmax(q Kᵀ/√128) V from the query of ALL S rows after norm_q and before RoPE, added to the attention output before
+    proj_out. The raw q only exists between the fused GEMM and norm + RoPE and attention overwrites it, so the term waits in a bf16
+    [B,S,d] buffer and one strided add puts it over q's columns after attention. Wherever the attention output would skip bf16 (the
+    "mx" level with e4m3 attention) such a block takes the bf16-output attention call and the quantise pass instead. With ``ip=None``
+    the launch sequence is unchanged."""
     T, d = ws.T, ws.d
     if mods is not None:
         m = mods
@@ -478,14 +495,17 @@ def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         ops.linear(xn8, pl.fused_w8, big, bias=pl.fused_b, gelu_from=3 * d, a_scale=ws.xs_all, w_scale=pl.fused_ws, **o8)
     else:
         ops.layernorm_modulate(ws.x, ws.xn, m[:, :d], m[:, d : 2 * d])
-        fused_rope = FUSED_QK_ROPE and not pl.fp8_attention and ops.QKRope.covers(d)
+        fused_rope = FUSED_QK_ROPE and ip is None and not pl.fp8_attention and ops.QKRope.covers(d)
         ops.linear(ws.xn, pl.fused_w, big, bias=pl.fused_b, gelu_from=3 * d,    # [k|v|q|gelu(mlp)]
                    rope=ops.QKRope(2 * d, 0, d, pl.nq, pl.nk, cos, sin) if fused_rope else None)
     q = big[..., 2 * d : 3 * d]
+    if ip is not None:
+        ip_out = ws.ip_buffer_joint()
+        ops.ip_attention_gated(q, pl.nq, ip[0], ip[1], ip_out, H, ip_scale=ip[2])
     if pl.fp8_attention:
         qk8, vt8 = ws.fp8_attn_buffers(H)
         ops.attention_fp8_prep(big, 2 * d, 0, d, H, 0, None, None, pl.nq, pl.nk, cos, sin, qk8, vt8)
-        if pl.mx:
+        if pl.mx and ip is None:
             ops.attention_fp8_mx(qk8, vt8, ws.fp8_wide(5 * d)[..., :d], ws.mx_scales(), H)
         else:
             ops.attention_fp8(qk8, vt8, q, H)
@@ -493,9 +513,11 @@ def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         if not fused_rope:
             ops.qk_rmsnorm_rope(big, 2 * d, 0, H, 0, None, None, pl.nq, pl.nk, cos, sin)
         ops.attention(q, big[..., :d], big[..., d : 2 * d], q, H)
+    if ip is not None:
+        ops.add_bf16_(q, ip_out)
     if pl.mx:
         a8, sc = ws.fp8_wide(5 * d), ws.mx_scales()
-        if not pl.fp8_attention:
+        if not pl.fp8_attention or ip is not None:
             ops.quantize_mx_fp8_into(q, a8[..., :d], sc)
         ops.linear(a8, pl.out_w8, ws.x, bias=pl.out_b, gate=m[:, 2 * d : 3 * d], res=ws.x, a_bscale=sc, w_scale=pl.out_ws)
     elif pl.out_w8 is not None:

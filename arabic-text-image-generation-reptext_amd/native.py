@@ -15,7 +15,7 @@ LIB_NAME = "librt_reptext_hip.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 RT_GEMM_MAX_GROUPS = 4
-ABI_VERSION = 13
+ABI_VERSION = 14
 RT_LORA_MAX_TERMS = 8
 
 
@@ -141,6 +141,13 @@ SIGNATURES["rt_lora_merge_bf16"] = [C.POINTER(LoraTerm), _i32, _vp, _i64, _vp, _
 
 # IP-Adapter cross-attention (csrc/ip_attention.hip)
 SIGNATURES["rt_ip_attention"] = [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _f32, _f32, _vp]
+
+# the InstantX IP-Adapter form (ABI 14): the gated entry of the same kernel, the exact GELU of its image projection, and the strided
+# add that puts a single block's term onto the attention output (csrc/ip_attention.hip, csrc/norm_elem.hip)
+SIGNATURES["rt_ip_attention_gated"] = [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32,
+                                       _f32, _f32, _f32, _vp]
+SIGNATURES["rt_gelu_erf_bf16"] = [_vp, _vp, _i64, _vp]
+SIGNATURES["rt_add_bf16_2d"] = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp]
 
 # CLIP vision encoder (csrc/attention_hd64.hip, csrc/image_encoder.hip)
 RT_ATTENTION_HD64_MAX_S = 4096

@@ -575,6 +575,64 @@ def ip_attention(q: torch.Tensor, wq: torch.Tensor, k: torch.Tensor, v: torch.Te
     return out
 
 
+def ip_attention_gated(q: torch.Tensor, wq: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, ip_scale: float = 1.0,
+                       gate: Optional[torch.Tensor] = None, accumulate: bool = False, scale: Optional[float] = None, eps: float = 1e-6) -> torch.Tensor:
+    """out (+)= gate[b] · ip_scale · softmax(bf16(rmsnorm(q)·wq) Kᵀ · scale) V (rt_ip_attention_gated): ip_attention with an optional
+    fp32 column gate [B, H·128] (a view with unit inner stride and any batch stride, e.g. the gate_msa chunk of the modulation table).
+    q may be any [B,rows,H·128] view (a single block: columns 2d:3d of the fused [k|v|q|mlp] buffer, all S rows); k as given."""
+    d = H * 128
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] != d:
+            raise ValueError(f"{name}: need [B,rows,{d}] with unit inner stride, got {tuple(t.shape)} / {t.stride()}")
+    B, N, _ = q.shape
+    if out.shape != q.shape or out.dtype not in (BF16, F32):
+        raise ValueError("out must match q in shape and be bf16 or f32")
+    if k.shape != v.shape or k.stride() != v.stride() or k.shape[0] not in (1, B):
+        raise ValueError("k and v must share shape and strides, with batch 1 or B")
+    n = k.shape[1]
+    if not 1 <= n <= 128:
+        raise ValueError(f"ip_attention_gated: 1..128 image-prompt tokens, got {n}")
+    if wq.numel() != 128 or not wq.is_contiguous():
+        raise ValueError("wq must be contiguous with 128 elements")
+    if gate is not None and (gate.dim() != 2 or gate.shape != (B, d) or gate.stride(1) != 1):
+        raise ValueError(f"gate must be a [B,{d}] view with unit inner stride")
+    sc = (128 ** -0.5) if scale is None else float(scale)
+    native.check("rt_ip_attention_gated", native.load().rt_ip_attention_gated(
+        _dev(q, "q", BF16), q.stride(1), q.stride(0), _dev(wq, "wq", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), k.stride(1),
+        k.stride(0) if k.shape[0] == B and B > 1 else 0, _opt(gate, "gate", F32), 0 if gate is None else gate.stride(0),
+        _dev(out, "out"), out.stride(1), out.stride(0), int(out.dtype == F32), int(accumulate), B, N, H, n, sc, float(ip_scale), float(eps), _stream()))
+    return out
+
+
+def gelu_erf(x: torch.Tensor) -> torch.Tensor:
+    """bf16(exact GELU(x)) of a contiguous f32 tensor (rt_gelu_erf_bf16)."""
+    if not x.is_contiguous():
+        raise ValueError("gelu_erf: contiguous input")
+    out = torch.empty(x.shape, device=x.device, dtype=BF16)
+    native.check("rt_gelu_erf_bf16", native.load().rt_gelu_erf_bf16(_dev(x, "x", F32), out.data_ptr(), x.numel(), _stream()))
+    return out
+
+
+def add_bf16_(y: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
+    """y = bf16(y + x) in place on [B,R,D] bf16 views with unit inner stride and any row / batch strides (rt_add_bf16_2d)."""
+    if x.shape != y.shape or x.dim() != 3 or x.stride(2) != 1 or y.stride(2) != 1:
+        raise ValueError("add_bf16_: [B,R,D] views of equal shape with unit inner stride")
+    B, R, D = x.shape
+    native.check("rt_add_bf16_2d", native.load().rt_add_bf16_2d(_dev(x, "x", BF16), x.stride(1), x.stride(0), _dev(y, "y", BF16), y.stride(1),
+                                                                y.stride(0), B, R, D, _stream()))
+    return y
+
+
+def rmsnorm_heads_(x: torch.Tensor, out: torch.Tensor, ones: torch.Tensor, eps: float) -> torch.Tensor:
+    """out = bf16(x · rsqrt(mean_128(x²) + eps)) per group of 128 consecutive elements (rt_rmsnorm_rows with a weight of ones, which
+    multiplies exactly): x contiguous f32, out contiguous bf16 of the same shape, numel % 128 == 0."""
+    if x.shape != out.shape or not x.is_contiguous() or not out.is_contiguous() or x.numel() % 128 or ones.numel() != 128:
+        raise ValueError("rmsnorm_heads_: contiguous tensors of equal shape, a multiple of 128 elements")
+    native.check("rt_rmsnorm_rows", native.load().rt_rmsnorm_rows(_dev(x, "x", F32), 128, 1, _dev(ones, "ones", BF16), _dev(out, "out", BF16), 128,
+                                                                  x.numel() // 128, 128, float(eps), _stream()))
+    return out
+
+
 def attention_hd64(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, scale: Optional[float] = None) -> torch.Tensor:
     """out[b, s, h·64:(h+1)·64] = softmax(scale · q_h k_hᵀ) v_h (rt_attention_hd64): non-causal self-attention with heads of 64, one
     launch. q, k, v [B,S,H·64] bf16 views of one buffer sharing strides (the fused q|k|v projection); out [B,S,H·64] bf16 view with its

@@ -334,15 +334,18 @@ class FluxTransformer2DModel(_MMDiTBase):
 
     # ---- IP-Adapter (image prompt): the FluxIPAdapterMixin subset; state in ip_adapter.py, not in the parameters
     def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder: Optional[str] = None, weight_name: Optional[str] = None):
-        """Read an IP-Adapter (dict, .safetensors file, directory + weight_name, or cached hub id; diffusers or XLabs key layout) and
-        make it this model's adapter at scale 1.0 in every double block. Replaces a loaded one."""
+        """Read an IP-Adapter (dict, .safetensors file, directory + weight_name, or cached hub id; diffusers, XLabs or InstantX key
+        layout, the last also as its upstream ``ip-adapter.bin``) and make it this model's adapter at scale 1.0 in every block it has
+        a term in: the double blocks, for the InstantX layout the single blocks too. Replaces a loaded one."""
         sd = ip_adapter.read_ip_adapter_file(pretrained_model_name_or_path_or_dict, subfolder, weight_name)
-        w = ip_adapter.parse_ip_adapter_state_dict(sd, self.config.num_layers, self.config.joint_attention_dim, self.inner_dim)
+        w = ip_adapter.parse_ip_adapter_state_dict(sd, self.config.num_layers, self.config.joint_attention_dim, self.inner_dim,
+                                                   self.config.num_single_layers)
         self._ip_adapter = ip_adapter.IPAdapter(w, self.device)
         return self
 
     def set_ip_adapter_scale(self, scale):
-        """One float for every double block, or a list of num_layers floats. A block at 0.0 launches nothing for the adapter."""
+        """One float for every block of the adapter, or a list: num_layers floats (diffusers / XLabs layouts), num_layers +
+        num_single_layers floats, double blocks first (InstantX layout). A block at 0.0 launches nothing for the adapter."""
         if self._ip_adapter is None:
             raise ValueError(f"{type(self).__name__}: no IP-Adapter is loaded")
         self._ip_adapter.set_scale(scale)
@@ -359,7 +362,7 @@ class FluxTransformer2DModel(_MMDiTBase):
                 _mods: Optional["mmdit.StepMods"] = None, _sample_events: Optional[Sequence["torch.cuda.Event"]] = None,
                 _static: Optional[StaticEmbeds] = None, _ip: Optional["ip_adapter.PreparedIP"] = None):
         """``joint_attention_kwargs["ip_adapter_image_embeds"]`` (as in diffusers): the image prompt of a loaded IP-Adapter, projected
-        and applied in every double block (ip_adapter.py); ``_ip`` (optional) = the same already prepared (``_ip_adapter.prepare``), so
+        and applied in every double block — in every block, single ones included, for an InstantX adapter (ip_adapter.py); ``_ip`` (optional) = the same already prepared (``_ip_adapter.prepare``), so
         that a loop does not redo the projection per step.
         ``_sample_events[k]`` (optional): event another stream records when controlnet_block_samples[k] is complete; the
         current stream waits for it right before the first block that consumes that sample. ``_static`` (optional): this
@@ -404,12 +407,16 @@ class FluxTransformer2DModel(_MMDiTBase):
                     torch.cuda.current_stream().wait_event(_sample_events[k])
                     waited.add(k)
             ip = None if _ip is None or _ip.scales[i] == 0.0 else (*_ip.kv[i], _ip.scales[i])
-            mmdit.run_double(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.double[i], ip=ip)
+            mmdit.run_double(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.double[i], ip=ip,
+                             ip_inside=_ip is not None and _ip.inside)
         for i, pl in enumerate(singles):
             inj = None
             if controlnet_single_block_samples is not None:
                 inj = controlnet_single_block_samples[i // int(math.ceil(ns / len(controlnet_single_block_samples)))]
-            mmdit.run_single(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.single[i])
+            ip = None
+            if _ip is not None and _ip.inside and _ip.scales[nl + i] != 0.0:
+                ip = (*_ip.kv[nl + i], _ip.scales[nl + i])
+            mmdit.run_single(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.single[i], ip=ip)
         # AdaLayerNormContinuous: chunk order (scale, shift)  — A.3
         if _mods is not None:
             m = _mods.out

@@ -310,6 +310,28 @@ int rt_ip_attention(const void* q, int64_t ldq, int64_t stride_qb, const void* w
                     const void* k, const void* v, int64_t ldkv, int64_t stride_kvb,
                     void* o, int64_t ldo, int64_t stride_ob, int32_t o_f32, int32_t accumulate,
                     int32_t B, int32_t N, int32_t H, int32_t n_ip, float sm_scale, float ip_scale, float eps, void* stream);
+/* ABI 14. The same kernel body with an optional fp32 column gate (the InstantX adapter form, ip_adapter.py):
+ *   o (+)= gate[b][h*128 + c] * ( ip_scale * softmax( bf16(rmsnorm(q) * wq) * K^T * sm_scale ) * V )
+ * gate: fp32 [B][>= H*128] with batch stride stride_gb (elements), e.g. the gate_msa chunk of a row of the adaLN modulation table, so
+ * that a double block accumulates its gated term straight onto the fp32 (or bf16) residual rows in one launch; NULL = no gate, which
+ * is rt_ip_attention bit for bit. The product with the gate is formed in fp32 before the write or accumulate. q may be any strided
+ * view: a single block passes column 2*H*128 of its fused [k|v|q|mlp] buffer with ldq = 7*H*128 and N = all S rows. K is used as
+ * given (this adapter form stores it already RMS-normalised); there is no K norm in the kernel.
+ * Rejected on the host as rt_ip_attention, and: a negative stride_gb (RT_E_BADARG); gate not 16-byte aligned or stride_gb % 4 (RT_E_ALIGN). */
+int rt_ip_attention_gated(const void* q, int64_t ldq, int64_t stride_qb, const void* wq,
+                          const void* k, const void* v, int64_t ldkv, int64_t stride_kvb,
+                          const float* gate, int64_t stride_gb,
+                          void* o, int64_t ldo, int64_t stride_ob, int32_t o_f32, int32_t accumulate,
+                          int32_t B, int32_t N, int32_t H, int32_t n_ip, float sm_scale, float ip_scale, float eps, void* stream);
+/* y[i] = bf16( 0.5 x[i] (1 + erf(x[i] / sqrt 2)) ): the exact GELU of the InstantX image projection (rt_gemm_group's epilogue has the
+ * tanh form only). x fp32, y bf16, n elements; once per call, outside the loop. Null pointers or n < 1: RT_E_BADARG. */
+int rt_gelu_erf_bf16(const float* x, void* y, int64_t n, void* stream);
+/* y[b][r][0..D) = bf16( y[b][r][:] + x[b][r][:] ) on bf16 views with their own leading dimensions and batch strides (elements): adds a
+ * single block's IP-Adapter term onto the attention output inside the fused [k|v|q|mlp] buffer (ldy = 7*H*128) before proj_out.
+ * Rejected on the host: null pointers, batch / rows < 1, D < 8, ld < D, a negative batch stride (RT_E_BADARG); D % 8 (RT_E_SHAPE);
+ * pointers not 16-byte aligned, a leading dimension or batch stride not a multiple of 8 (RT_E_ALIGN). */
+int rt_add_bf16_2d(const void* x, int64_t ldx, int64_t stride_xb, void* y, int64_t ldy, int64_t stride_yb,
+                   int32_t batch, int32_t rows, int32_t D, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Prompt encoders (PIPE:232-347: T5-XXL encoder -> prompt_embeds [B,512,4096], CLIP-L text model ->
