@@ -1,3 +1,3 @@
 #include "rt_common.h"
-extern "C" const char* rt_version(void) { return "reptext_hip abi14 gfx950"; }
-extern "C" int rt_abi_version(void) { return 14; }
+extern "C" const char* rt_version(void) { return "reptext_hip abi15 gfx950"; }
+extern "C" int rt_abi_version(void) { return 15; }

@@ -1,4 +1,6 @@
-"""CLIP vision encoder on the HIP kernels: the image encoder behind ``pipe(..., ip_adapter_image=img)``.
+"""The vision encoders on the HIP kernels: the image encoders behind ``pipe(..., ip_adapter_image=img)`` — CLIP ViT-L/14 for the
+XLabs / diffusers IP-Adapter, SigLIP-so400m for the InstantX one (``SiglipVisionModel``, second half of this file;
+``image_encoder_class`` picks between them from a directory's ``config.json``).
 
 ``CLIPVisionModelWithProjection`` has the class name, constructor config keys, module names and state-dict keys of `transformers`'
 class (``vision_model.pre_layrnorm`` in transformers' spelling, ``vision_model.post_layernorm``, a top-level
@@ -249,5 +251,274 @@ class CLIPVisionModelWithProjection(nn.Module, WeightsIO):
         embeds = torch.empty(B, c.projection_dim, device=dev, dtype=BF16)
         ops.linear(pooled.view(B, d), self.visual_projection.weight.data, embeds)
         return CLIPVisionModelOutput(embeds, last) if return_dict else (embeds, last)
+
+    __call__ = forward
+
+
+# ======================================================================================================================= SigLIP
+def siglip_preprocess(image, size: int = 384) -> torch.Tensor:
+    """SiglipImageProcessor's defaults on the host: RGB, resized straight to size x size (bicubic; no aspect keeping, no crop),
+    ·1/255, (x − 0.5)/0.5. ``image``: a PIL image, a uint8 HWC (or HW) numpy array, or a list of them -> f32 [B,3,size,size]."""
+    from PIL import Image
+
+    images = list(image) if isinstance(image, (list, tuple)) else [image]
+    if not images:
+        raise ValueError("siglip_preprocess: no image")
+    out = []
+    for im in images:
+        if isinstance(im, np.ndarray):
+            if im.dtype != np.uint8 or im.ndim not in (2, 3):
+                raise TypeError("siglip_preprocess: numpy images must be uint8 [H,W,C] (or [H,W])")
+            im = Image.fromarray(im)
+        if not isinstance(im, Image.Image):
+            raise TypeError(f"siglip_preprocess: expected a PIL image or a uint8 numpy array, got {type(im)}")
+        im = im.convert("RGB").resize((size, size), resample=Image.BICUBIC)
+        x = np.asarray(im, dtype=np.uint8).astype(np.float32) * np.float32(1.0 / 255.0)
+        out.append(((x - np.float32(0.5)) / np.float32(0.5)).transpose(2, 0, 1))
+    return torch.from_numpy(np.ascontiguousarray(np.stack(out), dtype=np.float32))
+
+
+def image_encoder_class(directory: str):
+    """The encoder class for a model directory, from its ``config.json``: ``model_type`` ``siglip_vision_model``, or ``siglip`` with
+    a ``vision_config``, -> SiglipVisionModel; anything else -> CLIPVisionModelWithProjection."""
+    with open(os.path.join(directory, "config.json")) as f:
+        cfg = json.load(f)
+    mt = cfg.get("model_type")
+    if mt == "siglip_vision_model" or (mt == "siglip" and isinstance(cfg.get("vision_config"), dict)):
+        return SiglipVisionModel
+    return CLIPVisionModelWithProjection
+
+
+def pad_mlp_to_64(w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor):
+    """(fc1.weight [F,d], fc1.bias [F], fc2.weight [d,F]) with F padded by zeros to the next multiple of 64 (the GEMM's K % 64 rule
+    for fc2: 4304 -> 4352). Exact: a padded hidden unit is gelu_tanh(0·x + 0) = 0 and meets a zero column of fc2."""
+    F_ = w1.shape[0]
+    Fp = (F_ + 63) // 64 * 64
+    if Fp == F_:
+        return w1.contiguous(), b1.contiguous(), w2.contiguous()
+    w1p = torch.zeros(Fp, w1.shape[1], device=w1.device, dtype=w1.dtype)
+    w1p[:F_] = w1
+    b1p = torch.zeros(Fp, device=b1.device, dtype=b1.dtype)
+    b1p[:F_] = b1
+    w2p = torch.zeros(w2.shape[0], Fp, device=w2.device, dtype=w2.dtype)
+    w2p[:, :F_] = w2
+    return w1p, b1p, w2p
+
+
+class SiglipVisionModelOutput(tuple):
+    """(last_hidden_state, pooler_output) with attribute access, transformers' field order."""
+
+    def __new__(cls, last_hidden_state, pooler_output):
+        obj = super().__new__(cls, (last_hidden_state, pooler_output))
+        obj.last_hidden_state, obj.pooler_output = last_hidden_state, pooler_output
+        return obj
+
+
+class _MHA(nn.Module):
+    """torch.nn.MultiheadAttention's parameters (in_proj_weight / in_proj_bias as q|k|v, out_proj)."""
+
+    def __init__(self, d, device=None, dtype=None):
+        super().__init__()
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * d, d, device=device, dtype=dtype), requires_grad=False)
+        self.in_proj_bias = nn.Parameter(torch.empty(3 * d, device=device, dtype=dtype), requires_grad=False)
+        self.out_proj = _WB(d, d, device=device, dtype=dtype)
+
+
+class SiglipVisionModel(nn.Module, WeightsIO):
+    """google/siglip-so400m-patch14-384's vision tower with its attention-pooling head: the class name, constructor config keys,
+    module names and state-dict keys of `transformers`' class (5.x layout: ``embeddings.*``, ``encoder.layers.*``,
+    ``post_layernorm.*``, ``head.*``; a ``vision_model.`` prefix, as in the published checkpoint, is accepted). Arithmetic: patch
+    convolution WITH bias + learned positions (no class token, no pre-norm; the convolution keeps image_size // patch_size patches per
+    side and drops the rest of the image), pre-LN blocks with gelu_pytorch_tanh, ``post_layernorm`` on all tokens, then the head:
+    MHA(probe, h, h), x + mlp(layernorm(x)), row 0. Heads of 72: one rt_attention_hd72 launch per layer on the fused q|k|v buffer
+    and one more for the head, whose query probe·Wqᵀ + bq is a constant of the weights (computed once with the plans)."""
+
+    config_name = "config.json"
+    weights_name = "model.safetensors"
+
+    def __init__(self, hidden_size: int = 1152, intermediate_size: int = 4304, num_hidden_layers: int = 27, num_attention_heads: int = 16,
+                 num_channels: int = 3, image_size: int = 384, patch_size: int = 14, hidden_act: str = "gelu_pytorch_tanh",
+                 layer_norm_eps: float = 1e-6, vision_use_head: bool = True, device=None, dtype=None, **unused):
+        super().__init__()
+        if hidden_size % num_attention_heads or hidden_size // num_attention_heads != 72:
+            raise ValueError(f"SiglipVisionModel (HIP): head dim must be 72 (so400m: 1152 / 16), got hidden_size {hidden_size} / "
+                             f"num_attention_heads {num_attention_heads}")
+        if hidden_size % 64:
+            raise ValueError(f"SiglipVisionModel (HIP): hidden_size {hidden_size} is not a multiple of 64")
+        if hidden_act != "gelu_pytorch_tanh":
+            raise ValueError(f"SiglipVisionModel (HIP): only gelu_pytorch_tanh is implemented, got hidden_act '{hidden_act}'")
+        if not vision_use_head:
+            raise ValueError("SiglipVisionModel (HIP): vision_use_head=False is not supported: pooler_output is what the encoder is for")
+        if num_channels != 3 or intermediate_size % 4 or image_size < patch_size:
+            raise ValueError("SiglipVisionModel (HIP): 3 channels, intermediate_size % 4 == 0 and image_size >= patch_size")
+        self.config = Config(model_type="siglip_vision_model", hidden_size=hidden_size, intermediate_size=intermediate_size,
+                             num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads, num_channels=num_channels,
+                             image_size=image_size, patch_size=patch_size, hidden_act=hidden_act, layer_norm_eps=layer_norm_eps)
+        kw = dict(device=device, dtype=dtype)
+
+        def mlp():
+            m = _H()
+            m.fc1, m.fc2 = _WB(intermediate_size, hidden_size, **kw), _WB(hidden_size, intermediate_size, **kw)
+            return m
+
+        emb = _H()
+        emb.patch_embedding = _H()                                               # Conv2d(3, d, kernel p, stride p) WITH bias
+        emb.patch_embedding.weight = nn.Parameter(torch.empty(hidden_size, num_channels, patch_size, patch_size, **kw), requires_grad=False)
+        emb.patch_embedding.bias = nn.Parameter(torch.empty(hidden_size, **kw), requires_grad=False)
+        emb.position_embedding = _W((image_size // patch_size) ** 2, hidden_size, **kw)
+        self.embeddings = emb
+        enc = _H()
+        enc.layers = nn.ModuleList()
+        for _ in range(num_hidden_layers):
+            l = _H()
+            sa = _H()
+            sa.q_proj, sa.k_proj, sa.v_proj, sa.out_proj = (_WB(hidden_size, hidden_size, **kw) for _ in range(4))
+            l.self_attn = sa
+            l.layer_norm1, l.layer_norm2 = _WB(hidden_size, **kw), _WB(hidden_size, **kw)
+            l.mlp = mlp()
+            enc.layers.append(l)
+        self.encoder = enc
+        self.post_layernorm = _WB(hidden_size, **kw)
+        head = _H()
+        head.probe = nn.Parameter(torch.empty(1, 1, hidden_size, **kw), requires_grad=False)
+        head.attention = _MHA(hidden_size, **kw)
+        head.layernorm = _WB(hidden_size, **kw)
+        head.mlp = mlp()
+        self.head = head
+        self._plans = None
+
+    @property
+    def dtype(self):
+        return self.head.probe.dtype
+
+    @property
+    def device(self):
+        return self.head.probe.device
+
+    def _apply(self, fn, *a, **k):
+        self._plans = None
+        return super()._apply(fn, *a, **k)
+
+    def load_state_dict(self, sd, strict: bool = True, **kw):
+        # a full SiglipModel checkpoint: the text tower and the two logit scalars are not ours; then the published prefix
+        sd = {k: v for k, v in sd.items() if not (k.startswith("text_model.") or k in ("logit_scale", "logit_bias"))}
+        sd = {(k[len("vision_model."):] if k.startswith("vision_model.") else k): v for k, v in sd.items()}
+        sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
+        self._plans = None
+        return super().load_state_dict(sd, strict=strict, **kw)
+
+    @classmethod
+    def from_pretrained(cls, path: str, torch_dtype=None, subfolder: Optional[str] = None, device=None, **unused):
+        d = cls._resolve_dir(path, subfolder)
+        with open(os.path.join(d, cls.config_name)) as f:
+            cfg = json.load(f)
+        cfg = {k: v for k, v in cfg.get("vision_config", cfg).items() if k not in ("dtype", "device")}    # transformers 5.x records a dtype
+        m = cls(**cfg, device=device or "cpu", dtype=torch_dtype or BF16)
+        m.load_state_dict({k: v.to(torch_dtype or BF16) for k, v in cls._load_safetensors_dir(d).items()}, strict=True)
+        return m
+
+    def random_init_(self, seed: int = 0):
+        """Random weights at an exercised scale, for tools and tests that run without a checkpoint: matrices at 1/sqrt(fan-in),
+        the probe and the positions at unit scale, LayerNorms at identity, biases zero."""
+        g = torch.Generator().manual_seed(seed)
+        for n, p in self.named_parameters():
+            if "norm" in n and n.endswith("weight"):
+                p.data.fill_(1.0)
+            elif n.endswith("bias"):
+                p.data.zero_()
+            else:
+                std = 1.0 if "probe" in n or "position_embedding" in n else p[0].numel() ** -0.5
+                p.data.copy_(torch.randn(p.shape, generator=g) * std)
+        self._plans = None
+        return self
+
+    def _ensure_plans(self):
+        if self._plans is not None:
+            return self._plans
+        if self.dtype != BF16 or not self.head.probe.is_cuda:
+            raise RuntimeError("SiglipVisionModel (HIP): bf16 on the GPU only; there is no CPU fallback")
+
+        def affine(ln):           # LayerNorm(x)·w + b == LN(x)·(1 + (w - 1)) + b: the adaLN kernel with constant vectors
+            return (ln.weight.data.to(F32) - 1.0).reshape(1, -1).contiguous(), ln.bias.data.to(F32).reshape(1, -1).contiguous()
+
+        c, emb, head = self.config, self.embeddings, self.head
+        d, k = c.hidden_size, 3 * c.patch_size ** 2
+        Kp = (k + 63) // 64 * 64                                                  # the GEMM's K % 64 rule: 588 -> 640 for p = 14
+        w_patch = torch.zeros(d, Kp, device=self.device, dtype=BF16)
+        w_patch[:, :k] = emb.patch_embedding.weight.data.reshape(d, k)
+        layers = []
+        for l in self.encoder.layers:
+            sa = l.self_attn
+            wqkv = torch.cat([sa.q_proj.weight.data, sa.k_proj.weight.data, sa.v_proj.weight.data], dim=0).contiguous()
+            bqkv = torch.cat([sa.q_proj.bias.data, sa.k_proj.bias.data, sa.v_proj.bias.data], dim=0).contiguous()
+            w1, b1, w2 = pad_mlp_to_64(l.mlp.fc1.weight.data, l.mlp.fc1.bias.data, l.mlp.fc2.weight.data)
+            layers.append((wqkv, bqkv, sa.out_proj.weight.data, sa.out_proj.bias.data, w1, b1, w2, l.mlp.fc2.bias.data,
+                           affine(l.layer_norm1), affine(l.layer_norm2)))
+        att = head.attention
+        wq, bq = att.in_proj_weight.data[:d].to(F32), att.in_proj_bias.data[:d].to(F32)
+        q_probe = (head.probe.data.to(F32).reshape(1, d) @ wq.t() + bq).to(BF16).reshape(1, 1, d).contiguous()   # a constant of the weights
+        hw1, hb1, hw2 = pad_mlp_to_64(head.mlp.fc1.weight.data, head.mlp.fc1.bias.data, head.mlp.fc2.weight.data)
+        self._plans = dict(w_patch=w_patch, b_patch=emb.patch_embedding.bias.data.contiguous(), Kp=Kp, Fp=hw1.shape[0],
+                           pos=emb.position_embedding.weight.data.to(F32).contiguous(), post=affine(self.post_layernorm), layers=layers,
+                           q_probe=q_probe, wkv=att.in_proj_weight.data[d:].contiguous(), bkv=att.in_proj_bias.data[d:].contiguous(),
+                           wo=att.out_proj.weight.data, bo=att.out_proj.bias.data, head_ln=affine(head.layernorm),
+                           head_mlp=(hw1, hb1, hw2, head.mlp.fc2.bias.data))
+        return self._plans
+
+    @torch.no_grad()
+    def forward(self, pixel_values: torch.Tensor, output_attentions=None, output_hidden_states=None, interpolate_pos_encoding: bool = False,
+                return_dict: bool = True, **unused):
+        if output_attentions or output_hidden_states or interpolate_pos_encoding:
+            raise NotImplementedError("SiglipVisionModel (HIP): only last_hidden_state and pooler_output are produced, at the configured "
+                                      "image size")
+        plans = self._ensure_plans()
+        c, dev = self.config, self.device
+        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, c.image_size, c.image_size):
+            raise ValueError(f"pixel_values must be [B,3,{c.image_size},{c.image_size}], got {tuple(pixel_values.shape)}")
+        if pixel_values.dtype not in (BF16, F32):
+            pixel_values = pixel_values.to(F32)
+        pixel_values = pixel_values.to(dev)
+        B, d, H, p = pixel_values.shape[0], c.hidden_size, c.num_attention_heads, c.patch_size
+        G = c.image_size // p
+        S, Fp = G * G, plans["Fp"]
+        eps, scale = float(c.layer_norm_eps), 72 ** -0.5
+        # 1. patches of the top-left G·p square (384 -> 378 for p = 14: the convolution drops the rest; patchify_nchw copies the crop
+        #    once) -> the fp32 residual stream: bias in the GEMM's bias slot, the position table in its residual slot
+        patches = ops.patchify_nchw(pixel_values[:, :, : G * p, : G * p], p, plans["Kp"])
+        x = torch.empty(B, S, d, device=dev, dtype=F32)
+        ops.linear(patches, plans["w_patch"], x, bias=plans["b_patch"], res=plans["pos"].unsqueeze(0).expand(B, -1, -1))
+        x2, x3 = x.view(B * S, d), x.view(1, B * S, d)
+        xn = torch.empty(B, S, d, device=dev, dtype=BF16)
+        xn2, xn3 = xn.view(B * S, d), xn.view(1, B * S, d)
+        qkv = torch.empty(B, S, 3 * d, device=dev, dtype=BF16)
+        att = torch.empty(B, S, d, device=dev, dtype=BF16)
+        hid = torch.empty(B * S, Fp, device=dev, dtype=BF16)
+        # 2. the layers
+        for wqkv, bqkv, wo, bo, w1, b1, w2, b2, ln1, ln2 in plans["layers"]:
+            ops.layernorm_modulate(x3, xn3, ln1[1], ln1[0], eps=eps)
+            ops.linear(xn2, wqkv, qkv.view(B * S, 3 * d), bias=bqkv)
+            ops.attention_hd72(qkv[..., :d], qkv[..., d : 2 * d], qkv[..., 2 * d :], att, H, scale)
+            ops.linear(att.view(B * S, d), wo, x2, bias=bo, res=x2)
+            ops.layernorm_modulate(x3, xn3, ln2[1], ln2[0], eps=eps)
+            ops.linear(xn2, w1, hid, bias=b1, gelu_from=0)
+            ops.linear(hid, w2, x2, bias=b2, res=x2)
+        # 3. post_layernorm on all tokens
+        last = torch.empty(B, S, d, device=dev, dtype=BF16)
+        ops.layernorm_modulate(x3, last.view(1, B * S, d), plans["post"][1], plans["post"][0], eps=eps)
+        # 4. the attention-pooling head: k|v of the normed tokens in one GEMM, one probe row per batch entry, out_proj, MLP
+        kv = torch.empty(B, S, 2 * d, device=dev, dtype=BF16)
+        ops.linear(last.view(B * S, d), plans["wkv"], kv.view(B * S, 2 * d), bias=plans["bkv"])
+        pa = torch.empty(B, 1, d, device=dev, dtype=BF16)
+        ops.attention_hd72(plans["q_probe"], kv[..., :d], kv[..., d:], pa, H, scale)
+        y = torch.empty(B, d, device=dev, dtype=F32)
+        ops.linear(pa.view(B, d), plans["wo"], y, bias=plans["bo"])
+        yn = torch.empty(1, B, d, device=dev, dtype=BF16)
+        ops.layernorm_modulate(y.view(1, B, d), yn, plans["head_ln"][1], plans["head_ln"][0], eps=eps)
+        hw1, hb1, hw2, hb2 = plans["head_mlp"]
+        hh = torch.empty(B, hw1.shape[0], device=dev, dtype=BF16)
+        ops.linear(yn.view(B, d), hw1, hh, bias=hb1, gelu_from=0)
+        ops.linear(hh, hw2, y, bias=hb2, res=y)
+        pooled = ops.to_bf16(y)
+        return SiglipVisionModelOutput(last, pooled) if return_dict else (last, pooled)
 
     __call__ = forward

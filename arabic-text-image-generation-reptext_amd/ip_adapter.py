@@ -38,8 +38,8 @@ offline, so parity with upstream is unpinned here too. What the tests pin is par
 — as a flat dict, a flat .safetensors file, or the upstream ``ip-adapter.bin`` (torch.save of {"image_proj": {...}, "ip_adapter": {...}},
 read with weights_only=True). Refused, naming the key: a block count other than L2 + L1, biases on to_k_ip / to_v_ip, wrong shapes,
 n outside 1..128, E not a multiple of 64 (rt_gemm_bf16 needs K % 64 == 0, and 2E is the second projection's K), unknown keys.
-The image encoder this adapter is trained with (SigLIP-so400m) is not here: the 1152-wide embedding comes in through
-``ip_adapter_image_embeds=``.
+The image encoder this adapter is trained with (SigLIP-so400m) is image_encoder.SiglipVisionModel: ``ip_adapter_image=`` runs it and takes
+its 1152-wide ``pooler_output``; an embedding computed elsewhere still comes in through ``ip_adapter_image_embeds=``.
 """
 from __future__ import annotations
 

@@ -15,7 +15,7 @@ LIB_NAME = "librt_reptext_hip.so"
 LIB_PATH = os.path.join(_HERE, LIB_NAME)
 
 RT_GEMM_MAX_GROUPS = 4
-ABI_VERSION = 14
+ABI_VERSION = 15
 RT_LORA_MAX_TERMS = 8
 
 
@@ -153,6 +153,10 @@ SIGNATURES["rt_add_bf16_2d"] = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i
 RT_ATTENTION_HD64_MAX_S = 4096
 SIGNATURES["rt_attention_hd64"] = [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _f32, _vp]
 SIGNATURES["rt_patchify_nchw"] = [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]
+
+# SigLIP vision encoder (ABI 15; csrc/attention_hd72.hip): heads of 72, separate query and key counts
+RT_ATTENTION_HD72_MAX_S = 1024
+SIGNATURES["rt_attention_hd72"] = [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp]
 
 # loop passes that moved out of the 256x256-tile GEMM / were merged (csrc/gemm_skinny.hip, csrc/norm_elem.hip)
 SIGNATURES["rt_gemm_skinny_bf16"] = [_vp, _vp, _i64, _i32, _i32, C.POINTER(SkinnyGroup), _i32, _vp]

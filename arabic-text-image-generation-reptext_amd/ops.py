@@ -652,6 +652,28 @@ def attention_hd64(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch
     return out
 
 
+def attention_hd72(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, scale: Optional[float] = None) -> torch.Tensor:
+    """out[b, s, h·72:(h+1)·72] = softmax(scale · q_h k_hᵀ) v_h (rt_attention_hd72): non-causal attention with heads of 72, one launch.
+    q [B or 1, Sq, H·72] bf16 (a leading 1 is shared by the batch: the pooling head's probe); k, v [B, Sk, H·72] bf16 views sharing
+    shape and strides (the fused projection); out [B, Sq, H·72] bf16 view with its own strides; 1 <= Sq, Sk <= native.RT_ATTENTION_HD72_MAX_S."""
+    d = H * 72
+    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] != d:
+            raise ValueError(f"{name}: need [B,S,{d}] with unit inner stride, got {tuple(t.shape)} / {t.stride()}")
+    B, Sk, _ = k.shape
+    Sq = q.shape[1]
+    if k.stride() != v.stride() or v.shape != k.shape:
+        raise ValueError("k,v must share shape and strides")
+    if q.shape[0] not in (1, B) or out.shape != (B, Sq, d):
+        raise ValueError(f"q must be [{B} or 1, Sq, {d}] and out [{B}, Sq, {d}], got {tuple(q.shape)} and {tuple(out.shape)}")
+    if not (1 <= Sq <= native.RT_ATTENTION_HD72_MAX_S and 1 <= Sk <= native.RT_ATTENTION_HD72_MAX_S):
+        raise ValueError(f"attention_hd72: 1..{native.RT_ATTENTION_HD72_MAX_S} rows, got {Sq} queries and {Sk} keys")
+    native.check("rt_attention_hd72", native.load().rt_attention_hd72(
+        _dev(q, "q", BF16), q.stride(1), q.stride(0) if q.shape[0] == B and B > 1 else 0, _dev(k, "k", BF16), _dev(v, "v", BF16), k.stride(1),
+        k.stride(0), _dev(out, "out", BF16), out.stride(1), out.stride(0), B, Sq, Sk, H, float(scale if scale is not None else 72 ** -0.5), _stream()))
+    return out
+
+
 def patchify_nchw(x: torch.Tensor, patch: int, Kp: Optional[int] = None) -> torch.Tensor:
     """im2col of a stride-p, kernel-p convolution (rt_patchify_nchw): x [B,3,G·p,G·p] f32 or bf16 -> bf16 [B, G², Kp] with
     row[gy·G + gx][c·p² + dy·p + dx] = x[b, c, gy·p + dy, gx·p + dx] and zero columns from 3p² up to Kp (default: 3p² rounded up to 64)."""

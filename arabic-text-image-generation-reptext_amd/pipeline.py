@@ -187,9 +187,9 @@ class FluxControlNetPipeline:
         tok, tok2 = kwargs.pop("tokenizer", None), kwargs.pop("tokenizer_2", None)
         image_encoder, feature_extractor = kwargs.pop("image_encoder", None), kwargs.pop("feature_extractor", None)
         if image_encoder is None and index.get("image_encoder") not in (None, [None, None]) and os.path.isdir(os.path.join(root, "image_encoder")):
-            from .image_encoder import CLIPVisionModelWithProjection
+            from .image_encoder import image_encoder_class
 
-            image_encoder = CLIPVisionModelWithProjection.from_pretrained(root, subfolder="image_encoder", torch_dtype=dt)
+            image_encoder = image_encoder_class(os.path.join(root, "image_encoder")).from_pretrained(root, subfolder="image_encoder", torch_dtype=dt)
         try:
             if te is None and listed("text_encoder") and os.path.isdir(os.path.join(root, "text_encoder")):
                 from .text_encoders import CLIPTextModel                 # the encoders themselves run on the HIP kernels
@@ -511,12 +511,13 @@ class FluxControlNetPipeline:
         self.transformer.disable_adapters()
 
     # ------------------------------------------------------------------ IP-Adapter (image prompt): the FluxIPAdapterMixin subset, routed
-    # to the transformer (ip_adapter.py); the image side is image_encoder.CLIPVisionModelWithProjection.
+    # to the transformer (ip_adapter.py); the image side is image_encoder.CLIPVisionModelWithProjection or SiglipVisionModel.
     def load_ip_adapter(self, pretrained_model_name_or_path_or_dict, subfolder: Optional[str] = None, weight_name: Optional[str] = None,
                         image_encoder_pretrained_model_name_or_path: Optional[str] = None, image_encoder_subfolder: Optional[str] = None,
                         **kwargs):
         """``image_encoder_pretrained_model_name_or_path`` (+ ``image_encoder_subfolder``): a local directory, or a hub id in the local
-        hub cache, that holds a CLIP vision ``config.json`` — loaded as ``self.image_encoder``. A name that does not resolve to one
+        hub cache, that holds a CLIP or SigLIP vision ``config.json`` (image_encoder.image_encoder_class picks the class) — loaded as
+        ``self.image_encoder``. A name that does not resolve to one
         leaves the pipeline's encoder as it is (one log line): nothing is fetched, and ``ip_adapter_image_embeds`` need no encoder."""
         self.transformer.load_ip_adapter(pretrained_model_name_or_path_or_dict, subfolder=subfolder, weight_name=weight_name)
         name = image_encoder_pretrained_model_name_or_path
@@ -534,9 +535,9 @@ class FluxControlNetPipeline:
             print(f"[reptext_amd] load_ip_adapter: image encoder '{name}' is not a local directory with a config.json; keeping "
                   f"image_encoder = {type(self.image_encoder).__name__}", file=sys.stderr, flush=True)
             return
-        from .image_encoder import CLIPVisionModelWithProjection
+        from .image_encoder import image_encoder_class
 
-        enc = CLIPVisionModelWithProjection.from_pretrained(d, torch_dtype=torch.bfloat16)
+        enc = image_encoder_class(d).from_pretrained(d, torch_dtype=torch.bfloat16)
         self.image_encoder = enc.to(self.transformer.device)
 
     def set_ip_adapter_scale(self, scale):
@@ -587,21 +588,26 @@ class FluxControlNetPipeline:
         return e.to(device=device, dtype=torch.bfloat16).contiguous(), kw
 
     def encode_image(self, image, device=None, num_images_per_prompt: int = 1) -> torch.Tensor:
-        """[B·num_images_per_prompt, projection_dim] bf16 image embeddings of ``self.image_encoder``. A tensor is taken as
-        ``pixel_values`` (diffusers' rule); anything else goes through ``self.feature_extractor(images=..., return_tensors="pt")``
-        when one is set, else ``image_encoder.clip_preprocess`` at the encoder's image size. One encoder run on the current stream."""
+        """[B·num_images_per_prompt, E] bf16 image embeddings of ``self.image_encoder``: ``image_embeds`` of the CLIP encoder,
+        ``pooler_output`` of a ``SiglipVisionModel``. A tensor is taken as ``pixel_values`` (diffusers' rule); anything else goes through
+        ``self.feature_extractor(images=..., return_tensors="pt")`` when one is set, else ``image_encoder.clip_preprocess`` /
+        ``siglip_preprocess`` at the encoder's image size. One encoder run on the current stream."""
         if self.image_encoder is None:
             raise ValueError("encode_image: this pipeline has no image_encoder")
         device = device or self._execution_device
+        from .image_encoder import SiglipVisionModel
+
+        siglip = isinstance(self.image_encoder, SiglipVisionModel)
         if isinstance(image, torch.Tensor):
             pixel_values = image if image.dim() == 4 else image[None]
         elif self.feature_extractor is not None:
             pixel_values = self.feature_extractor(images=image, return_tensors="pt").pixel_values
         else:
-            from .image_encoder import clip_preprocess
+            from .image_encoder import clip_preprocess, siglip_preprocess
 
-            pixel_values = clip_preprocess(image, size=self.image_encoder.config.image_size)
-        embeds = self.image_encoder(pixel_values.to(device)).image_embeds
+            pixel_values = (siglip_preprocess if siglip else clip_preprocess)(image, size=self.image_encoder.config.image_size)
+        out = self.image_encoder(pixel_values.to(device))
+        embeds = out.pooler_output if siglip else out.image_embeds
         return embeds.repeat_interleave(num_images_per_prompt, dim=0) if num_images_per_prompt != 1 else embeds
 
     def _lora_models(self) -> list:

@@ -382,6 +382,30 @@ int rt_attention_hd64(const void* q, const void* k, const void* v, int64_t ld, i
  * chunks of output (RT_E_SHAPE); Kp % 64, out not 16-byte aligned, x not aligned to its element (RT_E_ALIGN). */
 int rt_patchify_nchw(const void* x, int32_t x_f32, void* out, int32_t B, int32_t G, int32_t p, int32_t Kp, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * SigLIP vision encoder (ABI 15; image_encoder.py: `SiglipVisionModel`, the image encoder of the InstantX IP-Adapter). Once per
+ * image prompt, outside the loop. Matrix work is rt_gemm_bf16, norms rt_layernorm_modulate, patches rt_patchify_nchw.
+ * ---------------------------------------------------------------------------------------- */
+/* Attention with heads of 72, non-causal, no bias, separate query and key counts (csrc/attention_hd72.hip):
+ *   o[b][s][h*72 .. h*72+71] = softmax(scale * q_h k_h^T) v_h        for every batch entry b, head h and query row s < Sq, over Sk keys
+ * q: bf16 [B][Sq][ldq] with batch stride stride_qb (elements); stride_qb == 0 is allowed: one set of query rows shared by the
+ * batch (the probe of the attention-pooling head). k / v: bf16 views of one [B][Sk][ldkv] buffer (common row stride ldkv and batch
+ * stride stride_kvb; ldq = ldkv = 3*H*72 for the fused q|k|v projection), head h at column h*72 (144 bytes per head: 16-byte
+ * chunks stay aligned); o: bf16 [B][Sq][ldo]. Both products on v_mfma_f32_16x16x32_bf16 (columns 64..71 in a third k-step whose
+ * other lanes hold zeros); scores, row maximum, row sum and accumulators fp32; P rounded to bf16 as the second product's operand,
+ * the row sum taken from the unrounded P; online softmax over key tiles of 64, o normalised once at the end; keys past Sk are
+ * padded inside the kernel and masked; nothing is read outside rows < Sq / Sk and columns < H*72 of the inputs. Only rows < Sq and
+ * columns < H*72 of each batch entry of o are written; no atomics: two runs give the same bits, and a row's bits do not depend on
+ * the workgroup size the host picks. Any 1 <= Sq, Sk <= RT_ATTENTION_HD72_MAX_S.
+ * Rejected on the host: null pointers, B / Sq / Sk / H < 1, scale <= 0, ldq, ldkv or ldo < H*72, a negative batch stride
+ * (RT_E_BADARG); Sq or Sk > RT_ATTENTION_HD72_MAX_S, B or H > 65535 (RT_E_SHAPE); pointers not 16-byte aligned, a leading
+ * dimension or batch stride not a multiple of 8 (RT_E_ALIGN). */
+#define RT_ATTENTION_HD72_MAX_S 1024
+int rt_attention_hd72(const void* q, int64_t ldq, int64_t stride_qb,
+                      const void* k, const void* v, int64_t ldkv, int64_t stride_kvb,
+                      void* o, int64_t ldo, int64_t stride_ob,
+                      int32_t B, int32_t Sq, int32_t Sk, int32_t H, float scale, void* stream);
+
 /* FlowMatchEulerDiscreteScheduler.step (PIPE:1109; A.6): x = bf16(f32(x) + dsigma·f32(v)), in place. */
 int rt_euler_step(void* x, const void* v, float dsigma, int64_t n, void* stream);
 

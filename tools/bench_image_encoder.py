@@ -5,7 +5,10 @@
   three alternating timed runs each after warm-up, and the two outputs compared;
   * rt_attention_hd64 alone at (B = 1, S = 257, H = 16) and (B = 4, ...), on a rotating set of buffers; `--kernel-only` stops here
     (the form to run under `rocprofv3 --kernel-trace --stats`; RT_HD64_WAVES = 1 | 2 | 4 forces the workgroup size for an A/B).
-Prints a table and one JSON line.  python tools/bench_image_encoder.py [--repeats 3] [--layers 24] [--kernel-only]"""
+`--siglip` measures the SigLIP-so400m encoder instead (27 layers, d = 1152, 16 heads of 72, 729 tokens from a 384 x 384 image, random
+weights), B = 1 and B = 4: ms per forward, three timed runs each, and rt_attention_hd72 alone at the self-attention shape (Sq = Sk =
+729) and at the pooling call (Sq = 1, one probe row shared by the batch). There is no earlier form to compare against.
+Prints a table and one JSON line.  python tools/bench_image_encoder.py [--siglip] [--repeats 3] [--layers 24 | 27] [--kernel-only]"""
 import argparse
 import json
 import os
@@ -69,16 +72,69 @@ def kernel_bench(dev, S=257, H=16):
     return res
 
 
+def kernel_bench_hd72(dev, S=729, H=16):
+    d = H * 72
+    res = {"RT_HD72_WAVES": os.environ.get("RT_HD72_WAVES", "")}
+    nbuf = 8
+    for B in (1, 4):
+        qkv = [torch.randn(B, S, 3 * d, device=dev).to(torch.bfloat16) for _ in range(nbuf)]
+        out = [torch.empty(B, S, d, device=dev, dtype=torch.bfloat16) for _ in range(nbuf)]
+        pooled = [torch.empty(B, 1, d, device=dev, dtype=torch.bfloat16) for _ in range(nbuf)]
+        i = [0]
+
+        def self_attention():
+            j = i[0] % nbuf
+            ops.attention_hd72(qkv[j][..., :d], qkv[j][..., d:2 * d], qkv[j][..., 2 * d:], out[j], H)
+            i[0] += 1
+
+        def pooling():
+            j = i[0] % nbuf
+            ops.attention_hd72(qkv[j][:1, :1, :d], qkv[j][..., d:2 * d], qkv[j][..., 2 * d:], pooled[j], H)
+            i[0] += 1
+        res[f"B{B}"] = {}
+        for name, fn in (("self", self_attention), ("pooling", pooling)):
+            t = sorted(timed(fn, 25 * nbuf, warm=nbuf) for _ in range(3))[1]         # median of three; back-to-back launches
+            res[f"B{B}"][name + "_us"] = round(t * 1e6, 2)
+            print(f"rt_attention_hd72 B = {B}, Sk = {S}, H = {H}, {name:7s}: {t * 1e6:7.2f} us per launch (back to back)", flush=True)
+    return res
+
+
+def main_siglip(args, dev):
+    from reptext_amd.image_encoder import SiglipVisionModel
+
+    layers = args.layers if args.layers is not None else 27
+    result = {"tool": "bench_image_encoder", "encoder_model": "siglip-so400m-patch14-384 shape, random weights",
+              "device": torch.cuda.get_device_name(0), "layers": layers, "kernel": kernel_bench_hd72(dev)}
+    if args.kernel_only:
+        print(json.dumps(result), flush=True)
+        return
+    model = SiglipVisionModel(num_hidden_layers=layers, device=dev, dtype=torch.bfloat16).random_init_(seed=0)
+    g = torch.Generator(device=dev).manual_seed(0)
+    result["encoder"] = {}
+    for B in (1, 4):
+        pix = torch.randn(B, 3, 384, 384, device=dev, generator=g)
+        pooled = model(pix).pooler_output                                            # also the warm-up (plans, allocator)
+        assert bool(torch.isfinite(pooled.float()).all())
+        ms = [timed(lambda: model(pix), args.iters, warm=1) * 1e3 for _ in range(args.repeats)]
+        result["encoder"][f"B{B}"] = {"ms": [round(t, 3) for t in ms]}
+        print(f"B = {B} SigLIP encoder: ms per forward " + "  ".join(f"{t:8.3f}" for t in ms), flush=True)
+    print(json.dumps(result), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeats", type=int, default=3)
-    ap.add_argument("--layers", type=int, default=24)
+    ap.add_argument("--layers", type=int, default=None, help="default: 24 (CLIP ViT-L/14), 27 (--siglip)")
+    ap.add_argument("--siglip", action="store_true", help="the SigLIP-so400m encoder (rt_attention_hd72) instead of CLIP ViT-L/14")
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--kernel-only", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_image_encoder.py measures on an MI355X; no GPU is visible")
     dev = torch.device("cuda:0")
+    if args.siglip:
+        return main_siglip(args, dev)
+    args.layers = 24 if args.layers is None else args.layers
     result = {"tool": "bench_image_encoder", "device": torch.cuda.get_device_name(0), "layers": args.layers, "kernel": kernel_bench(dev)}
     if args.kernel_only:
         print(json.dumps(result), flush=True)

@@ -8,6 +8,8 @@ encoders, which sit outside the hot path. With real checkpoints on disk use `Flu
 
     python tools/infer_demo.py [--size 1024] [--steps 30] [--depth-scale 1.0] [--out gpurun_out/result.jpg]
     python tools/infer_demo.py --ip-image photo.jpg   # adds an image prompt: CLIP ViT-L/14 vision encoder + a 4-token IP-Adapter, random weights
+    python tools/infer_demo.py --ip-image photo.jpg --ip-layout instantx   # the InstantX layout instead: SigLIP-so400m encoder (1152-wide
+                                              # pooler_output) + a 128-token adapter with a term in all 19 + 38 blocks, random weights
     python tools/infer_demo.py --inpaint      # infer_inpaint.py's flow (infer_inpaint.py:48-155): second 68-channel tower, masked
                                               # background image, position mask = bbox+-5, true CFG with negative embeddings
 """
@@ -31,6 +33,7 @@ ap.add_argument("--depth-scale", type=float, default=1.0)
 ap.add_argument("--out", default="gpurun_out/result.jpg")
 ap.add_argument("--inpaint", action="store_true")
 ap.add_argument("--ip-image", default=None, help="image prompt for the text-to-image flow (ip_adapter_image=)")
+ap.add_argument("--ip-layout", choices=("xlabs", "instantx"), default="xlabs", help="adapter + encoder pair behind --ip-image")
 a = ap.parse_args()
 dev, bf16 = torch.device("cuda:0"), torch.bfloat16
 ct, cc = flux_dev_transformer_config(), reptext_controlnet_config()
@@ -87,11 +90,15 @@ if a.inpaint:
 ip_kwargs = {}
 if a.ip_image:
     from PIL import Image
-    from reptext_amd.image_encoder import CLIPVisionModelWithProjection
-    from tools.bench_ip_adapter import adapter_sd
+    from reptext_amd.image_encoder import CLIPVisionModelWithProjection, SiglipVisionModel
+    from tools.bench_ip_adapter import adapter_sd, adapter_sd_instantx
 
-    pipe.image_encoder = CLIPVisionModelWithProjection(device=dev, dtype=bf16).random_init_(seed=4)      # ViT-L/14 shape, 768-wide embeds
-    pipe.load_ip_adapter(adapter_sd(pipe.transformer, 4, dev, seed=5))
+    if a.ip_layout == "instantx":
+        pipe.image_encoder = SiglipVisionModel(device=dev, dtype=bf16).random_init_(seed=4)              # so400m shape, 1152-wide pooler_output
+        pipe.load_ip_adapter(adapter_sd_instantx(pipe.transformer, 128, dev, seed=5))
+    else:
+        pipe.image_encoder = CLIPVisionModelWithProjection(device=dev, dtype=bf16).random_init_(seed=4)  # ViT-L/14 shape, 768-wide embeds
+        pipe.load_ip_adapter(adapter_sd(pipe.transformer, 4, dev, seed=5))
     pipe.set_ip_adapter_scale(0.7)
     ip_kwargs = dict(ip_adapter_image=Image.open(a.ip_image))
 
