@@ -1,4 +1,4 @@
-// CLIP vision encoder (image_encoder.py): the patch embedding's im2col. The attention of its layers is attention_hd64.hip; every
+// CLIP vision encoder (image_encoder.py): the patch embedding's im2col. The attention of its layers is attention_small_head.hip; every
 // other step runs on the kernels the text encoders use.
 #include "rt_common.h"
 

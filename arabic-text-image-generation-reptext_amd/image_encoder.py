@@ -1,6 +1,7 @@
 """The vision encoders on the HIP kernels: the image encoders behind ``pipe(..., ip_adapter_image=img)`` — CLIP ViT-L/14 for the
-XLabs / diffusers IP-Adapter, SigLIP-so400m for the InstantX one (``SiglipVisionModel``, second half of this file;
-``image_encoder_class`` picks between them from a directory's ``config.json``).
+XLabs / diffusers IP-Adapter, SigLIP-so400m for the InstantX one (``image_encoder_class`` picks between them from a directory's
+``config.json``). Both are pre-LN ViT towers and share ``_VisionTower``: the plans, the input checks and the layer loop; a class keeps
+its constructor, its state-dict layout, and what comes before and after the layers.
 
 ``CLIPVisionModelWithProjection`` has the class name, constructor config keys, module names and state-dict keys of `transformers`'
 class (``vision_model.pre_layrnorm`` in transformers' spelling, ``vision_model.post_layernorm``, a top-level
@@ -11,10 +12,11 @@ quick_gelu and no mask, ``post_layernorm`` on the class token and the bias-free 
 
 It runs once per image prompt, outside the denoising loop. The patch convolution is rt_patchify_nchw (im2col) + rt_gemm_bf16, whose
 epilogue also adds the position embeddings; the residual stream is fp32, as in text_encoders.CLIPTextModel, and starts from the
-bf16 output of ``pre_layrnorm``; attention is ONE rt_attention_hd64 launch per layer (csrc/attention_hd64.hip) on the fused q|k|v
-buffer with the tokens as they are: S = 257 needs no padding to 64.
+bf16 output of ``pre_layrnorm``; attention is ONE rt_attention_hd64 launch per layer (csrc/attention_small_head.hip) on the fused
+q|k|v buffer with the tokens as they are: S = 257 needs no padding to 64. ``SiglipVisionModel`` is described at its class.
 
-``clip_preprocess`` is the host side (PIL), the way tokenisation is for the text encoders: CLIPImageProcessor's default steps.
+``clip_preprocess`` / ``siglip_preprocess`` are the host side (PIL), the way tokenisation is for the text encoders: the default
+steps of CLIPImageProcessor and SiglipImageProcessor.
 """
 from __future__ import annotations
 
@@ -35,6 +37,25 @@ OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
 
 
+def _rgb_images(image, who: str) -> list:
+    """``image`` — a PIL image, a uint8 HWC (or HW) numpy array, or a list of them — as a list of RGB PIL images."""
+    from PIL import Image
+
+    images = list(image) if isinstance(image, (list, tuple)) else [image]
+    if not images:
+        raise ValueError(f"{who}: no image")
+    out = []
+    for im in images:
+        if isinstance(im, np.ndarray):
+            if im.dtype != np.uint8 or im.ndim not in (2, 3):
+                raise TypeError(f"{who}: numpy images must be uint8 [H,W,C] (or [H,W])")
+            im = Image.fromarray(im)
+        if not isinstance(im, Image.Image):
+            raise TypeError(f"{who}: expected a PIL image or a uint8 numpy array, got {type(im)}")
+        out.append(im.convert("RGB"))
+    return out
+
+
 def clip_preprocess(image, size: int = 224) -> torch.Tensor:
     """CLIPImageProcessor's defaults on the host: RGB, shortest edge resized to ``size`` (bicubic; the long edge becomes
     int(size·long/short)), centre crop to size², ·1/255, (x − mean)/std with the OpenAI CLIP constants. ``image``: a PIL image, a
@@ -42,19 +63,9 @@ def clip_preprocess(image, size: int = 224) -> torch.Tensor:
     (expression order), not bit-equal."""
     from PIL import Image
 
-    images = list(image) if isinstance(image, (list, tuple)) else [image]
-    if not images:
-        raise ValueError("clip_preprocess: no image")
     mean, std = np.asarray(OPENAI_CLIP_MEAN, dtype=np.float32), np.asarray(OPENAI_CLIP_STD, dtype=np.float32)
     out = []
-    for im in images:
-        if isinstance(im, np.ndarray):
-            if im.dtype != np.uint8 or im.ndim not in (2, 3):
-                raise TypeError("clip_preprocess: numpy images must be uint8 [H,W,C] (or [H,W])")
-            im = Image.fromarray(im)
-        if not isinstance(im, Image.Image):
-            raise TypeError(f"clip_preprocess: expected a PIL image or a uint8 numpy array, got {type(im)}")
-        im = im.convert("RGB")
+    for im in _rgb_images(image, "clip_preprocess"):
         w, h = im.size
         short, long_ = (w, h) if w <= h else (h, w)
         new_long = int(size * long_ / short)
@@ -67,212 +78,14 @@ def clip_preprocess(image, size: int = 224) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(np.stack(out), dtype=np.float32))
 
 
-class CLIPVisionModelOutput(tuple):
-    """(image_embeds, last_hidden_state) with attribute access, transformers' field order."""
-
-    def __new__(cls, image_embeds, last_hidden_state):
-        obj = super().__new__(cls, (image_embeds, last_hidden_state))
-        obj.image_embeds, obj.last_hidden_state = image_embeds, last_hidden_state
-        return obj
-
-
-class CLIPVisionModelWithProjection(nn.Module, WeightsIO):
-    config_name = "config.json"
-    weights_name = "model.safetensors"
-
-    def __init__(self, hidden_size: int = 1024, intermediate_size: int = 4096, projection_dim: int = 768, num_hidden_layers: int = 24,
-                 num_attention_heads: int = 16, num_channels: int = 3, image_size: int = 224, patch_size: int = 14,
-                 hidden_act: str = "quick_gelu", layer_norm_eps: float = 1e-5, device=None, dtype=None, **unused):
-        super().__init__()
-        if hidden_size % num_attention_heads or hidden_size // num_attention_heads != 64:
-            raise ValueError("CLIPVisionModelWithProjection (HIP): head dim must be 64 (ViT-L/14: 1024 / 16; ViT-H's 80 is not built)")
-        if hidden_act != "quick_gelu":
-            raise ValueError("CLIPVisionModelWithProjection (HIP): only quick_gelu (openai/clip-vit-large-patch14) is implemented")
-        if image_size % patch_size:
-            raise ValueError(f"CLIPVisionModelWithProjection (HIP): image_size {image_size} is not a multiple of patch_size {patch_size}")
-        if num_channels != 3 or projection_dim % 4 or intermediate_size % 64:
-            raise ValueError("CLIPVisionModelWithProjection (HIP): 3 channels, projection_dim % 4 == 0 and intermediate_size % 64 == 0")
-        self.config = Config(hidden_size=hidden_size, intermediate_size=intermediate_size, projection_dim=projection_dim,
-                             num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads, num_channels=num_channels,
-                             image_size=image_size, patch_size=patch_size, hidden_act=hidden_act, layer_norm_eps=layer_norm_eps)
-        kw = dict(device=device, dtype=dtype)
-        vm = _H()
-        emb = _H()
-        emb.class_embedding = nn.Parameter(torch.empty(hidden_size, **kw), requires_grad=False)
-        emb.patch_embedding = _W(hidden_size, num_channels, patch_size, patch_size, **kw)
-        emb.position_embedding = _W((image_size // patch_size) ** 2 + 1, hidden_size, **kw)
-        vm.embeddings = emb
-        vm.pre_layrnorm = _WB(hidden_size, **kw)
-        enc = _H()
-        enc.layers = nn.ModuleList()
-        for _ in range(num_hidden_layers):
-            l = _H()
-            sa = _H()
-            sa.q_proj, sa.k_proj, sa.v_proj, sa.out_proj = (_WB(hidden_size, hidden_size, **kw) for _ in range(4))
-            l.self_attn = sa
-            l.layer_norm1, l.layer_norm2 = _WB(hidden_size, **kw), _WB(hidden_size, **kw)
-            mlp = _H()
-            mlp.fc1, mlp.fc2 = _WB(intermediate_size, hidden_size, **kw), _WB(hidden_size, intermediate_size, **kw)
-            l.mlp = mlp
-            enc.layers.append(l)
-        vm.encoder = enc
-        vm.post_layernorm = _WB(hidden_size, **kw)
-        self.vision_model = vm
-        self.visual_projection = _W(projection_dim, hidden_size, **kw)
-        self._plans = None
-
-    @property
-    def dtype(self):
-        return self.visual_projection.weight.dtype
-
-    @property
-    def device(self):
-        return self.visual_projection.weight.device
-
-    def _apply(self, fn, *a, **k):
-        self._plans = None
-        return super()._apply(fn, *a, **k)
-
-    def load_state_dict(self, sd, strict: bool = True, **kw):
-        # accept the encoder's keys with or without the `vision_model.` prefix (CLIPVisionModel's own layout), as CLIPTextModel does
-        if not any(k.startswith("vision_model.") for k in sd):
-            sd = {k if k.startswith("visual_projection.") else "vision_model." + k: v for k, v in sd.items()}
-        sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
-        self._plans = None
-        return super().load_state_dict(sd, strict=strict, **kw)
-
-    @classmethod
-    def from_pretrained(cls, path: str, torch_dtype=None, subfolder: Optional[str] = None, device=None, **unused):
-        d = cls._resolve_dir(path, subfolder)
-        with open(os.path.join(d, cls.config_name)) as f:
-            cfg = json.load(f)
-        cfg = cfg.get("vision_config", cfg)
-        m = cls(**cfg, device=device or "cpu", dtype=torch_dtype or BF16)
-        m.load_state_dict({k: v.to(torch_dtype or BF16) for k, v in cls._load_safetensors_dir(d).items()}, strict=True)
-        return m
-
-    def random_init_(self, seed: int = 0):
-        """Random weights at an exercised scale, for tools and tests that run without a checkpoint: matrices at 1/sqrt(fan-in),
-        embeddings at unit scale, LayerNorms at identity, biases zero."""
-        g = torch.Generator().manual_seed(seed)
-        for n, p in self.named_parameters():
-            if "norm" in n and n.endswith("weight"):
-                p.data.fill_(1.0)
-            elif n.endswith("bias"):
-                p.data.zero_()
-            else:
-                std = 1.0 if p.dim() == 1 or "position_embedding" in n else p[0].numel() ** -0.5
-                p.data.copy_(torch.randn(p.shape, generator=g) * std)
-        self._plans = None
-        return self
-
-    def _ensure_plans(self):
-        if self._plans is not None:
-            return self._plans
-        if self.dtype != BF16 or not self.visual_projection.weight.is_cuda:
-            raise RuntimeError("CLIPVisionModelWithProjection (HIP): bf16 on the GPU only; there is no CPU fallback")
-
-        def affine(ln):           # LayerNorm(x)·w + b == LN(x)·(1 + (w - 1)) + b: the adaLN kernel with constant vectors
-            return (ln.weight.data.to(F32) - 1.0).reshape(1, -1).contiguous(), ln.bias.data.to(F32).reshape(1, -1).contiguous()
-
-        c, vm = self.config, self.vision_model
-        d, k = c.hidden_size, 3 * c.patch_size ** 2
-        Kp = (k + 63) // 64 * 64                                                  # the GEMM's K % 64 rule: 588 -> 640 for p = 14
-        w_patch = torch.zeros(d, Kp, device=self.device, dtype=BF16)
-        w_patch[:, :k] = vm.embeddings.patch_embedding.weight.data.reshape(d, k)
-        pos = vm.embeddings.position_embedding.weight.data.to(F32)
-        cls_row = (vm.embeddings.class_embedding.data.to(F32) + pos[0]).contiguous()   # the class row is a constant of the weights
-        layers = []
-        for l in vm.encoder.layers:
-            sa = l.self_attn
-            wqkv = torch.cat([sa.q_proj.weight.data, sa.k_proj.weight.data, sa.v_proj.weight.data], dim=0).contiguous()
-            bqkv = torch.cat([sa.q_proj.bias.data, sa.k_proj.bias.data, sa.v_proj.bias.data], dim=0).contiguous()
-            layers.append((wqkv, bqkv, sa.out_proj.weight.data, sa.out_proj.bias.data, l.mlp.fc1.weight.data, l.mlp.fc1.bias.data,
-                           l.mlp.fc2.weight.data, l.mlp.fc2.bias.data, affine(l.layer_norm1), affine(l.layer_norm2)))
-        self._plans = dict(w_patch=w_patch, Kp=Kp, pos_patches=pos[1:].contiguous(), cls_row=cls_row, pre=affine(vm.pre_layrnorm),
-                           post=affine(vm.post_layernorm), layers=layers)
-        return self._plans
-
-    # The two hooks tools/bench_image_encoder.py overrides to time the per-head assembled attention on the same forward.
-    def _padded_tokens(self, S: int) -> int:
-        """Rows per batch entry of the token buffers: the fused attention takes S as it is."""
-        return S
-
-    def _attention(self, qkv: torch.Tensor, att: torch.Tensor, S: int) -> None:
-        d, H = self.config.hidden_size, self.config.num_attention_heads
-        ops.attention_hd64(qkv[:, :S, :d], qkv[:, :S, d : 2 * d], qkv[:, :S, 2 * d :], att[:, :S], H, 64 ** -0.5)
-
-    @torch.no_grad()
-    def forward(self, pixel_values: torch.Tensor, output_attentions=None, output_hidden_states=None, interpolate_pos_encoding: bool = False,
-                return_dict: bool = True, **unused):
-        if output_attentions or output_hidden_states or interpolate_pos_encoding:
-            raise NotImplementedError("CLIPVisionModelWithProjection (HIP): only image_embeds and last_hidden_state are produced, at the "
-                                      "configured image size")
-        plans = self._ensure_plans()
-        c, dev, lib = self.config, self.device, native.load()
-        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, c.image_size, c.image_size):
-            raise ValueError(f"pixel_values must be [B,3,{c.image_size},{c.image_size}], got {tuple(pixel_values.shape)}")
-        if pixel_values.dtype not in (BF16, F32):
-            pixel_values = pixel_values.to(F32)
-        pixel_values = pixel_values.to(dev)
-        B, d, F_, p = pixel_values.shape[0], c.hidden_size, c.intermediate_size, c.patch_size
-        G = c.image_size // p
-        S = G * G + 1
-        Sp = self._padded_tokens(S)
-        eps = float(c.layer_norm_eps)
-        # 1-2. patches -> fp32 rows 1.. of every batch entry, position embeddings added by the GEMM's residual slot; row 0 is constant
-        patches = ops.patchify_nchw(pixel_values, p, plans["Kp"])
-        e = torch.zeros(B, Sp, d, device=dev, dtype=F32) if Sp != S else torch.empty(B, S, d, device=dev, dtype=F32)
-        e[:, 0] = plans["cls_row"]
-        ops.linear(patches, plans["w_patch"], e[:, 1:S], res=plans["pos_patches"].unsqueeze(0).expand(B, -1, -1))
-        # 3. pre_layrnorm; its bf16 output starts the fp32 residual stream
-        xn = torch.empty(B, Sp, d, device=dev, dtype=BF16)
-        e2, xn2 = e.view(1, B * Sp, d), xn.view(1, B * Sp, d)
-        ops.layernorm_modulate(e2, xn2, plans["pre"][1], plans["pre"][0], eps=eps)
-        x = ops.to_f32(xn)
-        x2, x3 = x.view(B * Sp, d), x.view(1, B * Sp, d)
-        qkv = torch.empty(B, Sp, 3 * d, device=dev, dtype=BF16)
-        att = torch.zeros(B, Sp, d, device=dev, dtype=BF16) if Sp != S else torch.empty(B, S, d, device=dev, dtype=BF16)
-        hid = torch.empty(B * Sp, F_, device=dev, dtype=BF16)
-        # 4. the layers
-        for wqkv, bqkv, wo, bo, w1, b1, w2, b2, ln1, ln2 in plans["layers"]:
-            ops.layernorm_modulate(x3, xn2, ln1[1], ln1[0], eps=eps)
-            ops.linear(xn.view(B * Sp, d), wqkv, qkv.view(B * Sp, 3 * d), bias=bqkv)
-            self._attention(qkv, att, S)
-            ops.linear(att.view(B * Sp, d), wo, x2, bias=bo, res=x2)
-            ops.layernorm_modulate(x3, xn2, ln2[1], ln2[0], eps=eps)
-            ops.linear(xn.view(B * Sp, d), w1, hid, bias=b1)
-            native.check("rt_quick_gelu", lib.rt_quick_gelu(hid.data_ptr(), hid.numel(), _stream()))
-            ops.linear(hid, w2, x2, bias=b2, res=x2)
-        last = ops.to_bf16(x)[:, :S]
-        # 5-6. post_layernorm on the class token, visual_projection
-        pooled = torch.empty(B, 1, d, device=dev, dtype=BF16)
-        ops.layernorm_modulate(x[:, 0:1], pooled, plans["post"][1].expand(B, -1), plans["post"][0].expand(B, -1), eps=eps)
-        embeds = torch.empty(B, c.projection_dim, device=dev, dtype=BF16)
-        ops.linear(pooled.view(B, d), self.visual_projection.weight.data, embeds)
-        return CLIPVisionModelOutput(embeds, last) if return_dict else (embeds, last)
-
-    __call__ = forward
-
-
-# ======================================================================================================================= SigLIP
 def siglip_preprocess(image, size: int = 384) -> torch.Tensor:
     """SiglipImageProcessor's defaults on the host: RGB, resized straight to size x size (bicubic; no aspect keeping, no crop),
     ·1/255, (x − 0.5)/0.5. ``image``: a PIL image, a uint8 HWC (or HW) numpy array, or a list of them -> f32 [B,3,size,size]."""
     from PIL import Image
 
-    images = list(image) if isinstance(image, (list, tuple)) else [image]
-    if not images:
-        raise ValueError("siglip_preprocess: no image")
     out = []
-    for im in images:
-        if isinstance(im, np.ndarray):
-            if im.dtype != np.uint8 or im.ndim not in (2, 3):
-                raise TypeError("siglip_preprocess: numpy images must be uint8 [H,W,C] (or [H,W])")
-            im = Image.fromarray(im)
-        if not isinstance(im, Image.Image):
-            raise TypeError(f"siglip_preprocess: expected a PIL image or a uint8 numpy array, got {type(im)}")
-        im = im.convert("RGB").resize((size, size), resample=Image.BICUBIC)
+    for im in _rgb_images(image, "siglip_preprocess"):
+        im = im.resize((size, size), resample=Image.BICUBIC)
         x = np.asarray(im, dtype=np.uint8).astype(np.float32) * np.float32(1.0 / 255.0)
         out.append(((x - np.float32(0.5)) / np.float32(0.5)).transpose(2, 0, 1))
     return torch.from_numpy(np.ascontiguousarray(np.stack(out), dtype=np.float32))
@@ -305,6 +118,241 @@ def pad_mlp_to_64(w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor):
     return w1p, b1p, w2p
 
 
+def _affine(ln):                  # LayerNorm(x)·w + b == LN(x)·(1 + (w - 1)) + b: the adaLN kernel with constant vectors
+    return (ln.weight.data.to(F32) - 1.0).reshape(1, -1).contiguous(), ln.bias.data.to(F32).reshape(1, -1).contiguous()
+
+
+class _VisionTower(nn.Module, WeightsIO):
+    """What the two encoders share; it holds no parameters of its own. A class names the parameter its dtype and device are read
+    from (``_anchor``), the parameters ``random_init_`` gives unit scale (``_unit_scale``) and its head dim (``_head_dim``: which of
+    the two small-head attention entry points its layers call), builds its modules, and implements ``_build_plans`` and ``forward``."""
+
+    config_name = "config.json"
+    weights_name = "model.safetensors"
+    _anchor: str
+    _unit_scale: tuple
+    _head_dim: int
+
+    @property
+    def dtype(self):
+        return self.get_parameter(self._anchor).dtype
+
+    @property
+    def device(self):
+        return self.get_parameter(self._anchor).device
+
+    def _apply(self, fn, *a, **k):
+        self._plans = None
+        return super()._apply(fn, *a, **k)
+
+    @classmethod
+    def from_pretrained(cls, path: str, torch_dtype=None, subfolder: Optional[str] = None, device=None, **unused):
+        d = cls._resolve_dir(path, subfolder)
+        with open(os.path.join(d, cls.config_name)) as f:
+            cfg = json.load(f)
+        cfg = {k: v for k, v in cfg.get("vision_config", cfg).items() if k not in ("dtype", "device")}    # transformers 5.x records a dtype
+        m = cls(**cfg, device=device or "cpu", dtype=torch_dtype or BF16)
+        m.load_state_dict({k: v.to(torch_dtype or BF16) for k, v in cls._load_safetensors_dir(d).items()}, strict=True)
+        return m
+
+    def random_init_(self, seed: int = 0):
+        """Random weights at an exercised scale, for tools and tests that run without a checkpoint: matrices at 1/sqrt(fan-in),
+        the class token or probe and the positions at unit scale, LayerNorms at identity, biases zero."""
+        g = torch.Generator().manual_seed(seed)
+        for n, p in self.named_parameters():
+            if "norm" in n and n.endswith("weight"):
+                p.data.fill_(1.0)
+            elif n.endswith("bias"):
+                p.data.zero_()
+            else:
+                std = 1.0 if any(u in n for u in self._unit_scale) else p[0].numel() ** -0.5
+                p.data.copy_(torch.randn(p.shape, generator=g) * std)
+        self._plans = None
+        return self
+
+    def _ensure_plans(self):
+        if self._plans is None:
+            if self.dtype != BF16 or self.device.type != "cuda":
+                raise RuntimeError(f"{type(self).__name__} (HIP): bf16 on the GPU only; there is no CPU fallback")
+            self._plans = self._build_plans()
+        return self._plans
+
+    def _tower_plans(self, emb, layers) -> dict:
+        """The plans both towers need: the patch weight as a GEMM operand and, per layer, (wqkv, bqkv, wo, bo, w1, b1, w2, b2, ln1, ln2)."""
+        c = self.config
+        d, k = c.hidden_size, 3 * c.patch_size ** 2
+        Kp = (k + 63) // 64 * 64                                                  # the GEMM's K % 64 rule: 588 -> 640 for p = 14
+        w_patch = torch.zeros(d, Kp, device=self.device, dtype=BF16)
+        w_patch[:, :k] = emb.patch_embedding.weight.data.reshape(d, k)
+        plan = []
+        for l in layers:
+            sa = l.self_attn
+            wqkv = torch.cat([sa.q_proj.weight.data, sa.k_proj.weight.data, sa.v_proj.weight.data], dim=0).contiguous()
+            bqkv = torch.cat([sa.q_proj.bias.data, sa.k_proj.bias.data, sa.v_proj.bias.data], dim=0).contiguous()
+            # the identity for CLIP, whose constructor requires intermediate_size % 64 == 0
+            w1, b1, w2 = pad_mlp_to_64(l.mlp.fc1.weight.data, l.mlp.fc1.bias.data, l.mlp.fc2.weight.data)
+            plan.append((wqkv, bqkv, sa.out_proj.weight.data, sa.out_proj.bias.data, w1, b1, w2, l.mlp.fc2.bias.data,
+                         _affine(l.layer_norm1), _affine(l.layer_norm2)))
+        return dict(w_patch=w_patch, Kp=Kp, Fp=(c.intermediate_size + 63) // 64 * 64, layers=plan)
+
+    def _pixels(self, pixel_values: torch.Tensor) -> torch.Tensor:
+        c = self.config
+        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, c.image_size, c.image_size):
+            raise ValueError(f"pixel_values must be [B,3,{c.image_size},{c.image_size}], got {tuple(pixel_values.shape)}")
+        if pixel_values.dtype not in (BF16, F32):
+            pixel_values = pixel_values.to(F32)
+        return pixel_values.to(self.device)
+
+    # The two hooks tools/bench_image_encoder.py overrides to time the per-head assembled attention on the same forward.
+    def _padded_tokens(self, S: int) -> int:
+        """Rows per batch entry of the token buffers: the fused attention takes S as it is."""
+        return S
+
+    def _attention(self, qkv: torch.Tensor, att: torch.Tensor, S: int) -> None:
+        d, H = self.config.hidden_size, self.config.num_attention_heads
+        fused = ops.attention_hd64 if self._head_dim == 64 else ops.attention_hd72
+        fused(qkv[:, :S, :d], qkv[:, :S, d : 2 * d], qkv[:, :S, 2 * d :], att[:, :S], H, self._head_dim ** -0.5)
+
+    def _layers(self, plans: dict, x: torch.Tensor, S: int, act=None) -> None:
+        """The pre-LN blocks on the fp32 residual stream x [B,Sp,d] (rows >= S of an entry are padding), in place: LN1 -> q|k|v GEMM
+        -> attention -> out-proj + residual -> LN2 -> fc1 -> activation -> fc2 + residual. ``act``: a pass over the fc1 output in
+        place, or None for gelu_tanh in fc1's own epilogue."""
+        B, Sp, d = x.shape
+        dev, eps = x.device, float(self.config.layer_norm_eps)
+        x2, x3 = x.view(B * Sp, d), x.view(1, B * Sp, d)
+        xn = torch.empty(B, Sp, d, device=dev, dtype=BF16)
+        xn2, xn3 = xn.view(B * Sp, d), xn.view(1, B * Sp, d)
+        qkv = torch.empty(B, Sp, 3 * d, device=dev, dtype=BF16)
+        att = torch.zeros(B, Sp, d, device=dev, dtype=BF16) if Sp != S else torch.empty(B, S, d, device=dev, dtype=BF16)
+        qkv2, att2 = qkv.view(B * Sp, 3 * d), att.view(B * Sp, d)
+        hid = torch.empty(B * Sp, plans["Fp"], device=dev, dtype=BF16)
+        for wqkv, bqkv, wo, bo, w1, b1, w2, b2, ln1, ln2 in plans["layers"]:
+            ops.layernorm_modulate(x3, xn3, ln1[1], ln1[0], eps=eps)
+            ops.linear(xn2, wqkv, qkv2, bias=bqkv)
+            self._attention(qkv, att, S)
+            ops.linear(att2, wo, x2, bias=bo, res=x2)
+            ops.layernorm_modulate(x3, xn3, ln2[1], ln2[0], eps=eps)
+            if act is None:
+                ops.linear(xn2, w1, hid, bias=b1, gelu_from=0)
+            else:
+                ops.linear(xn2, w1, hid, bias=b1)
+                act(hid)
+            ops.linear(hid, w2, x2, bias=b2, res=x2)
+
+
+def _encoder_layers(n: int, d: int, F_: int, kw: dict) -> nn.Module:
+    """``encoder.layers.*`` of both transformers classes: self_attn.{q,k,v,out}_proj, layer_norm1/2, mlp.fc1/fc2."""
+    enc = _H()
+    enc.layers = nn.ModuleList()
+    for _ in range(n):
+        l = _H()
+        sa = _H()
+        sa.q_proj, sa.k_proj, sa.v_proj, sa.out_proj = (_WB(d, d, **kw) for _ in range(4))
+        l.self_attn = sa
+        l.layer_norm1, l.layer_norm2 = _WB(d, **kw), _WB(d, **kw)
+        mlp = _H()
+        mlp.fc1, mlp.fc2 = _WB(F_, d, **kw), _WB(d, F_, **kw)
+        l.mlp = mlp
+        enc.layers.append(l)
+    return enc
+
+
+# ========================================================================================================================= CLIP
+class CLIPVisionModelOutput(tuple):
+    """(image_embeds, last_hidden_state) with attribute access, transformers' field order."""
+
+    def __new__(cls, image_embeds, last_hidden_state):
+        obj = super().__new__(cls, (image_embeds, last_hidden_state))
+        obj.image_embeds, obj.last_hidden_state = image_embeds, last_hidden_state
+        return obj
+
+
+class CLIPVisionModelWithProjection(_VisionTower):
+    _anchor = "visual_projection.weight"
+    _unit_scale = ("class_embedding", "position_embedding")
+    _head_dim = 64
+
+    def __init__(self, hidden_size: int = 1024, intermediate_size: int = 4096, projection_dim: int = 768, num_hidden_layers: int = 24,
+                 num_attention_heads: int = 16, num_channels: int = 3, image_size: int = 224, patch_size: int = 14,
+                 hidden_act: str = "quick_gelu", layer_norm_eps: float = 1e-5, device=None, dtype=None, **unused):
+        super().__init__()
+        if hidden_size % num_attention_heads or hidden_size // num_attention_heads != 64:
+            raise ValueError("CLIPVisionModelWithProjection (HIP): head dim must be 64 (ViT-L/14: 1024 / 16; ViT-H's 80 is not built)")
+        if hidden_act != "quick_gelu":
+            raise ValueError("CLIPVisionModelWithProjection (HIP): only quick_gelu (openai/clip-vit-large-patch14) is implemented")
+        if image_size % patch_size:
+            raise ValueError(f"CLIPVisionModelWithProjection (HIP): image_size {image_size} is not a multiple of patch_size {patch_size}")
+        if num_channels != 3 or projection_dim % 4 or intermediate_size % 64:
+            raise ValueError("CLIPVisionModelWithProjection (HIP): 3 channels, projection_dim % 4 == 0 and intermediate_size % 64 == 0")
+        self.config = Config(hidden_size=hidden_size, intermediate_size=intermediate_size, projection_dim=projection_dim,
+                             num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads, num_channels=num_channels,
+                             image_size=image_size, patch_size=patch_size, hidden_act=hidden_act, layer_norm_eps=layer_norm_eps)
+        kw = dict(device=device, dtype=dtype)
+        vm = _H()
+        emb = _H()
+        emb.class_embedding = nn.Parameter(torch.empty(hidden_size, **kw), requires_grad=False)
+        emb.patch_embedding = _W(hidden_size, num_channels, patch_size, patch_size, **kw)
+        emb.position_embedding = _W((image_size // patch_size) ** 2 + 1, hidden_size, **kw)
+        vm.embeddings = emb
+        vm.pre_layrnorm = _WB(hidden_size, **kw)
+        vm.encoder = _encoder_layers(num_hidden_layers, hidden_size, intermediate_size, kw)
+        vm.post_layernorm = _WB(hidden_size, **kw)
+        self.vision_model = vm
+        self.visual_projection = _W(projection_dim, hidden_size, **kw)
+        self._plans = None
+
+    def load_state_dict(self, sd, strict: bool = True, **kw):
+        # accept the encoder's keys with or without the `vision_model.` prefix (CLIPVisionModel's own layout), as CLIPTextModel does
+        if not any(k.startswith("vision_model.") for k in sd):
+            sd = {k if k.startswith("visual_projection.") else "vision_model." + k: v for k, v in sd.items()}
+        sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
+        self._plans = None
+        return super().load_state_dict(sd, strict=strict, **kw)
+
+    def _build_plans(self):
+        vm = self.vision_model
+        pos = vm.embeddings.position_embedding.weight.data.to(F32)
+        cls_row = (vm.embeddings.class_embedding.data.to(F32) + pos[0]).contiguous()   # the class row is a constant of the weights
+        return dict(self._tower_plans(vm.embeddings, vm.encoder.layers), pos_patches=pos[1:].contiguous(), cls_row=cls_row,
+                    pre=_affine(vm.pre_layrnorm), post=_affine(vm.post_layernorm))
+
+    @torch.no_grad()
+    def forward(self, pixel_values: torch.Tensor, output_attentions=None, output_hidden_states=None, interpolate_pos_encoding: bool = False,
+                return_dict: bool = True, **unused):
+        if output_attentions or output_hidden_states or interpolate_pos_encoding:
+            raise NotImplementedError("CLIPVisionModelWithProjection (HIP): only image_embeds and last_hidden_state are produced, at the "
+                                      "configured image size")
+        plans = self._ensure_plans()
+        pixel_values = self._pixels(pixel_values)
+        c, dev, lib = self.config, self.device, native.load()
+        B, d, p = pixel_values.shape[0], c.hidden_size, c.patch_size
+        G = c.image_size // p
+        S = G * G + 1
+        Sp = self._padded_tokens(S)
+        eps = float(c.layer_norm_eps)
+        # 1-2. patches -> fp32 rows 1.. of every batch entry, position embeddings added by the GEMM's residual slot; row 0 is constant
+        patches = ops.patchify_nchw(pixel_values, p, plans["Kp"])
+        e = torch.zeros(B, Sp, d, device=dev, dtype=F32) if Sp != S else torch.empty(B, S, d, device=dev, dtype=F32)
+        e[:, 0] = plans["cls_row"]
+        ops.linear(patches, plans["w_patch"], e[:, 1:S], res=plans["pos_patches"].unsqueeze(0).expand(B, -1, -1))
+        # 3. pre_layrnorm; its bf16 output starts the fp32 residual stream
+        xn = torch.empty(B, Sp, d, device=dev, dtype=BF16)
+        ops.layernorm_modulate(e.view(1, B * Sp, d), xn.view(1, B * Sp, d), plans["pre"][1], plans["pre"][0], eps=eps)
+        x = ops.to_f32(xn)
+        # 4. the layers, quick_gelu as its own pass over the fc1 output
+        self._layers(plans, x, S, act=lambda hid: native.check("rt_quick_gelu", lib.rt_quick_gelu(hid.data_ptr(), hid.numel(), _stream())))
+        last = ops.to_bf16(x)[:, :S]
+        # 5-6. post_layernorm on the class token, visual_projection
+        pooled = torch.empty(B, 1, d, device=dev, dtype=BF16)
+        ops.layernorm_modulate(x[:, 0:1], pooled, plans["post"][1].expand(B, -1), plans["post"][0].expand(B, -1), eps=eps)
+        embeds = torch.empty(B, c.projection_dim, device=dev, dtype=BF16)
+        ops.linear(pooled.view(B, d), self.visual_projection.weight.data, embeds)
+        return CLIPVisionModelOutput(embeds, last) if return_dict else (embeds, last)
+
+    __call__ = forward
+
+
+# ======================================================================================================================= SigLIP
 class SiglipVisionModelOutput(tuple):
     """(last_hidden_state, pooler_output) with attribute access, transformers' field order."""
 
@@ -324,7 +372,7 @@ class _MHA(nn.Module):
         self.out_proj = _WB(d, d, device=device, dtype=dtype)
 
 
-class SiglipVisionModel(nn.Module, WeightsIO):
+class SiglipVisionModel(_VisionTower):
     """google/siglip-so400m-patch14-384's vision tower with its attention-pooling head: the class name, constructor config keys,
     module names and state-dict keys of `transformers`' class (5.x layout: ``embeddings.*``, ``encoder.layers.*``,
     ``post_layernorm.*``, ``head.*``; a ``vision_model.`` prefix, as in the published checkpoint, is accepted). Arithmetic: patch
@@ -333,8 +381,9 @@ class SiglipVisionModel(nn.Module, WeightsIO):
     MHA(probe, h, h), x + mlp(layernorm(x)), row 0. Heads of 72: one rt_attention_hd72 launch per layer on the fused q|k|v buffer
     and one more for the head, whose query probe·Wqᵀ + bq is a constant of the weights (computed once with the plans)."""
 
-    config_name = "config.json"
-    weights_name = "model.safetensors"
+    _anchor = "head.probe"
+    _unit_scale = ("probe", "position_embedding")
+    _head_dim = 72
 
     def __init__(self, hidden_size: int = 1152, intermediate_size: int = 4304, num_hidden_layers: int = 27, num_attention_heads: int = 16,
                  num_channels: int = 3, image_size: int = 384, patch_size: int = 14, hidden_act: str = "gelu_pytorch_tanh",
@@ -355,49 +404,22 @@ class SiglipVisionModel(nn.Module, WeightsIO):
                              num_hidden_layers=num_hidden_layers, num_attention_heads=num_attention_heads, num_channels=num_channels,
                              image_size=image_size, patch_size=patch_size, hidden_act=hidden_act, layer_norm_eps=layer_norm_eps)
         kw = dict(device=device, dtype=dtype)
-
-        def mlp():
-            m = _H()
-            m.fc1, m.fc2 = _WB(intermediate_size, hidden_size, **kw), _WB(hidden_size, intermediate_size, **kw)
-            return m
-
         emb = _H()
         emb.patch_embedding = _H()                                               # Conv2d(3, d, kernel p, stride p) WITH bias
         emb.patch_embedding.weight = nn.Parameter(torch.empty(hidden_size, num_channels, patch_size, patch_size, **kw), requires_grad=False)
         emb.patch_embedding.bias = nn.Parameter(torch.empty(hidden_size, **kw), requires_grad=False)
         emb.position_embedding = _W((image_size // patch_size) ** 2, hidden_size, **kw)
         self.embeddings = emb
-        enc = _H()
-        enc.layers = nn.ModuleList()
-        for _ in range(num_hidden_layers):
-            l = _H()
-            sa = _H()
-            sa.q_proj, sa.k_proj, sa.v_proj, sa.out_proj = (_WB(hidden_size, hidden_size, **kw) for _ in range(4))
-            l.self_attn = sa
-            l.layer_norm1, l.layer_norm2 = _WB(hidden_size, **kw), _WB(hidden_size, **kw)
-            l.mlp = mlp()
-            enc.layers.append(l)
-        self.encoder = enc
+        self.encoder = _encoder_layers(num_hidden_layers, hidden_size, intermediate_size, kw)
         self.post_layernorm = _WB(hidden_size, **kw)
         head = _H()
         head.probe = nn.Parameter(torch.empty(1, 1, hidden_size, **kw), requires_grad=False)
         head.attention = _MHA(hidden_size, **kw)
         head.layernorm = _WB(hidden_size, **kw)
-        head.mlp = mlp()
+        head.mlp = _H()
+        head.mlp.fc1, head.mlp.fc2 = _WB(intermediate_size, hidden_size, **kw), _WB(hidden_size, intermediate_size, **kw)
         self.head = head
         self._plans = None
-
-    @property
-    def dtype(self):
-        return self.head.probe.dtype
-
-    @property
-    def device(self):
-        return self.head.probe.device
-
-    def _apply(self, fn, *a, **k):
-        self._plans = None
-        return super()._apply(fn, *a, **k)
 
     def load_state_dict(self, sd, strict: bool = True, **kw):
         # a full SiglipModel checkpoint: the text tower and the two logit scalars are not ours; then the published prefix
@@ -407,63 +429,16 @@ class SiglipVisionModel(nn.Module, WeightsIO):
         self._plans = None
         return super().load_state_dict(sd, strict=strict, **kw)
 
-    @classmethod
-    def from_pretrained(cls, path: str, torch_dtype=None, subfolder: Optional[str] = None, device=None, **unused):
-        d = cls._resolve_dir(path, subfolder)
-        with open(os.path.join(d, cls.config_name)) as f:
-            cfg = json.load(f)
-        cfg = {k: v for k, v in cfg.get("vision_config", cfg).items() if k not in ("dtype", "device")}    # transformers 5.x records a dtype
-        m = cls(**cfg, device=device or "cpu", dtype=torch_dtype or BF16)
-        m.load_state_dict({k: v.to(torch_dtype or BF16) for k, v in cls._load_safetensors_dir(d).items()}, strict=True)
-        return m
-
-    def random_init_(self, seed: int = 0):
-        """Random weights at an exercised scale, for tools and tests that run without a checkpoint: matrices at 1/sqrt(fan-in),
-        the probe and the positions at unit scale, LayerNorms at identity, biases zero."""
-        g = torch.Generator().manual_seed(seed)
-        for n, p in self.named_parameters():
-            if "norm" in n and n.endswith("weight"):
-                p.data.fill_(1.0)
-            elif n.endswith("bias"):
-                p.data.zero_()
-            else:
-                std = 1.0 if "probe" in n or "position_embedding" in n else p[0].numel() ** -0.5
-                p.data.copy_(torch.randn(p.shape, generator=g) * std)
-        self._plans = None
-        return self
-
-    def _ensure_plans(self):
-        if self._plans is not None:
-            return self._plans
-        if self.dtype != BF16 or not self.head.probe.is_cuda:
-            raise RuntimeError("SiglipVisionModel (HIP): bf16 on the GPU only; there is no CPU fallback")
-
-        def affine(ln):           # LayerNorm(x)·w + b == LN(x)·(1 + (w - 1)) + b: the adaLN kernel with constant vectors
-            return (ln.weight.data.to(F32) - 1.0).reshape(1, -1).contiguous(), ln.bias.data.to(F32).reshape(1, -1).contiguous()
-
-        c, emb, head = self.config, self.embeddings, self.head
-        d, k = c.hidden_size, 3 * c.patch_size ** 2
-        Kp = (k + 63) // 64 * 64                                                  # the GEMM's K % 64 rule: 588 -> 640 for p = 14
-        w_patch = torch.zeros(d, Kp, device=self.device, dtype=BF16)
-        w_patch[:, :k] = emb.patch_embedding.weight.data.reshape(d, k)
-        layers = []
-        for l in self.encoder.layers:
-            sa = l.self_attn
-            wqkv = torch.cat([sa.q_proj.weight.data, sa.k_proj.weight.data, sa.v_proj.weight.data], dim=0).contiguous()
-            bqkv = torch.cat([sa.q_proj.bias.data, sa.k_proj.bias.data, sa.v_proj.bias.data], dim=0).contiguous()
-            w1, b1, w2 = pad_mlp_to_64(l.mlp.fc1.weight.data, l.mlp.fc1.bias.data, l.mlp.fc2.weight.data)
-            layers.append((wqkv, bqkv, sa.out_proj.weight.data, sa.out_proj.bias.data, w1, b1, w2, l.mlp.fc2.bias.data,
-                           affine(l.layer_norm1), affine(l.layer_norm2)))
+    def _build_plans(self):
+        emb, head, d = self.embeddings, self.head, self.config.hidden_size
         att = head.attention
         wq, bq = att.in_proj_weight.data[:d].to(F32), att.in_proj_bias.data[:d].to(F32)
         q_probe = (head.probe.data.to(F32).reshape(1, d) @ wq.t() + bq).to(BF16).reshape(1, 1, d).contiguous()   # a constant of the weights
         hw1, hb1, hw2 = pad_mlp_to_64(head.mlp.fc1.weight.data, head.mlp.fc1.bias.data, head.mlp.fc2.weight.data)
-        self._plans = dict(w_patch=w_patch, b_patch=emb.patch_embedding.bias.data.contiguous(), Kp=Kp, Fp=hw1.shape[0],
-                           pos=emb.position_embedding.weight.data.to(F32).contiguous(), post=affine(self.post_layernorm), layers=layers,
-                           q_probe=q_probe, wkv=att.in_proj_weight.data[d:].contiguous(), bkv=att.in_proj_bias.data[d:].contiguous(),
-                           wo=att.out_proj.weight.data, bo=att.out_proj.bias.data, head_ln=affine(head.layernorm),
-                           head_mlp=(hw1, hb1, hw2, head.mlp.fc2.bias.data))
-        return self._plans
+        return dict(self._tower_plans(emb, self.encoder.layers), b_patch=emb.patch_embedding.bias.data.contiguous(),
+                    pos=emb.position_embedding.weight.data.to(F32).contiguous(), post=_affine(self.post_layernorm), q_probe=q_probe,
+                    wkv=att.in_proj_weight.data[d:].contiguous(), bkv=att.in_proj_bias.data[d:].contiguous(), wo=att.out_proj.weight.data,
+                    bo=att.out_proj.bias.data, head_ln=_affine(head.layernorm), head_mlp=(hw1, hb1, hw2, head.mlp.fc2.bias.data))
 
     @torch.no_grad()
     def forward(self, pixel_values: torch.Tensor, output_attentions=None, output_hidden_states=None, interpolate_pos_encoding: bool = False,
@@ -472,39 +447,22 @@ class SiglipVisionModel(nn.Module, WeightsIO):
             raise NotImplementedError("SiglipVisionModel (HIP): only last_hidden_state and pooler_output are produced, at the configured "
                                       "image size")
         plans = self._ensure_plans()
+        pixel_values = self._pixels(pixel_values)
         c, dev = self.config, self.device
-        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, c.image_size, c.image_size):
-            raise ValueError(f"pixel_values must be [B,3,{c.image_size},{c.image_size}], got {tuple(pixel_values.shape)}")
-        if pixel_values.dtype not in (BF16, F32):
-            pixel_values = pixel_values.to(F32)
-        pixel_values = pixel_values.to(dev)
         B, d, H, p = pixel_values.shape[0], c.hidden_size, c.num_attention_heads, c.patch_size
         G = c.image_size // p
-        S, Fp = G * G, plans["Fp"]
+        S = G * G
         eps, scale = float(c.layer_norm_eps), 72 ** -0.5
         # 1. patches of the top-left G·p square (384 -> 378 for p = 14: the convolution drops the rest; patchify_nchw copies the crop
         #    once) -> the fp32 residual stream: bias in the GEMM's bias slot, the position table in its residual slot
         patches = ops.patchify_nchw(pixel_values[:, :, : G * p, : G * p], p, plans["Kp"])
         x = torch.empty(B, S, d, device=dev, dtype=F32)
         ops.linear(patches, plans["w_patch"], x, bias=plans["b_patch"], res=plans["pos"].unsqueeze(0).expand(B, -1, -1))
-        x2, x3 = x.view(B * S, d), x.view(1, B * S, d)
-        xn = torch.empty(B, S, d, device=dev, dtype=BF16)
-        xn2, xn3 = xn.view(B * S, d), xn.view(1, B * S, d)
-        qkv = torch.empty(B, S, 3 * d, device=dev, dtype=BF16)
-        att = torch.empty(B, S, d, device=dev, dtype=BF16)
-        hid = torch.empty(B * S, Fp, device=dev, dtype=BF16)
-        # 2. the layers
-        for wqkv, bqkv, wo, bo, w1, b1, w2, b2, ln1, ln2 in plans["layers"]:
-            ops.layernorm_modulate(x3, xn3, ln1[1], ln1[0], eps=eps)
-            ops.linear(xn2, wqkv, qkv.view(B * S, 3 * d), bias=bqkv)
-            ops.attention_hd72(qkv[..., :d], qkv[..., d : 2 * d], qkv[..., 2 * d :], att, H, scale)
-            ops.linear(att.view(B * S, d), wo, x2, bias=bo, res=x2)
-            ops.layernorm_modulate(x3, xn3, ln2[1], ln2[0], eps=eps)
-            ops.linear(xn2, w1, hid, bias=b1, gelu_from=0)
-            ops.linear(hid, w2, x2, bias=b2, res=x2)
+        # 2. the layers, gelu_tanh in fc1's epilogue
+        self._layers(plans, x, S)
         # 3. post_layernorm on all tokens
         last = torch.empty(B, S, d, device=dev, dtype=BF16)
-        ops.layernorm_modulate(x3, last.view(1, B * S, d), plans["post"][1], plans["post"][0], eps=eps)
+        ops.layernorm_modulate(x.view(1, B * S, d), last.view(1, B * S, d), plans["post"][1], plans["post"][0], eps=eps)
         # 4. the attention-pooling head: k|v of the normed tokens in one GEMM, one probe row per batch entry, out_proj, MLP
         kv = torch.empty(B, S, 2 * d, device=dev, dtype=BF16)
         ops.linear(last.view(B * S, d), plans["wkv"], kv.view(B * S, 2 * d), bias=plans["bkv"])

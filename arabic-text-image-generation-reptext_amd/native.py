@@ -149,12 +149,12 @@ SIGNATURES["rt_ip_attention_gated"] = [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i6
 SIGNATURES["rt_gelu_erf_bf16"] = [_vp, _vp, _i64, _vp]
 SIGNATURES["rt_add_bf16_2d"] = [_vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _vp]
 
-# CLIP vision encoder (csrc/attention_hd64.hip, csrc/image_encoder.hip)
+# CLIP vision encoder (csrc/attention_small_head.hip, csrc/image_encoder.hip)
 RT_ATTENTION_HD64_MAX_S = 4096
 SIGNATURES["rt_attention_hd64"] = [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _f32, _vp]
 SIGNATURES["rt_patchify_nchw"] = [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]
 
-# SigLIP vision encoder (ABI 15; csrc/attention_hd72.hip): heads of 72, separate query and key counts
+# SigLIP vision encoder (ABI 15; csrc/attention_small_head.hip): heads of 72, separate query and key counts
 RT_ATTENTION_HD72_MAX_S = 1024
 SIGNATURES["rt_attention_hd72"] = [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp]
 

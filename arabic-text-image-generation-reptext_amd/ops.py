@@ -633,45 +633,50 @@ def rmsnorm_heads_(x: torch.Tensor, out: torch.Tensor, ones: torch.Tensor, eps: 
     return out
 
 
+def _attention_small_head(hd: int, entry: str, max_s: int, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int,
+                          scale: Optional[float]) -> torch.Tensor:
+    """The body of attention_hd64 / attention_hd72 (csrc/attention_small_head.hip): head dim, entry point and row bound. 64 keeps its
+    stricter rule — q, k and v are views of one buffer sharing shape and strides — which its entry point's shorter argument list assumes."""
+    d = H * hd
+    for tn, t in (("q", q), ("k", k), ("v", v), ("out", out)):
+        if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] != d:
+            raise ValueError(f"{tn}: need [B,S,{d}] with unit inner stride, got {tuple(t.shape)} / {t.stride()}")
+    B, Sk, _ = k.shape
+    Sq = q.shape[1]
+    sc = float(scale if scale is not None else (64 ** -0.5 if hd == 64 else 72 ** -0.5))      # literals: folded when compiled
+    if hd == 64:
+        if not (q.stride() == k.stride() == v.stride()) or k.shape != q.shape or v.shape != q.shape or out.shape != q.shape:
+            raise ValueError("q,k,v must share shape and strides; out must have their shape")
+        if not 1 <= Sq <= max_s:
+            raise ValueError(f"{entry[3:]}: 1..{max_s} rows, got {Sq}")
+        code = native.load().rt_attention_hd64(_dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), q.stride(1), q.stride(0),
+                                               _dev(out, "out", BF16), out.stride(1), out.stride(0), B, Sq, H, sc, _stream())
+    else:
+        if k.stride() != v.stride() or v.shape != k.shape:
+            raise ValueError("k,v must share shape and strides")
+        if q.shape[0] not in (1, B) or out.shape != (B, Sq, d):
+            raise ValueError(f"q must be [{B} or 1, Sq, {d}] and out [{B}, Sq, {d}], got {tuple(q.shape)} and {tuple(out.shape)}")
+        if not (1 <= Sq <= max_s and 1 <= Sk <= max_s):
+            raise ValueError(f"{entry[3:]}: 1..{max_s} rows, got {Sq} queries and {Sk} keys")
+        code = native.load().rt_attention_hd72(_dev(q, "q", BF16), q.stride(1), q.stride(0) if q.shape[0] == B and B > 1 else 0, _dev(k, "k", BF16),
+                                               _dev(v, "v", BF16), k.stride(1), k.stride(0), _dev(out, "out", BF16), out.stride(1), out.stride(0), B,
+                                               Sq, Sk, H, sc, _stream())
+    native.check(entry, code)
+    return out
+
+
 def attention_hd64(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, scale: Optional[float] = None) -> torch.Tensor:
     """out[b, s, h·64:(h+1)·64] = softmax(scale · q_h k_hᵀ) v_h (rt_attention_hd64): non-causal self-attention with heads of 64, one
     launch. q, k, v [B,S,H·64] bf16 views of one buffer sharing strides (the fused q|k|v projection); out [B,S,H·64] bf16 view with its
     own strides; 1 <= S <= native.RT_ATTENTION_HD64_MAX_S."""
-    d = H * 64
-    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
-        if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] != d:
-            raise ValueError(f"{name}: need [B,S,{d}] with unit inner stride, got {tuple(t.shape)} / {t.stride()}")
-    B, S, _ = q.shape
-    if not (q.stride() == k.stride() == v.stride()) or k.shape != q.shape or v.shape != q.shape or out.shape != q.shape:
-        raise ValueError("q,k,v must share shape and strides; out must have their shape")
-    if not 1 <= S <= native.RT_ATTENTION_HD64_MAX_S:
-        raise ValueError(f"attention_hd64: 1..{native.RT_ATTENTION_HD64_MAX_S} rows, got {S}")
-    native.check("rt_attention_hd64", native.load().rt_attention_hd64(
-        _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), q.stride(1), q.stride(0), _dev(out, "out", BF16), out.stride(1),
-        out.stride(0), B, S, H, float(scale if scale is not None else 64 ** -0.5), _stream()))
-    return out
+    return _attention_small_head(64, "rt_attention_hd64", native.RT_ATTENTION_HD64_MAX_S, q, k, v, out, H, scale)
 
 
 def attention_hd72(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, scale: Optional[float] = None) -> torch.Tensor:
     """out[b, s, h·72:(h+1)·72] = softmax(scale · q_h k_hᵀ) v_h (rt_attention_hd72): non-causal attention with heads of 72, one launch.
     q [B or 1, Sq, H·72] bf16 (a leading 1 is shared by the batch: the pooling head's probe); k, v [B, Sk, H·72] bf16 views sharing
     shape and strides (the fused projection); out [B, Sq, H·72] bf16 view with its own strides; 1 <= Sq, Sk <= native.RT_ATTENTION_HD72_MAX_S."""
-    d = H * 72
-    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
-        if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] != d:
-            raise ValueError(f"{name}: need [B,S,{d}] with unit inner stride, got {tuple(t.shape)} / {t.stride()}")
-    B, Sk, _ = k.shape
-    Sq = q.shape[1]
-    if k.stride() != v.stride() or v.shape != k.shape:
-        raise ValueError("k,v must share shape and strides")
-    if q.shape[0] not in (1, B) or out.shape != (B, Sq, d):
-        raise ValueError(f"q must be [{B} or 1, Sq, {d}] and out [{B}, Sq, {d}], got {tuple(q.shape)} and {tuple(out.shape)}")
-    if not (1 <= Sq <= native.RT_ATTENTION_HD72_MAX_S and 1 <= Sk <= native.RT_ATTENTION_HD72_MAX_S):
-        raise ValueError(f"attention_hd72: 1..{native.RT_ATTENTION_HD72_MAX_S} rows, got {Sq} queries and {Sk} keys")
-    native.check("rt_attention_hd72", native.load().rt_attention_hd72(
-        _dev(q, "q", BF16), q.stride(1), q.stride(0) if q.shape[0] == B and B > 1 else 0, _dev(k, "k", BF16), _dev(v, "v", BF16), k.stride(1),
-        k.stride(0), _dev(out, "out", BF16), out.stride(1), out.stride(0), B, Sq, Sk, H, float(scale if scale is not None else 72 ** -0.5), _stream()))
-    return out
+    return _attention_small_head(72, "rt_attention_hd72", native.RT_ATTENTION_HD72_MAX_S, q, k, v, out, H, scale)
 
 
 def patchify_nchw(x: torch.Tensor, patch: int, Kp: Optional[int] = None) -> torch.Tensor:

@@ -358,7 +358,7 @@ int rt_quick_gelu(void* x, int64_t n, void* stream);
  * CLIP vision encoder (ABI 13; image_encoder.py: `CLIPVisionModelWithProjection`, the image encoder behind the pipeline's
  * ip_adapter_image=). Once per image prompt, outside the loop. Matrix work is rt_gemm_bf16, norms rt_layernorm_modulate.
  * ---------------------------------------------------------------------------------------- */
-/* Self-attention with heads of 64, non-causal, no bias (csrc/attention_hd64.hip):
+/* Self-attention with heads of 64, non-causal, no bias (csrc/attention_small_head.hip):
  *   o[b][s][h*64 .. h*64+63] = softmax(scale * q_h k_h^T) v_h        for every batch entry b, head h and row s < S
  * q / k / v: bf16 views of one fused [B][S][ld] buffer (common row stride ld and batch stride stride_b, in elements; ld = 3*H*64 for
  * the fused q|k|v projection), head h at column h*64; o: bf16 [B][S][ldo]. Both products on v_mfma_f32_16x16x32_bf16; scores, row
@@ -386,7 +386,7 @@ int rt_patchify_nchw(const void* x, int32_t x_f32, void* out, int32_t B, int32_t
  * SigLIP vision encoder (ABI 15; image_encoder.py: `SiglipVisionModel`, the image encoder of the InstantX IP-Adapter). Once per
  * image prompt, outside the loop. Matrix work is rt_gemm_bf16, norms rt_layernorm_modulate, patches rt_patchify_nchw.
  * ---------------------------------------------------------------------------------------- */
-/* Attention with heads of 72, non-causal, no bias, separate query and key counts (csrc/attention_hd72.hip):
+/* Attention with heads of 72, non-causal, no bias, separate query and key counts (csrc/attention_small_head.hip):
  *   o[b][s][h*72 .. h*72+71] = softmax(scale * q_h k_h^T) v_h        for every batch entry b, head h and query row s < Sq, over Sk keys
  * q: bf16 [B][Sq][ldq] with batch stride stride_qb (elements); stride_qb == 0 is allowed: one set of query rows shared by the
  * batch (the probe of the attention-pooling head). k / v: bf16 views of one [B][Sk][ldkv] buffer (common row stride ldkv and batch

@@ -1,7 +1,6 @@
 """GPU tests of the SigLIP vision encoder path: rt_attention_hd72 against fp64 with the error of a CPU emulation of its roundings as
 the yardstick, reptext_amd.image_encoder.SiglipVisionModel against the REAL transformers class with shared random weights, and
 the pipeline's ``ip_adapter_image=`` with the InstantX adapter against ``ip_adapter_image_embeds=``."""
-import functools
 import os
 import sys
 
@@ -13,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import instantx_reference as ixr  # noqa: E402
+import small_head_attention as sha  # noqa: E402
 from instantx_reference import SMALL_T, rel_l2  # noqa: E402
 
 # ------------------------------------------------------------------------------------------------------------------ the kernel
@@ -23,81 +23,23 @@ from instantx_reference import SMALL_T, rel_l2  # noqa: E402
 SELF_CASES = [(1, 1, 1, 1), (1, 17, 17, 2), (2, 64, 64, 1), (1, 65, 65, 3), (2, 729, 729, 2), (1, 320, 320, 1), (1, 513, 513, 16), (2, 513, 513, 16)]
 RECT_CASES = [(1, 1, 64, 2), (1, 1, 65, 2), (3, 5, 17, 2)]
 KERNEL_CASES = [c + (False,) for c in SELF_CASES + RECT_CASES] + [(2, 1, 729, 16, True)]
-SCALE = 72 ** -0.5
-PAD_COLS, PAD_ROWS = 64, 3
-
-
-@functools.lru_cache(maxsize=None)
-def _case(B, Sq, Sk, H, shared, q_gain):
-    """(fused q|k|v buffer bf16 [B, Sk + 3, 3·72H + 64] on the CPU whose extra rows and columns are NaN; fp64 softmax(scale·qkᵀ)v
-    from its bf16 values; the same through a CPU emulation of the kernel's roundings; the largest scale·score). The queries are
-    rows < Sq of the q columns, of batch entry 0 alone when they are shared."""
-    g = torch.Generator().manual_seed(100000 * Sq + 100 * Sk + 10 * H + B)
-    d = H * 72
-    vals = torch.randn(B, Sk, 3 * d, generator=g)
-    vals[..., :d] *= q_gain
-    buf = torch.full((B, Sk + PAD_ROWS, 3 * d + PAD_COLS), float("nan"), dtype=torch.bfloat16)
-    buf[:, :Sk, :3 * d] = vals.to(torch.bfloat16)
-    heads = lambda t: t.reshape(t.shape[0], t.shape[1], H, 72).transpose(1, 2)
-    q = heads(buf[:1 if shared else B, :Sq, :d])
-    k, v = heads(buf[:, :Sk, d:2 * d]), heads(buf[:, :Sk, 2 * d:3 * d])
-    s = (q.double() @ k.double().transpose(-1, -2)) * SCALE
-    ref = (torch.softmax(s, dim=-1) @ v.double()).transpose(1, 2).reshape(B, Sq, d)
-    # the kernel's roundings: fp32 scores, exp against the row maximum, the row sum from the unrounded P, P rounded to bf16 before the
-    # second product, o rounded to bf16
-    s32 = q.float() @ k.float().transpose(-1, -2)
-    p = torch.exp((s32 - s32.amax(dim=-1, keepdim=True)) * SCALE)
-    emu = ((p.to(torch.bfloat16).float() @ v.float()) / p.sum(dim=-1, keepdim=True)).to(torch.bfloat16)
-    emu = emu.expand(B, -1, -1, -1).transpose(1, 2).reshape(B, Sq, d)
-    return buf, ref, emu, float(s.amax(dim=-1).max())
-
-
-def _fused(gpu, buf, B, Sq, Sk, H, shared):
-    """rt_attention_hd72 on views of the fused buffer, into a wider and taller buffer of sentinels: twice as the host would launch it
-    and once per forced workgroup size. Checks what must not be written and that every launch gives the same bits."""
-    from reptext_amd import ops
-
-    d = H * 72
-    dev = buf.to(gpu)
-    q = dev[:1 if shared else B, :Sq, :d]
-    ldo, rows = d + 64, Sq + 3
-    sentinel = torch.full((B, rows, ldo), -7.0, dtype=torch.bfloat16)
-    outs = []
-    try:
-        for force in (None, None, "1", "2", "4"):
-            if force is not None:
-                os.environ["RT_HD72_WAVES"] = force
-            o = sentinel.to(gpu)
-            ops.attention_hd72(q, dev[:, :Sk, d:2 * d], dev[:, :Sk, 2 * d:3 * d], o[:, :Sq, :d], H, SCALE)
-            torch.cuda.synchronize()
-            outs.append(o.cpu())
-    finally:
-        os.environ.pop("RT_HD72_WAVES", None)
-    out = outs[0]
-    assert torch.equal(out[:, :, d:], sentinel[:, :, d:]) and torch.equal(out[:, Sq:], sentinel[:, Sq:])    # columns >= 72H, rows >= Sq
-    assert torch.isfinite(out.float()).all()                                     # a read of a guard row or column would be a NaN
-    for other in outs[1:]:
-        assert torch.equal(out, other)                                           # a second launch, and every workgroup size: the same bits
-    assert torch.equal(dev.cpu().view(torch.int16), buf.view(torch.int16))      # the inputs are not modified
-    return out[:, :Sq, :d]
 
 
 @pytest.mark.parametrize("B, Sq, Sk, H, shared", KERNEL_CASES)
 def test_attention_hd72_vs_fp64_and_the_emulated_roundings(gpu, B, Sq, Sk, H, shared):
     """rel-L2 against fp64 from the same bf16 values, bounded by 1.5 x the error of a CPU emulation of the kernel's roundings on the
-    same inputs (the margin rt_attention_hd64 is held to against its comparator). With one key the output is v, bit for bit.
+    same inputs (the margin rt_attention_hd64 is held to; the harness is tests/small_head_attention.py). With one key the output is v, bit for bit.
     Measured on an MI355X, kernel / emulation (B, Sq, Sk, H): (1,1,1,1) 0 / 0; (1,17,17,2) 2.052e-3 / 2.052e-3; (2,64,64,1) 2.123e-3 /
     2.122e-3; (1,65,65,3) 2.103e-3 / 2.100e-3; (2,729,729,2) 2.205e-3 / 2.245e-3; (1,320,320,1) 2.178e-3 / 2.215e-3; (1,513,513,16)
     2.200e-3 / 2.245e-3; (2,513,513,16) 2.180e-3 / 2.226e-3; (1,1,64,2) 1.779e-3 / 1.779e-3; (1,1,65,2) 2.490e-3 / 2.490e-3; (3,5,17,2)
     1.892e-3 / 1.892e-3; the pooling call (2,1,729,16) 2.178e-3 / 2.225e-3. Within one key tile the two agree to the last digit shown;
     over several tiles the kernel's running rescale orders the sums differently from the emulation's single pass."""
-    buf, ref, emu, _ = _case(B, Sq, Sk, H, shared, 1.0)
-    out = _fused(gpu, buf, B, Sq, Sk, H, shared)
+    buf, ref, emu, _ = sha.case(72, B, Sq, Sk, H, shared, 1.0)
+    out = sha.fused(gpu, 72, buf, B, Sq, Sk, H, shared)
     err_k, err_e = rel_l2(out.float(), ref), rel_l2(emu.float(), ref)
     print(f"attention_hd72 B={B} Sq={Sq} Sk={Sk} H={H}: rel-L2 vs fp64 kernel {err_k:.3e}, emulation {err_e:.3e}")
     if Sk == 1:
-        d = H * 72
-        assert torch.equal(out.view(torch.int16), buf[:, :1, 2 * d:3 * d].expand(B, Sq, d).contiguous().view(torch.int16))
+        assert sha.is_v(out, buf, 72, B, Sq, H)
     assert err_k <= 1.5 * err_e, (err_k, err_e)
 
 
@@ -106,9 +48,9 @@ def test_attention_hd72_large_scores(gpu, B, S, H):
     """q scaled so that the largest scale·score exceeds 100: fp32 exp overflows at 88.7 unless the row maximum is subtracted.
     Same bound, finite outputs. Measured, kernel / emulation: (1,65,3) 8.284e-4 / 8.284e-4 at a largest scale·score of 203; (2,257,2)
     9.531e-4 / 9.593e-4 at 227."""
-    buf, ref, emu, smax = _case(B, S, S, H, False, 48.0)
+    buf, ref, emu, smax = sha.case(72, B, S, S, H, False, 48.0)
     assert smax > 100.0, smax
-    err_k, err_e = rel_l2(_fused(gpu, buf, B, S, S, H, False).float(), ref), rel_l2(emu.float(), ref)
+    err_k, err_e = rel_l2(sha.fused(gpu, 72, buf, B, S, S, H, False).float(), ref), rel_l2(emu.float(), ref)
     print(f"attention_hd72 large scores B={B} S={S} H={H} (max scale*score {smax:.0f}): rel-L2 vs fp64 kernel {err_k:.3e}, emulation {err_e:.3e}")
     assert err_k <= 1.5 * err_e, (err_k, err_e)
 

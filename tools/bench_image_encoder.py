@@ -53,28 +53,11 @@ def timed(fn, iters, warm=2):
     return e0.elapsed_time(e1) / iters * 1e-3
 
 
-def kernel_bench(dev, S=257, H=16):
-    d = H * 64
-    res = {"RT_HD64_WAVES": os.environ.get("RT_HD64_WAVES", "")}
-    nbuf = 8
-    for B in (1, 4):
-        qkv = [torch.randn(B, S, 3 * d, device=dev).to(torch.bfloat16) for _ in range(nbuf)]
-        out = [torch.empty(B, S, d, device=dev, dtype=torch.bfloat16) for _ in range(nbuf)]
-        i = [0]
-
-        def one():
-            j = i[0] % nbuf
-            ops.attention_hd64(qkv[j][..., :d], qkv[j][..., d:2 * d], qkv[j][..., 2 * d:], out[j], H)
-            i[0] += 1
-        t = sorted(timed(one, 25 * nbuf, warm=nbuf) for _ in range(3))[1]           # median of three; back-to-back launches
-        res[f"B{B}"] = {"us": round(t * 1e6, 2)}
-        print(f"rt_attention_hd64 B = {B}, S = {S}, H = {H}: {t * 1e6:7.2f} us per launch (back to back)", flush=True)
-    return res
-
-
-def kernel_bench_hd72(dev, S=729, H=16):
-    d = H * 72
-    res = {"RT_HD72_WAVES": os.environ.get("RT_HD72_WAVES", "")}
+def kernel_bench(dev, hd, S, H=16):
+    """rt_attention_hd<hd> alone on a rotating set of buffers, B = 1 and 4: the self-attention call, and for 72 the pooling call too."""
+    d, env = H * hd, f"RT_HD{hd}_WAVES"
+    attention = ops.attention_hd64 if hd == 64 else ops.attention_hd72
+    res = {env: os.environ.get(env, "")}
     nbuf = 8
     for B in (1, 4):
         qkv = [torch.randn(B, S, 3 * d, device=dev).to(torch.bfloat16) for _ in range(nbuf)]
@@ -84,18 +67,18 @@ def kernel_bench_hd72(dev, S=729, H=16):
 
         def self_attention():
             j = i[0] % nbuf
-            ops.attention_hd72(qkv[j][..., :d], qkv[j][..., d:2 * d], qkv[j][..., 2 * d:], out[j], H)
+            attention(qkv[j][..., :d], qkv[j][..., d:2 * d], qkv[j][..., 2 * d:], out[j], H)
             i[0] += 1
 
         def pooling():
             j = i[0] % nbuf
-            ops.attention_hd72(qkv[j][:1, :1, :d], qkv[j][..., d:2 * d], qkv[j][..., 2 * d:], pooled[j], H)
+            attention(qkv[j][:1, :1, :d], qkv[j][..., d:2 * d], qkv[j][..., 2 * d:], pooled[j], H)
             i[0] += 1
         res[f"B{B}"] = {}
-        for name, fn in (("self", self_attention), ("pooling", pooling)):
+        for name, fn in (("self", self_attention), ("pooling", pooling))[:1 if hd == 64 else 2]:
             t = sorted(timed(fn, 25 * nbuf, warm=nbuf) for _ in range(3))[1]         # median of three; back-to-back launches
-            res[f"B{B}"][name + "_us"] = round(t * 1e6, 2)
-            print(f"rt_attention_hd72 B = {B}, Sk = {S}, H = {H}, {name:7s}: {t * 1e6:7.2f} us per launch (back to back)", flush=True)
+            res[f"B{B}"]["us" if hd == 64 else name + "_us"] = round(t * 1e6, 2)
+            print(f"rt_attention_hd{hd} B = {B}, Sk = {S}, H = {H}, {name:7s}: {t * 1e6:7.2f} us per launch (back to back)", flush=True)
     return res
 
 
@@ -104,7 +87,7 @@ def main_siglip(args, dev):
 
     layers = args.layers if args.layers is not None else 27
     result = {"tool": "bench_image_encoder", "encoder_model": "siglip-so400m-patch14-384 shape, random weights",
-              "device": torch.cuda.get_device_name(0), "layers": layers, "kernel": kernel_bench_hd72(dev)}
+              "device": torch.cuda.get_device_name(0), "layers": layers, "kernel": kernel_bench(dev, 72, 729)}
     if args.kernel_only:
         print(json.dumps(result), flush=True)
         return
@@ -135,7 +118,7 @@ def main():
     if args.siglip:
         return main_siglip(args, dev)
     args.layers = 24 if args.layers is None else args.layers
-    result = {"tool": "bench_image_encoder", "device": torch.cuda.get_device_name(0), "layers": args.layers, "kernel": kernel_bench(dev)}
+    result = {"tool": "bench_image_encoder", "device": torch.cuda.get_device_name(0), "layers": args.layers, "kernel": kernel_bench(dev, 64, 257)}
     if args.kernel_only:
         print(json.dumps(result), flush=True)
         return
