@@ -379,7 +379,11 @@ __global__ void rope_table_kernel(const float* __restrict__ ids, float* __restri
   cp[0] = c; cp[1] = c; sp[0] = sn; sp[1] = sn;
 }
 
+// x = bf16(x + ds·v) as the scheduler's reference computes it (oracle/flux_oracle.py euler_step; torch: x.float() + ds * v.float()):
+// the product is rounded to fp32, then the sum, then the result to bf16. Contraction is off in both kernels: a fused multiply-add
+// skips the product's rounding, which moves about one element in two million across a bf16 rounding boundary.
 __global__ void euler_step_kernel(bf16_t* __restrict__ x, const bf16_t* __restrict__ v, float ds, int64_t n8) {
+#pragma clang fp contract(off)
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += (int64_t)gridDim.x * blockDim.x) {
     u32x4 a = reinterpret_cast<u32x4*>(x)[i];
     const u32x4 b = reinterpret_cast<const u32x4*>(v)[i];
@@ -390,6 +394,7 @@ __global__ void euler_step_kernel(bf16_t* __restrict__ x, const bf16_t* __restri
   }
 }
 __global__ void euler_step_tail_kernel(bf16_t* x, const bf16_t* v, float ds, int64_t start, int64_t n) {
+#pragma clang fp contract(off)
   const int64_t i = start + blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) x[i] = f32_to_bf16(bf16_to_f32(x[i]) + ds * bf16_to_f32(v[i]));
 }

@@ -562,6 +562,7 @@ int rt_groupnorm_silu_nhwc(const void* x, void* y, const void* gamma, const void
                            int32_t H, int32_t W, int32_t C, int32_t G, float eps, int32_t silu, void* stream) {
   if (!x || !y || !gamma || !beta || !stats_ws || B < 1 || H < 1 || W < 1 || C < 8 || G < 1) return RT_E_BADARG;
   if (C % 8 || C % G || 256 % (C / 8) || C / 8 > 256) return RT_E_SHAPE;
+  if (2 * G > 1024 || (int64_t)B * H > 65535) return RT_E_SHAPE;   // gn_reduce's workgroup, gn_apply's grid.y: refused before anything is queued
   if (!RT_ALIGNED(x, 16) || !RT_ALIGNED(y, 16) || !RT_ALIGNED(gamma, 16) || !RT_ALIGNED(beta, 16) || !RT_ALIGNED(stats_ws, 8)) return RT_E_ALIGN;
   hipStream_t st = (hipStream_t)stream;
   const int HW = H * W;
@@ -570,9 +571,7 @@ int rt_groupnorm_silu_nhwc(const void* x, void* y, const void* gamma, const void
   float* mr = (float*)stats_ws;                            // [B][G][mean, 1/std] (in the first B*2G doubles of the workspace)
   double* part = (double*)stats_ws + (int64_t)B * 2 * G;   // [B][nblk][2G] workgroup partials
   hipLaunchKernelGGL(gn_stats_kernel, dim3(nblk, B), dim3(256), 0, st, (const bf16_t*)x, part, B, H, W, C, G, ppb);
-  if (2 * G > 1024) return RT_E_SHAPE;
   hipLaunchKernelGGL(gn_reduce_kernel, dim3(B), dim3(1024), 0, st, (const double*)part, nblk, 2 * G, mr, (double)HW * (C / G), eps);
-  if ((int64_t)B * H > 65535) return RT_E_SHAPE;
   hipLaunchKernelGGL(gn_apply_kernel, dim3((W * (C / 8) + 255) / 256, B * H), dim3(256), 0, st, (const bf16_t*)x, (bf16_t*)y,
                      (const float*)mr, (const bf16_t*)gamma, (const bf16_t*)beta, B, H, W, C, G, silu);
   return rt_hip_status();

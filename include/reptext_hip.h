@@ -406,7 +406,8 @@ int rt_attention_hd72(const void* q, int64_t ldq, int64_t stride_qb,
                       void* o, int64_t ldo, int64_t stride_ob,
                       int32_t B, int32_t Sq, int32_t Sk, int32_t H, float scale, void* stream);
 
-/* FlowMatchEulerDiscreteScheduler.step (PIPE:1109; A.6): x = bf16(f32(x) + dsigma·f32(v)), in place. */
+/* FlowMatchEulerDiscreteScheduler.step (PIPE:1109; A.6): x = bf16(f32(x) + dsigma·f32(v)), in place; the product and the sum are each
+ * rounded to fp32 (no fused multiply-add), as torch computes it. */
 int rt_euler_step(void* x, const void* v, float dsigma, int64_t n, void* stream);
 
 /* Same step on an fp32 master copy of the latents (x32 += dsigma·v, v bf16), optionally writing the bf16 copy the next model
@@ -440,7 +441,8 @@ int rt_masked_accumulate(const void* x, void* y, const float* rowscale, float al
  * ---------------------------------------------------------------------------------------- */
 /* GroupNorm(G groups, eps, affine gamma/beta bf16 [C]) + optional SiLU over the interior of x -> interior of y.
  * stats_ws: device scratch of rt_groupnorm_ws_bytes(B,H,W,G) bytes (8-byte aligned; need not be zeroed). All sums run in a
- * fixed order (no atomics): results are bitwise reproducible. C % 8 == 0, C % G == 0, 256 % (C/8) == 0. */
+ * fixed order (no atomics): results are bitwise reproducible. C % 8 == 0, C % G == 0, 256 % (C/8) == 0, G <= 512, B·H <= 65535;
+ * anything else is RT_E_SHAPE with nothing queued on the stream. */
 int64_t rt_groupnorm_ws_bytes(int32_t B, int32_t H, int32_t W, int32_t G);
 int rt_groupnorm_silu_nhwc(const void* x, void* y, const void* gamma, const void* beta, void* stats_ws,
                            int32_t B, int32_t H, int32_t W, int32_t C, int32_t G, float eps, int32_t silu, void* stream);
