@@ -10,6 +10,7 @@ The tower itself (CN:277-396) is re-expressed as a sequence of HIP launches over
 """
 from __future__ import annotations
 
+from collections import OrderedDict
 from dataclasses import dataclass
 from typing import Any, Dict, List, Optional, Sequence, Tuple, Union
 
@@ -31,6 +32,50 @@ class FluxControlNetOutput:
     def __iter__(self):          # lets callers unpack like the reference's tuple return
         yield self.controlnet_block_samples
         yield self.controlnet_single_block_samples
+
+
+ROW_WINDOW_ALIGN = 16    # rows of an MFMA tile
+_ROW_SPAN_CACHE: "OrderedDict" = OrderedDict()
+
+
+def _nonzero_row_span(mask: torch.Tensor) -> Optional[Tuple[int, int]]:
+    """(first, last) row of ``mask`` ([N], [B,N] or [B,N,1]) that is non-zero in any batch entry, None when every row is zero. One
+    small device-to-host read per tensor and version: the answer is cached on the tensor's storage address, layout and version
+    counter, and the cache keeps the tensor alive, so neither an in-place write (it bumps the version) nor another tensor that the
+    allocator places at the same address can be taken for it."""
+    key = (mask.data_ptr(), tuple(mask.shape), tuple(mask.stride()), str(mask.dtype), str(mask.device), mask._version)
+    hit = _ROW_SPAN_CACHE.get(key)
+    if hit is not None:
+        _ROW_SPAN_CACHE.move_to_end(key)
+        return hit[0]
+    m = mask.reshape(mask.shape[0], -1) if mask.dim() == 3 else mask.reshape(1, -1) if mask.dim() == 1 else mask
+    nz = (m != 0).any(dim=0)
+    pos = torch.arange(nz.numel(), device=nz.device)
+    lo, hi = torch.stack([torch.where(nz, pos, nz.numel()).min(), torch.where(nz, pos, -1).max()]).tolist()
+    span = None if hi < 0 else (int(lo), int(hi))
+    _ROW_SPAN_CACHE[key] = (span, mask)
+    while len(_ROW_SPAN_CACHE) > 8:
+        _ROW_SPAN_CACHE.popitem(last=False)
+    return span
+
+
+def active_row_window(masks: Sequence[torch.Tensor], N: int) -> Optional[Tuple[int, int]]:
+    """The contiguous image-row window [r0, r1) outside which the regional masks of ALL text lines and batch entries of a tower are
+    zero, rounded outward to ROW_WINDOW_ALIGN rows; None = take the full path: no mask, nothing non-zero, or a window of more than
+    half of the N rows (the cut-off: DESIGN.md §5). One window for all lines, because the first line overwrites the sample buffers
+    and the later ones add to them, on the same rows."""
+    lo, hi = N, -1
+    for m in masks:
+        if m.numel() == 0 or m.numel() % N:
+            return None
+        span = _nonzero_row_span(m)
+        if span is not None:
+            lo, hi = min(lo, span[0]), max(hi, span[1])
+    if hi < 0:
+        return None
+    a = ROW_WINDOW_ALIGN
+    r0, r1 = lo // a * a, min(N, (hi + a) // a * a)
+    return None if (r1 - r0) * 2 > N else (r0, r1)
 
 
 class FluxControlNetModel(_MMDiTBase):
@@ -125,6 +170,10 @@ class FluxControlNetModel(_MMDiTBase):
             why = f"in-features {lin.in_features} are not a multiple of 64: the K-padded copy of _padded_hint would go stale"
         return why
 
+    def supports_row_window(self) -> bool:
+        """May forward() take ``_window``? bf16 projections and attention (the e4m3 levels keep the full path)."""
+        return not getattr(self, "_fp8_linears", False) and not getattr(self, "_fp8_attention", False)
+
     def _invalidate_derived(self):
         self._cx_pad = None
 
@@ -151,7 +200,8 @@ class FluxControlNetModel(_MMDiTBase):
                 _rowscale: Optional[torch.Tensor] = None, _accumulate_into: Optional[Sequence[torch.Tensor]] = None,
                 _accumulate_single_into: Optional[Sequence[torch.Tensor]] = None, _mods: Optional["mmdit.StepMods"] = None,
                 _overwrite: bool = False, _sample_events: Optional[Sequence["torch.cuda.Event"]] = None, _ws_tag: str = "",
-                _static: Optional[StaticEmbeds] = None, _blocks_needed: Optional[Tuple[int, int]] = None):
+                _static: Optional[StaticEmbeds] = None, _blocks_needed: Optional[Tuple[int, int]] = None,
+                _window: Optional[Tuple[int, int]] = None):
         """Same contract as CN:216-413. ``joint_attention_kwargs["scale"]`` scales this call's LoRA adapters (CN:263-276; merged into
         the weights, lora.py). The private ``_rowscale`` / ``_accumulate_into`` arguments let the pipeline fuse its
         regional mask (PIPE:1062) and the sum over text lines (PIPE:1076-1080) into the zero-linear epilogues; with
@@ -161,7 +211,10 @@ class FluxControlNetModel(_MMDiTBase):
         ``_static``: this tower's loop-invariant embeddings for (prompt, this hint) from ``prepare_static`` — the per-step work
         is then x_embedder only. ``_blocks_needed`` = (double, single): evaluate only that many leading blocks; the samples of
         the rest come back as None (the pipeline knows which samples the transformer consumes: with 6 samples against 19
-        blocks the sixth is never read, quirk Q5)."""
+        blocks the sixth is never read, quirk Q5). ``_window`` = (r0, r1) from ``active_row_window``: ``_rowscale`` is zero outside
+        image rows [r0, r1) and the ``_accumulate_into`` buffers already read zero there, so the zero-linears compute those rows only
+        and the last evaluated double block, which nothing but its zero-linear reads, runs ``mmdit.run_double``'s windowed mode. For
+        bf16 towers whose single blocks are not evaluated."""
         doubles, singles = self._ensure_plans()
         self._apply_lora_scale(joint_attention_kwargs)
         cfg = self.config
@@ -198,8 +251,13 @@ class FluxControlNetModel(_MMDiTBase):
 
         def head(lin, dst_list, i):
             """zero-linear i on the current image rows: (W·h+b)·scale [·mask] [+ running sum] (CN:384-396)."""
-            a = mmdit.image_rows_bf16(ws)
-            if dst_list is not None:
+            a = mmdit.image_rows_bf16(ws, _window)
+            if _window is not None:
+                r0, r1 = _window
+                out = dst_list[i]
+                ops.linear(a, lin.weight.data, out[:, r0:r1], bias=lin.bias.data, alpha=scale, rowscale=_rowscale[..., r0:r1],
+                           res=None if _overwrite else out[:, r0:r1])
+            elif dst_list is not None:
                 out = dst_list[i]
                 ops.linear(a, lin.weight.data, out, bias=lin.bias.data, alpha=scale, rowscale=_rowscale, res=None if _overwrite else out)
             else:
@@ -211,12 +269,19 @@ class FluxControlNetModel(_MMDiTBase):
         ns = len(singles) if _blocks_needed is None else min(len(singles), int(_blocks_needed[1]))
         if ns > 0:
             nd = len(doubles)          # the single blocks read the stream all double blocks have written
+        if _window is not None:
+            if _rowscale is None or _accumulate_into is None or ns > 0 or nd < 1 or not self.supports_row_window():
+                raise ValueError("_window needs a row scale, sample buffers and a bf16 tower whose single blocks are not evaluated")
+            _window = (int(_window[0]), int(_window[1]))
+            if not (0 <= _window[0] < _window[1] <= N):
+                raise ValueError(f"_window {_window} is not inside the {N} image rows")
         block_samples: List[Optional[torch.Tensor]] = []
         for i, pl in enumerate(doubles):
             if i >= nd:
                 block_samples.append(None)
                 continue
-            mmdit.run_double(pl, ws, temb, cos, sin, H, mods=None if _mods is None else _mods.double[i])
+            mmdit.run_double(pl, ws, temb, cos, sin, H, mods=None if _mods is None else _mods.double[i],
+                             window=_window if i == nd - 1 else None)   # ns == 0: only zero-linear nd-1 reads this block
             block_samples.append(head(self.controlnet_blocks[i], _accumulate_into, i))
             if _sample_events is not None:
                 _sample_events[i].record(torch.cuda.current_stream())

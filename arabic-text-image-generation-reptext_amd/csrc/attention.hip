@@ -56,7 +56,7 @@ __host__ __device__ inline int group_slots(const SplitGeom& G, int xcd) {
 __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V, bf16_t* O,
     int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob, float scale_log2, const SplitGeom G,
-    int* counters, char* records) {
+    const int row_lo, const int row_hi, int* counters, char* records) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE_B];   // [slot][K|V]
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -127,6 +127,9 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
     if (te <= tb) break;
     const int head = item / G.nqb;
     const int q0 = (item - head * G.nqb) * BQ;
+    // rt_attention_fwd_rows: an item without a query row in [row_lo, row_hi) is nobody's work. The test depends on the item alone, so
+    // every workgroup that holds a piece of a split item decides alike and the item's tickets are either all drawn or none.
+    if (q0 + BQ <= row_lo || q0 >= row_hi) continue;
     const bf16_t* Qb = Q + b * stride_b + head * DH;
     const bf16_t* Kb = K + b * stride_b + head * DH;
     const bf16_t* Vb = V + b * stride_b + head * DH;
@@ -468,10 +471,21 @@ extern "C" int64_t rt_attention_ws_bytes(int32_t B, int32_t S, int32_t H) {
 // csrc/attention_v3.hip: the one-wave-per-SIMD kernel (64 query rows per wave); takes the launch when S % 256 == 0
 extern "C" int rt_attention_variant(int32_t mode) { return rt_attention_v3_mode(mode); }
 
+extern "C" int rt_attention_fwd_rows(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b, int64_t ldo,
+                                     int64_t stride_ob, int32_t B, int32_t S, int32_t H, float scale, int32_t row_lo, int32_t row_hi, void* ws,
+                                     int64_t ws_bytes, void* stream);
 extern "C" int rt_attention_fwd(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b,
                                 int64_t ldo, int64_t stride_ob, int32_t B, int32_t S, int32_t H, float scale,
                                 void* ws, int64_t ws_bytes, void* stream) {
-  if (!q || !k || !v || !o || B < 1 || S < 1 || H < 1) return RT_E_BADARG;
+  return rt_attention_fwd_rows(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, 0, S, ws, ws_bytes, stream);
+}
+
+// The full launch, cut exactly as rt_attention_fwd cuts it (same kernel, grid, key split and workspace), in which only the items that
+// hold a query row of [row_lo, row_hi) do any work: those rows get the bits rt_attention_fwd gives them, at the cost of their items.
+extern "C" int rt_attention_fwd_rows(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b,
+                                     int64_t ldo, int64_t stride_ob, int32_t B, int32_t S, int32_t H, float scale,
+                                     int32_t row_lo, int32_t row_hi, void* ws, int64_t ws_bytes, void* stream) {
+  if (!q || !k || !v || !o || B < 1 || S < 1 || H < 1 || row_lo < 0 || row_hi > S || row_lo >= row_hi) return RT_E_BADARG;
   if (!RT_ALIGNED(q, 16) || !RT_ALIGNED(k, 16) || !RT_ALIGNED(v, 16) || !RT_ALIGNED(o, 8) || ld % 8 || stride_b % 8 ||
       ldo % 4 || stride_ob % 4)
     return RT_E_ALIGN;
@@ -480,7 +494,7 @@ extern "C" int rt_attention_fwd(const void* q, const void* k, const void* v, voi
   if (!split_fits_32bit(make_geom(S, H, true))) return RT_E_SHAPE;
   {
     int taken = 0;
-    const int st = rt_attention_v3_try(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, ws, ws_bytes, stream, &taken);
+    const int st = rt_attention_v3_try(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, row_lo, row_hi, ws, ws_bytes, stream, &taken);
     if (taken || st != RT_OK) return st;
   }
   const int64_t need = rt_attention_ws_bytes(B, S, H);
@@ -492,7 +506,7 @@ extern "C" int rt_attention_fwd(const void* q, const void* k, const void* v, voi
   const dim3 grid(8 * wmax, B);
   hipLaunchKernelGGL(attention_fwd_kernel, grid, dim3(ATT_THREADS), 0, (hipStream_t)stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ld, stride_b, ldo, stride_ob,
-                     scale * 1.4426950408889634f, G, split ? (int*)ws : nullptr,
+                     scale * 1.4426950408889634f, G, row_lo, row_hi, split ? (int*)ws : nullptr,
                      split ? (char*)ws + split_cnt_bytes(B, S, H) : nullptr);
   return rt_hip_status();
 }

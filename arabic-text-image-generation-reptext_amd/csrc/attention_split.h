@@ -154,5 +154,6 @@ int64_t rt_attention_v3_ws_bytes(int32_t B, int32_t S, int32_t H);
 // Offers the launch to attention_v3. *taken = 1: the shape is attention_v3's and the return value (RT_OK, RT_E_* or a hipError_t)
 // is the launch's status; *taken = 0 (with RT_OK): left to attention.hip.
 int rt_attention_v3_try(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob,
-                        int32_t B, int32_t S, int32_t H, float scale, void* ws, int64_t ws_bytes, void* stream, int* taken);
+                        int32_t B, int32_t S, int32_t H, float scale, int32_t row_lo, int32_t row_hi, void* ws, int64_t ws_bytes, void* stream,
+                        int* taken);   // [row_lo, row_hi): only the items that hold a query row of this range are computed
 int rt_attention_v3_mode(int mode);

@@ -127,10 +127,13 @@ __device__ __forceinline__ f32x16 o_read(int f) {
 constexpr int REC3_WAVE_B = 8 * 16 * 64 * 4 + 64 * 16;   // one wave's partial: 8 O fragments (16 registers x 64 lanes, fp32) + (mA, lA, mB, lB) per lane
 constexpr int REC3_B = 4 * REC3_WAVE_B;                 // 135 168 B per (workgroup, segment)
 
+// ROWS: the rt_attention_fwd_rows form (row_lo / row_hi read). The whole launch is the ROWS = false instantiation: no scalar and no
+// branch is added to the code that 1708 of an image's 1736 attention launches run; the 28 ranged launches use the other instantiation.
+template <bool ROWS>
 __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                                      const bf16_t* __restrict__ V, bf16_t* O, int64_t ld, int64_t stride_b,
                                                                      int64_t ldo, int64_t stride_ob, float scale_log2, const SplitGeom G,
-                                                                     int* counters, char* records) {
+                                                                     int* counters, char* records, const int row_lo, const int row_hi) {
   extern __shared__ __attribute__((aligned(16))) char smem[];   // [3 stages][K|V]
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -172,6 +175,9 @@ __global__ __launch_bounds__(V3_THREADS, 1) void attention_v3_kernel(const bf16_
     }
     const int head = item / G.nqb;
     const int q0 = (item - head * G.nqb) * BQ3;
+    // rt_attention_fwd_rows: an item without a query row in [row_lo, row_hi) is nobody's work. The test depends on the item alone, so
+    // every workgroup that holds a piece of a split item decides alike and the item's tickets are either all drawn or none.
+    if (ROWS && (q0 + BQ3 <= row_lo || q0 >= row_hi)) continue;
     const bf16_t* Qb = Q + b * stride_b + head * DH;
     const rt_srd_t rsrcK = rt_make_srd(K + b * stride_b + head * DH), rsrcV = rt_make_srd(V + b * stride_b + head * DH);
     const uint32_t wdst = lds0 + wave * 4096;           // this wave's four pieces inside a K (or V) tile
@@ -543,7 +549,8 @@ int64_t rt_attention_v3_ws_bytes(int32_t B, int32_t S, int32_t H) {
 
 // Called by rt_attention_fwd (declared, with its contract, in attention_split.h)
 int rt_attention_v3_try(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob,
-                        int32_t B, int32_t S, int32_t H, float scale, void* ws, int64_t ws_bytes, void* stream, int* taken) {
+                        int32_t B, int32_t S, int32_t H, float scale, int32_t row_lo, int32_t row_hi, void* ws, int64_t ws_bytes, void* stream,
+                        int* taken) {
   *taken = 0;
   if (!v3_mode_now() || S % BQ3 != 0 || (ldo % 8) || (stride_ob % 8) || !RT_ALIGNED(o, 16)) return RT_OK;
   // short sequences (config 1's S = 768: 25 vs 19 us) stay with attention.hip, whose two workgroups per CU hide each other's
@@ -555,11 +562,13 @@ int rt_attention_v3_try(const void* q, const void* k, const void* v, void* o, in
   if (!split_fits_32bit(G)) return RT_OK;
   *taken = 1;
   const int lds = NSTAGE * STAGE_B;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(attention_v3_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+  const bool ranged = row_lo > 0 || row_hi < S;
+  auto kernel = ranged ? attention_v3_kernel<true> : attention_v3_kernel<false>;
+  static bool attr_done[2] = {false, false};
+  if (!attr_done[ranged]) {
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) return (int)e;
-    attr_done = true;
+    attr_done[ranged] = true;
   }
   int slots = 0;
   for (int x = 0; x < 8; ++x) {
@@ -567,9 +576,9 @@ int rt_attention_v3_try(const void* q, const void* k, const void* v, void* o, in
     const int s = c.rem ? G.spx : (c.nfull < G.spx ? c.nfull : G.spx);
     slots = s > slots ? s : slots;
   }
-  hipLaunchKernelGGL(attention_v3_kernel, dim3(8 * slots, B), dim3(V3_THREADS), lds, (hipStream_t)stream, (const bf16_t*)q, (const bf16_t*)k,
-                     (const bf16_t*)v, (bf16_t*)o, ld, stride_b, ldo, stride_ob, scale * 1.4426950408889634f, G, split ? (int*)ws : nullptr,
-                     split ? (char*)ws + split_cnt_bytes(B, S, H) : nullptr);
+  hipLaunchKernelGGL(kernel, dim3(8 * slots, B), dim3(V3_THREADS), lds, (hipStream_t)stream, (const bf16_t*)q, (const bf16_t*)k,
+                     (const bf16_t*)v, (bf16_t*)o, ld, stride_b, ldo, stride_ob, scale * 1.4426950408889634f, G,
+                     split ? (int*)ws : nullptr, split ? (char*)ws + split_cnt_bytes(B, S, H) : nullptr, (int)row_lo, (int)row_hi);
   return rt_hip_status();
 }
 

@@ -365,7 +365,8 @@ class ModulationTable:
 
 
 def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: int, inject: Optional[torch.Tensor] = None,
-               mods: Optional[tuple] = None, ip: Optional[tuple] = None, ip_inside: bool = False) -> None:
+               mods: Optional[tuple] = None, ip: Optional[tuple] = None, ip_inside: bool = False,
+               window: Optional[tuple] = None) -> None:
     """One FluxTransformerBlock on ws.x in place (A.1). ``inject`` [B,N,d] bf16 is added to the image rows after the
     block (A.3 ControlNet residual), fused into the last GEMM's epilogue. ``mods`` = precomputed (image, text) adaLN
     vectors for this step (ModulationTable); computed here from ``temb`` when absent. ``ip`` = (K, V, scale) of an IP-Adapter
@@ -373,8 +374,17 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
     feed-forward residual. ``ip_inside`` = the InstantX form of the same tuple: gate_msa · scale · softmax(q Kᵀ/√128) V, K used as given,
     accumulated straight onto the residual image rows by ONE launch placed where the raw query exists (before attention); the later
     x += gate_msa · to_out(attn) epilogue adds onto it, so h <- h + gate_msa · (to_out(attn) + scale · ip) up to the order of two
-    fp32 additions. With ``ip=None`` the launch sequence is unchanged."""
+    fp32 additions. With ``ip=None`` the launch sequence is unchanged. ``window`` = (r0, r1): the caller reads nothing of this block
+    but image rows [r0, r1) of the stream (the last evaluated block of a ControlNet tower under a regional mask, whose only reader is
+    its zero-linear): keys and values are still computed for all S rows, but attention runs only for the items of its launch that hold a
+    window query (same cut, same bits), the image
+    out / LayerNorm / ff1 / ff2 on the window's rows only, and nothing of the text stream after the QKV projection. The other rows of
+    ws.x are left as they were before the block. bf16 projections and attention without ``ip`` / ``inject`` only."""
     T, d = ws.T, ws.d
+    if window is not None:
+        if ip is not None or inject is not None or pl.qkv_img_w8 is not None or pl.fp8_attention or pl.mx:
+            raise ValueError("run_double: the windowed mode is the bf16 path without ip / inject")
+        return _run_double_window(pl, ws, temb, cos, sin, H, mods, int(window[0]), int(window[1]))
     x_t, x_i = ws.x[:, :T], ws.x[:, T:]
     xn_t, xn_i = ws.xn[:, :T], ws.xn[:, T:]
     # 1. adaLN-Zero vectors: chunk order shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
@@ -471,6 +481,40 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
             ops.masked_accumulate_(ws.x[b, T:].unsqueeze(0), ip_out[b : b + 1], None, 1.0, True)
 
 
+def _run_double_window(pl: DoublePlan, ws: Workspace, temb, cos, sin, H: int, mods: Optional[tuple], r0: int, r1: int) -> None:
+    """run_double's windowed mode (see there). Steps 1-5 are run_double's own launches: every row's k and v are needed. The q columns are
+    still projected for all rows and both streams: the fused q/k epilogue of the QKV GEMM describes a group that holds both q and k, and
+    restricting q to the window (one tile round of three at the headline shape) is not built."""
+    T, d = ws.T, ws.d
+    if not (0 <= r0 < r1 <= ws.N):
+        raise ValueError(f"window [{r0}, {r1}) is not inside the {ws.N} image rows")
+    x_t, x_i = ws.x[:, :T], ws.x[:, T:]
+    xn_t, xn_i = ws.xn[:, :T], ws.xn[:, T:]
+    if mods is not None:
+        mi, mt = mods
+    else:
+        mi, mt = ws.mod_a, ws.mod_b
+        ops.gemv(temb, pl.ada_img_w, pl.ada_img_b, mi, silu_in=True)
+        ops.gemv(temb, pl.ada_txt_w, pl.ada_txt_b, mt, silu_in=True)
+    ch = lambda m, i: m[:, i * d : (i + 1) * d]
+    ops.layernorm_modulate_pair(x_i, xn_i, ch(mi, 0), ch(mi, 1), x_t, xn_t, ch(mt, 0), ch(mt, 1))
+    fused_rope = FUSED_QK_ROPE and ops.QKRope.covers(d)
+    ri = ops.QKRope(0, d, d, pl.nq_img, pl.nk_img, cos, sin, pos0=T) if fused_rope else None
+    rt = ops.QKRope(0, d, d, pl.nq_txt, pl.nk_txt, cos, sin, pos0=0) if fused_rope else None
+    ops.linear_grouped([P(xn_i, pl.qkv_img_w, ws.qkv[:, T:], bias=pl.qkv_img_b, rope=ri), P(xn_t, pl.qkv_txt_w, ws.qkv[:, :T], bias=pl.qkv_txt_b, rope=rt)])
+    if not fused_rope:
+        ops.qk_rmsnorm_rope(ws.qkv, 0, d, H, T, pl.nq_txt, pl.nk_txt, pl.nq_img, pl.nk_img, cos, sin)
+    q, k, v = ws.qkv[..., :d], ws.qkv[..., d : 2 * d], ws.qkv[..., 2 * d :]
+    # the full launch's own cut, with only the items that hold a window row at work: the window's rows keep the bits of the full path
+    ops.attention(q, k, v, q, H, rows=(T + r0, T + r1))
+    qw = q[:, T + r0 : T + r1]                                # the window's attention output, over its queries
+    xw, xnw, hw = x_i[:, r0:r1], xn_i[:, r0:r1], ws.ffh[:, T + r0 : T + r1]
+    ops.linear(qw, pl.out_img_w, xw, bias=pl.out_img_b, gate=ch(mi, 2), res=xw)
+    ops.layernorm_modulate(xw, xnw, ch(mi, 3), ch(mi, 4))
+    ops.linear(xnw, pl.ff1_img_w, hw, bias=pl.ff1_img_b, gelu_from=0)
+    ops.linear(hw, pl.ff2_img_w, xw, bias=pl.ff2_img_b, gate=ch(mi, 5), res=xw)
+
+
 def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: int, inject: Optional[torch.Tensor] = None,
                mods: Optional[torch.Tensor] = None, ip: Optional[tuple] = None) -> None:
     """One FluxSingleTransformerBlock on ws.x in place (A.2). ``ip`` = (K, V, scale) of an InstantX IP-Adapter (ip_adapter.py):
@@ -531,13 +575,15 @@ def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
             ops.masked_accumulate_(ws.x[b, T:].unsqueeze(0), inject[b : b + 1].contiguous(), None, 1.0, True)
 
 
-def image_rows_bf16(ws: Workspace) -> torch.Tensor:
+def image_rows_bf16(ws: Workspace, rows: Optional[tuple] = None) -> torch.Tensor:
     """bf16 view/copy of the image rows of the residual stream, as a GEMM A operand (ControlNet zero-linears, CN:384-392).
-    With a bf16 stream this is the stream itself; with an fp32 stream the rows are cast into the (free) xn buffer."""
+    With a bf16 stream this is the stream itself; with an fp32 stream the rows are cast into the (free) xn buffer. ``rows`` = (r0, r1):
+    only those image rows (cast and returned)."""
     T = ws.T
+    r0, r1 = (0, ws.N) if rows is None else (int(rows[0]), int(rows[1]))
     if ws.x.dtype == BF16:
-        return ws.x[:, T:]
+        return ws.x[:, T + r0 : T + r1]
     for b in range(ws.B):
-        src, dst = ws.x[b, T:], ws.xn[b, T:]
+        src, dst = ws.x[b, T + r0 : T + r1], ws.xn[b, T + r0 : T + r1]
         native.check("rt_cast_f32_to_bf16", native.load().rt_cast_f32_to_bf16(src.data_ptr(), dst.data_ptr(), src.numel(), ops._stream()))
-    return ws.xn[:, T:]
+    return ws.xn[:, T + r0 : T + r1]

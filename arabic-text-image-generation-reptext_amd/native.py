@@ -158,6 +158,10 @@ SIGNATURES["rt_patchify_nchw"] = [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _vp]
 RT_ATTENTION_HD72_MAX_S = 1024
 SIGNATURES["rt_attention_hd72"] = [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _f32, _vp]
 
+# attention for a range of the query rows inside the full launch's cut (same bits): the last evaluated ControlNet tower block under a
+# regional mask
+SIGNATURES["rt_attention_fwd_rows"] = [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _f32, _i32, _i32, _vp, _i64, _vp]
+
 # loop passes that moved out of the 256x256-tile GEMM / were merged (csrc/gemm_skinny.hip, csrc/norm_elem.hip)
 SIGNATURES["rt_gemm_skinny_bf16"] = [_vp, _vp, _i64, _i32, _i32, C.POINTER(SkinnyGroup), _i32, _vp]
 SIGNATURES["rt_layernorm_modulate_pair"] = [C.POINTER(LnSegment), _i32, _i32, _f32, _vp]

@@ -530,9 +530,11 @@ def drop_attention_workspaces(keys) -> None:
 
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, scale: Optional[float] = None,
-              split: bool = True) -> torch.Tensor:
+              split: bool = True, rows: Optional[tuple] = None) -> torch.Tensor:
     """q,k,v [B,S,H*128] views (common strides) of one buffer; out [B,S,H*128] view (may alias q). ``split=False`` runs every
-    128-row block as one full-length workgroup (no key-split tail; A/B and tests)."""
+    128-row block as one full-length workgroup (no key-split tail; A/B and tests). ``rows`` = (r0, r1): only the items of the launch that
+    hold a query row of [r0, r1) do any work (rt_attention_fwd_rows): those rows of out get the bits the whole launch gives them, the
+    other rows of the touched items are written too, the rest of out is left as it is."""
     for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
         if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] != H * 128:
             raise ValueError(f"{name}: need [B,S,{H*128}] with unit inner stride")
@@ -541,9 +543,10 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
         raise ValueError("q,k,v must share shape and strides")
     sc = (128 ** -0.5) if scale is None else float(scale)
     ws = _attention_workspace(B, S, H, q.device) if split else None
-    native.check("rt_attention_fwd", native.load().rt_attention_fwd(
+    r0, r1 = (0, S) if rows is None else (int(rows[0]), int(rows[1]))
+    native.check("rt_attention_fwd_rows", native.load().rt_attention_fwd_rows(
         _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(out, "out", BF16), q.stride(1), q.stride(0),
-        out.stride(1), out.stride(0), B, S, H, sc, None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), _stream()))
+        out.stride(1), out.stride(0), B, S, H, sc, r0, r1, None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), _stream()))
     return out
 
 

@@ -26,7 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
-from .controlnet import FluxControlNetModel, FluxMultiControlNetModel
+from .controlnet import FluxControlNetModel, FluxMultiControlNetModel, active_row_window
 from .image_processor import PipelineImageInput, VaeImageProcessor
 from .scheduler import FlowMatchEulerDiscreteScheduler, calculate_shift
 from .transformer import FluxTransformer2DModel
@@ -107,6 +107,10 @@ OVERLAP_TOWER = os.environ.get("RT_OVERLAP_TOWER", "1") == "1"
 # The first call of a signature always runs eagerly (it also warms every lazily built buffer); capture failures fall back to
 # eager for good. `pipe.capture_graphs = False` (or RT_GRAPH=0) turns it off.
 GRAPH_CAPTURE = os.environ.get("RT_GRAPH", "1") == "1"
+# A regional mask is zero outside the box of its text line, and a zero row of a tower sample adds exactly ±0 to the transformer. With
+# RT_TOWER_WINDOW=1 (default) the tower's zero-linears compute only the row window that holds every non-zero mask row, and its last
+# evaluated block — read by nothing but its zero-linear — runs attention, out, LayerNorm, ff1 and ff2 for those rows alone.
+TOWER_WINDOW = os.environ.get("RT_TOWER_WINDOW", "1") == "1"
 GRAPH_CACHE_MAX = 2
 
 
@@ -756,10 +760,13 @@ class FluxControlNetPipeline:
         """Eager loop, or the replay of its captured hipGraph when this exact call signature has been seen before (GRAPH_CAPTURE)."""
         tvals = timesteps.to(torch.float32).cpu().tolist()                 # host copies: no per-step device sync
         ipe = getattr(self, "_ip_embeds", None)                             # image prompt of this call (None: nothing to add)
+        # the rows the regional masks leave non-zero: read here, never inside the loop or a capture; part of the call signature below
+        win = active_row_window(masks, latents.shape[1]) if masks and len(masks) == len(hints) else None
 
         def eager(callback=None):
             return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
-                                       cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe)
+                                       cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe,
+                                       _tower_window=win)
 
         use_graph = (GRAPH_CAPTURE and getattr(self, "capture_graphs", True) and callback is None and latents.is_cuda
                      and not self.interrupt and isinstance(self.controlnet, (FluxControlNetModel, type(None)))
@@ -773,7 +780,8 @@ class FluxControlNetPipeline:
                         bool(getattr(m, "_fp8_attention", False))) for m in (self.transformer, self.controlnet) if m is not None)
         key = (sig(latents), sig(prompt_embeds), sig(pooled), sig(text_ids), sig(image_ids), tuple(sig(h) for h in hints), tuple(sig(m) for m in masks),
                tuple(tvals), tuple(self.scheduler.sigmas.tolist()), float(guidance_scale), repr(cn_scale), int(cn_steps), int(num_inference_steps),
-               str(latents.device), models, bool(self.reference_bf16_scalars), bool(_mm.RESIDUAL_F32), bool(OVERLAP_TOWER), bool(_mm.FUSED_QK_ROPE))
+               str(latents.device), models, bool(self.reference_bf16_scalars), bool(_mm.RESIDUAL_F32), bool(OVERLAP_TOWER), bool(_mm.FUSED_QK_ROPE),
+               win, bool(TOWER_WINDOW))
         if ipe is not None:
             # the embeds are one more static input of the graph; the per-block scales are kernel scalars baked into the capture
             adapter = self.transformer._ip_adapter
@@ -806,7 +814,7 @@ class FluxControlNetPipeline:
                 with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                     out = self._denoise_eager(static[0], static[1], static[2], static[3], static[4], tvals, static[5 : 5 + nh], static[5 + nh : 5 + nh + nm],
                                               guidance_scale, cn_scale, cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps,
-                                              _quiet=True, _ip_embeds=static[-1] if ipe is not None else None)
+                                              _quiet=True, _ip_embeds=static[-1] if ipe is not None else None, _tower_window=win)
                     out32 = self._master_latents
             except Exception as e:                           # capture is an optimisation, never a requirement
                 import sys
@@ -814,6 +822,8 @@ class FluxControlNetPipeline:
                 cache[key] = "failed"
                 _mm.CAPTURE_KEEP = ops.CAPTURE_KEEP = None
                 ops.drop_attention_workspaces(set(ops._ATTN_WS) - attn_keys)     # their zero fill was recorded, never executed
+                if getattr(self, "_sample_cache", None) is not None:
+                    self._sample_cache[3][0] = None                              # and so was a zero fill of the sample buffers
                 torch.cuda.synchronize()
                 self.scheduler._step_index = step_index
                 return eager()
@@ -821,10 +831,13 @@ class FluxControlNetPipeline:
             keep.append(getattr(self, "_sample_cache", None))
             keep.extend(dict(m._rope_cache) for m in (self.transformer, self.controlnet) if m is not None and hasattr(m, "_rope_cache"))
             self.scheduler._step_index = step_index
-            ent = cache[key] = {"graph": graph, "static": static, "out": out, "out32": out32, "keep": keep}
+            # the sample buffers the capture wrote into and the window its zero-linears were restricted to (None: every row)
+            ent = cache[key] = {"graph": graph, "static": static, "out": out, "out32": out32, "keep": keep,
+                                "samples": getattr(self, "_sample_cache", None), "window": self._tower_window_used}
         for dst, src in zip(ent["static"], ins):
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
+        self._zero_samples_for(ent["samples"], ent["window"])       # another call may have left rows outside this window non-zero
         ent["graph"].replay()
         self.scheduler._step_index = (self.scheduler._step_index or 0) + len(tvals)      # what the eager loop's step() calls leave behind
         self._master_latents = ent["out32"].clone()
@@ -832,13 +845,26 @@ class FluxControlNetPipeline:
             bar.update(num_inference_steps)
         return ent["out"].clone()
 
+    @staticmethod
+    def _zero_samples_for(cache, window) -> None:
+        """The tower sample buffers of ``cache`` (a ``_sample_cache`` tuple) must read zero outside ``window``, whose rows alone the
+        zero-linears will write. They are zeroed once, when the window is set or changes, not per step; the tuple's last element
+        remembers the window they are valid for (None: no promise — the full path overwrites every row)."""
+        if cache is None:
+            return
+        state = cache[3]
+        if window is not None and state[0] != window:
+            for buf in cache[1]:
+                buf.zero_()
+        state[0] = window
+
     def _denoise_eager(self, latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale,
                        cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _quiet=False,
-                       _ip_embeds=None, _extra_towers=(), _velocity=None):
+                       _ip_embeds=None, _extra_towers=(), _velocity=None, _tower_window=None):
         """The one loop over timesteps, for both pipelines. ``_extra_towers``: (FluxControlNetModel, hint, conditioning scale) of
         towers evaluated after the text-line towers into the same sample buffers, unmasked (the inpaint tower). ``_velocity(i,
         noise_pred)``: what the scheduler steps with instead of the transformer's output (true CFG). With extra towers the loop stays
-        on one stream."""
+        on one stream. ``_tower_window``: ``active_row_window`` of ``masks`` from the call prologue (None: every row)."""
         device = latents.device
         B = latents.shape[0]
         guidance = torch.full((B,), float(guidance_scale), device=device, dtype=torch.float32) if self.transformer.config.guidance_embeds else None
@@ -889,8 +915,17 @@ class FluxControlNetPipeline:
             key = (Bc, N_, d_, n_cd, n_cs, str(device))
             if getattr(self, "_sample_cache", None) is None or self._sample_cache[0] != key:
                 mk = lambda n: [torch.empty(Bc, N_, d_, device=device, dtype=torch.bfloat16) for _ in range(n)]
-                self._sample_cache = (key, mk(n_cd), mk(n_cs))
+                self._sample_cache = (key, mk(n_cd), mk(n_cs), [None])
             sample_buf, single_buf = self._sample_cache[1], self._sample_cache[2]
+        # Zero-linears and the last tower block on the masked rows only (controlnet.forward: _window). The extra towers are unmasked
+        # and ADD to every row of the buffers, step after step, so with them every row must be overwritten first: full path.
+        window = None
+        if (TOWER_WINDOW and _tower_window is not None and towers and not _extra_towers and blocks_needed is not None
+                and blocks_needed[0] >= 1 and blocks_needed[1] == 0 and self.controlnet.supports_row_window()):
+            window = _tower_window
+        self._tower_window_used = window
+        if fused_cn:
+            self._zero_samples_for(self._sample_cache, window)
         # fp32 master copy of the latents between steps (the models read its bf16 copy): the scheduler computes in fp32 anyway
         # (A.6); not rounding the STATE 28 times keeps the loop close to the fp32 reference path. Callbacks see the bf16 copy.
         lat32 = latents.to(torch.float32).contiguous()
@@ -930,7 +965,7 @@ class FluxControlNetPipeline:
                                 txt_ids=text_ids, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs,
                                 return_dict=False, _rowscale=rowscale, _accumulate_into=sample_buf, _accumulate_single_into=single_buf,
                                 _overwrite=(k == 0), _sample_events=events if k == len(towers) - 1 else None, _mods=table.step(i),
-                                _ws_tag="tower" if overlap else "", _static=static, _blocks_needed=blocks_needed)
+                                _ws_tag="tower" if overlap else "", _static=static, _blocks_needed=blocks_needed, _window=window)
                             if k == 0:
                                 merged, merged_single = samples          # the buffers, None where a block was skipped
                 noise_pred = self.transformer(

@@ -245,6 +245,15 @@ int rt_attention_fwd(const void* q, const void* k, const void* v, void* o,
                      int32_t B, int32_t S, int32_t H, float scale,
                      void* ws, int64_t ws_bytes, void* stream);
 
+/* rt_attention_fwd in which only the 128- or 256-row items that hold a query row of [row_lo, row_hi) do any work: the same kernel,
+ * grid, key split and workspace as rt_attention_fwd for (B, S, H), so rows row_lo..row_hi-1 of o get exactly the bits rt_attention_fwd
+ * gives them. The other rows of those items are written too; rows of untouched items are left as they are (with o aliasing q: the raw
+ * query). 0 <= row_lo < row_hi <= S. rt_attention_fwd is the range [0, S). Added without an ABI bump: nothing existing changed. */
+int rt_attention_fwd_rows(const void* q, const void* k, const void* v, void* o,
+                          int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob,
+                          int32_t B, int32_t S, int32_t H, float scale, int32_t row_lo, int32_t row_hi,
+                          void* ws, int64_t ws_bytes, void* stream);
+
 /* Which kernel serves rt_attention_fwd (speed only; both are tested against the same references): 1 (default, env RT_ATTN_V3) =
  * shapes with S % 256 == 0 and S >= 1536 run csrc/attention_v3.hip — one wave per SIMD, 64 query rows per wave, O / Q / row sums
  * in asm-owned accumulator registers, hand-placed MFMA gaps (S = 4608: 247 vs 264 us) —, everything else csrc/attention.hip;
