@@ -1,7 +1,8 @@
 """The vision encoders on the HIP kernels: the image encoders behind ``pipe(..., ip_adapter_image=img)`` — CLIP ViT-L/14 for the
 XLabs / diffusers IP-Adapter, SigLIP-so400m for the InstantX one (``image_encoder_class`` picks between them from a directory's
-``config.json``). Both are pre-LN ViT towers and share ``_VisionTower``: the plans, the input checks and the layer loop; a class keeps
-its constructor, its state-dict layout, and what comes before and after the layers.
+``config.json``). Both are pre-LN ViT towers on the stack CLIP text also runs (``encoder_common._PreLNStack``: the plans and the layer
+loop) and share ``_VisionTower``: the patch weight and the input checks; a class keeps its constructor, its state-dict layout, and
+what comes before and after the layers.
 
 ``CLIPVisionModelWithProjection`` has the class name, constructor config keys, module names and state-dict keys of `transformers`'
 class (``vision_model.pre_layrnorm`` in transformers' spelling, ``vision_model.post_layernorm``, a top-level
@@ -22,16 +23,14 @@ from __future__ import annotations
 
 import json
 import os
-from typing import Optional
 
 import numpy as np
 import torch
 import torch.nn as nn
 
-from . import native, ops
+from . import ops
 from .config import Config
-from .modules import WeightsIO
-from .text_encoders import BF16, F32, _H, _W, _WB, _stream
+from .encoder_common import BF16, F32, _H, _W, _WB, _encoder_layers, _mlp_padded, _PreLNStack, _quick_gelu, pad_mlp_to_64  # noqa: F401
 
 OPENAI_CLIP_MEAN = (0.48145466, 0.4578275, 0.40821073)
 OPENAI_CLIP_STD = (0.26862954, 0.26130258, 0.27577711)
@@ -102,58 +101,12 @@ def image_encoder_class(directory: str):
     return CLIPVisionModelWithProjection
 
 
-def pad_mlp_to_64(w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor):
-    """(fc1.weight [F,d], fc1.bias [F], fc2.weight [d,F]) with F padded by zeros to the next multiple of 64 (the GEMM's K % 64 rule
-    for fc2: 4304 -> 4352). Exact: a padded hidden unit is gelu_tanh(0·x + 0) = 0 and meets a zero column of fc2."""
-    F_ = w1.shape[0]
-    Fp = (F_ + 63) // 64 * 64
-    if Fp == F_:
-        return w1.contiguous(), b1.contiguous(), w2.contiguous()
-    w1p = torch.zeros(Fp, w1.shape[1], device=w1.device, dtype=w1.dtype)
-    w1p[:F_] = w1
-    b1p = torch.zeros(Fp, device=b1.device, dtype=b1.dtype)
-    b1p[:F_] = b1
-    w2p = torch.zeros(w2.shape[0], Fp, device=w2.device, dtype=w2.dtype)
-    w2p[:, :F_] = w2
-    return w1p, b1p, w2p
+class _VisionTower(_PreLNStack):
+    """What the two vision encoders add to the shared stack: the patch weight as a GEMM operand, the input checks and
+    ``random_init_``. A class names the parameters ``random_init_`` gives unit scale (``_unit_scale``)."""
 
-
-def _affine(ln):                  # LayerNorm(x)·w + b == LN(x)·(1 + (w - 1)) + b: the adaLN kernel with constant vectors
-    return (ln.weight.data.to(F32) - 1.0).reshape(1, -1).contiguous(), ln.bias.data.to(F32).reshape(1, -1).contiguous()
-
-
-class _VisionTower(nn.Module, WeightsIO):
-    """What the two encoders share; it holds no parameters of its own. A class names the parameter its dtype and device are read
-    from (``_anchor``), the parameters ``random_init_`` gives unit scale (``_unit_scale``) and its head dim (``_head_dim``: which of
-    the two small-head attention entry points its layers call), builds its modules, and implements ``_build_plans`` and ``forward``."""
-
-    config_name = "config.json"
-    weights_name = "model.safetensors"
-    _anchor: str
+    _config_section = "vision_config"
     _unit_scale: tuple
-    _head_dim: int
-
-    @property
-    def dtype(self):
-        return self.get_parameter(self._anchor).dtype
-
-    @property
-    def device(self):
-        return self.get_parameter(self._anchor).device
-
-    def _apply(self, fn, *a, **k):
-        self._plans = None
-        return super()._apply(fn, *a, **k)
-
-    @classmethod
-    def from_pretrained(cls, path: str, torch_dtype=None, subfolder: Optional[str] = None, device=None, **unused):
-        d = cls._resolve_dir(path, subfolder)
-        with open(os.path.join(d, cls.config_name)) as f:
-            cfg = json.load(f)
-        cfg = {k: v for k, v in cfg.get("vision_config", cfg).items() if k not in ("dtype", "device")}    # transformers 5.x records a dtype
-        m = cls(**cfg, device=device or "cpu", dtype=torch_dtype or BF16)
-        m.load_state_dict({k: v.to(torch_dtype or BF16) for k, v in cls._load_safetensors_dir(d).items()}, strict=True)
-        return m
 
     def random_init_(self, seed: int = 0):
         """Random weights at an exercised scale, for tools and tests that run without a checkpoint: matrices at 1/sqrt(fan-in),
@@ -167,33 +120,19 @@ class _VisionTower(nn.Module, WeightsIO):
             else:
                 std = 1.0 if any(u in n for u in self._unit_scale) else p[0].numel() ** -0.5
                 p.data.copy_(torch.randn(p.shape, generator=g) * std)
-        self._plans = None
+        self._reset_plans()
         return self
 
-    def _ensure_plans(self):
-        if self._plans is None:
-            if self.dtype != BF16 or self.device.type != "cuda":
-                raise RuntimeError(f"{type(self).__name__} (HIP): bf16 on the GPU only; there is no CPU fallback")
-            self._plans = self._build_plans()
-        return self._plans
-
     def _tower_plans(self, emb, layers) -> dict:
-        """The plans both towers need: the patch weight as a GEMM operand and, per layer, (wqkv, bqkv, wo, bo, w1, b1, w2, b2, ln1, ln2)."""
+        """``_layer_plans`` and the patch weight as a GEMM operand [d,Kp]; ``patch_embedding.weight`` becomes a view of its first 3p²
+        columns."""
         c = self.config
-        d, k = c.hidden_size, 3 * c.patch_size ** 2
+        d, p, k = c.hidden_size, c.patch_size, 3 * c.patch_size ** 2
         Kp = (k + 63) // 64 * 64                                                  # the GEMM's K % 64 rule: 588 -> 640 for p = 14
         w_patch = torch.zeros(d, Kp, device=self.device, dtype=BF16)
         w_patch[:, :k] = emb.patch_embedding.weight.data.reshape(d, k)
-        plan = []
-        for l in layers:
-            sa = l.self_attn
-            wqkv = torch.cat([sa.q_proj.weight.data, sa.k_proj.weight.data, sa.v_proj.weight.data], dim=0).contiguous()
-            bqkv = torch.cat([sa.q_proj.bias.data, sa.k_proj.bias.data, sa.v_proj.bias.data], dim=0).contiguous()
-            # the identity for CLIP, whose constructor requires intermediate_size % 64 == 0
-            w1, b1, w2 = pad_mlp_to_64(l.mlp.fc1.weight.data, l.mlp.fc1.bias.data, l.mlp.fc2.weight.data)
-            plan.append((wqkv, bqkv, sa.out_proj.weight.data, sa.out_proj.bias.data, w1, b1, w2, l.mlp.fc2.bias.data,
-                         _affine(l.layer_norm1), _affine(l.layer_norm2)))
-        return dict(w_patch=w_patch, Kp=Kp, Fp=(c.intermediate_size + 63) // 64 * 64, layers=plan)
+        emb.patch_embedding.weight.data = w_patch[:, :k].view(d, 3, p, p)
+        return dict(self._layer_plans(layers), w_patch=w_patch, Kp=Kp)
 
     def _pixels(self, pixel_values: torch.Tensor) -> torch.Tensor:
         c = self.config
@@ -202,59 +141,6 @@ class _VisionTower(nn.Module, WeightsIO):
         if pixel_values.dtype not in (BF16, F32):
             pixel_values = pixel_values.to(F32)
         return pixel_values.to(self.device)
-
-    # The two hooks tools/bench_image_encoder.py overrides to time the per-head assembled attention on the same forward.
-    def _padded_tokens(self, S: int) -> int:
-        """Rows per batch entry of the token buffers: the fused attention takes S as it is."""
-        return S
-
-    def _attention(self, qkv: torch.Tensor, att: torch.Tensor, S: int) -> None:
-        d, H = self.config.hidden_size, self.config.num_attention_heads
-        fused = ops.attention_hd64 if self._head_dim == 64 else ops.attention_hd72
-        fused(qkv[:, :S, :d], qkv[:, :S, d : 2 * d], qkv[:, :S, 2 * d :], att[:, :S], H, self._head_dim ** -0.5)
-
-    def _layers(self, plans: dict, x: torch.Tensor, S: int, act=None) -> None:
-        """The pre-LN blocks on the fp32 residual stream x [B,Sp,d] (rows >= S of an entry are padding), in place: LN1 -> q|k|v GEMM
-        -> attention -> out-proj + residual -> LN2 -> fc1 -> activation -> fc2 + residual. ``act``: a pass over the fc1 output in
-        place, or None for gelu_tanh in fc1's own epilogue."""
-        B, Sp, d = x.shape
-        dev, eps = x.device, float(self.config.layer_norm_eps)
-        x2, x3 = x.view(B * Sp, d), x.view(1, B * Sp, d)
-        xn = torch.empty(B, Sp, d, device=dev, dtype=BF16)
-        xn2, xn3 = xn.view(B * Sp, d), xn.view(1, B * Sp, d)
-        qkv = torch.empty(B, Sp, 3 * d, device=dev, dtype=BF16)
-        att = torch.zeros(B, Sp, d, device=dev, dtype=BF16) if Sp != S else torch.empty(B, S, d, device=dev, dtype=BF16)
-        qkv2, att2 = qkv.view(B * Sp, 3 * d), att.view(B * Sp, d)
-        hid = torch.empty(B * Sp, plans["Fp"], device=dev, dtype=BF16)
-        for wqkv, bqkv, wo, bo, w1, b1, w2, b2, ln1, ln2 in plans["layers"]:
-            ops.layernorm_modulate(x3, xn3, ln1[1], ln1[0], eps=eps)
-            ops.linear(xn2, wqkv, qkv2, bias=bqkv)
-            self._attention(qkv, att, S)
-            ops.linear(att2, wo, x2, bias=bo, res=x2)
-            ops.layernorm_modulate(x3, xn3, ln2[1], ln2[0], eps=eps)
-            if act is None:
-                ops.linear(xn2, w1, hid, bias=b1, gelu_from=0)
-            else:
-                ops.linear(xn2, w1, hid, bias=b1)
-                act(hid)
-            ops.linear(hid, w2, x2, bias=b2, res=x2)
-
-
-def _encoder_layers(n: int, d: int, F_: int, kw: dict) -> nn.Module:
-    """``encoder.layers.*`` of both transformers classes: self_attn.{q,k,v,out}_proj, layer_norm1/2, mlp.fc1/fc2."""
-    enc = _H()
-    enc.layers = nn.ModuleList()
-    for _ in range(n):
-        l = _H()
-        sa = _H()
-        sa.q_proj, sa.k_proj, sa.v_proj, sa.out_proj = (_WB(d, d, **kw) for _ in range(4))
-        l.self_attn = sa
-        l.layer_norm1, l.layer_norm2 = _WB(d, **kw), _WB(d, **kw)
-        mlp = _H()
-        mlp.fc1, mlp.fc2 = _WB(F_, d, **kw), _WB(d, F_, **kw)
-        l.mlp = mlp
-        enc.layers.append(l)
-    return enc
 
 
 # ========================================================================================================================= CLIP
@@ -299,22 +185,15 @@ class CLIPVisionModelWithProjection(_VisionTower):
         vm.post_layernorm = _WB(hidden_size, **kw)
         self.vision_model = vm
         self.visual_projection = _W(projection_dim, hidden_size, **kw)
-        self._plans = None
 
     def load_state_dict(self, sd, strict: bool = True, **kw):
         # accept the encoder's keys with or without the `vision_model.` prefix (CLIPVisionModel's own layout), as CLIPTextModel does
         if not any(k.startswith("vision_model.") for k in sd):
             sd = {k if k.startswith("visual_projection.") else "vision_model." + k: v for k, v in sd.items()}
-        sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
-        self._plans = None
-        return super().load_state_dict(sd, strict=strict, **kw)
+        return self._load(sd, strict, **kw)
 
     def _build_plans(self):
-        vm = self.vision_model
-        pos = vm.embeddings.position_embedding.weight.data.to(F32)
-        cls_row = (vm.embeddings.class_embedding.data.to(F32) + pos[0]).contiguous()   # the class row is a constant of the weights
-        return dict(self._tower_plans(vm.embeddings, vm.encoder.layers), pos_patches=pos[1:].contiguous(), cls_row=cls_row,
-                    pre=_affine(vm.pre_layrnorm), post=_affine(vm.post_layernorm))
+        return self._tower_plans(self.vision_model.embeddings, self.vision_model.encoder.layers)
 
     @torch.no_grad()
     def forward(self, pixel_values: torch.Tensor, output_attentions=None, output_hidden_states=None, interpolate_pos_encoding: bool = False,
@@ -324,27 +203,30 @@ class CLIPVisionModelWithProjection(_VisionTower):
                                       "configured image size")
         plans = self._ensure_plans()
         pixel_values = self._pixels(pixel_values)
-        c, dev, lib = self.config, self.device, native.load()
+        c, dev, vm = self.config, self.device, self.vision_model
         B, d, p = pixel_values.shape[0], c.hidden_size, c.patch_size
         G = c.image_size // p
         S = G * G + 1
         Sp = self._padded_tokens(S)
-        eps = float(c.layer_norm_eps)
-        # 1-2. patches -> fp32 rows 1.. of every batch entry, position embeddings added by the GEMM's residual slot; row 0 is constant
+        eps, aff = float(c.layer_norm_eps), plans["norms"].refresh()
+        pre, post = aff[vm.pre_layrnorm], aff[vm.post_layernorm]
+        # 1-2. patches -> fp32 rows 1.. of every batch entry, position embeddings added by the GEMM's residual slot; row 0 is the class
+        #      token plus its position
         patches = ops.patchify_nchw(pixel_values, p, plans["Kp"])
+        pos = vm.embeddings.position_embedding.weight.data.to(F32)
         e = torch.zeros(B, Sp, d, device=dev, dtype=F32) if Sp != S else torch.empty(B, S, d, device=dev, dtype=F32)
-        e[:, 0] = plans["cls_row"]
-        ops.linear(patches, plans["w_patch"], e[:, 1:S], res=plans["pos_patches"].unsqueeze(0).expand(B, -1, -1))
+        e[:, 0] = pos[0] + vm.embeddings.class_embedding.data
+        ops.linear(patches, plans["w_patch"], e[:, 1:S], res=pos[1:].unsqueeze(0).expand(B, -1, -1))
         # 3. pre_layrnorm; its bf16 output starts the fp32 residual stream
         xn = torch.empty(B, Sp, d, device=dev, dtype=BF16)
-        ops.layernorm_modulate(e.view(1, B * Sp, d), xn.view(1, B * Sp, d), plans["pre"][1], plans["pre"][0], eps=eps)
+        ops.layernorm_modulate(e.view(1, B * Sp, d), xn.view(1, B * Sp, d), pre[1], pre[0], eps=eps)
         x = ops.to_f32(xn)
         # 4. the layers, quick_gelu as its own pass over the fc1 output
-        self._layers(plans, x, S, act=lambda hid: native.check("rt_quick_gelu", lib.rt_quick_gelu(hid.data_ptr(), hid.numel(), _stream())))
+        self._layers(plans, aff, x, S, act=_quick_gelu)
         last = ops.to_bf16(x)[:, :S]
         # 5-6. post_layernorm on the class token, visual_projection
         pooled = torch.empty(B, 1, d, device=dev, dtype=BF16)
-        ops.layernorm_modulate(x[:, 0:1], pooled, plans["post"][1].expand(B, -1), plans["post"][0].expand(B, -1), eps=eps)
+        ops.layernorm_modulate(x[:, 0:1], pooled, post[1].expand(B, -1), post[0].expand(B, -1), eps=eps)
         embeds = torch.empty(B, c.projection_dim, device=dev, dtype=BF16)
         ops.linear(pooled.view(B, d), self.visual_projection.weight.data, embeds)
         return CLIPVisionModelOutput(embeds, last) if return_dict else (embeds, last)
@@ -379,7 +261,7 @@ class SiglipVisionModel(_VisionTower):
     convolution WITH bias + learned positions (no class token, no pre-norm; the convolution keeps image_size // patch_size patches per
     side and drops the rest of the image), pre-LN blocks with gelu_pytorch_tanh, ``post_layernorm`` on all tokens, then the head:
     MHA(probe, h, h), x + mlp(layernorm(x)), row 0. Heads of 72: one rt_attention_hd72 launch per layer on the fused q|k|v buffer
-    and one more for the head, whose query probe·Wqᵀ + bq is a constant of the weights (computed once with the plans)."""
+    and one more for the head, whose query is the one row probe·Wqᵀ + bq."""
 
     _anchor = "head.probe"
     _unit_scale = ("probe", "position_embedding")
@@ -419,26 +301,18 @@ class SiglipVisionModel(_VisionTower):
         head.mlp = _H()
         head.mlp.fc1, head.mlp.fc2 = _WB(intermediate_size, hidden_size, **kw), _WB(hidden_size, intermediate_size, **kw)
         self.head = head
-        self._plans = None
 
     def load_state_dict(self, sd, strict: bool = True, **kw):
         # a full SiglipModel checkpoint: the text tower and the two logit scalars are not ours; then the published prefix
         sd = {k: v for k, v in sd.items() if not (k.startswith("text_model.") or k in ("logit_scale", "logit_bias"))}
         sd = {(k[len("vision_model."):] if k.startswith("vision_model.") else k): v for k, v in sd.items()}
-        sd = {k: v for k, v in sd.items() if not k.endswith("position_ids")}
-        self._plans = None
-        return super().load_state_dict(sd, strict=strict, **kw)
+        return self._load(sd, strict, **kw)
 
     def _build_plans(self):
-        emb, head, d = self.embeddings, self.head, self.config.hidden_size
-        att = head.attention
-        wq, bq = att.in_proj_weight.data[:d].to(F32), att.in_proj_bias.data[:d].to(F32)
-        q_probe = (head.probe.data.to(F32).reshape(1, d) @ wq.t() + bq).to(BF16).reshape(1, 1, d).contiguous()   # a constant of the weights
-        hw1, hb1, hw2 = pad_mlp_to_64(head.mlp.fc1.weight.data, head.mlp.fc1.bias.data, head.mlp.fc2.weight.data)
-        return dict(self._tower_plans(emb, self.encoder.layers), b_patch=emb.patch_embedding.bias.data.contiguous(),
-                    pos=emb.position_embedding.weight.data.to(F32).contiguous(), post=_affine(self.post_layernorm), q_probe=q_probe,
-                    wkv=att.in_proj_weight.data[d:].contiguous(), bkv=att.in_proj_bias.data[d:].contiguous(), wo=att.out_proj.weight.data,
-                    bo=att.out_proj.bias.data, head_ln=_affine(head.layernorm), head_mlp=(hw1, hb1, hw2, head.mlp.fc2.bias.data))
+        emb, att, d = self.embeddings, self.head.attention, self.config.hidden_size
+        return dict(self._tower_plans(emb, self.encoder.layers), b_patch=emb.patch_embedding.bias.data, wq=att.in_proj_weight.data[:d],
+                    bq=att.in_proj_bias.data[:d], wkv=att.in_proj_weight.data[d:], bkv=att.in_proj_bias.data[d:], wo=att.out_proj.weight.data,
+                    bo=att.out_proj.bias.data, head_mlp=_mlp_padded(self.head.mlp))
 
     @torch.no_grad()
     def forward(self, pixel_values: torch.Tensor, output_attentions=None, output_hidden_states=None, interpolate_pos_encoding: bool = False,
@@ -452,26 +326,28 @@ class SiglipVisionModel(_VisionTower):
         B, d, H, p = pixel_values.shape[0], c.hidden_size, c.num_attention_heads, c.patch_size
         G = c.image_size // p
         S = G * G
-        eps, scale = float(c.layer_norm_eps), 72 ** -0.5
+        eps, scale, aff = float(c.layer_norm_eps), 72 ** -0.5, plans["norms"].refresh()
+        post, head_ln = aff[self.post_layernorm], aff[self.head.layernorm]
         # 1. patches of the top-left G·p square (384 -> 378 for p = 14: the convolution drops the rest; patchify_nchw copies the crop
         #    once) -> the fp32 residual stream: bias in the GEMM's bias slot, the position table in its residual slot
         patches = ops.patchify_nchw(pixel_values[:, :, : G * p, : G * p], p, plans["Kp"])
         x = torch.empty(B, S, d, device=dev, dtype=F32)
-        ops.linear(patches, plans["w_patch"], x, bias=plans["b_patch"], res=plans["pos"].unsqueeze(0).expand(B, -1, -1))
+        ops.linear(patches, plans["w_patch"], x, bias=plans["b_patch"], res=self.embeddings.position_embedding.weight.data.to(F32).unsqueeze(0).expand(B, -1, -1))
         # 2. the layers, gelu_tanh in fc1's epilogue
-        self._layers(plans, x, S)
+        self._layers(plans, aff, x, S)
         # 3. post_layernorm on all tokens
         last = torch.empty(B, S, d, device=dev, dtype=BF16)
-        ops.layernorm_modulate(x.view(1, B * S, d), last.view(1, B * S, d), plans["post"][1], plans["post"][0], eps=eps)
+        ops.layernorm_modulate(x.view(1, B * S, d), last.view(1, B * S, d), post[1], post[0], eps=eps)
         # 4. the attention-pooling head: k|v of the normed tokens in one GEMM, one probe row per batch entry, out_proj, MLP
         kv = torch.empty(B, S, 2 * d, device=dev, dtype=BF16)
         ops.linear(last.view(B * S, d), plans["wkv"], kv.view(B * S, 2 * d), bias=plans["bkv"])
         pa = torch.empty(B, 1, d, device=dev, dtype=BF16)
-        ops.attention_hd72(plans["q_probe"], kv[..., :d], kv[..., d:], pa, H, scale)
+        q_probe = (self.head.probe.data.to(F32).reshape(1, d) @ plans["wq"].to(F32).t() + plans["bq"]).to(BF16).reshape(1, 1, d)
+        ops.attention_hd72(q_probe, kv[..., :d], kv[..., d:], pa, H, scale)
         y = torch.empty(B, d, device=dev, dtype=F32)
         ops.linear(pa.view(B, d), plans["wo"], y, bias=plans["bo"])
         yn = torch.empty(1, B, d, device=dev, dtype=BF16)
-        ops.layernorm_modulate(y.view(1, B, d), yn, plans["head_ln"][1], plans["head_ln"][0], eps=eps)
+        ops.layernorm_modulate(y.view(1, B, d), yn, head_ln[1], head_ln[0], eps=eps)
         hw1, hb1, hw2, hb2 = plans["head_mlp"]
         hh = torch.empty(B, hw1.shape[0], device=dev, dtype=BF16)
         ops.linear(yn.view(B, d), hw1, hh, bias=hb1, gelu_from=0)

@@ -21,6 +21,7 @@ from typing import List, Optional
 import torch
 
 from . import native, ops
+from .modules import _fuse
 from .ops import LinearProblem as P
 
 import os
@@ -116,20 +117,6 @@ class SinglePlan:
     out_ws: Optional[torch.Tensor] = None
     fp8_attention: bool = False
     mx: bool = False
-
-
-def _fuse(lins) -> tuple:
-    """Concatenate Linear weights/biases along the output dim and re-point the originals at views of the fused
-    storage, so the separate copies are freed and later in-place loads (load_state_dict) stay fused."""
-    w = torch.cat([l.weight.data for l in lins], dim=0).contiguous()
-    b = torch.cat([l.bias.data for l in lins], dim=0).contiguous()
-    o = 0
-    for l in lins:
-        n = l.weight.shape[0]
-        l.weight.data = w[o : o + n]
-        l.bias.data = b[o : o + n]
-        o += n
-    return w, b
 
 
 def plan_double(blk, fp8=False, fp8_attention: bool = False) -> DoublePlan:

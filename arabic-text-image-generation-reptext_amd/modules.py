@@ -102,6 +102,22 @@ class TimeTextEmbedParams(nn.Module):
         self.text_embedder = mlp(pooled_dim)
 
 
+def _fuse(lins) -> tuple:
+    """Concatenate Linear weights (and biases, where the Linears have them: else None) along the output dim and re-point the
+    originals at views of the fused storage, so the separate copies are freed and later in-place writes stay fused."""
+    w = torch.cat([l.weight.data for l in lins], dim=0).contiguous()
+    has_bias = getattr(lins[0], "bias", None) is not None
+    b = torch.cat([l.bias.data for l in lins], dim=0).contiguous() if has_bias else None
+    o = 0
+    for l in lins:
+        n = l.weight.shape[0]
+        l.weight.data = w[o : o + n]
+        if has_bias:
+            l.bias.data = b[o : o + n]
+        o += n
+    return w, b
+
+
 def hf_cache_dirs():
     """The hub cache root, by huggingface_hub's precedence: HF_HUB_CACHE, HUGGINGFACE_HUB_CACHE, $HF_HOME/hub,
     ~/.cache/huggingface/hub — the first one that is set is THE cache (no network is ever touched)."""

@@ -1,6 +1,6 @@
 """CLIP vision encoder cost at the ViT-L/14 shape (24 layers, d = 1024, 16 heads, 257 tokens, random weights), B = 1 and B = 4:
   * the encoder as shipped: one rt_attention_hd64 launch per layer;
-  * the same forward with attention routed through text_encoders._attention_heads, the per-(batch, head) GEMM -> softmax ->
+  * the same forward with attention routed through encoder_common._attention_heads, the per-(batch, head) GEMM -> softmax ->
     transpose -> GEMM chain that was the only head-dim-64 attention before, with the tokens padded to 320;
   three alternating timed runs each after warm-up, and the two outputs compared;
   * rt_attention_hd64 alone at (B = 1, S = 257, H = 16) and (B = 4, ...), on a rotating set of buffers; `--kernel-only` stops here
@@ -18,26 +18,13 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 
 import reptext_amd.ops as ops
-from reptext_amd import text_encoders as te
+from reptext_amd.encoder_common import _AssembledAttention
 from reptext_amd.image_encoder import CLIPVisionModelWithProjection
 
 
-class AssembledAttention(CLIPVisionModelWithProjection):
-    """The same model with its attention as text_encoders.CLIPTextModel runs it: tokens padded to a multiple of 64, one GEMM ->
-    rt_softmax_rows_bias -> rt_transpose_bf16 -> GEMM chain per (batch, head)."""
-
-    def _padded_tokens(self, S):
-        return (S + 63) // 64 * 64
-
-    def _attention(self, qkv, att, S):
-        d, H, Tp = self.config.hidden_size, self.config.num_attention_heads, qkv.shape[1]
-        key = (Tp, str(qkv.device))
-        if getattr(self, "_scratch_key", None) != key:
-            dev = qkv.device
-            self._scratch = (torch.empty(Tp, Tp, device=dev, dtype=torch.float32), torch.zeros(Tp, Tp, device=dev, dtype=torch.bfloat16),
-                             torch.empty(64, Tp, device=dev, dtype=torch.bfloat16))
-            self._scratch_key = key
-        te._attention_heads(qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:], att, H, None, 64 ** -0.5, S, Tp, self._scratch)
+class AssembledAttention(_AssembledAttention, CLIPVisionModelWithProjection):
+    """The same model with its attention as text_encoders.CLIPTextModel runs it, without a mask: tokens padded to a multiple of 64, one
+    GEMM -> rt_softmax_rows_bias -> rt_transpose_bf16 -> GEMM chain per (batch, head)."""
 
 
 def timed(fn, iters, warm=2):
