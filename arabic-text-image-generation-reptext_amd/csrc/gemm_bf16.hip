@@ -678,6 +678,9 @@ static int launch_gemm(const rt_gemm_group* groups, int32_t ngroups, void* strea
     if (!g.A || !g.W || !g.C || g.M < 1 || g.N < 1 || g.K < 1 || g.batch < 1) return RT_E_BADARG;
     if (g.K % bke != 0 || g.N % 4 != 0) return RT_E_SHAPE;
     if (g.rows_per_batch > 0 && g.M % g.rows_per_batch != 0) return RT_E_SHAPE;
+    // the epilogue decides n >= gelu_from once per 4-column group of a lane: a boundary inside a group would leave up to three
+    // columns un-activated
+    if (g.gelu_from > 0 && g.gelu_from < g.N && g.gelu_from % 4 != 0) return RT_E_SHAPE;
     if (!RT_ALIGNED(g.A, 16) || !RT_ALIGNED(g.W, 16) || g.lda % al || g.ldw % al || g.strideA % al) return RT_E_ALIGN;
     if ((g.conv_ks == 0 && g.lda < g.K) || g.ldw < g.K || g.ldc < g.N) return RT_E_SHAPE;
     // staging offsets are 32-bit byte offsets from the (per-batch) operand base

@@ -254,6 +254,8 @@ class LinearProblem:
             g.rope_q0, g.rope_k0, g.rope_w, g.rope_pos0, g.rope_eps = int(r.q0), int(r.k0), int(r.width), int(r.pos0), float(r.eps)
         g.rows_per_batch = rpb
         g.gelu_from = N if self.gelu_from is None else int(self.gelu_from)
+        if 0 < g.gelu_from < N and g.gelu_from % 4:
+            raise ValueError(f"gelu_from = {g.gelu_from}: a first GELU column inside (0, N) must be a multiple of 4 (the epilogue decides per 4-column group)")
         g.alpha = float(self.alpha)
         return g
 

@@ -68,7 +68,8 @@ typedef struct rt_gemm_group {
   int32_t M, N, K;      /* K % 64 == 0, N % 4 == 0        */
   int32_t batch;
   int32_t rows_per_batch; /* rows sharing one gate vector; 0 => M */
-  int32_t gelu_from;    /* first column that gets GELU-tanh; >= N => none */
+  int32_t gelu_from;    /* first column that gets GELU-tanh; <= 0 => all, >= N => none; a value inside (0, N) must be a
+                         * multiple of 4 (the epilogue decides per 4-column group), anything else is RT_E_SHAPE */
   int32_t out_f32;      /* C/res dtype: 0 bf16, 1 f32     */
   float alpha;
   /* fp8 operands (rt_gemm_fp8 only; ignored by rt_gemm_bf16): A and W hold OCP e4m3 bytes, lda/ldw/strideA count

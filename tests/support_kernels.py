@@ -1,4 +1,5 @@
-"""What the tests of tests/test_support_kernels_gpu.py share: guarded buffers (NaN where a kernel must not read, a sentinel where it must
+"""What the tests of tests/test_support_kernels_gpu.py, test_gemm_epilogue_gpu.py and test_attention_edges_gpu.py share: the fp64 references
+of the GEMM epilogue and of attention, the per-element bound check, guarded buffers (NaN where a kernel must not read, a sentinel where it must
 not write), the bf16 error bound, ulp distances and the run-twice check. A plain helper module, not a test file."""
 import torch
 
@@ -129,3 +130,82 @@ def groupnorm_ref(x, gamma, beta, G, eps):
     var = ((xd - mean) ** 2).mean(dim=(1, 3), keepdim=True)
     n = ((xd - mean) / torch.sqrt(var + eps)).reshape(B, H, W, C) * gamma.double() + beta.double()
     return n, n * torch.sigmoid(n)
+
+
+def check_bound(what, got, ref, bound):
+    """|got - ref| <= bound elementwise (bound a tensor of ref's shape) and every output finite. Prints the worst err/bound before it
+    asserts and returns it."""
+    got, ref, bound = got.double().cpu(), ref.double().cpu(), bound.double().cpu()
+    assert got.shape == ref.shape == bound.shape, (what, got.shape, ref.shape, bound.shape)
+    finite = bool(torch.isfinite(got).all())
+    err = (got - ref).abs()
+    ratio = torch.where(torch.isfinite(err), err / bound.clamp_min(1e-300), torch.full_like(err, float("inf")))
+    worst = float(ratio.max())
+    at = tuple(int(i) for i in torch.unravel_index(ratio.argmax(), ratio.shape))
+    print(f"[bound] {what}: max|err| {float(err[torch.isfinite(err)].max()) if finite else NAN:.3e}  worst err/bound {worst:.3f} at {at}")
+    assert finite, f"{what}: non-finite output"
+    assert worst <= 1.0, f"{what}: worst err/bound {worst:.3f} at {at} (got {float(got[at]):.6g}, ref {float(ref[at]):.6g}, bound {float(bound[at]):.3g})"
+    return worst
+
+
+def gelu_tanh_ref(v):
+    """fp64 GELU, tanh form: 0.5 v (1 + tanh(sqrt(2/pi) (v + 0.044715 v^3)))."""
+    v = v.double()
+    return 0.5 * v * (1.0 + torch.tanh(0.7978845608028654 * (v + 0.044715 * v ** 3)))
+
+
+def gemm_epilogue_ref(a, w, *, bias=None, gelu_from=None, gate=None, alpha=1.0, rowscale=None, res=None, add2=None, rows_per_batch=0,
+                      a_scale=None, w_scale=None):
+    """fp64 rt_gemm_group of CPU tensors holding exactly the values the kernel reads (any dtype; widened here), in the header's order:
+    acc (* a_scale * w_scale) + bias -> GELU-tanh for n >= gelu_from -> gate -> alpha -> rowscale -> + res -> + add2.
+      a [B, M, K], w [N, K], bias [N], gate [B * (M / rows), N] (rows = rows_per_batch or M), rowscale [rows] or [B, rows],
+      res / add2 [B, M, N], a_scale [B * M], w_scale [N].
+    Returns (ref, mag), both fp64 [B, M, N]. mag is the sum of the absolute values of every addend of the element: sum_k |a||w|
+    carried through the same scalings (|a_scale w_scale|, |gate|, |alpha|, |rowscale|; GELU passes it on unchanged), plus |bias|
+    (scaled like the product it is added to), |res| and |add2| — what a rounding error of the evaluation is relative to."""
+    a, w = a.double(), w.double()
+    B, M, K = a.shape
+    N = w.shape[0]
+    v = torch.einsum("bmk,nk->bmn", a, w)
+    mag = torch.einsum("bmk,nk->bmn", a.abs(), w.abs())
+    if a_scale is not None:
+        s = a_scale.double().reshape(B, M, 1)
+        v, mag = v * s, mag * s.abs()
+    if w_scale is not None:
+        s = w_scale.double().reshape(1, 1, N)
+        v, mag = v * s, mag * s.abs()
+    if bias is not None:
+        v, mag = v + bias.double().reshape(1, 1, N), mag + bias.double().abs().reshape(1, 1, N)
+    gf = N if gelu_from is None else max(int(gelu_from), 0)
+    if gf < N:
+        v = torch.cat([v[..., :gf], gelu_tanh_ref(v[..., gf:])], dim=-1)
+    rows = rows_per_batch if rows_per_batch > 0 else M
+    if gate is not None:
+        s = gate.double().reshape(B, M // rows, 1, N).expand(B, M // rows, rows, N).reshape(B, M, N)
+        v, mag = v * s, mag * s.abs()
+    v, mag = v * float(alpha), mag * abs(float(alpha))
+    if rowscale is not None:
+        r = rowscale.double()
+        r = r.reshape(1, rows).expand(B, rows) if r.dim() == 1 else r
+        s = r.reshape(B, 1, rows).expand(B, M // rows, rows).reshape(B, M, 1)
+        v, mag = v * s, mag * s.abs()
+    if res is not None:
+        v, mag = v + res.double(), mag + res.double().abs()
+    if add2 is not None:
+        v, mag = v + add2.double(), mag + add2.double().abs()
+    return v, mag
+
+
+def attention_ref(q, k, v, scale=None):
+    """fp64 softmax(q k^T scale) v of CPU tensors [B, S, H, Dh] holding exactly the values the kernel reads. Returns (ref, pv) as
+    [B, S, H * Dh]: the value and sum_j p_j |v_j| with p the fp64 softmax row — what the bf16 rounding of P (the second product's
+    operand) and of the normaliser is relative to."""
+    q, k, v = q.double(), k.double(), v.double()
+    B, S, H, Dh = q.shape
+    sc = Dh ** -0.5 if scale is None else float(scale)
+    ref, pv = torch.empty(B, S, H, Dh, dtype=F64), torch.empty(B, S, H, Dh, dtype=F64)
+    for b in range(B):
+        for h in range(H):                     # one [S, S] matrix at a time
+            p = torch.softmax(q[b, :, h] @ k[b, :, h].t() * sc, dim=-1)
+            ref[b, :, h], pv[b, :, h] = p @ v[b, :, h], p @ v[b, :, h].abs()
+    return ref.reshape(B, S, H * Dh), pv.reshape(B, S, H * Dh)

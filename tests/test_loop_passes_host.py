@@ -151,3 +151,30 @@ int main(){ printf("%zu %zu %zu %zu %zu %zu %zu\n", sizeof(rt_gemm_group), offse
     assert call(group(rope_wk=0x80008)) == ALIGN
     assert call(group(ldc=1540)) == ALIGN
     assert lib.rt_gemm_fp8(ctypes.pointer(group(K=512)), 1, None) == BADARG
+
+
+def test_gemm_rejects_gelu_from_inside_a_column_group():
+    """The epilogue decides `n >= gelu_from` once per 4-column group of a lane: a first GELU column inside (0, N) that is no multiple
+    of 4 is refused by both entries before anything is queued; <= 0 (all columns), >= N (none) and multiples of 4 are not."""
+    native, lib = _lib()
+
+    def group(**kw):
+        g = native.GemmGroup()
+        g.A, g.W, g.C = 0x10000, 0x20000, 0x30000                     # never dereferenced: every call below is rejected
+        g.M, g.N, g.K, g.batch = 300, 264, 384, 1
+        g.lda = g.ldw = 384
+        g.ldc, g.alpha = 264, 1.0
+        for k, v in kw.items():
+            setattr(g, k, v)
+        return g
+
+    for entry in (lib.rt_gemm_bf16, lib.rt_gemm_fp8):
+        call = lambda g: entry(ctypes.pointer(g), 1, None)
+        assert call(group(gelu_from=130)) == SHAPE
+        assert call(group(gelu_from=1)) == SHAPE
+        assert call(group(gelu_from=263)) == SHAPE
+        # the accepted values must get past this rule: a LATER check stops them (C not 8-byte aligned), the rule itself stops 130
+        assert call(group(gelu_from=130, C=0x30004)) == SHAPE
+        for ok in (-3, 0, 132, 264, 265, 1000):
+            assert call(group(gelu_from=ok, C=0x30004)) == ALIGN, ok
+
