@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import native, ops
+from .ops import _dev, _opt
 from .modules import WeightsIO, _fuse
 
 BF16, F32 = torch.bfloat16, torch.float32
@@ -108,7 +109,7 @@ def _mlp_padded(mlp) -> tuple:
 
 
 def _quick_gelu(hid: torch.Tensor) -> None:
-    native.check("rt_quick_gelu", native.load().rt_quick_gelu(hid.data_ptr(), hid.numel(), _stream()))
+    native.call("rt_quick_gelu", _dev(hid, "hid", BF16), hid.numel(), _stream())
 
 
 def _attention_heads(q, k, v, out, H, bias, scale, T, Tp, scratch):
@@ -116,7 +117,6 @@ def _attention_heads(q, k, v, out, H, bias, scale, T, Tp, scratch):
 
     q, k, v, out: [B, Tp, H*64] bf16 views (row stride = their own ld); bias f32 [Hb, T, T] with Hb in (1, H) or None.
     Tp = T rounded up to 64 (rows/keys >= T are padding: keys masked by writing zero probabilities, rows ignored)."""
-    lib = native.load()
     B = q.shape[0]
     scores, probs, vt = scratch
     for b in range(B):
@@ -124,10 +124,9 @@ def _attention_heads(q, k, v, out, H, bias, scale, T, Tp, scratch):
             qh, kh, vh = q[b, :, h * 64 : (h + 1) * 64], k[b, :, h * 64 : (h + 1) * 64], v[b, :, h * 64 : (h + 1) * 64]
             ops.linear(qh, kh, scores)                                           # [Tp, Tp] f32 = q_h k_hᵀ
             bh = None if bias is None else bias[h if bias.shape[0] > 1 else 0]
-            native.check("rt_softmax_rows_bias", lib.rt_softmax_rows_bias(
-                scores.data_ptr(), Tp, None if bh is None else bh.data_ptr(), 0 if bh is None else bh.stride(0), probs.data_ptr(), Tp,
-                T, T, Tp, float(scale), _stream()))
-            native.check("rt_transpose_bf16", lib.rt_transpose_bf16(vh.data_ptr(), vt.data_ptr(), Tp, 64, vh.stride(0), Tp, _stream()))
+            native.call("rt_softmax_rows_bias", _dev(scores, "scores", F32), Tp, _opt(bh, "bias", F32), 0 if bh is None else bh.stride(0),
+                        _dev(probs, "probs", BF16), Tp, T, T, Tp, float(scale), _stream())
+            native.call("rt_transpose_bf16", _dev(vh, "v", BF16), _dev(vt, "vt", BF16), Tp, 64, vh.stride(0), Tp, _stream())
             ops.linear(probs, vt, out[b, :, h * 64 : (h + 1) * 64])              # [Tp, 64] = P v_h
 
 

@@ -36,7 +36,7 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-MAX_TERMS = 8                      # RT_LORA_MAX_TERMS of include/reptext_hip.h
+from .native import RT_LORA_MAX_TERMS as MAX_TERMS
 DEFAULT_WEIGHT_NAME = "pytorch_lora_weights.safetensors"
 _SUFFIX_A, _SUFFIX_B, _SUFFIX_ALPHA = ".lora_A.weight", ".lora_B.weight", ".alpha"
 

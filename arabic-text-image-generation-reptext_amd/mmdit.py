@@ -572,5 +572,5 @@ def image_rows_bf16(ws: Workspace, rows: Optional[tuple] = None) -> torch.Tensor
         return ws.x[:, T + r0 : T + r1]
     for b in range(ws.B):
         src, dst = ws.x[b, T + r0 : T + r1], ws.xn[b, T + r0 : T + r1]
-        native.check("rt_cast_f32_to_bf16", native.load().rt_cast_f32_to_bf16(src.data_ptr(), dst.data_ptr(), src.numel(), ops._stream()))
+        native.call("rt_cast_f32_to_bf16", ops._dev(src, "x", F32), ops._dev(dst, "xn", BF16), src.numel(), ops._stream())
     return ws.xn[:, T + r0 : T + r1]

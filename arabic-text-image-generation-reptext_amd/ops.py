@@ -53,6 +53,30 @@ def _batched(t: torch.Tensor, name: str):
     return t.shape[0], t.shape[1], t.shape[2], t.stride(1), t.stride(0)
 
 
+def _rows3(t: torch.Tensor, name: str, width: Optional[int] = None, shape=None):
+    """(B, R, D, ld, batch_stride) of a [B,R,D] view with unit inner stride; D == width and t.shape == shape where given."""
+    if t.dim() != 3 or t.stride(2) != 1 or (width is not None and t.shape[2] != width) or (shape is not None and t.shape != shape):
+        want = ",".join(map(str, shape)) if shape is not None else f"B,R,{'D' if width is None else width}"
+        raise ValueError(f"{name}: need a [{want}] view with unit inner stride, got {tuple(t.shape)} / {t.stride()}")
+    return t.shape[0], t.shape[1], t.shape[2], t.stride(1), t.stride(0)
+
+
+def _modulation(shift: Optional[torch.Tensor], scale: Optional[torch.Tensor], B: int, D: int) -> int:
+    """mod_ld of a LayerNorm's shift/scale pair: [B,D] views with unit inner stride and one row stride; 0 without a scale."""
+    if scale is None:
+        return 0
+    if scale.shape != (B, D) or shift.shape != (B, D) or scale.stride(1) != 1 or shift.stride(1) != 1 or scale.stride(0) != shift.stride(0):
+        raise ValueError("shift/scale must be [B,D] views with equal row stride")
+    return scale.stride(0)
+
+
+def _is_f32(x: torch.Tensor, name: str = "x") -> int:
+    """The x_f32 flag of an operand that may be bf16 or f32."""
+    if x.dtype not in (BF16, F32):
+        raise TypeError(f"{name} must be bf16 or f32")
+    return int(x.dtype == F32)
+
+
 @dataclass
 class BlockScales:
     """E8M0 block scales of an e4m3 activation tensor [B, R, D] (one byte per 32 consecutive elements of a row) in rt_gemm_group's
@@ -203,10 +227,8 @@ class LinearProblem:
                 g.c_bscale_k0 = self.out8_scales.k0
         elif self.a_scale is not None or self.w_scale is not None or self.a_bscale is not None or self.out8 is not None:
             raise TypeError("a_scale / w_scale / block scales belong to fp8 problems")
-        if self.out.dtype not in (BF16, F32):
-            raise TypeError("out must be bf16 or f32")
+        g.out_f32 = _is_f32(self.out, "out")
         g.C = _dev(self.out, "out")
-        g.out_f32 = 1 if self.out.dtype == F32 else 0
         g.lda, g.ldw, g.ldc = lda, ldw, ldc
         g.strideA, g.strideC = sA, sC
         g.M, g.N, g.K, g.batch = M, N, K, Bt
@@ -269,10 +291,7 @@ def linear_grouped(problems: Sequence[LinearProblem]) -> None:
     fp8 = problems[0].is_fp8
     if any(p.is_fp8 != fp8 for p in problems):
         raise TypeError("all problems of one launch must have the same operand dtype")
-    if fp8:
-        native.check("rt_gemm_fp8", native.load().rt_gemm_fp8(arr, n, _stream()))
-    else:
-        native.check("rt_gemm_bf16", native.load().rt_gemm_bf16(arr, n, _stream()))
+    native.call("rt_gemm_fp8" if fp8 else "rt_gemm_bf16", arr, n, _stream())
 
 
 def linear(a, w, out, **kw) -> torch.Tensor:
@@ -297,7 +316,7 @@ def linear_skinny(hi: torch.Tensor, lo: torch.Tensor, problems: Sequence[tuple])
             raise ValueError(f"linear_skinny shapes mismatch: hi{tuple(hi.shape)} w{tuple(w.shape)} out{tuple(out.shape)}")
         g.W, g.bias, g.C = _dev(w, "w", BF16), _opt(bias, "bias", BF16), _dev(out, "out", F32)
         g.ldw, g.ldc, g.N = ldw, ldc, N
-    native.check("rt_gemm_skinny_bf16", native.load().rt_gemm_skinny_bf16(_dev(hi, "hi", BF16), _dev(lo, "lo", BF16), lda, M, K, arr, n, _stream()))
+    native.call("rt_gemm_skinny_bf16", _dev(hi, "hi", BF16), _dev(lo, "lo", BF16), lda, M, K, arr, n, _stream())
 
 
 def add_rows_(y: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -306,7 +325,7 @@ def add_rows_(y: torch.Tensor, a: torch.Tensor, b: Optional[torch.Tensor] = None
     B = a.shape[0]
     if not y.is_contiguous() or not a.is_contiguous() or a.shape[1] != D or (b is not None and (b.shape != a.shape or not b.is_contiguous())):
         raise ValueError("add_rows_: y [rows,D], a / b [B,D], contiguous")
-    native.check("rt_add_rows_f32", native.load().rt_add_rows_f32(_dev(y, "y", F32), _dev(a, "a", F32), _opt(b, "b", F32), rows, B, D, _stream()))
+    native.call("rt_add_rows_f32", _dev(y, "y", F32), _dev(a, "a", F32), _opt(b, "b", F32), rows, B, D, _stream())
     return y
 
 
@@ -318,20 +337,18 @@ def gemv(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: to
     Bo, No, ldy = _rowmajor2d(out, "out")
     if Kw != K or Bo != B or No != N:
         raise ValueError("gemv shapes mismatch")
-    lib = native.load()
     step = max(1, min(8, 16384 // K))      # rt_gemv_bf16w: at most 8 rows and 64 KiB of staged fp32 activations per launch; rows are independent
     for b0 in range(0, B, step):
         nb = min(step, B - b0)
-        native.check("rt_gemv_bf16w", lib.rt_gemv_bf16w(
-            _dev(x, "x", F32) + b0 * ldx * 4, ldx, _dev(w, "w", BF16), ldw, _opt(bias, "bias", BF16),
-            _dev(out, "out", F32) + b0 * ldy * 4, ldy, nb, N, K, int(silu_in), int(silu_out), int(accumulate), _stream()))
+        native.call("rt_gemv_bf16w", _dev(x, "x", F32) + b0 * ldx * 4, ldx, _dev(w, "w", BF16), ldw, _opt(bias, "bias", BF16),
+                    _dev(out, "out", F32) + b0 * ldy * 4, ldy, nb, N, K, int(silu_in), int(silu_out), int(accumulate), _stream())
     return out
 
 
 def timestep_embedding(t: torch.Tensor, dim: int = 256) -> torch.Tensor:
     t = t.contiguous()
     out = torch.empty(t.numel(), dim, device=t.device, dtype=F32)
-    native.check("rt_timestep_embedding", native.load().rt_timestep_embedding(_dev(t, "t", F32), out.data_ptr(), t.numel(), dim, _stream()))
+    native.call("rt_timestep_embedding", _dev(t, "t", F32), out.data_ptr(), t.numel(), dim, _stream())
     return out
 
 
@@ -342,26 +359,18 @@ def rope_table(ids: torch.Tensor, axes_dim=(16, 56, 56), theta: float = 10000.0)
     cos = torch.empty(S, D, device=ids.device, dtype=F32)
     sin = torch.empty(S, D, device=ids.device, dtype=F32)
     ax = (C.c_int32 * 3)(*[int(a) for a in axes_dim])
-    native.check("rt_rope_table", native.load().rt_rope_table(_dev(ids, "ids", F32), cos.data_ptr(), sin.data_ptr(), S, ax, float(theta), _stream()))
+    native.call("rt_rope_table", _dev(ids, "ids", F32), cos.data_ptr(), sin.data_ptr(), S, ax, float(theta), _stream())
     return cos, sin
 
 
 def layernorm_modulate(x: torch.Tensor, out: torch.Tensor, shift: Optional[torch.Tensor], scale: Optional[torch.Tensor],
                        eps: float = 1e-6) -> torch.Tensor:
     """x [B,R,D] (bf16|f32, unit inner stride) -> out [B,R,D] bf16 = LN(x)*(1+scale[b])+shift[b]; shift/scale f32 [B,D] views."""
-    if x.dim() != 3 or out.dim() != 3 or x.shape != out.shape or x.stride(2) != 1 or out.stride(2) != 1:
-        raise ValueError("layernorm_modulate: x/out must be [B,R,D] with unit inner stride")
-    B, R, D = x.shape
-    mod_ld = 0
-    if scale is not None:
-        if scale.shape != (B, D) or shift.shape != (B, D) or scale.stride(1) != 1 or shift.stride(1) != 1 or scale.stride(0) != shift.stride(0):
-            raise ValueError("shift/scale must be [B,D] views with equal row stride")
-        mod_ld = scale.stride(0)
-    if x.dtype not in (BF16, F32):
-        raise TypeError("x must be bf16 or f32")
-    native.check("rt_layernorm_modulate", native.load().rt_layernorm_modulate(
-        _dev(x, "x"), x.stride(1), x.stride(0), int(x.dtype == F32), _dev(out, "out", BF16), out.stride(1), out.stride(0),
-        _opt(shift, "shift", F32), _opt(scale, "scale", F32), mod_ld, B, R, D, float(eps), _stream()))
+    B, R, D, ldx, sxb = _rows3(x, "x")
+    _, _, _, ldo, sob = _rows3(out, "out", shape=x.shape)
+    mod_ld, x_f32 = _modulation(shift, scale, B, D), _is_f32(x)
+    native.call("rt_layernorm_modulate", _dev(x, "x"), ldx, sxb, x_f32, _dev(out, "out", BF16), ldo, sob,
+                _opt(shift, "shift", F32), _opt(scale, "scale", F32), mod_ld, B, R, D, float(eps), _stream())
     return out
 
 
@@ -369,92 +378,66 @@ def layernorm_modulate_pair(x0, out0, shift0, scale0, x1, out1, shift1, scale1, 
     """layernorm_modulate(x0, out0, shift0, scale0) and layernorm_modulate(x1, out1, shift1, scale1) as ONE launch (the image rows and
     the text rows of a double block): same dtype of x and same D, everything else per segment. Bit-identical to the two calls."""
     segs = (native.LnSegment * 2)()
-    D = x0.shape[2]
+    D, x_f32 = x0.shape[2], _is_f32(x0)
     for g, (x, out, shift, scale) in zip(segs, ((x0, out0, shift0, scale0), (x1, out1, shift1, scale1))):
-        if x.dim() != 3 or out.dim() != 3 or x.shape != out.shape or x.stride(2) != 1 or out.stride(2) != 1 or x.shape[2] != D or x.dtype != x0.dtype:
-            raise ValueError("layernorm_modulate_pair: x/out must be [B,R,D] with unit inner stride, one D and one dtype of x")
-        B, R, _ = x.shape
-        if scale is not None:
-            if scale.shape != (B, D) or shift.shape != (B, D) or scale.stride(1) != 1 or shift.stride(1) != 1 or scale.stride(0) != shift.stride(0):
-                raise ValueError("shift/scale must be [B,D] views with equal row stride")
-            g.mod_ld = scale.stride(0)
+        g.batch, g.rows_per_batch, _, g.ldx, g.stride_xb = _rows3(x, "x", width=D)
+        _, _, _, g.ldo, g.stride_ob = _rows3(out, "out", shape=x.shape)
+        if x.dtype != x0.dtype:
+            raise ValueError("layernorm_modulate_pair: the two segments must have one dtype of x")
+        g.mod_ld = _modulation(shift, scale, g.batch, D)
         g.x, g.out, g.shift, g.scale = _dev(x, "x"), _dev(out, "out", BF16), _opt(shift, "shift", F32), _opt(scale, "scale", F32)
-        g.ldx, g.stride_xb, g.ldo, g.stride_ob, g.batch, g.rows_per_batch = x.stride(1), x.stride(0), out.stride(1), out.stride(0), B, R
-    if x0.dtype not in (BF16, F32):
-        raise TypeError("x must be bf16 or f32")
-    native.check("rt_layernorm_modulate_pair", native.load().rt_layernorm_modulate_pair(segs, int(x0.dtype == F32), D, float(eps), _stream()))
+    native.call("rt_layernorm_modulate_pair", segs, x_f32, D, float(eps), _stream())
 
 
 def layernorm_modulate_fp8(x: torch.Tensor, out: torch.Tensor, row_scale: torch.Tensor, shift: Optional[torch.Tensor],
                            scale: Optional[torch.Tensor], eps: float = 1e-6) -> torch.Tensor:
     """As layernorm_modulate, quantising each modulated row to e4m3: out [B,R,D] float8_e4m3fn, row_scale f32 [B*R] contiguous
     (row b*R + r) — the A operand and a_scale of an fp8 LinearProblem."""
-    if x.dim() != 3 or out.dim() != 3 or x.shape != out.shape or x.stride(2) != 1 or out.stride(2) != 1:
-        raise ValueError("layernorm_modulate_fp8: x/out must be [B,R,D] with unit inner stride")
-    B, R, D = x.shape
+    B, R, D, ldx, sxb = _rows3(x, "x")
+    _, _, _, ldo, sob = _rows3(out, "out", shape=x.shape)
     if row_scale.numel() != B * R or not row_scale.is_contiguous():
         raise ValueError("row_scale must be contiguous with B*R elements")
-    mod_ld = 0
-    if scale is not None:
-        if scale.shape != (B, D) or shift.shape != (B, D) or scale.stride(1) != 1 or shift.stride(1) != 1 or scale.stride(0) != shift.stride(0):
-            raise ValueError("shift/scale must be [B,D] views with equal row stride")
-        mod_ld = scale.stride(0)
-    if x.dtype not in (BF16, F32):
-        raise TypeError("x must be bf16 or f32")
-    native.check("rt_layernorm_modulate_fp8", native.load().rt_layernorm_modulate_fp8(
-        _dev(x, "x"), x.stride(1), x.stride(0), int(x.dtype == F32), _dev(out, "out", FP8), out.stride(1), out.stride(0),
-        _dev(row_scale, "row_scale", F32), _opt(shift, "shift", F32), _opt(scale, "scale", F32), mod_ld, B, R, D, float(eps), _stream()))
+    mod_ld, x_f32 = _modulation(shift, scale, B, D), _is_f32(x)
+    native.call("rt_layernorm_modulate_fp8", _dev(x, "x"), ldx, sxb, x_f32, _dev(out, "out", FP8), ldo, sob,
+                _dev(row_scale, "row_scale", F32), _opt(shift, "shift", F32), _opt(scale, "scale", F32), mod_ld, B, R, D, float(eps), _stream())
     return out
 
 
 def quantize_rows_fp8(x: torch.Tensor):
     """x [rows, D] bf16|f32 (unit inner stride) -> (e4m3 [rows, D], scale f32 [rows]) with x ≈ q * scale[:, None]."""
     rows, D, ldx = _rowmajor2d(x, "x")
-    if x.dtype not in (BF16, F32):
-        raise TypeError("x must be bf16 or f32")
+    x_f32 = _is_f32(x)
     q = torch.empty(rows, D, device=x.device, dtype=FP8)
     sc = torch.empty(rows, device=x.device, dtype=F32)
-    native.check("rt_quantize_rows_fp8", native.load().rt_quantize_rows_fp8(
-        _dev(x, "x"), ldx, int(x.dtype == F32), q.data_ptr(), D, sc.data_ptr(), rows, D, _stream()))
+    native.call("rt_quantize_rows_fp8", _dev(x, "x"), ldx, x_f32, q.data_ptr(), D, sc.data_ptr(), rows, D, _stream())
     return q, sc
 
 
 def quantize_rows_fp8_into(x: torch.Tensor, out: torch.Tensor, scale: torch.Tensor) -> None:
     """x [B,R,D] bf16|f32 view (unit inner stride, any row / batch stride) -> out [B,R,D] e4m3 view, scale f32 [B*R] contiguous
     (row b*R + r): the A operand and a_scale of an fp8 LinearProblem for activations that do not come out of a LayerNorm."""
-    if x.dim() != 3 or out.dim() != 3 or x.shape != out.shape or x.stride(2) != 1 or out.stride(2) != 1:
-        raise ValueError("quantize_rows_fp8_into: x/out must be [B,R,D] views with unit inner stride")
-    B, R, D = x.shape
+    B, R, D, ldx, sxb = _rows3(x, "x")
+    _, _, _, ldo, sob = _rows3(out, "out", shape=x.shape)
     if scale.numel() != B * R or not scale.is_contiguous():
         raise ValueError("scale must be contiguous with B*R elements")
-    if x.dtype not in (BF16, F32):
-        raise TypeError("x must be bf16 or f32")
-    lib, st = native.load(), _stream()
-    esz = x.element_size()
-    _dev(out, "out", FP8), _dev(scale, "scale", F32), _dev(x, "x")
+    x_f32, esz, st = _is_f32(x), x.element_size(), _stream()
+    po, ps, px = _dev(out, "out", FP8), _dev(scale, "scale", F32), _dev(x, "x")
     for b in range(B):
-        native.check("rt_quantize_rows_fp8", lib.rt_quantize_rows_fp8(
-            x.data_ptr() + b * x.stride(0) * esz, x.stride(1), int(x.dtype == F32), out.data_ptr() + b * out.stride(0), out.stride(1),
-            scale.data_ptr() + b * R * 4, R, D, st))
+        native.call("rt_quantize_rows_fp8", px + b * sxb * esz, ldx, x_f32, po + b * sob, ldo, ps + b * R * 4, R, D, st)
 
 
 def quantize_mx_fp8_into(x: torch.Tensor, out: torch.Tensor, scales: BlockScales) -> None:
     """x [B,R,D] bf16|f32 view -> out [B,R,D] e4m3 view + E8M0 block scales (one per 32 elements, rt_quantize_mx_fp8): the A operand
     and a_bscale of an fp8 LinearProblem for tensors no fused producer writes."""
-    if x.dim() != 3 or out.dim() != 3 or x.shape != out.shape or x.stride(2) != 1 or out.stride(2) != 1:
-        raise ValueError("quantize_mx_fp8_into: x/out must be [B,R,D] views with unit inner stride")
-    B, R, D = x.shape
-    if x.dtype not in (BF16, F32):
-        raise TypeError("x must be bf16 or f32")
+    B, R, D, ldx, sxb = _rows3(x, "x")
+    _, _, _, ldo, sob = _rows3(out, "out", shape=x.shape)
+    x_f32, esz, st = _is_f32(x), x.element_size(), _stream()
     if D % 256 or scales.k0 != 0 or scales.columns_left() < D:
         raise ValueError("D % 256 == 0, written from column 0 of a scale tensor that covers D")
-    lib, st = native.load(), _stream()
-    esz = x.element_size()
-    _dev(out, "out", FP8), _dev(x, "x")
+    po, px = _dev(out, "out", FP8), _dev(x, "x")
     for b in range(B):
-        native.check("rt_quantize_mx_fp8", lib.rt_quantize_mx_fp8(
-            x.data_ptr() + b * x.stride(0) * esz, x.stride(1), int(x.dtype == F32), out.data_ptr() + b * out.stride(0), out.stride(1),
-            scales.ptr() + b * (scales.R // 64) * 2048, scales.plane, R, D, st))
+        native.call("rt_quantize_mx_fp8", px + b * sxb * esz, ldx, x_f32, po + b * sob, ldo,
+                    scales.ptr() + b * (scales.R // 64) * 2048, scales.plane, R, D, st)
 
 
 def dequantize_mx(q: torch.Tensor, scales: BlockScales) -> torch.Tensor:
@@ -486,21 +469,18 @@ def lora_merge_(w: torch.Tensor, w0: torch.Tensor, terms: Sequence[tuple]) -> to
         if b.device != w.device or at.device != w.device:
             raise RuntimeError("lora_merge_: factors and weight must be on the same device")
         arr[t] = native.LoraTerm(_dev(b, "B", BF16), _dev(at, "At", BF16), ldb, lda, r_pad, float(c))
-    native.check("rt_lora_merge_bf16", native.load().rt_lora_merge_bf16(arr, len(terms), p0, ld0, pw, ldw, N, K, _stream()))
+    native.call("rt_lora_merge_bf16", arr, len(terms), p0, ld0, pw, ldw, N, K, _stream())
     return w
 
 
 def qk_rmsnorm_rope(buf: torch.Tensor, q_off: int, k_off: int, H: int, T: int, wq_txt, wk_txt, wq_img, wk_img,
                     cos: torch.Tensor, sin: torch.Tensor, eps: float = 1e-6) -> None:
     """In place on buf [B,S,ld] bf16: heads at columns q_off + h*128 / k_off + h*128."""
-    if buf.dim() != 3 or buf.stride(2) != 1:
-        raise ValueError("buf must be [B,S,ld] with unit inner stride")
-    B, S, _ = buf.shape
+    B, S, _, ld, sb = _rows3(buf, "buf")
     if cos.shape != (S, 128) or sin.shape != (S, 128) or not cos.is_contiguous() or not sin.is_contiguous():
         raise ValueError("cos/sin must be contiguous [S,128]")
-    native.check("rt_qk_rmsnorm_rope", native.load().rt_qk_rmsnorm_rope(
-        _dev(buf, "buf", BF16), buf.stride(1), buf.stride(0), q_off, k_off, _opt(wq_txt, "wq_txt", BF16), _opt(wk_txt, "wk_txt", BF16),
-        _dev(wq_img, "wq_img", BF16), _dev(wk_img, "wk_img", BF16), _dev(cos, "cos", F32), _dev(sin, "sin", F32), B, S, T, H, float(eps), _stream()))
+    native.call("rt_qk_rmsnorm_rope", _dev(buf, "buf", BF16), ld, sb, q_off, k_off, _opt(wq_txt, "wq_txt", BF16), _opt(wk_txt, "wk_txt", BF16),
+                _dev(wq_img, "wq_img", BF16), _dev(wk_img, "wk_img", BF16), _dev(cos, "cos", F32), _dev(sin, "sin", F32), B, S, T, H, float(eps), _stream())
 
 
 _ATTN_WS = {}
@@ -537,18 +517,14 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     128-row block as one full-length workgroup (no key-split tail; A/B and tests). ``rows`` = (r0, r1): only the items of the launch that
     hold a query row of [r0, r1) do any work (rt_attention_fwd_rows): those rows of out get the bits the whole launch gives them, the
     other rows of the touched items are written too, the rest of out is left as it is."""
-    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
-        if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] != H * 128:
-            raise ValueError(f"{name}: need [B,S,{H*128}] with unit inner stride")
-    B, S, _ = q.shape
+    (B, S, _, ld, sb), _, _, (_, _, _, ldo, sob) = [_rows3(t, name, width=H * 128) for name, t in (("q", q), ("k", k), ("v", v), ("out", out))]
     if not (q.stride() == k.stride() == v.stride()) or k.shape != q.shape or v.shape != q.shape or out.shape != q.shape:
         raise ValueError("q,k,v must share shape and strides")
     sc = (128 ** -0.5) if scale is None else float(scale)
     ws = _attention_workspace(B, S, H, q.device) if split else None
     r0, r1 = (0, S) if rows is None else (int(rows[0]), int(rows[1]))
-    native.check("rt_attention_fwd_rows", native.load().rt_attention_fwd_rows(
-        _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(out, "out", BF16), q.stride(1), q.stride(0),
-        out.stride(1), out.stride(0), B, S, H, sc, r0, r1, None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), _stream()))
+    native.call("rt_attention_fwd_rows", _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(out, "out", BF16), ld, sb,
+                ldo, sob, B, S, H, sc, r0, r1, None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), _stream())
     return out
 
 
@@ -557,27 +533,9 @@ def ip_attention(q: torch.Tensor, wq: torch.Tensor, k: torch.Tensor, v: torch.Te
     """out (+)= ip_scale · softmax(bf16(rmsnorm(q)·wq) Kᵀ · scale) V (rt_ip_attention): the IP-Adapter term of a double block.
     q [B,N,H·128] bf16 view of the RAW query projection (unit inner stride, e.g. columns :d of the fused q|k|v buffer; not modified);
     wq bf16 [128] (norm_q.weight); k, v [B or 1, n, H·128] bf16 views sharing strides, 1 <= n <= 128 (batch 1: one image prompt for
-    every batch entry); out [B,N,H·128] bf16 or f32 view."""
-    d = H * 128
-    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
-        if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] != d:
-            raise ValueError(f"{name}: need [B,rows,{d}] with unit inner stride, got {tuple(t.shape)} / {t.stride()}")
-    B, N, _ = q.shape
-    if out.shape != q.shape or out.dtype not in (BF16, F32):
-        raise ValueError("out must match q in shape and be bf16 or f32")
-    if k.shape != v.shape or k.stride() != v.stride() or k.shape[0] not in (1, B):
-        raise ValueError("k and v must share shape and strides, with batch 1 or B")
-    n = k.shape[1]
-    if not 1 <= n <= 128:
-        raise ValueError(f"ip_attention: 1..128 image-prompt tokens, got {n}")
-    if wq.numel() != 128 or not wq.is_contiguous():
-        raise ValueError("wq must be contiguous with 128 elements")
-    sc = (128 ** -0.5) if scale is None else float(scale)
-    native.check("rt_ip_attention", native.load().rt_ip_attention(
-        _dev(q, "q", BF16), q.stride(1), q.stride(0), _dev(wq, "wq", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), k.stride(1),
-        k.stride(0) if k.shape[0] == B and B > 1 else 0, _dev(out, "out"), out.stride(1), out.stride(0), int(out.dtype == F32),
-        int(accumulate), B, N, H, n, sc, float(ip_scale), float(eps), _stream()))
-    return out
+    every batch entry); out [B,N,H·128] bf16 or f32 view. The launch is ip_attention_gated's without a gate, to which the C entry
+    rt_ip_attention itself forwards."""
+    return ip_attention_gated(q, wq, k, v, out, H, ip_scale, None, accumulate, scale, eps)
 
 
 def ip_attention_gated(q: torch.Tensor, wq: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, ip_scale: float = 1.0,
@@ -586,15 +544,11 @@ def ip_attention_gated(q: torch.Tensor, wq: torch.Tensor, k: torch.Tensor, v: to
     fp32 column gate [B, H·128] (a view with unit inner stride and any batch stride, e.g. the gate_msa chunk of the modulation table).
     q may be any [B,rows,H·128] view (a single block: columns 2d:3d of the fused [k|v|q|mlp] buffer, all S rows); k as given."""
     d = H * 128
-    for name, t in (("q", q), ("k", k), ("v", v), ("out", out)):
-        if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] != d:
-            raise ValueError(f"{name}: need [B,rows,{d}] with unit inner stride, got {tuple(t.shape)} / {t.stride()}")
-    B, N, _ = q.shape
+    (B, N, _, ldq, sqb), (Bk, n, _, ldkv, skvb), _, (_, _, _, ldo, sob) = [_rows3(t, name, width=d) for name, t in (("q", q), ("k", k), ("v", v), ("out", out))]
     if out.shape != q.shape or out.dtype not in (BF16, F32):
         raise ValueError("out must match q in shape and be bf16 or f32")
-    if k.shape != v.shape or k.stride() != v.stride() or k.shape[0] not in (1, B):
+    if k.shape != v.shape or k.stride() != v.stride() or Bk not in (1, B):
         raise ValueError("k and v must share shape and strides, with batch 1 or B")
-    n = k.shape[1]
     if not 1 <= n <= 128:
         raise ValueError(f"ip_attention_gated: 1..128 image-prompt tokens, got {n}")
     if wq.numel() != 128 or not wq.is_contiguous():
@@ -602,10 +556,9 @@ def ip_attention_gated(q: torch.Tensor, wq: torch.Tensor, k: torch.Tensor, v: to
     if gate is not None and (gate.dim() != 2 or gate.shape != (B, d) or gate.stride(1) != 1):
         raise ValueError(f"gate must be a [B,{d}] view with unit inner stride")
     sc = (128 ** -0.5) if scale is None else float(scale)
-    native.check("rt_ip_attention_gated", native.load().rt_ip_attention_gated(
-        _dev(q, "q", BF16), q.stride(1), q.stride(0), _dev(wq, "wq", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), k.stride(1),
-        k.stride(0) if k.shape[0] == B and B > 1 else 0, _opt(gate, "gate", F32), 0 if gate is None else gate.stride(0),
-        _dev(out, "out"), out.stride(1), out.stride(0), int(out.dtype == F32), int(accumulate), B, N, H, n, sc, float(ip_scale), float(eps), _stream()))
+    native.call("rt_ip_attention_gated", _dev(q, "q", BF16), ldq, sqb, _dev(wq, "wq", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), ldkv,
+                skvb if Bk == B and B > 1 else 0, _opt(gate, "gate", F32), 0 if gate is None else gate.stride(0),
+                _dev(out, "out"), ldo, sob, int(out.dtype == F32), int(accumulate), B, N, H, n, sc, float(ip_scale), float(eps), _stream())
     return out
 
 
@@ -614,17 +567,15 @@ def gelu_erf(x: torch.Tensor) -> torch.Tensor:
     if not x.is_contiguous():
         raise ValueError("gelu_erf: contiguous input")
     out = torch.empty(x.shape, device=x.device, dtype=BF16)
-    native.check("rt_gelu_erf_bf16", native.load().rt_gelu_erf_bf16(_dev(x, "x", F32), out.data_ptr(), x.numel(), _stream()))
+    native.call("rt_gelu_erf_bf16", _dev(x, "x", F32), out.data_ptr(), x.numel(), _stream())
     return out
 
 
 def add_bf16_(y: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     """y = bf16(y + x) in place on [B,R,D] bf16 views with unit inner stride and any row / batch strides (rt_add_bf16_2d)."""
-    if x.shape != y.shape or x.dim() != 3 or x.stride(2) != 1 or y.stride(2) != 1:
-        raise ValueError("add_bf16_: [B,R,D] views of equal shape with unit inner stride")
-    B, R, D = x.shape
-    native.check("rt_add_bf16_2d", native.load().rt_add_bf16_2d(_dev(x, "x", BF16), x.stride(1), x.stride(0), _dev(y, "y", BF16), y.stride(1),
-                                                                y.stride(0), B, R, D, _stream()))
+    B, R, D, ldx, sxb = _rows3(x, "x")
+    _, _, _, ldy, syb = _rows3(y, "y", shape=x.shape)
+    native.call("rt_add_bf16_2d", _dev(x, "x", BF16), ldx, sxb, _dev(y, "y", BF16), ldy, syb, B, R, D, _stream())
     return y
 
 
@@ -633,8 +584,8 @@ def rmsnorm_heads_(x: torch.Tensor, out: torch.Tensor, ones: torch.Tensor, eps: 
     multiplies exactly): x contiguous f32, out contiguous bf16 of the same shape, numel % 128 == 0."""
     if x.shape != out.shape or not x.is_contiguous() or not out.is_contiguous() or x.numel() % 128 or ones.numel() != 128:
         raise ValueError("rmsnorm_heads_: contiguous tensors of equal shape, a multiple of 128 elements")
-    native.check("rt_rmsnorm_rows", native.load().rt_rmsnorm_rows(_dev(x, "x", F32), 128, 1, _dev(ones, "ones", BF16), _dev(out, "out", BF16), 128,
-                                                                  x.numel() // 128, 128, float(eps), _stream()))
+    native.call("rt_rmsnorm_rows", _dev(x, "x", F32), 128, 1, _dev(ones, "ones", BF16), _dev(out, "out", BF16), 128,
+                x.numel() // 128, 128, float(eps), _stream())
     return out
 
 
@@ -643,30 +594,23 @@ def _attention_small_head(hd: int, entry: str, max_s: int, q: torch.Tensor, k: t
     """The body of attention_hd64 / attention_hd72 (csrc/attention_small_head.hip): head dim, entry point and row bound. 64 keeps its
     stricter rule — q, k and v are views of one buffer sharing shape and strides — which its entry point's shorter argument list assumes."""
     d = H * hd
-    for tn, t in (("q", q), ("k", k), ("v", v), ("out", out)):
-        if t.dim() != 3 or t.stride(2) != 1 or t.shape[2] != d:
-            raise ValueError(f"{tn}: need [B,S,{d}] with unit inner stride, got {tuple(t.shape)} / {t.stride()}")
-    B, Sk, _ = k.shape
-    Sq = q.shape[1]
+    (Bq, Sq, _, ldq, sqb), (B, Sk, _, ldkv, skvb), _, (_, _, _, ldo, sob) = [_rows3(t, name, width=d) for name, t in (("q", q), ("k", k), ("v", v), ("out", out))]
     sc = float(scale if scale is not None else (64 ** -0.5 if hd == 64 else 72 ** -0.5))      # literals: folded when compiled
     if hd == 64:
         if not (q.stride() == k.stride() == v.stride()) or k.shape != q.shape or v.shape != q.shape or out.shape != q.shape:
             raise ValueError("q,k,v must share shape and strides; out must have their shape")
         if not 1 <= Sq <= max_s:
             raise ValueError(f"{entry[3:]}: 1..{max_s} rows, got {Sq}")
-        code = native.load().rt_attention_hd64(_dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), q.stride(1), q.stride(0),
-                                               _dev(out, "out", BF16), out.stride(1), out.stride(0), B, Sq, H, sc, _stream())
+        native.call(entry, _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), ldq, sqb, _dev(out, "out", BF16), ldo, sob, B, Sq, H, sc, _stream())
     else:
         if k.stride() != v.stride() or v.shape != k.shape:
             raise ValueError("k,v must share shape and strides")
-        if q.shape[0] not in (1, B) or out.shape != (B, Sq, d):
+        if Bq not in (1, B) or out.shape != (B, Sq, d):
             raise ValueError(f"q must be [{B} or 1, Sq, {d}] and out [{B}, Sq, {d}], got {tuple(q.shape)} and {tuple(out.shape)}")
         if not (1 <= Sq <= max_s and 1 <= Sk <= max_s):
             raise ValueError(f"{entry[3:]}: 1..{max_s} rows, got {Sq} queries and {Sk} keys")
-        code = native.load().rt_attention_hd72(_dev(q, "q", BF16), q.stride(1), q.stride(0) if q.shape[0] == B and B > 1 else 0, _dev(k, "k", BF16),
-                                               _dev(v, "v", BF16), k.stride(1), k.stride(0), _dev(out, "out", BF16), out.stride(1), out.stride(0), B,
-                                               Sq, Sk, H, sc, _stream())
-    native.check(entry, code)
+        native.call(entry, _dev(q, "q", BF16), ldq, sqb if Bq == B and B > 1 else 0, _dev(k, "k", BF16), _dev(v, "v", BF16), ldkv, skvb,
+                    _dev(out, "out", BF16), ldo, sob, B, Sq, Sk, H, sc, _stream())
     return out
 
 
@@ -693,7 +637,7 @@ def patchify_nchw(x: torch.Tensor, patch: int, Kp: Optional[int] = None) -> torc
     B, G = x.shape[0], x.shape[2] // patch
     Kp = (3 * patch * patch + 63) // 64 * 64 if Kp is None else int(Kp)
     out = torch.empty(B, G * G, Kp, device=x.device, dtype=BF16)
-    native.check("rt_patchify_nchw", native.load().rt_patchify_nchw(_dev(x, "x"), int(x.dtype == F32), out.data_ptr(), B, G, patch, Kp, _stream()))
+    native.call("rt_patchify_nchw", _dev(x, "x"), int(x.dtype == F32), out.data_ptr(), B, G, patch, Kp, _stream())
     return out
 
 
@@ -701,28 +645,24 @@ def attention_fp8_prep(buf: torch.Tensor, q_off: int, k_off: int, v_off: int, H:
                        cos: torch.Tensor, sin: torch.Tensor, qk8: torch.Tensor, vt8: torch.Tensor, eps: float = 1e-6) -> None:
     """From the fused projection buffer buf [B,S,ld] bf16 (not modified): qk8 [B,S,2·H·128] e4m3 = 16 · RoPE(RMSNorm(q | k)),
     vt8 flat e4m3 of rt_attention_fp8_vt_bytes(B,S,H) bytes = Vᵀ per (batch, head), keys in MFMA operand order."""
-    if buf.dim() != 3 or buf.stride(2) != 1:
-        raise ValueError("buf must be [B,S,ld] with unit inner stride")
-    B, S, _ = buf.shape
+    B, S, _, ld, sb = _rows3(buf, "buf")
     if cos.shape != (S, 128) or sin.shape != (S, 128) or not cos.is_contiguous() or not sin.is_contiguous():
         raise ValueError("cos/sin must be contiguous [S,128]")
-    lib = native.load()
-    if qk8.shape != (B, S, 2 * H * 128) or not qk8.is_contiguous() or vt8.numel() < int(lib.rt_attention_fp8_vt_bytes(B, S, H)):
+    if qk8.shape != (B, S, 2 * H * 128) or not qk8.is_contiguous() or vt8.numel() < int(native.load().rt_attention_fp8_vt_bytes(B, S, H)):
         raise ValueError("qk8 must be contiguous [B,S,2*H*128]; vt8 must hold rt_attention_fp8_vt_bytes(B,S,H) bytes")
-    native.check("rt_attention_fp8_prep", lib.rt_attention_fp8_prep(
-        _dev(buf, "buf", BF16), buf.stride(1), buf.stride(0), q_off, k_off, v_off, _opt(wq_txt, "wq_txt", BF16), _opt(wk_txt, "wk_txt", BF16),
-        _dev(wq_img, "wq_img", BF16), _dev(wk_img, "wk_img", BF16), _dev(cos, "cos", F32), _dev(sin, "sin", F32),
-        _dev(qk8, "qk8", FP8), _dev(vt8, "vt8", FP8), B, S, T, H, float(eps), _stream()))
+    native.call("rt_attention_fp8_prep", _dev(buf, "buf", BF16), ld, sb, q_off, k_off, v_off, _opt(wq_txt, "wq_txt", BF16), _opt(wk_txt, "wk_txt", BF16),
+                _dev(wq_img, "wq_img", BF16), _dev(wk_img, "wk_img", BF16), _dev(cos, "cos", F32), _dev(sin, "sin", F32),
+                _dev(qk8, "qk8", FP8), _dev(vt8, "vt8", FP8), B, S, T, H, float(eps), _stream())
 
 
 def attention_fp8(qk8: torch.Tensor, vt8: torch.Tensor, out: torch.Tensor, H: int, scale: Optional[float] = None) -> torch.Tensor:
     """softmax(q kᵀ · scale) v from attention_fp8_prep's buffers -> out [B,S,>=H*128] bf16 view (unit inner stride)."""
     B, S, _ = qk8.shape
-    if out.dim() != 3 or out.shape[0] != B or out.shape[1] != S or out.stride(2) != 1:
-        raise ValueError("out must be [B,S,*] with unit inner stride")
-    native.check("rt_attention_fp8_fwd", native.load().rt_attention_fp8_fwd(
-        _dev(qk8, "qk8", FP8), _dev(vt8, "vt8", FP8), _dev(out, "out", BF16), out.stride(1), out.stride(0), B, S, H,
-        float(scale if scale is not None else 128 ** -0.5), _stream()))
+    Bo, So, _, ldo, sob = _rows3(out, "out")
+    if (Bo, So) != (B, S):
+        raise ValueError("out must be [B,S,*] with qk8's B and S")
+    native.call("rt_attention_fp8_fwd", _dev(qk8, "qk8", FP8), _dev(vt8, "vt8", FP8), _dev(out, "out", BF16), ldo, sob, B, S, H,
+                float(scale if scale is not None else 128 ** -0.5), _stream())
     return out
 
 
@@ -730,20 +670,20 @@ def attention_fp8_mx(qk8: torch.Tensor, vt8: torch.Tensor, out8: torch.Tensor, s
     """attention_fp8 with the output as e4m3 + E8M0 block scales (rt_attention_fp8_fwd_mx): out8 [B,S,>=H*128] e4m3 view, head h at
     columns h*128.. of the view; ``scales`` addresses the same view."""
     B, S, _ = qk8.shape
-    if out8.dim() != 3 or out8.shape[0] != B or out8.shape[1] != S or out8.stride(2) != 1:
-        raise ValueError("out8 must be [B,S,*] with unit inner stride")
+    Bo, So, _, ldo, sob = _rows3(out8, "out8")
+    if (Bo, So) != (B, S):
+        raise ValueError("out8 must be [B,S,*] with qk8's B and S")
     if scales.columns_left() < H * 128:
         raise ValueError("the scale tensor must cover the H*128 output columns")
-    native.check("rt_attention_fp8_fwd_mx", native.load().rt_attention_fp8_fwd_mx(
-        _dev(qk8, "qk8", FP8), _dev(vt8, "vt8", FP8), _dev(out8, "out8", FP8), out8.stride(1), out8.stride(0), scales.ptr(), scales.plane, scales.R, scales.k0,
-        B, S, H, float(scale if scale is not None else 128 ** -0.5), _stream()))
+    native.call("rt_attention_fp8_fwd_mx", _dev(qk8, "qk8", FP8), _dev(vt8, "vt8", FP8), _dev(out8, "out8", FP8), ldo, sob,
+                scales.ptr(), scales.plane, scales.R, scales.k0, B, S, H, float(scale if scale is not None else 128 ** -0.5), _stream())
     return out8
 
 
 def euler_step_(x: torch.Tensor, v: torch.Tensor, dsigma: float) -> torch.Tensor:
     if not (x.is_contiguous() and v.is_contiguous()) or x.shape != v.shape:
         raise ValueError("euler_step_: contiguous tensors of equal shape")
-    native.check("rt_euler_step", native.load().rt_euler_step(_dev(x, "x", BF16), _dev(v, "v", BF16), float(dsigma), x.numel(), _stream()))
+    native.call("rt_euler_step", _dev(x, "x", BF16), _dev(v, "v", BF16), float(dsigma), x.numel(), _stream())
     return x
 
 
@@ -753,15 +693,15 @@ def euler_step_f32_(x32: torch.Tensor, v: torch.Tensor, dsigma: float, x_bf16: O
         raise ValueError("euler_step_f32_: contiguous tensors of equal shape")
     if x_bf16 is not None and (x_bf16.shape != x32.shape or not x_bf16.is_contiguous()):
         raise ValueError("x_bf16 must match x32")
-    native.check("rt_euler_step_f32", native.load().rt_euler_step_f32(_dev(x32, "x32", F32), _dev(v, "v", BF16), _opt(x_bf16, "x_bf16", BF16),
-                                                                      float(dsigma), x32.numel(), _stream()))
+    native.call("rt_euler_step_f32", _dev(x32, "x32", F32), _dev(v, "v", BF16), _opt(x_bf16, "x_bf16", BF16),
+                float(dsigma), x32.numel(), _stream())
     return x32
 
 
 def cfg_mix(v_uncond: torch.Tensor, v_text: torch.Tensor, s: float) -> torch.Tensor:
     u, t = v_uncond.contiguous(), v_text.contiguous()
     out = torch.empty_like(t)
-    native.check("rt_cfg_mix", native.load().rt_cfg_mix(_dev(u, "u", BF16), _dev(t, "t", BF16), out.data_ptr(), float(s), out.numel(), _stream()))
+    native.call("rt_cfg_mix", _dev(u, "u", BF16), _dev(t, "t", BF16), out.data_ptr(), float(s), out.numel(), _stream())
     return out
 
 
@@ -769,7 +709,7 @@ def pack_latents(x: torch.Tensor) -> torch.Tensor:
     B, Cc, H2, W2 = x.shape
     x = x.contiguous()
     out = torch.empty(B, (H2 // 2) * (W2 // 2), Cc * 4, device=x.device, dtype=BF16)
-    native.check("rt_pack_latents", native.load().rt_pack_latents(_dev(x, "x", BF16), out.data_ptr(), B, Cc, H2, W2, _stream()))
+    native.call("rt_pack_latents", _dev(x, "x", BF16), out.data_ptr(), B, Cc, H2, W2, _stream())
     return out
 
 
@@ -779,21 +719,21 @@ def unpack_latents_nhwc(packed: torch.Tensor, H2: int, W2: int, scaling: float, 
     Cc = C4 // 4
     packed = packed.contiguous()
     out = torch.empty(B, H2, W2, Cc, device=packed.device, dtype=BF16)
-    native.check("rt_unpack_latents", native.load().rt_unpack_latents(_dev(packed, "packed", BF16), out.data_ptr(), B, Cc, H2, W2, 1.0 / float(scaling), float(shift), _stream()))
+    native.call("rt_unpack_latents", _dev(packed, "packed", BF16), out.data_ptr(), B, Cc, H2, W2, 1.0 / float(scaling), float(shift), _stream())
     return out
 
 
 def to_bf16(x: torch.Tensor) -> torch.Tensor:
     x = x.contiguous()
     out = torch.empty(x.shape, device=x.device, dtype=BF16)
-    native.check("rt_cast_f32_to_bf16", native.load().rt_cast_f32_to_bf16(_dev(x, "x", F32), out.data_ptr(), x.numel(), _stream()))
+    native.call("rt_cast_f32_to_bf16", _dev(x, "x", F32), out.data_ptr(), x.numel(), _stream())
     return out
 
 
 def to_f32(x: torch.Tensor) -> torch.Tensor:
     x = x.contiguous()
     out = torch.empty(x.shape, device=x.device, dtype=F32)
-    native.check("rt_cast_bf16_to_f32", native.load().rt_cast_bf16_to_f32(_dev(x, "x", BF16), out.data_ptr(), x.numel(), _stream()))
+    native.call("rt_cast_bf16_to_f32", _dev(x, "x", BF16), out.data_ptr(), x.numel(), _stream())
     return out
 
 
@@ -804,9 +744,8 @@ def masked_accumulate_(y: torch.Tensor, x: torch.Tensor, rowscale: Optional[torc
     B, R, D = x.shape
     if rowscale is not None and (rowscale.numel() != R or not rowscale.is_contiguous()):
         raise ValueError("rowscale must be contiguous with R elements")
-    native.check("rt_masked_accumulate", native.load().rt_masked_accumulate(
-        _dev(x, "x", BF16), _dev(y, "y"), _opt(rowscale, "rowscale", F32), float(alpha), B, R, D, int(accumulate),
-        int(y.dtype == F32), _stream()))
+    native.call("rt_masked_accumulate", _dev(x, "x", BF16), _dev(y, "y"), _opt(rowscale, "rowscale", F32), float(alpha), B, R, D, int(accumulate),
+        int(y.dtype == F32), _stream())
     return y
 
 
@@ -815,7 +754,7 @@ def silu_split(x: torch.Tensor, apply_silu: bool = True):
     x = x.contiguous()
     hi = torch.empty(x.shape, device=x.device, dtype=BF16)
     lo = torch.empty(x.shape, device=x.device, dtype=BF16)
-    native.check("rt_silu_split_bf16", native.load().rt_silu_split_bf16(_dev(x, "x", F32), hi.data_ptr(), lo.data_ptr(), x.numel(), int(apply_silu), _stream()))
+    native.call("rt_silu_split_bf16", _dev(x, "x", F32), hi.data_ptr(), lo.data_ptr(), x.numel(), int(apply_silu), _stream())
     return hi, lo
 
 
@@ -839,8 +778,8 @@ def resize2d(x: torch.Tensor, size=None, scale_factor: Optional[float] = None, m
         raise TypeError("resize2d: fp32 input, or uint8 input together with u8_scale")
     planes = x.numel() // (H * W)
     out = torch.empty(*x.shape[:-2], OH, OW, device=x.device, dtype=F32)
-    native.check("rt_resize2d", native.load().rt_resize2d(_dev(x, "x"), int(is_u8), float(u8_scale or 1.0), out.data_ptr(), planes, H, W, OH, OW,
-                                                      sf, sf, int(mode == "bilinear"), _stream()))
+    native.call("rt_resize2d", _dev(x, "x"), int(is_u8), float(u8_scale or 1.0), out.data_ptr(), planes, H, W, OH, OW,
+                                                      sf, sf, int(mode == "bilinear"), _stream())
     return out
 
 
@@ -852,8 +791,8 @@ def glyph_blend(image: torch.Tensor, latents: torch.Tensor, noise: torch.Tensor)
     B, Cimg, H, W = image.shape
     _, Cl, OH, OW = latents.shape
     out = torch.empty_like(noise)
-    native.check("rt_glyph_blend", native.load().rt_glyph_blend(_dev(image, "image", F32), _dev(latents, "latents", F32), _dev(noise, "noise", F32),
-                                                             out.data_ptr(), B, Cimg, H, W, Cl, OH, OW, _stream()))
+    native.call("rt_glyph_blend", _dev(image, "image", F32), _dev(latents, "latents", F32), _dev(noise, "noise", F32),
+                                                             out.data_ptr(), B, Cimg, H, W, Cl, OH, OW, _stream())
     return out
 
 
@@ -865,11 +804,10 @@ def canny_u8(img: torch.Tensor, low: float = 50.0, high: float = 100.0, invert: 
     img = img.contiguous()
     H, W = img.shape[0], img.shape[1]
     Cc = 1 if img.dim() == 2 else img.shape[2]
-    lib = native.load()
-    ws = torch.empty(int(lib.rt_canny_ws_bytes(H, W)), device=img.device, dtype=torch.uint8)
+    ws = torch.empty(int(native.load().rt_canny_ws_bytes(H, W)), device=img.device, dtype=torch.uint8)
     out = torch.empty(H, W, out_channels, device=img.device, dtype=torch.uint8)
-    native.check("rt_canny_u8", lib.rt_canny_u8(_dev(img, "img"), H, W, Cc, float(low), float(high), out.data_ptr(), out_channels, int(invert),
-                                               ws.data_ptr(), ws.numel(), _stream()))
+    native.call("rt_canny_u8", _dev(img, "img"), H, W, Cc, float(low), float(high), out.data_ptr(), out_channels, int(invert),
+                                               ws.data_ptr(), ws.numel(), _stream())
     return out
 
 
@@ -885,5 +823,5 @@ def preprocess_u8(img: torch.Tensor, normalize: bool = True) -> torch.Tensor:
     img = img.contiguous()
     B, H, W, Cc = img.shape
     out = torch.empty(B, Cc, H, W, device=img.device, dtype=F32)
-    native.check("rt_preprocess_u8", native.load().rt_preprocess_u8(_dev(img, "img"), out.data_ptr(), B, H, W, Cc, int(normalize), _stream()))
+    native.call("rt_preprocess_u8", _dev(img, "img"), out.data_ptr(), B, H, W, Cc, int(normalize), _stream())
     return out

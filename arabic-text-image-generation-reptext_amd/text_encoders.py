@@ -22,6 +22,7 @@ import torch
 import torch.nn as nn
 
 from . import native, ops
+from .ops import _dev
 from .config import Config
 from .encoder_common import (BF16, F32, _H, _W, _WB, _AssembledAttention, _attention_heads, _attention_scratch, _Encoder,  # noqa: F401
                              _encoder_layers, _fuse, _PreLNStack, _quick_gelu, _stream, pad_mlp_to_64)
@@ -121,7 +122,6 @@ class T5EncoderModel(_Encoder):
         plans = self._ensure_plans()
         c = self.config
         dev = self.device
-        lib = native.load()
         B, T = input_ids.shape
         if T % 64:
             raise ValueError("T5EncoderModel (HIP): sequence length must be a multiple of 64 (the pipelines pad to 512)")
@@ -129,8 +129,8 @@ class T5EncoderModel(_Encoder):
         inner = H * 64
         ids = _ids_i32(input_ids.reshape(-1), dev)
         emb = torch.empty(B * T, d, device=dev, dtype=BF16)
-        native.check("rt_embedding_gather", lib.rt_embedding_gather(self.shared.weight.data_ptr(), d, ids.data_ptr(), emb.data_ptr(), d, B * T, d,
-                                                                    c.vocab_size, _stream()))
+        native.call("rt_embedding_gather", _dev(self.shared.weight.data, "shared", BF16), d, _dev(ids, "ids", torch.int32), _dev(emb, "emb", BF16), d,
+                    B * T, d, c.vocab_size, _stream())
         x = ops.to_f32(emb)                                                     # fp32 residual stream [B*T, d]
         xn = torch.empty(B * T, d, device=dev, dtype=BF16)
         qkv = torch.empty(B, T, 3 * inner, device=dev, dtype=BF16)
@@ -142,7 +142,7 @@ class T5EncoderModel(_Encoder):
         eps = float(c.layer_norm_epsilon)
 
         def rms(w, dst):
-            native.check("rt_rmsnorm_rows", lib.rt_rmsnorm_rows(x.data_ptr(), d, 1, w.data_ptr(), dst.data_ptr(), d, B * T, d, eps, _stream()))
+            native.call("rt_rmsnorm_rows", _dev(x, "x", F32), d, 1, _dev(w, "w", BF16), _dev(dst, "out", BF16), d, B * T, d, eps, _stream())
 
         for wqkv, wo, wi, wff, ln0, ln1 in plans:
             rms(ln0, xn)
@@ -151,7 +151,7 @@ class T5EncoderModel(_Encoder):
             ops.linear(att.view(B * T, inner), wo, x, res=x)
             rms(ln1, xn)
             ops.linear(xn, wi, hid, gelu_from=F_)                                # [wi_1 x | gelu(wi_0 x)]
-            native.check("rt_gated_mul", lib.rt_gated_mul(hid.data_ptr(), 2 * F_, act.data_ptr(), F_, B * T, F_, _stream()))
+            native.call("rt_gated_mul", _dev(hid, "hid", BF16), 2 * F_, _dev(act, "act", BF16), F_, B * T, F_, _stream())
             ops.linear(act, wff, x, res=x)
         out = torch.empty(B * T, d, device=dev, dtype=BF16)
         rms(self.encoder.final_layer_norm.weight.data, out)
@@ -205,7 +205,7 @@ class CLIPTextModel(_AssembledAttention, _PreLNStack):
         if attention_mask is not None:
             raise NotImplementedError("CLIPTextModel (HIP): the FLUX pipelines pass no attention mask (PIPE:337-339)")
         plans = self._ensure_plans()
-        tm, c, dev, lib = self.text_model, self.config, self.device, native.load()
+        tm, c, dev = self.text_model, self.config, self.device
         B, T = input_ids.shape
         if T > c.max_position_embeddings:
             raise ValueError("sequence longer than max_position_embeddings")
@@ -214,8 +214,8 @@ class CLIPTextModel(_AssembledAttention, _PreLNStack):
         ids = torch.zeros(B, Tp, dtype=torch.int32, device=dev)
         ids[:, :T] = input_ids.to(dev, torch.int32)
         emb = torch.empty(B * Tp, d, device=dev, dtype=BF16)
-        native.check("rt_embedding_gather", lib.rt_embedding_gather(tm.embeddings.token_embedding.weight.data_ptr(), d, ids.data_ptr(),
-                                                                    emb.data_ptr(), d, B * Tp, d, c.vocab_size, _stream()))
+        native.call("rt_embedding_gather", _dev(tm.embeddings.token_embedding.weight.data, "token_embedding", BF16), d, _dev(ids, "ids", torch.int32),
+                    _dev(emb, "emb", BF16), d, B * Tp, d, c.vocab_size, _stream())
         pos = torch.zeros(Tp, d, device=dev, dtype=BF16)
         pos[:T] = tm.embeddings.position_embedding.weight.data[:T]
         x = ops.to_f32(emb).view(B, Tp, d)

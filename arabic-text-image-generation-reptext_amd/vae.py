@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import native, ops
+from .ops import _dev, _opt
 from .config import Config, flux_vae_config
 from .modules import WeightsIO
 
@@ -262,22 +263,19 @@ class AutoencoderKL(nn.Module, WeightsIO):
         cout = w.shape[0]
         if out is None:
             out = self._pool.get(B, Ho, Wo, cout, F32 if out_f32 else BF16)
-        native.check("rt_conv2d_nhwc", native.load().rt_conv2d_nhwc(
-            x.data_ptr(), w.data_ptr(), b.data_ptr(), None if res is None else res.data_ptr(), out.data_ptr(), B, Hs, Ws, Cin,
-            cout, w.shape[1], stride, int(up), int(out_f32), _stream()))
+        native.call("rt_conv2d_nhwc", _dev(x, "x", BF16), _dev(w, "w", BF16), _dev(b, "bias", BF16), _opt(res, "res", BF16),
+                    _dev(out, "out", F32 if out_f32 else BF16), B, Hs, Ws, Cin, cout, w.shape[1], stride, int(up), int(out_f32), _stream())
         return out
 
     def _gn(self, norm: _Affine, x: torch.Tensor, silu: bool, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         B, Hp, Wp, C = x.shape
         if out is None:
             out = self._pool.get(B, Hp - 2, Wp - 2, C)
-        lib = native.load()
-        need = int(lib.rt_groupnorm_ws_bytes(B, Hp - 2, Wp - 2, self.config.norm_num_groups))
+        need = int(native.load().rt_groupnorm_ws_bytes(B, Hp - 2, Wp - 2, self.config.norm_num_groups))
         if self._stats is None or self._stats.numel() * 8 < need:
             self._stats = torch.empty((need + 7) // 8, device=self.device, dtype=torch.float64)
-        native.check("rt_groupnorm_silu_nhwc", lib.rt_groupnorm_silu_nhwc(
-            x.data_ptr(), out.data_ptr(), norm.weight.data_ptr(), norm.bias.data_ptr(), self._stats.data_ptr(), B, Hp - 2, Wp - 2, C,
-            self.config.norm_num_groups, 1e-6, int(silu), _stream()))
+        native.call("rt_groupnorm_silu_nhwc", _dev(x, "x", BF16), _dev(out, "out", BF16), _dev(norm.weight.data, "gamma", BF16), _dev(norm.bias.data, "beta", BF16),
+                    _dev(self._stats, "stats", torch.float64), B, Hp - 2, Wp - 2, C, self.config.norm_num_groups, 1e-6, int(silu), _stream())
         return out
 
     def _resnet(self, m, x: torch.Tensor) -> torch.Tensor:
@@ -313,9 +311,8 @@ class AutoencoderKL(nn.Module, WeightsIO):
         # one head of C channels over HW positions, flash-style: no HW x HW scores (csrc/vae_attention.hip)
         o = torch.empty(B, HW, C, device=x.device, dtype=BF16)
         q, k, v = qkv[..., :C], qkv[..., C : 2 * C], qkv[..., 2 * C :]
-        native.check("rt_vae_attention", native.load().rt_vae_attention(
-            q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), qkv.stride(1), qkv.stride(0), o.stride(1), o.stride(0), B, HW, C,
-            1.0 / math.sqrt(C), _stream()))
+        native.call("rt_vae_attention", _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(o, "o", BF16), qkv.stride(1), qkv.stride(0),
+                    o.stride(1), o.stride(0), B, HW, C, 1.0 / math.sqrt(C), _stream())
         for b in range(B):
             # to_out + residual, written row by row into the haloed buffer: batch = image rows
             xin = x[b, 1:-1, 1:-1, :]                              # [H, W, C] strided view of the interior
@@ -352,10 +349,10 @@ class AutoencoderKL(nn.Module, WeightsIO):
         H, W, C = Hp - 2, Wp - 2, self.config.out_channels
         if want_u8:
             out = torch.empty(B, H, W, C, device=img.device, dtype=torch.uint8)
-            native.check("rt_image_out", native.load().rt_image_out(img.data_ptr(), None, out.data_ptr(), B, H, W, Cp, C, _stream()))
+            native.call("rt_image_out", _dev(img, "img", F32), None, _dev(out, "out", torch.uint8), B, H, W, Cp, C, _stream())
         else:
             out = torch.empty(B, C, H, W, device=img.device, dtype=F32)
-            native.check("rt_image_out", native.load().rt_image_out(img.data_ptr(), out.data_ptr(), None, B, H, W, Cp, C, _stream()))
+            native.call("rt_image_out", _dev(img, "img", F32), _dev(out, "out", F32), None, B, H, W, Cp, C, _stream())
         self._pool.put(img)
         return out
 
@@ -368,9 +365,8 @@ class AutoencoderKL(nn.Module, WeightsIO):
         C = self.config.latent_channels
         z = self._pool.get(B, h2, w2, _pad64(C))
         packed = packed.contiguous()          # named, so the buffer outlives the raw-pointer call
-        native.check("rt_unpack_latents_haloed", native.load().rt_unpack_latents_haloed(
-            packed.data_ptr(), z.data_ptr(), B, C, h2, w2, _pad64(C), 1.0 / self.config.scaling_factor,
-            self.config.shift_factor, _stream()))
+        native.call("rt_unpack_latents_haloed", _dev(packed, "packed", BF16), _dev(z, "z", BF16), B, C, h2, w2, _pad64(C), 1.0 / self.config.scaling_factor,
+                    self.config.shift_factor, _stream())
         img = self._decode_haloed(z)
         self._pool.put(z)
         return self._image_out(img, output_u8)
@@ -382,8 +378,7 @@ class AutoencoderKL(nn.Module, WeightsIO):
         B, C, h, w = z.shape
         zin = self._pool.get(B, h, w, _pad64(C))
         z32 = z.to(F32).contiguous()
-        native.check("rt_nchw_to_haloed_nhwc", native.load().rt_nchw_to_haloed_nhwc(
-            z32.data_ptr(), zin.data_ptr(), B, C, h, w, _pad64(C), _stream()))
+        native.call("rt_nchw_to_haloed_nhwc", _dev(z32, "z", F32), _dev(zin, "zin", BF16), B, C, h, w, _pad64(C), _stream())
         img = self._decode_haloed(zin)
         self._pool.put(zin)
         out = self._image_out(img, False).to(z.dtype if z.dtype in (BF16, F32) else F32)
@@ -396,9 +391,8 @@ class AutoencoderKL(nn.Module, WeightsIO):
         e = self.encoder
         B, C, H, W = x.shape
         xin = self._pool.get(B, H, W, _pad64(C))
-        lib = native.load()
         x32 = x.to(F32).contiguous()
-        native.check("rt_nchw_to_haloed_nhwc", lib.rt_nchw_to_haloed_nhwc(x32.data_ptr(), xin.data_ptr(), B, C, H, W, _pad64(C), _stream()))
+        native.call("rt_nchw_to_haloed_nhwc", _dev(x32, "x", F32), _dev(xin, "xin", BF16), B, C, H, W, _pad64(C), _stream())
         h = self._conv(e.conv_in, xin)
         self._pool.put(xin)
         for blk in e.down_blocks:
@@ -415,7 +409,7 @@ class AutoencoderKL(nn.Module, WeightsIO):
         self._pool.put(t)
         Bm, Hp, Wp, Cm = mom.shape
         out = torch.empty(B, Cm, Hp - 2, Wp - 2, device=x.device, dtype=F32)
-        native.check("rt_haloed_nhwc_to_nchw", lib.rt_haloed_nhwc_to_nchw(mom.data_ptr(), out.data_ptr(), B, Cm, Hp - 2, Wp - 2, Cm, _stream()))
+        native.call("rt_haloed_nhwc_to_nchw", _dev(mom, "moments", BF16), _dev(out, "out", F32), B, Cm, Hp - 2, Wp - 2, Cm, _stream())
         self._pool.put(mom)
         mean, logvar = out[:, : Cm // 2], out[:, Cm // 2 :]
         dt = x.dtype if x.dtype in (BF16, F32) else F32

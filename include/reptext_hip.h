@@ -31,7 +31,9 @@ extern "C" {
 
 /* Library identity: returns a static string "reptext_hip <abi> gfx950". */
 const char* rt_version(void);
-/* ABI revision; bumped when any struct or entry point below changes. */
+/* ABI revision; bumped when any struct or entry point below changes. rt_abi_version() returns the RT_ABI_VERSION the library was
+ * built with; the Python binding reads this header and refuses a library whose number differs from it. */
+#define RT_ABI_VERSION 15
 int rt_abi_version(void);
 
 /* ------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 """CPU checks of the boundary: the shared library loads without a GPU, exports every symbol include/reptext_hip.h
-declares, the ctypes binding covers exactly that set, struct layouts agree, and the product never touches oracle/."""
+declares, the ctypes binding covers exactly that set, struct layouts agree, and the product never touches oracle/.
+The binding itself (parser known answers, strictness, native.call) is tested in tests/test_native_binding_host.py."""
 import ctypes
 import os
 import re
@@ -35,22 +36,24 @@ def test_library_builds_and_exports_every_declared_symbol():
 
 
 def test_gemm_group_struct_layout_matches_c(tmp_path):
-    """Compile a tiny host program against the header and compare sizeof/offsetof with the ctypes mirror."""
+    """Compile a tiny host program against the header and compare sizeof and the offsetof of EVERY field of every struct with the
+    ctypes classes the binding generates (the field list of the program comes from those classes)."""
     from reptext_amd import native
 
-    prog = r'''
-#include <stdio.h>
-#include <stddef.h>
-#include "reptext_hip.h"
-int main(){ printf("%zu %zu %zu %zu %zu %zu\n", sizeof(rt_gemm_group), offsetof(rt_gemm_group, lda), offsetof(rt_gemm_group, strideA),
-  offsetof(rt_gemm_group, M), offsetof(rt_gemm_group, out_f32), offsetof(rt_gemm_group, alpha)); return 0; }
-'''
+    assert set(native.STRUCTS) == {"rt_gemm_group", "rt_skinny_group", "rt_ln_segment", "rt_lora_term"}
+    assert [native.STRUCTS[n] for n in sorted(native.STRUCTS)] == [native.GemmGroup, native.LnSegment, native.LoraTerm, native.SkinnyGroup]
+    fields = [(c, f) for c, cls in native.STRUCTS.items() for f, _ in cls._fields_]
+    assert len(fields) == 56 + 7 + 11 + 6                                       # counted in the header
+    lines = [f'printf("%zu\\n", sizeof({c}));' for c in native.STRUCTS] + [f'printf("%zu\\n", offsetof({c}, {f}));' for c, f in fields]
+    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "reptext_hip.h"\nint main(){\n' + "\n".join(lines) + "\nreturn 0; }\n"
     src, exe = str(tmp_path / "_layout.c"), str(tmp_path / "_layout")
     open(src, "w").write(prog)
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
-    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()
+    out = [int(x) for x in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.split()]
+    want = [ctypes.sizeof(cls) for cls in native.STRUCTS.values()] + [getattr(native.STRUCTS[c], f).offset for c, f in fields]
+    assert out == want, [(cf, a, b) for cf, a, b in zip(list(native.STRUCTS) + fields, out, want) if a != b]
     G = native.GemmGroup
-    assert [int(x) for x in out] == [ctypes.sizeof(G), G.lda.offset, G.strideA.offset, G.M.offset, G.out_f32.offset, G.alpha.offset]
+    assert (ctypes.sizeof(G), G.lda.offset, G.strideA.offset, G.M.offset, G.out_f32.offset, G.alpha.offset) == (360, 64, 112, 144, 168, 172)
 
 
 def test_calls_are_rejected_not_crashed_without_gpu_memory():

@@ -1,7 +1,9 @@
 """Interleaved timing of the ablation builds of attention_v3 (tools/attn_v3_dev/make_ablations.py) in ONE process."""
-import ctypes as C, os, sys
+import os, sys
 import torch
 here = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, os.path.dirname(os.path.dirname(here)))
+from reptext_amd import native
 S = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
 H = int(sys.argv[2]) if len(sys.argv) > 2 else 32
 dev = torch.device("cuda:0")
@@ -12,17 +14,12 @@ libs = {}
 for n in sorted(os.listdir(here)):
     p = os.path.join(here, n, "librt_reptext_hip.so")
     if n.startswith("lib_") and os.path.isfile(p):
-        lib = C.CDLL(p)
-        lib.rt_attention_fwd.argtypes = [C.c_void_p] * 4 + [C.c_int64] * 4 + [C.c_int32] * 3 + [C.c_float, C.c_void_p, C.c_int64, C.c_void_p]
-        libs[n[4:]] = lib
+        libs[n[4:]] = native.bind(p)
 use_ws = len(sys.argv) > 3 and sys.argv[3] == "ws"
 st = torch.cuda.current_stream().cuda_stream
 ws = None
 if use_ws:
-    any_lib = next(iter(libs.values()))
-    any_lib.rt_attention_ws_bytes.restype = C.c_int64
-    any_lib.rt_attention_ws_bytes.argtypes = [C.c_int32] * 3
-    n = any_lib.rt_attention_ws_bytes(1, S, H)
+    n = next(iter(libs.values())).rt_attention_ws_bytes(1, S, H)
     ws = torch.zeros(max(n, 256), device=dev, dtype=torch.uint8)
     print("workspace bytes", n)
 q, k, v = qkv[..., :d], qkv[..., d:2 * d], qkv[..., 2 * d:]
@@ -31,7 +28,6 @@ def run(lib):
     assert r == 0, r
 res = {n: [] for n in libs}
 for lib in libs.values():
-    lib.rt_attention_variant.argtypes = [C.c_int32]
     lib.rt_attention_variant(2)
 for rnd in range(4):
     for n, lib in libs.items():

@@ -18,8 +18,7 @@ for name, M, N, K, ld in [("single proj_out", 4608, 3072, 15360, 21504), ("ff.ne
     res = torch.randn(M, N, device=dev)
     out = torch.empty(M, N, device=dev)
     gate = torch.randn(1, N, device=dev)
-    lib = native.load()
-    q = lambda: native.check("q", lib.rt_quantize_rows_fp8(a.data_ptr(), ld, 0, a8.data_ptr(), K, sa.data_ptr(), M, K, ops._stream()))
+    q = lambda: native.call("rt_quantize_rows_fp8", a.data_ptr(), ld, 0, a8.data_ptr(), K, sa.data_ptr(), M, K, ops._stream())
     t_q = timeit(q)
     t_8 = timeit(lambda: ops.linear(a8, w8, out, gate=gate, res=res, a_scale=sa, w_scale=sw))
     t_16 = timeit(lambda: ops.linear(a, w, out, gate=gate, res=res))
