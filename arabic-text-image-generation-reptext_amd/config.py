@@ -48,6 +48,12 @@ def reptext_controlnet_config(**over) -> Config:
     return c
 
 
+def union_pro2_controlnet_config(**over) -> Config:
+    """FLUX.1-dev-ControlNet-Union-Pro-2.0 as recalled (its config.json is not pinned here): a plain tower of 6 double blocks, no
+    single blocks, no mode embedding (2.0 removed it) and a 64-channel hint — the VAE latents of the control image."""
+    return reptext_controlnet_config(extra_condition_channels=0, **over)
+
+
 def flux_vae_config(**over) -> Config:
     c = Config(in_channels=3, out_channels=3, latent_channels=16, block_out_channels=[128, 256, 512, 512],
                layers_per_block=2, norm_num_groups=32, act_fn="silu", scaling_factor=0.3611, shift_factor=0.1159,

@@ -199,14 +199,15 @@ class FluxControlNetModel(_MMDiTBase):
                 joint_attention_kwargs: Optional[Dict[str, Any]] = None, return_dict: bool = True,
                 _rowscale: Optional[torch.Tensor] = None, _accumulate_into: Optional[Sequence[torch.Tensor]] = None,
                 _accumulate_single_into: Optional[Sequence[torch.Tensor]] = None, _mods: Optional["mmdit.StepMods"] = None,
-                _overwrite: bool = False, _sample_events: Optional[Sequence["torch.cuda.Event"]] = None, _ws_tag: str = "",
+                _overwrite: Union[bool, Tuple[int, int]] = False, _sample_events: Optional[Sequence["torch.cuda.Event"]] = None, _ws_tag: str = "",
                 _static: Optional[StaticEmbeds] = None, _blocks_needed: Optional[Tuple[int, int]] = None,
                 _window: Optional[Tuple[int, int]] = None):
         """Same contract as CN:216-413. ``joint_attention_kwargs["scale"]`` scales this call's LoRA adapters (CN:263-276; merged into
         the weights, lora.py). The private ``_rowscale`` / ``_accumulate_into`` arguments let the pipeline fuse its
         regional mask (PIPE:1062) and the sum over text lines (PIPE:1076-1080) into the zero-linear epilogues; with
         ``_overwrite`` the ``_accumulate_into`` buffers are written, not added to (first text line into preallocated
-        buffers). ``_sample_events[i]`` is recorded on the current stream once double-block sample i is complete and
+        buffers); a pair (n_double, n_single) instead of a bool: that many leading buffers were written earlier in this step and
+        are added to, the rest are written (a tower that follows a shallower one). ``_sample_events[i]`` is recorded on the current stream once double-block sample i is complete and
         ``_ws_tag`` selects a private workspace — both for running the tower on a side stream next to the transformer.
         ``_static``: this tower's loop-invariant embeddings for (prompt, this hint) from ``prepare_static`` — the per-step work
         is then x_embedder only. ``_blocks_needed`` = (double, single): evaluate only that many leading blocks; the samples of
@@ -249,17 +250,20 @@ class FluxControlNetModel(_MMDiTBase):
 
         scale = float(conditioning_scale)
 
-        def head(lin, dst_list, i):
+        # first buffer index that is overwritten, per kind: 0 = all (True), past the end = none (False)
+        ow_d, ow_s = ((0, 0) if _overwrite else (1 << 30, 1 << 30)) if isinstance(_overwrite, bool) else (int(_overwrite[0]), int(_overwrite[1]))
+
+        def head(lin, dst_list, i, overwrite):
             """zero-linear i on the current image rows: (W·h+b)·scale [·mask] [+ running sum] (CN:384-396)."""
             a = mmdit.image_rows_bf16(ws, _window)
             if _window is not None:
                 r0, r1 = _window
                 out = dst_list[i]
                 ops.linear(a, lin.weight.data, out[:, r0:r1], bias=lin.bias.data, alpha=scale, rowscale=_rowscale[..., r0:r1],
-                           res=None if _overwrite else out[:, r0:r1])
+                           res=None if overwrite else out[:, r0:r1])
             elif dst_list is not None:
                 out = dst_list[i]
-                ops.linear(a, lin.weight.data, out, bias=lin.bias.data, alpha=scale, rowscale=_rowscale, res=None if _overwrite else out)
+                ops.linear(a, lin.weight.data, out, bias=lin.bias.data, alpha=scale, rowscale=_rowscale, res=None if overwrite else out)
             else:
                 out = torch.empty(Bc, N, d, device=hs.device, dtype=torch.bfloat16)
                 ops.linear(a, lin.weight.data, out, bias=lin.bias.data, alpha=scale, rowscale=_rowscale)
@@ -282,7 +286,7 @@ class FluxControlNetModel(_MMDiTBase):
                 continue
             mmdit.run_double(pl, ws, temb, cos, sin, H, mods=None if _mods is None else _mods.double[i],
                              window=_window if i == nd - 1 else None)   # ns == 0: only zero-linear nd-1 reads this block
-            block_samples.append(head(self.controlnet_blocks[i], _accumulate_into, i))
+            block_samples.append(head(self.controlnet_blocks[i], _accumulate_into, i, i >= ow_d))
             if _sample_events is not None:
                 _sample_events[i].record(torch.cuda.current_stream())
         single_samples: List[Optional[torch.Tensor]] = []
@@ -291,7 +295,7 @@ class FluxControlNetModel(_MMDiTBase):
                 single_samples.append(None)
                 continue
             mmdit.run_single(pl, ws, temb, cos, sin, H, mods=None if _mods is None else _mods.single[i])
-            single_samples.append(head(self.controlnet_single_blocks[i], _accumulate_single_into, i))
+            single_samples.append(head(self.controlnet_single_blocks[i], _accumulate_single_into, i, i >= ow_s))
 
         bs = block_samples if block_samples else None
         ss = single_samples if single_samples else None

@@ -102,17 +102,18 @@ def canny_hint(glyph_rgb: np.ndarray, low_threshold: float = 50, high_threshold:
     return 255 - np.concatenate([e, e, e], axis=2)
 
 
-def canny_hint_device(glyph_rgb: np.ndarray, device, low_threshold: float = 50, high_threshold: float = 100):
+def canny_hint_device(glyph_rgb: np.ndarray, device, low_threshold: float = 50, high_threshold: float = 100, invert: bool = True):
     """`canny()` of infer.py:16-22 followed by VaeImageProcessor.preprocess (PIPE:680), both on the device: the glyph's uint8
     pixels are uploaded once, rt_canny_u8 writes the inverted 3-channel edge hint, rt_preprocess_u8 turns it into the float32
     [1,3,H,W] tensor in [-1,1] that `prepare_image` would otherwise build on the host. Bit-identical to
-    preprocess(Image.fromarray(canny_hint(glyph))) (tests/test_hints_gpu.py)."""
+    preprocess(Image.fromarray(canny_hint(glyph))) (tests/test_hints_gpu.py). ``invert=False`` keeps white edges on black, the form
+    of a Canny control image for the union tower (``control_image_union``)."""
     import torch
 
     from . import ops
 
     g = torch.from_numpy(np.ascontiguousarray(glyph_rgb)).to(device)
-    return ops.preprocess_u8(ops.canny_u8(g, low_threshold, high_threshold, invert=True, out_channels=3))
+    return ops.preprocess_u8(ops.canny_u8(g, low_threshold, high_threshold, invert=invert, out_channels=3))
 
 
 def build_text_hints(texts: Sequence[str], positions: Sequence[Tuple[int, int]], colors: Sequence[Tuple[int, int, int]], font,

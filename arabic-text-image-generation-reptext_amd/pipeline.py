@@ -129,6 +129,30 @@ def accepts_ip_adapter_arguments(call):
     return wrapper
 
 
+def union_active_steps(num_steps: int, start: float, end: float) -> Tuple[int, ...]:
+    """The steps, of ``num_steps``, at which a tower with the guidance interval [start, end] is evaluated: step i iff
+    ``not (i / n < start or (i + 1) / n > end)`` — diffusers' ``controlnet_keep`` (recalled, not read). ``start > end`` gives none."""
+    n = int(num_steps)
+    return tuple(i for i in range(n) if not (i / n < start or (i + 1) / n > end))
+
+
+def accepts_union_arguments(call):
+    """The second ControlNet's four arguments — ``control_image_union``, ``controlnet_conditioning_scale_union``,
+    ``control_guidance_start_union``, ``control_guidance_end_union`` — are keyword-only extensions of the BASE pipeline's ``__call__``,
+    taken off here like the IP-Adapter's (``accepts_ip_adapter_arguments``) and left on the pipeline as ``_union_call_args`` for the
+    duration of the call; what the call derives from them (``_union``, read by ``_denoise``) is cleared with them."""
+    @functools.wraps(call)
+    def wrapper(self, *args, control_image_union=None, controlnet_conditioning_scale_union: float = 1.0,
+                control_guidance_start_union: float = 0.0, control_guidance_end_union: float = 1.0, **kwargs):
+        self._union_call_args = (control_image_union, controlnet_conditioning_scale_union, control_guidance_start_union,
+                                 control_guidance_end_union)
+        try:
+            return call(self, *args, **kwargs)
+        finally:
+            self._union_call_args, self._union = None, None
+    return wrapper
+
+
 class FluxControlNetPipeline:
     model_cpu_offload_seq = "text_encoder->text_encoder_2->transformer->vae"
     _optional_components: List[str] = []
@@ -149,13 +173,20 @@ class FluxControlNetPipeline:
         self._ip_call_args, self._ip_embeds = (None, None), None
         # the IP-Adapter's image side (image_encoder.py); set by from_pretrained / load_ip_adapter or assigned, not components
         self.image_encoder, self.feature_extractor = None, None
+        # a second, unmasked ControlNet with its own step window beside the text-line tower (Union-Pro-2.0: canny / depth / pose); set
+        # by from_pretrained(controlnet_union=) or assigned, fed by __call__(control_image_union=...) — base pipeline only
+        self.controlnet_union: Optional[FluxControlNetModel] = None
+        self._union_call_args, self._union = None, None
 
     # ------------------------------------------------------------------ component plumbing
     @property
     def components(self) -> Dict[str, Any]:
-        return dict(scheduler=self.scheduler, vae=self.vae, text_encoder=self.text_encoder, tokenizer=self.tokenizer,
-                    text_encoder_2=self.text_encoder_2, tokenizer_2=self.tokenizer_2, transformer=self.transformer,
-                    controlnet=self.controlnet)
+        c = dict(scheduler=self.scheduler, vae=self.vae, text_encoder=self.text_encoder, tokenizer=self.tokenizer,
+                 text_encoder_2=self.text_encoder_2, tokenizer_2=self.tokenizer_2, transformer=self.transformer,
+                 controlnet=self.controlnet)
+        if self.controlnet_union is not None:
+            c["controlnet_union"] = self.controlnet_union
+        return c
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: str, controlnet=None, torch_dtype=None, **kwargs):
@@ -215,10 +246,14 @@ class FluxControlNetPipeline:
             raise OSError(f"could not load text encoders from {root}: {e}") from e
         if isinstance(controlnet, str):
             controlnet = FluxControlNetModel.from_pretrained(controlnet, torch_dtype=dt)
+        controlnet_union = kwargs.pop("controlnet_union", None)          # a model, a local directory or a cached hub id, like controlnet=
+        if isinstance(controlnet_union, str):
+            controlnet_union = FluxControlNetModel.from_pretrained(controlnet_union, torch_dtype=dt)
         extra = {k: kwargs[k] for k in ("controlnet_inpaint",) if k in kwargs}
         pipe = cls(scheduler=scheduler, vae=vae, text_encoder=te, tokenizer=tok, text_encoder_2=te2, tokenizer_2=tok2,
                    transformer=transformer, controlnet=controlnet, **extra)
         pipe.image_encoder, pipe.feature_extractor = image_encoder, feature_extractor
+        pipe.controlnet_union = controlnet_union
         return pipe
 
     def save_pretrained(self, root: str, max_shard_bytes: int = 10 << 30) -> None:
@@ -617,7 +652,7 @@ class FluxControlNetPipeline:
     def _lora_models(self) -> list:
         cn = self.controlnet
         nets = list(cn.nets) if isinstance(cn, FluxMultiControlNetModel) else [cn]
-        models = [self.transformer] + nets + [getattr(self, "controlnet_inpaint", None)]
+        models = [self.transformer] + nets + [getattr(self, "controlnet_inpaint", None), getattr(self, "controlnet_union", None)]
         return [m for m in models if m is not None and getattr(m, "_lora", None) is not None]
 
     def _apply_lora_scale(self) -> None:
@@ -631,7 +666,53 @@ class FluxControlNetPipeline:
         kw = self.joint_attention_kwargs
         return kw is None or (set(kw) == {"scale"} and bool(self._lora_models()))
 
+    # ------------------------------------------------------------------ the second ControlNet (controlnet_union)
+    def _check_union_inputs(self, height, width, total) -> bool:
+        """Refusals of the call's ``control_image_union`` against ``self.controlnet_union`` and the first tower — host-side checks on
+        shapes and configs only, made before any device work. True when the union tower takes part in this call."""
+        image = self._union_call_args[0] if self._union_call_args is not None else None
+        if image is None:
+            return False
+        un, cn = self.controlnet_union, self.controlnet
+        if un is None:
+            raise ValueError("control_image_union was passed but this pipeline has no second ControlNet: set pipe.controlnet_union")
+        if not isinstance(cn, FluxControlNetModel):
+            raise ValueError("control_image_union needs pipe.controlnet to be a FluxControlNetModel: the union tower adds into the first "
+                             "tower's sample buffers (a union tower without a RepText tower is not supported)")
+        if un.union:
+            raise NotImplementedError("ControlNet-Union mode embedding is outside the RepText hot path (SURVEY.md §2 #11): "
+                                      "controlnet_union must have num_mode=None (Union-Pro-2.0)")
+        depth = lambda m: (len(m.transformer_blocks), len(m.single_transformer_blocks))
+        if depth(un)[0] > depth(cn)[0] or depth(un)[1] > depth(cn)[1]:
+            raise ValueError(f"control_image_union: controlnet_union has {depth(un)} double/single blocks, more than the first tower's "
+                             f"{depth(cn)}: there is one sample buffer per block of the first tower")
+        if un.inner_dim != cn.inner_dim:
+            raise ValueError(f"control_image_union: controlnet_union's inner_dim {un.inner_dim} != the first tower's {cn.inner_dim}")
+        if isinstance(image, torch.Tensor) and image.dim() == 3:          # packed hint latents [B, N, in_channels]
+            width_in = un.controlnet_x_embedder.weight.shape[1]
+            n_rows = (int(height) // self.vae_scale_factor) * (int(width) // self.vae_scale_factor)
+            if image.shape[-1] != width_in:
+                raise ValueError(f"control_image_union: packed hint width {image.shape[-1]} != controlnet_union's hint width {width_in}")
+            if image.shape[0] not in (1, total):
+                raise ValueError(f"control_image_union: packed hint batch {image.shape[0]} is neither 1 nor the number of images {total}")
+            if image.shape[1] != n_rows:
+                raise ValueError(f"control_image_union: packed hint has N = {image.shape[1]} rows, {height}x{width} pixels need {n_rows}")
+        elif self.vae is None:
+            raise ValueError("control_image_union: an image needs the pipeline's VAE; pass packed [B, N, 64] hint latents instead")
+        return True
+
+    def _union_hint(self, image, width, height, total, num_images_per_prompt, device, dtype) -> torch.Tensor:
+        """[B or 1, N, 64] hint of the union tower: packed latents as they are, an image as ``prepare_image`` treats the canny hint
+        (preprocess, VAE posterior SAMPLE from the global RNG (Q2), (z - shift)·scale, pack) without the position channels."""
+        if self._is_packed_hint(image, self.controlnet_union):
+            return image.to(device=device, dtype=dtype)
+        image = self._prep_pixels(image, width, height, total, num_images_per_prompt, device, dtype)
+        sf, sc = self.vae.config.shift_factor, self.vae.config.scaling_factor
+        lat = ((self.vae.encode(image.to(self.vae.dtype)).latent_dist.sample() - sf) * sc).to(dtype)
+        return self._pack_latents(lat, lat.shape[0], lat.shape[1], lat.shape[2], lat.shape[3])
+
     # ------------------------------------------------------------------ the call
+    @accepts_union_arguments
     @accepts_ip_adapter_arguments
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
@@ -658,6 +739,7 @@ class FluxControlNetPipeline:
         batch_size = self._batch_size(prompt, prompt_embeds)
         device, dtype = self._execution_device, self.transformer.dtype
         total = batch_size * num_images_per_prompt
+        with_union = self._check_union_inputs(height, width, total)
         self._ip_embeds, self._joint_attention_kwargs = self._resolve_ip_embeds(*self._ip_call_args, joint_attention_kwargs, batch_size,
                                                                                 num_images_per_prompt, device)
 
@@ -668,9 +750,15 @@ class FluxControlNetPipeline:
         pooled_prompt_embeds = pooled_prompt_embeds.to(device=device)
 
         hints, height, width = self._collect_hints(control_image, control_position, height, width, total, num_images_per_prompt, device, dtype)
+        # the union hint is encoded AFTER the text lines' hints: a call without it draws the same random numbers as before
+        union_hint = self._union_hint(self._union_call_args[0], width, height, total, num_images_per_prompt, device, dtype) if with_union else None
         timesteps, num_inference_steps = self._schedule(height, width, num_inference_steps, timesteps, device)
         latents, latent_image_ids = self._initial_latents(control_glyph, total, height, width, prompt_embeds.dtype, device, generator, latents)
         masks = self._region_masks(control_mask, latents.device, latents.dtype)
+        if with_union:
+            _, u_scale, u_start, u_end = self._union_call_args
+            active = union_active_steps(len(timesteps), float(u_start), float(u_end))
+            self._union = (self.controlnet_union, union_hint, float(u_scale), active) if active else None
 
         self._apply_lora_scale()
         latents = self._denoise(latents, prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids, timesteps, hints, masks,
@@ -762,11 +850,12 @@ class FluxControlNetPipeline:
         ipe = getattr(self, "_ip_embeds", None)                             # image prompt of this call (None: nothing to add)
         # the rows the regional masks leave non-zero: read here, never inside the loop or a capture; part of the call signature below
         win = active_row_window(masks, latents.shape[1]) if masks and len(masks) == len(hints) else None
+        union = getattr(self, "_union", None)         # (tower, hint, scale, active steps) of this call's second ControlNet, or None
 
         def eager(callback=None):
             return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
                                        cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe,
-                                       _tower_window=win)
+                                       _tower_window=win, _union=union)
 
         use_graph = (GRAPH_CAPTURE and getattr(self, "capture_graphs", True) and callback is None and latents.is_cuda
                      and not self.interrupt and isinstance(self.controlnet, (FluxControlNetModel, type(None)))
@@ -776,8 +865,9 @@ class FluxControlNetPipeline:
         from . import mmdit as _mm
         _mm.reference_bf16_scalars(self.reference_bf16_scalars)      # the module switch follows THIS pipeline before the key is built
         sig = lambda t: (tuple(t.shape), str(t.dtype), tuple(t.stride()))
-        models = tuple((id(m), id(m._ensure_plans()), id(getattr(m, "_cx_pad", None)), bool(getattr(m, "_fp8_linears", False)),
-                        bool(getattr(m, "_fp8_attention", False))) for m in (self.transformer, self.controlnet) if m is not None)
+        ident = lambda m: (id(m), id(m._ensure_plans()), id(getattr(m, "_cx_pad", None)), bool(getattr(m, "_fp8_linears", False)),
+                           bool(getattr(m, "_fp8_attention", False)))
+        models = tuple(ident(m) for m in (self.transformer, self.controlnet) if m is not None)
         key = (sig(latents), sig(prompt_embeds), sig(pooled), sig(text_ids), sig(image_ids), tuple(sig(h) for h in hints), tuple(sig(m) for m in masks),
                tuple(tvals), tuple(self.scheduler.sigmas.tolist()), float(guidance_scale), repr(cn_scale), int(cn_steps), int(num_inference_steps),
                str(latents.device), models, bool(self.reference_bf16_scalars), bool(_mm.RESIDUAL_F32), bool(OVERLAP_TOWER), bool(_mm.FUSED_QK_ROPE),
@@ -786,6 +876,9 @@ class FluxControlNetPipeline:
             # the embeds are one more static input of the graph; the per-block scales are kernel scalars baked into the capture
             adapter = self.transformer._ip_adapter
             key += (sig(ipe), adapter.version, tuple(adapter.scales))
+        if union is not None:
+            # the union hint is one more static input; the tower's scale and its active steps are baked into the capture
+            key += ("union", ident(union[0]), sig(union[1]), union[2], union[3])
         cache = self.__dict__.setdefault("_graph_cache", {})
         ent = cache.get(key)
         if ent is None:                                      # first sight of this signature: eager (and warm), remember it
@@ -796,11 +889,16 @@ class FluxControlNetPipeline:
         if ent == "failed":
             return eager()
         ins = [latents, prompt_embeds, pooled, text_ids, image_ids] + list(hints) + list(masks) + ([ipe] if ipe is not None else [])
+        if union is not None:
+            ins.append(union[1])                              # always the last static input
         if ent == "seen":                                    # second call: capture
             static = [t.clone() for t in ins]
             nh, nm = len(hints), len(masks)
             keep = [m._ensure_plans() for m in (self.transformer, self.controlnet) if m is not None] + [getattr(self.controlnet, "_cx_pad", None)]
             keep.append(getattr(self.transformer, "_ip_adapter", None) if ipe is not None else None)     # its weights are read by the graph
+            n_ip = 5 + nh + nm                                # where the image prompt sits among the static inputs, when there is one
+            if union is not None:
+                keep += [union[0]._ensure_plans(), getattr(union[0], "_cx_pad", None)]
             graph = torch.cuda.CUDAGraph()
             step_index = self.scheduler._step_index
             # The graph bakes in the device pointers of every buffer the loop touches. Buffers that live in caches which may evict or
@@ -814,7 +912,8 @@ class FluxControlNetPipeline:
                 with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                     out = self._denoise_eager(static[0], static[1], static[2], static[3], static[4], tvals, static[5 : 5 + nh], static[5 + nh : 5 + nh + nm],
                                               guidance_scale, cn_scale, cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps,
-                                              _quiet=True, _ip_embeds=static[-1] if ipe is not None else None, _tower_window=win)
+                                              _quiet=True, _ip_embeds=static[n_ip] if ipe is not None else None, _tower_window=win,
+                                              _union=None if union is None else (union[0], static[-1]) + tuple(union[2:]))
                     out32 = self._master_latents
             except Exception as e:                           # capture is an optimisation, never a requirement
                 import sys
@@ -829,11 +928,12 @@ class FluxControlNetPipeline:
                 return eager()
             _mm.CAPTURE_KEEP = ops.CAPTURE_KEEP = None
             keep.append(getattr(self, "_sample_cache", None))
-            keep.extend(dict(m._rope_cache) for m in (self.transformer, self.controlnet) if m is not None and hasattr(m, "_rope_cache"))
+            keep.extend(dict(m._rope_cache) for m in (self.transformer, self.controlnet, union[0] if union is not None else None)
+                        if m is not None and hasattr(m, "_rope_cache"))
             self.scheduler._step_index = step_index
             # the sample buffers the capture wrote into and the window its zero-linears were restricted to (None: every row)
             ent = cache[key] = {"graph": graph, "static": static, "out": out, "out32": out32, "keep": keep,
-                                "samples": getattr(self, "_sample_cache", None), "window": self._tower_window_used}
+                                "samples": getattr(self, "_sample_cache", None), "window": self._sample_promise}
         for dst, src in zip(ent["static"], ins):
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
@@ -849,7 +949,8 @@ class FluxControlNetPipeline:
     def _zero_samples_for(cache, window) -> None:
         """The tower sample buffers of ``cache`` (a ``_sample_cache`` tuple) must read zero outside ``window``, whose rows alone the
         zero-linears will write. They are zeroed once, when the window is set or changes, not per step; the tuple's last element
-        remembers the window they are valid for (None: no promise — the full path overwrites every row)."""
+        remembers the window they are valid for (None: no promise — the full path overwrites every row, and a call with a union tower,
+        which writes every row at its steps, zeroes inside its own step sequence instead)."""
         if cache is None:
             return
         state = cache[3]
@@ -860,11 +961,13 @@ class FluxControlNetPipeline:
 
     def _denoise_eager(self, latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale,
                        cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _quiet=False,
-                       _ip_embeds=None, _extra_towers=(), _velocity=None, _tower_window=None):
+                       _ip_embeds=None, _extra_towers=(), _velocity=None, _tower_window=None, _union=None):
         """The one loop over timesteps, for both pipelines. ``_extra_towers``: (FluxControlNetModel, hint, conditioning scale) of
         towers evaluated after the text-line towers into the same sample buffers, unmasked (the inpaint tower). ``_velocity(i,
         noise_pred)``: what the scheduler steps with instead of the transformer's output (true CFG). With extra towers the loop stays
-        on one stream. ``_tower_window``: ``active_row_window`` of ``masks`` from the call prologue (None: every row)."""
+        on one stream. ``_tower_window``: ``active_row_window`` of ``masks`` from the call prologue (None: every row). ``_union``:
+        (FluxControlNetModel, hint, conditioning scale, active steps) of the base flow's second tower: unmasked, evaluated FIRST at its
+        own steps (``union_active_steps``), also where no text tower runs; it keeps the side stream and the text towers' row window."""
         device = latents.device
         B = latents.shape[0]
         guidance = torch.full((B,), float(guidance_scale), device=device, dtype=torch.float32) if self.transformer.config.guidance_embeds else None
@@ -887,6 +990,13 @@ class FluxControlNetPipeline:
             tab_c = self.controlnet.build_modulation_table(ts_c, g_tab, pooled)
             towers = [(self.controlnet, h, cn_scale, rowscales[line] if rowscales else None, tab_c) for line, h in enumerate(hints)]
             towers += [(m, h, s, None, m.build_modulation_table(ts_c, g_tab, pooled)) for m, h, s in _extra_towers]
+        # The union tower: its modulation table holds ITS active steps only and is indexed by position in that list (the text towers'
+        # table can be indexed by the step because they start at step 0).
+        utower, upos = None, {}
+        if _union is not None and _union[3] and isinstance(self.controlnet, FluxControlNetModel):
+            um, uh, us, uact = _union
+            utower = (um, uh, us, None, um.build_modulation_table([model_ts[i] for i in uact], g_tab, pooled))
+            upos = {step: k for k, step in enumerate(uact)}
 
         # Loop-invariant work, once per image instead of once per step (the prompt and the hint latents do not change inside the
         # loop): context_embedder(prompt) of every model, controlnet_x_embedder(hint) per tower. A callback that replaces
@@ -895,6 +1005,7 @@ class FluxControlNetPipeline:
             return self.transformer.prepare_static(pe), [tw[0].prepare_static(pe, tw[1]) for tw in towers]
 
         static_t, static_c = prepare_static(prompt_embeds)
+        static_u = utower[0].prepare_static(prompt_embeds, utower[1]) if utower is not None else None
         # the image prompt's tokens and every block's K/V of them: loop-invariant too (ip_adapter.py steps 1-2)
         ip_prep = self.transformer._ip_adapter.prepare(_ip_embeds) if _ip_embeds is not None else None
         # Which tower samples does the transformer read? Block i takes sample i // ceil(n_blocks / n_samples) (A.3): with 6
@@ -902,11 +1013,12 @@ class FluxControlNetPipeline:
         # An extra tower of another depth adds into the first tower's buffers (it must not be deeper: there is one buffer per block
         # of the first tower) and every block of every tower is then evaluated.
         blocks_needed, sample_buf, single_buf = None, None, None
-        if fused_cn:
+        if fused_cn or utower is not None:
             cnet = self.controlnet
             n_cd, n_cs = len(cnet.transformer_blocks), len(cnet.single_transformer_blocks)
             n_td, n_ts = len(self.transformer.transformer_blocks), len(self.transformer.single_transformer_blocks)
-            if all((len(m.transformer_blocks), len(m.single_transformer_blocks)) == (n_cd, n_cs) for m, _, _ in _extra_towers):
+            others = [m for m, _, _ in _extra_towers] + ([utower[0]] if utower is not None else [])
+            if all((len(m.transformer_blocks), len(m.single_transformer_blocks)) == (n_cd, n_cs) for m in others):
                 need_d = 0 if n_cd == 0 else (n_td - 1) // int(np.ceil(n_td / n_cd)) + 1
                 need_s = 0 if n_cs == 0 or n_ts == 0 else (n_ts - 1) // int(np.ceil(n_ts / n_cs)) + 1
                 blocks_needed = (min(need_d, n_cd), min(need_s, n_cs))
@@ -924,8 +1036,13 @@ class FluxControlNetPipeline:
                 and blocks_needed[0] >= 1 and blocks_needed[1] == 0 and self.controlnet.supports_row_window()):
             window = _tower_window
         self._tower_window_used = window
-        if fused_cn:
-            self._zero_samples_for(self._sample_cache, window)
+        # A union step writes every row, so with a union tower the "rows outside the window read zero" promise is kept by the step
+        # sequence itself: the buffers count as dirty from the start and after every union step, and the first text-only step that
+        # follows zeroes them on the tower's stream (captured with the loop; one fill per transition of the union interval).
+        self._sample_promise = None if utower is not None else window
+        if fused_cn or utower is not None:
+            self._zero_samples_for(self._sample_cache, self._sample_promise)
+        dirty = utower is not None
         # fp32 master copy of the latents between steps (the models read its bf16 copy): the scheduler computes in fp32 anyway
         # (A.6); not rounding the STATE 28 times keeps the loop close to the fp32 reference path. Callbacks see the bf16 copy.
         lat32 = latents.to(torch.float32).contiguous()
@@ -938,7 +1055,9 @@ class FluxControlNetPipeline:
         # On by default (OVERLAP_TOWER; RT_OVERLAP_TOWER=0 turns it off): -0.5 % eager, -1.1 % inside the captured graph.
         # `not _extra_towers`: the inpaint flow is serial by decision (its second tower has no side stream or "tower" workspace of its
         # own yet); an extra tower added to the BASE flow would switch the overlap off here too — extend this rule then, not the call.
-        overlap = (OVERLAP_TOWER and bool(towers) and not _extra_towers and device.type == "cuda"
+        # The base flow's union tower shares the side stream and the "tower" workspace with the text towers: the towers of a step are
+        # serial with each other, only the transformer runs beside them.
+        overlap = (OVERLAP_TOWER and (bool(towers) or utower is not None) and not _extra_towers and device.type == "cuda"
                    and len(self.controlnet.single_transformer_blocks) == 0)
         side = sample_ev = None
         if overlap:
@@ -952,7 +1071,40 @@ class FluxControlNetPipeline:
                     continue
                 timestep = torch.full((B,), self._model_timestep(t), device=device, dtype=torch.float32)      # PIPE:1025,1048 (Q4)
                 merged = merged_single = events = None
-                if towers and i < cn_steps:
+                if utower is not None:
+                    # per-step tower list: the union tower first (it overwrites every row of the buffers), then the text lines
+                    step_towers = ([(utower, static_u, upos[i], None)] if i in upos else []) + \
+                                  ([(tw, st, i, window) for tw, st in zip(towers, static_c)] if towers and i < cn_steps else [])
+                    if step_towers:
+                        if overlap:
+                            side.wait_stream(torch.cuda.current_stream())
+                            events = sample_ev
+                        with torch.cuda.stream(side) if overlap else contextlib.nullcontext():
+                            if i in upos:
+                                dirty = True
+                            elif window is not None and dirty:       # text-only step after a union step (or the first one of the call)
+                                for buf in sample_buf:
+                                    buf.zero_()
+                                dirty = False
+                            done_d = done_s = 0                        # leading buffers already written in this step: add to those
+                            for k, ((model, hint, scale, rowscale, table), static, pos, win_k) in enumerate(step_towers):
+                                last = k == len(step_towers) - 1
+                                bs, ss = model(
+                                    hidden_states=latents, controlnet_cond=hint, controlnet_mode=control_mode, conditioning_scale=scale,
+                                    timestep=timestep, guidance=guidance, pooled_projections=pooled, encoder_hidden_states=prompt_embeds,
+                                    txt_ids=text_ids, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs,
+                                    return_dict=False, _rowscale=rowscale, _accumulate_into=sample_buf, _accumulate_single_into=single_buf,
+                                    _overwrite=(done_d, done_s), _sample_events=events if last else None, _mods=table.step(pos),
+                                    _ws_tag="tower" if overlap else "", _static=static, _blocks_needed=blocks_needed, _window=win_k)
+                                done_d = max(done_d, sum(b is not None for b in bs or ()))
+                                done_s = max(done_s, sum(b is not None for b in ss or ()))
+                            if events is not None:
+                                for ev in events[done_d:]:             # a shallower union tower alone: nothing writes (or reads) these
+                                    ev.record(torch.cuda.current_stream())
+                        # buffers no tower of this step wrote are not injected (None), the block-to-sample map keeps the first tower's depth
+                        merged = [b if j < done_d else None for j, b in enumerate(sample_buf)] or None
+                        merged_single = [b if j < done_s else None for j, b in enumerate(single_buf)] or None
+                elif towers and i < cn_steps:
                     if overlap:
                         side.wait_stream(torch.cuda.current_stream())    # latents of this step (and, at i = 0, tables and hints) are ready
                         events = sample_ev                               # recorded by the last tower, once the sums are complete
@@ -987,6 +1139,7 @@ class FluxControlNetPipeline:
                     if "prompt_embeds" in out:                       # the loop-invariant embeddings are no longer valid
                         prompt_embeds = out.pop("prompt_embeds")
                         static_t, static_c = prepare_static(prompt_embeds)
+                        static_u = utower[0].prepare_static(prompt_embeds, utower[1]) if utower is not None else None
                 if i == len(tvals) - 1 or ((i + 1) > num_warmup and (i + 1) % self.scheduler.order == 0):
                     bar.update()
         self._master_latents = lat32          # fp32 state of the loop; `latents` is its bf16 copy

@@ -10,6 +10,8 @@ encoders, which sit outside the hot path. With real checkpoints on disk use `Flu
     python tools/infer_demo.py --ip-image photo.jpg   # adds an image prompt: CLIP ViT-L/14 vision encoder + a 4-token IP-Adapter, random weights
     python tools/infer_demo.py --ip-image photo.jpg --ip-layout instantx   # the InstantX layout instead: SigLIP-so400m encoder (1152-wide
                                               # pooler_output) + a 128-token adapter with a term in all 19 + 38 blocks, random weights
+    python tools/infer_demo.py --union-image photo.jpg [--union-scale 0.7 --union-end 0.8]   # a second ControlNet (Union-Pro-2.0 shape,
+                                              # random weights) steered by the device Canny of the photo, beside the RepText tower
     python tools/infer_demo.py --inpaint      # infer_inpaint.py's flow (infer_inpaint.py:48-155): second 68-channel tower, masked
                                               # background image, position mask = bbox+-5, true CFG with negative embeddings
 """
@@ -21,7 +23,7 @@ from PIL import ImageFont
 from controlnet_flux import FluxControlNetModel
 from pipeline_flux_controlnet import FluxControlNetPipeline
 from reptext_amd import hints
-from reptext_amd.config import flux_dev_transformer_config, flux_vae_config, reptext_controlnet_config
+from reptext_amd.config import flux_dev_transformer_config, flux_vae_config, reptext_controlnet_config, union_pro2_controlnet_config
 from reptext_amd.scheduler import FlowMatchEulerDiscreteScheduler
 from reptext_amd.transformer import FluxTransformer2DModel
 from reptext_amd.vae import AutoencoderKL
@@ -34,6 +36,9 @@ ap.add_argument("--out", default="gpurun_out/result.jpg")
 ap.add_argument("--inpaint", action="store_true")
 ap.add_argument("--ip-image", default=None, help="image prompt for the text-to-image flow (ip_adapter_image=)")
 ap.add_argument("--ip-layout", choices=("xlabs", "instantx"), default="xlabs", help="adapter + encoder pair behind --ip-image")
+ap.add_argument("--union-image", default=None, help="photo whose Canny edges steer the second ControlNet (control_image_union=)")
+ap.add_argument("--union-scale", type=float, default=0.7)
+ap.add_argument("--union-end", type=float, default=0.8)
 a = ap.parse_args()
 dev, bf16 = torch.device("cuda:0"), torch.bfloat16
 ct, cc = flux_dev_transformer_config(), reptext_controlnet_config()
@@ -101,6 +106,15 @@ if a.ip_image:
         pipe.load_ip_adapter(adapter_sd(pipe.transformer, 4, dev, seed=5))
     pipe.set_ip_adapter_scale(0.7)
     ip_kwargs = dict(ip_adapter_image=Image.open(a.ip_image))
+
+if a.union_image:
+    import numpy as np
+    from PIL import Image
+
+    pipe.controlnet_union = FluxControlNetModel(**union_pro2_controlnet_config(num_layers=cc["num_layers"]), device=dev, dtype=bf16).random_init_(seed=6)
+    photo = np.asarray(Image.open(a.union_image).convert("RGB").resize((width, height)))
+    ip_kwargs.update(control_image_union=hints.canny_hint_device(photo, dev, 100, 200, invert=False),      # [1,3,H,W] in [-1,1]
+                     controlnet_conditioning_scale_union=a.union_scale, control_guidance_end_union=a.union_end)
 
 for it in range(2):
     torch.cuda.synchronize(); t0 = time.perf_counter()
