@@ -409,6 +409,20 @@ __global__ void euler_step_f32_kernel(float* __restrict__ x, const bf16_t* __res
   }
 }
 
+// true CFG fused into the fp32 master step: v = u + s·(t − u) from the two bf16 halves of the transformer's output, kept in fp32 (the
+// mixed velocity is never rounded to bf16), then the same `x + ds * v` expression as euler_step_f32_kernel: with t == u the mix is
+// u exactly (u + s·0) and the step is that kernel's, bit for bit.
+__global__ void cfg_euler_step_f32_kernel(float* __restrict__ x, const bf16_t* __restrict__ u, const bf16_t* __restrict__ t,
+                                          bf16_t* __restrict__ xb, float s, float ds, int64_t n) {
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float a = bf16_to_f32(u[i]), b = bf16_to_f32(t[i]);
+    const float v = a + s * (b - a);
+    const float r = x[i] + ds * v;
+    x[i] = r;
+    if (xb) xb[i] = f32_to_bf16(r);
+  }
+}
+
 __global__ void cfg_mix_kernel(const bf16_t* __restrict__ u, const bf16_t* __restrict__ t, bf16_t* __restrict__ o,
                                float s, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -736,6 +750,14 @@ int rt_euler_step_f32(float* x, const void* v, void* x_bf16, float dsigma, int64
   if (!x || !v || n < 1) return RT_E_BADARG;
   hipLaunchKernelGGL(euler_step_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)v,
                      (bf16_t*)x_bf16, dsigma, n);
+  return rt_hip_status();
+}
+
+int rt_cfg_euler_step_f32(float* x, const void* v_uncond, const void* v_text, void* x_bf16, float s, float dsigma, int64_t n,
+                          void* stream) {
+  if (!x || !v_uncond || !v_text || n < 1) return RT_E_BADARG;
+  hipLaunchKernelGGL(cfg_euler_step_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x,
+                     (const bf16_t*)v_uncond, (const bf16_t*)v_text, (bf16_t*)x_bf16, s, dsigma, n);
   return rt_hip_status();
 }
 

@@ -698,6 +698,18 @@ def euler_step_f32_(x32: torch.Tensor, v: torch.Tensor, dsigma: float, x_bf16: O
     return x32
 
 
+def cfg_euler_step_f32_(x32: torch.Tensor, v_uncond: torch.Tensor, v_text: torch.Tensor, s: float, dsigma: float,
+                       x_bf16: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x32 += dsigma*(u + s*(t - u)) on an fp32 master state, the mix kept in fp32; optionally refreshes its bf16 copy."""
+    if not (x32.is_contiguous() and v_uncond.is_contiguous() and v_text.is_contiguous()) or not (x32.shape == v_uncond.shape == v_text.shape):
+        raise ValueError("cfg_euler_step_f32_: contiguous tensors of equal shape")
+    if x_bf16 is not None and (x_bf16.shape != x32.shape or not x_bf16.is_contiguous()):
+        raise ValueError("x_bf16 must match x32")
+    native.call("rt_cfg_euler_step_f32", _dev(x32, "x32", F32), _dev(v_uncond, "v_uncond", BF16), _dev(v_text, "v_text", BF16),
+                _opt(x_bf16, "x_bf16", BF16), float(s), float(dsigma), x32.numel(), _stream())
+    return x32
+
+
 def cfg_mix(v_uncond: torch.Tensor, v_text: torch.Tensor, s: float) -> torch.Tensor:
     u, t = v_uncond.contiguous(), v_text.contiguous()
     out = torch.empty_like(t)

@@ -153,6 +153,35 @@ def accepts_union_arguments(call):
     return wrapper
 
 
+TRUE_CFG_ARGUMENTS = ("negative_prompt", "negative_prompt_2", "true_cfg_scale", "negative_prompt_embeds", "negative_pooled_prompt_embeds",
+                      "negative_ip_adapter_image", "negative_ip_adapter_image_embeds")
+
+
+def accepts_true_cfg_arguments(call):
+    """The negative prompt's seven arguments (``TRUE_CFG_ARGUMENTS``; diffusers' names, rules recalled: DESIGN.md §7) are keyword-only
+    extensions of the BASE pipeline's ``__call__``, taken off here like the union tower's (``accepts_union_arguments``) and left on the
+    pipeline as ``_cfg_call_args`` for the duration of the call; what the call derives from them (``_cfg_scale``, read by ``_denoise``)
+    is cleared with them."""
+    @functools.wraps(call)
+    def wrapper(self, *args, negative_prompt=None, negative_prompt_2=None, true_cfg_scale: float = 1.0, negative_prompt_embeds=None,
+                negative_pooled_prompt_embeds=None, negative_ip_adapter_image=None, negative_ip_adapter_image_embeds=None, **kwargs):
+        self._cfg_call_args = dict(negative_prompt=negative_prompt, negative_prompt_2=negative_prompt_2, true_cfg_scale=true_cfg_scale,
+                                   negative_prompt_embeds=negative_prompt_embeds, negative_pooled_prompt_embeds=negative_pooled_prompt_embeds,
+                                   negative_ip_adapter_image=negative_ip_adapter_image,
+                                   negative_ip_adapter_image_embeds=negative_ip_adapter_image_embeds)
+        try:
+            return call(self, *args, **kwargs)
+        finally:
+            self._cfg_call_args, self._cfg_scale = None, None
+    return wrapper
+
+
+def do_true_cfg(true_cfg_scale, negative_prompt=None, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None) -> bool:
+    """diffusers' rule (recalled): a scale above 1 AND a negative prompt, as text or as both embeddings."""
+    has_negative = negative_prompt is not None or (negative_prompt_embeds is not None and negative_pooled_prompt_embeds is not None)
+    return bool(float(true_cfg_scale) > 1 and has_negative)
+
+
 class FluxControlNetPipeline:
     model_cpu_offload_seq = "text_encoder->text_encoder_2->transformer->vae"
     _optional_components: List[str] = []
@@ -177,6 +206,8 @@ class FluxControlNetPipeline:
         # by from_pretrained(controlnet_union=) or assigned, fed by __call__(control_image_union=...) — base pipeline only
         self.controlnet_union: Optional[FluxControlNetModel] = None
         self._union_call_args, self._union = None, None
+        # the negative prompt of a call (true CFG, base pipeline only): accepts_true_cfg_arguments / _check_true_cfg_inputs
+        self._cfg_call_args, self._cfg_scale = None, None
 
     # ------------------------------------------------------------------ component plumbing
     @property
@@ -499,6 +530,9 @@ class FluxControlNetPipeline:
         out = []
         if control_mask is not None:
             for m in control_mask:
+                if isinstance(m, torch.Tensor) and m.dim() == 3 and m.shape[-1] == 1:
+                    out.append(m.to(device=device, dtype=dtype))      # an extension, like packed hints: token masks, one per image [B,N,1]
+                    continue
                 arr = np.array(m)
                 if torch.device(device).type == "cuda" and arr.dtype == np.uint8 and arr.ndim == 2:
                     t = ops.resize2d(torch.from_numpy(arr).to(device)[None, None], scale_factor=1 / 16, mode="bilinear", u8_scale=255.0)
@@ -711,7 +745,98 @@ class FluxControlNetPipeline:
         lat = ((self.vae.encode(image.to(self.vae.dtype)).latent_dist.sample() - sf) * sc).to(dtype)
         return self._pack_latents(lat, lat.shape[0], lat.shape[1], lat.shape[2], lat.shape[3])
 
+    # ------------------------------------------------------------------ the negative prompt (true CFG)
+    def _check_true_cfg_inputs(self, prompt_embeds, pooled_prompt_embeds, batch_size, joint_attention_kwargs) -> bool:
+        """Refusals of the call's negative-prompt arguments — host-side checks on types and shapes only, made before any device work
+        and whether or not the scale switches CFG on. True when this call runs true CFG (``do_true_cfg``); a scale above 1 without a
+        negative prompt logs one line and is the plain call."""
+        a = self._cfg_call_args
+        if a is None:
+            return False
+        neg, neg2 = a["negative_prompt"], a["negative_prompt_2"]
+        npe, npooled = a["negative_prompt_embeds"], a["negative_pooled_prompt_embeds"]
+        if (npe is None) != (npooled is None):
+            missing = "negative_pooled_prompt_embeds" if npooled is None else "negative_prompt_embeds"
+            raise ValueError(f"`{missing}` is missing: negative_prompt_embeds and negative_pooled_prompt_embeds have to be passed together")
+        for name, value in (("negative_prompt", neg), ("negative_prompt_2", neg2)):
+            if value is not None and npe is not None:
+                raise ValueError(f"Cannot forward both `{name}` and `negative_prompt_embeds`. Please make sure to only forward one of the two.")
+            if value is not None and not isinstance(value, (str, list)):
+                raise ValueError(f"`{name}` has to be of type `str` or `list` but is {type(value)}")
+            if isinstance(value, list) and len(value) != batch_size:
+                raise ValueError(f"`{name}`: {len(value)} negative prompts for a batch of {batch_size} prompts (one per prompt, or one string for all)")
+        if npe is not None and prompt_embeds is not None:
+            self._check_negative_embeds_shape(npe, npooled, prompt_embeds, pooled_prompt_embeds)
+        kw = joint_attention_kwargs or {}
+        positive_ip = any(x is not None for x in self._ip_call_args) or "ip_adapter_image_embeds" in kw
+        for name in ("negative_ip_adapter_image", "negative_ip_adapter_image_embeds"):
+            if a[name] is not None and not positive_ip:
+                raise ValueError(f"`{name}` was passed without a positive image prompt (ip_adapter_image / ip_adapter_image_embeds)")
+        if a["negative_ip_adapter_image"] is not None and a["negative_ip_adapter_image_embeds"] is not None:
+            raise ValueError("pass either negative_ip_adapter_image or negative_ip_adapter_image_embeds, not both")
+        on = do_true_cfg(a["true_cfg_scale"], neg, npe, npooled)
+        if not on and float(a["true_cfg_scale"]) > 1:
+            import sys
+            print(f"[reptext_amd] true_cfg_scale = {a['true_cfg_scale']} without a negative prompt: classifier-free guidance stays off",
+                  file=sys.stderr, flush=True)
+        return on
+
+    @staticmethod
+    def _check_negative_embeds_shape(npe, npooled, prompt_embeds, pooled_prompt_embeds) -> None:
+        if tuple(npe.shape) != tuple(prompt_embeds.shape):
+            raise ValueError(f"`negative_prompt_embeds`: shape {tuple(npe.shape)} != prompt_embeds' {tuple(prompt_embeds.shape)}")
+        if tuple(npooled.shape) != tuple(pooled_prompt_embeds.shape):
+            raise ValueError(f"`negative_pooled_prompt_embeds`: shape {tuple(npooled.shape)} != pooled_prompt_embeds' "
+                             f"{tuple(pooled_prompt_embeds.shape)}")
+
+    def _encode_negative_prompt(self, prompt_embeds, pooled_prompt_embeds, batch_size, num_images_per_prompt, max_sequence_length, device):
+        """(negative prompt_embeds, negative pooled) of this call, shaped like the positive ones: the embeddings as passed, or the
+        negative prompt through ``encode_prompt`` (``negative_prompt_2`` defaults to ``negative_prompt``; one string serves the batch)."""
+        a = self._cfg_call_args
+        npe, npooled = a["negative_prompt_embeds"], a["negative_pooled_prompt_embeds"]
+        if npe is None:
+            per_prompt = lambda p: [p] * batch_size if isinstance(p, str) else p
+            neg = per_prompt(a["negative_prompt"])
+            neg2 = per_prompt(a["negative_prompt_2"]) if a["negative_prompt_2"] is not None else neg
+            npe, npooled, _ = self.encode_prompt(prompt=neg, prompt_2=neg2, device=device, num_images_per_prompt=num_images_per_prompt,
+                                                 max_sequence_length=max_sequence_length)
+        self._check_negative_embeds_shape(npe, npooled, prompt_embeds, pooled_prompt_embeds)
+        return npe.to(device=device, dtype=prompt_embeds.dtype), npooled.to(device=device, dtype=pooled_prompt_embeds.dtype)
+
+    def _negative_ip_embeds(self, positive: torch.Tensor, total: int, device) -> torch.Tensor:
+        """The image prompt of the negative half, shaped like ``positive`` ([total or 1, E], what ``_resolve_ip_embeds`` returned):
+        ``negative_ip_adapter_image_embeds`` if given, else ``negative_ip_adapter_image`` through ``encode_image``, else an all-black
+        image through the same encoder when the positive one was an image, else a zero embedding."""
+        from . import ip_adapter as _ipa
+
+        a = self._cfg_call_args
+        neg_image, neg_embeds = a["negative_ip_adapter_image"], a["negative_ip_adapter_image_embeds"]
+        if neg_embeds is None and neg_image is None and self._ip_call_args[0] is not None:
+            if self.image_encoder is not None:
+                neg_image = self._black_image(self.image_encoder.config.image_size)
+        if neg_embeds is None and neg_image is not None:
+            if self.image_encoder is None:
+                raise NotImplementedError("negative_ip_adapter_image needs an image encoder, which this pipeline does not have: encode the "
+                                          "image yourself and pass negative_ip_adapter_image_embeds")
+            neg_embeds = self.encode_image(neg_image, device)
+        if neg_embeds is None:
+            return torch.zeros_like(positive)
+        e = _ipa.normalize_embeds(neg_embeds).to(device=device, dtype=torch.bfloat16)
+        if e.shape[1] != positive.shape[1]:
+            raise ValueError(f"negative_ip_adapter_image_embeds: width {e.shape[1]} != the adapter's image embedding width {positive.shape[1]}")
+        if e.shape[0] not in (1, positive.shape[0]):
+            raise ValueError(f"negative_ip_adapter_image_embeds: batch {e.shape[0]} is neither 1 nor the positive image prompt's {positive.shape[0]}")
+        return e.expand(positive.shape[0], -1)
+
+    @staticmethod
+    def _black_image(size: int):
+        """The default negative image prompt: an all-black PIL image, preprocessed and encoded like any other."""
+        from PIL import Image
+
+        return Image.new("RGB", (size, size), (0, 0, 0))
+
     # ------------------------------------------------------------------ the call
+    @accepts_true_cfg_arguments
     @accepts_union_arguments
     @accepts_ip_adapter_arguments
     @torch.no_grad()
@@ -740,21 +865,39 @@ class FluxControlNetPipeline:
         device, dtype = self._execution_device, self.transformer.dtype
         total = batch_size * num_images_per_prompt
         with_union = self._check_union_inputs(height, width, total)
+        cfg = self._check_true_cfg_inputs(prompt_embeds, pooled_prompt_embeds, batch_size, joint_attention_kwargs)
         self._ip_embeds, self._joint_attention_kwargs = self._resolve_ip_embeds(*self._ip_call_args, joint_attention_kwargs, batch_size,
                                                                                 num_images_per_prompt, device)
+        if cfg and self._ip_embeds is not None:
+            # [2·total, E], negative first like the prompt: rt_ip_attention takes K/V per entry of the conditioning batch
+            pos = self._ip_embeds.expand(total, -1)
+            self._ip_embeds = torch.cat([self._negative_ip_embeds(pos, total, device), pos], dim=0).contiguous()
 
         prompt_embeds, pooled_prompt_embeds, text_ids = self.encode_prompt(
             prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds, device=device,
             num_images_per_prompt=num_images_per_prompt, max_sequence_length=max_sequence_length)
         prompt_embeds = prompt_embeds.to(device=device)
         pooled_prompt_embeds = pooled_prompt_embeds.to(device=device)
+        if cfg:
+            # True CFG: the conditioning batch is cat([negative, positive]) (negative first, INP:1034-1035) against latents of batch B;
+            # the models repeat the latents over it, and the step mixes the two halves of the velocity (_denoise_eager: _cfg_scale)
+            npe, npooled = self._encode_negative_prompt(prompt_embeds, pooled_prompt_embeds, batch_size, num_images_per_prompt,
+                                                        max_sequence_length, device)
+            prompt_embeds = torch.cat([npe, prompt_embeds], dim=0)
+            pooled_prompt_embeds = torch.cat([npooled, pooled_prompt_embeds], dim=0)
+            self._cfg_scale = float(self._cfg_call_args["true_cfg_scale"])
 
-        hints, height, width = self._collect_hints(control_image, control_position, height, width, total, num_images_per_prompt, device, dtype)
+        hints, height, width = self._collect_hints(control_image, control_position, height, width, total, num_images_per_prompt, device, dtype,
+                                                   cfg=cfg)
         # the union hint is encoded AFTER the text lines' hints: a call without it draws the same random numbers as before
         union_hint = self._union_hint(self._union_call_args[0], width, height, total, num_images_per_prompt, device, dtype) if with_union else None
+        if cfg and union_hint is not None and union_hint.shape[0] == total:
+            union_hint = torch.cat([union_hint] * 2)
         timesteps, num_inference_steps = self._schedule(height, width, num_inference_steps, timesteps, device)
         latents, latent_image_ids = self._initial_latents(control_glyph, total, height, width, prompt_embeds.dtype, device, generator, latents)
         masks = self._region_masks(control_mask, latents.device, latents.dtype)
+        if cfg:
+            masks = [torch.cat([m] * 2) if m.shape[0] == total and total > 1 else m for m in masks]      # per image [B,N,1]; [1,N,1] is shared
         if with_union:
             _, u_scale, u_start, u_end = self._union_call_args
             active = union_active_steps(len(timesteps), float(u_start), float(u_end))
@@ -851,11 +994,12 @@ class FluxControlNetPipeline:
         # the rows the regional masks leave non-zero: read here, never inside the loop or a capture; part of the call signature below
         win = active_row_window(masks, latents.shape[1]) if masks and len(masks) == len(hints) else None
         union = getattr(self, "_union", None)         # (tower, hint, scale, active steps) of this call's second ControlNet, or None
+        cfg_scale = getattr(self, "_cfg_scale", None)  # true CFG of this call: prompt_embeds / pooled / hints hold [negative, positive]
 
         def eager(callback=None):
             return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
                                        cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe,
-                                       _tower_window=win, _union=union)
+                                       _tower_window=win, _union=union, _cfg_scale=cfg_scale)
 
         use_graph = (GRAPH_CAPTURE and getattr(self, "capture_graphs", True) and callback is None and latents.is_cuda
                      and not self.interrupt and isinstance(self.controlnet, (FluxControlNetModel, type(None)))
@@ -879,6 +1023,9 @@ class FluxControlNetPipeline:
         if union is not None:
             # the union hint is one more static input; the tower's scale and its active steps are baked into the capture
             key += ("union", ident(union[0]), sig(union[1]), union[2], union[3])
+        if cfg_scale is not None:
+            # the scale is a kernel scalar of every step (rt_cfg_euler_step_f32); the static inputs' shapes already carry the batch 2B
+            key += (("cfg", cfg_scale),)
         cache = self.__dict__.setdefault("_graph_cache", {})
         ent = cache.get(key)
         if ent is None:                                      # first sight of this signature: eager (and warm), remember it
@@ -913,7 +1060,8 @@ class FluxControlNetPipeline:
                     out = self._denoise_eager(static[0], static[1], static[2], static[3], static[4], tvals, static[5 : 5 + nh], static[5 + nh : 5 + nh + nm],
                                               guidance_scale, cn_scale, cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps,
                                               _quiet=True, _ip_embeds=static[n_ip] if ipe is not None else None, _tower_window=win,
-                                              _union=None if union is None else (union[0], static[-1]) + tuple(union[2:]))
+                                              _union=None if union is None else (union[0], static[-1]) + tuple(union[2:]),
+                                              _cfg_scale=cfg_scale)
                     out32 = self._master_latents
             except Exception as e:                           # capture is an optimisation, never a requirement
                 import sys
@@ -961,13 +1109,15 @@ class FluxControlNetPipeline:
 
     def _denoise_eager(self, latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale,
                        cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _quiet=False,
-                       _ip_embeds=None, _extra_towers=(), _velocity=None, _tower_window=None, _union=None):
+                       _ip_embeds=None, _extra_towers=(), _velocity=None, _tower_window=None, _union=None, _cfg_scale=None):
         """The one loop over timesteps, for both pipelines. ``_extra_towers``: (FluxControlNetModel, hint, conditioning scale) of
         towers evaluated after the text-line towers into the same sample buffers, unmasked (the inpaint tower). ``_velocity(i,
         noise_pred)``: what the scheduler steps with instead of the transformer's output (true CFG). With extra towers the loop stays
         on one stream. ``_tower_window``: ``active_row_window`` of ``masks`` from the call prologue (None: every row). ``_union``:
         (FluxControlNetModel, hint, conditioning scale, active steps) of the base flow's second tower: unmasked, evaluated FIRST at its
-        own steps (``union_active_steps``), also where no text tower runs; it keeps the side stream and the text towers' row window."""
+        own steps (``union_active_steps``), also where no text tower runs; it keeps the side stream and the text towers' row window.
+        ``_cfg_scale``: true CFG of the base flow — the conditioning batch is [negative, positive] (2B against the latents' B) and the
+        step mixes the two halves of the velocity in fp32 (``scheduler.step_master_cfg_``); everything else just sees Bc = 2B."""
         device = latents.device
         B = latents.shape[0]
         guidance = torch.full((B,), float(guidance_scale), device=device, dtype=torch.float32) if self.transformer.config.guidance_embeds else None
@@ -977,7 +1127,7 @@ class FluxControlNetPipeline:
         # adaLN vectors of every block for every step, once per image (timesteps/guidance/pooled are loop-invariant inputs); under
         # true CFG the conditioning batch is 2B against the latents' B (Q6) and the tables take guidance at that batch
         model_ts = [self._model_timestep(t) for t in tvals]
-        g_tab = guidance if guidance is None or pooled.shape[0] == B else guidance.expand(pooled.shape[0]).contiguous()
+        g_tab = guidance if guidance is None or pooled.shape[0] == B else guidance.repeat(pooled.shape[0] // B)
         tab_t = self.transformer.build_modulation_table(model_ts, g_tab, pooled)
         fused_cn = isinstance(self.controlnet, FluxControlNetModel) and len(hints) > 0
         # The towers of a step, in evaluation order: (model, hint, conditioning scale, row scale, modulation table). One entry per
@@ -1129,7 +1279,10 @@ class FluxControlNetPipeline:
                     torch.cuda.current_stream().wait_stream(side)     # the tower has finished reading `latents` (its last sample is unused, Q5)
                 if _velocity is not None:
                     noise_pred = _velocity(i, noise_pred)
-                self.scheduler.step_master_(noise_pred, lat32, latents)
+                if _cfg_scale is not None:
+                    self.scheduler.step_master_cfg_(noise_pred[:B], noise_pred[B:], _cfg_scale, lat32, latents)
+                else:
+                    self.scheduler.step_master_(noise_pred, lat32, latents)
                 if callback is not None:
                     env = {"latents": latents, "prompt_embeds": prompt_embeds}
                     out = callback(self, i, timesteps[i], {k: env[k] for k in callback_inputs})

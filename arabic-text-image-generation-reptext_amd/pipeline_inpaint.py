@@ -55,8 +55,10 @@ class FluxControlNetPipeline(_BasePipeline):
             if negative_prompt_embeds is not None:
                 npe, npooled = negative_prompt_embeds, negative_pooled_prompt_embeds
             else:
-                neg = negative_prompt or DEFAULT_NEGATIVE_PROMPT
-                neg2 = negative_prompt_2 or neg
+                batch = pe.shape[0] // num_images_per_prompt            # one negative string serves every prompt of the batch
+                per_prompt = lambda p: [p] * batch if isinstance(p, str) else p
+                neg = per_prompt(negative_prompt or DEFAULT_NEGATIVE_PROMPT)
+                neg2 = per_prompt(negative_prompt_2) if negative_prompt_2 else neg
                 npooled = self._get_clip_prompt_embeds(neg, num_images_per_prompt, device)
                 npe = self._get_t5_prompt_embeds(neg2, num_images_per_prompt, max_sequence_length, device)
         return pe, pooled, npe, npooled, text_ids
@@ -115,9 +117,9 @@ class FluxControlNetPipeline(_BasePipeline):
         cfg = self.do_classifier_free_guidance                          # enabled by guidance_scale > 1, scaled by true_guidance_scale (Q8)
         device, dtype = self._execution_device, self.transformer.dtype
         total = self._batch_size(prompt, prompt_embeds) * num_images_per_prompt
-        if cfg and total != 1:
-            # INP:1033-1035,1145: latents keep batch B while the conditioning is 2B; the reference only broadcasts for B == 1 (Q6)
-            raise ValueError("classifier-free guidance in this pipeline supports a single image per call (batch 1), as the reference does")
+        # INP:1033-1035,1145: latents keep batch B while the conditioning is 2B = cat([negative × B, positive × B]). The reference only
+        # broadcasts for B == 1 (Q6); a larger batch is this project's: the models repeat the latents over the conditioning batch, hints
+        # and per-image masks are doubled, and chunk(2) below splits the velocity into its negative and positive halves.
 
         pe, pooled, npe, npooled, text_ids = self.encode_prompt(
             prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
@@ -142,6 +144,8 @@ class FluxControlNetPipeline(_BasePipeline):
         timesteps, num_inference_steps = self._schedule(height, width, num_inference_steps, timesteps, device)
         latents, image_ids = self._initial_latents(control_glyph, total, height, width, pe.dtype, device, generator, latents)
         masks = self._region_masks(control_mask, latents.device, latents.dtype)
+        if cfg:
+            masks = [torch.cat([m] * 2) if m.shape[0] == total and total > 1 else m for m in masks]      # per image [B,N,1]; [1,N,1] is shared
 
         def cfg_velocity(i, noise_pred):
             """True CFG on the two halves of the conditioning batch (negative first, INP:1264-1270); zero velocity at step 0 (Q7)."""

@@ -99,6 +99,17 @@ class FlowMatchEulerDiscreteScheduler:
         ops.euler_step_f32_(sample32, model_output.contiguous(), float(self.sigmas[i + 1] - self.sigmas[i]), sample_bf16)
         self._step_index = i + 1
 
+    def step_master_cfg_(self, v_uncond: torch.Tensor, v_text: torch.Tensor, s: float, sample32: torch.Tensor,
+                         sample_bf16: Optional[torch.Tensor] = None) -> None:
+        """``step_master_`` with the velocity ``v_uncond + s·(v_text − v_uncond)`` (true CFG), mixed in fp32 inside the step's kernel:
+        the mix is not rounded to bf16 before the fp32 state takes it. Advances the step index exactly like ``step_master_``."""
+        if self._step_index is None:
+            self._step_index = self._begin_index if self._begin_index is not None else 0
+        i = self._step_index
+        ops.cfg_euler_step_f32_(sample32, v_uncond.contiguous(), v_text.contiguous(), float(s),
+                                float(self.sigmas[i + 1] - self.sigmas[i]), sample_bf16)
+        self._step_index = i + 1
+
     def step(self, model_output: torch.Tensor, timestep: Union[float, torch.Tensor], sample: torch.Tensor,
              return_dict: bool = True, **unused):
         if self._step_index is None:

@@ -430,6 +430,14 @@ int rt_euler_step_f32(float* x, const void* v, void* x_bf16 /* nullable */, floa
 /* True-CFG mix of the inpaint pipeline (INP:1264-1270): out = uncond + s·(text − uncond); bf16. */
 int rt_cfg_mix(const void* v_uncond, const void* v_text, void* out, float s, int64_t n, void* stream);
 
+/* True CFG of the text-to-image pipeline fused into the fp32 master step (pipeline._denoise_eager with a negative prompt, through
+ * scheduler.step_master_cfg_): x32 += dsigma·(u + s·(t − u)), u / t the bf16 halves [negative, positive] of the transformer's output
+ * widened to fp32. All in fp32: the mixed velocity is never rounded to bf16 (rt_cfg_mix + rt_euler_step_f32 would round it once per
+ * step before the fp32 state consumes it). x_bf16, when given, receives bf16(x32). With t == u this is rt_euler_step_f32(x, u, ...)
+ * bit for bit, for any s. NULL x / v_uncond / v_text or n < 1: RT_E_BADARG. */
+int rt_cfg_euler_step_f32(float* x, const void* v_uncond, const void* v_text, void* x_bf16 /* nullable */,
+                          float s, float dsigma, int64_t n, void* stream);
+
 /* _pack_latents / _unpack_latents (PIPE:550-570): [B][C][2h][2w] <-> [B][h*w][4C], channel order (c,dy,dx).
  * unpack also applies z/scaling + shift (PIPE:1137) and writes NHWC bf16 [B][H2][W2][C]. */
 int rt_pack_latents(const void* nchw, void* packed, int32_t B, int32_t C, int32_t H2, int32_t W2, void* stream);

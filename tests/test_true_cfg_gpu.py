@@ -1,0 +1,317 @@
+"""Negative prompts (true CFG) in the text-to-image pipeline on the GPU: parity with the CPU oracle's loop (tests/cfg_reference.py),
+alone, with the union tower and with both IP-Adapter forms, and the bitwise properties of the call — off means off, equal halves
+collapse to the plain call, eager = captured, batch invariance, the loop's toggles, the fp8 modes — plus batch > 1 under true CFG in
+the inpaint pipeline. 256x256 (N = 256, T = 64) with the reduced models of test_vae_pipeline_gpu.py, 3-4 steps."""
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+from oracle import flux_oracle as orc  # noqa: E402
+from test_models_gpu import assert_at_dtype_floor  # noqa: E402
+from test_vae_pipeline_gpu import SMALL_CN, SMALL_T, rel_l2  # noqa: E402
+
+import instantx_reference as ixr  # noqa: E402
+import ip_adapter_reference as ipr  # noqa: E402
+from cfg_reference import denoise_loop_cfg  # noqa: E402
+
+SMALL_UN = dict(SMALL_T, num_layers=2, num_single_layers=0)
+BOXES = ((48, 96, 30, 200), (100, 150, 60, 240))        # two text lines inside image rows 48..144 of 256: the row window is active
+H = W = 256
+N, T, E = 256, 64, 64
+
+
+def mask_images(boxes):
+    from PIL import Image
+
+    out = []
+    for box in boxes:
+        m = np.zeros([H, W], dtype=np.uint8); m[box[0]:box[1], box[2]:box[3]] = 255
+        out.append(Image.fromarray(m))
+    return out
+
+
+def token_mask(box):
+    m = np.zeros([H, W], dtype=np.uint8); m[box[0]:box[1], box[2]:box[3]] = 255
+    return torch.nn.functional.interpolate(torch.from_numpy(m)[None, None].float() / 255.0, scale_factor=1 / 16, mode="bilinear").reshape(1, -1, 1)
+
+
+def random_pipe(gpu, seed, union=False):
+    """(pipe, r): a base pipeline with random transformer and text tower (and union tower); r(*shape) draws bf16 device tensors."""
+    import reptext_amd.pipeline as P
+    from reptext_amd.controlnet import FluxControlNetModel
+    from reptext_amd.scheduler import FlowMatchEulerDiscreteScheduler
+    from reptext_amd.transformer import FluxTransformer2DModel
+
+    tr = FluxTransformer2DModel(**SMALL_T, device=gpu, dtype=torch.bfloat16).random_init_(seed)
+    cn = FluxControlNetModel(**SMALL_CN, device=gpu, dtype=torch.bfloat16).random_init_(seed + 1)
+    pipe = P.FluxControlNetPipeline(FlowMatchEulerDiscreteScheduler(), None, None, None, None, None, tr, cn)
+    if union:
+        pipe.controlnet_union = FluxControlNetModel(**SMALL_UN, device=gpu, dtype=torch.bfloat16).random_init_(seed + 2)
+    pipe.set_progress_bar_config(disable=True)
+    g = torch.Generator().manual_seed(seed)
+    return pipe, (lambda *s: torch.randn(*s, generator=g).to(gpu, torch.bfloat16))
+
+
+def two_line_call(r, steps=3, cn_steps=2, B=1):
+    """Two masked text lines (row window active), the tower on for cn_steps of the steps."""
+    return dict(prompt_embeds=r(B, T, 256), pooled_prompt_embeds=r(B, 64), height=H, width=W, num_inference_steps=steps, guidance_scale=3.5,
+                control_image=[r(B, N, 128), r(B, N, 128)], control_mask=mask_images(BOXES), controlnet_conditioning_step=cn_steps,
+                latents=r(B, N, 64), output_type="latent")
+
+
+def negatives(r, B=1):
+    return dict(negative_prompt_embeds=r(B, T, 256), negative_pooled_prompt_embeds=r(B, 64))
+
+
+def graph_keys(pipe):
+    return list(getattr(pipe, "_graph_cache", {}))
+
+
+# ------------------------------------------------------------------------------------------------------------------ 1. parity
+@pytest.mark.parametrize("case", ["plain", "union", "ip_diffusers", "ip_instantx"])
+def test_true_cfg_matches_the_oracle_loop(gpu, case):
+    """3 steps, one masked text line, s = 2.0, negative != positive embeddings: GPU error at the bf16-storage oracle's own floor, and
+    the plain loop (no negative half) is far from the reference. Also with the union tower on [0.3, 1.0] (text tower for 2 of the 3
+    steps) and with an image prompt with explicit negative embeds, for a diffusers-layout and an InstantX-layout adapter."""
+    from PIL import Image
+
+    from reptext_amd.controlnet import FluxControlNetModel
+    from reptext_amd.pipeline import FluxControlNetPipeline
+    from reptext_amd.scheduler import FlowMatchEulerDiscreteScheduler
+    from reptext_amd.transformer import FluxTransformer2DModel
+
+    tp = orc.init_mmdit_params(SMALL_T, seed=711)
+    cp = orc.init_mmdit_params(SMALL_CN, seed=712, controlnet=True)
+    tr = FluxTransformer2DModel(**SMALL_T, device=gpu, dtype=torch.bfloat16)
+    cn = FluxControlNetModel(**SMALL_CN, device=gpu, dtype=torch.bfloat16)
+    tr.load_state_dict(tp); cn.load_state_dict(cp)
+    pipe = FluxControlNetPipeline(FlowMatchEulerDiscreteScheduler(), None, None, None, None, None, tr, cn)
+    pipe.set_progress_bar_config(disable=True)
+    g = torch.Generator().manual_seed(713)
+    r = lambda *s: torch.randn(*s, generator=g).to(torch.bfloat16).float()
+    pe, pooled, npe, npooled, hint = r(1, T, 256), r(1, 64), r(1, T, 256), r(1, 64), r(1, N, 128)
+    # With these reduced random models the whole velocity moves the latents by a few per cent, and a negative prompt drawn like the
+    # positive one moves the result by 10 x the bf16 floor (measured on the CPU oracle alone). "The negative half is felt" is a
+    # condition on the inputs, so the negative embeddings are drawn three times as large: 25 x floor.
+    npe, npooled = (3 * npe).to(torch.bfloat16).float(), (3 * npooled).to(torch.bfloat16).float()
+    lat0 = orc.pack_latents(r(1, 16, 32, 32))
+    uhint, emb, nemb = r(1, N, 64), r(1, E), r(1, E)
+    mask_np = np.zeros([H, W], dtype=np.uint8)
+    mask_np[60:140, 80:200] = 255                                   # the box of test_pipeline_c1_latents_and_image
+    rm = token_mask((60, 140, 80, 200))
+    b16 = lambda t: t.to(gpu, torch.bfloat16)
+    cn_steps = 2 if case == "union" else 30
+    call = dict(prompt_embeds=b16(pe), pooled_prompt_embeds=b16(pooled), negative_prompt_embeds=b16(npe), negative_pooled_prompt_embeds=b16(npooled),
+                true_cfg_scale=2.0, height=H, width=W, num_inference_steps=3, guidance_scale=3.5, control_image=[b16(hint)],
+                control_mask=[Image.fromarray(mask_np)], controlnet_conditioning_scale=1.0, controlnet_conditioning_step=cn_steps,
+                latents=b16(lat0), output_type="latent")
+    rkw = dict(conditioning_scale=1.0, conditioning_step=cn_steps)
+    if case == "union":
+        up = orc.init_mmdit_params(SMALL_UN, seed=714, controlnet=True)
+        un = FluxControlNetModel(**SMALL_UN, device=gpu, dtype=torch.bfloat16)
+        un.load_state_dict(up)
+        pipe.controlnet_union = un
+        call.update(control_image_union=b16(uhint), controlnet_conditioning_scale_union=0.7, control_guidance_start_union=0.3,
+                    control_guidance_end_union=1.0)
+        rkw["union"] = dict(params=up, cfg=SMALL_UN, cond=uhint, scale=0.7, start=0.3, end=1.0)
+    elif case == "ip_diffusers":
+        ipp, scales = ipr.init_ip_params(SMALL_T, n_tokens=4, embed_dim=E, seed=715), [1.0, -0.7]
+        pipe.load_ip_adapter(ipp)
+        pipe.set_ip_adapter_scale(scales)
+        rkw["image_prompt"] = dict(forward=ipr.transformer_forward, ip_params=ipp, ip_scales=scales, embeds=emb, neg_embeds=nemb)
+    elif case == "ip_instantx":
+        ipp, scales = ixr.init_instantx_params(SMALL_T, n_tokens=16, embed_dim=E, seed=716, v_std=ixr.MODEL_V_STD), [1.0, -0.7, 0.9, -0.5, 0.6]
+        pipe.load_ip_adapter(ipp)
+        pipe.set_ip_adapter_scale(scales)
+        rkw["image_prompt"] = dict(forward=ixr.transformer_forward, ip_params=ipp, ip_scales=scales, embeds=emb, neg_embeds=nemb)
+    if case.startswith("ip_"):
+        call.update(ip_adapter_image_embeds=b16(emb), negative_ip_adapter_image_embeds=[b16(nemb)[:, None]])
+    sig = orc.flow_sigmas(3, orc.calculate_shift(N, 256, 4096, 0.5, 1.15))
+    args = (tp, SMALL_T, cp, SMALL_CN, lat0, pe, pooled, npe, npooled, [hint], [rm], sig, orc.latent_image_ids(32, 32), torch.zeros(T, 3), 3.5, 2.0)
+    ref = denoise_loop_cfg(*args, **rkw)
+    with orc.stored_as(torch.bfloat16):
+        ref16 = denoise_loop_cfg(*args, **rkw)
+    out = pipe(**call).images.float().cpu()
+    assert pipe._tower_window_used is not None
+    err, err16, floor = rel_l2(out, ref), rel_l2(out, ref16), rel_l2(ref16, ref)
+    plain = orc.denoise_loop(tp, SMALL_T, cp, SMALL_CN, lat0, pe, pooled, [hint], [rm], sig, orc.latent_image_ids(32, 32), torch.zeros(T, 3), 3.5,
+                             conditioning_step=cn_steps)
+    felt = rel_l2(plain, ref)
+    print(f"true CFG [{case}] latents rel-L2 {err:.3e} vs fp32 oracle, {err16:.3e} vs bf16-storage oracle (floor {floor:.3e}); the plain "
+          f"loop lies {felt:.3e} = {felt / floor:.0f} x floor away")
+    assert felt > 20 * floor
+    assert_at_dtype_floor(err, err16, floor)
+    if case.startswith("ip_"):
+        # the negative half's image prompt is felt: zeros in its place give another result
+        other = pipe(**{**call, "negative_ip_adapter_image_embeds": None}).images.float().cpu()
+        assert rel_l2(other, ref) > 3 * floor
+
+
+# ------------------------------------------------------------------------------------------------------------------ 2. off means off
+def test_off_means_off(gpu, capfd):
+    pipe, r = random_pipe(gpu, 721)
+    kw = two_line_call(r)
+    want = pipe(**kw).images.clone()
+    keys = graph_keys(pipe)
+    assert len(keys) == 1
+    assert not torch.equal(want, kw["latents"].float())
+    capfd.readouterr()
+    for extra in ({}, dict(true_cfg_scale=1.0, negative_prompt="blurry letters, extra text"), dict(true_cfg_scale=1.0, **negatives(r)),
+                  dict(true_cfg_scale=3.5)):
+        assert torch.equal(pipe(**kw, **extra).images, want), extra          # eager, captured, replayed, replayed
+        assert graph_keys(pipe) == keys
+    assert capfd.readouterr().err.count("true_cfg_scale") == 1             # the scale without a negative prompt: one line
+    assert sum(isinstance(v, dict) for v in pipe._graph_cache.values()) == 1
+    pipe.capture_graphs = False
+    calls = []
+    real = pipe.scheduler.step_master_
+    pipe.scheduler.step_master_ = lambda *a, **k: (calls.append(a[0].shape[0]), real(*a, **k))[1]
+    assert torch.equal(pipe(**kw, true_cfg_scale=3.5).images, want)
+    assert calls == [1, 1, 1]                                               # the plain step on a batch-1 velocity: the same launches
+
+
+# ------------------------------------------------------------------------------------------------------------------ 3. collapse
+def test_equal_halves_collapse_to_the_plain_call(gpu):
+    """Negative embeddings equal to the positive ones at s = 3.5: both halves of every launch hold the same rows (batch invariance,
+    test_block_batch4_invariance_at_c2_shape) and the step with equal halves is the plain step (test_cfg_step_kernel_gpu.py), so the
+    result is the plain call's bit for bit — eager and captured."""
+    pipe, r = random_pipe(gpu, 731)
+    kw = two_line_call(r)
+    same = dict(negative_prompt_embeds=kw["prompt_embeds"].clone(), negative_pooled_prompt_embeds=kw["pooled_prompt_embeds"].clone(),
+                true_cfg_scale=3.5)
+    pipe.capture_graphs = False
+    want = pipe(**kw).images.clone()
+    seen = []
+    real = pipe.scheduler.step_master_cfg_
+    pipe.scheduler.step_master_cfg_ = lambda u, t, *a, **k: (seen.append(torch.equal(u, t)), real(u, t, *a, **k))[1]
+    got = pipe(**kw, **same).images.clone()
+    assert seen == [True] * 3, "the two halves of the transformer's output differ: a launch is not batch invariant"
+    assert torch.equal(got, want)
+    pipe.scheduler.step_master_cfg_ = real
+    pipe.capture_graphs = True
+    for _ in range(3):
+        assert torch.equal(pipe(**kw, **same).images, want)
+    other = pipe(**kw, **dict(same, **negatives(r))).images
+    assert not torch.equal(other, want)                                     # and a real negative prompt is felt
+
+
+# ------------------------------------------------------------------------------------------------------------------ 4. eager = captured
+def test_cfg_loop_graph_replay_is_bitwise_the_eager_loop(gpu):
+    pipe, r = random_pipe(gpu, 741)
+    kw = dict(two_line_call(r), **negatives(r), true_cfg_scale=2.0)
+    pipe.capture_graphs = False
+    eager = pipe(**kw).images.clone()
+    plain = pipe(**{k: v for k, v in kw.items() if "negative" not in k and k != "true_cfg_scale"}).images.clone()
+    assert not torch.equal(eager, plain)
+    pipe.capture_graphs = True
+    for _ in range(3):                                                      # seen, captured, replayed
+        assert torch.equal(pipe(**kw).images, eager)
+    assert pipe.scheduler._step_index == 3
+    keys = graph_keys(pipe)
+    assert len(keys) == 1 and ("cfg", 2.0) in keys[0] and isinstance(pipe._graph_cache[keys[0]], dict)
+    # new negative VALUES, same signature: replayed, copied in
+    kw2 = dict(kw, **negatives(r))
+    pipe.capture_graphs = False
+    eager2 = pipe(**kw2).images.clone()
+    pipe.capture_graphs = True
+    assert torch.equal(pipe(**kw2).images, eager2) and not torch.equal(eager2, eager)
+    assert graph_keys(pipe) == keys
+    # a second scale is a second key with its own result
+    kw3 = dict(kw, true_cfg_scale=3.0)
+    pipe.capture_graphs = False
+    eager3 = pipe(**kw3).images.clone()
+    pipe.capture_graphs = True
+    for _ in range(2):
+        assert torch.equal(pipe(**kw3).images, eager3)
+    assert not torch.equal(eager3, eager)
+    assert len(graph_keys(pipe)) == 2 and ("cfg", 3.0) in graph_keys(pipe)[1]
+    assert torch.equal(pipe(**kw).images, eager)
+    assert pipe._cfg_call_args is None and pipe._cfg_scale is None
+
+
+# ------------------------------------------------------------------------------------------------------------------ 5. batch
+def test_cfg_batch_of_two_is_two_calls(gpu):
+    """B = 2 with per-sample prompts, negatives, hints and per-image token masks equals two B = 1 calls, bitwise per sample."""
+    pipe, r = random_pipe(gpu, 751)
+    pipe.capture_graphs = False
+    kw = dict(two_line_call(r, B=2), **negatives(r, B=2), true_cfg_scale=2.0)
+    per_image = [torch.cat([token_mask(a), token_mask(b)]).to(gpu, torch.bfloat16) for a, b in
+                 (((48, 96, 30, 200), (64, 112, 10, 120)), ((100, 150, 60, 240), (90, 140, 100, 250)))]
+    kw["control_mask"] = per_image
+    both = pipe(**kw).images.clone()
+    assert pipe._tower_window_used is not None
+    assert not torch.equal(both[0], both[1])
+    for b in range(2):
+        one = {k: (v[b : b + 1] if isinstance(v, torch.Tensor) else [t[b : b + 1] for t in v] if k in ("control_image", "control_mask") else v)
+               for k, v in kw.items()}
+        assert torch.equal(pipe(**one).images, both[b : b + 1]), b
+
+
+# ------------------------------------------------------------------------------------------------------------------ 6. toggles
+def test_overlap_and_row_window_are_bitwise_neutral_under_cfg(gpu, monkeypatch):
+    import reptext_amd.pipeline as P
+
+    pipe, r = random_pipe(gpu, 761, union=True)
+    pipe.capture_graphs = False
+    kw = dict(two_line_call(r, steps=4, cn_steps=4), **negatives(r), true_cfg_scale=2.0, control_image_union=r(1, N, 64),
+              controlnet_conditioning_scale_union=0.7, control_guidance_start_union=0.2, control_guidance_end_union=0.8)
+    monkeypatch.setattr(P, "OVERLAP_TOWER", False)
+    serial = pipe(**kw).images.clone()
+    assert pipe._tower_window_used is not None
+    monkeypatch.setattr(P, "OVERLAP_TOWER", True)
+    for _ in range(2):
+        assert torch.equal(pipe(**kw).images, serial)
+    assert pipe._tower_window_used is not None
+    monkeypatch.setattr(P, "TOWER_WINDOW", False)
+    for overlap in (False, True):
+        monkeypatch.setattr(P, "OVERLAP_TOWER", overlap)
+        assert torch.equal(pipe(**kw).images, serial)
+        assert pipe._tower_window_used is None
+    assert not torch.equal(pipe(**{k: v for k, v in kw.items() if "union" not in k}).images, serial)
+
+
+# ------------------------------------------------------------------------------------------------------------------ 7. precision modes
+def test_cfg_in_the_fp8_modes(gpu):
+    pipe, r = random_pipe(gpu, 771)
+    pipe.transformer.enable_fp8_linears("mx").enable_fp8_attention(True)
+    kw = dict(two_line_call(r), **negatives(r), true_cfg_scale=2.0)
+    pipe.capture_graphs = False
+    eager = pipe(**kw).images.clone()
+    assert bool(torch.isfinite(eager).all()) and not torch.equal(eager, kw["latents"].float())
+    pipe.capture_graphs = True
+    for _ in range(3):
+        assert torch.equal(pipe(**kw).images, eager)
+    assert sum(isinstance(v, dict) for v in pipe._graph_cache.values()) == 1
+
+
+# ------------------------------------------------------------------------------------------------------------------ 8. inpaint batch
+def test_inpaint_cfg_batch_of_two_is_two_calls(gpu):
+    """The inpaint pipeline under true CFG at B = 2 (packed hints, latents given, per-image token masks): each sample is the B = 1
+    call's, bit for bit. (B = 1 itself stays guarded by test_inpaint_pipeline_cfg_and_second_tower.)"""
+    from reptext_amd.controlnet import FluxControlNetModel
+    from reptext_amd.pipeline_inpaint import FluxControlNetPipeline as Inpaint
+    from reptext_amd.scheduler import FlowMatchEulerDiscreteScheduler
+    from reptext_amd.transformer import FluxTransformer2DModel
+
+    tr = FluxTransformer2DModel(**SMALL_T, device=gpu, dtype=torch.bfloat16).random_init_(781)
+    cn = FluxControlNetModel(**SMALL_CN, device=gpu, dtype=torch.bfloat16).random_init_(782)
+    cni = FluxControlNetModel(**dict(SMALL_CN, extra_condition_channels=4), device=gpu, dtype=torch.bfloat16).random_init_(783)
+    pipe = Inpaint(FlowMatchEulerDiscreteScheduler(), None, None, None, None, None, tr, cn, cni)
+    pipe.set_progress_bar_config(disable=True)
+    g = torch.Generator().manual_seed(784)
+    r = lambda *s: torch.randn(*s, generator=g).to(gpu, torch.bfloat16)
+    kw = dict(two_line_call(r, B=2, cn_steps=30), **negatives(r, B=2), true_guidance_scale=2.0, control_image_inpaint=r(2, N, 68),
+              controlnet_conditioning_scale_inpaint=0.9)
+    kw["control_mask"] = [torch.cat([token_mask(a), token_mask(b)]).to(gpu, torch.bfloat16) for a, b in
+                          (((48, 96, 30, 200), (64, 112, 10, 120)), ((100, 150, 60, 240), (90, 140, 100, 250)))]
+    both = pipe(**kw).images.clone()
+    assert not torch.equal(both[0], both[1]) and bool(torch.isfinite(both).all())
+    per_sample = ("control_image", "control_mask")
+    for b in range(2):
+        one = {k: (v[b : b + 1] if isinstance(v, torch.Tensor) else [t[b : b + 1] for t in v] if k in per_sample else v) for k, v in kw.items()}
+        assert torch.equal(pipe(**one).images, both[b : b + 1]), b
+    # the negative half is felt at B = 2 as well
+    felt = pipe(**dict(kw, **negatives(r, B=2))).images
+    assert not torch.equal(felt, both)

@@ -12,6 +12,9 @@ encoders, which sit outside the hot path. With real checkpoints on disk use `Flu
                                               # pooler_output) + a 128-token adapter with a term in all 19 + 38 blocks, random weights
     python tools/infer_demo.py --union-image photo.jpg [--union-scale 0.7 --union-end 0.8]   # a second ControlNet (Union-Pro-2.0 shape,
                                               # random weights) steered by the device Canny of the photo, beside the RepText tower
+    python tools/infer_demo.py --negative-prompt "blurry letters, extra text" --true-cfg-scale 3.5   # true CFG in the text-to-image flow:
+                                              # internal batch 2, [negative, positive]; without text encoders the negative embeddings are
+                                              # random tensors seeded by the text (with checkpoints: negative_prompt= goes through encode_prompt)
     python tools/infer_demo.py --inpaint      # infer_inpaint.py's flow (infer_inpaint.py:48-155): second 68-channel tower, masked
                                               # background image, position mask = bbox+-5, true CFG with negative embeddings
 """
@@ -39,6 +42,8 @@ ap.add_argument("--ip-layout", choices=("xlabs", "instantx"), default="xlabs", h
 ap.add_argument("--union-image", default=None, help="photo whose Canny edges steer the second ControlNet (control_image_union=)")
 ap.add_argument("--union-scale", type=float, default=0.7)
 ap.add_argument("--union-end", type=float, default=0.8)
+ap.add_argument("--negative-prompt", default=None, help="negative prompt of the text-to-image flow (true CFG; needs --true-cfg-scale > 1)")
+ap.add_argument("--true-cfg-scale", type=float, default=1.0)
 a = ap.parse_args()
 dev, bf16 = torch.device("cuda:0"), torch.bfloat16
 ct, cc = flux_dev_transformer_config(), reptext_controlnet_config()
@@ -115,6 +120,15 @@ if a.union_image:
     photo = np.asarray(Image.open(a.union_image).convert("RGB").resize((width, height)))
     ip_kwargs.update(control_image_union=hints.canny_hint_device(photo, dev, 100, 200, invert=False),      # [1,3,H,W] in [-1,1]
                      controlnet_conditioning_scale_union=a.union_scale, control_guidance_end_union=a.union_end)
+
+if a.negative_prompt is not None:
+    import zlib
+
+    gn = torch.Generator().manual_seed(zlib.crc32(a.negative_prompt.encode("utf-8")))     # no text encoders here: embeddings named by the text
+    ip_kwargs.update(negative_prompt_embeds=torch.randn(1, 512, 4096, generator=gn).to(dev, bf16),
+                     negative_pooled_prompt_embeds=torch.randn(1, 768, generator=gn).to(dev, bf16), true_cfg_scale=a.true_cfg_scale)
+elif a.true_cfg_scale != 1.0:
+    ip_kwargs.update(true_cfg_scale=a.true_cfg_scale)                               # logs one line: no negative prompt, CFG stays off
 
 for it in range(2):
     torch.cuda.synchronize(); t0 = time.perf_counter()
