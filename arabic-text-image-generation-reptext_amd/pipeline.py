@@ -136,6 +136,35 @@ def union_active_steps(num_steps: int, start: float, end: float) -> Tuple[int, .
     return tuple(i for i in range(n) if not (i / n < start or (i + 1) / n > end))
 
 
+def tower_schedule(num_steps: int, cn_steps: int, n_lines: int, union_active: Optional[Tuple[int, ...]] = None,
+                   n_extra: int = 0) -> List[List[Tuple[int, int]]]:
+    """The towers of every denoising step in evaluation order — the order of the sum into the sample buffers — from host scalars alone.
+    Entry i lists (tower, position in that tower's modulation table) for step i; towers are numbered [the union tower, if
+    ``union_active`` names a step] + [text lines] + [extra towers]. The union tower comes first, at its active steps
+    (``union_active_steps``), also where no text tower runs; its table holds those steps only, so its position is the step's index among
+    them. The text lines follow at steps i < ``cn_steps`` (PIPE:1076-1087; past them no tower runs, Q3), then the extra towers: their
+    residuals are added to the text towers' and dropped without them (INP:1231-1245), so they run only where text towers do. Both take
+    table position i."""
+    union = tuple(union_active or ())
+    first_line = 1 if union else 0
+    n_text = n_lines + n_extra if n_lines > 0 else 0
+    return [([(0, union.index(i))] if i in union else []) + ([(first_line + k, i) for k in range(n_text)] if i < cn_steps else [])
+            for i in range(int(num_steps))]
+
+
+@dataclass
+class _Tower:
+    """One ControlNet tower of ``_denoise_eager``. ``masked``: a text line, which takes the regional mask (``rowscale``) and the row
+    window; the union and extra towers write every row. ``static``: the loop-invariant embeddings of (prompt, ``hint``)."""
+    model: FluxControlNetModel
+    hint: torch.Tensor
+    scale: Any
+    rowscale: Optional[torch.Tensor]
+    table: Any
+    masked: bool
+    static: Any = None
+
+
 def accepts_union_arguments(call):
     """The second ControlNet's four arguments — ``control_image_union``, ``controlnet_conditioning_scale_union``,
     ``control_guidance_start_union``, ``control_guidance_end_union`` — are keyword-only extensions of the BASE pipeline's ``__call__``,
@@ -1016,13 +1045,17 @@ class FluxControlNetPipeline:
                tuple(tvals), tuple(self.scheduler.sigmas.tolist()), float(guidance_scale), repr(cn_scale), int(cn_steps), int(num_inference_steps),
                str(latents.device), models, bool(self.reference_bf16_scalars), bool(_mm.RESIDUAL_F32), bool(OVERLAP_TOWER), bool(_mm.FUSED_QK_ROPE),
                win, bool(TOWER_WINDOW))
+        # the graph's static inputs by name, in the order they are cloned and refreshed; hints and masks are lists of tensors
+        ins = dict(latents=latents, prompt_embeds=prompt_embeds, pooled=pooled, text_ids=text_ids, image_ids=image_ids, hints=list(hints), masks=list(masks))
         if ipe is not None:
             # the embeds are one more static input of the graph; the per-block scales are kernel scalars baked into the capture
             adapter = self.transformer._ip_adapter
             key += (sig(ipe), adapter.version, tuple(adapter.scales))
+            ins["ip_embeds"] = ipe
         if union is not None:
             # the union hint is one more static input; the tower's scale and its active steps are baked into the capture
             key += ("union", ident(union[0]), sig(union[1]), union[2], union[3])
+            ins["union_hint"] = union[1]
         if cfg_scale is not None:
             # the scale is a kernel scalar of every step (rt_cfg_euler_step_f32); the static inputs' shapes already carry the batch 2B
             key += (("cfg", cfg_scale),)
@@ -1035,15 +1068,11 @@ class FluxControlNetPipeline:
             return eager()
         if ent == "failed":
             return eager()
-        ins = [latents, prompt_embeds, pooled, text_ids, image_ids] + list(hints) + list(masks) + ([ipe] if ipe is not None else [])
-        if union is not None:
-            ins.append(union[1])                              # always the last static input
+        tensors = lambda named: [t for v in named.values() for t in (v if isinstance(v, list) else [v])]
         if ent == "seen":                                    # second call: capture
-            static = [t.clone() for t in ins]
-            nh, nm = len(hints), len(masks)
+            static = {name: [t.clone() for t in v] if isinstance(v, list) else v.clone() for name, v in ins.items()}
             keep = [m._ensure_plans() for m in (self.transformer, self.controlnet) if m is not None] + [getattr(self.controlnet, "_cx_pad", None)]
             keep.append(getattr(self.transformer, "_ip_adapter", None) if ipe is not None else None)     # its weights are read by the graph
-            n_ip = 5 + nh + nm                                # where the image prompt sits among the static inputs, when there is one
             if union is not None:
                 keep += [union[0]._ensure_plans(), getattr(union[0], "_cx_pad", None)]
             graph = torch.cuda.CUDAGraph()
@@ -1057,11 +1086,11 @@ class FluxControlNetPipeline:
             try:
                 # thread-local capture mode: calls made by OTHER threads (RCCL's watchdog polling its events) do not invalidate the capture
                 with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    out = self._denoise_eager(static[0], static[1], static[2], static[3], static[4], tvals, static[5 : 5 + nh], static[5 + nh : 5 + nh + nm],
-                                              guidance_scale, cn_scale, cn_steps, control_mode, None, callback_inputs, num_inference_steps, timesteps,
-                                              _quiet=True, _ip_embeds=static[n_ip] if ipe is not None else None, _tower_window=win,
-                                              _union=None if union is None else (union[0], static[-1]) + tuple(union[2:]),
-                                              _cfg_scale=cfg_scale)
+                    out = self._denoise_eager(static["latents"], static["prompt_embeds"], static["pooled"], static["text_ids"], static["image_ids"],
+                                              tvals, static["hints"], static["masks"], guidance_scale, cn_scale, cn_steps, control_mode, None,
+                                              callback_inputs, num_inference_steps, timesteps, _quiet=True, _ip_embeds=static.get("ip_embeds"),
+                                              _tower_window=win, _cfg_scale=cfg_scale,
+                                              _union=None if union is None else (union[0], static["union_hint"]) + tuple(union[2:]))
                     out32 = self._master_latents
             except Exception as e:                           # capture is an optimisation, never a requirement
                 import sys
@@ -1082,7 +1111,7 @@ class FluxControlNetPipeline:
             # the sample buffers the capture wrote into and the window its zero-linears were restricted to (None: every row)
             ent = cache[key] = {"graph": graph, "static": static, "out": out, "out32": out32, "keep": keep,
                                 "samples": getattr(self, "_sample_cache", None), "window": self._sample_promise}
-        for dst, src in zip(ent["static"], ins):
+        for dst, src in zip(tensors(ent["static"]), tensors(ins)):
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
         self._zero_samples_for(ent["samples"], ent["window"])       # another call may have left rows outside this window non-zero
@@ -1110,16 +1139,15 @@ class FluxControlNetPipeline:
     def _denoise_eager(self, latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale,
                        cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _quiet=False,
                        _ip_embeds=None, _extra_towers=(), _velocity=None, _tower_window=None, _union=None, _cfg_scale=None):
-        """The one loop over timesteps, for both pipelines. ``_extra_towers``: (FluxControlNetModel, hint, conditioning scale) of
-        towers evaluated after the text-line towers into the same sample buffers, unmasked (the inpaint tower). ``_velocity(i,
-        noise_pred)``: what the scheduler steps with instead of the transformer's output (true CFG). With extra towers the loop stays
-        on one stream. ``_tower_window``: ``active_row_window`` of ``masks`` from the call prologue (None: every row). ``_union``:
-        (FluxControlNetModel, hint, conditioning scale, active steps) of the base flow's second tower: unmasked, evaluated FIRST at its
-        own steps (``union_active_steps``), also where no text tower runs; it keeps the side stream and the text towers' row window.
-        ``_cfg_scale``: true CFG of the base flow — the conditioning batch is [negative, positive] (2B against the latents' B) and the
-        step mixes the two halves of the velocity in fp32 (``scheduler.step_master_cfg_``); everything else just sees Bc = 2B."""
-        device = latents.device
-        B = latents.shape[0]
+        """The one loop over timesteps, for both pipelines. Every tower — text lines, ``_extra_towers``, ``_union`` — is a ``_Tower`` of
+        one list, and each step walks its entry of ``tower_schedule``, which alone decides who runs when and in which order.
+        ``_extra_towers``: (FluxControlNetModel, hint, conditioning scale) of unmasked towers after the text lines (the inpaint tower);
+        with them the loop stays on one stream. ``_union``: (FluxControlNetModel, hint, conditioning scale, active steps) of the base
+        flow's second tower, unmasked; it keeps the side stream and the text towers' row window. ``_velocity(i, noise_pred)``: what the
+        scheduler steps with instead of the transformer's output (the inpaint flow's CFG). ``_tower_window``: ``active_row_window`` of
+        ``masks`` from the call prologue (None: every row). ``_cfg_scale``: true CFG of the base flow — the conditioning batch is [negative,
+        positive] (2B against the latents' B) and the step mixes its halves in fp32 (``scheduler.step_master_cfg_``); all else sees Bc = 2B."""
+        device, B = latents.device, latents.shape[0]
         guidance = torch.full((B,), float(guidance_scale), device=device, dtype=torch.float32) if self.transformer.config.guidance_embeds else None
         # one regional mask per text line, shared by the batch ([1,N,1], the reference's form) or one per image ([B,N,1])
         rowscales = [m.to(torch.float32).reshape(-1).contiguous() if m.shape[0] == 1 else m.to(torch.float32).reshape(m.shape[0], -1).contiguous() for m in masks]
@@ -1130,47 +1158,42 @@ class FluxControlNetPipeline:
         g_tab = guidance if guidance is None or pooled.shape[0] == B else guidance.repeat(pooled.shape[0] // B)
         tab_t = self.transformer.build_modulation_table(model_ts, g_tab, pooled)
         fused_cn = isinstance(self.controlnet, FluxControlNetModel) and len(hints) > 0
-        # The towers of a step, in evaluation order: (model, hint, conditioning scale, row scale, modulation table). One entry per
-        # text line (masked; the first one writes the sample buffers, PIPE:1076-1087) and then the extra towers, whose residuals are
-        # ADDED to the text towers' and dropped when those are absent (INP:1231-1245: both sums are guarded by `control_block_samples
-        # is not None`) — they are therefore only evaluated when they can matter. Past `cn_steps` no tower runs (Q3).
-        towers = []
+        # The towers of every step and every tower of this call, numbered as `tower_schedule` numbers them. The union tower's table holds
+        # ITS active steps only; the text lines share one table over the steps below `cn_steps`, whose steps the extra towers follow.
+        union_active = _union[3] if _union is not None and isinstance(self.controlnet, FluxControlNetModel) else ()
+        steps = tower_schedule(len(tvals), cn_steps, len(hints) if fused_cn else 0, union_active, len(_extra_towers))
+        towers: List[_Tower] = []
+        if union_active:
+            towers.append(_Tower(*_union[:3], None, _union[0].build_modulation_table([model_ts[i] for i in union_active], g_tab, pooled), masked=False))
         if fused_cn and cn_steps > 0:
             ts_c = model_ts[: min(len(model_ts), cn_steps)]
             tab_c = self.controlnet.build_modulation_table(ts_c, g_tab, pooled)
-            towers = [(self.controlnet, h, cn_scale, rowscales[line] if rowscales else None, tab_c) for line, h in enumerate(hints)]
-            towers += [(m, h, s, None, m.build_modulation_table(ts_c, g_tab, pooled)) for m, h, s in _extra_towers]
-        # The union tower: its modulation table holds ITS active steps only and is indexed by position in that list (the text towers'
-        # table can be indexed by the step because they start at step 0).
-        utower, upos = None, {}
-        if _union is not None and _union[3] and isinstance(self.controlnet, FluxControlNetModel):
-            um, uh, us, uact = _union
-            utower = (um, uh, us, None, um.build_modulation_table([model_ts[i] for i in uact], g_tab, pooled))
-            upos = {step: k for k, step in enumerate(uact)}
-
+            towers += [_Tower(self.controlnet, h, cn_scale, rowscales[line] if rowscales else None, tab_c, masked=True) for line, h in enumerate(hints)]
+            towers += [_Tower(m, h, s, None, m.build_modulation_table(ts_c, g_tab, pooled), masked=False) for m, h, s in _extra_towers]
         # Loop-invariant work, once per image instead of once per step (the prompt and the hint latents do not change inside the
         # loop): context_embedder(prompt) of every model, controlnet_x_embedder(hint) per tower. A callback that replaces
         # prompt_embeds invalidates them (recomputed below).
         def prepare_static(pe):
-            return self.transformer.prepare_static(pe), [tw[0].prepare_static(pe, tw[1]) for tw in towers]
+            static_t = self.transformer.prepare_static(pe)
+            for tw in towers:
+                tw.static = tw.model.prepare_static(pe, tw.hint)
+            return static_t
 
-        static_t, static_c = prepare_static(prompt_embeds)
-        static_u = utower[0].prepare_static(prompt_embeds, utower[1]) if utower is not None else None
+        static_t = prepare_static(prompt_embeds)
         # the image prompt's tokens and every block's K/V of them: loop-invariant too (ip_adapter.py steps 1-2)
         ip_prep = self.transformer._ip_adapter.prepare(_ip_embeds) if _ip_embeds is not None else None
         # Which tower samples does the transformer read? Block i takes sample i // ceil(n_blocks / n_samples) (A.3): with 6
         # samples against 19 double blocks the sixth is never consumed (Q5), so its block and zero-linear are not evaluated.
-        # An extra tower of another depth adds into the first tower's buffers (it must not be deeper: there is one buffer per block
+        # A tower of another depth adds into the first tower's buffers (it must not be deeper: there is one buffer per block
         # of the first tower) and every block of every tower is then evaluated.
-        blocks_needed, sample_buf, single_buf = None, None, None
-        if fused_cn or utower is not None:
+        blocks_needed, sample_buf, single_buf, need_d = None, None, None, 0
+        if fused_cn or towers:
             cnet = self.controlnet
             n_cd, n_cs = len(cnet.transformer_blocks), len(cnet.single_transformer_blocks)
             n_td, n_ts = len(self.transformer.transformer_blocks), len(self.transformer.single_transformer_blocks)
-            others = [m for m, _, _ in _extra_towers] + ([utower[0]] if utower is not None else [])
-            if all((len(m.transformer_blocks), len(m.single_transformer_blocks)) == (n_cd, n_cs) for m in others):
-                need_d = 0 if n_cd == 0 else (n_td - 1) // int(np.ceil(n_td / n_cd)) + 1
-                need_s = 0 if n_cs == 0 or n_ts == 0 else (n_ts - 1) // int(np.ceil(n_ts / n_cs)) + 1
+            need_d = 0 if n_cd == 0 else (n_td - 1) // int(np.ceil(n_td / n_cd)) + 1      # the transformer reads (and waits for) samples < need_d
+            need_s = 0 if n_cs == 0 or n_ts == 0 else (n_ts - 1) // int(np.ceil(n_ts / n_cs)) + 1
+            if all((len(tw.model.transformer_blocks), len(tw.model.single_transformer_blocks)) == (n_cd, n_cs) for tw in towers):
                 blocks_needed = (min(need_d, n_cd), min(need_s, n_cs))
             # sample buffers: allocated once per shape, written by the zero-linear epilogues every step (no per-step allocation)
             Bc, N_, d_ = prompt_embeds.shape[0], latents.shape[1], cnet.inner_dim
@@ -1179,20 +1202,18 @@ class FluxControlNetPipeline:
                 mk = lambda n: [torch.empty(Bc, N_, d_, device=device, dtype=torch.bfloat16) for _ in range(n)]
                 self._sample_cache = (key, mk(n_cd), mk(n_cs), [None])
             sample_buf, single_buf = self._sample_cache[1], self._sample_cache[2]
-        # Zero-linears and the last tower block on the masked rows only (controlnet.forward: _window). The extra towers are unmasked
-        # and ADD to every row of the buffers, step after step, so with them every row must be overwritten first: full path.
-        window = None
-        if (TOWER_WINDOW and _tower_window is not None and towers and not _extra_towers and blocks_needed is not None
-                and blocks_needed[0] >= 1 and blocks_needed[1] == 0 and self.controlnet.supports_row_window()):
-            window = _tower_window
-        self._tower_window_used = window
+        # Zero-linears and the last block of the masked towers on the masked rows only (controlnet.forward: _window). The extra towers
+        # are unmasked and ADD to every row of the buffers, step after step, so with them every row must be overwritten first: full path.
+        use_window = (TOWER_WINDOW and any(tw.masked for tw in towers) and not _extra_towers and blocks_needed is not None
+                      and blocks_needed[0] >= 1 and blocks_needed[1] == 0 and self.controlnet.supports_row_window())
+        self._tower_window_used = window = _tower_window if use_window else None
         # A union step writes every row, so with a union tower the "rows outside the window read zero" promise is kept by the step
         # sequence itself: the buffers count as dirty from the start and after every union step, and the first text-only step that
         # follows zeroes them on the tower's stream (captured with the loop; one fill per transition of the union interval).
-        self._sample_promise = None if utower is not None else window
-        if fused_cn or utower is not None:
+        dirty = any(not tw.masked for tw in towers)
+        self._sample_promise = None if dirty else window
+        if fused_cn or towers:
             self._zero_samples_for(self._sample_cache, self._sample_promise)
-        dirty = utower is not None
         # fp32 master copy of the latents between steps (the models read its bf16 copy): the scheduler computes in fp32 anyway
         # (A.6); not rounding the STATE 28 times keeps the loop close to the fp32 reference path. Callbacks see the bf16 copy.
         lat32 = latents.to(torch.float32).contiguous()
@@ -1202,12 +1223,11 @@ class FluxControlNetPipeline:
         # sample buffers and the transformer waits, block by block, on the event of the sample it needs. At batch 1 most
         # launches fill only 27/32 of their last round of workgroups (216 GEMM tiles on 256 CUs, 864 attention workgroups on
         # 512 slots); two independent chains in flight fill some of those holes. Results are bitwise those of the serial order.
-        # On by default (OVERLAP_TOWER; RT_OVERLAP_TOWER=0 turns it off): -0.5 % eager, -1.1 % inside the captured graph.
         # `not _extra_towers`: the inpaint flow is serial by decision (its second tower has no side stream or "tower" workspace of its
         # own yet); an extra tower added to the BASE flow would switch the overlap off here too — extend this rule then, not the call.
         # The base flow's union tower shares the side stream and the "tower" workspace with the text towers: the towers of a step are
         # serial with each other, only the transformer runs beside them.
-        overlap = (OVERLAP_TOWER and (bool(towers) or utower is not None) and not _extra_towers and device.type == "cuda"
+        overlap = (OVERLAP_TOWER and bool(towers) and not _extra_towers and device.type == "cuda"
                    and len(self.controlnet.single_transformer_blocks) == 0)
         side = sample_ev = None
         if overlap:
@@ -1221,55 +1241,35 @@ class FluxControlNetPipeline:
                     continue
                 timestep = torch.full((B,), self._model_timestep(t), device=device, dtype=torch.float32)      # PIPE:1025,1048 (Q4)
                 merged = merged_single = events = None
-                if utower is not None:
-                    # per-step tower list: the union tower first (it overwrites every row of the buffers), then the text lines
-                    step_towers = ([(utower, static_u, upos[i], None)] if i in upos else []) + \
-                                  ([(tw, st, i, window) for tw, st in zip(towers, static_c)] if towers and i < cn_steps else [])
-                    if step_towers:
-                        if overlap:
-                            side.wait_stream(torch.cuda.current_stream())
-                            events = sample_ev
-                        with torch.cuda.stream(side) if overlap else contextlib.nullcontext():
-                            if i in upos:
-                                dirty = True
-                            elif window is not None and dirty:       # text-only step after a union step (or the first one of the call)
-                                for buf in sample_buf:
-                                    buf.zero_()
-                                dirty = False
-                            done_d = done_s = 0                        # leading buffers already written in this step: add to those
-                            for k, ((model, hint, scale, rowscale, table), static, pos, win_k) in enumerate(step_towers):
-                                last = k == len(step_towers) - 1
-                                bs, ss = model(
-                                    hidden_states=latents, controlnet_cond=hint, controlnet_mode=control_mode, conditioning_scale=scale,
-                                    timestep=timestep, guidance=guidance, pooled_projections=pooled, encoder_hidden_states=prompt_embeds,
-                                    txt_ids=text_ids, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs,
-                                    return_dict=False, _rowscale=rowscale, _accumulate_into=sample_buf, _accumulate_single_into=single_buf,
-                                    _overwrite=(done_d, done_s), _sample_events=events if last else None, _mods=table.step(pos),
-                                    _ws_tag="tower" if overlap else "", _static=static, _blocks_needed=blocks_needed, _window=win_k)
-                                done_d = max(done_d, sum(b is not None for b in bs or ()))
-                                done_s = max(done_s, sum(b is not None for b in ss or ()))
-                            if events is not None:
-                                for ev in events[done_d:]:             # a shallower union tower alone: nothing writes (or reads) these
-                                    ev.record(torch.cuda.current_stream())
-                        # buffers no tower of this step wrote are not injected (None), the block-to-sample map keeps the first tower's depth
-                        merged = [b if j < done_d else None for j, b in enumerate(sample_buf)] or None
-                        merged_single = [b if j < done_s else None for j, b in enumerate(single_buf)] or None
-                elif towers and i < cn_steps:
+                if steps[i]:
                     if overlap:
                         side.wait_stream(torch.cuda.current_stream())    # latents of this step (and, at i = 0, tables and hints) are ready
                         events = sample_ev                               # recorded by the last tower, once the sums are complete
                     with torch.cuda.stream(side) if overlap else contextlib.nullcontext():
-                        for k, ((model, hint, scale, rowscale, table), static) in enumerate(zip(towers, static_c)):
-                            # zero-linear epilogues write (first tower) or add to (later ones) the preallocated buffers
-                            samples = model(
-                                hidden_states=latents, controlnet_cond=hint, controlnet_mode=control_mode, conditioning_scale=scale,
+                        if any(not towers[k].masked for k, _ in steps[i]):
+                            dirty = True
+                        elif window is not None and dirty:           # text-only step after a union step (or the first one of the call)
+                            for buf in sample_buf:
+                                buf.zero_()
+                            dirty = False
+                        done_d = done_s = 0       # leading buffers already written in this step: the zero-linear epilogues add to those
+                        for n, (k, pos) in enumerate(steps[i]):
+                            tw = towers[k]
+                            bs, ss = tw.model(
+                                hidden_states=latents, controlnet_cond=tw.hint, controlnet_mode=control_mode, conditioning_scale=tw.scale,
                                 timestep=timestep, guidance=guidance, pooled_projections=pooled, encoder_hidden_states=prompt_embeds,
-                                txt_ids=text_ids, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs,
-                                return_dict=False, _rowscale=rowscale, _accumulate_into=sample_buf, _accumulate_single_into=single_buf,
-                                _overwrite=(k == 0), _sample_events=events if k == len(towers) - 1 else None, _mods=table.step(i),
-                                _ws_tag="tower" if overlap else "", _static=static, _blocks_needed=blocks_needed, _window=window)
-                            if k == 0:
-                                merged, merged_single = samples          # the buffers, None where a block was skipped
+                                txt_ids=text_ids, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs, return_dict=False,
+                                _rowscale=tw.rowscale, _accumulate_into=sample_buf, _accumulate_single_into=single_buf, _overwrite=(done_d, done_s),
+                                _sample_events=events if n == len(steps[i]) - 1 else None, _mods=tw.table.step(pos), _static=tw.static,
+                                _ws_tag="tower" if overlap else "", _blocks_needed=blocks_needed, _window=window if tw.masked else None)
+                            done_d = max(done_d, sum(b is not None for b in bs or ()))
+                            done_s = max(done_s, sum(b is not None for b in ss or ()))
+                        if events is not None:
+                            for ev in events[done_d:need_d]:   # the transformer waits on these; a shallower union tower alone left them
+                                ev.record(torch.cuda.current_stream())
+                    # buffers no tower of this step wrote are not injected (None), the block-to-sample map keeps the first tower's depth
+                    merged = [b if j < done_d else None for j, b in enumerate(sample_buf)] or None
+                    merged_single = [b if j < done_s else None for j, b in enumerate(single_buf)] or None
                 noise_pred = self.transformer(
                     hidden_states=latents, timestep=timestep, guidance=guidance, pooled_projections=pooled,
                     encoder_hidden_states=prompt_embeds, controlnet_block_samples=merged, controlnet_single_block_samples=merged_single,
@@ -1291,8 +1291,7 @@ class FluxControlNetPipeline:
                         lat32 = latents.to(torch.float32)
                     if "prompt_embeds" in out:                       # the loop-invariant embeddings are no longer valid
                         prompt_embeds = out.pop("prompt_embeds")
-                        static_t, static_c = prepare_static(prompt_embeds)
-                        static_u = utower[0].prepare_static(prompt_embeds, utower[1]) if utower is not None else None
+                        static_t = prepare_static(prompt_embeds)
                 if i == len(tvals) - 1 or ((i + 1) > num_warmup and (i + 1) % self.scheduler.order == 0):
                     bar.update()
         self._master_latents = lat32          # fp32 state of the loop; `latents` is its bf16 copy

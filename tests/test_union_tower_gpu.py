@@ -36,7 +36,7 @@ def mask_images(boxes, H=256, W=256):
     return out
 
 
-def random_pipe(gpu, vae, seed, zero_union=False):
+def random_pipe(gpu, vae, seed, zero_union=False, cn_layers=2, un_layers=2):
     """(pipe, r): a base pipeline with random transformer, text tower and union tower; r(*shape) draws bf16 device tensors."""
     import reptext_amd.pipeline as P
     from reptext_amd.controlnet import FluxControlNetModel
@@ -44,8 +44,8 @@ def random_pipe(gpu, vae, seed, zero_union=False):
     from reptext_amd.transformer import FluxTransformer2DModel
 
     tr = FluxTransformer2DModel(**SMALL_T, device=gpu, dtype=torch.bfloat16).random_init_(seed)
-    cn = FluxControlNetModel(**SMALL_CN, device=gpu, dtype=torch.bfloat16).random_init_(seed + 1)
-    un = FluxControlNetModel(**SMALL_UN, device=gpu, dtype=torch.bfloat16).random_init_(seed + 2)
+    cn = FluxControlNetModel(**dict(SMALL_CN, num_layers=cn_layers), device=gpu, dtype=torch.bfloat16).random_init_(seed + 1)
+    un = FluxControlNetModel(**dict(SMALL_UN, num_layers=un_layers), device=gpu, dtype=torch.bfloat16).random_init_(seed + 2)
     if zero_union:
         un.zero_init_controlnet_()
     pipe = P.FluxControlNetPipeline(FlowMatchEulerDiscreteScheduler(), vae, None, None, None, None, tr, cn)
@@ -146,6 +146,63 @@ def test_empty_union_interval_is_the_call_without_it(vae, gpu):
     assert torch.equal(got, want)
     felt = pipe(**kw, control_image_union=r(1, 256, 64)).images
     assert not torch.equal(felt, want)
+
+
+@pytest.mark.parametrize("case", ["equal_depths", "deeper_text_tower", "shallow_union_alone"])
+def test_event_records_per_step_are_what_the_transformer_waits_on(vae, gpu, monkeypatch, case):
+    """The side stream's events, counted on the host per step (``torch.cuda.Event.record`` patched on the class; eager loop). The
+    transformer waits on the events k < need_d, the highest sample its block map i // ceil(n_blocks / n_samples) reaches. A call
+    without a union image records exactly those per tower step: the one loop must not cost it a stream operation, which no output bit
+    would show. A union call records no fewer, and a step without towers none. Two masked text lines, 4 steps, union on steps 1 and 2.
+    ``deeper_text_tower``: 3 tower blocks against the transformer's 2, so sample 2 is never read or waited on. ``shallow_union_alone``:
+    a 1-block union tower with the text towers off after step 2, so step 2 is the union tower alone, which writes one sample of two."""
+    import math
+
+    import reptext_amd.pipeline as P
+
+    cn_layers, un_layers, cn_steps = {"equal_depths": (2, 2, 4), "deeper_text_tower": (3, 2, 4), "shallow_union_alone": (2, 1, 2)}[case]
+    pipe, r = random_pipe(gpu, vae, 181, cn_layers=cn_layers, un_layers=un_layers)
+    pipe.capture_graphs = False
+    monkeypatch.setattr(P, "OVERLAP_TOWER", True)
+    n_td = len(pipe.transformer.transformer_blocks)
+    need_d = (n_td - 1) // math.ceil(n_td / cn_layers) + 1
+    assert need_d == 2
+    per_step, pending, joining = [], [0], [False]
+    record, wait_stream, forward = torch.cuda.Event.record, torch.cuda.Stream.wait_stream, pipe.transformer.forward
+
+    def counted_record(self, *a, **k):
+        pending[0] += not joining[0]
+        return record(self, *a, **k)
+
+    def uncounted_wait_stream(self, stream):                            # the step's fork and join record an event of their own
+        joining[0] = True
+        try:
+            return wait_stream(self, stream)
+        finally:
+            joining[0] = False
+
+    def counted_forward(*a, **k):                                       # the tower(s) of a step are enqueued before its transformer
+        per_step.append(pending[0]); pending[0] = 0
+        return forward(*a, **k)
+
+    monkeypatch.setattr(torch.cuda.Event, "record", counted_record)
+    monkeypatch.setattr(torch.cuda.Stream, "wait_stream", uncounted_wait_stream)
+    monkeypatch.setattr(pipe.transformer, "forward", counted_forward)
+    kw = two_line_call(r, cn_steps=cn_steps)
+    want = pipe(**kw).images.clone()
+    tower_step = [i < cn_steps for i in range(4)]
+    print(f"[{case}] need_d {need_d}; records per step without a union image {per_step}")
+    assert per_step == [need_d if on else 0 for on in tower_step] and pending[0] == 0
+    del per_step[:]
+    empty = pipe(**kw, control_image_union=r(1, 256, 64), control_guidance_start_union=0.9, control_guidance_end_union=0.1).images
+    assert torch.equal(empty, want)
+    assert per_step == [need_d if on else 0 for on in tower_step] and pending[0] == 0
+    del per_step[:]
+    pipe(**kw, control_image_union=r(1, 256, 64), **UNION_MID)
+    print(f"[{case}] records per step with the union tower on steps 1 and 2 {per_step}")
+    tower_step = [on or i in (1, 2) for i, on in enumerate(tower_step)]
+    assert len(per_step) == 4 and pending[0] == 0
+    assert all(n >= need_d if on else n == 0 for n, on in zip(per_step, tower_step))
 
 
 def test_overlap_and_row_window_are_bitwise_neutral_with_a_union_tower(vae, gpu, monkeypatch):

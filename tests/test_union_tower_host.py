@@ -42,6 +42,28 @@ def test_active_step_rule_known_answers():
     assert union_active_steps(3, 0.9, 0.1) == ()
 
 
+def test_tower_schedule_known_answers():
+    """``tower_schedule`` per step, as literal lists of (tower, table position). Towers are numbered union (if any), text lines, extra
+    towers; U / T / X below name them for each case."""
+    from reptext_amd.pipeline import tower_schedule, union_active_steps
+
+    U, T = 0, 1
+    assert tower_schedule(4, 30, 1, (1, 2)) == [[(T, 0)], [(U, 0), (T, 1)], [(U, 1), (T, 2)], [(T, 3)]]
+    assert tower_schedule(3, 1, 1, (0, 1, 2)) == [[(U, 0), (T, 0)], [(U, 1)], [(U, 2)]]
+    assert tower_schedule(3, 30, 0, (1,)) == [[], [(U, 0)], []]
+    assert tower_schedule(3, 0, 1, (0,)) == [[(U, 0)], [], []]
+    T0, T1, X = 0, 1, 2
+    assert tower_schedule(3, 2, 2) == [[(T0, 0), (T1, 0)], [(T0, 1), (T1, 1)], []]
+    assert tower_schedule(3, 2, 2, None, 0) == tower_schedule(3, 2, 2, (), 0) == tower_schedule(3, 2, 2)
+    assert tower_schedule(3, 2, 2, None, 1) == [[(T0, 0), (T1, 0), (X, 0)], [(T0, 1), (T1, 1), (X, 1)], []]
+    # an extra tower without a text line, or with the text towers switched off: nothing at any step
+    assert tower_schedule(3, 2, 0, None, 1) == [[], [], []]
+    assert tower_schedule(3, 0, 2, None, 1) == [[], [], []]
+    # an empty guidance interval (start > end), fed through: no union tower anywhere, the text lines keep their numbers
+    assert union_active_steps(3, 0.9, 0.1) == ()
+    assert tower_schedule(3, 2, 2, union_active_steps(3, 0.9, 0.1)) == [[(T0, 0), (T1, 0)], [(T0, 1), (T1, 1)], []]
+
+
 def test_call_signature_and_keywords():
     """The base ``__call__`` still reports the reference's parameter list; the four union keywords are taken by the base pipeline
     (they reach the refusal that names them) and are unknown to the inpaint pipeline."""

@@ -19,7 +19,7 @@ pipe.set_progress_bar_config(disable=True)
 g = torch.Generator().manual_seed(1)
 pe, pooled = torch.randn(1, 512, 4096, generator=g).to(dev, bf16), torch.randn(1, 768, generator=g).to(dev, bf16)
 hints = [torch.randn(1, 4096, 128, generator=g).to(dev, bf16)]
-masks = [torch.ones(4096, device=dev)]
+masks = [torch.ones(1, 4096, device=dev)]            # bench.run_image takes one [B, N] row scale per text line
 for prec in ("bf16", "fp8"):
     if prec == "fp8":
         for m in (tr, cn):
