@@ -508,6 +508,8 @@ int rt_conv2d_nhwc(const void* x, const void* w, const void* bias, const void* r
   if (Cin % 64 || Cout % 4) return RT_E_SHAPE;
   if (stride == 2 && (Hs % 2 || Ws % 2)) return RT_E_SHAPE;
   if (!RT_ALIGNED(x, 16) || !RT_ALIGNED(w, 16) || !RT_ALIGNED(y, 16)) return RT_E_ALIGN;
+  // both kernels load 4 channels of bias and of res as one 8-byte word (Cout % 4 == 0 keeps every pixel's offset a multiple of 8 bytes)
+  if ((bias && !RT_ALIGNED(bias, 8)) || (res && !RT_ALIGNED(res, 8))) return RT_E_ALIGN;
   ConvArgs a;
   a.x = (const bf16_t*)x; a.w = (const bf16_t*)w; a.bias = (const bf16_t*)bias; a.res = (const bf16_t*)res; a.y = y;
   a.B = B; a.Hs = Hs; a.Ws = Ws; a.Cin = Cin; a.Cout = Cout; a.ks = ksize; a.stride = stride; a.ups = upsample2x ? 1 : 0;

@@ -470,7 +470,10 @@ int rt_groupnorm_silu_nhwc(const void* x, void* y, const void* gamma, const void
  * from OIHW), y haloed [B][Ho+2][Wo+2][Cout] bf16|f32, res (optional) like y in bf16.
  *   stride 1: pad k/2; upsample2x fuses a nearest-2x Upsample2D in front (Ho = 2Hs)
  *   stride 2: k = 3, pad (0,1,0,1) = diffusers Downsample2D (Ho = Hs/2)
- * Cin % 64 == 0 (callers zero-pad channels), Cout % 4 == 0. */
+ * Cin % 64 == 0 (callers zero-pad channels), Cout % 4 == 0.
+ * Rejected on the host, before anything is queued: null x / w / y or a size < 1 (RT_E_BADARG); a kernel size, stride or channel
+ * count outside the above, odd Hs / Ws with stride 2 (RT_E_SHAPE); x / w / y not 16-byte aligned, or a bias or res that is given
+ * and not 8-byte aligned — whichever kernel serves the call (RT_E_ALIGN). */
 int rt_conv2d_nhwc(const void* x, const void* w, const void* bias, const void* res, void* y,
                    int32_t B, int32_t Hs, int32_t Ws, int32_t Cin, int32_t Cout, int32_t ksize, int32_t stride,
                    int32_t upsample2x, int32_t out_f32, void* stream);

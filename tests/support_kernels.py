@@ -1,5 +1,5 @@
-"""What the tests of tests/test_support_kernels_gpu.py, test_gemm_epilogue_gpu.py and test_attention_edges_gpu.py share: the fp64 references
-of the GEMM epilogue and of attention, the per-element bound check, guarded buffers (NaN where a kernel must not read, a sentinel where it must
+"""What the tests of tests/test_support_kernels_gpu.py, test_gemm_epilogue_gpu.py, test_attention_edges_gpu.py and test_vae_kernels_gpu.py
+share: the fp64 references of the GEMM epilogue, of the convolution and of attention, the per-element bound check, guarded buffers (NaN where a kernel must not read, a sentinel where it must
 not write), the bf16 error bound, ulp distances and the run-twice check. A plain helper module, not a test file."""
 import torch
 
@@ -194,6 +194,34 @@ def gemm_epilogue_ref(a, w, *, bias=None, gelu_from=None, gate=None, alpha=1.0, 
     if add2 is not None:
         v, mag = v + add2.double(), mag + add2.double().abs()
     return v, mag
+
+
+def conv_ref(x, w, bias, res, stride, up):
+    """fp64 rt_conv2d_nhwc of CPU tensors holding exactly the values the kernel reads (any dtype; widened here), in the kernel's own
+    layouts without the halo: x [B, Hs, Ws, Cin], w [Cout, ks, ks, Cin], bias [Cout] or None, res [B, Ho, Wo, Cout] or None. The three
+    geometries of include/reptext_hip.h: stride 1 pads ks // 2; up puts a nearest-2x upsample in front; stride 2 pads (0, 1, 0, 1).
+    Returns (ref, mag), both fp64 [B, Ho, Wo, Cout]. mag is the same convolution of |x| with |w|, plus |bias|, plus |res|: the sum of
+    the absolute values of every addend of the element — what a rounding error of the evaluation is relative to."""
+    import torch.nn.functional as F
+
+    ks = w.shape[1]
+
+    def conv(xx, ww):
+        xx, ww = xx.double().permute(0, 3, 1, 2), ww.double().permute(0, 3, 1, 2)
+        if stride == 2:
+            out = F.conv2d(F.pad(xx, (0, 1, 0, 1)), ww, stride=2)
+        elif up:
+            out = F.conv2d(F.interpolate(xx, scale_factor=2.0, mode="nearest"), ww, padding=ks // 2)
+        else:
+            out = F.conv2d(xx, ww, padding=ks // 2)
+        return out.permute(0, 2, 3, 1).contiguous()
+
+    ref, mag = conv(x, w), conv(x.abs(), w.abs())
+    if bias is not None:
+        ref, mag = ref + bias.double(), mag + bias.double().abs()
+    if res is not None:
+        ref, mag = ref + res.double(), mag + res.double().abs()
+    return ref, mag
 
 
 def attention_ref(q, k, v, scale=None):

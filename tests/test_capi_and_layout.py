@@ -68,6 +68,32 @@ def test_calls_are_rejected_not_crashed_without_gpu_memory():
     assert lib.rt_layernorm_modulate(8, 8, 0, 0, 8, 8, 0, None, None, 0, 1, 1, 12, 1e-6, None) in (-2, -3)   # D % 8 != 0
 
 
+def test_conv2d_rejects_a_misaligned_bias_or_res_whichever_kernel_serves_the_call():
+    """rt_conv2d_nhwc: both of its kernels load 4 channels of bias and of res as one 8-byte word. A bias or res that is not 8-byte
+    aligned is RT_E_ALIGN from the entry point itself, before anything is queued (null stream, fake pointers, no GPU) — for the calls
+    the GEMM's convolution form takes and for those conv_nhwc_kernel takes (fp32 output, stride 2, upsample, Cout < 64, variant 0)."""
+    from reptext_amd import native
+
+    lib = native.load()
+    X, W, Y, OK8, ODD = 0x10000, 0x20000, 0x30000, 0x40008, 0x40004
+    #        Cout ks stride up out_f32
+    calls = [(128, 3, 1, 0, 0), (260, 1, 1, 0, 0), (4, 3, 1, 0, 1), (128, 3, 2, 0, 0), (128, 3, 1, 1, 0), (32, 3, 1, 0, 0)]
+    prev = lib.rt_conv2d_variant(-1)
+    try:
+        for mode in (1, 0):
+            lib.rt_conv2d_variant(mode)
+            for Cout, ks, stride, up, f32 in calls:
+                shape = (2, 8, 8, 64, Cout, ks, stride, up, f32, None)
+                assert lib.rt_conv2d_nhwc(X, W, ODD, None, Y, *shape) == native.RT_E_ALIGN, (mode, Cout, ks, stride, up, f32, "bias")
+                assert lib.rt_conv2d_nhwc(X, W, None, ODD, Y, *shape) == native.RT_E_ALIGN, (mode, Cout, ks, stride, up, f32, "res")
+                assert lib.rt_conv2d_nhwc(X, W, OK8, ODD + 2, Y, *shape) == native.RT_E_ALIGN, (mode, Cout, ks, stride, up, f32, "res + 2")
+                assert lib.rt_conv2d_nhwc(X + 8, W, OK8, OK8, Y, *shape) == native.RT_E_ALIGN        # x / w / y keep their 16 bytes
+            assert lib.rt_conv2d_nhwc(X, W, ODD, ODD, Y, 2, 8, 8, 64, 130, 3, 1, 0, 0, None) == native.RT_E_SHAPE   # the shape is judged first
+            assert lib.rt_conv2d_nhwc(None, W, ODD, ODD, Y, 2, 8, 8, 64, 128, 3, 1, 0, 0, None) == native.RT_E_BADARG
+    finally:
+        lib.rt_conv2d_variant(prev)
+
+
 def test_product_never_imports_the_oracle_and_has_no_cpu_fallback():
     bad = []
     for dirpath, _, files in os.walk(PKG):
