@@ -18,7 +18,7 @@ import functools
 import inspect
 import json
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, replace
 from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
@@ -114,21 +114,6 @@ TOWER_WINDOW = os.environ.get("RT_TOWER_WINDOW", "1") == "1"
 GRAPH_CACHE_MAX = 2
 
 
-def accepts_ip_adapter_arguments(call):
-    """``__call__`` keeps the reference's parameter list (PIPE:751-781, which ``inspect.signature`` still reports); the IP-Adapter's two
-    arguments, ``ip_adapter_image`` and ``ip_adapter_image_embeds``, are keyword-only extensions taken off here and left on the pipeline
-    as ``_ip_call_args`` for the duration of the call. What the call derives from them (``_ip_embeds``, read by ``_denoise``) is cleared
-    with them, so a later direct ``_denoise`` never sees a previous call's image prompt. Not re-entrant, like the rest of the call state."""
-    @functools.wraps(call)
-    def wrapper(self, *args, ip_adapter_image=None, ip_adapter_image_embeds=None, **kwargs):
-        self._ip_call_args = (ip_adapter_image, ip_adapter_image_embeds)
-        try:
-            return call(self, *args, **kwargs)
-        finally:
-            self._ip_call_args, self._ip_embeds = (None, None), None
-    return wrapper
-
-
 def union_active_steps(num_steps: int, start: float, end: float) -> Tuple[int, ...]:
     """The steps, of ``num_steps``, at which a tower with the guidance interval [start, end] is evaluated: step i iff
     ``not (i / n < start or (i + 1) / n > end)`` — diffusers' ``controlnet_keep`` (recalled, not read). ``start > end`` gives none."""
@@ -165,44 +150,68 @@ class _Tower:
     static: Any = None
 
 
-def accepts_union_arguments(call):
-    """The second ControlNet's four arguments — ``control_image_union``, ``controlnet_conditioning_scale_union``,
-    ``control_guidance_start_union``, ``control_guidance_end_union`` — are keyword-only extensions of the BASE pipeline's ``__call__``,
-    taken off here like the IP-Adapter's (``accepts_ip_adapter_arguments``) and left on the pipeline as ``_union_call_args`` for the
-    duration of the call; what the call derives from them (``_union``, read by ``_denoise``) is cleared with them."""
-    @functools.wraps(call)
-    def wrapper(self, *args, control_image_union=None, controlnet_conditioning_scale_union: float = 1.0,
-                control_guidance_start_union: float = 0.0, control_guidance_end_union: float = 1.0, **kwargs):
-        self._union_call_args = (control_image_union, controlnet_conditioning_scale_union, control_guidance_start_union,
-                                 control_guidance_end_union)
-        try:
-            return call(self, *args, **kwargs)
-        finally:
-            self._union_call_args, self._union = None, None
-    return wrapper
-
-
 TRUE_CFG_ARGUMENTS = ("negative_prompt", "negative_prompt_2", "true_cfg_scale", "negative_prompt_embeds", "negative_pooled_prompt_embeds",
                       "negative_ip_adapter_image", "negative_ip_adapter_image_embeds")
 
 
-def accepts_true_cfg_arguments(call):
-    """The negative prompt's seven arguments (``TRUE_CFG_ARGUMENTS``; diffusers' names, rules recalled: DESIGN.md §7) are keyword-only
-    extensions of the BASE pipeline's ``__call__``, taken off here like the union tower's (``accepts_union_arguments``) and left on the
-    pipeline as ``_cfg_call_args`` for the duration of the call; what the call derives from them (``_cfg_scale``, read by ``_denoise``)
-    is cleared with them."""
-    @functools.wraps(call)
-    def wrapper(self, *args, negative_prompt=None, negative_prompt_2=None, true_cfg_scale: float = 1.0, negative_prompt_embeds=None,
-                negative_pooled_prompt_embeds=None, negative_ip_adapter_image=None, negative_ip_adapter_image_embeds=None, **kwargs):
-        self._cfg_call_args = dict(negative_prompt=negative_prompt, negative_prompt_2=negative_prompt_2, true_cfg_scale=true_cfg_scale,
-                                   negative_prompt_embeds=negative_prompt_embeds, negative_pooled_prompt_embeds=negative_pooled_prompt_embeds,
-                                   negative_ip_adapter_image=negative_ip_adapter_image,
-                                   negative_ip_adapter_image_embeds=negative_ip_adapter_image_embeds)
-        try:
-            return call(self, *args, **kwargs)
-        finally:
-            self._cfg_call_args, self._cfg_scale = None, None
-    return wrapper
+@dataclass
+class CallExtensions:
+    """The keyword-only extensions of a ``__call__``, as the caller passed them: the IP-Adapter's image prompt, the second ControlNet's
+    four arguments and the negative prompt's seven (``TRUE_CFG_ARGUMENTS``; diffusers' names, rules recalled: DESIGN.md §7)."""
+    ip_adapter_image: Any = None
+    ip_adapter_image_embeds: Any = None
+    control_image_union: Any = None
+    controlnet_conditioning_scale_union: float = 1.0
+    control_guidance_start_union: float = 0.0
+    control_guidance_end_union: float = 1.0
+    negative_prompt: Any = None
+    negative_prompt_2: Any = None
+    true_cfg_scale: float = 1.0
+    negative_prompt_embeds: Any = None
+    negative_pooled_prompt_embeds: Any = None
+    negative_ip_adapter_image: Any = None
+    negative_ip_adapter_image_embeds: Any = None
+
+
+def accepts_call_extensions(*names):
+    """``__call__`` keeps the reference's parameter list (PIPE:751-781, which ``inspect.signature`` still reports). The fields of
+    ``CallExtensions`` in ``names`` are keyword-only extensions of it, taken off here and left on the pipeline, as passed, as
+    ``_call_extensions`` for the duration of the call: the only call state that comes from them (what the call derives from them goes to
+    ``_denoise`` as an argument). Any other keyword reaches ``__call__`` and its ``TypeError``. Not re-entrant, like the rest of the call state."""
+    def decorate(call):
+        @functools.wraps(call)
+        def wrapper(self, *args, **kwargs):
+            self._call_extensions = CallExtensions(**{k: kwargs.pop(k) for k in names if k in kwargs})
+            try:
+                return call(self, *args, **kwargs)
+            finally:
+                self._call_extensions = None
+        return wrapper
+    return decorate
+
+
+@dataclass(frozen=True)
+class UnionTower:
+    """The base flow's second ControlNet in one call: unmasked, evaluated at ``active_steps`` (``union_active_steps``) only."""
+    model: FluxControlNetModel
+    hint: torch.Tensor
+    scale: float
+    active_steps: Tuple[int, ...]
+
+
+@dataclass(frozen=True)
+class LoopExtras:
+    """What a call adds to the plain loop of ``_denoise_eager``. ``_denoise`` takes the first three and sets ``tower_window`` itself."""
+    ip_embeds: Optional[torch.Tensor] = None     # the image prompt, [total or 1, E] ([2·total, E] under true CFG); None: nothing to add
+    union: Optional[UnionTower] = None           # it keeps the side stream and the text towers' row window
+    # true CFG of the base flow: the conditioning batch is [negative, positive] (2B against the latents' B) and the step mixes its halves in
+    # fp32 (``scheduler.step_master_cfg_``); all else sees Bc = 2B
+    cfg_scale: Optional[float] = None
+    tower_window: Any = None                     # ``active_row_window`` of the masks from the call prologue (None: every row)
+    # (FluxControlNetModel, hint, conditioning scale) of unmasked towers after the text lines (the inpaint tower); the loop then stays on one stream
+    extra_towers: Tuple = ()
+    velocity: Optional[Callable] = None          # (i, noise_pred) -> what the scheduler steps with in its place (the inpaint flow's CFG)
+    quiet: bool = False                          # no progress bar (a capture)
 
 
 def do_true_cfg(true_cfg_scale, negative_prompt=None, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None) -> bool:
@@ -228,15 +237,12 @@ class FluxControlNetPipeline:
         self.default_sample_size = 64
         self._guidance_scale, self._joint_attention_kwargs, self._interrupt, self._num_timesteps = 1.0, None, False, 0
         self._progress_disabled = False
-        self._ip_call_args, self._ip_embeds = (None, None), None
+        self._call_extensions: Optional[CallExtensions] = None          # set by accepts_call_extensions while a call runs
         # the IP-Adapter's image side (image_encoder.py); set by from_pretrained / load_ip_adapter or assigned, not components
         self.image_encoder, self.feature_extractor = None, None
         # a second, unmasked ControlNet with its own step window beside the text-line tower (Union-Pro-2.0: canny / depth / pose); set
         # by from_pretrained(controlnet_union=) or assigned, fed by __call__(control_image_union=...) — base pipeline only
         self.controlnet_union: Optional[FluxControlNetModel] = None
-        self._union_call_args, self._union = None, None
-        # the negative prompt of a call (true CFG, base pipeline only): accepts_true_cfg_arguments / _check_true_cfg_inputs
-        self._cfg_call_args, self._cfg_scale = None, None
 
     # ------------------------------------------------------------------ component plumbing
     @property
@@ -730,10 +736,9 @@ class FluxControlNetPipeline:
         return kw is None or (set(kw) == {"scale"} and bool(self._lora_models()))
 
     # ------------------------------------------------------------------ the second ControlNet (controlnet_union)
-    def _check_union_inputs(self, height, width, total) -> bool:
-        """Refusals of the call's ``control_image_union`` against ``self.controlnet_union`` and the first tower — host-side checks on
-        shapes and configs only, made before any device work. True when the union tower takes part in this call."""
-        image = self._union_call_args[0] if self._union_call_args is not None else None
+    def _check_union_inputs(self, image, height, width, total) -> bool:
+        """Refusals of the call's ``control_image_union`` (``image``) against ``self.controlnet_union`` and the first tower — host-side
+        checks on shapes and configs only, made before any device work. True when the union tower takes part in this call."""
         if image is None:
             return False
         un, cn = self.controlnet_union, self.controlnet
@@ -775,15 +780,12 @@ class FluxControlNetPipeline:
         return self._pack_latents(lat, lat.shape[0], lat.shape[1], lat.shape[2], lat.shape[3])
 
     # ------------------------------------------------------------------ the negative prompt (true CFG)
-    def _check_true_cfg_inputs(self, prompt_embeds, pooled_prompt_embeds, batch_size, joint_attention_kwargs) -> bool:
-        """Refusals of the call's negative-prompt arguments — host-side checks on types and shapes only, made before any device work
+    def _check_true_cfg_inputs(self, a: CallExtensions, prompt_embeds, pooled_prompt_embeds, batch_size, joint_attention_kwargs) -> bool:
+        """Refusals of the negative-prompt arguments in ``a`` — host-side checks on types and shapes only, made before any device work
         and whether or not the scale switches CFG on. True when this call runs true CFG (``do_true_cfg``); a scale above 1 without a
         negative prompt logs one line and is the plain call."""
-        a = self._cfg_call_args
-        if a is None:
-            return False
-        neg, neg2 = a["negative_prompt"], a["negative_prompt_2"]
-        npe, npooled = a["negative_prompt_embeds"], a["negative_pooled_prompt_embeds"]
+        neg, neg2 = a.negative_prompt, a.negative_prompt_2
+        npe, npooled = a.negative_prompt_embeds, a.negative_pooled_prompt_embeds
         if (npe is None) != (npooled is None):
             missing = "negative_pooled_prompt_embeds" if npooled is None else "negative_prompt_embeds"
             raise ValueError(f"`{missing}` is missing: negative_prompt_embeds and negative_pooled_prompt_embeds have to be passed together")
@@ -797,16 +799,16 @@ class FluxControlNetPipeline:
         if npe is not None and prompt_embeds is not None:
             self._check_negative_embeds_shape(npe, npooled, prompt_embeds, pooled_prompt_embeds)
         kw = joint_attention_kwargs or {}
-        positive_ip = any(x is not None for x in self._ip_call_args) or "ip_adapter_image_embeds" in kw
+        positive_ip = a.ip_adapter_image is not None or a.ip_adapter_image_embeds is not None or "ip_adapter_image_embeds" in kw
         for name in ("negative_ip_adapter_image", "negative_ip_adapter_image_embeds"):
-            if a[name] is not None and not positive_ip:
+            if getattr(a, name) is not None and not positive_ip:
                 raise ValueError(f"`{name}` was passed without a positive image prompt (ip_adapter_image / ip_adapter_image_embeds)")
-        if a["negative_ip_adapter_image"] is not None and a["negative_ip_adapter_image_embeds"] is not None:
+        if a.negative_ip_adapter_image is not None and a.negative_ip_adapter_image_embeds is not None:
             raise ValueError("pass either negative_ip_adapter_image or negative_ip_adapter_image_embeds, not both")
-        on = do_true_cfg(a["true_cfg_scale"], neg, npe, npooled)
-        if not on and float(a["true_cfg_scale"]) > 1:
+        on = do_true_cfg(a.true_cfg_scale, neg, npe, npooled)
+        if not on and float(a.true_cfg_scale) > 1:
             import sys
-            print(f"[reptext_amd] true_cfg_scale = {a['true_cfg_scale']} without a negative prompt: classifier-free guidance stays off",
+            print(f"[reptext_amd] true_cfg_scale = {a.true_cfg_scale} without a negative prompt: classifier-free guidance stays off",
                   file=sys.stderr, flush=True)
         return on
 
@@ -818,29 +820,28 @@ class FluxControlNetPipeline:
             raise ValueError(f"`negative_pooled_prompt_embeds`: shape {tuple(npooled.shape)} != pooled_prompt_embeds' "
                              f"{tuple(pooled_prompt_embeds.shape)}")
 
-    def _encode_negative_prompt(self, prompt_embeds, pooled_prompt_embeds, batch_size, num_images_per_prompt, max_sequence_length, device):
-        """(negative prompt_embeds, negative pooled) of this call, shaped like the positive ones: the embeddings as passed, or the
+    def _encode_negative_prompt(self, a: CallExtensions, prompt_embeds, pooled_prompt_embeds, batch_size, num_images_per_prompt,
+                                max_sequence_length, device):
+        """(negative prompt_embeds, negative pooled) of the call ``a``, shaped like the positive ones: the embeddings as passed, or the
         negative prompt through ``encode_prompt`` (``negative_prompt_2`` defaults to ``negative_prompt``; one string serves the batch)."""
-        a = self._cfg_call_args
-        npe, npooled = a["negative_prompt_embeds"], a["negative_pooled_prompt_embeds"]
+        npe, npooled = a.negative_prompt_embeds, a.negative_pooled_prompt_embeds
         if npe is None:
             per_prompt = lambda p: [p] * batch_size if isinstance(p, str) else p
-            neg = per_prompt(a["negative_prompt"])
-            neg2 = per_prompt(a["negative_prompt_2"]) if a["negative_prompt_2"] is not None else neg
+            neg = per_prompt(a.negative_prompt)
+            neg2 = per_prompt(a.negative_prompt_2) if a.negative_prompt_2 is not None else neg
             npe, npooled, _ = self.encode_prompt(prompt=neg, prompt_2=neg2, device=device, num_images_per_prompt=num_images_per_prompt,
                                                  max_sequence_length=max_sequence_length)
         self._check_negative_embeds_shape(npe, npooled, prompt_embeds, pooled_prompt_embeds)
         return npe.to(device=device, dtype=prompt_embeds.dtype), npooled.to(device=device, dtype=pooled_prompt_embeds.dtype)
 
-    def _negative_ip_embeds(self, positive: torch.Tensor, total: int, device) -> torch.Tensor:
+    def _negative_ip_embeds(self, a: CallExtensions, positive: torch.Tensor, total: int, device) -> torch.Tensor:
         """The image prompt of the negative half, shaped like ``positive`` ([total or 1, E], what ``_resolve_ip_embeds`` returned):
         ``negative_ip_adapter_image_embeds`` if given, else ``negative_ip_adapter_image`` through ``encode_image``, else an all-black
         image through the same encoder when the positive one was an image, else a zero embedding."""
         from . import ip_adapter as _ipa
 
-        a = self._cfg_call_args
-        neg_image, neg_embeds = a["negative_ip_adapter_image"], a["negative_ip_adapter_image_embeds"]
-        if neg_embeds is None and neg_image is None and self._ip_call_args[0] is not None:
+        neg_image, neg_embeds = a.negative_ip_adapter_image, a.negative_ip_adapter_image_embeds
+        if neg_embeds is None and neg_image is None and a.ip_adapter_image is not None:
             if self.image_encoder is not None:
                 neg_image = self._black_image(self.image_encoder.config.image_size)
         if neg_embeds is None and neg_image is not None:
@@ -865,9 +866,7 @@ class FluxControlNetPipeline:
         return Image.new("RGB", (size, size), (0, 0, 0))
 
     # ------------------------------------------------------------------ the call
-    @accepts_true_cfg_arguments
-    @accepts_union_arguments
-    @accepts_ip_adapter_arguments
+    @accepts_call_extensions(*CallExtensions.__dataclass_fields__)
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 28,
@@ -893,14 +892,15 @@ class FluxControlNetPipeline:
         batch_size = self._batch_size(prompt, prompt_embeds)
         device, dtype = self._execution_device, self.transformer.dtype
         total = batch_size * num_images_per_prompt
-        with_union = self._check_union_inputs(height, width, total)
-        cfg = self._check_true_cfg_inputs(prompt_embeds, pooled_prompt_embeds, batch_size, joint_attention_kwargs)
-        self._ip_embeds, self._joint_attention_kwargs = self._resolve_ip_embeds(*self._ip_call_args, joint_attention_kwargs, batch_size,
-                                                                                num_images_per_prompt, device)
-        if cfg and self._ip_embeds is not None:
+        ext = self._call_extensions
+        with_union = self._check_union_inputs(ext.control_image_union, height, width, total)
+        cfg = self._check_true_cfg_inputs(ext, prompt_embeds, pooled_prompt_embeds, batch_size, joint_attention_kwargs)
+        ip_embeds, self._joint_attention_kwargs = self._resolve_ip_embeds(ext.ip_adapter_image, ext.ip_adapter_image_embeds, joint_attention_kwargs,
+                                                                          batch_size, num_images_per_prompt, device)
+        if cfg and ip_embeds is not None:
             # [2·total, E], negative first like the prompt: rt_ip_attention takes K/V per entry of the conditioning batch
-            pos = self._ip_embeds.expand(total, -1)
-            self._ip_embeds = torch.cat([self._negative_ip_embeds(pos, total, device), pos], dim=0).contiguous()
+            pos = ip_embeds.expand(total, -1)
+            ip_embeds = torch.cat([self._negative_ip_embeds(ext, pos, total, device), pos], dim=0).contiguous()
 
         prompt_embeds, pooled_prompt_embeds, text_ids = self.encode_prompt(
             prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds, device=device,
@@ -909,33 +909,28 @@ class FluxControlNetPipeline:
         pooled_prompt_embeds = pooled_prompt_embeds.to(device=device)
         if cfg:
             # True CFG: the conditioning batch is cat([negative, positive]) (negative first, INP:1034-1035) against latents of batch B;
-            # the models repeat the latents over it, and the step mixes the two halves of the velocity (_denoise_eager: _cfg_scale)
-            npe, npooled = self._encode_negative_prompt(prompt_embeds, pooled_prompt_embeds, batch_size, num_images_per_prompt,
+            # the models repeat the latents over it, and the step mixes the two halves of the velocity (LoopExtras.cfg_scale)
+            npe, npooled = self._encode_negative_prompt(ext, prompt_embeds, pooled_prompt_embeds, batch_size, num_images_per_prompt,
                                                         max_sequence_length, device)
             prompt_embeds = torch.cat([npe, prompt_embeds], dim=0)
             pooled_prompt_embeds = torch.cat([npooled, pooled_prompt_embeds], dim=0)
-            self._cfg_scale = float(self._cfg_call_args["true_cfg_scale"])
 
         hints, height, width = self._collect_hints(control_image, control_position, height, width, total, num_images_per_prompt, device, dtype,
                                                    cfg=cfg)
         # the union hint is encoded AFTER the text lines' hints: a call without it draws the same random numbers as before
-        union_hint = self._union_hint(self._union_call_args[0], width, height, total, num_images_per_prompt, device, dtype) if with_union else None
-        if cfg and union_hint is not None and union_hint.shape[0] == total:
-            union_hint = torch.cat([union_hint] * 2)
+        union_hint = self._doubled_under_cfg(self._union_hint(ext.control_image_union, width, height, total, num_images_per_prompt, device, dtype),
+                                             total, cfg) if with_union else None
         timesteps, num_inference_steps = self._schedule(height, width, num_inference_steps, timesteps, device)
         latents, latent_image_ids = self._initial_latents(control_glyph, total, height, width, prompt_embeds.dtype, device, generator, latents)
-        masks = self._region_masks(control_mask, latents.device, latents.dtype)
-        if cfg:
-            masks = [torch.cat([m] * 2) if m.shape[0] == total and total > 1 else m for m in masks]      # per image [B,N,1]; [1,N,1] is shared
-        if with_union:
-            _, u_scale, u_start, u_end = self._union_call_args
-            active = union_active_steps(len(timesteps), float(u_start), float(u_end))
-            self._union = (self.controlnet_union, union_hint, float(u_scale), active) if active else None
+        masks = [self._doubled_under_cfg(m, total, cfg, mask=True) for m in self._region_masks(control_mask, latents.device, latents.dtype)]
+        active = union_active_steps(len(timesteps), float(ext.control_guidance_start_union), float(ext.control_guidance_end_union)) if with_union else ()
+        union = UnionTower(self.controlnet_union, union_hint, float(ext.controlnet_conditioning_scale_union), active) if active else None
+        extras = LoopExtras(ip_embeds=ip_embeds, union=union, cfg_scale=float(ext.true_cfg_scale) if cfg else None)
 
         self._apply_lora_scale()
         latents = self._denoise(latents, prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids, timesteps, hints, masks,
                                 guidance_scale, controlnet_conditioning_scale, controlnet_conditioning_step, control_mode,
-                                callback_on_step_end, callback_on_step_end_tensor_inputs, num_inference_steps)
+                                callback_on_step_end, callback_on_step_end_tensor_inputs, num_inference_steps, extras)
         return self._finish(latents, height, width, output_type, return_dict)
 
     # ------------------------------------------------------------------ stages of the call (shared with pipeline_inpaint.py)
@@ -944,6 +939,14 @@ class FluxControlNetPipeline:
         if isinstance(prompt, str):
             return 1
         return len(prompt) if isinstance(prompt, list) else prompt_embeds.shape[0]
+
+    @staticmethod
+    def _doubled_under_cfg(t: torch.Tensor, total: int, cfg: bool, mask: bool = False) -> torch.Tensor:
+        """Under CFG the conditioning batch is [negative, positive]: a per-image tensor ([total,N,·]) is doubled, a shared one ([1,N,·])
+        serves both halves. At ``total == 1`` the two forms coincide: a hint counts as per-image, a ``mask`` ([1,N,1], the reference's
+        form) as shared."""
+        per_image = t.shape[0] == total and not (mask and total == 1)
+        return torch.cat([t] * 2) if cfg and per_image else t
 
     def _collect_hints(self, control_image, control_position, height, width, total, num_images_per_prompt, device, dtype, cfg=False):
         """One packed [B,N,128] hint per text line (PIPE:928-942), doubled under true CFG; returns (hints, height, width) as
@@ -954,8 +957,7 @@ class FluxControlNetPipeline:
             positions = control_position if control_position is not None else [None] * len(control_image)
             for img, pos in zip(control_image, positions):
                 if self._is_packed_hint(img):
-                    h = img.to(device=device, dtype=dtype)
-                    hints.append(torch.cat([h] * 2) if (cfg and h.shape[0] == total) else h)
+                    hints.append(self._doubled_under_cfg(img.to(device=device, dtype=dtype), total, cfg))
                 else:
                     h, height, width = self.prepare_image(image=img, image_position=pos, width=width, height=height, batch_size=total,
                                                           num_images_per_prompt=num_images_per_prompt, device=device, dtype=dtype,
@@ -1016,19 +1018,19 @@ class FluxControlNetPipeline:
 
     # ------------------------------------------------------------------ hot loop (PIPE:1016-1130)
     def _denoise(self, latents, prompt_embeds, pooled, text_ids, image_ids, timesteps, hints, masks, guidance_scale,
-                 cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps):
-        """Eager loop, or the replay of its captured hipGraph when this exact call signature has been seen before (GRAPH_CAPTURE)."""
+                 cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, extras: Optional[LoopExtras] = None):
+        """Eager loop, or the replay of its captured hipGraph when this exact call signature has been seen before (GRAPH_CAPTURE).
+        ``extras``: the image prompt, the union tower and the CFG scale of the call (None: a plain loop)."""
         tvals = timesteps.to(torch.float32).cpu().tolist()                 # host copies: no per-step device sync
-        ipe = getattr(self, "_ip_embeds", None)                             # image prompt of this call (None: nothing to add)
         # the rows the regional masks leave non-zero: read here, never inside the loop or a capture; part of the call signature below
         win = active_row_window(masks, latents.shape[1]) if masks and len(masks) == len(hints) else None
-        union = getattr(self, "_union", None)         # (tower, hint, scale, active steps) of this call's second ControlNet, or None
-        cfg_scale = getattr(self, "_cfg_scale", None)  # true CFG of this call: prompt_embeds / pooled / hints hold [negative, positive]
+        extras = replace(extras or LoopExtras(), tower_window=win)
+        # under true CFG (cfg_scale) prompt_embeds / pooled / hints hold [negative, positive]
+        ipe, union, cfg_scale = extras.ip_embeds, extras.union, extras.cfg_scale
 
         def eager(callback=None):
             return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
-                                       cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _ip_embeds=ipe,
-                                       _tower_window=win, _union=union, _cfg_scale=cfg_scale)
+                                       cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, extras=extras)
 
         use_graph = (GRAPH_CAPTURE and getattr(self, "capture_graphs", True) and callback is None and latents.is_cuda
                      and not self.interrupt and isinstance(self.controlnet, (FluxControlNetModel, type(None)))
@@ -1054,8 +1056,8 @@ class FluxControlNetPipeline:
             ins["ip_embeds"] = ipe
         if union is not None:
             # the union hint is one more static input; the tower's scale and its active steps are baked into the capture
-            key += ("union", ident(union[0]), sig(union[1]), union[2], union[3])
-            ins["union_hint"] = union[1]
+            key += ("union", ident(union.model), sig(union.hint), union.scale, union.active_steps)
+            ins["union_hint"] = union.hint
         if cfg_scale is not None:
             # the scale is a kernel scalar of every step (rt_cfg_euler_step_f32); the static inputs' shapes already carry the batch 2B
             key += (("cfg", cfg_scale),)
@@ -1074,7 +1076,7 @@ class FluxControlNetPipeline:
             keep = [m._ensure_plans() for m in (self.transformer, self.controlnet) if m is not None] + [getattr(self.controlnet, "_cx_pad", None)]
             keep.append(getattr(self.transformer, "_ip_adapter", None) if ipe is not None else None)     # its weights are read by the graph
             if union is not None:
-                keep += [union[0]._ensure_plans(), getattr(union[0], "_cx_pad", None)]
+                keep += [union.model._ensure_plans(), getattr(union.model, "_cx_pad", None)]
             graph = torch.cuda.CUDAGraph()
             step_index = self.scheduler._step_index
             # The graph bakes in the device pointers of every buffer the loop touches. Buffers that live in caches which may evict or
@@ -1086,11 +1088,11 @@ class FluxControlNetPipeline:
             try:
                 # thread-local capture mode: calls made by OTHER threads (RCCL's watchdog polling its events) do not invalidate the capture
                 with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                    captured = replace(extras, quiet=True, ip_embeds=static.get("ip_embeds"),
+                                       union=union and replace(union, hint=static["union_hint"]))
                     out = self._denoise_eager(static["latents"], static["prompt_embeds"], static["pooled"], static["text_ids"], static["image_ids"],
                                               tvals, static["hints"], static["masks"], guidance_scale, cn_scale, cn_steps, control_mode, None,
-                                              callback_inputs, num_inference_steps, timesteps, _quiet=True, _ip_embeds=static.get("ip_embeds"),
-                                              _tower_window=win, _cfg_scale=cfg_scale,
-                                              _union=None if union is None else (union[0], static["union_hint"]) + tuple(union[2:]))
+                                              callback_inputs, num_inference_steps, timesteps, extras=captured)
                     out32 = self._master_latents
             except Exception as e:                           # capture is an optimisation, never a requirement
                 import sys
@@ -1105,7 +1107,7 @@ class FluxControlNetPipeline:
                 return eager()
             _mm.CAPTURE_KEEP = ops.CAPTURE_KEEP = None
             keep.append(getattr(self, "_sample_cache", None))
-            keep.extend(dict(m._rope_cache) for m in (self.transformer, self.controlnet, union[0] if union is not None else None)
+            keep.extend(dict(m._rope_cache) for m in (self.transformer, self.controlnet, union and union.model)
                         if m is not None and hasattr(m, "_rope_cache"))
             self.scheduler._step_index = step_index
             # the sample buffers the capture wrote into and the window its zero-linears were restricted to (None: every row)
@@ -1137,16 +1139,11 @@ class FluxControlNetPipeline:
         state[0] = window
 
     def _denoise_eager(self, latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale,
-                       cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, _quiet=False,
-                       _ip_embeds=None, _extra_towers=(), _velocity=None, _tower_window=None, _union=None, _cfg_scale=None):
-        """The one loop over timesteps, for both pipelines. Every tower — text lines, ``_extra_towers``, ``_union`` — is a ``_Tower`` of
-        one list, and each step walks its entry of ``tower_schedule``, which alone decides who runs when and in which order.
-        ``_extra_towers``: (FluxControlNetModel, hint, conditioning scale) of unmasked towers after the text lines (the inpaint tower);
-        with them the loop stays on one stream. ``_union``: (FluxControlNetModel, hint, conditioning scale, active steps) of the base
-        flow's second tower, unmasked; it keeps the side stream and the text towers' row window. ``_velocity(i, noise_pred)``: what the
-        scheduler steps with instead of the transformer's output (the inpaint flow's CFG). ``_tower_window``: ``active_row_window`` of
-        ``masks`` from the call prologue (None: every row). ``_cfg_scale``: true CFG of the base flow — the conditioning batch is [negative,
-        positive] (2B against the latents' B) and the step mixes its halves in fp32 (``scheduler.step_master_cfg_``); all else sees Bc = 2B."""
+                       cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps,
+                       extras: LoopExtras = LoopExtras()):
+        """The one loop over timesteps, for both pipelines. Every tower — text lines, ``extras.extra_towers``, ``extras.union`` — is a
+        ``_Tower`` of one list, and each step walks its entry of ``tower_schedule``, which alone decides who runs when and in which order."""
+        union, extra_towers = extras.union, extras.extra_towers
         device, B = latents.device, latents.shape[0]
         guidance = torch.full((B,), float(guidance_scale), device=device, dtype=torch.float32) if self.transformer.config.guidance_embeds else None
         # one regional mask per text line, shared by the batch ([1,N,1], the reference's form) or one per image ([B,N,1])
@@ -1160,16 +1157,17 @@ class FluxControlNetPipeline:
         fused_cn = isinstance(self.controlnet, FluxControlNetModel) and len(hints) > 0
         # The towers of every step and every tower of this call, numbered as `tower_schedule` numbers them. The union tower's table holds
         # ITS active steps only; the text lines share one table over the steps below `cn_steps`, whose steps the extra towers follow.
-        union_active = _union[3] if _union is not None and isinstance(self.controlnet, FluxControlNetModel) else ()
-        steps = tower_schedule(len(tvals), cn_steps, len(hints) if fused_cn else 0, union_active, len(_extra_towers))
+        union_active = union.active_steps if union is not None and isinstance(self.controlnet, FluxControlNetModel) else ()
+        steps = tower_schedule(len(tvals), cn_steps, len(hints) if fused_cn else 0, union_active, len(extra_towers))
         towers: List[_Tower] = []
         if union_active:
-            towers.append(_Tower(*_union[:3], None, _union[0].build_modulation_table([model_ts[i] for i in union_active], g_tab, pooled), masked=False))
+            towers.append(_Tower(union.model, union.hint, union.scale, None,
+                                 union.model.build_modulation_table([model_ts[i] for i in union_active], g_tab, pooled), masked=False))
         if fused_cn and cn_steps > 0:
             ts_c = model_ts[: min(len(model_ts), cn_steps)]
             tab_c = self.controlnet.build_modulation_table(ts_c, g_tab, pooled)
             towers += [_Tower(self.controlnet, h, cn_scale, rowscales[line] if rowscales else None, tab_c, masked=True) for line, h in enumerate(hints)]
-            towers += [_Tower(m, h, s, None, m.build_modulation_table(ts_c, g_tab, pooled), masked=False) for m, h, s in _extra_towers]
+            towers += [_Tower(m, h, s, None, m.build_modulation_table(ts_c, g_tab, pooled), masked=False) for m, h, s in extra_towers]
         # Loop-invariant work, once per image instead of once per step (the prompt and the hint latents do not change inside the
         # loop): context_embedder(prompt) of every model, controlnet_x_embedder(hint) per tower. A callback that replaces
         # prompt_embeds invalidates them (recomputed below).
@@ -1181,7 +1179,7 @@ class FluxControlNetPipeline:
 
         static_t = prepare_static(prompt_embeds)
         # the image prompt's tokens and every block's K/V of them: loop-invariant too (ip_adapter.py steps 1-2)
-        ip_prep = self.transformer._ip_adapter.prepare(_ip_embeds) if _ip_embeds is not None else None
+        ip_prep = self.transformer._ip_adapter.prepare(extras.ip_embeds) if extras.ip_embeds is not None else None
         # Which tower samples does the transformer read? Block i takes sample i // ceil(n_blocks / n_samples) (A.3): with 6
         # samples against 19 double blocks the sixth is never consumed (Q5), so its block and zero-linear are not evaluated.
         # A tower of another depth adds into the first tower's buffers (it must not be deeper: there is one buffer per block
@@ -1204,9 +1202,9 @@ class FluxControlNetPipeline:
             sample_buf, single_buf = self._sample_cache[1], self._sample_cache[2]
         # Zero-linears and the last block of the masked towers on the masked rows only (controlnet.forward: _window). The extra towers
         # are unmasked and ADD to every row of the buffers, step after step, so with them every row must be overwritten first: full path.
-        use_window = (TOWER_WINDOW and any(tw.masked for tw in towers) and not _extra_towers and blocks_needed is not None
+        use_window = (TOWER_WINDOW and any(tw.masked for tw in towers) and not extra_towers and blocks_needed is not None
                       and blocks_needed[0] >= 1 and blocks_needed[1] == 0 and self.controlnet.supports_row_window())
-        self._tower_window_used = window = _tower_window if use_window else None
+        self._tower_window_used = window = extras.tower_window if use_window else None
         # A union step writes every row, so with a union tower the "rows outside the window read zero" promise is kept by the step
         # sequence itself: the buffers count as dirty from the start and after every union step, and the first text-only step that
         # follows zeroes them on the tower's stream (captured with the loop; one fill per transition of the union interval).
@@ -1223,11 +1221,11 @@ class FluxControlNetPipeline:
         # sample buffers and the transformer waits, block by block, on the event of the sample it needs. At batch 1 most
         # launches fill only 27/32 of their last round of workgroups (216 GEMM tiles on 256 CUs, 864 attention workgroups on
         # 512 slots); two independent chains in flight fill some of those holes. Results are bitwise those of the serial order.
-        # `not _extra_towers`: the inpaint flow is serial by decision (its second tower has no side stream or "tower" workspace of its
+        # `not extra_towers`: the inpaint flow is serial by decision (its second tower has no side stream or "tower" workspace of its
         # own yet); an extra tower added to the BASE flow would switch the overlap off here too — extend this rule then, not the call.
         # The base flow's union tower shares the side stream and the "tower" workspace with the text towers: the towers of a step are
         # serial with each other, only the transformer runs beside them.
-        overlap = (OVERLAP_TOWER and bool(towers) and not _extra_towers and device.type == "cuda"
+        overlap = (OVERLAP_TOWER and bool(towers) and not extra_towers and device.type == "cuda"
                    and len(self.controlnet.single_transformer_blocks) == 0)
         side = sample_ev = None
         if overlap:
@@ -1235,7 +1233,7 @@ class FluxControlNetPipeline:
                 self._side_stream = torch.cuda.Stream(device=device)
             side = self._side_stream
             sample_ev = [torch.cuda.Event() for _ in range(len(self.controlnet.transformer_blocks))]
-        with (_Progress(num_inference_steps, disable=True) if _quiet else self.progress_bar(total=num_inference_steps)) as bar:
+        with (_Progress(num_inference_steps, disable=True) if extras.quiet else self.progress_bar(total=num_inference_steps)) as bar:
             for i, t in enumerate(tvals):
                 if self.interrupt:
                     continue
@@ -1277,10 +1275,10 @@ class FluxControlNetPipeline:
                     _mods=tab_t.step(i), _sample_events=events, _static=static_t, _ip=ip_prep)[0]
                 if events is not None:
                     torch.cuda.current_stream().wait_stream(side)     # the tower has finished reading `latents` (its last sample is unused, Q5)
-                if _velocity is not None:
-                    noise_pred = _velocity(i, noise_pred)
-                if _cfg_scale is not None:
-                    self.scheduler.step_master_cfg_(noise_pred[:B], noise_pred[B:], _cfg_scale, lat32, latents)
+                if extras.velocity is not None:
+                    noise_pred = extras.velocity(i, noise_pred)
+                if extras.cfg_scale is not None:
+                    self.scheduler.step_master_cfg_(noise_pred[:B], noise_pred[B:], extras.cfg_scale, lat32, latents)
                 else:
                     self.scheduler.step_master_(noise_pred, lat32, latents)
                 if callback is not None:

@@ -8,8 +8,8 @@ Interface parity target: /root/reference/RepText/pipeline_flux_controlnet_inpain
   * __call__ keywords ............................................................... INP:846-883
   * loop: text towers (masked, summed) + inpaint tower (unmasked) + CFG mix with a zero first step (Q6,Q7,Q8) ... INP:1138-1285
 This file holds only what the inpaint flow adds: the negative prompt, the masked-image hint, and a ``__call__`` that hands the
-inpaint tower and the CFG mix to the base class's loop (``_denoise_eager``: ``_extra_towers``, ``_velocity``). The stages of the
-call (hints, schedule, initial latents, decode) and the loop itself live in pipeline.py, once.
+inpaint tower and the CFG mix to the base class's loop (``_denoise_eager``: ``LoopExtras.extra_towers``, ``.velocity``). The stages of
+the call (hints, schedule, initial latents, decode) and the loop itself live in pipeline.py, once.
 """
 from __future__ import annotations
 
@@ -21,7 +21,7 @@ import torch.nn.functional as F
 from . import ops
 from .image_processor import PipelineImageInput, VaeImageProcessor
 from .pipeline import FluxControlNetPipeline as _BasePipeline
-from .pipeline import accepts_ip_adapter_arguments
+from .pipeline import LoopExtras, accepts_call_extensions
 
 DEFAULT_NEGATIVE_PROMPT = "bad quality, worst quality, text, signature, watermark, extra words"     # INP:416
 
@@ -84,7 +84,7 @@ class FluxControlNetPipeline(_BasePipeline):
         return packed, height, width
 
     # ------------------------------------------------------------------ INP:846-1313
-    @accepts_ip_adapter_arguments
+    @accepts_call_extensions("ip_adapter_image", "ip_adapter_image_embeds")      # taken only to be refused by name below
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  true_guidance_scale: float = 3.5, negative_prompt: Optional[Union[str, List[str]]] = None,
@@ -110,7 +110,8 @@ class FluxControlNetPipeline(_BasePipeline):
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, prompt_2, height, width, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,
                           callback_on_step_end_tensor_inputs=callback_on_step_end_tensor_inputs, max_sequence_length=max_sequence_length)
-        if any(a is not None for a in self._ip_call_args) or "ip_adapter_image_embeds" in (joint_attention_kwargs or {}):
+        ext = self._call_extensions
+        if ext.ip_adapter_image is not None or ext.ip_adapter_image_embeds is not None or "ip_adapter_image_embeds" in (joint_attention_kwargs or {}):
             # the conditioning batch is 2B under true CFG: the unconditional half would need a negative image prompt
             raise ValueError("the inpaint pipeline does not support IP-Adapter image prompts (ip_adapter_image / ip_adapter_image_embeds)")
         self._guidance_scale, self._joint_attention_kwargs, self._interrupt = guidance_scale, joint_attention_kwargs, False
@@ -134,18 +135,14 @@ class FluxControlNetPipeline(_BasePipeline):
         hints, height, width = self._collect_hints(control_image, control_position, height, width, total, num_images_per_prompt, device,
                                                    dtype, cfg=cfg)
         if self._is_packed_hint(control_image_inpaint, self.controlnet_inpaint):
-            hint_inp = control_image_inpaint.to(device=device, dtype=dtype)
-            if cfg and hint_inp.shape[0] == total:
-                hint_inp = torch.cat([hint_inp] * 2)
+            hint_inp = self._doubled_under_cfg(control_image_inpaint.to(device=device, dtype=dtype), total, cfg)
         else:
             hint_inp, height, width = self.prepare_image_with_mask(image=control_image_inpaint, mask=control_mask_inpaint, width=width,
                                                                    height=height, batch_size=total, num_images_per_prompt=num_images_per_prompt,
                                                                    device=device, dtype=dtype, do_classifier_free_guidance=cfg)
         timesteps, num_inference_steps = self._schedule(height, width, num_inference_steps, timesteps, device)
         latents, image_ids = self._initial_latents(control_glyph, total, height, width, pe.dtype, device, generator, latents)
-        masks = self._region_masks(control_mask, latents.device, latents.dtype)
-        if cfg:
-            masks = [torch.cat([m] * 2) if m.shape[0] == total and total > 1 else m for m in masks]      # per image [B,N,1]; [1,N,1] is shared
+        masks = [self._doubled_under_cfg(m, total, cfg, mask=True) for m in self._region_masks(control_mask, latents.device, latents.dtype)]
 
         def cfg_velocity(i, noise_pred):
             """True CFG on the two halves of the conditioning batch (negative first, INP:1264-1270); zero velocity at step 0 (Q7)."""
@@ -158,6 +155,6 @@ class FluxControlNetPipeline(_BasePipeline):
         latents = self._denoise_eager(latents, pe, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale,
                                       controlnet_conditioning_scale, controlnet_conditioning_step, control_mode, callback_on_step_end,
                                       callback_on_step_end_tensor_inputs, num_inference_steps, timesteps,
-                                      _extra_towers=[(self.controlnet_inpaint, hint_inp, controlnet_conditioning_scale_inpaint)],
-                                      _velocity=cfg_velocity if cfg else None)
+                                      extras=LoopExtras(extra_towers=((self.controlnet_inpaint, hint_inp, controlnet_conditioning_scale_inpaint),),
+                                                        velocity=cfg_velocity if cfg else None))
         return self._finish(latents, height, width, output_type, return_dict)

@@ -1,8 +1,8 @@
 """Reference of the text-to-image denoising loop under true CFG (a negative prompt), assembled from the oracle's model forwards.
 Not a test module: test_true_cfg_gpu.py imports it.
 
-The contract of pipeline._denoise_eager with ``_cfg_scale``: the conditioning batch is cat([negative, positive]) against latents of
-batch B, which the models see repeated ([lat_0..lat_{B-1}, lat_0..]); hints, the union hint and per-image masks are doubled the same
+The contract of pipeline._denoise_eager with ``extras.cfg_scale`` (pipeline.LoopExtras): the conditioning batch is
+cat([negative, positive]) against latents of batch B, which the models see repeated ([lat_0..lat_{B-1}, lat_0..]); hints, the union hint and per-image masks are doubled the same
 way, a shared [1,N,1] mask serves both halves; at EVERY step (no zero-velocity first step: that quirk is the inpaint pipeline's)
 
     latents <- latents + (sigma_{i+1} - sigma_i) · (v_neg + s · (v_pos - v_neg))

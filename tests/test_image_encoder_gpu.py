@@ -15,6 +15,7 @@ pytestmark = pytest.mark.gpu
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ip_adapter_reference as ipr  # noqa: E402
 import small_head_attention as sha  # noqa: E402
+from test_true_cfg_host import assert_no_call_state  # noqa: E402
 
 
 def rel_l2(a, b):
@@ -239,7 +240,7 @@ def test_pipeline_image_prompt_is_the_embeds_path(gpu):
     assert torch.equal(pipe(**kw, ip_adapter_image=img2).images, other)        # another image: new values of the same static input
     assert len(calls) == n_before
     pipe._denoise_eager = orig
-    assert pipe._ip_embeds is None and pipe._ip_call_args == (None, None)
+    assert_no_call_state(pipe)
     # scale 0 short-circuits after the encoder; no adapter is still the embeds path's error
     pipe.set_ip_adapter_scale(0.0)
     assert torch.equal(pipe(**kw, ip_adapter_image=img1).images, base)

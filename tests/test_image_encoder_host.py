@@ -10,6 +10,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ip_adapter_reference as ipr  # noqa: E402
+from test_true_cfg_host import assert_no_call_state  # noqa: E402
 
 TINY = dict(hidden_size=128, intermediate_size=256, num_hidden_layers=2, num_attention_heads=2, image_size=56, patch_size=14, projection_dim=32)
 
@@ -180,7 +181,7 @@ def test_pipeline_rules_without_a_device(tmp_path):
         pipe(**kw, ip_adapter_image=torch.zeros(3, 3, 56, 56))
     with pytest.raises(RuntimeError, match="no CPU fallback"):                  # a valid request reaches the encoder, which has no CPU path
         pipe(**kw, ip_adapter_image=img)
-    assert pipe._ip_embeds is None and pipe._ip_call_args == (None, None)
+    assert_no_call_state(pipe)
     # a directory that holds an encoder is loaded by load_ip_adapter
     pipe.image_encoder.save_pretrained(str(tmp_path / "enc"))
     pipe.image_encoder = None

@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ip_adapter_reference as ipr  # noqa: E402
+from test_true_cfg_host import assert_no_call_state  # noqa: E402
 
 from oracle import flux_oracle as orc  # noqa: E402
 
@@ -287,7 +288,7 @@ def test_pipeline_two_steps_with_tower_masks_and_adapter(gpu):
     assert moved >= 10 * floor
     assert_at_dtype_floor(err, err16, floor)
     assert torch.equal(pipe(**kw, joint_attention_kwargs={"ip_adapter_image_embeds": emb}).images.float().cpu(), out)
-    assert pipe._ip_embeds is None and pipe._ip_call_args == (None, None)      # nothing of the call is left on the pipeline
+    assert_no_call_state(pipe)
     pipe.set_ip_adapter_scale(0.0)
     assert torch.equal(pipe(**kw, ip_adapter_image_embeds=emb).images, base)   # all scales 0
     pipe.set_ip_adapter_scale(1.0)

@@ -10,6 +10,7 @@ pytestmark = pytest.mark.gpu
 
 from oracle import flux_oracle as orc  # noqa: E402
 from test_models_gpu import assert_at_dtype_floor  # noqa: E402
+from test_true_cfg_host import assert_no_call_state  # noqa: E402
 from test_vae_pipeline_gpu import SMALL_CN, SMALL_T, rel_l2  # noqa: E402
 
 import instantx_reference as ixr  # noqa: E402
@@ -228,7 +229,7 @@ def test_cfg_loop_graph_replay_is_bitwise_the_eager_loop(gpu):
     assert not torch.equal(eager3, eager)
     assert len(graph_keys(pipe)) == 2 and ("cfg", 3.0) in graph_keys(pipe)[1]
     assert torch.equal(pipe(**kw).images, eager)
-    assert pipe._cfg_call_args is None and pipe._cfg_scale is None
+    assert_no_call_state(pipe)
 
 
 # ------------------------------------------------------------------------------------------------------------------ 5. batch

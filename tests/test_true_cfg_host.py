@@ -47,6 +47,13 @@ def _pipe(inpaint=False):
     return FluxControlNetPipeline(FlowMatchEulerDiscreteScheduler(), None, None, None, None, None, tr, None)
 
 
+def assert_no_call_state(pipe):
+    """Nothing of a call is left on the pipeline: the one attribute that carries a call's extension arguments is None again, and none of
+    the six attributes that once carried them and what was derived from them exists."""
+    assert pipe._call_extensions is None
+    assert not {"_ip_call_args", "_ip_embeds", "_union_call_args", "_union", "_cfg_call_args", "_cfg_scale"} & set(pipe.__dict__)
+
+
 def _kw(B=1, T=8):
     return dict(prompt_embeds=torch.zeros(B, T, C), pooled_prompt_embeds=torch.zeros(B, 32), height=64, width=64, num_inference_steps=1)
 
@@ -105,7 +112,7 @@ def test_positive_and_negative_image_prompts_are_checked_together(no_native_call
     # the positive one inside joint_attention_kwargs counts as a positive one: the next refusal in line is the width check of the embeds
     with pytest.raises(ValueError, match="width 48"):
         pipe(**_kw(), joint_attention_kwargs={"ip_adapter_image_embeds": torch.zeros(1, 1, 48)}, negative_ip_adapter_image_embeds=pos)
-    assert pipe._cfg_call_args is None and pipe._cfg_scale is None      # nothing of a call is left on the pipeline
+    assert_no_call_state(pipe)
 
 
 def test_inpaint_pipeline_does_not_take_true_cfg_scale():
@@ -116,26 +123,31 @@ def test_inpaint_pipeline_does_not_take_true_cfg_scale():
 
 
 def test_a_scale_without_a_negative_prompt_logs_one_line_and_stays_off(capsys):
+    from reptext_amd.pipeline import CallExtensions
+
     pipe = _pipe()
-    pipe._cfg_call_args = dict(negative_prompt=None, negative_prompt_2=None, true_cfg_scale=3.5, negative_prompt_embeds=None,
-                               negative_pooled_prompt_embeds=None, negative_ip_adapter_image=None, negative_ip_adapter_image_embeds=None)
+    ext = CallExtensions(negative_prompt=None, negative_prompt_2=None, true_cfg_scale=3.5, negative_prompt_embeds=None,
+                         negative_pooled_prompt_embeds=None, negative_ip_adapter_image=None, negative_ip_adapter_image_embeds=None)
     kw = _kw()
-    assert pipe._check_true_cfg_inputs(kw["prompt_embeds"], kw["pooled_prompt_embeds"], 1, None) is False
+    assert pipe._check_true_cfg_inputs(ext, kw["prompt_embeds"], kw["pooled_prompt_embeds"], 1, None) is False
     err = capsys.readouterr().err
     assert err.count("\n") == 1 and "true_cfg_scale" in err and "negative prompt" in err
-    pipe._cfg_call_args["true_cfg_scale"] = 1.0
-    pipe._cfg_call_args["negative_prompt"] = "blurry"
-    assert pipe._check_true_cfg_inputs(kw["prompt_embeds"], kw["pooled_prompt_embeds"], 1, None) is False
-    pipe._cfg_call_args["true_cfg_scale"] = 1.5
-    assert pipe._check_true_cfg_inputs(kw["prompt_embeds"], kw["pooled_prompt_embeds"], 1, None) is True
+    ext.true_cfg_scale = 1.0
+    ext.negative_prompt = "blurry"
+    assert pipe._check_true_cfg_inputs(ext, kw["prompt_embeds"], kw["pooled_prompt_embeds"], 1, None) is False
+    ext.true_cfg_scale = 1.5
+    assert pipe._check_true_cfg_inputs(ext, kw["prompt_embeds"], kw["pooled_prompt_embeds"], 1, None) is True
     assert capsys.readouterr().err == ""
-    pipe._cfg_call_args = None
-    assert pipe._check_true_cfg_inputs(kw["prompt_embeds"], kw["pooled_prompt_embeds"], 1, None) is False      # a direct _denoise user
+    # no extension passed at all, which is what a direct _denoise user amounts to
+    assert pipe._check_true_cfg_inputs(CallExtensions(), kw["prompt_embeds"], kw["pooled_prompt_embeds"], 1, None) is False
+    assert capsys.readouterr().err == ""
 
 
 def test_negative_prompt_is_encoded_by_the_same_path(monkeypatch):
     """negative_prompt_2 defaults to negative_prompt, one string serves the batch, num_images_per_prompt and max_sequence_length are
     passed on; the result must have the positive embeddings' shape."""
+    from reptext_amd.pipeline import CallExtensions
+
     pipe = _pipe()
     seen = []
 
@@ -147,20 +159,20 @@ def test_negative_prompt_is_encoded_by_the_same_path(monkeypatch):
     monkeypatch.setattr(pipe, "encode_prompt", encode_prompt)
     args = dict(negative_prompt="blurry", negative_prompt_2=None, true_cfg_scale=2.0, negative_prompt_embeds=None,
                 negative_pooled_prompt_embeds=None, negative_ip_adapter_image=None, negative_ip_adapter_image_embeds=None)
-    pipe._cfg_call_args = dict(args)
+    ext = CallExtensions(**args)
     pe, pooled = torch.zeros(4, 8, C, dtype=torch.bfloat16), torch.zeros(4, 32, dtype=torch.bfloat16)
-    npe, npooled = pipe._encode_negative_prompt(pe, pooled, 2, 2, 8, "cpu")
+    npe, npooled = pipe._encode_negative_prompt(ext, pe, pooled, 2, 2, 8, "cpu")
     assert seen == [(["blurry", "blurry"], ["blurry", "blurry"], 2, 8)]
     assert npe.shape == pe.shape and npooled.shape == pooled.shape and npe.dtype == torch.bfloat16 and float(npe.float().min()) == 1.0
-    pipe._cfg_call_args = dict(args, negative_prompt=["a", "b"], negative_prompt_2="c")
-    pipe._encode_negative_prompt(pe, pooled, 2, 2, 8, "cpu")
+    ext = CallExtensions(**dict(args, negative_prompt=["a", "b"], negative_prompt_2="c"))
+    pipe._encode_negative_prompt(ext, pe, pooled, 2, 2, 8, "cpu")
     assert seen[-1] == (["a", "b"], ["c", "c"], 2, 8)
     with pytest.raises(ValueError, match="`negative_prompt_embeds`"):           # T = 8 positive embeddings against max_sequence_length 16
-        pipe._encode_negative_prompt(pe, pooled, 2, 2, 16, "cpu")
+        pipe._encode_negative_prompt(ext, pe, pooled, 2, 2, 16, "cpu")
     # embeddings as passed are taken as they are
-    pipe._cfg_call_args = dict(args, negative_prompt=None, negative_prompt_embeds=pe + 2, negative_pooled_prompt_embeds=pooled + 3)
+    ext = CallExtensions(**dict(args, negative_prompt=None, negative_prompt_embeds=pe + 2, negative_pooled_prompt_embeds=pooled + 3))
     n = len(seen)
-    npe, npooled = pipe._encode_negative_prompt(pe, pooled, 2, 2, 8, "cpu")
+    npe, npooled = pipe._encode_negative_prompt(ext, pe, pooled, 2, 2, 8, "cpu")
     assert len(seen) == n and float(npe.float().min()) == 2.0 and float(npooled.float().min()) == 3.0
 
 
@@ -168,6 +180,8 @@ def test_the_negative_image_prompt_rule_with_a_stub_encoder(monkeypatch):
     """negative embeds if given; else the negative image through encode_image; else an all-black image through the same encoder when
     the positive prompt was an image; else a zero embedding."""
     from PIL import Image
+
+    from reptext_amd.pipeline import CallExtensions
 
     pipe = _pipe()
     pipe.image_encoder = type("Enc", (), {"config": type("Cfg", (), {"image_size": 24})()})()
@@ -179,37 +193,30 @@ def test_the_negative_image_prompt_rule_with_a_stub_encoder(monkeypatch):
 
     monkeypatch.setattr(pipe, "encode_image", encode_image)
     none = dict(negative_ip_adapter_image=None, negative_ip_adapter_image_embeds=None)
+    negative = lambda ext: pipe._negative_ip_embeds(ext, positive, 2, "cpu")
     positive = torch.ones(2, E, dtype=torch.bfloat16)
     picture = Image.new("RGB", (8, 8), (200, 10, 10))
     # 1. explicit embeds win, also over a positive image; one row serves the batch
-    pipe._ip_call_args = (picture, None)
-    pipe._cfg_call_args = dict(none, negative_ip_adapter_image_embeds=torch.full((1, 1, E), 7.0))
-    out = pipe._negative_ip_embeds(positive, 2, "cpu")
+    out = negative(CallExtensions(ip_adapter_image=picture, **dict(none, negative_ip_adapter_image_embeds=torch.full((1, 1, E), 7.0))))
     assert seen == [] and out.shape == (2, E) and out.dtype == torch.bfloat16 and float(out.float().min()) == 7.0
     # 2. a negative image goes through the encoder
-    pipe._cfg_call_args = dict(none, negative_ip_adapter_image=picture)
-    out = pipe._negative_ip_embeds(positive, 2, "cpu")
+    out = negative(CallExtensions(ip_adapter_image=picture, **dict(none, negative_ip_adapter_image=picture)))
     assert seen == [picture] and out.shape == (2, E) and float(out.float().min()) == 5.0
     # 3. nothing negative, the positive was an image: an all-black image at the encoder's size through the same encoder
-    pipe._cfg_call_args = dict(none)
-    out = pipe._negative_ip_embeds(positive, 2, "cpu")
+    out = negative(CallExtensions(ip_adapter_image=picture, **none))
     assert len(seen) == 2 and isinstance(seen[1], Image.Image) and seen[1].size == (24, 24) and seen[1].getextrema() == ((0, 0),) * 3
     assert float(out.float().min()) == 5.0
     # 4. nothing negative, the positive were embeds: zeros, no encoder run
-    pipe._ip_call_args = (None, positive)
-    out = pipe._negative_ip_embeds(positive, 2, "cpu")
+    out = negative(CallExtensions(ip_adapter_image_embeds=positive, **none))
     assert len(seen) == 2 and out.shape == (2, E) and float(out.float().abs().max()) == 0.0
     # refusals
-    pipe._cfg_call_args = dict(none, negative_ip_adapter_image_embeds=torch.zeros(1, 1, 48))
     with pytest.raises(ValueError, match="negative_ip_adapter_image_embeds: width 48"):
-        pipe._negative_ip_embeds(positive, 2, "cpu")
-    pipe._cfg_call_args = dict(none, negative_ip_adapter_image_embeds=torch.zeros(3, 1, E))
+        negative(CallExtensions(ip_adapter_image_embeds=positive, **dict(none, negative_ip_adapter_image_embeds=torch.zeros(1, 1, 48))))
     with pytest.raises(ValueError, match="negative_ip_adapter_image_embeds: batch 3"):
-        pipe._negative_ip_embeds(positive, 2, "cpu")
+        negative(CallExtensions(ip_adapter_image_embeds=positive, **dict(none, negative_ip_adapter_image_embeds=torch.zeros(3, 1, E))))
     pipe.image_encoder = None
-    pipe._cfg_call_args = dict(none, negative_ip_adapter_image=picture)
     with pytest.raises(NotImplementedError, match="negative_ip_adapter_image_embeds"):
-        pipe._negative_ip_embeds(positive, 2, "cpu")
+        negative(CallExtensions(ip_adapter_image_embeds=positive, **dict(none, negative_ip_adapter_image=picture)))
 
 
 def test_token_masks_per_image_are_taken_as_they_are():

@@ -6,6 +6,8 @@ from types import SimpleNamespace
 import pytest
 import torch
 
+from test_true_cfg_host import assert_no_call_state
+
 SMALL_T = dict(patch_size=1, in_channels=64, num_layers=1, num_single_layers=1, attention_head_dim=128, num_attention_heads=1,
                joint_attention_dim=64, pooled_projection_dim=32, guidance_embeds=True, axes_dims_rope=(16, 56, 56))
 SMALL_CN = dict(SMALL_T, num_single_layers=0, extra_condition_channels=64)
@@ -77,7 +79,7 @@ def test_call_signature_and_keywords():
     assert pipe.controlnet_union is None and "controlnet_union" not in pipe.components
     with pytest.raises(ValueError, match="control_image_union"):       # accepted as keywords, refused for the missing tower
         pipe(**call_kwargs(controlnet_conditioning_scale_union=0.7, control_guidance_start_union=0.0, control_guidance_end_union=0.8))
-    assert pipe._union_call_args is None and pipe._union is None      # call state is cleared
+    assert_no_call_state(pipe)
     inp = make_pipe(cls=Inpaint, controlnet_inpaint=None)
     base_kw = call_kwargs()
     del base_kw["control_image_union"]

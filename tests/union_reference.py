@@ -1,7 +1,7 @@
 """Reference of the denoising loop with a second, unmasked ControlNet (the union tower) beside the text-line towers, assembled from
 the oracle's model forwards. Not a test module: test_union_tower_gpu.py imports it.
 
-Order of the sum within a step (the contract of pipeline._denoise_eager): the union tower first, when the step is inside its guidance
+Order of the sum within a step (the contract of pipeline._denoise_eager with ``extras.union``, a pipeline.UnionTower): the union tower first, when the step is inside its guidance
 interval, then the text lines while ``i < conditioning_step``; the first tower evaluated sets the samples, every later one is added
 and the sum is rounded to the storage dtype per added tower (``_s(a + b)``), the regional mask applied before the sum — where
 ``oracle.flux_oracle.denoise_loop`` rounds."""
