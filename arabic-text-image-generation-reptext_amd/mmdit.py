@@ -54,121 +54,95 @@ def bf16_round_trip_x1000(v: torch.Tensor) -> torch.Tensor:
 
 
 @dataclass
+class Proj:
+    """One projection of a block: views of its bf16 weight and bias and, where the plan's level quantises it, the e4m3 copy of the
+    weight with its per-output-channel scales (None otherwise)."""
+    w: torch.Tensor
+    b: torch.Tensor
+    w8: Optional[torch.Tensor] = None
+    ws: Optional[torch.Tensor] = None
+
+
+@dataclass
 class DoublePlan:
-    ada_img_w: torch.Tensor
-    ada_img_b: torch.Tensor
-    ada_txt_w: torch.Tensor
-    ada_txt_b: torch.Tensor
-    qkv_img_w: torch.Tensor
-    qkv_img_b: torch.Tensor
-    qkv_txt_w: torch.Tensor
-    qkv_txt_b: torch.Tensor
+    ada_img: Proj
+    ada_txt: Proj
+    qkv_img: Proj
+    qkv_txt: Proj
+    out_img: Proj
+    out_txt: Proj
+    ff1_img: Proj
+    ff1_txt: Proj
+    ff2_img: Proj
+    ff2_txt: Proj
     nq_img: torch.Tensor
     nk_img: torch.Tensor
     nq_txt: torch.Tensor
     nk_txt: torch.Tensor
-    out_img_w: torch.Tensor
-    out_img_b: torch.Tensor
-    out_txt_w: torch.Tensor
-    out_txt_b: torch.Tensor
-    ff1_img_w: torch.Tensor
-    ff1_img_b: torch.Tensor
-    ff2_img_w: torch.Tensor
-    ff2_img_b: torch.Tensor
-    ff1_txt_w: torch.Tensor
-    ff1_txt_b: torch.Tensor
-    ff2_txt_w: torch.Tensor
-    ff2_txt_b: torch.Tensor
-    # e4m3 copies (+ per-output-channel scales) of the projections fed by a LayerNorm; None = bf16 path
-    qkv_img_w8: Optional[torch.Tensor] = None
-    qkv_img_ws: Optional[torch.Tensor] = None
-    qkv_txt_w8: Optional[torch.Tensor] = None
-    qkv_txt_ws: Optional[torch.Tensor] = None
-    ff1_img_w8: Optional[torch.Tensor] = None
-    ff1_img_ws: Optional[torch.Tensor] = None
-    ff1_txt_w8: Optional[torch.Tensor] = None
-    ff1_txt_ws: Optional[torch.Tensor] = None
-    # level "all": also the projections whose input is a bf16 activation (attention output, GELU hidden), quantised by a pass
-    out_img_w8: Optional[torch.Tensor] = None
-    out_img_ws: Optional[torch.Tensor] = None
-    out_txt_w8: Optional[torch.Tensor] = None
-    out_txt_ws: Optional[torch.Tensor] = None
-    ff2_img_w8: Optional[torch.Tensor] = None
-    ff2_img_ws: Optional[torch.Tensor] = None
-    ff2_txt_w8: Optional[torch.Tensor] = None
-    ff2_txt_ws: Optional[torch.Tensor] = None
+    # None = bf16; "ln": e4m3 copies of the projections fed by a LayerNorm; "all": also of those whose input is a bf16 activation
+    # (attention output, GELU hidden), quantised by a pass; "mx": those read e4m3 + E8M0 block scales written by the producing epilogue
+    level: Optional[str] = None
     fp8_attention: bool = False
-    mx: bool = False        # level "mx": those projections read e4m3 + E8M0 block scales written by the producing epilogue
 
 
 @dataclass
 class SinglePlan:
-    ada_w: torch.Tensor
-    ada_b: torch.Tensor
-    fused_w: torch.Tensor   # rows: [to_k | to_v | to_q | proj_mlp]
-    fused_b: torch.Tensor
+    ada: Proj
+    fused: Proj             # rows: [to_k | to_v | to_q | proj_mlp]
+    out: Proj
     nq: torch.Tensor
     nk: torch.Tensor
-    out_w: torch.Tensor
-    out_b: torch.Tensor
-    fused_w8: Optional[torch.Tensor] = None
-    fused_ws: Optional[torch.Tensor] = None
-    out_w8: Optional[torch.Tensor] = None
-    out_ws: Optional[torch.Tensor] = None
+    level: Optional[str] = None
     fp8_attention: bool = False
-    mx: bool = False
+
+
+def _quantised(pl) -> tuple:
+    """The projections of a plan that its level keeps an e4m3 copy of, in the order they are quantised: the LayerNorm-fed ones at
+    every level, the activation-fed ones at "all" and "mx"."""
+    if isinstance(pl, DoublePlan):
+        ln_fed, act_fed = (pl.qkv_img, pl.qkv_txt, pl.ff1_img, pl.ff1_txt), (pl.out_img, pl.out_txt, pl.ff2_img, pl.ff2_txt)
+    else:
+        ln_fed, act_fed = (pl.fused,), (pl.out,)
+    return () if pl.level is None else ln_fed + act_fed if pl.level in ("all", "mx") else ln_fed
+
+
+def _linear_of(m) -> Proj:
+    return Proj(m.weight.data, m.bias.data)
+
+
+def _set_level(pl, fp8, fp8_attention: bool, d: int):
+    """Store the level of a fresh plan (inner width d) once, and quantise the projections it names."""
+    pl.level, pl.fp8_attention = "ln" if fp8 is True else (fp8 or None), fp8_attention
+    if pl.level == "mx" and d % 256:
+        raise ValueError("the 'mx' level needs an inner width that is a multiple of 256")
+    for p in _quantised(pl):
+        p.w8, p.ws = ops.quantize_rows_fp8(p.w)
+    return pl
 
 
 def plan_double(blk, fp8=False, fp8_attention: bool = False) -> DoublePlan:
     """fp8: False | 'ln' (LayerNorm-fed projections) | 'all' (every projection of the block, per-row scales, one quantise pass per
     bf16 input) | 'mx' (every projection; the non-LayerNorm inputs as e4m3 + block scales written by their producers)."""
-    a = blk.attn
-    qi_w, qi_b = _fuse([a.to_q, a.to_k, a.to_v])
-    qt_w, qt_b = _fuse([a.add_q_proj, a.add_k_proj, a.add_v_proj])
-    pl = DoublePlan(
-        blk.norm1.linear.weight.data, blk.norm1.linear.bias.data, blk.norm1_context.linear.weight.data,
-        blk.norm1_context.linear.bias.data, qi_w, qi_b, qt_w, qt_b, a.norm_q.weight.data, a.norm_k.weight.data,
-        a.norm_added_q.weight.data, a.norm_added_k.weight.data, a.to_out[0].weight.data, a.to_out[0].bias.data,
-        a.to_add_out.weight.data, a.to_add_out.bias.data, blk.ff.net[0].proj.weight.data, blk.ff.net[0].proj.bias.data,
-        blk.ff.net[2].weight.data, blk.ff.net[2].bias.data, blk.ff_context.net[0].proj.weight.data,
-        blk.ff_context.net[0].proj.bias.data, blk.ff_context.net[2].weight.data, blk.ff_context.net[2].bias.data)
-    if fp8:
-        pl.qkv_img_w8, pl.qkv_img_ws = ops.quantize_rows_fp8(pl.qkv_img_w)
-        pl.qkv_txt_w8, pl.qkv_txt_ws = ops.quantize_rows_fp8(pl.qkv_txt_w)
-        pl.ff1_img_w8, pl.ff1_img_ws = ops.quantize_rows_fp8(pl.ff1_img_w)
-        pl.ff1_txt_w8, pl.ff1_txt_ws = ops.quantize_rows_fp8(pl.ff1_txt_w)
-    if fp8 in ("all", "mx"):
-        pl.mx = fp8 == "mx"
-        if pl.mx and pl.out_img_w.shape[1] % 256:
-            raise ValueError("the 'mx' level needs an inner width that is a multiple of 256")
-        pl.out_img_w8, pl.out_img_ws = ops.quantize_rows_fp8(pl.out_img_w)
-        pl.out_txt_w8, pl.out_txt_ws = ops.quantize_rows_fp8(pl.out_txt_w)
-        pl.ff2_img_w8, pl.ff2_img_ws = ops.quantize_rows_fp8(pl.ff2_img_w)
-        pl.ff2_txt_w8, pl.ff2_txt_ws = ops.quantize_rows_fp8(pl.ff2_txt_w)
-    pl.fp8_attention = fp8_attention
-    return pl
+    a, lin = blk.attn, _linear_of
+    pl = DoublePlan(ada_img=lin(blk.norm1.linear), ada_txt=lin(blk.norm1_context.linear),
+                    qkv_img=Proj(*_fuse([a.to_q, a.to_k, a.to_v])), qkv_txt=Proj(*_fuse([a.add_q_proj, a.add_k_proj, a.add_v_proj])),
+                    out_img=lin(a.to_out[0]), out_txt=lin(a.to_add_out), ff1_img=lin(blk.ff.net[0].proj), ff1_txt=lin(blk.ff_context.net[0].proj),
+                    ff2_img=lin(blk.ff.net[2]), ff2_txt=lin(blk.ff_context.net[2]), nq_img=a.norm_q.weight.data, nk_img=a.norm_k.weight.data,
+                    nq_txt=a.norm_added_q.weight.data, nk_txt=a.norm_added_k.weight.data)
+    return _set_level(pl, fp8, fp8_attention, pl.out_img.w.shape[1])
 
 
 def plan_single(blk, fp8=False, fp8_attention: bool = False) -> SinglePlan:
     a = blk.attn
-    fw, fb = _fuse([a.to_k, a.to_v, a.to_q, blk.proj_mlp])
-    pl = SinglePlan(blk.norm.linear.weight.data, blk.norm.linear.bias.data, fw, fb, a.norm_q.weight.data,
-                    a.norm_k.weight.data, blk.proj_out.weight.data, blk.proj_out.bias.data)
-    if fp8:
-        pl.fused_w8, pl.fused_ws = ops.quantize_rows_fp8(pl.fused_w)
-    if fp8 in ("all", "mx"):
-        pl.mx = fp8 == "mx"
-        if pl.mx and pl.out_w.shape[0] % 256:
-            raise ValueError("the 'mx' level needs an inner width that is a multiple of 256")
-        pl.out_w8, pl.out_ws = ops.quantize_rows_fp8(pl.out_w)
-    pl.fp8_attention = fp8_attention
-    return pl
+    pl = SinglePlan(_linear_of(blk.norm.linear), Proj(*_fuse([a.to_k, a.to_v, a.to_q, blk.proj_mlp])), _linear_of(blk.proj_out),
+                    a.norm_q.weight.data, a.norm_k.weight.data)
+    return _set_level(pl, fp8, fp8_attention, pl.out.w.shape[0])
 
 
 def fp8_copies(pl) -> list:
     """(bf16 weight, e4m3 copy, per-row scales) of every projection of a plan that has an e4m3 copy (enable_fp8_linears)."""
-    names = ("qkv_img", "qkv_txt", "ff1_img", "ff1_txt", "out_img", "out_txt", "ff2_img", "ff2_txt") if isinstance(pl, DoublePlan) else ("fused", "out")
-    return [(getattr(pl, n + "_w"), getattr(pl, n + "_w8"), getattr(pl, n + "_ws")) for n in names if getattr(pl, n + "_w8") is not None]
+    return [(p.w, p.w8, p.ws) for p in _quantised(pl)]
+
 
 class Workspace:
     """Preallocated activations for one (B,T,N) shape; reused across blocks, steps and models on the same device."""
@@ -330,12 +304,12 @@ class ModulationTable:
                 ops.linear_grouped([P(lo, w, o, res=o) for w, b, o in problems])
 
         for pl in doubles:
-            oi, ot = out_buf(pl.ada_img_w), out_buf(pl.ada_txt_w)
-            table([(pl.ada_img_w, pl.ada_img_b, oi), (pl.ada_txt_w, pl.ada_txt_b, ot)])
+            oi, ot = out_buf(pl.ada_img.w), out_buf(pl.ada_txt.w)
+            table([(pl.ada_img.w, pl.ada_img.b, oi), (pl.ada_txt.w, pl.ada_txt.b, ot)])
             self.double.append((oi, ot))
         for pl in singles:
-            o = out_buf(pl.ada_w)
-            table([(pl.ada_w, pl.ada_b, o)])
+            o = out_buf(pl.ada.w)
+            table([(pl.ada.w, pl.ada.b, o)])
             self.single.append(o)
         if out_lin is not None:
             o = out_buf(out_lin.weight.data)
@@ -344,11 +318,95 @@ class ModulationTable:
 
     @staticmethod
     def _widths(doubles, singles, out_lin):
-        return [w for pl in doubles for w in (pl.ada_img_w, pl.ada_txt_w)] + [pl.ada_w for pl in singles] + ([out_lin.weight.data] if out_lin is not None else [])
+        return [w for pl in doubles for w in (pl.ada_img.w, pl.ada_txt.w)] + [pl.ada.w for pl in singles] + ([out_lin.weight.data] if out_lin is not None else [])
 
     def step(self, i: int) -> StepMods:
         r = slice(i * self.B, (i + 1) * self.B)
         return StepMods([(a[r], b[r]) for a, b in self.double], [s[r] for s in self.single], None if self.out is None else self.out[r])
+
+
+def _ch(m: torch.Tensor, i: int, d: int) -> torch.Tensor:
+    """Chunk i of a stream's adaLN vectors. Double block: shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp; single
+    block: shift, scale, gate."""
+    return m[:, i * d : (i + 1) * d]
+
+
+def _row_scales(ws: Workspace, r: slice) -> torch.Tensor:
+    """fp32 per-row scales of the e4m3 rows r of every image: one contiguous [B·rows] buffer for each stream (all rows, text, image)."""
+    ws.fp8_buffers()
+    return ws.xs_all if (r.start, r.stop) == (0, ws.S) else ws.xs_t if r.stop == ws.T else ws.xs_i
+
+
+def _ln_linear(ws: Workspace, level: Optional[str], c: int, out: torch.Tensor, streams, ropes=None, mx_out=None) -> bool:
+    """The projections fed by a LayerNorm. For one or two row streams of ws.x — ``streams`` = (rows, adaLN vectors, Proj, epilogue
+    arguments) each, the image stream first — LayerNorm + modulation with chunks c (shift) and c + 1 (scale), then the ONE grouped GEMM
+    that reads the result into the same rows of ``out``.
+      bf16          one LayerNorm launch (the pair kernel for two streams) into ws.xn, the bf16 weights; ``ropes`` (a QKRope per stream)
+                    ride this GEMM's epilogue, which no e4m3 GEMM has: returns whether they were applied
+      e4m3 levels   one quantising LayerNorm per stream into e4m3 rows + per-row scales, the e4m3 weights
+      "mx"          also, with ``mx_out`` = (width, col0, first): columns first.. of the result (the GELU hidden) leave the epilogue as
+                    e4m3 + block scales, columns col0.. of the width-wide operand of the projection that reads them (out does not get them)"""
+    d = ws.d
+    if level is None:
+        ln = [(ws.x[:, r], ws.xn[:, r], _ch(m, c, d), _ch(m, c + 1, d)) for r, m, _, _ in streams]
+        if len(ln) == 2:
+            ops.layernorm_modulate_pair(*ln[0], *ln[1])
+        else:
+            ops.layernorm_modulate(*ln[0])
+        ops.linear_grouped([P(ws.xn[:, r], p.w, out[:, r], bias=p.b, rope=ropes[i] if ropes else None, **kw)
+                            for i, (r, _, p, kw) in enumerate(streams)])
+        return ropes is not None
+    xn8, problems = ws.fp8_buffers(), []
+    for r, m, p, kw in streams:
+        xs = _row_scales(ws, r)
+        ops.layernorm_modulate_fp8(ws.x[:, r], xn8[:, r], xs, _ch(m, c, d), _ch(m, c + 1, d))
+        if level == "mx" and mx_out is not None:
+            width, col0, first = mx_out
+            kw = dict(kw, out8=ws.fp8_wide(width)[:, r, col0:], out8_scales=ws.mx_scales().rows(r.start).cols(col0), out8_from=first)
+        problems.append(P(xn8[:, r], p.w8, out[:, r], bias=p.b, a_scale=xs, w_scale=p.ws, **kw))
+    ops.linear_grouped(problems)
+    return False
+
+
+def _act_linear(ws: Workspace, level: Optional[str], src: torch.Tensor, out: torch.Tensor, streams, fresh: int) -> None:
+    """The projections of a bf16 activation ``src`` [B,S,K] (attention output, GELU hidden): ONE grouped GEMM from the rows of src into
+    the same rows of ``out``; ``streams`` = (rows, Proj, epilogue arguments) each, the image stream first.
+      bf16, "ln"    the bf16 weights on src itself
+      "all"         one per-row quantise pass per stream into the e4m3 staging buffer, then the e4m3 weights
+      "mx"          the staging buffer with its block scales; the producer's epilogue has written it, except the first ``fresh``
+                    columns, which exist in src only and take one block-quantise pass (all rows)"""
+    if level not in ("all", "mx"):
+        ops.linear_grouped([P(src[:, r], p.w, out[:, r], bias=p.b, **kw) for r, p, kw in streams])
+        return
+    a8, problems = ws.fp8_wide(src.shape[2]), []
+    if level == "mx" and fresh:
+        ops.quantize_mx_fp8_into(src[..., :fresh], a8[..., :fresh], ws.mx_scales())
+    for r, p, kw in streams:
+        if level == "mx":
+            scale = dict(a_bscale=ws.mx_scales().rows(r.start))
+        else:
+            scale = dict(a_scale=_row_scales(ws, r))
+            ops.quantize_rows_fp8_into(src[:, r], a8[:, r], scale["a_scale"])
+        problems.append(P(a8[:, r], p.w8, out[:, r], bias=p.b, w_scale=p.ws, **scale, **kw))
+    ops.linear_grouped(problems)
+
+
+def _double_front(pl: DoublePlan, ws: Workspace, temb, cos, sin, mods: Optional[tuple], rope: bool) -> tuple:
+    """Steps 1-3 of a double block, shared by run_double and its windowed mode: (image, text adaLN vectors, whether the QKV GEMM applied
+    q/k RMSNorm + RoPE). The unfused norm + RoPE pass is the caller's: the IP-Adapter launches need the raw query first."""
+    T, d = ws.T, ws.d
+    # 1. adaLN-Zero vectors
+    if mods is not None:
+        mi, mt = mods
+    else:
+        mi, mt = ws.mod_a, ws.mod_b
+        ops.gemv(temb, pl.ada_img.w, pl.ada_img.b, mi, silu_in=True)
+        ops.gemv(temb, pl.ada_txt.w, pl.ada_txt.b, mt, silu_in=True)
+    # 2. norm + modulate, 3. q,k,v projections of both streams, one launch
+    ropes = (ops.QKRope(0, d, d, pl.nq_img, pl.nk_img, cos, sin, pos0=T), ops.QKRope(0, d, d, pl.nq_txt, pl.nk_txt, cos, sin, pos0=0))
+    fused = _ln_linear(ws, pl.level, 0, ws.qkv, [(slice(T, ws.S), mi, pl.qkv_img, {}), (slice(0, T), mt, pl.qkv_txt, {})],
+                       ropes=ropes if rope and FUSED_QK_ROPE and ops.QKRope.covers(d) else None)
+    return mi, mt, fused
 
 
 def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: int, inject: Optional[torch.Tensor] = None,
@@ -369,39 +427,15 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
     ws.x are left as they were before the block. bf16 projections and attention without ``ip`` / ``inject`` only."""
     T, d = ws.T, ws.d
     if window is not None:
-        if ip is not None or inject is not None or pl.qkv_img_w8 is not None or pl.fp8_attention or pl.mx:
+        if ip is not None or inject is not None or pl.level is not None or pl.fp8_attention:
             raise ValueError("run_double: the windowed mode is the bf16 path without ip / inject")
         return _run_double_window(pl, ws, temb, cos, sin, H, mods, int(window[0]), int(window[1]))
-    x_t, x_i = ws.x[:, :T], ws.x[:, T:]
-    xn_t, xn_i = ws.xn[:, :T], ws.xn[:, T:]
-    # 1. adaLN-Zero vectors: chunk order shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp
-    if mods is not None:
-        mi, mt = mods
-    else:
-        mi, mt = ws.mod_a, ws.mod_b
-        ops.gemv(temb, pl.ada_img_w, pl.ada_img_b, mi, silu_in=True)
-        ops.gemv(temb, pl.ada_txt_w, pl.ada_txt_b, mt, silu_in=True)
-    ch = lambda m, i: m[:, i * d : (i + 1) * d]
-    fp8 = pl.qkv_img_w8 is not None
-    fused_rope = False
-    if fp8:
-        xn8 = ws.fp8_buffers()
-        xn8_t, xn8_i = xn8[:, :T], xn8[:, T:]
-    # 2. norm + modulate, 3. q,k,v projections of both streams, one launch
-    if fp8:
-        ops.layernorm_modulate_fp8(x_i, xn8_i, ws.xs_i, ch(mi, 0), ch(mi, 1))
-        ops.layernorm_modulate_fp8(x_t, xn8_t, ws.xs_t, ch(mt, 0), ch(mt, 1))
-        ops.linear_grouped([P(xn8_i, pl.qkv_img_w8, ws.qkv[:, T:], bias=pl.qkv_img_b, a_scale=ws.xs_i, w_scale=pl.qkv_img_ws),
-                            P(xn8_t, pl.qkv_txt_w8, ws.qkv[:, :T], bias=pl.qkv_txt_b, a_scale=ws.xs_t, w_scale=pl.qkv_txt_ws)])
-    else:
-        ops.layernorm_modulate_pair(x_i, xn_i, ch(mi, 0), ch(mi, 1), x_t, xn_t, ch(mt, 0), ch(mt, 1))
-        fused_rope = FUSED_QK_ROPE and ip is None and not pl.fp8_attention and ops.QKRope.covers(d)
-        ri = ops.QKRope(0, d, d, pl.nq_img, pl.nk_img, cos, sin, pos0=T) if fused_rope else None
-        rt = ops.QKRope(0, d, d, pl.nq_txt, pl.nk_txt, cos, sin, pos0=0) if fused_rope else None
-        ops.linear_grouped([P(xn_i, pl.qkv_img_w, ws.qkv[:, T:], bias=pl.qkv_img_b, rope=ri), P(xn_t, pl.qkv_txt_w, ws.qkv[:, :T], bias=pl.qkv_txt_b, rope=rt)])
+    txt, img = slice(0, T), slice(T, ws.S)
+    x_t, x_i = ws.x[:, txt], ws.x[:, img]
+    mi, mt, fused_rope = _double_front(pl, ws, temb, cos, sin, mods, rope=ip is None and not pl.fp8_attention)
     q, k, v = ws.qkv[..., :d], ws.qkv[..., d : 2 * d], ws.qkv[..., 2 * d :]
     if ip is not None and ip_inside:
-        ops.ip_attention_gated(q[:, T:], pl.nq_img, ip[0], ip[1], x_i, H, ip_scale=ip[2], gate=ch(mi, 2), accumulate=True)
+        ops.ip_attention_gated(q[:, T:], pl.nq_img, ip[0], ip[1], x_i, H, ip_scale=ip[2], gate=_ch(mi, 2, d), accumulate=True)
         ip = None
     if ip is not None:
         # the raw image query is only here: qk_rmsnorm_rope works in place and the attention output overwrites q
@@ -409,12 +443,13 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         ops.ip_attention(q[:, T:], pl.nq_img, ip[0], ip[1], ip_out, H, ip_scale=ip[2])
         if inject is None:
             inject, ip = ip_out, None                # no ControlNet sample: the term rides the add2 slot of the ff2 epilogue
+    attn_mx = pl.fp8_attention and pl.level == "mx"           # the attention kernel is the producer of the out-projections' operand
     if pl.fp8_attention:
         # 4.-6. RMSNorm(q,k) + RoPE -> e4m3 q|k and permuted Vᵀ, e4m3 joint attention; output over q ("mx": straight into the
         # out-projections' e4m3 operand with its block scales)
         qk8, vt8 = ws.fp8_attn_buffers(H)
         ops.attention_fp8_prep(ws.qkv, 0, d, 2 * d, H, T, pl.nq_txt, pl.nk_txt, pl.nq_img, pl.nk_img, cos, sin, qk8, vt8)
-        if pl.mx:
+        if attn_mx:
             ops.attention_fp8_mx(qk8, vt8, ws.fp8_wide(d), ws.mx_scales(), H)
         else:
             ops.attention_fp8(qk8, vt8, q, H)
@@ -424,82 +459,35 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
             ops.qk_rmsnorm_rope(ws.qkv, 0, d, H, T, pl.nq_txt, pl.nk_txt, pl.nq_img, pl.nk_img, cos, sin)
         ops.attention(q, k, v, q, H)
     # 7./8. x += gate_msa * out_proj(attn)
-    if pl.mx:
-        a8, sc = ws.fp8_wide(d), ws.mx_scales()
-        if not pl.fp8_attention:
-            ops.quantize_mx_fp8_into(q, a8, sc)
-        ops.linear_grouped([P(a8[:, T:], pl.out_img_w8, x_i, bias=pl.out_img_b, gate=ch(mi, 2), res=x_i, a_bscale=sc.rows(T), w_scale=pl.out_img_ws),
-                            P(a8[:, :T], pl.out_txt_w8, x_t, bias=pl.out_txt_b, gate=ch(mt, 2), res=x_t, a_bscale=sc.rows(0), w_scale=pl.out_txt_ws)])
-    elif pl.out_img_w8 is not None:
-        a8 = ws.fp8_wide(d)
-        ops.quantize_rows_fp8_into(q[:, T:], a8[:, T:], ws.xs_i)
-        ops.quantize_rows_fp8_into(q[:, :T], a8[:, :T], ws.xs_t)
-        ops.linear_grouped([P(a8[:, T:], pl.out_img_w8, x_i, bias=pl.out_img_b, gate=ch(mi, 2), res=x_i, a_scale=ws.xs_i, w_scale=pl.out_img_ws),
-                            P(a8[:, :T], pl.out_txt_w8, x_t, bias=pl.out_txt_b, gate=ch(mt, 2), res=x_t, a_scale=ws.xs_t, w_scale=pl.out_txt_ws)])
-    else:
-        ops.linear_grouped([P(q[:, T:], pl.out_img_w, x_i, bias=pl.out_img_b, gate=ch(mi, 2), res=x_i),
-                            P(q[:, :T], pl.out_txt_w, x_t, bias=pl.out_txt_b, gate=ch(mt, 2), res=x_t)])
-    if fp8:
-        ops.layernorm_modulate_fp8(x_i, xn8_i, ws.xs_i, ch(mi, 3), ch(mi, 4))
-        ops.layernorm_modulate_fp8(x_t, xn8_t, ws.xs_t, ch(mt, 3), ch(mt, 4))
-        # "mx": the GELU hidden leaves the epilogue as e4m3 + block scales (ffh is not written)
-        h8, hs = (ws.fp8_wide(4 * d), ws.mx_scales()) if pl.mx else (None, None)
-        o8 = lambda r0, r1: dict(out8=h8[:, r0:r1], out8_scales=hs.rows(r0), out8_from=0) if pl.mx else {}
-        ops.linear_grouped([P(xn8_i, pl.ff1_img_w8, ws.ffh[:, T:], bias=pl.ff1_img_b, gelu_from=0, a_scale=ws.xs_i, w_scale=pl.ff1_img_ws, **o8(T, ws.S)),
-                            P(xn8_t, pl.ff1_txt_w8, ws.ffh[:, :T], bias=pl.ff1_txt_b, gelu_from=0, a_scale=ws.xs_t, w_scale=pl.ff1_txt_ws, **o8(0, T))])
-    else:
-        ops.layernorm_modulate_pair(x_i, xn_i, ch(mi, 3), ch(mi, 4), x_t, xn_t, ch(mt, 3), ch(mt, 4))
-        ops.linear_grouped([P(xn_i, pl.ff1_img_w, ws.ffh[:, T:], bias=pl.ff1_img_b, gelu_from=0),
-                            P(xn_t, pl.ff1_txt_w, ws.ffh[:, :T], bias=pl.ff1_txt_b, gelu_from=0)])
-    if pl.mx:
-        ops.linear_grouped([P(h8[:, T:], pl.ff2_img_w8, x_i, bias=pl.ff2_img_b, gate=ch(mi, 5), res=x_i, add2=inject, a_bscale=hs.rows(T), w_scale=pl.ff2_img_ws),
-                            P(h8[:, :T], pl.ff2_txt_w8, x_t, bias=pl.ff2_txt_b, gate=ch(mt, 5), res=x_t, a_bscale=hs.rows(0), w_scale=pl.ff2_txt_ws)])
-    elif pl.ff2_img_w8 is not None:
-        a8 = ws.fp8_wide(4 * d)
-        ops.quantize_rows_fp8_into(ws.ffh[:, T:], a8[:, T:], ws.xs_i)
-        ops.quantize_rows_fp8_into(ws.ffh[:, :T], a8[:, :T], ws.xs_t)
-        ops.linear_grouped([P(a8[:, T:], pl.ff2_img_w8, x_i, bias=pl.ff2_img_b, gate=ch(mi, 5), res=x_i, add2=inject, a_scale=ws.xs_i, w_scale=pl.ff2_img_ws),
-                            P(a8[:, :T], pl.ff2_txt_w8, x_t, bias=pl.ff2_txt_b, gate=ch(mt, 5), res=x_t, a_scale=ws.xs_t, w_scale=pl.ff2_txt_ws)])
-    else:
-        ops.linear_grouped([P(ws.ffh[:, T:], pl.ff2_img_w, x_i, bias=pl.ff2_img_b, gate=ch(mi, 5), res=x_i, add2=inject),
-                            P(ws.ffh[:, :T], pl.ff2_txt_w, x_t, bias=pl.ff2_txt_b, gate=ch(mt, 5), res=x_t)])
+    _act_linear(ws, pl.level, q, ws.x, [(img, pl.out_img, dict(gate=_ch(mi, 2, d), res=x_i)),
+                                        (txt, pl.out_txt, dict(gate=_ch(mt, 2, d), res=x_t))], fresh=0 if attn_mx else d)
+    # "mx": the GELU hidden leaves the epilogue as e4m3 + block scales (ffh is not written)
+    _ln_linear(ws, pl.level, 3, ws.ffh, [(img, mi, pl.ff1_img, dict(gelu_from=0)), (txt, mt, pl.ff1_txt, dict(gelu_from=0))], mx_out=(4 * d, 0, 0))
+    _act_linear(ws, pl.level, ws.ffh, ws.x, [(img, pl.ff2_img, dict(gate=_ch(mi, 5, d), res=x_i, add2=inject)),
+                                             (txt, pl.ff2_txt, dict(gate=_ch(mt, 5, d), res=x_t))], fresh=0)
     if ip is not None:                               # the add2 slot holds the ControlNet sample: one accumulate pass per image
         for b in range(ws.B):
             ops.masked_accumulate_(ws.x[b, T:].unsqueeze(0), ip_out[b : b + 1], None, 1.0, True)
 
 
 def _run_double_window(pl: DoublePlan, ws: Workspace, temb, cos, sin, H: int, mods: Optional[tuple], r0: int, r1: int) -> None:
-    """run_double's windowed mode (see there). Steps 1-5 are run_double's own launches: every row's k and v are needed. The q columns are
+    """run_double's windowed mode (see there). The front is run_double's own: every row's k and v are needed. The q columns are
     still projected for all rows and both streams: the fused q/k epilogue of the QKV GEMM describes a group that holds both q and k, and
     restricting q to the window (one tile round of three at the headline shape) is not built."""
     T, d = ws.T, ws.d
     if not (0 <= r0 < r1 <= ws.N):
         raise ValueError(f"window [{r0}, {r1}) is not inside the {ws.N} image rows")
-    x_t, x_i = ws.x[:, :T], ws.x[:, T:]
-    xn_t, xn_i = ws.xn[:, :T], ws.xn[:, T:]
-    if mods is not None:
-        mi, mt = mods
-    else:
-        mi, mt = ws.mod_a, ws.mod_b
-        ops.gemv(temb, pl.ada_img_w, pl.ada_img_b, mi, silu_in=True)
-        ops.gemv(temb, pl.ada_txt_w, pl.ada_txt_b, mt, silu_in=True)
-    ch = lambda m, i: m[:, i * d : (i + 1) * d]
-    ops.layernorm_modulate_pair(x_i, xn_i, ch(mi, 0), ch(mi, 1), x_t, xn_t, ch(mt, 0), ch(mt, 1))
-    fused_rope = FUSED_QK_ROPE and ops.QKRope.covers(d)
-    ri = ops.QKRope(0, d, d, pl.nq_img, pl.nk_img, cos, sin, pos0=T) if fused_rope else None
-    rt = ops.QKRope(0, d, d, pl.nq_txt, pl.nk_txt, cos, sin, pos0=0) if fused_rope else None
-    ops.linear_grouped([P(xn_i, pl.qkv_img_w, ws.qkv[:, T:], bias=pl.qkv_img_b, rope=ri), P(xn_t, pl.qkv_txt_w, ws.qkv[:, :T], bias=pl.qkv_txt_b, rope=rt)])
+    mi, _, fused_rope = _double_front(pl, ws, temb, cos, sin, mods, rope=True)
     if not fused_rope:
         ops.qk_rmsnorm_rope(ws.qkv, 0, d, H, T, pl.nq_txt, pl.nk_txt, pl.nq_img, pl.nk_img, cos, sin)
     q, k, v = ws.qkv[..., :d], ws.qkv[..., d : 2 * d], ws.qkv[..., 2 * d :]
     # the full launch's own cut, with only the items that hold a window row at work: the window's rows keep the bits of the full path
     ops.attention(q, k, v, q, H, rows=(T + r0, T + r1))
-    qw = q[:, T + r0 : T + r1]                                # the window's attention output, over its queries
-    xw, xnw, hw = x_i[:, r0:r1], xn_i[:, r0:r1], ws.ffh[:, T + r0 : T + r1]
-    ops.linear(qw, pl.out_img_w, xw, bias=pl.out_img_b, gate=ch(mi, 2), res=xw)
-    ops.layernorm_modulate(xw, xnw, ch(mi, 3), ch(mi, 4))
-    ops.linear(xnw, pl.ff1_img_w, hw, bias=pl.ff1_img_b, gelu_from=0)
-    ops.linear(hw, pl.ff2_img_w, xw, bias=pl.ff2_img_b, gate=ch(mi, 5), res=xw)
+    win = slice(T + r0, T + r1)                               # the window's attention output lies over its queries
+    xw = ws.x[:, win]
+    _act_linear(ws, pl.level, q, ws.x, [(win, pl.out_img, dict(gate=_ch(mi, 2, d), res=xw))], fresh=d)
+    _ln_linear(ws, pl.level, 3, ws.ffh, [(win, mi, pl.ff1_img, dict(gelu_from=0))])
+    _act_linear(ws, pl.level, ws.ffh, ws.x, [(win, pl.ff2_img, dict(gate=_ch(mi, 5, d), res=xw))], fresh=0)
 
 
 def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: int, inject: Optional[torch.Tensor] = None,
@@ -515,28 +503,21 @@ def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         m = mods
     else:
         m = ws.mod_a[:, : 3 * d]
-        ops.gemv(temb, pl.ada_w, pl.ada_b, m, silu_in=True)                   # shift, scale, gate
-    big = ws.big
-    fused_rope = False
-    if pl.fused_w8 is not None:
-        xn8 = ws.fp8_buffers()
-        ops.layernorm_modulate_fp8(ws.x, xn8, ws.xs_all, m[:, :d], m[:, d : 2 * d])
-        # "mx": the gelu(mlp) columns leave the epilogue as columns d.. of proj_out's e4m3 operand [attn|mlp], with their block scales
-        o8 = dict(out8=ws.fp8_wide(5 * d)[..., d:], out8_scales=ws.mx_scales().cols(d), out8_from=3 * d) if pl.mx else {}
-        ops.linear(xn8, pl.fused_w8, big, bias=pl.fused_b, gelu_from=3 * d, a_scale=ws.xs_all, w_scale=pl.fused_ws, **o8)
-    else:
-        ops.layernorm_modulate(ws.x, ws.xn, m[:, :d], m[:, d : 2 * d])
-        fused_rope = FUSED_QK_ROPE and ip is None and not pl.fp8_attention and ops.QKRope.covers(d)
-        ops.linear(ws.xn, pl.fused_w, big, bias=pl.fused_b, gelu_from=3 * d,    # [k|v|q|gelu(mlp)]
-                   rope=ops.QKRope(2 * d, 0, d, pl.nq, pl.nk, cos, sin) if fused_rope else None)
+        ops.gemv(temb, pl.ada.w, pl.ada.b, m, silu_in=True)                   # shift, scale, gate
+    big, rows = ws.big, slice(0, ws.S)
+    # [k|v|q|gelu(mlp)]. "mx": the gelu(mlp) columns leave the epilogue as columns d.. of proj_out's e4m3 operand [attn|mlp], with their block scales
+    rope = FUSED_QK_ROPE and ip is None and not pl.fp8_attention and ops.QKRope.covers(d)
+    fused_rope = _ln_linear(ws, pl.level, 0, big, [(rows, m, pl.fused, dict(gelu_from=3 * d))], mx_out=(5 * d, d, 3 * d),
+                            ropes=(ops.QKRope(2 * d, 0, d, pl.nq, pl.nk, cos, sin),) if rope else None)
     q = big[..., 2 * d : 3 * d]
     if ip is not None:
         ip_out = ws.ip_buffer_joint()
         ops.ip_attention_gated(q, pl.nq, ip[0], ip[1], ip_out, H, ip_scale=ip[2])
+    attn_mx = pl.fp8_attention and pl.level == "mx" and ip is None
     if pl.fp8_attention:
         qk8, vt8 = ws.fp8_attn_buffers(H)
         ops.attention_fp8_prep(big, 2 * d, 0, d, H, 0, None, None, pl.nq, pl.nk, cos, sin, qk8, vt8)
-        if pl.mx and ip is None:
+        if attn_mx:
             ops.attention_fp8_mx(qk8, vt8, ws.fp8_wide(5 * d)[..., :d], ws.mx_scales(), H)
         else:
             ops.attention_fp8(qk8, vt8, q, H)
@@ -546,17 +527,7 @@ def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         ops.attention(q, big[..., :d], big[..., d : 2 * d], q, H)
     if ip is not None:
         ops.add_bf16_(q, ip_out)
-    if pl.mx:
-        a8, sc = ws.fp8_wide(5 * d), ws.mx_scales()
-        if not pl.fp8_attention or ip is not None:
-            ops.quantize_mx_fp8_into(q, a8[..., :d], sc)
-        ops.linear(a8, pl.out_w8, ws.x, bias=pl.out_b, gate=m[:, 2 * d : 3 * d], res=ws.x, a_bscale=sc, w_scale=pl.out_ws)
-    elif pl.out_w8 is not None:
-        a8 = ws.fp8_wide(5 * d)
-        ops.quantize_rows_fp8_into(big[..., 2 * d :], a8, ws.xs_all)
-        ops.linear(a8, pl.out_w8, ws.x, bias=pl.out_b, gate=m[:, 2 * d : 3 * d], res=ws.x, a_scale=ws.xs_all, w_scale=pl.out_ws)
-    else:
-        ops.linear(big[..., 2 * d :], pl.out_w, ws.x, bias=pl.out_b, gate=m[:, 2 * d : 3 * d], res=ws.x)
+    _act_linear(ws, pl.level, big[..., 2 * d :], ws.x, [(rows, pl.out, dict(gate=_ch(m, 2, d), res=ws.x))], fresh=0 if attn_mx else d)
     if inject is not None:                                                       # A.3: image tokens only
         for b in range(ws.B):   # image rows of one batch entry are contiguous; one call per image
             ops.masked_accumulate_(ws.x[b, T:].unsqueeze(0), inject[b : b + 1].contiguous(), None, 1.0, True)

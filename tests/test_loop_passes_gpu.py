@@ -107,7 +107,7 @@ def _table_the_old_way(ops, mmdit, tr, timesteps, guidance, pooled):
         temb_all[i * B : (i + 1) * B].copy_(tr._temb(sc, ts, guidance, pooled))
     hi, lo = ops.silu_split(temb_all, apply_silu=True)
     tabs = []
-    ws = [w for pl in doubles for w in ((pl.ada_img_w, pl.ada_img_b), (pl.ada_txt_w, pl.ada_txt_b))] + [(pl.ada_w, pl.ada_b) for pl in singles]
+    ws = [(p.w, p.b) for pl in doubles for p in (pl.ada_img, pl.ada_txt)] + [(pl.ada.w, pl.ada.b) for pl in singles]
     ws.append((tr.norm_out.linear.weight.data, tr.norm_out.linear.bias.data))
     for w, b in ws:
         o = torch.empty(temb_all.shape[0], w.shape[0], device=dev, dtype=F32)
