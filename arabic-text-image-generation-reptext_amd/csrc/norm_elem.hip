@@ -423,6 +423,58 @@ __global__ void cfg_euler_step_f32_kernel(float* __restrict__ x, const bf16_t* _
   }
 }
 
+// Latent-blend repaint fused into the fp32 master step. One element: the step's result r (the two kernels above, their expressions), the
+// source re-noised to the next sigma, and the blend of the two under the mask. keep and the blend are computed with contraction off,
+// every product and sum rounded once: keep is then what torch's (1 − σ)·src + σ·noise gives bit for bit (scheduler.scale_noise), and
+// with m = 1 the blend is 0·keep + r = r, with m = 0 it is keep + 0·r = keep, with σ = 0 keep is src + 0·noise = src, for finite inputs.
+__device__ __forceinline__ float repaint_blend(float r, float src, float noise, float m, float sn) {
+#pragma clang fp contract(off)
+  const float keep = (1.0f - sn) * src + sn * noise;
+  return (1.0f - m) * keep + m * r;
+}
+
+// n4 groups of four elements with 16-byte loads and stores (8-byte ones for bf16), then the elements from 4·n4 on one at a time:
+// the up to three left over when the mask has x's length and that is no multiple of 4, or all of them — the host sets n4 = 0 where
+// a group could straddle the mask's period (n_mask < n and no multiple of 4) or a pointer is not aligned. m = mask[i % n_mask].
+template <bool CFG>
+__global__ void repaint_euler_step_f32_kernel(float* __restrict__ x, const bf16_t* __restrict__ u, const bf16_t* __restrict__ t,
+                                              bf16_t* __restrict__ xb, const float* __restrict__ src, const float* __restrict__ noise,
+                                              const float* __restrict__ mask, float s, float ds, float sn, int64_t n, int64_t n_mask,
+                                              int64_t n4) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t g = tid; g < n4; g += nthr) {
+    const f32x4 xv = reinterpret_cast<const f32x4*>(x)[g];
+    const f32x4 sv = reinterpret_cast<const f32x4*>(src)[g], nv = reinterpret_cast<const f32x4*>(noise)[g];
+    const f32x4 mv = *reinterpret_cast<const f32x4*>(mask + (g * 4) % n_mask);
+    const u32x2 uv = reinterpret_cast<const u32x2*>(u)[g];
+    u32x2 tv = uv;
+    if (CFG) tv = reinterpret_cast<const u32x2*>(t)[g];
+    f32x4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float a = (j & 1) ? bf16hi(uv[j >> 1]) : bf16lo(uv[j >> 1]);
+      float v = a;
+      if (CFG) {
+        const float b = (j & 1) ? bf16hi(tv[j >> 1]) : bf16lo(tv[j >> 1]);
+        v = a + s * (b - a);
+      }
+      const float r = xv[j] + ds * v;
+      o[j] = repaint_blend(r, sv[j], nv[j], mv[j], sn);
+    }
+    reinterpret_cast<f32x4*>(x)[g] = o;
+    if (xb) reinterpret_cast<u32x2*>(xb)[g] = u32x2{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
+  }
+  for (int64_t i = n4 * 4 + tid; i < n; i += nthr) {
+    const float a = bf16_to_f32(u[i]);
+    float v = a;
+    if (CFG) v = a + s * (bf16_to_f32(t[i]) - a);
+    const float r = x[i] + ds * v;
+    const float o = repaint_blend(r, src[i], noise[i], mask[i % n_mask], sn);
+    x[i] = o;
+    if (xb) xb[i] = f32_to_bf16(o);
+  }
+}
+
 __global__ void cfg_mix_kernel(const bf16_t* __restrict__ u, const bf16_t* __restrict__ t, bf16_t* __restrict__ o,
                                float s, int64_t n) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
@@ -758,6 +810,23 @@ int rt_cfg_euler_step_f32(float* x, const void* v_uncond, const void* v_text, vo
   if (!x || !v_uncond || !v_text || n < 1) return RT_E_BADARG;
   hipLaunchKernelGGL(cfg_euler_step_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x,
                      (const bf16_t*)v_uncond, (const bf16_t*)v_text, (bf16_t*)x_bf16, s, dsigma, n);
+  return rt_hip_status();
+}
+
+int rt_repaint_euler_step_f32(float* x, const void* v, const void* v_text, void* x_bf16, const float* src, const float* noise,
+                              const float* mask, float s, float dsigma, float sigma_next, int64_t n, int64_t n_mask, void* stream) {
+  if (!x || !v || !src || !noise || !mask || n < 1 || n_mask < 1) return RT_E_BADARG;
+  if (n % n_mask) return RT_E_SHAPE;
+  const bool vec = (n_mask % 4 == 0 || n_mask == n) && RT_ALIGNED(x, 16) && RT_ALIGNED(src, 16) && RT_ALIGNED(noise, 16) && RT_ALIGNED(mask, 16) &&
+                   RT_ALIGNED(v, 8) && (!v_text || RT_ALIGNED(v_text, 8)) && (!x_bf16 || RT_ALIGNED(x_bf16, 8));
+  const int64_t n4 = vec ? n / 4 : 0;
+  const dim3 grid(grid_for(n4 > 0 ? n4 : n, 256)), block(256);
+  if (v_text)
+    hipLaunchKernelGGL(repaint_euler_step_f32_kernel<true>, grid, block, 0, (hipStream_t)stream, x, (const bf16_t*)v,
+                       (const bf16_t*)v_text, (bf16_t*)x_bf16, src, noise, mask, s, dsigma, sigma_next, n, n_mask, n4);
+  else
+    hipLaunchKernelGGL(repaint_euler_step_f32_kernel<false>, grid, block, 0, (hipStream_t)stream, x, (const bf16_t*)v,
+                       (const bf16_t*)nullptr, (bf16_t*)x_bf16, src, noise, mask, s, dsigma, sigma_next, n, n_mask, n4);
   return rt_hip_status();
 }
 

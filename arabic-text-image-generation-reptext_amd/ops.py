@@ -710,6 +710,24 @@ def cfg_euler_step_f32_(x32: torch.Tensor, v_uncond: torch.Tensor, v_text: torch
     return x32
 
 
+def repaint_euler_step_f32_(x32: torch.Tensor, v: torch.Tensor, v_text: Optional[torch.Tensor], s: float, dsigma: float, sigma_next: float,
+                           src32: torch.Tensor, noise32: torch.Tensor, mask: torch.Tensor, x_bf16: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The fp32 master step (``v_text`` given: the true-CFG one, ``v`` its unconditional half) followed by the latent blend of a
+    repaint: x32 = (1 − m)·((1 − sigma_next)·src + sigma_next·noise) + m·(x32 + dsigma·vel); optionally refreshes the bf16 copy.
+    ``mask`` has x32's shape, or a leading 1 where x32 has its batch: one mask for every sample."""
+    vs = [v] if v_text is None else [v, v_text]
+    if not all(t.is_contiguous() for t in [x32, src32, noise32, mask] + vs) or not all(t.shape == x32.shape for t in [src32, noise32] + vs):
+        raise ValueError("repaint_euler_step_f32_: contiguous tensors of equal shape")
+    if x_bf16 is not None and (x_bf16.shape != x32.shape or not x_bf16.is_contiguous()):
+        raise ValueError("x_bf16 must match x32")
+    if mask.shape != x32.shape and not (x32.dim() > 1 and tuple(mask.shape) == (1,) + tuple(x32.shape[1:])):
+        raise ValueError(f"repaint_euler_step_f32_: mask {tuple(mask.shape)} is neither x32's shape {tuple(x32.shape)} nor that of one sample")
+    native.call("rt_repaint_euler_step_f32", _dev(x32, "x32", F32), _dev(v, "v", BF16), _opt(v_text, "v_text", BF16), _opt(x_bf16, "x_bf16", BF16),
+                _dev(src32, "src32", F32), _dev(noise32, "noise32", F32), _dev(mask, "mask", F32), float(s), float(dsigma), float(sigma_next),
+                x32.numel(), mask.numel(), _stream())
+    return x32
+
+
 def cfg_mix(v_uncond: torch.Tensor, v_text: torch.Tensor, s: float) -> torch.Tensor:
     u, t = v_uncond.contiguous(), v_text.contiguous()
     out = torch.empty_like(t)

@@ -200,8 +200,18 @@ class UnionTower:
 
 
 @dataclass(frozen=True)
+class Repaint:
+    """Latent-blend repaint: after every step the state becomes ``src32`` re-noised with ``noise32`` to the next sigma where ``mask`` is
+    0 and stays the step's result where it is 1 (``scheduler.step_master_repaint_``). fp32; under true CFG at the latents' batch B."""
+    src32: torch.Tensor       # [B, N, 64] packed source latents
+    noise32: torch.Tensor     # [B, N, 64] the noise the start state was mixed with
+    mask: torch.Tensor        # [1 or B, N, 64]; fractional values blend
+
+
+@dataclass(frozen=True)
 class LoopExtras:
-    """What a call adds to the plain loop of ``_denoise_eager``. ``_denoise`` takes the first three and sets ``tower_window`` itself."""
+    """What a call adds to the plain loop of ``_denoise_eager``. ``_denoise`` takes the first three and ``repaint`` (static inputs and key
+    of the captured graph) and sets ``tower_window`` itself."""
     ip_embeds: Optional[torch.Tensor] = None     # the image prompt, [total or 1, E] ([2·total, E] under true CFG); None: nothing to add
     union: Optional[UnionTower] = None           # it keeps the side stream and the text towers' row window
     # true CFG of the base flow: the conditioning batch is [negative, positive] (2B against the latents' B) and the step mixes its halves in
@@ -211,6 +221,7 @@ class LoopExtras:
     # (FluxControlNetModel, hint, conditioning scale) of unmasked towers after the text lines (the inpaint tower); the loop then stays on one stream
     extra_towers: Tuple = ()
     velocity: Optional[Callable] = None          # (i, noise_pred) -> what the scheduler steps with in its place (the inpaint flow's CFG)
+    repaint: Optional[Repaint] = None            # the step also blends the re-noised source back in (pipeline_repaint.py)
     quiet: bool = False                          # no progress bar (a capture)
 
 
@@ -883,6 +894,19 @@ class FluxControlNetPipeline:
                  callback_on_step_end_tensor_inputs: List[str] = ["latents"], max_sequence_length: int = 512,
                  control_mask: Optional[torch.FloatTensor] = None, control_position: Optional[torch.FloatTensor] = None,
                  control_glyph: Optional[torch.FloatTensor] = None):
+        return self._generate(None, prompt, prompt_2, height, width, num_inference_steps, timesteps, guidance_scale, control_guidance_start,
+                              control_guidance_end, control_image, control_mode, controlnet_conditioning_scale, controlnet_conditioning_step,
+                              num_images_per_prompt, generator, latents, prompt_embeds, pooled_prompt_embeds, output_type, return_dict,
+                              joint_attention_kwargs, callback_on_step_end, callback_on_step_end_tensor_inputs, max_sequence_length,
+                              control_mask, control_position, control_glyph)
+
+    def _generate(self, start, prompt, prompt_2, height, width, num_inference_steps, timesteps, guidance_scale, control_guidance_start,
+                  control_guidance_end, control_image, control_mode, controlnet_conditioning_scale, controlnet_conditioning_step,
+                  num_images_per_prompt, generator, latents, prompt_embeds, pooled_prompt_embeds, output_type, return_dict,
+                  joint_attention_kwargs, callback_on_step_end, callback_on_step_end_tensor_inputs, max_sequence_length, control_mask,
+                  control_position, control_glyph):
+        """The body of ``__call__``, whose arguments these are, in its order. ``start`` is whatever a subclass's ``__call__`` wants its own
+        ``_cut_schedule`` and ``_start_state`` to receive (a value of one call, so that nothing of it lives on the pipeline); None here."""
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         # control_guidance_start/end are normalised like the reference but have no effect on the result (inert: Q3)
@@ -921,11 +945,12 @@ class FluxControlNetPipeline:
         union_hint = self._doubled_under_cfg(self._union_hint(ext.control_image_union, width, height, total, num_images_per_prompt, device, dtype),
                                              total, cfg) if with_union else None
         timesteps, num_inference_steps = self._schedule(height, width, num_inference_steps, timesteps, device)
-        latents, latent_image_ids = self._initial_latents(control_glyph, total, height, width, prompt_embeds.dtype, device, generator, latents)
-        masks = [self._doubled_under_cfg(m, total, cfg, mask=True) for m in self._region_masks(control_mask, latents.device, latents.dtype)]
+        timesteps, num_inference_steps = self._cut_schedule(start, timesteps, num_inference_steps)
+        latents, latent_image_ids, repaint = self._start_state(start, control_glyph, total, height, width, prompt_embeds.dtype, device, generator, latents)
+        masks = [self._doubled_under_cfg(m, total, cfg, mask=True) for m in self._region_masks(control_mask, latents.device, prompt_embeds.dtype)]
         active = union_active_steps(len(timesteps), float(ext.control_guidance_start_union), float(ext.control_guidance_end_union)) if with_union else ()
         union = UnionTower(self.controlnet_union, union_hint, float(ext.controlnet_conditioning_scale_union), active) if active else None
-        extras = LoopExtras(ip_embeds=ip_embeds, union=union, cfg_scale=float(ext.true_cfg_scale) if cfg else None)
+        extras = LoopExtras(ip_embeds=ip_embeds, union=union, cfg_scale=float(ext.true_cfg_scale) if cfg else None, repaint=repaint)
 
         self._apply_lora_scale()
         latents = self._denoise(latents, prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids, timesteps, hints, masks,
@@ -975,6 +1000,14 @@ class FluxControlNetPipeline:
         self._num_timesteps = len(timesteps)
         return timesteps, num_inference_steps
 
+    def _cut_schedule(self, start, timesteps, num_inference_steps):
+        """The steps of the grid that the loop runs: all of them (the repaint pipeline runs the last ``strength`` of them)."""
+        return timesteps, num_inference_steps
+
+    def _start_state(self, start, control_glyph, total, height, width, dtype, device, generator, latents):
+        """(the loop's start state, image ids, the loop's ``Repaint`` record or None): the initial latents and no record."""
+        return (*self._initial_latents(control_glyph, total, height, width, dtype, device, generator, latents), None)
+
     def _initial_latents(self, control_glyph, total, height, width, dtype, device, generator, latents):
         """(packed latents, image ids): from the glyph image when one is given (``latents`` is then ignored, as in the reference)."""
         num_channels_latents = self.transformer.config.in_channels // 4
@@ -1020,13 +1053,13 @@ class FluxControlNetPipeline:
     def _denoise(self, latents, prompt_embeds, pooled, text_ids, image_ids, timesteps, hints, masks, guidance_scale,
                  cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, extras: Optional[LoopExtras] = None):
         """Eager loop, or the replay of its captured hipGraph when this exact call signature has been seen before (GRAPH_CAPTURE).
-        ``extras``: the image prompt, the union tower and the CFG scale of the call (None: a plain loop)."""
+        ``extras``: the image prompt, the union tower, the CFG scale and the repaint record of the call (None: a plain loop)."""
         tvals = timesteps.to(torch.float32).cpu().tolist()                 # host copies: no per-step device sync
         # the rows the regional masks leave non-zero: read here, never inside the loop or a capture; part of the call signature below
         win = active_row_window(masks, latents.shape[1]) if masks and len(masks) == len(hints) else None
         extras = replace(extras or LoopExtras(), tower_window=win)
         # under true CFG (cfg_scale) prompt_embeds / pooled / hints hold [negative, positive]
-        ipe, union, cfg_scale = extras.ip_embeds, extras.union, extras.cfg_scale
+        ipe, union, cfg_scale, repaint = extras.ip_embeds, extras.union, extras.cfg_scale, extras.repaint
 
         def eager(callback=None):
             return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
@@ -1061,6 +1094,10 @@ class FluxControlNetPipeline:
         if cfg_scale is not None:
             # the scale is a kernel scalar of every step (rt_cfg_euler_step_f32); the static inputs' shapes already carry the batch 2B
             key += (("cfg", cfg_scale),)
+        if repaint is not None:
+            # source, noise and mask are three more static inputs; the sigmas the blend re-noises to are in the key already
+            key += (("repaint", sig(repaint.src32), sig(repaint.noise32), sig(repaint.mask)),)
+            ins.update(repaint_src=repaint.src32, repaint_noise=repaint.noise32, repaint_mask=repaint.mask)
         cache = self.__dict__.setdefault("_graph_cache", {})
         ent = cache.get(key)
         if ent is None:                                      # first sight of this signature: eager (and warm), remember it
@@ -1089,7 +1126,8 @@ class FluxControlNetPipeline:
                 # thread-local capture mode: calls made by OTHER threads (RCCL's watchdog polling its events) do not invalidate the capture
                 with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                     captured = replace(extras, quiet=True, ip_embeds=static.get("ip_embeds"),
-                                       union=union and replace(union, hint=static["union_hint"]))
+                                       union=union and replace(union, hint=static["union_hint"]),
+                                       repaint=repaint and Repaint(static["repaint_src"], static["repaint_noise"], static["repaint_mask"]))
                     out = self._denoise_eager(static["latents"], static["prompt_embeds"], static["pooled"], static["text_ids"], static["image_ids"],
                                               tvals, static["hints"], static["masks"], guidance_scale, cn_scale, cn_steps, control_mode, None,
                                               callback_inputs, num_inference_steps, timesteps, extras=captured)
@@ -1118,7 +1156,9 @@ class FluxControlNetPipeline:
                 dst.copy_(src)
         self._zero_samples_for(ent["samples"], ent["window"])       # another call may have left rows outside this window non-zero
         ent["graph"].replay()
-        self.scheduler._step_index = (self.scheduler._step_index or 0) + len(tvals)      # what the eager loop's step() calls leave behind
+        # what the eager loop's step() calls leave behind: they start at the begin index, if one is set
+        first = self.scheduler._step_index if self.scheduler._step_index is not None else (self.scheduler._begin_index or 0)
+        self.scheduler._step_index = first + len(tvals)
         self._master_latents = ent["out32"].clone()
         with self.progress_bar(total=num_inference_steps) as bar:
             bar.update(num_inference_steps)
@@ -1277,7 +1317,11 @@ class FluxControlNetPipeline:
                     torch.cuda.current_stream().wait_stream(side)     # the tower has finished reading `latents` (its last sample is unused, Q5)
                 if extras.velocity is not None:
                     noise_pred = extras.velocity(i, noise_pred)
-                if extras.cfg_scale is not None:
+                if extras.repaint is not None:
+                    cfg, rp = extras.cfg_scale is not None, extras.repaint
+                    self.scheduler.step_master_repaint_(noise_pred[:B] if cfg else noise_pred, noise_pred[B:] if cfg else None, extras.cfg_scale,
+                                                        lat32, latents, rp.src32, rp.noise32, rp.mask)
+                elif extras.cfg_scale is not None:
                     self.scheduler.step_master_cfg_(noise_pred[:B], noise_pred[B:], extras.cfg_scale, lat32, latents)
                 else:
                     self.scheduler.step_master_(noise_pred, lat32, latents)

@@ -110,6 +110,30 @@ class FlowMatchEulerDiscreteScheduler:
                                 float(self.sigmas[i + 1] - self.sigmas[i]), sample_bf16)
         self._step_index = i + 1
 
+    def step_master_repaint_(self, v: torch.Tensor, v_text: Optional[torch.Tensor], s: Optional[float], sample32: torch.Tensor,
+                             sample_bf16: Optional[torch.Tensor], src32: torch.Tensor, noise32: torch.Tensor, mask: torch.Tensor) -> None:
+        """``step_master_`` (``v_text`` None) or ``step_master_cfg_`` (``v`` the unconditional half) followed, inside the same kernel, by
+        the latent blend of a repaint: where ``mask`` is 0 the state becomes the source re-noised to the NEXT sigma,
+        ``scale_noise(src32, sigmas[i + 1], noise32)`` — the source itself after the last step. Advances the step index like ``step_master_``."""
+        if self._step_index is None:
+            self._step_index = self._begin_index if self._begin_index is not None else 0
+        i = self._step_index
+        ops.repaint_euler_step_f32_(sample32, v.contiguous(), None if v_text is None else v_text.contiguous(), float(s or 0.0),
+                                    float(self.sigmas[i + 1] - self.sigmas[i]), float(self.sigmas[i + 1]), src32, noise32, mask, sample_bf16)
+        self._step_index = i + 1
+
+    def scale_noise(self, sample: torch.Tensor, sigma_or_timestep, noise: torch.Tensor) -> torch.Tensor:
+        """``sigma·noise + (1 − sigma)·sample``: the forward process of flow matching (diffusers' rule, recalled). A value of at most 1 is
+        the sigma itself; a larger one is a timestep of the current schedule, whose sigma is looked up (t / num_train_timesteps where it
+        is not on the schedule). Computed in ``sample``'s dtype, each product and the sum rounded once."""
+        t = float(sigma_or_timestep)
+        if t <= 1.0:
+            sigma = t
+        else:
+            idx = (self.timesteps.cpu() == t).nonzero() if self.timesteps is not None else []
+            sigma = float(self.sigmas[int(idx[0])]) if len(idx) > 0 else t / self.config.num_train_timesteps
+        return sigma * noise + (1.0 - sigma) * sample
+
     def step(self, model_output: torch.Tensor, timestep: Union[float, torch.Tensor], sample: torch.Tensor,
              return_dict: bool = True, **unused):
         if self._step_index is None:

@@ -438,6 +438,19 @@ int rt_cfg_mix(const void* v_uncond, const void* v_text, void* out, float s, int
 int rt_cfg_euler_step_f32(float* x, const void* v_uncond, const void* v_text, void* x_bf16 /* nullable */,
                           float s, float dsigma, int64_t n, void* stream);
 
+/* Latent-blend repaint fused into the fp32 master step (pipeline._denoise_eager with LoopExtras.repaint, through
+ * scheduler.step_master_repaint_). Per element i, all in fp32:
+ *   vel  = v_text ? u + s·(t − u) : v          u = v, t = v_text, bf16 widened (rt_cfg_euler_step_f32's expression; s unused without v_text)
+ *   r    = x + dsigma·vel                       (rt_euler_step_f32's expression)
+ *   keep = (1 − sigma_next)·src + sigma_next·noise
+ *   x[i] = (1 − m)·keep + m·r,  m = mask[i % n_mask];   x_bf16[i] = bf16(x[i]) when given
+ * n_mask is n or the per-sample length: one mask serves the batch. keep and the blend are computed without fused multiply-adds, so
+ * for finite inputs m = 1 is rt_euler_step_f32 / rt_cfg_euler_step_f32 bit for bit, m = 0 gives keep as torch computes it, and
+ * sigma_next = 0 gives src there. NULL x / v / src / noise / mask, n < 1 or n_mask < 1: RT_E_BADARG; n % n_mask != 0: RT_E_SHAPE. */
+int rt_repaint_euler_step_f32(float* x, const void* v, const void* v_text /* nullable */, void* x_bf16 /* nullable */,
+                              const float* src, const float* noise, const float* mask, float s, float dsigma, float sigma_next,
+                              int64_t n, int64_t n_mask, void* stream);
+
 /* _pack_latents / _unpack_latents (PIPE:550-570): [B][C][2h][2w] <-> [B][h*w][4C], channel order (c,dy,dx).
  * unpack also applies z/scaling + shift (PIPE:1137) and writes NHWC bf16 [B][H2][W2][C]. */
 int rt_pack_latents(const void* nchw, void* packed, int32_t B, int32_t C, int32_t H2, int32_t W2, void* stream);

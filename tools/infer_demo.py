@@ -15,6 +15,10 @@ encoders, which sit outside the hot path. With real checkpoints on disk use `Flu
     python tools/infer_demo.py --negative-prompt "blurry letters, extra text" --true-cfg-scale 3.5   # true CFG in the text-to-image flow:
                                               # internal batch 2, [negative, positive]; without text encoders the negative embeddings are
                                               # random tensors seeded by the text (with checkpoints: negative_prompt= goes through encode_prompt)
+    python tools/infer_demo.py --source-image photo.jpg [--strength 0.6]   # repaint: the two lines are rendered INTO the photo by latent-blend
+                                              # inpainting (FluxControlNetRepaintPipeline): the last strength·steps steps from the noised
+                                              # photo, the photo put back outside the lines' boxes after every step; no second tower, no CFG
+                                              # doubling; combines with the flags above
     python tools/infer_demo.py --inpaint      # infer_inpaint.py's flow (infer_inpaint.py:48-155): second 68-channel tower, masked
                                               # background image, position mask = bbox+-5, true CFG with negative embeddings
 """
@@ -44,6 +48,8 @@ ap.add_argument("--union-scale", type=float, default=0.7)
 ap.add_argument("--union-end", type=float, default=0.8)
 ap.add_argument("--negative-prompt", default=None, help="negative prompt of the text-to-image flow (true CFG; needs --true-cfg-scale > 1)")
 ap.add_argument("--true-cfg-scale", type=float, default=1.0)
+ap.add_argument("--source-image", default=None, help="photo to render the text into (the repaint pipeline's image=; the mask is the union of the lines' boxes)")
+ap.add_argument("--strength", type=float, default=0.6, help="share of the schedule a repaint runs")
 a = ap.parse_args()
 dev, bf16 = torch.device("cuda:0"), torch.bfloat16
 ct, cc = flux_dev_transformer_config(), reptext_controlnet_config()
@@ -51,7 +57,11 @@ if a.depth_scale != 1.0:
     ct["num_layers"] = max(1, int(ct["num_layers"] * a.depth_scale)); ct["num_single_layers"] = max(1, int(ct["num_single_layers"] * a.depth_scale))
     cc["num_layers"] = max(1, int(cc["num_layers"] * a.depth_scale))
 controlnet = FluxControlNetModel(**cc, device=dev, dtype=bf16).random_init_(seed=1)
-pipe = FluxControlNetPipeline(FlowMatchEulerDiscreteScheduler(), AutoencoderKL(**flux_vae_config(), device=dev, dtype=bf16).random_init_(seed=2),
+pipeline_class = FluxControlNetPipeline
+if a.source_image:
+    from pipeline_flux_controlnet_repaint import FluxControlNetRepaintPipeline as pipeline_class      # the same components
+
+pipe = pipeline_class(FlowMatchEulerDiscreteScheduler(), AutoencoderKL(**flux_vae_config(), device=dev, dtype=bf16).random_init_(seed=2),
                               None, None, None, None, FluxTransformer2DModel(**ct, device=dev, dtype=bf16).random_init_(seed=0), controlnet)
 pipe.set_progress_bar_config(disable=True)
 
@@ -129,6 +139,11 @@ if a.negative_prompt is not None:
                      negative_pooled_prompt_embeds=torch.randn(1, 768, generator=gn).to(dev, bf16), true_cfg_scale=a.true_cfg_scale)
 elif a.true_cfg_scale != 1.0:
     ip_kwargs.update(true_cfg_scale=a.true_cfg_scale)                               # logs one line: no negative prompt, CFG stays off
+
+if a.source_image:
+    from PIL import Image
+
+    ip_kwargs.update(image=Image.open(a.source_image).convert("RGB"), strength=a.strength)     # mask_image=None: the union of control_mask
 
 for it in range(2):
     torch.cuda.synchronize(); t0 = time.perf_counter()
