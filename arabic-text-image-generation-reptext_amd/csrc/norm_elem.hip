@@ -399,77 +399,64 @@ __global__ void euler_step_tail_kernel(bf16_t* x, const bf16_t* v, float ds, int
   if (i < n) x[i] = f32_to_bf16(bf16_to_f32(x[i]) + ds * bf16_to_f32(v[i]));
 }
 
-// fp32 master latents: x32 += ds * v (v bf16); also emits the bf16 copy the next step's x_embedder reads
-__global__ void euler_step_f32_kernel(float* __restrict__ x, const bf16_t* __restrict__ v, bf16_t* __restrict__ xb, float ds,
-                                      int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float r = x[i] + ds * bf16_to_f32(v[i]);
-    x[i] = r;
-    if (xb) xb[i] = f32_to_bf16(r);
-  }
-}
-
-// true CFG fused into the fp32 master step: v = u + s·(t − u) from the two bf16 halves of the transformer's output, kept in fp32 (the
-// mixed velocity is never rounded to bf16), then the same `x + ds * v` expression as euler_step_f32_kernel: with t == u the mix is
-// u exactly (u + s·0) and the step is that kernel's, bit for bit.
-__global__ void cfg_euler_step_f32_kernel(float* __restrict__ x, const bf16_t* __restrict__ u, const bf16_t* __restrict__ t,
-                                          bf16_t* __restrict__ xb, float s, float ds, int64_t n) {
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float a = bf16_to_f32(u[i]), b = bf16_to_f32(t[i]);
-    const float v = a + s * (b - a);
-    const float r = x[i] + ds * v;
-    x[i] = r;
-    if (xb) xb[i] = f32_to_bf16(r);
-  }
-}
-
-// Latent-blend repaint fused into the fp32 master step. One element: the step's result r (the two kernels above, their expressions), the
-// source re-noised to the next sigma, and the blend of the two under the mask. keep and the blend are computed with contraction off,
-// every product and sum rounded once: keep is then what torch's (1 − σ)·src + σ·noise gives bit for bit (scheduler.scale_noise), and
-// with m = 1 the blend is 0·keep + r = r, with m = 0 it is keep + 0·r = keep, with σ = 0 keep is src + 0·noise = src, for finite inputs.
+// The fp32 master step, per element and all in fp32 (u, t bf16 widened; the mixed velocity is never rounded to bf16):
+//   v = CFG ? u + s·(t − u) : u;   r = x + ds·v;   x = REPAINT ? (1 − m)·keep + m·r : r,   keep = (1 − sn)·src + sn·noise
+// and xb, when given, receives bf16(x): the copy the next step's x_embedder reads. The three entries run instantiations of this
+// one text; the tests hold them to bit equality where they must agree: t == u (the mix is u + s·0 = u exactly) and m = 1.
+//
+// keep and the blend are computed with contraction off, every product and sum rounded once: keep is then what torch's
+// (1 − σ)·src + σ·noise gives bit for bit (scheduler.scale_noise), and with m = 1 the blend is 0·keep + r = r, with m = 0 it is
+// keep + 0·r = keep, with σ = 0 keep is src + 0·noise = src, for finite inputs. The pragma stays inside repaint_blend: v and r are
+// left to the compiler's default contraction.
 __device__ __forceinline__ float repaint_blend(float r, float src, float noise, float m, float sn) {
 #pragma clang fp contract(off)
   const float keep = (1.0f - sn) * src + sn * noise;
   return (1.0f - m) * keep + m * r;
 }
 
+template <bool CFG, bool REPAINT>
+__device__ __forceinline__ float master_step_element(float x, float u, float t, float src, float noise, float m, float s, float ds,
+                                                     float sn) {
+  const float v = CFG ? u + s * (t - u) : u;
+  const float r = x + ds * v;
+  return REPAINT ? repaint_blend(r, src, noise, m, sn) : r;
+}
+
 // n4 groups of four elements with 16-byte loads and stores (8-byte ones for bf16), then the elements from 4·n4 on one at a time:
-// the up to three left over when the mask has x's length and that is no multiple of 4, or all of them — the host sets n4 = 0 where
-// a group could straddle the mask's period (n_mask < n and no multiple of 4) or a pointer is not aligned. m = mask[i % n_mask].
-template <bool CFG>
-__global__ void repaint_euler_step_f32_kernel(float* __restrict__ x, const bf16_t* __restrict__ u, const bf16_t* __restrict__ t,
-                                              bf16_t* __restrict__ xb, const float* __restrict__ src, const float* __restrict__ noise,
-                                              const float* __restrict__ mask, float s, float ds, float sn, int64_t n, int64_t n_mask,
-                                              int64_t n4) {
+// the up to three left over, or all of them — the host sets n4 = 0 where a pointer is not aligned or a group could straddle the
+// mask's period (n_mask < n and no multiple of 4). m = mask[i % n_mask]; t is read only under CFG, src / noise / mask only under REPAINT.
+template <bool CFG, bool REPAINT>
+__global__ void master_step_f32_kernel(float* __restrict__ x, const bf16_t* __restrict__ u, const bf16_t* __restrict__ t,
+                                       bf16_t* __restrict__ xb, const float* __restrict__ src, const float* __restrict__ noise,
+                                       const float* __restrict__ mask, float s, float ds, float sn, int64_t n, int64_t n_mask,
+                                       int64_t n4) {
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
   for (int64_t g = tid; g < n4; g += nthr) {
     const f32x4 xv = reinterpret_cast<const f32x4*>(x)[g];
-    const f32x4 sv = reinterpret_cast<const f32x4*>(src)[g], nv = reinterpret_cast<const f32x4*>(noise)[g];
-    const f32x4 mv = *reinterpret_cast<const f32x4*>(mask + (g * 4) % n_mask);
     const u32x2 uv = reinterpret_cast<const u32x2*>(u)[g];
     u32x2 tv = uv;
     if (CFG) tv = reinterpret_cast<const u32x2*>(t)[g];
+    f32x4 sv = xv, nv = xv, mv = xv;      // like tv: placeholders that the helper ignores without REPAINT
+    if (REPAINT) {
+      sv = reinterpret_cast<const f32x4*>(src)[g];
+      nv = reinterpret_cast<const f32x4*>(noise)[g];
+      mv = *reinterpret_cast<const f32x4*>(mask + (g * 4) % n_mask);
+    }
     f32x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float a = (j & 1) ? bf16hi(uv[j >> 1]) : bf16lo(uv[j >> 1]);
-      float v = a;
-      if (CFG) {
-        const float b = (j & 1) ? bf16hi(tv[j >> 1]) : bf16lo(tv[j >> 1]);
-        v = a + s * (b - a);
-      }
-      const float r = xv[j] + ds * v;
-      o[j] = repaint_blend(r, sv[j], nv[j], mv[j], sn);
+      const float b = (j & 1) ? bf16hi(tv[j >> 1]) : bf16lo(tv[j >> 1]);
+      o[j] = master_step_element<CFG, REPAINT>(xv[j], a, b, sv[j], nv[j], mv[j], s, ds, sn);
     }
     reinterpret_cast<f32x4*>(x)[g] = o;
     if (xb) reinterpret_cast<u32x2*>(xb)[g] = u32x2{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
   }
   for (int64_t i = n4 * 4 + tid; i < n; i += nthr) {
-    const float a = bf16_to_f32(u[i]);
-    float v = a;
-    if (CFG) v = a + s * (bf16_to_f32(t[i]) - a);
-    const float r = x[i] + ds * v;
-    const float o = repaint_blend(r, src[i], noise[i], mask[i % n_mask], sn);
+    const float a = bf16_to_f32(u[i]), b = CFG ? bf16_to_f32(t[i]) : a;
+    float sv = 0.0f, nv = 0.0f, mv = 0.0f;
+    if (REPAINT) { sv = src[i]; nv = noise[i]; mv = mask[i % n_mask]; }
+    const float o = master_step_element<CFG, REPAINT>(x[i], a, b, sv, nv, mv, s, ds, sn);
     x[i] = o;
     if (xb) xb[i] = f32_to_bf16(o);
   }
@@ -785,6 +772,20 @@ int rt_rope_table(const float* ids, float* cos_out, float* sin_out, int32_t S, c
   return rt_hip_status();
 }
 
+// The one launcher of master_step_f32_kernel: v_text selects CFG, mask selects REPAINT (src and noise come with it). The 16-byte path
+// needs every pointer that is present aligned for its access and, with a mask, no group of four across the mask's period.
+static int launch_master_step_f32(float* x, const void* v, const void* v_text, void* x_bf16, const float* src, const float* noise,
+                                  const float* mask, float s, float ds, float sn, int64_t n, int64_t n_mask, void* stream) {
+  const bool vec = RT_ALIGNED(x, 16) && RT_ALIGNED(v, 8) && (!v_text || RT_ALIGNED(v_text, 8)) && (!x_bf16 || RT_ALIGNED(x_bf16, 8)) &&
+                   (!mask || ((n_mask % 4 == 0 || n_mask == n) && RT_ALIGNED(src, 16) && RT_ALIGNED(noise, 16) && RT_ALIGNED(mask, 16)));
+  const int64_t n4 = vec ? n / 4 : 0;
+  const auto kernel = mask ? (v_text ? master_step_f32_kernel<true, true> : master_step_f32_kernel<false, true>)
+                           : (v_text ? master_step_f32_kernel<true, false> : master_step_f32_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(grid_for(n4 > 0 ? n4 : n, 256)), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)v,
+                     (const bf16_t*)v_text, (bf16_t*)x_bf16, src, noise, mask, s, ds, sn, n, n_mask, n4);
+  return rt_hip_status();
+}
+
 int rt_euler_step(void* x, const void* v, float dsigma, int64_t n, void* stream) {
   if (!x || !v || n < 1) return RT_E_BADARG;
   if (!RT_ALIGNED(x, 16) || !RT_ALIGNED(v, 16)) return RT_E_ALIGN;
@@ -800,34 +801,20 @@ int rt_euler_step(void* x, const void* v, float dsigma, int64_t n, void* stream)
 
 int rt_euler_step_f32(float* x, const void* v, void* x_bf16, float dsigma, int64_t n, void* stream) {
   if (!x || !v || n < 1) return RT_E_BADARG;
-  hipLaunchKernelGGL(euler_step_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)v,
-                     (bf16_t*)x_bf16, dsigma, n);
-  return rt_hip_status();
+  return launch_master_step_f32(x, v, nullptr, x_bf16, nullptr, nullptr, nullptr, 0.0f, dsigma, 0.0f, n, n, stream);
 }
 
 int rt_cfg_euler_step_f32(float* x, const void* v_uncond, const void* v_text, void* x_bf16, float s, float dsigma, int64_t n,
                           void* stream) {
   if (!x || !v_uncond || !v_text || n < 1) return RT_E_BADARG;
-  hipLaunchKernelGGL(cfg_euler_step_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x,
-                     (const bf16_t*)v_uncond, (const bf16_t*)v_text, (bf16_t*)x_bf16, s, dsigma, n);
-  return rt_hip_status();
+  return launch_master_step_f32(x, v_uncond, v_text, x_bf16, nullptr, nullptr, nullptr, s, dsigma, 0.0f, n, n, stream);
 }
 
 int rt_repaint_euler_step_f32(float* x, const void* v, const void* v_text, void* x_bf16, const float* src, const float* noise,
                               const float* mask, float s, float dsigma, float sigma_next, int64_t n, int64_t n_mask, void* stream) {
   if (!x || !v || !src || !noise || !mask || n < 1 || n_mask < 1) return RT_E_BADARG;
   if (n % n_mask) return RT_E_SHAPE;
-  const bool vec = (n_mask % 4 == 0 || n_mask == n) && RT_ALIGNED(x, 16) && RT_ALIGNED(src, 16) && RT_ALIGNED(noise, 16) && RT_ALIGNED(mask, 16) &&
-                   RT_ALIGNED(v, 8) && (!v_text || RT_ALIGNED(v_text, 8)) && (!x_bf16 || RT_ALIGNED(x_bf16, 8));
-  const int64_t n4 = vec ? n / 4 : 0;
-  const dim3 grid(grid_for(n4 > 0 ? n4 : n, 256)), block(256);
-  if (v_text)
-    hipLaunchKernelGGL(repaint_euler_step_f32_kernel<true>, grid, block, 0, (hipStream_t)stream, x, (const bf16_t*)v,
-                       (const bf16_t*)v_text, (bf16_t*)x_bf16, src, noise, mask, s, dsigma, sigma_next, n, n_mask, n4);
-  else
-    hipLaunchKernelGGL(repaint_euler_step_f32_kernel<false>, grid, block, 0, (hipStream_t)stream, x, (const bf16_t*)v,
-                       (const bf16_t*)nullptr, (bf16_t*)x_bf16, src, noise, mask, s, dsigma, sigma_next, n, n_mask, n4);
-  return rt_hip_status();
+  return launch_master_step_f32(x, v, v_text, x_bf16, src, noise, mask, s, dsigma, sigma_next, n, n_mask, stream);
 }
 
 int rt_cfg_mix(const void* v_uncond, const void* v_text, void* out, float s, int64_t n, void* stream) {

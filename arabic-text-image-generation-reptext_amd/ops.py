@@ -687,27 +687,38 @@ def euler_step_(x: torch.Tensor, v: torch.Tensor, dsigma: float) -> torch.Tensor
     return x
 
 
-def euler_step_f32_(x32: torch.Tensor, v: torch.Tensor, dsigma: float, x_bf16: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """x32 += dsigma*v on an fp32 master state; optionally refreshes its bf16 copy."""
-    if not (x32.is_contiguous() and v.is_contiguous()) or x32.shape != v.shape:
-        raise ValueError("euler_step_f32_: contiguous tensors of equal shape")
+def _master_step_f32(name: str, x32: torch.Tensor, v: torch.Tensor, v_text: Optional[torch.Tensor], s: float, dsigma: float,
+                     x_bf16: Optional[torch.Tensor], sigma_next: float = 0.0, src32: Optional[torch.Tensor] = None,
+                     noise32: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The body of euler_step_f32_ / cfg_euler_step_f32_ / repaint_euler_step_f32_ (``name``, for the messages): the checks, and the
+    entry that what is given selects. One fp32 master step x32 += dsigma·vel, vel = v or v + s·(v_text − v); with a mask, the blend."""
+    like = [t for t in (v, v_text, src32, noise32) if t is not None]
+    if not all(t.is_contiguous() for t in [x32, *like] + ([] if mask is None else [mask])) or not all(t.shape == x32.shape for t in like):
+        raise ValueError(f"{name}: contiguous tensors of equal shape")
     if x_bf16 is not None and (x_bf16.shape != x32.shape or not x_bf16.is_contiguous()):
         raise ValueError("x_bf16 must match x32")
-    native.call("rt_euler_step_f32", _dev(x32, "x32", F32), _dev(v, "v", BF16), _opt(x_bf16, "x_bf16", BF16),
-                float(dsigma), x32.numel(), _stream())
+    if mask is not None and mask.shape != x32.shape and not (x32.dim() > 1 and tuple(mask.shape) == (1,) + tuple(x32.shape[1:])):
+        raise ValueError(f"{name}: mask {tuple(mask.shape)} is neither x32's shape {tuple(x32.shape)} nor that of one sample")
+    x, xb, n = _dev(x32, "x32", F32), _opt(x_bf16, "x_bf16", BF16), x32.numel()
+    if mask is not None:
+        native.call("rt_repaint_euler_step_f32", x, _dev(v, "v", BF16), _opt(v_text, "v_text", BF16), xb, _dev(src32, "src32", F32),
+                    _dev(noise32, "noise32", F32), _dev(mask, "mask", F32), float(s), float(dsigma), float(sigma_next), n, mask.numel(), _stream())
+    elif v_text is not None:
+        native.call("rt_cfg_euler_step_f32", x, _dev(v, "v_uncond", BF16), _dev(v_text, "v_text", BF16), xb, float(s), float(dsigma), n, _stream())
+    else:
+        native.call("rt_euler_step_f32", x, _dev(v, "v", BF16), xb, float(dsigma), n, _stream())
     return x32
+
+
+def euler_step_f32_(x32: torch.Tensor, v: torch.Tensor, dsigma: float, x_bf16: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """x32 += dsigma*v on an fp32 master state; optionally refreshes its bf16 copy."""
+    return _master_step_f32("euler_step_f32_", x32, v, None, 0.0, dsigma, x_bf16)
 
 
 def cfg_euler_step_f32_(x32: torch.Tensor, v_uncond: torch.Tensor, v_text: torch.Tensor, s: float, dsigma: float,
                        x_bf16: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x32 += dsigma*(u + s*(t - u)) on an fp32 master state, the mix kept in fp32; optionally refreshes its bf16 copy."""
-    if not (x32.is_contiguous() and v_uncond.is_contiguous() and v_text.is_contiguous()) or not (x32.shape == v_uncond.shape == v_text.shape):
-        raise ValueError("cfg_euler_step_f32_: contiguous tensors of equal shape")
-    if x_bf16 is not None and (x_bf16.shape != x32.shape or not x_bf16.is_contiguous()):
-        raise ValueError("x_bf16 must match x32")
-    native.call("rt_cfg_euler_step_f32", _dev(x32, "x32", F32), _dev(v_uncond, "v_uncond", BF16), _dev(v_text, "v_text", BF16),
-                _opt(x_bf16, "x_bf16", BF16), float(s), float(dsigma), x32.numel(), _stream())
-    return x32
+    return _master_step_f32("cfg_euler_step_f32_", x32, v_uncond, v_text, s, dsigma, x_bf16)
 
 
 def repaint_euler_step_f32_(x32: torch.Tensor, v: torch.Tensor, v_text: Optional[torch.Tensor], s: float, dsigma: float, sigma_next: float,
@@ -715,17 +726,7 @@ def repaint_euler_step_f32_(x32: torch.Tensor, v: torch.Tensor, v_text: Optional
     """The fp32 master step (``v_text`` given: the true-CFG one, ``v`` its unconditional half) followed by the latent blend of a
     repaint: x32 = (1 − m)·((1 − sigma_next)·src + sigma_next·noise) + m·(x32 + dsigma·vel); optionally refreshes the bf16 copy.
     ``mask`` has x32's shape, or a leading 1 where x32 has its batch: one mask for every sample."""
-    vs = [v] if v_text is None else [v, v_text]
-    if not all(t.is_contiguous() for t in [x32, src32, noise32, mask] + vs) or not all(t.shape == x32.shape for t in [src32, noise32] + vs):
-        raise ValueError("repaint_euler_step_f32_: contiguous tensors of equal shape")
-    if x_bf16 is not None and (x_bf16.shape != x32.shape or not x_bf16.is_contiguous()):
-        raise ValueError("x_bf16 must match x32")
-    if mask.shape != x32.shape and not (x32.dim() > 1 and tuple(mask.shape) == (1,) + tuple(x32.shape[1:])):
-        raise ValueError(f"repaint_euler_step_f32_: mask {tuple(mask.shape)} is neither x32's shape {tuple(x32.shape)} nor that of one sample")
-    native.call("rt_repaint_euler_step_f32", _dev(x32, "x32", F32), _dev(v, "v", BF16), _opt(v_text, "v_text", BF16), _opt(x_bf16, "x_bf16", BF16),
-                _dev(src32, "src32", F32), _dev(noise32, "noise32", F32), _dev(mask, "mask", F32), float(s), float(dsigma), float(sigma_next),
-                x32.numel(), mask.numel(), _stream())
-    return x32
+    return _master_step_f32("repaint_euler_step_f32_", x32, v, v_text, s, dsigma, x_bf16, sigma_next, src32, noise32, mask)
 
 
 def cfg_mix(v_uncond: torch.Tensor, v_text: torch.Tensor, s: float) -> torch.Tensor:

@@ -202,7 +202,7 @@ class UnionTower:
 @dataclass(frozen=True)
 class Repaint:
     """Latent-blend repaint: after every step the state becomes ``src32`` re-noised with ``noise32`` to the next sigma where ``mask`` is
-    0 and stays the step's result where it is 1 (``scheduler.step_master_repaint_``). fp32; under true CFG at the latents' batch B."""
+    0 and stays the step's result where it is 1 (``scheduler.step_master_(repaint=)``). fp32; under true CFG at the latents' batch B."""
     src32: torch.Tensor       # [B, N, 64] packed source latents
     noise32: torch.Tensor     # [B, N, 64] the noise the start state was mixed with
     mask: torch.Tensor        # [1 or B, N, 64]; fractional values blend
@@ -215,7 +215,7 @@ class LoopExtras:
     ip_embeds: Optional[torch.Tensor] = None     # the image prompt, [total or 1, E] ([2·total, E] under true CFG); None: nothing to add
     union: Optional[UnionTower] = None           # it keeps the side stream and the text towers' row window
     # true CFG of the base flow: the conditioning batch is [negative, positive] (2B against the latents' B) and the step mixes its halves in
-    # fp32 (``scheduler.step_master_cfg_``); all else sees Bc = 2B
+    # fp32 (``scheduler.step_master_(v_text=, s=)``); all else sees Bc = 2B
     cfg_scale: Optional[float] = None
     tower_window: Any = None                     # ``active_row_window`` of the masks from the call prologue (None: every row)
     # (FluxControlNetModel, hint, conditioning scale) of unmasked towers after the text lines (the inpaint tower); the loop then stays on one stream
@@ -1317,14 +1317,9 @@ class FluxControlNetPipeline:
                     torch.cuda.current_stream().wait_stream(side)     # the tower has finished reading `latents` (its last sample is unused, Q5)
                 if extras.velocity is not None:
                     noise_pred = extras.velocity(i, noise_pred)
-                if extras.repaint is not None:
-                    cfg, rp = extras.cfg_scale is not None, extras.repaint
-                    self.scheduler.step_master_repaint_(noise_pred[:B] if cfg else noise_pred, noise_pred[B:] if cfg else None, extras.cfg_scale,
-                                                        lat32, latents, rp.src32, rp.noise32, rp.mask)
-                elif extras.cfg_scale is not None:
-                    self.scheduler.step_master_cfg_(noise_pred[:B], noise_pred[B:], extras.cfg_scale, lat32, latents)
-                else:
-                    self.scheduler.step_master_(noise_pred, lat32, latents)
+                cfg = extras.cfg_scale is not None             # then noise_pred is [negative, positive], B each
+                self.scheduler.step_master_(noise_pred[:B] if cfg else noise_pred, lat32, latents, v_text=noise_pred[B:] if cfg else None,
+                                            s=extras.cfg_scale, repaint=extras.repaint)
                 if callback is not None:
                     env = {"latents": latents, "prompt_embeds": prompt_embeds}
                     out = callback(self, i, timesteps[i], {k: env[k] for k in callback_inputs})

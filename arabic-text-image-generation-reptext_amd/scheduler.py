@@ -90,37 +90,27 @@ class FlowMatchEulerDiscreteScheduler:
         idx = (self.timesteps.cpu() == t).nonzero()
         self._step_index = int(idx[1 if len(idx) > 1 else 0]) if len(idx) > 0 else 0
 
-    def step_master_(self, model_output: torch.Tensor, sample32: torch.Tensor, sample_bf16: Optional[torch.Tensor] = None) -> None:
+    def _advance(self):
+        """(sigmas[i], sigmas[i + 1]) of the step about to be taken, and the index moves on. The loop walks the timesteps in order, so
+        the first step is the begin index or 0: looking the timestep up would cost a device sync."""
+        if self._step_index is None:
+            self._step_index = self._begin_index if self._begin_index is not None else 0
+        i = self._step_index
+        self._step_index = i + 1
+        return self.sigmas[i], self.sigmas[i + 1]
+
+    def step_master_(self, v: torch.Tensor, sample32: torch.Tensor, sample_bf16: Optional[torch.Tensor] = None, *,
+                     v_text: Optional[torch.Tensor] = None, s: Optional[float] = None, repaint=None) -> None:
         """In-place Euler step on an fp32 master copy of the latents (used by this repo's pipelines between steps; ``step`` keeps
-        the diffusers contract of returning the model dtype). Advances the step index exactly like ``step``."""
-        if self._step_index is None:
-            self._step_index = self._begin_index if self._begin_index is not None else 0
-        i = self._step_index
-        ops.euler_step_f32_(sample32, model_output.contiguous(), float(self.sigmas[i + 1] - self.sigmas[i]), sample_bf16)
-        self._step_index = i + 1
-
-    def step_master_cfg_(self, v_uncond: torch.Tensor, v_text: torch.Tensor, s: float, sample32: torch.Tensor,
-                         sample_bf16: Optional[torch.Tensor] = None) -> None:
-        """``step_master_`` with the velocity ``v_uncond + s·(v_text − v_uncond)`` (true CFG), mixed in fp32 inside the step's kernel:
-        the mix is not rounded to bf16 before the fp32 state takes it. Advances the step index exactly like ``step_master_``."""
-        if self._step_index is None:
-            self._step_index = self._begin_index if self._begin_index is not None else 0
-        i = self._step_index
-        ops.cfg_euler_step_f32_(sample32, v_uncond.contiguous(), v_text.contiguous(), float(s),
-                                float(self.sigmas[i + 1] - self.sigmas[i]), sample_bf16)
-        self._step_index = i + 1
-
-    def step_master_repaint_(self, v: torch.Tensor, v_text: Optional[torch.Tensor], s: Optional[float], sample32: torch.Tensor,
-                             sample_bf16: Optional[torch.Tensor], src32: torch.Tensor, noise32: torch.Tensor, mask: torch.Tensor) -> None:
-        """``step_master_`` (``v_text`` None) or ``step_master_cfg_`` (``v`` the unconditional half) followed, inside the same kernel, by
-        the latent blend of a repaint: where ``mask`` is 0 the state becomes the source re-noised to the NEXT sigma,
-        ``scale_noise(src32, sigmas[i + 1], noise32)`` — the source itself after the last step. Advances the step index like ``step_master_``."""
-        if self._step_index is None:
-            self._step_index = self._begin_index if self._begin_index is not None else 0
-        i = self._step_index
-        ops.repaint_euler_step_f32_(sample32, v.contiguous(), None if v_text is None else v_text.contiguous(), float(s or 0.0),
-                                    float(self.sigmas[i + 1] - self.sigmas[i]), float(self.sigmas[i + 1]), src32, noise32, mask, sample_bf16)
-        self._step_index = i + 1
+        the diffusers contract of returning the model dtype), one kernel. Advances the step index exactly like ``step``.
+        ``v_text``: true CFG, the velocity is ``v + s·(v_text − v)`` (``v`` the unconditional half), mixed in fp32 inside the kernel and
+        not rounded to bf16 before the state takes it. ``repaint`` (a record with ``src32``, ``noise32``, ``mask``): where ``mask`` is 0
+        the state becomes the source re-noised to the NEXT sigma, ``scale_noise(src32, sigmas[i + 1], noise32)`` — the source itself
+        after the last step."""
+        sigma, sigma_next = self._advance()
+        v_text = None if v_text is None else v_text.contiguous()
+        rp = {} if repaint is None else dict(sigma_next=float(sigma_next), src32=repaint.src32, noise32=repaint.noise32, mask=repaint.mask)
+        ops._master_step_f32("step_master_", sample32, v.contiguous(), v_text, float(s or 0.0), float(sigma_next - sigma), sample_bf16, **rp)
 
     def scale_noise(self, sample: torch.Tensor, sigma_or_timestep, noise: torch.Tensor) -> torch.Tensor:
         """``sigma·noise + (1 − sigma)·sample``: the forward process of flow matching (diffusers' rule, recalled). A value of at most 1 is
@@ -136,14 +126,9 @@ class FlowMatchEulerDiscreteScheduler:
 
     def step(self, model_output: torch.Tensor, timestep: Union[float, torch.Tensor], sample: torch.Tensor,
              return_dict: bool = True, **unused):
-        if self._step_index is None:
-            # the loop walks timesteps in order; avoid a device sync by starting at 0 unless a begin index was set
-            self._step_index = self._begin_index if self._begin_index is not None else 0
-        i = self._step_index
-        dsigma = float(self.sigmas[i + 1] - self.sigmas[i])
+        sigma, sigma_next = self._advance()
         prev = sample.to(model_output.dtype).clone()
-        ops.euler_step_(prev, model_output.contiguous(), dsigma)
-        self._step_index = i + 1
+        ops.euler_step_(prev, model_output.contiguous(), float(sigma_next - sigma))
         if not return_dict:
             return (prev,)
         return Config(prev_sample=prev)

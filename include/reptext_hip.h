@@ -422,31 +422,29 @@ int rt_attention_hd72(const void* q, int64_t ldq, int64_t stride_qb,
  * rounded to fp32 (no fused multiply-add), as torch computes it. */
 int rt_euler_step(void* x, const void* v, float dsigma, int64_t n, void* stream);
 
-/* Same step on an fp32 master copy of the latents (x32 += dsigma·v, v bf16), optionally writing the bf16 copy the next model
- * call reads. diffusers computes the step in fp32 and rounds the STATE back to bf16 every step; keeping the state in fp32
- * removes 28 accumulated roundings (the fp32 CPU reference path keeps fp32 throughout). */
-int rt_euler_step_f32(float* x, const void* v, void* x_bf16 /* nullable */, float dsigma, int64_t n, void* stream);
-
 /* True-CFG mix of the inpaint pipeline (INP:1264-1270): out = uncond + s·(text − uncond); bf16. */
 int rt_cfg_mix(const void* v_uncond, const void* v_text, void* out, float s, int64_t n, void* stream);
 
-/* True CFG of the text-to-image pipeline fused into the fp32 master step (pipeline._denoise_eager with a negative prompt, through
- * scheduler.step_master_cfg_): x32 += dsigma·(u + s·(t − u)), u / t the bf16 halves [negative, positive] of the transformer's output
- * widened to fp32. All in fp32: the mixed velocity is never rounded to bf16 (rt_cfg_mix + rt_euler_step_f32 would round it once per
- * step before the fp32 state consumes it). x_bf16, when given, receives bf16(x32). With t == u this is rt_euler_step_f32(x, u, ...)
- * bit for bit, for any s. NULL x / v_uncond / v_text or n < 1: RT_E_BADARG. */
+/* The step on an fp32 master copy of the latents (pipeline._denoise_eager, through scheduler.step_master_), one kernel. diffusers
+ * computes the step in fp32 and rounds the STATE back to bf16 every step; keeping the state in fp32 removes 28 accumulated roundings
+ * (the fp32 CPU reference path keeps fp32 throughout). Per element i, all in fp32:
+ *   vel  = v_text ? u + s·(t − u) : v          u = v, t = v_text: bf16 widened, under true CFG the halves [negative, positive] of the
+ *                                              transformer's output; the mix is never rounded to bf16 (rt_cfg_mix would round it
+ *                                              once per step before the fp32 state consumes it); s unused without v_text
+ *   r    = x + dsigma·vel
+ *   keep = (1 − sigma_next)·src + sigma_next·noise
+ *   x[i] = mask ? (1 − m)·keep + m·r : r,  m = mask[i % n_mask]
+ *   x_bf16[i] = bf16(x[i]) when given: the copy the next model call reads
+ * The three entries below are views of this one step and run instantiations of one kernel: rt_euler_step_f32 has neither v_text nor
+ * a mask, rt_cfg_euler_step_f32 has v_text, rt_repaint_euler_step_f32 has the mask (the latent blend of a repaint, LoopExtras.repaint)
+ * and v_text or not. With t == u the mix is u exactly, for any s, so rt_cfg_euler_step_f32 is then rt_euler_step_f32.
+ * n_mask is n or the per-sample length: one mask serves the batch. keep and the blend are computed without fused multiply-adds, so for
+ * finite inputs m = 1 is the step without a mask bit for bit, m = 0 gives keep as torch computes it, and sigma_next = 0 gives src there.
+ * NULL x / v (v_uncond) / src / noise / mask, NULL v_text where it is not nullable, n < 1 or n_mask < 1: RT_E_BADARG;
+ * n % n_mask != 0: RT_E_SHAPE. */
+int rt_euler_step_f32(float* x, const void* v, void* x_bf16 /* nullable */, float dsigma, int64_t n, void* stream);
 int rt_cfg_euler_step_f32(float* x, const void* v_uncond, const void* v_text, void* x_bf16 /* nullable */,
                           float s, float dsigma, int64_t n, void* stream);
-
-/* Latent-blend repaint fused into the fp32 master step (pipeline._denoise_eager with LoopExtras.repaint, through
- * scheduler.step_master_repaint_). Per element i, all in fp32:
- *   vel  = v_text ? u + s·(t − u) : v          u = v, t = v_text, bf16 widened (rt_cfg_euler_step_f32's expression; s unused without v_text)
- *   r    = x + dsigma·vel                       (rt_euler_step_f32's expression)
- *   keep = (1 − sigma_next)·src + sigma_next·noise
- *   x[i] = (1 − m)·keep + m·r,  m = mask[i % n_mask];   x_bf16[i] = bf16(x[i]) when given
- * n_mask is n or the per-sample length: one mask serves the batch. keep and the blend are computed without fused multiply-adds, so
- * for finite inputs m = 1 is rt_euler_step_f32 / rt_cfg_euler_step_f32 bit for bit, m = 0 gives keep as torch computes it, and
- * sigma_next = 0 gives src there. NULL x / v / src / noise / mask, n < 1 or n_mask < 1: RT_E_BADARG; n % n_mask != 0: RT_E_SHAPE. */
 int rt_repaint_euler_step_f32(float* x, const void* v, const void* v_text /* nullable */, void* x_bf16 /* nullable */,
                               const float* src, const float* noise, const float* mask, float s, float dsigma, float sigma_next,
                               int64_t n, int64_t n_mask, void* stream);

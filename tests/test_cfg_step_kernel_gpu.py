@@ -12,7 +12,10 @@ import pytest
 import torch
 
 BF16, F32 = torch.bfloat16, torch.float32
-SIZES = [1, 255, 257, 2 * 256 * 64 + 3]        # one thread, a block less one, a block plus one, two 256x64 latents' worth plus a tail
+WRAP = 4 * (4096 * 256 + 1000)                 # 1000 groups of four more than one pass of the largest grid (4096 blocks of 256) takes
+# the kernel takes groups of four (16-byte accesses), then what is left one at a time: no group; a tail alone; one group; a group and a
+# tail; 16 groups and 3; around a block's worth; two 256x64 latents' worth plus a tail; the vector loop's grid stride wraps, then 3
+SIZES = [1, 3, 4, 5, 67, 255, 257, 2 * 256 * 64 + 3, WRAP + 3]
 SCALES = [0.0, 1.0, 3.5]
 DS = -0.0116
 
@@ -74,6 +77,35 @@ def test_equal_halves_are_the_plain_step_bit_for_bit(gpu, n, s):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("with_bf16", [False, True])
+@pytest.mark.parametrize("n", [67, 16384])
+@pytest.mark.parametrize("cfg", [False, True])
+def test_vector_and_one_element_paths_agree_bit_for_bit(gpu, cfg, n, with_bf16):
+    """The same values through aligned tensors (the 16-byte path, at n = 67 with its tail) and through contiguous views that start one
+    element into their buffers (4 bytes off for fp32, 2 for bf16): there no 16-byte access is possible and every element takes the
+    one-element path. Both entries, rt_euler_step_f32 and rt_cfg_euler_step_f32."""
+    from reptext_amd import ops
+
+    x, u, t = _inputs(n, 900 + n % 1000 + 2 * cfg + with_bf16)
+    outs = []
+    for off in (0, 1):
+        place = lambda a: torch.cat([a[:off], a]).to(gpu)[off:]
+        dx, du, dt = place(x), place(u), place(t)
+        xb = place(torch.full((n,), 12345.0, dtype=BF16)) if with_bf16 else None
+        assert all(a.is_contiguous() and (a.data_ptr() % 16 == 0) == (off == 0) for a in (dx, du, dt) + (() if xb is None else (xb,)))
+        if cfg:
+            ops.cfg_euler_step_f32_(dx, du, dt, 3.5, DS, xb)
+        else:
+            ops.euler_step_f32_(dx, du, DS, xb)
+        outs.append((dx.cpu(), None if xb is None else xb.cpu()))
+    assert torch.equal(outs[0][0].view(torch.int32), outs[1][0].view(torch.int32))
+    assert not torch.equal(outs[0][0], x)
+    if with_bf16:
+        assert torch.equal(outs[0][1].view(torch.int16), outs[1][1].view(torch.int16))
+        assert torch.equal(outs[0][1].view(torch.int16), outs[0][0].to(BF16).view(torch.int16))
+
+
+@pytest.mark.gpu
 def test_scheduler_step_master_cfg_advances_like_step_master(gpu):
     from reptext_amd import ops
     from reptext_amd.scheduler import FlowMatchEulerDiscreteScheduler
@@ -85,7 +117,7 @@ def test_scheduler_step_master_cfg_advances_like_step_master(gpu):
     a32, ab = x.to(gpu), torch.zeros(1000, dtype=BF16, device=gpu)
     b32 = x.to(gpu)
     for i in range(3):
-        scheds[0].step_master_cfg_(u.to(gpu), t.to(gpu), 2.0, a32, ab)
+        scheds[0].step_master_(u.to(gpu), a32, ab, v_text=t.to(gpu), s=2.0)
         ds = float(scheds[1].sigmas[i + 1] - scheds[1].sigmas[i])
         ops.cfg_euler_step_f32_(b32, u.to(gpu), t.to(gpu), 2.0, ds)
         scheds[1].step_master_(u.to(gpu), torch.zeros(1000, device=gpu))

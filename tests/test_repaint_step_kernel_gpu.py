@@ -162,6 +162,7 @@ def test_one_mask_for_the_batch_is_the_mask_repeated(gpu, n):
 @pytest.mark.gpu
 def test_scheduler_step_master_repaint_takes_both_sigmas_and_honours_the_begin_index(gpu):
     from reptext_amd import ops
+    from reptext_amd.pipeline import Repaint
     from reptext_amd.scheduler import FlowMatchEulerDiscreteScheduler
 
     x, u, t, src, noise, mask = _inputs(2, 1000, 7, True)
@@ -176,7 +177,7 @@ def test_scheduler_step_master_repaint_takes_both_sigmas_and_honours_the_begin_i
                 first = begin
             a32, ab, b32 = dev(x), torch.zeros(2, 1000, dtype=BF16, device=gpu), dev(x)
             for i in range(first, 3):
-                sc.step_master_repaint_(dev(u), dev(t) if cfg else None, 2.0 if cfg else None, a32, ab, dev(src), dev(noise), dev(mask))
+                sc.step_master_(dev(u), a32, ab, v_text=dev(t) if cfg else None, s=2.0 if cfg else None, repaint=Repaint(dev(src), dev(noise), dev(mask)))
                 ops.repaint_euler_step_f32_(b32, dev(u), dev(t) if cfg else None, 2.0, float(sc.sigmas[i + 1] - sc.sigmas[i]), float(sc.sigmas[i + 1]),
                                             dev(src), dev(noise), dev(mask))
                 assert sc.step_index == i + 1

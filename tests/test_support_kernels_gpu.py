@@ -454,10 +454,12 @@ def test_euler_step_sizes(ops, gpu, n):
 
 
 @pytest.mark.parametrize("with_bf16", [False, True])
-@pytest.mark.parametrize("n", [1000, GRID_CAP + 3])
+@pytest.mark.parametrize("n", [1, 3, 4, 5, 67, 1000, GRID_CAP + 3, 4 * (GRID_CAP + 1000) + 3])
 def test_euler_step_f32(ops, gpu, n, with_bf16):
     """fp32 master state x32 += dsigma·v (v bf16): within one fp32 ulp of the fp64 axpy, and the optional bf16 copy is EXACTLY the bf16
-    rounding of the x32 that was returned. n past the grid cap takes the second grid-stride trip."""
+    rounding of the x32 that was returned. The kernel takes groups of four elements, then what is left one at a time: no group (1, 3),
+    one group (4), a group and a tail (5, 67), and a last size at which a thread takes a second group (the grid-stride trip past the
+    grid cap) and three elements are left for the tail."""
     g = torch.Generator().manual_seed(n % 1000 + with_bf16)
     x = torch.randn(n, generator=g)
     v = torch.randn(n, generator=g).to(BF16)

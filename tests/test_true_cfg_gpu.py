@@ -166,11 +166,11 @@ def test_off_means_off(gpu, capfd):
     assert capfd.readouterr().err.count("true_cfg_scale") == 1             # the scale without a negative prompt: one line
     assert sum(isinstance(v, dict) for v in pipe._graph_cache.values()) == 1
     pipe.capture_graphs = False
-    calls = []
+    calls, texts = [], []
     real = pipe.scheduler.step_master_
-    pipe.scheduler.step_master_ = lambda *a, **k: (calls.append(a[0].shape[0]), real(*a, **k))[1]
+    pipe.scheduler.step_master_ = lambda *a, **k: (calls.append(a[0].shape[0]), texts.append(k.get("v_text")), real(*a, **k))[-1]
     assert torch.equal(pipe(**kw, true_cfg_scale=3.5).images, want)
-    assert calls == [1, 1, 1]                                               # the plain step on a batch-1 velocity: the same launches
+    assert calls == [1, 1, 1] and texts == [None] * 3                       # the plain step on a batch-1 velocity: the same launches
 
 
 # ------------------------------------------------------------------------------------------------------------------ 3. collapse
@@ -185,12 +185,12 @@ def test_equal_halves_collapse_to_the_plain_call(gpu):
     pipe.capture_graphs = False
     want = pipe(**kw).images.clone()
     seen = []
-    real = pipe.scheduler.step_master_cfg_
-    pipe.scheduler.step_master_cfg_ = lambda u, t, *a, **k: (seen.append(torch.equal(u, t)), real(u, t, *a, **k))[1]
+    real = pipe.scheduler.step_master_
+    pipe.scheduler.step_master_ = lambda v, *a, **k: (seen.append(torch.equal(v, k["v_text"])), real(v, *a, **k))[1]
     got = pipe(**kw, **same).images.clone()
     assert seen == [True] * 3, "the two halves of the transformer's output differ: a launch is not batch invariant"
     assert torch.equal(got, want)
-    pipe.scheduler.step_master_cfg_ = real
+    pipe.scheduler.step_master_ = real
     pipe.capture_graphs = True
     for _ in range(3):
         assert torch.equal(pipe(**kw, **same).images, want)
