@@ -724,6 +724,7 @@ int rt_qk_rmsnorm_rope(void* buf, int64_t ld, int64_t stride_b, int64_t q_off, i
   if (!RT_ALIGNED(buf, 16) || ld % 8 || stride_b % 8 || q_off % 8 || k_off % 8 || !RT_ALIGNED(cosv, 16) ||
       !RT_ALIGNED(sinv, 16) || !RT_ALIGNED(wq_img, 16) || !RT_ALIGNED(wk_img, 16))
     return RT_E_ALIGN;
+  if (T > 0 && (!RT_ALIGNED(wq_txt, 16) || !RT_ALIGNED(wk_txt, 16))) return RT_E_ALIGN;   // loaded as 16-byte vectors like the image weights
   const int64_t ngrp = (int64_t)B * S * ((H + QK_HC - 1) / QK_HC);
   const int64_t blocks = (ngrp + 15) / 16;
   if (blocks > 0x7fffffff) return RT_E_SHAPE;

@@ -223,7 +223,9 @@ int rt_layernorm_modulate_fp8(const void* x, int64_t ldx, int64_t stride_xb, int
 /* RMSNorm(Dh, weight, eps) on q and k heads + interleaved-pair RoPE, in place on a fused
  * projection buffer (A.1 steps 3,5; A.2). Row (b,s) holds q at column q_off and k at k_off,
  * H heads of Dh=128 each. Rows s < T use the text weights (norm_added_q/k), others the image
- * weights; pass T = 0 for single-stream blocks. cos/sin f32 [S][128]. */
+ * weights; pass T = 0 for single-stream blocks. cos/sin f32 [S][128]. The weights are read as
+ * 16-byte vectors: wq_img / wk_img, and wq_txt / wk_txt when T > 0, must be 16-byte aligned
+ * (RT_E_ALIGN otherwise; with T = 0 the text weights are not looked at). */
 int rt_qk_rmsnorm_rope(void* buf, int64_t ld, int64_t stride_b, int64_t q_off, int64_t k_off,
                        const void* wq_txt, const void* wk_txt, const void* wq_img, const void* wk_img,
                        const float* cosv, const float* sinv,
@@ -269,7 +271,8 @@ int rt_attention_variant(int32_t mode);
  * rt_attention_fp8_prep replaces rt_qk_rmsnorm_rope on this path: from the fused projection buffer (row (b,s): q at q_off,
  * k at k_off, v at v_off, H heads of 128) it writes qk8 = [B][S][2·H·128] bytes (normalised, rotated q | k) and
  * vt8 = [B][H][128][S64] bytes (S64 = S rounded up to 64; Vᵀ with the keys of every 64-key tile permuted into MFMA operand
- * order, zero beyond S); rt_attention_fp8_vt_bytes gives vt8's size. buf is not modified. */
+ * order, zero beyond S); rt_attention_fp8_vt_bytes gives vt8's size. buf is not modified. The norm weights follow
+ * rt_qk_rmsnorm_rope's rule: wq_img / wk_img, and wq_txt / wk_txt when T > 0, 16-byte aligned or RT_E_ALIGN. */
 int64_t rt_attention_fp8_vt_bytes(int32_t B, int32_t S, int32_t H);
 int rt_attention_fp8_prep(const void* buf, int64_t ld, int64_t stride_b, int64_t q_off, int64_t k_off, int64_t v_off,
                           const void* wq_txt, const void* wk_txt, const void* wq_img, const void* wk_img,

@@ -1,6 +1,9 @@
 """What the tests of tests/test_support_kernels_gpu.py, test_gemm_epilogue_gpu.py, test_attention_edges_gpu.py and test_vae_kernels_gpu.py
 share: the fp64 references of the GEMM epilogue, of the convolution and of attention, the per-element bound check, guarded buffers (NaN where a kernel must not read, a sentinel where it must
-not write), the bf16 error bound, ulp distances and the run-twice check. A plain helper module, not a test file."""
+not write), the bf16 error bound, ulp distances and the run-twice check. Further down, for test_token_passes_gpu.py and
+test_e4m3_producers_gpu.py: batched guarded views, the fp64 references and fp32-evaluation bounds of LayerNorm + modulation and of q/k
+RMSNorm + RoPE, the e4m3 grid (ulp_e4m3, finite bytes), the row-quantisation rule and the documented key order of the e4m3 V^T.
+A plain helper module, not a test file."""
 import torch
 
 NAN = float("nan")
@@ -237,3 +240,220 @@ def attention_ref(q, k, v, scale=None):
             p = torch.softmax(q[b, :, h] @ k[b, :, h].t() * sc, dim=-1)
             ref[b, :, h], pv[b, :, h] = p @ v[b, :, h], p @ v[b, :, h].abs()
     return ref.reshape(B, S, H * Dh), pv.reshape(B, S, H * Dh)
+
+
+# ------------------------------------------------------------------------------------------------ token passes and e4m3 producers
+FP8 = torch.float8_e4m3fn
+NAN_U8 = 0x7F                    # an e4m3 NaN: what a byte the kernel must not read, or failed to write, holds
+U24, U23 = 2.0 ** -24, 2.0 ** -23   # one fp32 rounding (half an ulp, relative); one fp32 ulp
+
+
+def guarded3(vals, pad_rows, ld, fill, dtype, device="cpu"):
+    """[B, R + pad_rows, ld] holding `fill`, with vals [B, R, D] at [:, :R, :D]: row stride ld > D and a padded batch stride.
+    Returns (buffer, the [B, R, D] view)."""
+    B, R, D = vals.shape
+    buf = torch.full((B, R + pad_rows, ld), fill, dtype=dtype)
+    buf[:, :R, :D] = vals.to(dtype)
+    buf = buf.to(device)
+    return buf, buf[:, :R, :D]
+
+
+def outside3_is(buf, R, D, fill):
+    """True when everything of the 3-D buffer outside [:, :R, :D] still holds `fill` exactly."""
+    m = torch.ones(buf.shape, dtype=torch.bool, device=buf.device)
+    m[:, :R, :D] = False
+    rest = buf[m]
+    return same_bits(rest, torch.full_like(rest, fill))
+
+
+def ulp_e4m3(t):
+    """The spacing of the e4m3 grid at t (fp64): 2^(max(floor(log2 |t|), -6) - 3). Three mantissa bits; below 2^-6 the grid is the
+    subnormal one, spacing 2^-9 (also at 0)."""
+    a = t.double().abs().clamp_min(2.0 ** -6)
+    return torch.exp2(torch.floor(torch.log2(a)).clamp_min(-6.0) - 3.0)
+
+
+def e4m3_finite(q):
+    """True when no byte of the e4m3 tensor is a NaN pattern (0x7f / 0xff); e4m3fn has no infinity, so every other byte is
+    finite with |value| <= 448."""
+    return not bool(((q.view(torch.uint8) & 0x7F) == 0x7F).any())
+
+
+def fold_zero(b):
+    """e4m3 bytes with -0 (0x80) folded onto +0."""
+    b = b.view(torch.uint8)
+    return torch.where(b == 0x80, torch.zeros_like(b), b)
+
+
+def ln_depth(D):
+    """Additions an element's value goes through in layernorm_mod_kernel's row sums: a lane adds the 8 values of each of its chunks
+    in sequence (at most ceil(D / 512) chunks hold columns < D for a lane), then six butterfly levels, then the division by D, and
+    one more for the product or subtraction that made the addend. D / 64 + 8 where D is a multiple of 512."""
+    return 8 * ((D + 511) // 512) + 8
+
+
+def layernorm_ref(x, shift, scale, eps=1e-6, mean_div=None):
+    """fp64 LayerNorm (no affine, biased variance) + modulation of x [B, R, D] with shift / scale [B, D] or None:
+        y = (x - mean) rstd (1 + scale) + shift.
+    Returns (y, by): by bounds the kernel's fp32 evaluation of the element (everything but the rounding of the output), to first
+    order, with u = 2^-24 and k = ln_depth(D):
+      em = k u mean|x|                                      the row mean (summation depth k, relative to the sum of |x|)
+      ev = (k + 4) u var + 2 em mean|x - mean| + em^2       the variance: its own sum, the squares of d = x - mean each carrying
+                                                            em + u |d|
+      er = rstd (ev / (2 (var + eps)) + 2 u + 2^-22)        rsqrtf(var / D + eps): its argument's error halved, the division and
+                                                            the sum with eps, and 2 ulp for the device's rsqrtf (its documented
+                                                            accuracy is 1 ulp)
+      by = ((em + u |d|) rstd + |d| er) |1 + scale| + 8 u (|d| rstd |1 + scale| + |shift|)
+    the last term the element's own operations (subtraction, two products, 1 + scale, the sum with shift).
+    mean_div: divide the row sum by this instead of D — a deliberately wrong reference for the tests of the bound itself."""
+    xd = x.double()
+    D = xd.shape[-1]
+    mean = xd.sum(-1, keepdim=True) / (D if mean_div is None else mean_div)
+    d = xd - mean
+    var = (d * d).mean(-1, keepdim=True)
+    rstd = 1.0 / torch.sqrt(var + eps)
+    s1 = torch.ones(xd.shape[0], 1, D, dtype=F64) if scale is None else 1.0 + scale.double()[:, None, :]
+    sh = torch.zeros(xd.shape[0], 1, D, dtype=F64) if shift is None else shift.double()[:, None, :]
+    y = d * rstd * s1 + sh
+    k = ln_depth(D)
+    em = k * U24 * xd.abs().mean(-1, keepdim=True)
+    ev = (k + 4) * U24 * var + 2 * em * d.abs().mean(-1, keepdim=True) + em * em
+    er = rstd * (ev / (2 * (var + eps)) + 2 * U24 + 2.0 ** -22)
+    by = ((em + U24 * d.abs()) * rstd + d.abs() * er) * s1.abs() + 8 * U24 * (d.abs() * rstd * s1.abs() + sh.abs())
+    return y, by
+
+
+def ln_case(B, R, D, dtype, seed):
+    """Data of one LayerNorm case, on the CPU: x [B, R, D] in `dtype` (rows 3 randn + 0.5; row (0, 1) = 100 + randn, where a
+    one-pass variance fails; row (0, 3) constant, variance 0; row (1, 2) randn with one element 50 in the last 8 columns), and the
+    modulation table [B, 2 D + 8] fp32, NaN except shift at columns 4 .. 4 + D and scale behind it (chunk views, mod_ld != D).
+    Returns (x, table, shift view, scale view)."""
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(B, R, D, generator=g) * 3 + 0.5
+    x[0, 1] = 100 + torch.randn(D, generator=g)
+    x[0, 3] = 1.7
+    x[1, 2] = torch.randn(D, generator=g)
+    x[1, 2, D - 3] = 50.0
+    table = torch.full((B, 2 * D + 8), NAN, dtype=F32)
+    table[:, 4 : 4 + D] = torch.randn(B, D, generator=g)
+    table[:, 4 + D : 4 + 2 * D] = torch.randn(B, D, generator=g) * 0.5
+    return x.to(dtype), table, table[:, 4 : 4 + D], table[:, 4 + D : 4 + 2 * D]
+
+
+# rt_qk_norm_rope8, in units of 2^-23 relative to |a cos| + |b sin| (a, b the pair's normalised values): the sum of 128 squares is 8
+# sequential + 4 butterfly additions of rounded products, 13 roundings of 2^-24 on a sum of positive terms; the fma with eps one
+# more; rsqrt halves that relative error: 7 x 2^-24. Two multiplications per value (by r, by the weight): 2 x 2^-24. The rotation:
+# the inner product, the fma and the other operand's share: 3 x 2^-24. 12 x 2^-24 = 6 x 2^-23. The device rsqrtf's own error is
+# not in this count.
+QK_COUNTED = 6.0
+
+
+def qk_norm_rope_ref(x, w_txt, w_img, T, cos, sin, eps=1e-6, txt_rows=None):
+    """fp64 q or k RMSNorm + interleaved-pair RoPE of x [B, S, H, 128] (values as the kernel reads them): rows s < T with w_txt, the
+    others with w_img; n = x rsqrt(mean(x^2) + eps) w; pair (n0, n1) -> (n0 c - n1 s, n1 c + n0 s) with the row's cos / sin [S, 128].
+    Returns (ref, mag): mag = |a cos| + |b sin| of the element, what the fp32 evaluation's error is relative to.
+    txt_rows: rows < txt_rows take the text weights instead of rows < T — a deliberately wrong reference for the tests of the bound."""
+    xd = x.double()
+    B, S, H, Dh = xd.shape
+    tr = T if txt_rows is None else txt_rows
+    w = torch.empty(S, Dh, dtype=F64)
+    if tr > 0:
+        w[:tr] = w_txt.double()
+    w[tr:] = w_img.double()
+    n = xd * torch.rsqrt((xd * xd).mean(-1, keepdim=True) + eps) * w[None, :, None, :]
+    c, s = cos.double()[None, :, None, :], sin.double()[None, :, None, :]
+    pr = n.reshape(B, S, H, Dh // 2, 2)
+    n0, n1 = pr[..., 0], pr[..., 1]
+    cp, sp = c.reshape(1, S, 1, Dh // 2, 2), s.reshape(1, S, 1, Dh // 2, 2)
+    ref = torch.stack([n0 * cp[..., 0] - n1 * sp[..., 0], n1 * cp[..., 1] + n0 * sp[..., 1]], dim=-1).reshape(B, S, H, Dh)
+    mag = torch.stack([(n0 * cp[..., 0]).abs() + (n1 * sp[..., 0]).abs(), (n1 * cp[..., 1]).abs() + (n0 * sp[..., 1]).abs()],
+                      dim=-1).reshape(B, S, H, Dh)
+    return ref, mag
+
+
+QK_EPS = 1e-6
+
+
+def _orc():
+    from oracle import flux_oracle
+
+    return flux_oracle
+
+
+def qk_weights(seed):
+    """bf16 norm weights far apart — wq_txt ~ 1, wk_txt ~ -0.5, wq_img ~ 2, wk_img ~ -1.5, each +- 0.1 — so that a row normalised
+    with the wrong set is off by O(1) at its own element."""
+    g = torch.Generator().manual_seed(seed)
+    return [(c + 0.1 * torch.randn(128, generator=g)).to(BF16) for c in (1.0, -0.5, 2.0, -1.5)]
+
+
+def qk_tables(S, T, pos0=0):
+    """cos / sin [S, 128] from the oracle's rope_table on real ids: text rows at id 0, image rows from latent_image_ids (+ pos0 on
+    both axes, so that the angles are not small)."""
+    n = S - T
+    img = _orc().latent_image_ids(2 * 10, 2 * ((n + 9) // 10))[:n] if n > 0 else torch.zeros(0, 3)
+    img = img.clone()
+    img[:, 1:] += pos0
+    return _orc().rope_table(torch.cat([torch.zeros(T, 3), img], dim=0))
+
+
+def qk_layout(single, d):
+    """(q_off, k_off, ld): the double blocks' q | k | v buffer, or the single blocks' k | v | q | mlp one."""
+    return (2 * d, 0, 7 * d + 8) if single else (0, d, 3 * d + 8)
+
+
+def quant_rows_rule(x, skip_cols=None):
+    """The row-quantisation rule in the kernel's own fp32 arithmetic on the CPU, x [rows, D] (values as the kernel reads them):
+    scale = fp32(amax * fp32(1 / 448)), 1.0 for an all-zero row; q = e4m3(clamp(x * fp32(1 / scale), +-448)), round to nearest even.
+    The clamp comes first: torch's CPU cast gives NaN above 464. Returns (q e4m3, scale fp32).
+    skip_cols = (c0, c1): those columns are left out of the row maximum — a deliberately wrong rule for the tests of the checks."""
+    x = x.float()
+    a = x.abs()
+    if skip_cols is not None:
+        a = a.clone()
+        a[:, skip_cols[0] : skip_cols[1]] = 0
+    amax = a.amax(dim=1)
+    sc = torch.where(amax > 0, amax * (1.0 / 448.0), torch.ones_like(amax))
+    y = (x * (1.0 / sc)[:, None]).clamp(-448.0, 448.0)
+    return y.to(FP8), sc
+
+
+def check_quant_rows(what, q, scale, x):
+    """q e4m3 [rows, D] and scale fp32 [rows] from a row quantiser against x [rows, D] (values as read). Every byte finite, and with
+    t = x / scale in fp64:
+        |q - t| <= ulp_e4m3(t) / 2 + 2^-21 |t|
+    the first term the rounding to the e4m3 grid, the second the fp32 reciprocal and product (three roundings, one of them possibly
+    a whole ulp). t is not clamped: with the right scale it passes 448 by the second term at most, and a row maximum the scale
+    missed shows as |t| far above 448 against a saturated byte."""
+    assert e4m3_finite(q), f"{what}: NaN byte"
+    qv = q.float().double()
+    t = x.double() / scale.double()[:, None]
+    return check_bound(what, qv, t, 0.5 * ulp_e4m3(t) + 2.0 ** -21 * t.abs())
+
+
+def vt8_key_order():
+    """Key (inside a 64-key tile) at each of the 64 positions of a row of the e4m3 V^T, from the layout comment at the top of
+    csrc/attention_fp8.hip: position p = 32 hh + 16 kt + 4 g + e holds key 32 kt + 8 g + 4 hh + e."""
+    key = torch.empty(64, dtype=torch.long)
+    for hh in range(2):
+        for kt in range(2):
+            for g in range(4):
+                for e in range(4):
+                    key[32 * hh + 16 * kt + 4 * g + e] = 32 * kt + 8 * g + 4 * hh + e
+    return key
+
+
+def vt8_expected(v, swap=None):
+    """uint8 [B, H, 128, S64] (S64 = S rounded up to 64): byte [b][h][dd][64 t + p] = e4m3(clamp(v[b][64 t + key(p)][h][dd], +-448)),
+    zero for keys >= S. v [B, S, H, 128], values as the kernel reads them. -0 folded onto +0.
+    swap = (p0, p1): those two positions of every tile exchanged — a deliberately wrong layout for the tests of the comparison."""
+    B, S, H, Dh = v.shape
+    S64 = (S + 63) // 64 * 64
+    v8 = torch.zeros(B, S64, H, Dh, dtype=torch.uint8)
+    v8[:, :S] = v.float().clamp(-448.0, 448.0).to(FP8).view(torch.uint8)
+    order = vt8_key_order()
+    if swap is not None:
+        order = order.clone()
+        order[[swap[0], swap[1]]] = order[[swap[1], swap[0]]]
+    idx = (torch.arange(S64 // 64)[:, None] * 64 + order[None, :]).reshape(-1)
+    return fold_zero(v8[:, idx].permute(0, 2, 3, 1).contiguous())

@@ -105,6 +105,33 @@ def test_layernorm_pair_and_add_rows_reject_bad_arguments():
     assert lib.rt_add_rows_f32(0x1000, 0x2000, 0x3008, 28, 1, 3072, None) == ALIGN
 
 
+def test_qk_norm_entries_reject_misaligned_norm_weights():
+    """rt_qk_rmsnorm_rope and rt_attention_fp8_prep load all four norm weights as 16-byte vectors: the image weights always, the text
+    weights when T > 0. A weight that is not 16-byte aligned is refused with RT_E_ALIGN before anything is queued; with T = 0 the text
+    weights are not looked at. Made-up pointers, never dereferenced."""
+    _, lib = _lib()
+    buf, cos, sin, qk8, vt8 = 0x10000, 0x20000, 0x30000, 0x40000, 0x50000
+    W = dict(wq_txt=0x1000, wk_txt=0x1100, wq_img=0x1200, wk_img=0x1300)
+
+    def norm(T=8, **kw):
+        w = dict(W, **kw)
+        return lib.rt_qk_rmsnorm_rope(buf, 392, 392 * 16, 0, 128, w["wq_txt"], w["wk_txt"], w["wq_img"], w["wk_img"], cos, sin, 1, 16, T, 1, 1e-6, None)
+
+    def prep(T=8, **kw):
+        w = dict(W, **kw)
+        return lib.rt_attention_fp8_prep(buf, 392, 392 * 16, 0, 128, 256, w["wq_txt"], w["wk_txt"], w["wq_img"], w["wk_img"], cos, sin, qk8, vt8,
+                                         1, 16, T, 1, 1e-6, None)
+
+    for call in (norm, prep):
+        for name in W:
+            assert call(**{name: W[name] + 8}) == ALIGN, (call.__name__, name)
+            assert call(**{name: W[name] + 2}) == ALIGN, (call.__name__, name)
+        assert call(wq_txt=None) == BADARG and call(wk_txt=None) == BADARG           # T > 0 needs them
+        assert call(T=0, wq_img=W["wq_img"] + 8) == ALIGN and call(T=0, wk_img=W["wk_img"] + 8) == ALIGN
+    # Only refusals are exercised: every call above returns before the launch. That T = 0 accepts text weights of any alignment (or
+    # none) is what the T = 0 cases of test_token_passes_gpu.py and test_e4m3_producers_gpu.py run, with real buffers.
+
+
 def test_rope_fields_layout_and_rejections(tmp_path):
     """rt_gemm_group's fused q/k fields: offsets against the header; all-zero = no fused step; bad descriptions are rejected."""
     native, lib = _lib()
