@@ -414,51 +414,67 @@ __device__ __forceinline__ float repaint_blend(float r, float src, float noise, 
   return (1.0f - m) * keep + m * r;
 }
 
-template <bool CFG, bool REPAINT>
+// MULTI (the second-order multistep form, scheduler.FlowMatchMultistepScheduler): h holds the velocity of the step before, and
+//   v2 = w != 0 ? v + w·(v − h) : v;   r = x + ds·v2;   h = v
+// w is a kernel scalar, so the branch is uniform: with w = 0 (the first step of a run) h is written and never read — it may be
+// uninitialised memory — and r is the text of the form without MULTI, the same bits.
+template <bool CFG, bool REPAINT, bool MULTI>
 __device__ __forceinline__ float master_step_element(float x, float u, float t, float src, float noise, float m, float s, float ds,
-                                                     float sn) {
+                                                     float sn, float w, float& h) {
   const float v = CFG ? u + s * (t - u) : u;
-  const float r = x + ds * v;
+  float v2 = v;
+  if (MULTI) {
+    if (w != 0.0f) v2 = v + w * (v - h);
+    h = v;
+  }
+  const float r = x + ds * v2;
   return REPAINT ? repaint_blend(r, src, noise, m, sn) : r;
 }
 
 // n4 groups of four elements with 16-byte loads and stores (8-byte ones for bf16), then the elements from 4·n4 on one at a time:
 // the up to three left over, or all of them — the host sets n4 = 0 where a pointer is not aligned or a group could straddle the
-// mask's period (n_mask < n and no multiple of 4). m = mask[i % n_mask]; t is read only under CFG, src / noise / mask only under REPAINT.
-template <bool CFG, bool REPAINT>
+// mask's period (n_mask < n and no multiple of 4). m = mask[i % n_mask]; t is read only under CFG, src / noise / mask only under
+// REPAINT, hist only under MULTI (read where w != 0, always written), in the groups and by the tail rules of x.
+template <bool CFG, bool REPAINT, bool MULTI>
 __global__ void master_step_f32_kernel(float* __restrict__ x, const bf16_t* __restrict__ u, const bf16_t* __restrict__ t,
                                        bf16_t* __restrict__ xb, const float* __restrict__ src, const float* __restrict__ noise,
-                                       const float* __restrict__ mask, float s, float ds, float sn, int64_t n, int64_t n_mask,
-                                       int64_t n4) {
+                                       const float* __restrict__ mask, float* __restrict__ hist, float s, float ds, float sn, float w,
+                                       int64_t n, int64_t n_mask, int64_t n4) {
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
   for (int64_t g = tid; g < n4; g += nthr) {
     const f32x4 xv = reinterpret_cast<const f32x4*>(x)[g];
     const u32x2 uv = reinterpret_cast<const u32x2*>(u)[g];
     u32x2 tv = uv;
     if (CFG) tv = reinterpret_cast<const u32x2*>(t)[g];
-    f32x4 sv = xv, nv = xv, mv = xv;      // like tv: placeholders that the helper ignores without REPAINT
+    f32x4 sv = xv, nv = xv, mv = xv, hv = xv;      // like tv: placeholders that the helper ignores without REPAINT / MULTI
     if (REPAINT) {
       sv = reinterpret_cast<const f32x4*>(src)[g];
       nv = reinterpret_cast<const f32x4*>(noise)[g];
       mv = *reinterpret_cast<const f32x4*>(mask + (g * 4) % n_mask);
     }
+    if (MULTI && w != 0.0f) hv = reinterpret_cast<const f32x4*>(hist)[g];
     f32x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float a = (j & 1) ? bf16hi(uv[j >> 1]) : bf16lo(uv[j >> 1]);
       const float b = (j & 1) ? bf16hi(tv[j >> 1]) : bf16lo(tv[j >> 1]);
-      o[j] = master_step_element<CFG, REPAINT>(xv[j], a, b, sv[j], nv[j], mv[j], s, ds, sn);
+      float h = hv[j];
+      o[j] = master_step_element<CFG, REPAINT, MULTI>(xv[j], a, b, sv[j], nv[j], mv[j], s, ds, sn, w, h);
+      hv[j] = h;
     }
     reinterpret_cast<f32x4*>(x)[g] = o;
     if (xb) reinterpret_cast<u32x2*>(xb)[g] = u32x2{pack_bf16x2(o[0], o[1]), pack_bf16x2(o[2], o[3])};
+    if (MULTI) reinterpret_cast<f32x4*>(hist)[g] = hv;
   }
   for (int64_t i = n4 * 4 + tid; i < n; i += nthr) {
     const float a = bf16_to_f32(u[i]), b = CFG ? bf16_to_f32(t[i]) : a;
-    float sv = 0.0f, nv = 0.0f, mv = 0.0f;
+    float sv = 0.0f, nv = 0.0f, mv = 0.0f, h = 0.0f;
     if (REPAINT) { sv = src[i]; nv = noise[i]; mv = mask[i % n_mask]; }
-    const float o = master_step_element<CFG, REPAINT>(x[i], a, b, sv, nv, mv, s, ds, sn);
+    if (MULTI && w != 0.0f) h = hist[i];
+    const float o = master_step_element<CFG, REPAINT, MULTI>(x[i], a, b, sv, nv, mv, s, ds, sn, w, h);
     x[i] = o;
     if (xb) xb[i] = f32_to_bf16(o);
+    if (MULTI) hist[i] = h;
   }
 }
 
@@ -773,17 +789,23 @@ int rt_rope_table(const float* ids, float* cos_out, float* sin_out, int32_t S, c
   return rt_hip_status();
 }
 
-// The one launcher of master_step_f32_kernel: v_text selects CFG, mask selects REPAINT (src and noise come with it). The 16-byte path
-// needs every pointer that is present aligned for its access and, with a mask, no group of four across the mask's period.
+// The one launcher of master_step_f32_kernel: v_text selects CFG, mask selects REPAINT (src and noise come with it), hist selects
+// MULTI. The 16-byte path needs every pointer that is present aligned for its access and, with a mask, no group of four across the
+// mask's period.
 static int launch_master_step_f32(float* x, const void* v, const void* v_text, void* x_bf16, const float* src, const float* noise,
-                                  const float* mask, float s, float ds, float sn, int64_t n, int64_t n_mask, void* stream) {
+                                  const float* mask, float* hist, float s, float ds, float sn, float w, int64_t n, int64_t n_mask,
+                                  void* stream) {
   const bool vec = RT_ALIGNED(x, 16) && RT_ALIGNED(v, 8) && (!v_text || RT_ALIGNED(v_text, 8)) && (!x_bf16 || RT_ALIGNED(x_bf16, 8)) &&
-                   (!mask || ((n_mask % 4 == 0 || n_mask == n) && RT_ALIGNED(src, 16) && RT_ALIGNED(noise, 16) && RT_ALIGNED(mask, 16)));
+                   (!mask || ((n_mask % 4 == 0 || n_mask == n) && RT_ALIGNED(src, 16) && RT_ALIGNED(noise, 16) && RT_ALIGNED(mask, 16))) &&
+                   (!hist || RT_ALIGNED(hist, 16));
   const int64_t n4 = vec ? n / 4 : 0;
-  const auto kernel = mask ? (v_text ? master_step_f32_kernel<true, true> : master_step_f32_kernel<false, true>)
-                           : (v_text ? master_step_f32_kernel<true, false> : master_step_f32_kernel<false, false>);
+  const auto plain = mask ? (v_text ? master_step_f32_kernel<true, true, false> : master_step_f32_kernel<false, true, false>)
+                          : (v_text ? master_step_f32_kernel<true, false, false> : master_step_f32_kernel<false, false, false>);
+  const auto multi = mask ? (v_text ? master_step_f32_kernel<true, true, true> : master_step_f32_kernel<false, true, true>)
+                          : (v_text ? master_step_f32_kernel<true, false, true> : master_step_f32_kernel<false, false, true>);
+  const auto kernel = hist ? multi : plain;
   hipLaunchKernelGGL(kernel, dim3(grid_for(n4 > 0 ? n4 : n, 256)), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)v,
-                     (const bf16_t*)v_text, (bf16_t*)x_bf16, src, noise, mask, s, ds, sn, n, n_mask, n4);
+                     (const bf16_t*)v_text, (bf16_t*)x_bf16, src, noise, mask, hist, s, ds, sn, w, n, n_mask, n4);
   return rt_hip_status();
 }
 
@@ -802,20 +824,28 @@ int rt_euler_step(void* x, const void* v, float dsigma, int64_t n, void* stream)
 
 int rt_euler_step_f32(float* x, const void* v, void* x_bf16, float dsigma, int64_t n, void* stream) {
   if (!x || !v || n < 1) return RT_E_BADARG;
-  return launch_master_step_f32(x, v, nullptr, x_bf16, nullptr, nullptr, nullptr, 0.0f, dsigma, 0.0f, n, n, stream);
+  return launch_master_step_f32(x, v, nullptr, x_bf16, nullptr, nullptr, nullptr, nullptr, 0.0f, dsigma, 0.0f, 0.0f, n, n, stream);
 }
 
 int rt_cfg_euler_step_f32(float* x, const void* v_uncond, const void* v_text, void* x_bf16, float s, float dsigma, int64_t n,
                           void* stream) {
   if (!x || !v_uncond || !v_text || n < 1) return RT_E_BADARG;
-  return launch_master_step_f32(x, v_uncond, v_text, x_bf16, nullptr, nullptr, nullptr, s, dsigma, 0.0f, n, n, stream);
+  return launch_master_step_f32(x, v_uncond, v_text, x_bf16, nullptr, nullptr, nullptr, nullptr, s, dsigma, 0.0f, 0.0f, n, n, stream);
 }
 
 int rt_repaint_euler_step_f32(float* x, const void* v, const void* v_text, void* x_bf16, const float* src, const float* noise,
                               const float* mask, float s, float dsigma, float sigma_next, int64_t n, int64_t n_mask, void* stream) {
   if (!x || !v || !src || !noise || !mask || n < 1 || n_mask < 1) return RT_E_BADARG;
   if (n % n_mask) return RT_E_SHAPE;
-  return launch_master_step_f32(x, v, v_text, x_bf16, src, noise, mask, s, dsigma, sigma_next, n, n_mask, stream);
+  return launch_master_step_f32(x, v, v_text, x_bf16, src, noise, mask, nullptr, s, dsigma, sigma_next, 0.0f, n, n_mask, stream);
+}
+
+int rt_multistep_step_f32(float* x, const void* v, const void* v_text, void* x_bf16, float* hist, float w, const float* src,
+                          const float* noise, const float* mask, float s, float dsigma, float sigma_next, int64_t n, int64_t n_mask,
+                          void* stream) {
+  if (!x || !v || !hist || n < 1 || n_mask < 1 || (mask && (!src || !noise))) return RT_E_BADARG;
+  if (n % n_mask) return RT_E_SHAPE;
+  return launch_master_step_f32(x, v, v_text, x_bf16, src, noise, mask, hist, s, dsigma, sigma_next, w, n, n_mask, stream);
 }
 
 int rt_cfg_mix(const void* v_uncond, const void* v_text, void* out, float s, int64_t n, void* stream) {

@@ -689,10 +689,14 @@ def euler_step_(x: torch.Tensor, v: torch.Tensor, dsigma: float) -> torch.Tensor
 
 def _master_step_f32(name: str, x32: torch.Tensor, v: torch.Tensor, v_text: Optional[torch.Tensor], s: float, dsigma: float,
                      x_bf16: Optional[torch.Tensor], sigma_next: float = 0.0, src32: Optional[torch.Tensor] = None,
-                     noise32: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """The body of euler_step_f32_ / cfg_euler_step_f32_ / repaint_euler_step_f32_ (``name``, for the messages): the checks, and the
-    entry that what is given selects. One fp32 master step x32 += dsigma·vel, vel = v or v + s·(v_text − v); with a mask, the blend."""
-    like = [t for t in (v, v_text, src32, noise32) if t is not None]
+                     noise32: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None,
+                     w: float = 0.0) -> torch.Tensor:
+    """The body of euler_step_f32_ / cfg_euler_step_f32_ / repaint_euler_step_f32_ / multistep_step_f32_ (``name``, for the messages):
+    the checks, and the entry that what is given selects. One fp32 master step x32 += dsigma·vel, vel = v or v + s·(v_text − v); with a
+    mask, the blend; with ``hist`` (the fp32 velocity of the step before, replaced by this step's), vel + w·(vel − hist) in vel's place."""
+    if hist is not None and mask is not None and (src32 is None or noise32 is None):
+        raise ValueError(f"{name}: a mask needs src32 and noise32")
+    like = [t for t in (v, v_text, src32, noise32, hist) if t is not None]
     if not all(t.is_contiguous() for t in [x32, *like] + ([] if mask is None else [mask])) or not all(t.shape == x32.shape for t in like):
         raise ValueError(f"{name}: contiguous tensors of equal shape")
     if x_bf16 is not None and (x_bf16.shape != x32.shape or not x_bf16.is_contiguous()):
@@ -700,7 +704,11 @@ def _master_step_f32(name: str, x32: torch.Tensor, v: torch.Tensor, v_text: Opti
     if mask is not None and mask.shape != x32.shape and not (x32.dim() > 1 and tuple(mask.shape) == (1,) + tuple(x32.shape[1:])):
         raise ValueError(f"{name}: mask {tuple(mask.shape)} is neither x32's shape {tuple(x32.shape)} nor that of one sample")
     x, xb, n = _dev(x32, "x32", F32), _opt(x_bf16, "x_bf16", BF16), x32.numel()
-    if mask is not None:
+    if hist is not None:
+        native.call("rt_multistep_step_f32", x, _dev(v, "v", BF16), _opt(v_text, "v_text", BF16), xb, _dev(hist, "hist", F32), float(w),
+                    _opt(src32 if mask is not None else None, "src32", F32), _opt(noise32 if mask is not None else None, "noise32", F32),
+                    _opt(mask, "mask", F32), float(s), float(dsigma), float(sigma_next), n, n if mask is None else mask.numel(), _stream())
+    elif mask is not None:
         native.call("rt_repaint_euler_step_f32", x, _dev(v, "v", BF16), _opt(v_text, "v_text", BF16), xb, _dev(src32, "src32", F32),
                     _dev(noise32, "noise32", F32), _dev(mask, "mask", F32), float(s), float(dsigma), float(sigma_next), n, mask.numel(), _stream())
     elif v_text is not None:
@@ -727,6 +735,15 @@ def repaint_euler_step_f32_(x32: torch.Tensor, v: torch.Tensor, v_text: Optional
     repaint: x32 = (1 − m)·((1 − sigma_next)·src + sigma_next·noise) + m·(x32 + dsigma·vel); optionally refreshes the bf16 copy.
     ``mask`` has x32's shape, or a leading 1 where x32 has its batch: one mask for every sample."""
     return _master_step_f32("repaint_euler_step_f32_", x32, v, v_text, s, dsigma, x_bf16, sigma_next, src32, noise32, mask)
+
+
+def multistep_step_f32_(x32: torch.Tensor, v: torch.Tensor, hist32: torch.Tensor, w: float, dsigma: float,
+                        x_bf16: Optional[torch.Tensor] = None, *, v_text: Optional[torch.Tensor] = None, s: float = 0.0, sigma_next: float = 0.0,
+                        src32: Optional[torch.Tensor] = None, noise32: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The second-order multistep form of the fp32 master step: x32 += dsigma·(vel + w·(vel − hist32)) and hist32 = vel, with vel, the
+    blend under ``mask`` and the bf16 copy as in the three steps above. ``w`` = 0: hist32 is written and not read (it may be
+    uninitialised) and x32 gets the bits of the step above that the other arguments select."""
+    return _master_step_f32("multistep_step_f32_", x32, v, v_text, s, dsigma, x_bf16, sigma_next, src32, noise32, mask, hist32, w)
 
 
 def cfg_mix(v_uncond: torch.Tensor, v_text: torch.Tensor, s: float) -> torch.Tensor:

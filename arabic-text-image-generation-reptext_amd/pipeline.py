@@ -28,7 +28,7 @@ import torch.nn.functional as F
 from . import ops
 from .controlnet import FluxControlNetModel, FluxMultiControlNetModel, active_row_window
 from .image_processor import PipelineImageInput, VaeImageProcessor
-from .scheduler import FlowMatchEulerDiscreteScheduler, calculate_shift
+from .scheduler import FlowMatchEulerDiscreteScheduler, FlowMatchMultistepScheduler, calculate_shift
 from .transformer import FluxTransformer2DModel
 from .utils import randn_tensor
 from .vae import AutoencoderKL
@@ -286,13 +286,22 @@ class FluxControlNetPipeline:
         for required in ("transformer", "vae"):
             if required not in kwargs and not (listed(required) and os.path.isdir(os.path.join(root, required))):
                 raise OSError(f"{cls.__name__}.from_pretrained: component '{required}' is neither passed nor present under {root}")
-        sched_cfg = {}
+        sched_cfg, sched_name = {}, None
         sp = os.path.join(root, "scheduler", "scheduler_config.json")
         if os.path.isfile(sp):
             with open(sp) as f:
-                sched_cfg = {k: v for k, v in json.load(f).items() if not k.startswith("_")}
-        known = set(FlowMatchEulerDiscreteScheduler().config.keys())
-        scheduler = kwargs.pop("scheduler", None) or FlowMatchEulerDiscreteScheduler(**{k: v for k, v in sched_cfg.items() if k in known})
+                saved = json.load(f)
+            sched_cfg, sched_name = {k: v for k, v in saved.items() if not k.startswith("_")}, saved.get("_class_name")
+        # the file's _class_name picks one of the two schedulers; any other name (a diffusers scheduler this package does not have)
+        # keeps the Euler class with the keys it knows
+        sched_cls = {c.__name__: c for c in (FlowMatchEulerDiscreteScheduler, FlowMatchMultistepScheduler)}.get(sched_name)
+        if sched_cls is None:
+            if sched_name is not None and "scheduler" not in kwargs:
+                import sys
+                print(f"[reptext_amd] scheduler class {sched_name!r} is not available; using FlowMatchEulerDiscreteScheduler", file=sys.stderr, flush=True)
+            sched_cls = FlowMatchEulerDiscreteScheduler
+        known = set(sched_cls().config.keys())
+        scheduler = kwargs.pop("scheduler", None) or sched_cls(**{k: v for k, v in sched_cfg.items() if k in known})
         transformer = kwargs.pop("transformer", None) or FluxTransformer2DModel.from_pretrained(root, torch_dtype=dt, subfolder="transformer")
         vae = kwargs.pop("vae", None) or AutoencoderKL.from_pretrained(root, torch_dtype=dt, subfolder="vae")
         te, te2 = kwargs.pop("text_encoder", None), kwargs.pop("text_encoder_2", None)
@@ -354,8 +363,8 @@ class FluxControlNetPipeline:
                 index[name] = [None, None]
         os.makedirs(os.path.join(root, "scheduler"), exist_ok=True)
         with open(os.path.join(root, "scheduler", "scheduler_config.json"), "w") as f:
-            json.dump(dict(_class_name="FlowMatchEulerDiscreteScheduler", **dict(self.scheduler.config)), f, indent=2)
-        index["scheduler"] = ["reptext_amd", "FlowMatchEulerDiscreteScheduler"]
+            json.dump(dict(_class_name=type(self.scheduler).__name__, **dict(self.scheduler.config)), f, indent=2)
+        index["scheduler"] = ["reptext_amd", type(self.scheduler).__name__]
         with open(os.path.join(root, "model_index.json"), "w") as f:
             json.dump(index, f, indent=2)
 
@@ -1098,6 +1107,13 @@ class FluxControlNetPipeline:
             # source, noise and mask are three more static inputs; the sigmas the blend re-noises to are in the key already
             key += (("repaint", sig(repaint.src32), sig(repaint.noise32), sig(repaint.mask)),)
             ins.update(repaint_src=repaint.src32, repaint_noise=repaint.noise32, repaint_mask=repaint.mask)
+        solver_order = getattr(self.scheduler, "solver_order", 1)
+        if solver_order > 1:
+            # the multistep weights are kernel scalars of every step, fixed by the sigmas and the timesteps that are in the key already;
+            # the velocity history is allocated inside the capture, in the graph's pool, like the fp32 state
+            key += (("solver", solver_order),)
+        # host state of a multistep scheduler (whether its history holds a velocity): a capture must not move it, a replay leaves it full
+        history_len = self.scheduler._history_len if solver_order > 1 else None
         cache = self.__dict__.setdefault("_graph_cache", {})
         ent = cache.get(key)
         if ent is None:                                      # first sight of this signature: eager (and warm), remember it
@@ -1142,12 +1158,16 @@ class FluxControlNetPipeline:
                     self._sample_cache[3][0] = None                              # and so was a zero fill of the sample buffers
                 torch.cuda.synchronize()
                 self.scheduler._step_index = step_index
+                if history_len is not None:
+                    self.scheduler._history_len = history_len
                 return eager()
             _mm.CAPTURE_KEEP = ops.CAPTURE_KEEP = None
             keep.append(getattr(self, "_sample_cache", None))
             keep.extend(dict(m._rope_cache) for m in (self.transformer, self.controlnet, union and union.model)
                         if m is not None and hasattr(m, "_rope_cache"))
             self.scheduler._step_index = step_index
+            if history_len is not None:
+                self.scheduler._history_len = history_len
             # the sample buffers the capture wrote into and the window its zero-linears were restricted to (None: every row)
             ent = cache[key] = {"graph": graph, "static": static, "out": out, "out32": out32, "keep": keep,
                                 "samples": getattr(self, "_sample_cache", None), "window": self._sample_promise}
@@ -1159,6 +1179,8 @@ class FluxControlNetPipeline:
         # what the eager loop's step() calls leave behind: they start at the begin index, if one is set
         first = self.scheduler._step_index if self.scheduler._step_index is not None else (self.scheduler._begin_index or 0)
         self.scheduler._step_index = first + len(tvals)
+        if history_len is not None and len(tvals) > 0:
+            self.scheduler._history_len = 1                 # the history (the graph's own) holds the last step's velocity
         self._master_latents = ent["out32"].clone()
         with self.progress_bar(total=num_inference_steps) as bar:
             bar.update(num_inference_steps)
@@ -1256,6 +1278,8 @@ class FluxControlNetPipeline:
         # (A.6); not rounding the STATE 28 times keeps the loop close to the fp32 reference path. Callbacks see the bf16 copy.
         lat32 = latents.to(torch.float32).contiguous()
         latents = latents.to(torch.bfloat16).contiguous().clone()
+        # a multistep scheduler's velocity of the step before, fp32 like the state and owned here; its first step does not read it
+        hist = dict(history=torch.empty_like(lat32)) if getattr(self.scheduler, "solver_order", 1) > 1 else {}
         # Tower ∥ transformer: within a step the tower's chain of kernels and the transformer's are independent except that
         # transformer block i consumes tower sample i // 4 (A.3). The tower therefore runs on a side stream into preallocated
         # sample buffers and the transformer waits, block by block, on the event of the sample it needs. At batch 1 most
@@ -1319,13 +1343,15 @@ class FluxControlNetPipeline:
                     noise_pred = extras.velocity(i, noise_pred)
                 cfg = extras.cfg_scale is not None             # then noise_pred is [negative, positive], B each
                 self.scheduler.step_master_(noise_pred[:B] if cfg else noise_pred, lat32, latents, v_text=noise_pred[B:] if cfg else None,
-                                            s=extras.cfg_scale, repaint=extras.repaint)
+                                            s=extras.cfg_scale, repaint=extras.repaint, **hist)
                 if callback is not None:
                     env = {"latents": latents, "prompt_embeds": prompt_embeds}
                     out = callback(self, i, timesteps[i], {k: env[k] for k in callback_inputs})
                     if "latents" in out:
                         latents = out.pop("latents").to(torch.bfloat16).contiguous()
                         lat32 = latents.to(torch.float32)
+                        if hist:
+                            self.scheduler.reset_history()       # the velocity before belongs to the replaced state: first order next
                     if "prompt_embeds" in out:                       # the loop-invariant embeddings are no longer valid
                         prompt_embeds = out.pop("prompt_embeds")
                         static_t = prepare_static(prompt_embeds)

@@ -3,6 +3,9 @@ diffusers (PIPE:18) and drives at PIPE:948-967 (``set_timesteps(sigmas=..., mu=.
 
 Math per SURVEY.md Appendix A.6. The sigma schedule is host-side fp32 (n+1 scalars); ``step`` is one HIP axpy
 (fp32 arithmetic, result rounded once to the sample dtype, as diffusers upcasts inside ``step``).
+
+``FlowMatchMultistepScheduler`` is the same grid with a second-order multistep step (Adams–Bashforth 2 in sigma, ``multistep_weights``):
+one model evaluation per step as before, plus the velocity of the step before in an fp32 buffer.
 """
 from __future__ import annotations
 
@@ -129,6 +132,110 @@ class FlowMatchEulerDiscreteScheduler:
         sigma, sigma_next = self._advance()
         prev = sample.to(model_output.dtype).clone()
         ops.euler_step_(prev, model_output.contiguous(), float(sigma_next - sigma))
+        if not return_dict:
+            return (prev,)
+        return Config(prev_sample=prev)
+
+
+def _multistep_weight(sigmas, i: int) -> float:
+    """w_i = (σ_{i+1} − σ_i) / (2·(σ_i − σ_{i−1})) in float64 from the fp32 table."""
+    a, b, c = float(sigmas[i - 1]), float(sigmas[i]), float(sigmas[i + 1])
+    return (c - b) / (2.0 * (b - a))
+
+
+def multistep_weights(sigmas, begin: int = 0, order: int = 2) -> List[float]:
+    """The weight of every step of the second-order multistep rule (Adams–Bashforth 2 on the sigma grid)
+
+        x_{i+1} = x_i + dσ_i·(v_i + w_i·(v_i − v_{i−1})),   dσ_i = σ_{i+1} − σ_i,   w_i = dσ_i / (2·dσ_{i−1})
+
+    for a run that starts at step ``begin``: that step has no velocity before it and is first order, w = 0 (as are the entries before
+    it, which do not run). ``sigmas``: the n + 1 entries of the scheduler's table; n weights come back, computed in float64 from the
+    table's values. ``order`` 1: all zero, the Euler rule."""
+    if order not in (1, 2):
+        raise ValueError(f"multistep_weights: order {order} is not supported (1 or 2)")
+    n = len(sigmas) - 1
+    return [0.0 if order == 1 or i <= begin else _multistep_weight(sigmas, i) for i in range(n)]
+
+
+class FlowMatchMultistepScheduler(FlowMatchEulerDiscreteScheduler):
+    """The Euler scheduler's grid with a second-order multistep step (``multistep_weights``): one model evaluation per step, as for
+    Euler, plus the velocity of the step before. That velocity lives in an fp32 ``history`` tensor of the state's shape which the
+    CALLER of ``step_master_`` owns (the denoising loop allocates it beside its fp32 state; a captured loop keeps it in the graph's
+    pool); the scheduler holds host state only: whether the history holds a velocity. ``set_timesteps``, ``set_begin_index`` and
+    ``reset_history`` empty it, and the step after is first order. ``solver_order=1`` is the Euler scheduler."""
+    order = 1               # model evaluations per step (the pipelines' progress and warm-up arithmetic), not the solver's order
+
+    def __init__(self, **config):
+        solver_order = int(config.pop("solver_order", 2))
+        if solver_order not in (1, 2):
+            raise ValueError(f"solver_order {solver_order} is not supported (1 or 2)")
+        super().__init__(**config)
+        self.config["solver_order"] = solver_order
+        self._history_len = 0                       # velocities the history holds: 0 or 1
+        self._step_history: Optional[torch.Tensor] = None       # the history of ``step`` (the diffusers contract), fp32
+
+    @classmethod
+    def from_config(cls, config):
+        """From a saved config of this class or of the Euler class; keys of other schedulers are ignored, as the loader ignores them."""
+        known = set(flux_scheduler_config().keys()) | {"solver_order"}
+        return cls(**{k: v for k, v in dict(config).items() if k in known})
+
+    @property
+    def solver_order(self) -> int:
+        return self.config["solver_order"]
+
+    def reset_history(self) -> None:
+        """Forget the velocity of the step before: the next step is first order."""
+        self._history_len = 0
+        self._step_history = None
+
+    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, sigmas: Optional[List[float]] = None,
+                      mu: Optional[float] = None, timesteps: Optional[List[float]] = None):
+        """The Euler scheduler's grid, unchanged (the signature is spelled out: ``retrieve_timesteps`` inspects it); empties the history."""
+        super().set_timesteps(num_inference_steps, device=device, sigmas=sigmas, mu=mu, timesteps=timesteps)
+        self.reset_history()
+
+    def set_begin_index(self, begin_index: int = 0):
+        super().set_begin_index(begin_index)
+        self.reset_history()
+
+    def _advance_weight(self):
+        """``_advance`` plus the weight of the step about to be taken; the history then counts as holding its velocity."""
+        sigma, sigma_next = self._advance()
+        i = self._step_index - 1
+        w = _multistep_weight(self.sigmas, i) if self._history_len > 0 and i > 0 else 0.0
+        self._history_len = 1
+        return sigma, sigma_next, w
+
+    def step_master_(self, v: torch.Tensor, sample32: torch.Tensor, sample_bf16: Optional[torch.Tensor] = None, *,
+                     v_text: Optional[torch.Tensor] = None, s: Optional[float] = None, repaint=None,
+                     history: Optional[torch.Tensor] = None) -> None:
+        """``FlowMatchEulerDiscreteScheduler.step_master_`` with the multistep rule, one kernel: ``history`` (fp32, the state's shape)
+        is read unless it is empty — it may then be uninitialised memory — and receives this step's velocity, under true CFG the mixed
+        one in fp32. The blend of a repaint comes after, as it does there."""
+        if self.solver_order == 1:
+            return super().step_master_(v, sample32, sample_bf16, v_text=v_text, s=s, repaint=repaint)
+        if history is None:
+            raise ValueError("step_master_: the multistep scheduler needs history=, an fp32 tensor of the state's shape")
+        sigma, sigma_next, w = self._advance_weight()
+        v_text = None if v_text is None else v_text.contiguous()
+        rp = {} if repaint is None else dict(src32=repaint.src32, noise32=repaint.noise32, mask=repaint.mask)
+        ops.multistep_step_f32_(sample32, v.contiguous(), history, w, float(sigma_next - sigma), sample_bf16, v_text=v_text,
+                                s=float(s or 0.0), sigma_next=float(sigma_next) if repaint is not None else 0.0, **rp)
+
+    def step(self, model_output: torch.Tensor, timestep: Union[float, torch.Tensor], sample: torch.Tensor,
+             return_dict: bool = True, **unused):
+        if self.solver_order == 1:
+            return super().step(model_output, timestep, sample, return_dict=return_dict)
+        hist = self._step_history if self._history_len > 0 else None
+        if hist is None or hist.shape != sample.shape or hist.device != sample.device:
+            self._history_len = 0
+            hist = torch.empty(sample.shape, dtype=torch.float32, device=sample.device)
+        sigma, sigma_next, w = self._advance_weight()
+        x32 = sample.to(torch.float32).contiguous().clone()
+        ops.multistep_step_f32_(x32, model_output.contiguous(), hist, w, float(sigma_next - sigma))
+        self._step_history = hist
+        prev = x32.to(model_output.dtype)
         if not return_dict:
             return (prev,)
         return Config(prev_sample=prev)

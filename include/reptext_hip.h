@@ -451,6 +451,18 @@ int rt_cfg_euler_step_f32(float* x, const void* v_uncond, const void* v_text, vo
 int rt_repaint_euler_step_f32(float* x, const void* v, const void* v_text /* nullable */, void* x_bf16 /* nullable */,
                               const float* src, const float* noise, const float* mask, float s, float dsigma, float sigma_next,
                               int64_t n, int64_t n_mask, void* stream);
+/* The second-order multistep form of the same step (Adams–Bashforth 2 in sigma; scheduler.FlowMatchMultistepScheduler), one more
+ * instantiation family of the same kernel. hist is an fp32 buffer of the state's length that holds the velocity of the step before:
+ *   vel2 = w != 0 ? vel + w·(vel − hist) : vel        w = dsigma_i / (2·dsigma_{i-1}), 0 for the first step of a run
+ *   r    = x + dsigma·vel2                            then the blend and x_bf16 as above
+ *   hist = vel                                        under true CFG the mixed fp32 velocity
+ * With w == 0 hist is written and never read (it may be uninitialised) and x gets the bits of the entry above that the other
+ * arguments select. src / noise / mask are all NULL or all given; without a mask pass n_mask = n.
+ * NULL x / v / hist, n < 1, n_mask < 1, a mask without src and noise: RT_E_BADARG; n % n_mask != 0: RT_E_SHAPE.
+ * Added without an ABI bump: nothing existing changed. */
+int rt_multistep_step_f32(float* x, const void* v, const void* v_text /* nullable */, void* x_bf16 /* nullable */, float* hist, float w,
+                          const float* src /* nullable */, const float* noise /* nullable */, const float* mask /* nullable */,
+                          float s, float dsigma, float sigma_next, int64_t n, int64_t n_mask, void* stream);
 
 /* _pack_latents / _unpack_latents (PIPE:550-570): [B][C][2h][2w] <-> [B][h*w][4C], channel order (c,dy,dx).
  * unpack also applies z/scaling + shift (PIPE:1137) and writes NHWC bf16 [B][H2][W2][C]. */
