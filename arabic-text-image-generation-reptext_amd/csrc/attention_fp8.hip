@@ -28,7 +28,6 @@ constexpr int THREADS = 256;
 constexpr float RESCALE_THR = 6.0f;
 constexpr float QK_PRESCALE = 16.0f;
 constexpr float P_BIAS = 2.0f;         // numerators are stored as exp2(s - m + 2) <= 2^8 < 448: two more binades above e4m3's floor
-constexpr float E4M3_MAX = 448.f;
 
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 typedef __attribute__((ext_vector_type(8))) int i32x8;
@@ -38,8 +37,6 @@ __device__ __forceinline__ i32x8 lds_read32(lds_cptr p0, lds_cptr p1) {
   const i32x4 b = *(const __attribute__((address_space(3))) i32x4*)p1;
   return __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
 }
-
-__device__ __forceinline__ float sat448(float v) { return fminf(fmaxf(v, -E4M3_MAX), E4M3_MAX); }
 
 // ---------------------------------------------------------------------------------------------------
 // prep, part 1: q/k RMSNorm(128) + RoPE (math of qk_rmsnorm_rope_kernel) -> e4m3(16·x). 16 lanes per 128-vector.
@@ -58,22 +55,16 @@ __global__ __launch_bounds__(256) void prep_qk_kernel(const bf16_t* __restrict__
   const int h = (int)(t % H); t /= H;
   const int s = (int)(t % S);
   const int b = (int)(t / S);
-  const float* cp = cosv + (int64_t)s * 128 + sub * 8;
-  const float* sp = sinv + (int64_t)s * 128 + sub * 8;
-  const f32x4 c0 = *reinterpret_cast<const f32x4*>(cp), c1 = *reinterpret_cast<const f32x4*>(cp + 4);
-  const f32x4 s0 = *reinterpret_cast<const f32x4*>(sp), s1 = *reinterpret_cast<const f32x4*>(sp + 4);
-  const float cs[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-  const float sn[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
+  const rt_qk_row tb = rt_qk_load_row(cosv, sinv, wq_txt, wk_txt, wq_img, wk_img, s, T, sub);
+  const float (&cs)[8] = tb.cs, (&sn)[8] = tb.sn;
   const bf16_t* row = buf + b * stride_b + (int64_t)s * ld + h * 128 + sub * 8;
   u32x4 uu[2] = {*reinterpret_cast<const u32x4*>(row + q_off), *reinterpret_cast<const u32x4*>(row + k_off)};
 #pragma unroll
   for (int isk = 0; isk < 2; ++isk) {
-    const bf16_t* w = (s < T) ? (isk ? wk_txt : wq_txt) : (isk ? wk_img : wq_img);
-    const u32x4 u = uu[isk];
-    const u32x4 wu = *reinterpret_cast<const u32x4*>(w + sub * 8);
+    const u32x4 wu = isk ? tb.wk : tb.wq;
+    // The arithmetic of rt_qk_norm_rope8 written out, its contraction left to the compiler: calling that function's core here moves qk8 bytes.
     float x[8];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { x[2 * i] = bf16lo(u[i]); x[2 * i + 1] = bf16hi(u[i]); }
+    rt_unpack8(uu[isk], x);
     float ss = 0.f;
 #pragma unroll
     for (int i = 0; i < 8; ++i) ss += x[i] * x[i];
@@ -85,16 +76,11 @@ __global__ __launch_bounds__(256) void prep_qk_kernel(const bf16_t* __restrict__
     for (int i = 0; i < 4; ++i) {
       const float a = x[2 * i] * r * bf16lo(wu[i]);
       const float bq = x[2 * i + 1] * r * bf16hi(wu[i]);
-      y[2 * i] = sat448((a * cs[2 * i] - bq * sn[2 * i]) * QK_PRESCALE);
-      y[2 * i + 1] = sat448((bq * cs[2 * i + 1] + a * sn[2 * i + 1]) * QK_PRESCALE);
+      y[2 * i] = rt_sat_e4m3((a * cs[2 * i] - bq * sn[2 * i]) * QK_PRESCALE);
+      y[2 * i + 1] = rt_sat_e4m3((bq * cs[2 * i + 1] + a * sn[2 * i + 1]) * QK_PRESCALE);
     }
-    int lo = 0, hi = 0;
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], lo, false);
-    lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], hi, false);
-    hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
     uint8_t* o = qk8 + ((int64_t)b * S + s) * (2 * H * 128) + (isk ? H * 128 : 0) + h * 128 + sub * 8;
-    *reinterpret_cast<u32x2*>(o) = u32x2{(uint32_t)lo, (uint32_t)hi};
+    *reinterpret_cast<u32x2*>(o) = rt_pack_e4m3x8(y);
   }
 }
 
@@ -126,12 +112,9 @@ __global__ __launch_bounds__(256) void prep_vt_kernel(const bf16_t* __restrict__
       const int j = 4 * q4 + e;
       const int kt = j >> 4, g = (j >> 2) & 3;
       const int key = 32 * kt + 8 * g + 4 * hf + e;
-      y[e] = sat448(__uint_as_float((uint32_t)tile[key][d] << 16));
+      y[e] = rt_sat_e4m3(__uint_as_float((uint32_t)tile[key][d] << 16));
     }
-    int v = 0;
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], v, false);
-    v = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], v, true);
-    w[q4] = (uint32_t)v;
+    w[q4] = rt_pack_e4m3x4(y[0], y[1], y[2], y[3]);
   }
   uint8_t* dst = vt8 + (((int64_t)b * H + h) * DH + d) * S64 + (int64_t)t * BKV + 32 * hf;
   *reinterpret_cast<u32x4*>(dst) = u32x4{w[0], w[1], w[2], w[3]};
@@ -290,10 +273,7 @@ __global__ __launch_bounds__(THREADS, 2) void attention_fp8_kernel(const uint8_t
           p[e] = __builtin_amdgcn_exp2f(__builtin_fmaf(s_acc[kt][4 * r4 + e], scale_log2, -m_sub));
           psum += p[e];
         }
-        int w = 0;
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(p[0], p[1], w, false);
-        w = __builtin_amdgcn_cvt_pk_fp8_f32(p[2], p[3], w, true);
-        pf[4 * kt + r4] = w;
+        pf[4 * kt + r4] = (int)rt_pack_e4m3x4(p[0], p[1], p[2], p[3]);
       }
     l_run += psum;
 
@@ -343,8 +323,8 @@ __global__ __launch_bounds__(THREADS, 2) void attention_fp8_kernel(const uint8_t
 #pragma unroll
       for (int g = 0; g < 4; ++g) {
         w[g] = 0;
-        w[g] = __builtin_amdgcn_cvt_pk_fp8_f32(sat448(o_acc[dt][4 * g + 0] * f), sat448(o_acc[dt][4 * g + 1] * f), w[g], false);
-        w[g] = __builtin_amdgcn_cvt_pk_fp8_f32(sat448(o_acc[dt][4 * g + 2] * f), sat448(o_acc[dt][4 * g + 3] * f), w[g], true);
+        w[g] = __builtin_amdgcn_cvt_pk_fp8_f32(rt_sat_e4m3(o_acc[dt][4 * g + 0] * f), rt_sat_e4m3(o_acc[dt][4 * g + 1] * f), w[g], false);
+        w[g] = __builtin_amdgcn_cvt_pk_fp8_f32(rt_sat_e4m3(o_acc[dt][4 * g + 2] * f), rt_sat_e4m3(o_acc[dt][4 * g + 3] * f), w[g], true);
       }
 #pragma unroll
       for (int g = 0; g < 4; g += 2) {

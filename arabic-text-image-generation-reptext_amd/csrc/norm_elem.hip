@@ -3,24 +3,39 @@
 // statistics in fp32. Math per SURVEY.md Appendix A.1/A.2/A.5/A.6 and PIPE:550-570,1109.
 #include "rt_common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
+
+// The tail of the per-row e4m3 producers (one wave per row), once the lanes know their maxima: the row's scale, stored by lane 0,
+// then every chunk times the reciprocal, clamped, packed and stored as 8 bytes. get(c, col, y) hands over chunk c (columns col .. +7)
+// as the kernel kept it; NCH > 0: the lane's chunks are c = 0 .. NCH-1 (unrolled, those inside the row), NCH == 0: it strides the row.
+template <int NCH, class Get>
+__device__ __forceinline__ void quantize_row_tail(float amax, int lane, int D, float* __restrict__ scale, uint8_t* __restrict__ orow, Get get) {
+  const float sc = rt_e4m3_row_scale(wave_max(amax));
+  const float inv = 1.f / sc;
+  if (lane == 0) *scale = sc;
+  auto put = [&](int c, int col) {
+    float y[8];
+    get(c, col, y);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) y[i] = rt_sat_e4m3(y[i] * inv);
+    *reinterpret_cast<u32x2*>(orow + col) = rt_pack_e4m3x8(y);
+  };
+  if constexpr (NCH > 0) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      const int col = (c * 64 + lane) * 8;
+      if (col < D) put(c, col);
+    }
+  } else {
+    for (int col = lane * 8; col < D; col += 512) put(0, col);
+  }
+}
 
 // ---------------------------------------------------------------------------------------------------
 // LayerNorm (no affine) + (1+scale)·x + shift. One wave per row, row kept in registers (single HBM read).
 // ---------------------------------------------------------------------------------------------------
-// 8 floats -> 8 e4m3 bytes (OCP e4m3fn on gfx950), inputs already divided by the row scale and clamped to +-448
-__device__ __forceinline__ u32x2 pack_e4m3x8(const float (&y)[8]) {
-  int lo = 0, hi = 0;
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[0], y[1], lo, false);
-  lo = __builtin_amdgcn_cvt_pk_fp8_f32(y[2], y[3], lo, true);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[4], y[5], hi, false);
-  hi = __builtin_amdgcn_cvt_pk_fp8_f32(y[6], y[7], hi, true);
-  return u32x2{(uint32_t)lo, (uint32_t)hi};
-}
-
-constexpr float E4M3_MAX = 448.f;
-
 // A launch covers one or two row segments (rt_layernorm_modulate_pair: image rows + text rows of a double block), each with its own
 // tensors, leading dimensions and adaLN vectors; a wave picks its segment from its row index and then works as before.
 struct LnLaunch {
@@ -44,23 +59,14 @@ __global__ __launch_bounds__(256) void layernorm_mod_kernel(const LnLaunch L, in
   const int rows_per_batch = sg.rows_per_batch;
   const int srow = second ? row - L.rows0 : row;
   const int b = srow / rows_per_batch, r = srow - b * rows_per_batch;
+  const void* xrow = rt_row<X_F32>(x, b * stride_xb + (int64_t)r * ldx);
   float v[NCH][8];
   float s = 0.f;
 #pragma unroll
   for (int c = 0; c < NCH; ++c) {
     const int col = (c * 64 + lane) * 8;
     if (col < D) {
-      if (X_F32) {
-        const float* p = reinterpret_cast<const float*>(x) + b * stride_xb + (int64_t)r * ldx + col;
-        const f32x4 a = *reinterpret_cast<const f32x4*>(p), bb = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { v[c][i] = a[i]; v[c][4 + i] = bb[i]; }
-      } else {
-        const bf16_t* p = reinterpret_cast<const bf16_t*>(x) + b * stride_xb + (int64_t)r * ldx + col;
-        const u32x4 u = *reinterpret_cast<const u32x4*>(p);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { v[c][2 * i] = bf16lo(u[i]); v[c][2 * i + 1] = bf16hi(u[i]); }
-      }
+      rt_load8<X_F32>(xrow, col, v[c]);
 #pragma unroll
       for (int i = 0; i < 8; ++i) s += v[c][i];
     } else {
@@ -102,108 +108,54 @@ __global__ __launch_bounds__(256) void layernorm_mod_kernel(const LnLaunch L, in
 #pragma unroll
         for (int i = 0; i < 8; ++i) { v[c][i] = y[i]; amax = fmaxf(amax, fabsf(y[i])); }
       } else {
-        u32x4 o;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(y[2 * i], y[2 * i + 1]);
-        *reinterpret_cast<u32x4*>(out + b * stride_ob + (int64_t)r * ldo + col) = o;
+        rt_store8(out + b * stride_ob + (int64_t)r * ldo + col, y);
       }
     }
   }
-  if constexpr (OUT_FP8) {
-    amax = wave_max(amax);
-    const float sc = amax > 0.f ? amax * (1.f / E4M3_MAX) : 1.f;
-    const float inv = 1.f / sc;
-    if (lane == 0) row_scale[row] = sc;
-    uint8_t* o8 = reinterpret_cast<uint8_t*>(out) + b * stride_ob + (int64_t)r * ldo;
+  if constexpr (OUT_FP8)
+    quantize_row_tail<NCH>(amax, lane, D, row_scale + row, reinterpret_cast<uint8_t*>(out) + b * stride_ob + (int64_t)r * ldo,
+                           [&](int c, int, float (&y)[8]) {
 #pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-      const int col = (c * 64 + lane) * 8;
-      if (col < D) {
-        float y[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) y[i] = fminf(fmaxf(v[c][i] * inv, -E4M3_MAX), E4M3_MAX);
-        *reinterpret_cast<u32x2*>(o8 + col) = pack_e4m3x8(y);
-      }
-    }
-  }
+                             for (int i = 0; i < 8; ++i) y[i] = v[c][i];
+                           });
 }
 
 // ---------------------------------------------------------------------------------------------------
 // Row-wise e4m3 quantisation (weights once at load; activation rows that do not come out of a LayerNorm).
 // One wave per row. bf16 rows of up to 64·8·NCH elements are read ONCE and held packed in registers between the max pass and
-// the convert pass (quantize_rows_fp8_reg_kernel); longer or f32 rows are read twice (quantize_rows_fp8_kernel).
+// the convert pass (NCH > 0); longer or f32 rows are read twice (NCH == 0).
 // ---------------------------------------------------------------------------------------------------
-template <int NCH>
-__global__ __launch_bounds__(256) void quantize_rows_fp8_reg_kernel(const bf16_t* __restrict__ x, int64_t ldx, uint8_t* __restrict__ out,
-                                                                    int64_t ldo, float* __restrict__ scale, int rows, int D) {
-  const int lane = threadIdx.x & 63;
-  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (row >= rows) return;
-  u32x4 v[NCH];
-  float amax = 0.f;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int col = (c * 64 + lane) * 8;
-    v[c] = u32x4{0u, 0u, 0u, 0u};
-    if (col < D) v[c] = *reinterpret_cast<const u32x4*>(x + (int64_t)row * ldx + col);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) amax = fmaxf(amax, fmaxf(fabsf(bf16lo(v[c][i])), fabsf(bf16hi(v[c][i]))));
-  }
-  amax = wave_max(amax);
-  const float sc = amax > 0.f ? amax * (1.f / E4M3_MAX) : 1.f;
-  const float inv = 1.f / sc;
-  if (lane == 0) scale[row] = sc;
-#pragma unroll
-  for (int c = 0; c < NCH; ++c) {
-    const int col = (c * 64 + lane) * 8;
-    if (col < D) {
-      float y[8];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        y[2 * i] = fminf(fmaxf(bf16lo(v[c][i]) * inv, -E4M3_MAX), E4M3_MAX);
-        y[2 * i + 1] = fminf(fmaxf(bf16hi(v[c][i]) * inv, -E4M3_MAX), E4M3_MAX);
-      }
-      *reinterpret_cast<u32x2*>(out + (int64_t)row * ldo + col) = pack_e4m3x8(y);
-    }
-  }
-}
-
-template <bool X_F32>
+template <bool X_F32, int NCH>
 __global__ __launch_bounds__(256) void quantize_rows_fp8_kernel(const void* __restrict__ x, int64_t ldx, uint8_t* __restrict__ out,
                                                                 int64_t ldo, float* __restrict__ scale, int rows, int D) {
+  static_assert(NCH == 0 || !X_F32, "only bf16 rows are held in registers");
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  auto load8 = [&](int col, float (&y)[8]) {
-    if (X_F32) {
-      const float* p = reinterpret_cast<const float*>(x) + (int64_t)row * ldx + col;
-      const f32x4 a = *reinterpret_cast<const f32x4*>(p), bb = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { y[i] = a[i]; y[4 + i] = bb[i]; }
-    } else {
-      const u32x4 u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(x) + (int64_t)row * ldx + col);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { y[2 * i] = bf16lo(u[i]); y[2 * i + 1] = bf16hi(u[i]); }
-    }
-  };
+  const void* xrow = rt_row<X_F32>(x, (int64_t)row * ldx);
+  u32x4 v[NCH > 0 ? NCH : 1];
   float amax = 0.f;
-  for (int col = lane * 8; col < D; col += 512) {
-    float y[8];
-    load8(col, y);
+  if constexpr (NCH > 0) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(y[i]));
-  }
-  amax = wave_max(amax);
-  const float sc = amax > 0.f ? amax * (1.f / E4M3_MAX) : 1.f;
-  const float inv = 1.f / sc;
-  if (lane == 0) scale[row] = sc;
-  for (int col = lane * 8; col < D; col += 512) {
-    float y[8];
-    load8(col, y);
+    for (int c = 0; c < NCH; ++c) {
+      const int col = (c * 64 + lane) * 8;
+      v[c] = u32x4{0u, 0u, 0u, 0u};
+      if (col < D) v[c] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(xrow) + col);
 #pragma unroll
-    for (int i = 0; i < 8; ++i) y[i] = fminf(fmaxf(y[i] * inv, -E4M3_MAX), E4M3_MAX);
-    *reinterpret_cast<u32x2*>(out + (int64_t)row * ldo + col) = pack_e4m3x8(y);
+      for (int i = 0; i < 4; ++i) amax = fmaxf(amax, fmaxf(fabsf(bf16lo(v[c][i])), fabsf(bf16hi(v[c][i]))));
+    }
+  } else {
+    for (int col = lane * 8; col < D; col += 512) {
+      float y[8];
+      rt_load8<X_F32>(xrow, col, y);
+#pragma unroll
+      for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(y[i]));
+    }
   }
+  quantize_row_tail<NCH>(amax, lane, D, scale + row, out + (int64_t)row * ldo, [&](int c, int col, float (&z)[8]) {
+    if constexpr (NCH > 0) rt_unpack8(v[c], z);
+    else rt_load8<X_F32>(xrow, col, z);
+  });
 }
 
 // MX block quantisation (reptext_hip.h: rt_quantize_mx_fp8): 8 elements per thread, 4 threads per 32-element block.
@@ -218,18 +170,7 @@ __global__ __launch_bounds__(256) void quantize_mx_fp8_kernel(const void* __rest
   float y[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) y[i] = 0.f;
-  if (ok) {
-    if (X_F32) {
-      const float* p = reinterpret_cast<const float*>(x) + (int64_t)row * ldx + col;
-      const f32x4 a = *reinterpret_cast<const f32x4*>(p), bb = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { y[i] = a[i]; y[4 + i] = bb[i]; }
-    } else {
-      const u32x4 u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(x) + (int64_t)row * ldx + col);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { y[2 * i] = bf16lo(u[i]); y[2 * i + 1] = bf16hi(u[i]); }
-    }
-  }
+  if (ok) rt_load8<X_F32>(rt_row<X_F32>(x, (int64_t)row * ldx), col, y);
   float amax = 0.f;
 #pragma unroll
   for (int i = 0; i < 8; ++i) amax = fmaxf(amax, fabsf(y[i]));
@@ -239,8 +180,8 @@ __global__ __launch_bounds__(256) void quantize_mx_fp8_kernel(const void* __rest
   const float inv = rt_mx_inv_scale(sb);
   if (!ok) return;
 #pragma unroll
-  for (int i = 0; i < 8; ++i) y[i] = fminf(fmaxf(y[i] * inv, -E4M3_MAX), E4M3_MAX);
-  *reinterpret_cast<u32x2*>(out + (int64_t)row * ldo + col) = pack_e4m3x8(y);
+  for (int i = 0; i < 8; ++i) y[i] = rt_sat_e4m3(y[i] * inv);
+  *reinterpret_cast<u32x2*>(out + (int64_t)row * ldo + col) = rt_pack_e4m3x8(y);
   if ((threadIdx.x & 3) == 0) bscale[rt_mx_scale_offset(row, col, plane)] = (uint8_t)sb;
 }
 
@@ -266,15 +207,7 @@ __global__ __launch_bounds__(256) void qk_rmsnorm_rope_kernel(
   const int s = (int)(row % S);
   const int b = (int)(row / S);
   bf16_t* base = buf + b * stride_b + (int64_t)s * ld + sub * 8;
-  const bf16_t* wq = (s < T) ? wq_txt : wq_img;
-  const bf16_t* wk = (s < T) ? wk_txt : wk_img;
-  const u32x4 wuq = *reinterpret_cast<const u32x4*>(wq + sub * 8), wuk = *reinterpret_cast<const u32x4*>(wk + sub * 8);
-  const float* cp = cosv + (int64_t)s * 128 + sub * 8;
-  const float* sp = sinv + (int64_t)s * 128 + sub * 8;
-  const f32x4 c0 = *reinterpret_cast<const f32x4*>(cp), c1 = *reinterpret_cast<const f32x4*>(cp + 4);
-  const f32x4 s0 = *reinterpret_cast<const f32x4*>(sp), s1 = *reinterpret_cast<const f32x4*>(sp + 4);
-  const float cs[8] = {c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3]};
-  const float sn[8] = {s0[0], s0[1], s0[2], s0[3], s1[0], s1[1], s1[2], s1[3]};
+  const rt_qk_row t = rt_qk_load_row(cosv, sinv, wq_txt, wk_txt, wq_img, wk_img, s, T, sub);
   u32x4 u[2 * QK_HC];
 #pragma unroll
   for (int v = 0; v < 2 * QK_HC; ++v) {
@@ -285,7 +218,7 @@ __global__ __launch_bounds__(256) void qk_rmsnorm_rope_kernel(
 #pragma unroll
   for (int v = 0; v < 2 * QK_HC; ++v) {
     const int h = hc * QK_HC + (v >> 1);
-    const u32x4 o = rt_qk_norm_rope8(u[v], (v & 1) ? wuk : wuq, cs, sn, eps);
+    const u32x4 o = rt_qk_norm_rope8(u[v], (v & 1) ? t.wk : t.wq, t.cs, t.sn, eps);
     if (h < H) *reinterpret_cast<u32x4*>(base + ((v & 1) ? k_off : q_off) + h * 128) = o;
   }
 }
@@ -590,25 +523,54 @@ __global__ void add_rows_f32_kernel(float* __restrict__ y, const float* __restri
   }
 }
 
-inline int grid_for(int64_t n, int block) {
-  int64_t g = (n + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+// Compile-time choice of a row kernel's instance: f(integral_constant<int, N>) for the first N of the list with nch <= N, and for
+// the last of the list when there is none (the widest instance, or 0 = the instance that strides the row).
+template <int N0, int... Ns, class F>
+void for_nch(int nch, F f) {
+  if constexpr (sizeof...(Ns) == 0) f(std::integral_constant<int, N0>{});
+  else if (nch <= N0) f(std::integral_constant<int, N0>{});
+  else for_nch<Ns...>(nch, f);
 }
 
-int launch_layernorm(const LnLaunch& L, int x_f32, int D, float eps, void* stream) {
+// e4m3 output with row scales: instances {2, 6, 16}; bf16 output: instances {1, 2, 4, 6, 8, 16}.
+int launch_layernorm(const LnLaunch& L, int x_f32, bool out_fp8, float* row_scale, int D, float eps, void* stream) {
   const dim3 grid((L.rows + 3) / 4), block(256);
   hipStream_t st = (hipStream_t)stream;
   const int nch = (D + 511) / 512;
-#define LN_LAUNCH(F32, N) hipLaunchKernelGGL((layernorm_mod_kernel<F32, N>), grid, block, 0, st, L, D, eps)
-  if (x_f32) {
-    if (nch <= 1) LN_LAUNCH(true, 1); else if (nch <= 2) LN_LAUNCH(true, 2); else if (nch <= 4) LN_LAUNCH(true, 4);
-    else if (nch <= 6) LN_LAUNCH(true, 6); else if (nch <= 8) LN_LAUNCH(true, 8); else LN_LAUNCH(true, 16);
-  } else {
-    if (nch <= 1) LN_LAUNCH(false, 1); else if (nch <= 2) LN_LAUNCH(false, 2); else if (nch <= 4) LN_LAUNCH(false, 4);
-    else if (nch <= 6) LN_LAUNCH(false, 6); else if (nch <= 8) LN_LAUNCH(false, 8); else LN_LAUNCH(false, 16);
-  }
-#undef LN_LAUNCH
+  auto with_x = [&](auto f32) {
+    constexpr bool F32 = decltype(f32)::value;
+    if (out_fp8)
+      for_nch<2, 6, 16>(nch, [&](auto n) {
+        hipLaunchKernelGGL((layernorm_mod_kernel<F32, decltype(n)::value, true>), grid, block, 0, st, L, D, eps, row_scale);
+      });
+    else
+      for_nch<1, 2, 4, 6, 8, 16>(nch, [&](auto n) {
+        hipLaunchKernelGGL((layernorm_mod_kernel<F32, decltype(n)::value, false>), grid, block, 0, st, L, D, eps, row_scale);
+      });
+  };
+  if (x_f32) with_x(std::true_type{}); else with_x(std::false_type{});
   return rt_hip_status();
+}
+
+// The refusals of one segment: its arguments, then its alignment (out_align: 16 for bf16 output, 8 for e4m3).
+int check_ln_segment(const rt_ln_segment& g, int out_align) {
+  if (!g.x || !g.out || g.batch < 1 || g.rows_per_batch < 1) return RT_E_BADARG;
+  if ((g.shift == nullptr) != (g.scale == nullptr)) return RT_E_BADARG;
+  if (!RT_ALIGNED(g.x, 16) || !RT_ALIGNED(g.out, out_align) || g.ldx % 8 || g.ldo % 8 || g.stride_xb % 8 || g.stride_ob % 8) return RT_E_ALIGN;
+  if (g.scale && (!RT_ALIGNED(g.scale, 16) || !RT_ALIGNED(g.shift, 16) || g.mod_ld % 4)) return RT_E_ALIGN;
+  return RT_OK;
+}
+
+// The two entries of one segment: argument refusals, then the shape of D, then alignment.
+int layernorm_one_segment(const rt_ln_segment& g, int x_f32, bool out_fp8, float* row_scale, int D, float eps, void* stream) {
+  const int refusal = check_ln_segment(g, out_fp8 ? 8 : 16);
+  if (refusal == RT_E_BADARG || (out_fp8 && !row_scale) || D < 8) return RT_E_BADARG;
+  if (D % 8 || D > 8192) return RT_E_SHAPE;
+  if (refusal) return refusal;
+  LnLaunch L{};
+  L.seg[0] = g;
+  L.rows0 = L.rows = g.batch * g.rows_per_batch;
+  return launch_layernorm(L, x_f32, out_fp8, row_scale, D, eps, stream);
 }
 
 // y = bf16(gelu(x)), the exact (erf) form 0.5 x (1 + erf(x / sqrt 2)): the InstantX image projection's activation (the GEMM epilogue
@@ -645,16 +607,8 @@ extern "C" {
 int rt_layernorm_modulate(const void* x, int64_t ldx, int64_t stride_xb, int32_t x_f32, void* out, int64_t ldo,
                           int64_t stride_ob, const float* shift, const float* scale, int64_t mod_ld, int32_t batch,
                           int32_t rows_per_batch, int32_t D, float eps, void* stream) {
-  if (!x || !out || batch < 1 || rows_per_batch < 1 || D < 8) return RT_E_BADARG;
-  if ((shift == nullptr) != (scale == nullptr)) return RT_E_BADARG;
-  if (D % 8 || D > 8192) return RT_E_SHAPE;
-  if (!RT_ALIGNED(x, 16) || !RT_ALIGNED(out, 16) || ldx % 8 || ldo % 8 || stride_xb % 8 || stride_ob % 8)
-    return RT_E_ALIGN;
-  if (scale && (!RT_ALIGNED(scale, 16) || !RT_ALIGNED(shift, 16) || mod_ld % 4)) return RT_E_ALIGN;
-  LnLaunch L{};
-  L.seg[0] = rt_ln_segment{x, out, shift, scale, ldx, stride_xb, ldo, stride_ob, mod_ld, batch, rows_per_batch};
-  L.rows0 = L.rows = batch * rows_per_batch;
-  return launch_layernorm(L, x_f32, D, eps, stream);
+  return layernorm_one_segment(rt_ln_segment{x, out, shift, scale, ldx, stride_xb, ldo, stride_ob, mod_ld, batch, rows_per_batch}, x_f32,
+                               false, nullptr, D, eps, stream);
 }
 
 int rt_layernorm_modulate_pair(const rt_ln_segment* segs, int32_t x_f32, int32_t D, float eps, void* stream) {
@@ -662,42 +616,19 @@ int rt_layernorm_modulate_pair(const rt_ln_segment* segs, int32_t x_f32, int32_t
   if (D % 8 || D > 8192) return RT_E_SHAPE;
   LnLaunch L{};
   for (int i = 0; i < 2; ++i) {
-    const rt_ln_segment& g = segs[i];
-    if (!g.x || !g.out || g.batch < 1 || g.rows_per_batch < 1) return RT_E_BADARG;
-    if ((g.shift == nullptr) != (g.scale == nullptr)) return RT_E_BADARG;
-    if (!RT_ALIGNED(g.x, 16) || !RT_ALIGNED(g.out, 16) || g.ldx % 8 || g.ldo % 8 || g.stride_xb % 8 || g.stride_ob % 8) return RT_E_ALIGN;
-    if (g.scale && (!RT_ALIGNED(g.scale, 16) || !RT_ALIGNED(g.shift, 16) || g.mod_ld % 4)) return RT_E_ALIGN;
-    L.seg[i] = g;
+    if (const int refusal = check_ln_segment(segs[i], 16)) return refusal;
+    L.seg[i] = segs[i];
   }
   L.rows0 = segs[0].batch * segs[0].rows_per_batch;
   L.rows = L.rows0 + segs[1].batch * segs[1].rows_per_batch;
-  return launch_layernorm(L, x_f32, D, eps, stream);
+  return launch_layernorm(L, x_f32, false, nullptr, D, eps, stream);
 }
 
 int rt_layernorm_modulate_fp8(const void* x, int64_t ldx, int64_t stride_xb, int32_t x_f32, void* out, int64_t ldo,
                               int64_t stride_ob, float* row_scale, const float* shift, const float* scale, int64_t mod_ld,
                               int32_t batch, int32_t rows_per_batch, int32_t D, float eps, void* stream) {
-  if (!x || !out || !row_scale || batch < 1 || rows_per_batch < 1 || D < 8) return RT_E_BADARG;
-  if ((shift == nullptr) != (scale == nullptr)) return RT_E_BADARG;
-  if (D % 8 || D > 8192) return RT_E_SHAPE;
-  if (!RT_ALIGNED(x, 16) || !RT_ALIGNED(out, 8) || ldx % 8 || ldo % 8 || stride_xb % 8 || stride_ob % 8) return RT_E_ALIGN;
-  if (scale && (!RT_ALIGNED(scale, 16) || !RT_ALIGNED(shift, 16) || mod_ld % 4)) return RT_E_ALIGN;
-  const int rows = batch * rows_per_batch;
-  const dim3 grid((rows + 3) / 4), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const int nch = (D + 511) / 512;
-  LnLaunch L{};
-  L.seg[0] = rt_ln_segment{x, out, shift, scale, ldx, stride_xb, ldo, stride_ob, mod_ld, batch, rows_per_batch};
-  L.rows0 = L.rows = rows;
-#define LN8_LAUNCH(F32, N)                                                                                        \
-  hipLaunchKernelGGL((layernorm_mod_kernel<F32, N, true>), grid, block, 0, st, L, D, eps, row_scale)
-  if (x_f32) {
-    if (nch <= 2) LN8_LAUNCH(true, 2); else if (nch <= 6) LN8_LAUNCH(true, 6); else LN8_LAUNCH(true, 16);
-  } else {
-    if (nch <= 2) LN8_LAUNCH(false, 2); else if (nch <= 6) LN8_LAUNCH(false, 6); else LN8_LAUNCH(false, 16);
-  }
-#undef LN8_LAUNCH
-  return rt_hip_status();
+  return layernorm_one_segment(rt_ln_segment{x, out, shift, scale, ldx, stride_xb, ldo, stride_ob, mod_ld, batch, rows_per_batch}, x_f32,
+                               true, row_scale, D, eps, stream);
 }
 
 int rt_quantize_rows_fp8(const void* x, int64_t ldx, int32_t x_f32, void* out, int64_t ldo, float* scale, int32_t rows,
@@ -708,14 +639,12 @@ int rt_quantize_rows_fp8(const void* x, int64_t ldx, int32_t x_f32, void* out, i
   const dim3 grid((rows + 3) / 4), block(256);
   hipStream_t st = (hipStream_t)stream;
   const int nch = (D + 511) / 512;
-#define QR_LAUNCH(N) hipLaunchKernelGGL(quantize_rows_fp8_reg_kernel<N>, grid, block, 0, st, (const bf16_t*)x, ldx, (uint8_t*)out, ldo, scale, rows, D)
-  if (x_f32) hipLaunchKernelGGL(quantize_rows_fp8_kernel<true>, grid, block, 0, st, x, ldx, (uint8_t*)out, ldo, scale, rows, D);
-  else if (nch <= 6) QR_LAUNCH(6);
-  else if (nch <= 12) QR_LAUNCH(12);
-  else if (nch <= 24) QR_LAUNCH(24);
-  else if (nch <= 30) QR_LAUNCH(30);
-  else hipLaunchKernelGGL(quantize_rows_fp8_kernel<false>, grid, block, 0, st, x, ldx, (uint8_t*)out, ldo, scale, rows, D);
-#undef QR_LAUNCH
+  auto launch = [&](auto f32, auto n) {
+    hipLaunchKernelGGL((quantize_rows_fp8_kernel<decltype(f32)::value, decltype(n)::value>), grid, block, 0, st, x, ldx, (uint8_t*)out, ldo,
+                       scale, rows, D);
+  };
+  if (x_f32) launch(std::true_type{}, std::integral_constant<int, 0>{});
+  else for_nch<6, 12, 24, 30, 0>(nch, [&](auto n) { launch(std::false_type{}, n); });   // rows above 64·8·30 elements: two passes
   return rt_hip_status();
 }
 
@@ -767,8 +696,7 @@ int rt_add_rows_f32(float* y, const float* a, const float* b, int32_t rows, int3
   if (!y || !a || rows < 1 || B < 1 || D < 4) return RT_E_BADARG;
   if (D % 4) return RT_E_SHAPE;
   if (!RT_ALIGNED(y, 16) || !RT_ALIGNED(a, 16) || (b && !RT_ALIGNED(b, 16))) return RT_E_ALIGN;
-  hipLaunchKernelGGL(add_rows_f32_kernel, dim3(grid_for((int64_t)rows * (D / 4), 256)), dim3(256), 0, (hipStream_t)stream, y, a, b, rows, B, D / 4);
-  return rt_hip_status();
+  return launch_1d(add_rows_f32_kernel, (int64_t)rows * (D / 4), stream, y, a, b, rows, B, D / 4);
 }
 
 int rt_timestep_embedding(const float* t, float* out, int32_t B, int32_t dim, void* stream) {
@@ -850,44 +778,34 @@ int rt_multistep_step_f32(float* x, const void* v, const void* v_text, void* x_b
 
 int rt_cfg_mix(const void* v_uncond, const void* v_text, void* out, float s, int64_t n, void* stream) {
   if (!v_uncond || !v_text || !out || n < 1) return RT_E_BADARG;
-  hipLaunchKernelGGL(cfg_mix_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)v_uncond,
-                     (const bf16_t*)v_text, (bf16_t*)out, s, n);
-  return rt_hip_status();
+  return launch_1d(cfg_mix_kernel, n, stream, (const bf16_t*)v_uncond, (const bf16_t*)v_text, (bf16_t*)out, s, n);
 }
 
 int rt_pack_latents(const void* nchw, void* packed, int32_t B, int32_t C, int32_t H2, int32_t W2, void* stream) {
   if (!nchw || !packed || B < 1 || C < 1 || H2 < 2 || W2 < 2 || H2 % 2 || W2 % 2) return RT_E_BADARG;
   const int64_t n = (int64_t)B * C * H2 * W2;
-  hipLaunchKernelGGL(pack_latents_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)nchw, (bf16_t*)packed, B, C, H2, W2);
-  return rt_hip_status();
+  return launch_1d(pack_latents_kernel, n, stream, (const bf16_t*)nchw, (bf16_t*)packed, B, C, H2, W2);
 }
 
 int rt_unpack_latents(const void* packed, void* nhwc, int32_t B, int32_t C, int32_t H2, int32_t W2, float inv_scale,
                       float shift, void* stream) {
   if (!packed || !nhwc || B < 1 || C < 1 || H2 < 2 || W2 < 2 || H2 % 2 || W2 % 2) return RT_E_BADARG;
   const int64_t n = (int64_t)B * C * H2 * W2;
-  hipLaunchKernelGGL(unpack_latents_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)packed, (bf16_t*)nhwc, B, C, H2, W2, inv_scale, shift);
-  return rt_hip_status();
+  return launch_1d(unpack_latents_kernel, n, stream, (const bf16_t*)packed, (bf16_t*)nhwc, B, C, H2, W2, inv_scale, shift);
 }
 
 int rt_cast_f32_to_bf16(const float* x, void* y, int64_t n, void* stream) {
   if (!x || !y || n < 1) return RT_E_BADARG;
-  hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)y, n);
-  return rt_hip_status();
+  return launch_1d(cast_f32_bf16_kernel, n, stream, x, (bf16_t*)y, n);
 }
 int rt_cast_bf16_to_f32(const void* x, float* y, int64_t n, void* stream) {
   if (!x || !y || n < 1) return RT_E_BADARG;
-  hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, y, n);
-  return rt_hip_status();
+  return launch_1d(cast_bf16_f32_kernel, n, stream, (const bf16_t*)x, y, n);
 }
 
 int rt_silu_split_bf16(const float* x, void* hi, void* lo, int64_t n, int32_t apply_silu, void* stream) {
   if (!x || !hi || !lo || n < 1) return RT_E_BADARG;
-  hipLaunchKernelGGL(silu_split_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)hi, (bf16_t*)lo, n,
-                     apply_silu);
-  return rt_hip_status();
+  return launch_1d(silu_split_kernel, n, stream, x, (bf16_t*)hi, (bf16_t*)lo, n, apply_silu);
 }
 
 int rt_masked_accumulate(const void* x, void* y, const float* rowscale, float alpha, int32_t batch, int32_t rows,
@@ -896,20 +814,13 @@ int rt_masked_accumulate(const void* x, void* y, const float* rowscale, float al
   if (D % 8) return RT_E_SHAPE;
   if (!RT_ALIGNED(x, 16) || !RT_ALIGNED(y, 16)) return RT_E_ALIGN;
   const int64_t n = (int64_t)batch * rows * (D / 8);
-  if (y_f32) {
-    hipLaunchKernelGGL(masked_accumulate_f32_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, (float*)y, rowscale, alpha, batch, rows, D / 8, accumulate);
-    return rt_hip_status();
-  }
-  hipLaunchKernelGGL(masked_accumulate_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, (bf16_t*)y, rowscale, alpha, batch, rows, D / 8, accumulate);
-  return rt_hip_status();
+  if (y_f32) return launch_1d(masked_accumulate_f32_kernel, n, stream, (const bf16_t*)x, (float*)y, rowscale, alpha, batch, rows, D / 8, accumulate);
+  return launch_1d(masked_accumulate_kernel, n, stream, (const bf16_t*)x, (bf16_t*)y, rowscale, alpha, batch, rows, D / 8, accumulate);
 }
 
 int rt_gelu_erf_bf16(const float* x, void* y, int64_t n, void* stream) {
   if (!x || !y || n < 1) return RT_E_BADARG;
-  hipLaunchKernelGGL(gelu_erf_kernel, dim3(grid_for(n, 256)), dim3(256), 0, (hipStream_t)stream, x, (bf16_t*)y, n);
-  return rt_hip_status();
+  return launch_1d(gelu_erf_kernel, n, stream, x, (bf16_t*)y, n);
 }
 
 int rt_add_bf16_2d(const void* x, int64_t ldx, int64_t stride_xb, void* y, int64_t ldy, int64_t stride_yb, int32_t batch, int32_t rows,
@@ -917,9 +828,8 @@ int rt_add_bf16_2d(const void* x, int64_t ldx, int64_t stride_xb, void* y, int64
   if (!x || !y || batch < 1 || rows < 1 || D < 8 || ldx < D || ldy < D || stride_xb < 0 || stride_yb < 0) return RT_E_BADARG;
   if (D % 8) return RT_E_SHAPE;
   if (!RT_ALIGNED(x, 16) || !RT_ALIGNED(y, 16) || ldx % 8 || ldy % 8 || stride_xb % 8 || stride_yb % 8) return RT_E_ALIGN;
-  hipLaunchKernelGGL(add_bf16_2d_kernel, dim3(grid_for((int64_t)batch * rows * (D / 8), 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)x, ldx, stride_xb, (bf16_t*)y, ldy, stride_yb, batch, rows, D / 8);
-  return rt_hip_status();
+  return launch_1d(add_bf16_2d_kernel, (int64_t)batch * rows * (D / 8), stream, (const bf16_t*)x, ldx, stride_xb, (bf16_t*)y, ldy, stride_yb,
+                   batch, rows, D / 8);
 }
 
 }  // extern "C"

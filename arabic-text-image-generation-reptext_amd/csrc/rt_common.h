@@ -81,6 +81,55 @@ __device__ __forceinline__ float wave_max(float v) {
   return v;
 }
 
+// ---- row chunks: the 8 consecutive elements a lane takes of a bf16 or fp32 row, as fp32 ------------------------------------------
+__device__ __forceinline__ void rt_unpack8(const u32x4 u, float (&y)[8]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) { y[2 * i] = bf16lo(u[i]); y[2 * i + 1] = bf16hi(u[i]); }
+}
+// element `off` of a tensor of bf16 or fp32 elements
+template <bool X_F32>
+__device__ __forceinline__ const void* rt_row(const void* x, int64_t off) {
+  if constexpr (X_F32) return reinterpret_cast<const float*>(x) + off;
+  else return reinterpret_cast<const bf16_t*>(x) + off;
+}
+// elements col .. col+7 of a row: two 16-byte loads (fp32) or one (bf16)
+template <bool X_F32>
+__device__ __forceinline__ void rt_load8(const void* row, int col, float (&y)[8]) {
+  if constexpr (X_F32) {
+    const float* p = reinterpret_cast<const float*>(row) + col;
+    const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { y[i] = a[i]; y[4 + i] = b[i]; }
+  } else {
+    rt_unpack8(*reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(row) + col), y);
+  }
+}
+// 8 floats -> 8 bf16 (RNE), one 16-byte store
+__device__ __forceinline__ void rt_store8(bf16_t* p, const float (&y)[8]) {
+  u32x4 o;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(y[2 * i], y[2 * i + 1]);
+  *reinterpret_cast<u32x4*>(p) = o;
+}
+
+// The lane's share of token row s in the q/k passes: its eight cos and eight sin entries (the lane holds elements 8·sub .. +7 of a
+// head vector) and the q and k norm weights of the row's kind, text rows (s < T) or image rows.
+struct rt_qk_row {
+  float cs[8], sn[8];
+  u32x4 wq, wk;
+};
+__device__ __forceinline__ rt_qk_row rt_qk_load_row(const float* __restrict__ cosv, const float* __restrict__ sinv,
+                                                    const bf16_t* __restrict__ wq_txt, const bf16_t* __restrict__ wk_txt,
+                                                    const bf16_t* __restrict__ wq_img, const bf16_t* __restrict__ wk_img, int s, int T,
+                                                    int sub) {
+  rt_qk_row t;
+  rt_load8<true>(cosv + (int64_t)s * 128, sub * 8, t.cs);
+  rt_load8<true>(sinv + (int64_t)s * 128, sub * 8, t.sn);
+  t.wq = *reinterpret_cast<const u32x4*>((s < T ? wq_txt : wq_img) + sub * 8);
+  t.wk = *reinterpret_cast<const u32x4*>((s < T ? wk_txt : wk_img) + sub * 8);
+  return t;
+}
+
 // q/k RMSNorm(128) + interleaved-pair RoPE of the 8 elements one lane of a 16-lane group holds (elements 8·sub .. +7 of a head
 // vector; the group's 16 lanes are consecutive lanes of a wave). ONE definition for the stand-alone pass (norm_elem.hip,
 // qk_rmsnorm_rope_kernel) and the QKV GEMM's fused epilogue (gemm_bf16.hip), so the two give the same bits: per-lane sum of squares
@@ -91,8 +140,7 @@ __device__ __forceinline__ float wave_max(float v) {
 __device__ __forceinline__ u32x4 rt_qk_norm_rope8(const u32x4 u, const u32x4 wu, const float (&cs)[8], const float (&sn)[8], float eps) {
 #pragma clang fp contract(off)
   float x[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { x[2 * i] = bf16lo(u[i]); x[2 * i + 1] = bf16hi(u[i]); }
+  rt_unpack8(u, x);
   float ss = 0.f;
 #pragma unroll
   for (int i = 0; i < 8; ++i) ss += x[i] * x[i];
@@ -114,6 +162,18 @@ static inline int rt_hip_status() {
   return e == hipSuccess ? RT_OK : (int)e;
 }
 #define RT_ALIGNED(p, a) ((((uintptr_t)(p)) & ((a)-1)) == 0)
+
+// Grid of a grid-stride kernel over n items: enough blocks for all of them, at most `cap`.
+inline int grid_for(int64_t n, int block, int cap = 4096) {
+  int64_t g = (n + block - 1) / block;
+  return (int)(g < 1 ? 1 : (g > cap ? cap : g));
+}
+// One launch of a grid-stride kernel over n items with 256 threads per block, and the status every entry returns.
+template <int CAP = 4096, class K, class... A>
+inline int launch_1d(K kernel, int64_t n, void* stream, A... args) {
+  hipLaunchKernelGGL(kernel, dim3(grid_for(n, 256, CAP)), dim3(256), 0, (hipStream_t)stream, args...);
+  return rt_hip_status();
+}
 
 // Row-per-lane epilogue of the attention kernels: lane (q = lane&31, hh = lane>>5) holds, per (dt, g), the four consecutive
 // output columns 32dt + 8g + 4hh .. +3 of its query row. v_permlane32_swap on the registers of groups (g, g+1) hands the lower
@@ -172,6 +232,24 @@ __device__ __forceinline__ rt_srd_t rt_make_srd(const void* base) {
 __device__ __forceinline__ void rt_dma16_asm(rt_srd_t srd, uint32_t lds_addr, uint32_t voff, uint32_t soff) {
   asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(lds_addr), "v"(voff), "s"(srd), "s"(soff) : "memory");
 }
+
+// ---- e4m3 (OCP e4m3fn on gfx950): what every kernel that writes e4m3 operands shares -----------------------------------------------
+constexpr float RT_E4M3_MAX = 448.f;   // the largest finite value
+__device__ __forceinline__ float rt_sat_e4m3(float v) { return fminf(fmaxf(v, -RT_E4M3_MAX), RT_E4M3_MAX); }
+// four floats -> four e4m3 bytes of one dword (RNE), a in the lowest byte; inputs already scaled into +-448. (The GEMM's out8
+// epilogue and the e4m3 attention's MX epilogue keep the builtin pair typed out: they compute two products, convert, two products,
+// convert, and evaluating all four first, as a call does, changes those kernels' register allocation.)
+__device__ __forceinline__ uint32_t rt_pack_e4m3x4(float a, float b, float c, float d) {
+  int w = 0;
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(a, b, w, false);
+  w = __builtin_amdgcn_cvt_pk_fp8_f32(c, d, w, true);
+  return (uint32_t)w;
+}
+__device__ __forceinline__ u32x2 rt_pack_e4m3x8(const float (&y)[8]) {
+  return u32x2{rt_pack_e4m3x4(y[0], y[1], y[2], y[3]), rt_pack_e4m3x4(y[4], y[5], y[6], y[7])};
+}
+// Scale of a row with maximum magnitude amax: the row's maximum lands on 448; an all-zero row gets 1.
+__device__ __forceinline__ float rt_e4m3_row_scale(float amax) { return amax > 0.f ? amax * (1.f / RT_E4M3_MAX) : 1.f; }
 
 // ---- MX block scales (config 5): one E8M0 byte per 32 consecutive K-elements of an activation row -------------------------------
 // Scale of a block with maximum magnitude amax: the smallest power of two 2^e with amax <= 448 * 2^e (448 = 1.75 * 2^8 is e4m3's

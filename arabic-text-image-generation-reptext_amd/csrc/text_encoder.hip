@@ -26,34 +26,22 @@ __global__ __launch_bounds__(256) void rmsnorm_rows_kernel(const void* __restric
   const int lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
-  auto load8 = [&](int col, float (&y)[8]) {
-    if (X_F32) {
-      const float* p = reinterpret_cast<const float*>(x) + (int64_t)row * ldx + col;
-      const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { y[i] = a[i]; y[4 + i] = b[i]; }
-    } else {
-      const u32x4 u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const bf16_t*>(x) + (int64_t)row * ldx + col);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) { y[2 * i] = bf16lo(u[i]); y[2 * i + 1] = bf16hi(u[i]); }
-    }
-  };
+  const void* xrow = rt_row<X_F32>(x, (int64_t)row * ldx);
   float ss = 0.f;
   for (int col = lane * 8; col < D; col += 512) {
     float y[8];
-    load8(col, y);
+    rt_load8<X_F32>(xrow, col, y);
 #pragma unroll
     for (int i = 0; i < 8; ++i) ss += y[i] * y[i];
   }
   const float r = rsqrtf(wave_sum(ss) / (float)D + eps);
   for (int col = lane * 8; col < D; col += 512) {
-    float y[8];
-    load8(col, y);
-    const u32x4 wu = *reinterpret_cast<const u32x4*>(w + col);
-    u32x4 o;
+    float y[8], wf[8];
+    rt_load8<X_F32>(xrow, col, y);
+    rt_load8<false>(w, col, wf);
 #pragma unroll
-    for (int i = 0; i < 4; ++i) o[i] = pack_bf16x2(y[2 * i] * r * bf16lo(wu[i]), y[2 * i + 1] * r * bf16hi(wu[i]));
-    *reinterpret_cast<u32x4*>(out + (int64_t)row * ldo + col) = o;
+    for (int i = 0; i < 8; ++i) y[i] = y[i] * r * wf[i];
+    rt_store8(out + (int64_t)row * ldo + col, y);
   }
 }
 
@@ -117,10 +105,7 @@ __global__ __launch_bounds__(256) void quick_gelu_kernel(bf16_t* __restrict__ x,
   }
 }
 
-static inline unsigned grid_for(int64_t n, int block) {
-  int64_t g = (n + block - 1) / block;
-  return (unsigned)(g > 65536 ? 65536 : (g < 1 ? 1 : g));
-}
+constexpr int GRID_CAP = 65536;   // of this file's grid-stride kernels
 
 }  // namespace
 
@@ -129,9 +114,7 @@ extern "C" int rt_embedding_gather(const void* table, int64_t ld, const int32_t*
   if (!table || !ids || !out || n < 1 || D < 8 || vocab < 1) return RT_E_BADARG;
   if (D % 8 || ld % 8 || ldo % 8 || ld < D || ldo < D) return RT_E_SHAPE;
   if (!RT_ALIGNED(table, 16) || !RT_ALIGNED(out, 16)) return RT_E_ALIGN;
-  hipLaunchKernelGGL(embedding_gather_kernel, dim3(grid_for((int64_t)n * (D / 8), 256)), dim3(256), 0, (hipStream_t)stream,
-                     (const bf16_t*)table, ld, ids, (bf16_t*)out, ldo, n, D, vocab);
-  return rt_hip_status();
+  return launch_1d<GRID_CAP>(embedding_gather_kernel, (int64_t)n * (D / 8), stream, (const bf16_t*)table, ld, ids, (bf16_t*)out, ldo, n, D, vocab);
 }
 
 extern "C" int rt_rmsnorm_rows(const void* x, int64_t ldx, int32_t x_f32, const void* w, void* out, int64_t ldo, int32_t rows, int32_t D,
@@ -158,15 +141,12 @@ extern "C" int rt_gated_mul(const void* x, int64_t ldx, void* out, int64_t ldo, 
   if (!x || !out || rows < 1 || F < 8) return RT_E_BADARG;
   if (F % 8 || ldx % 8 || ldo % 8 || ldx < 2 * (int64_t)F || ldo < F) return RT_E_SHAPE;
   if (!RT_ALIGNED(x, 16) || !RT_ALIGNED(out, 16)) return RT_E_ALIGN;
-  hipLaunchKernelGGL(gated_mul_kernel, dim3(grid_for((int64_t)rows * (F / 8), 256)), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)x, ldx,
-                     (bf16_t*)out, ldo, rows, F);
-  return rt_hip_status();
+  return launch_1d<GRID_CAP>(gated_mul_kernel, (int64_t)rows * (F / 8), stream, (const bf16_t*)x, ldx, (bf16_t*)out, ldo, rows, F);
 }
 
 extern "C" int rt_quick_gelu(void* x, int64_t n, void* stream) {
   if (!x || n < 8) return RT_E_BADARG;
   if (n % 8) return RT_E_SHAPE;
   if (!RT_ALIGNED(x, 16)) return RT_E_ALIGN;
-  hipLaunchKernelGGL(quick_gelu_kernel, dim3(grid_for(n / 8, 256)), dim3(256), 0, (hipStream_t)stream, (bf16_t*)x, n / 8);
-  return rt_hip_status();
+  return launch_1d<GRID_CAP>(quick_gelu_kernel, n / 8, stream, (bf16_t*)x, n / 8);
 }

@@ -409,10 +409,7 @@ __global__ void unpack_to_haloed_kernel(const bf16_t* __restrict__ p, bf16_t* __
   }
 }
 
-inline int grid_for(int64_t n, int block) {
-  int64_t g = (n + block - 1) / block;
-  return (int)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
-}
+constexpr int GRID_CAP = 8192;   // of this file's grid-stride kernels
 
 }  // namespace
 
@@ -597,21 +594,21 @@ int rt_transpose_bf16(const void* in, void* out, int32_t R, int32_t C, int64_t l
 int rt_image_out(const float* x, float* nchw, uint8_t* u8, int32_t B, int32_t H, int32_t W, int32_t Cp, int32_t C,
                  void* stream) {
   if (!x || (!nchw && !u8) || B < 1 || H < 1 || W < 1 || C < 1 || Cp < C) return RT_E_BADARG;
-  hipLaunchKernelGGL(image_out_kernel, dim3(grid_for((int64_t)B * H * W, 256)), dim3(256), 0, (hipStream_t)stream, x, nchw,
+  hipLaunchKernelGGL(image_out_kernel, dim3(grid_for((int64_t)B * H * W, 256, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, x, nchw,
                      u8, B, H, W, Cp, C);
   return rt_hip_status();
 }
 
 int rt_nchw_to_haloed_nhwc(const float* x, void* y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t Cp, void* stream) {
   if (!x || !y || B < 1 || C < 1 || H < 1 || W < 1 || Cp < C) return RT_E_BADARG;
-  hipLaunchKernelGGL(nchw_to_haloed_nhwc_kernel, dim3(grid_for((int64_t)B * H * W * Cp, 256)), dim3(256), 0,
+  hipLaunchKernelGGL(nchw_to_haloed_nhwc_kernel, dim3(grid_for((int64_t)B * H * W * Cp, 256, GRID_CAP)), dim3(256), 0,
                      (hipStream_t)stream, x, (bf16_t*)y, B, C, H, W, Cp);
   return rt_hip_status();
 }
 
 int rt_haloed_nhwc_to_nchw(const void* x, float* y, int32_t B, int32_t C, int32_t H, int32_t W, int32_t Cp, void* stream) {
   if (!x || !y || B < 1 || C < 1 || H < 1 || W < 1 || Cp < C) return RT_E_BADARG;
-  hipLaunchKernelGGL(haloed_nhwc_to_nchw_kernel, dim3(grid_for((int64_t)B * C * H * W, 256)), dim3(256), 0,
+  hipLaunchKernelGGL(haloed_nhwc_to_nchw_kernel, dim3(grid_for((int64_t)B * C * H * W, 256, GRID_CAP)), dim3(256), 0,
                      (hipStream_t)stream, (const bf16_t*)x, y, B, C, H, W, Cp);
   return rt_hip_status();
 }
@@ -619,7 +616,7 @@ int rt_haloed_nhwc_to_nchw(const void* x, float* y, int32_t B, int32_t C, int32_
 int rt_unpack_latents_haloed(const void* packed, void* y, int32_t B, int32_t C, int32_t H2, int32_t W2, int32_t Cp,
                              float inv_scale, float shift, void* stream) {
   if (!packed || !y || B < 1 || C < 1 || H2 < 2 || W2 < 2 || H2 % 2 || W2 % 2 || Cp < C) return RT_E_BADARG;
-  hipLaunchKernelGGL(unpack_to_haloed_kernel, dim3(grid_for((int64_t)B * H2 * W2 * Cp, 256)), dim3(256), 0,
+  hipLaunchKernelGGL(unpack_to_haloed_kernel, dim3(grid_for((int64_t)B * H2 * W2 * Cp, 256, GRID_CAP)), dim3(256), 0,
                      (hipStream_t)stream, (const bf16_t*)packed, (bf16_t*)y, B, C, H2, W2, Cp, inv_scale, shift);
   return rt_hip_status();
 }
@@ -629,7 +626,7 @@ int rt_resize2d(const void* in, int32_t in_u8, float in_scale, float* out, int32
   if (!in || !out || planes < 1 || H < 1 || W < 1 || OH < 1 || OW < 1 || (in_u8 && in_scale == 0.f)) return RT_E_BADARG;
   // ATen: ratio = (float)(1.0 / (double)scale) when a scale factor was given, else (float)in / out
   const float rh = scale_h > 0.f ? (float)(1.0 / (double)scale_h) : (float)H / (float)OH, rw = scale_w > 0.f ? (float)(1.0 / (double)scale_w) : (float)W / (float)OW;
-  hipLaunchKernelGGL(resize2d_kernel, dim3(grid_for((int64_t)planes * OH * OW, 256)), dim3(256), 0, (hipStream_t)stream, in, in_u8, in_scale,
+  hipLaunchKernelGGL(resize2d_kernel, dim3(grid_for((int64_t)planes * OH * OW, 256, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, in, in_u8, in_scale,
                      out, planes, H, W, OH, OW, rh, rw, bilinear);
   return rt_hip_status();
 }
@@ -637,7 +634,7 @@ int rt_resize2d(const void* in, int32_t in_u8, float in_scale, float* out, int32
 int rt_glyph_blend(const float* image, const float* latents, const float* noise, float* out, int32_t B, int32_t Cimg, int32_t H, int32_t W,
                    int32_t Cl, int32_t OH, int32_t OW, void* stream) {
   if (!image || !latents || !noise || !out || B < 1 || Cimg < 1 || H < 1 || W < 1 || Cl < 1 || OH < 1 || OW < 1) return RT_E_BADARG;
-  hipLaunchKernelGGL(glyph_blend_kernel, dim3(grid_for((int64_t)B * OH * OW, 256)), dim3(256), 0, (hipStream_t)stream, image, latents, noise,
+  hipLaunchKernelGGL(glyph_blend_kernel, dim3(grid_for((int64_t)B * OH * OW, 256, GRID_CAP)), dim3(256), 0, (hipStream_t)stream, image, latents, noise,
                      out, B, Cimg, H, W, Cl, OH, OW, (float)H / (float)OH, (float)W / (float)OW);
   return rt_hip_status();
 }

@@ -8,8 +8,8 @@ where the kernel must not read or has to write, a sentinel around what it writes
 Every launch runs twice from restored buffers and must repeat its bits. Each case prints its worst err/bound and where (run with -s).
 
 Dispatch reached (csrc/norm_elem.hip; nch = ceil(D / 512)):
-    rt_quantize_rows_fp8, bf16 x: D = 8, 3072 -> quantize_rows_fp8_reg_kernel<6>; 3080, 6144 -> <12>; 6152, 12288 -> <24>;
-        12296, 15360 -> <30>; 15368, 65536 -> quantize_rows_fp8_kernel<false> (two passes). fp32 x: quantize_rows_fp8_kernel<true>.
+    rt_quantize_rows_fp8, bf16 x: D = 8, 3072 -> quantize_rows_fp8_kernel<false, 6>; 3080, 6144 -> <false, 12>; 6152, 12288 -> <false, 24>;
+        12296, 15360 -> <false, 30>; 15368, 65536 -> quantize_rows_fp8_kernel<false, 0> (two passes). fp32 x: quantize_rows_fp8_kernel<true, 0>.
     rt_layernorm_modulate_fp8: D = 8, 1024 -> layernorm_mod_kernel<., 2, true>; 1032, 3072 -> <., 6, true>; 3080, 8192 -> <., 16, true>;
         bf16 and fp32 x each."""
 import math

@@ -31,7 +31,7 @@ def traffic(fetch, write, names):
 
 names_bf16 = {"gemm": "gemm_pp_kernel", "attn": "attention_v3_kernel", "attn_short_sequences": "attention_fwd_kernel", "ln": "layernorm_mod_kernel", "rope": "qk_rmsnorm_rope_kernel"}
 names_fp8 = {"gemm_pp_kernel": "gemm_pp_kernel", "attention_fp8_kernel": "attention_fp8_kernel", "prep_qk_kernel": "prep_qk_kernel",
-             "prep_vt_kernel": "prep_vt_kernel", "quantize_rows": "quantize_rows_fp8_reg_kernel<30>", "ln": "layernorm_mod_kernel"}
+             "prep_vt_kernel": "prep_vt_kernel", "quantize_rows": "quantize_rows_fp8_kernel<false, 30>", "ln": "layernorm_mod_kernel"}
 t = {"source": "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/collect_profiles.sh) over `python bench.py --full --steps 1 --warmup 0 --no-cpu-baseline "
                "--no-roofline-pass --no-graph`; per-kernel means over all launches of one image; FETCH_SIZE doubled per MI355X_MICROARCH.md (gfx950 counts 128-B requests as 64 B); "
                f"hbm_bytes = (2*FETCH + WRITE) KiB * 1024 (final kernels of round {tag})",
