@@ -873,3 +873,69 @@ def preprocess_u8(img: torch.Tensor, normalize: bool = True) -> torch.Tensor:
     out = torch.empty(B, Cc, H, W, device=img.device, dtype=F32)
     native.call("rt_preprocess_u8", _dev(img, "img"), out.data_ptr(), B, H, W, Cc, int(normalize), _stream())
     return out
+
+
+def _window(window, H: int, W: int, name: str):
+    """(x0, y0, cw, ch) of a crop rectangle inside an H x W image."""
+    x0, y0, cw, ch = (int(v) for v in window)
+    if cw < 1 or ch < 1 or x0 < 0 or y0 < 0 or x0 + cw > W or y0 + ch > H:
+        raise ValueError(f"{name}: window (x0={x0}, y0={y0}, w={cw}, h={ch}) is not inside the {W}x{H} image")
+    return x0, y0, cw, ch
+
+
+def resize_aa(x: torch.Tensor, window, size, mul: float = 1.0, add: float = 0.0) -> torch.Tensor:
+    """Crop + antialiased bilinear resample on the device: the ``window`` (x0, y0, w, h; None: all of it) of ``x`` — uint8 [H,W] / [H,W,C]
+    interleaved (a sample is x/255) or fp32 [C,H,W] planar, C in {1, 3} — to fp32 [C, size[0], size[1]] = mul·r + add. The filter is
+    ``F.interpolate(window, size, mode="bilinear", antialias=True, align_corners=False)``; a window resampled to its own size is
+    mul·(x/255) + add bit for bit. At most native.RT_RESIZE_AA_MAX_SCALE input samples per output sample and axis."""
+    is_u8 = x.dtype == torch.uint8
+    if not ((is_u8 and x.dim() in (2, 3)) or (x.dtype == F32 and x.dim() == 3)):
+        raise TypeError("resize_aa: uint8 [H,W] / [H,W,C] or fp32 [C,H,W]")
+    x = x.contiguous()
+    if is_u8:
+        H, W, Cc = x.shape[0], x.shape[1], (1 if x.dim() == 2 else x.shape[2])
+    else:
+        Cc, H, W = x.shape
+    x0, y0, cw, ch = _window((0, 0, W, H) if window is None else window, H, W, "resize_aa")
+    OH, OW = int(size[0]), int(size[1])
+    if OH < 1 or OW < 1:
+        raise ValueError(f"resize_aa: size {tuple(size)}")
+    out = torch.empty(Cc, OH, OW, device=x.device, dtype=F32)
+    ws = torch.empty(int(native.load().rt_resize_aa_ws_bytes(Cc, ch, OW)), device=x.device, dtype=torch.uint8)
+    native.call("rt_resize_aa", _dev(x, "x"), int(is_u8), Cc, H, W, x0, y0, cw, ch, out.data_ptr(), OH, OW, float(mul), float(add),
+                ws.data_ptr(), ws.numel(), _stream())
+    return out
+
+
+def gaussian_blur(plane: torch.Tensor, sigma: float) -> torch.Tensor:
+    """Separable Gaussian blur of one fp32 plane [H,W]: radius ceil(3·sigma), fp32 weights normalised to sum 1, replicated borders.
+    sigma = 0 returns the plane; sigma above native.RT_BLUR_MAX_RADIUS / 3 is refused."""
+    if plane.dim() != 2:
+        raise ValueError(f"gaussian_blur: one [H,W] plane, got {tuple(plane.shape)}")
+    _dev(plane, "plane", F32)
+    if float(sigma) < 0:
+        raise ValueError(f"gaussian_blur: sigma {sigma} < 0")
+    if float(sigma) == 0:
+        return plane
+    plane = plane.contiguous()
+    H, W = plane.shape
+    out, ws = torch.empty_like(plane), torch.empty_like(plane)
+    native.call("rt_gaussian_blur_f32", plane.data_ptr(), out.data_ptr(), H, W, float(sigma), ws.data_ptr(), ws.numel() * 4, _stream())
+    return out
+
+
+def composite_u8(photo: torch.Tensor, gen: torch.Tensor, alpha: torch.Tensor, window) -> torch.Tensor:
+    """A copy of ``photo`` (uint8 [H,W,C], C in {1, 3}) with ``gen`` (fp32 [C,h,w] in [-1,1], the decoder's range) blended into the
+    ``window`` (x0, y0, w, h) under ``alpha`` (fp32 [h,w] in [0,1]): rint((1 − a)·photo + a·clamp(gen/2 + 0.5, 0, 1)·255). alpha 0 keeps
+    the photo's byte, alpha 1 writes the byte the decoder's uint8 output has for ``gen``."""
+    if photo.dtype != torch.uint8 or photo.dim() != 3:
+        raise TypeError("composite_u8: photo uint8 [H,W,C]")
+    photo, gen, alpha = photo.contiguous(), gen.contiguous(), alpha.contiguous()
+    H, W, Cc = photo.shape
+    x0, y0, cw, ch = _window(window, H, W, "composite_u8")
+    if tuple(gen.shape) != (Cc, ch, cw) or tuple(alpha.shape) != (ch, cw):
+        raise ValueError(f"composite_u8: gen {tuple(gen.shape)} / alpha {tuple(alpha.shape)} against a {cw}x{ch} window of {Cc} channels")
+    out = torch.empty_like(photo)
+    native.call("rt_composite_u8", _dev(photo, "photo"), out.data_ptr(), H, W, Cc, x0, y0, cw, ch, _dev(gen, "gen", F32), _dev(alpha, "alpha", F32),
+                _stream())
+    return out

@@ -561,6 +561,40 @@ int rt_canny_u8(const uint8_t* img, int32_t H, int32_t W, int32_t C, float low, 
  * out f32 [B][C][H][W] = x / 255, then 2x - 1 when `normalize` (the same fp32 roundings numpy/torch take: bit-identical). */
 int rt_preprocess_u8(const uint8_t* img, float* out, int32_t B, int32_t H, int32_t W, int32_t C, int32_t normalize, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The photo flow's pixel work (reptext_amd/pipeline_photo.py; csrc/photo.hip): crop + antialiased resample, the mask's
+ * feather, and the blend of the result into the full-size photo. Added entries; the ABI revision is unchanged.
+ * ---------------------------------------------------------------------------------------- */
+#define RT_RESIZE_AA_MAX_SCALE 16   /* rt_resize_aa: the window may be at most this many times the output, per axis */
+#define RT_BLUR_MAX_RADIUS 96       /* rt_gaussian_blur_f32: ceil(3·sigma) may be at most this, i.e. sigma <= 32 */
+/* Crop + antialiased separable bilinear resample: the window (x0, y0, cw, ch) of `in` — uint8 [H][W][C] interleaved (in_u8, a sample
+ * is x/255) or f32 [C][H][W] planar — to out f32 [C][OH][OW] = mul·r + add. The filter is ATen's _upsample_bilinear2d_aa
+ * (align_corners = False) applied to the window as if it were the whole image: per axis scale = in/out, support = max(scale, 1),
+ * center = scale·(i + 0.5), taps max(0, int(center − support + 0.5)) .. min(in, int(center + support + 0.5)), triangle weights
+ * normalised to sum 1 (formed in fp64, rounded to fp32 once; fp32 accumulation, along x then along y). Upscaling is plain
+ * bilinear; a window resampled to its own size is mul·(x/255) + add bit for bit (each operation rounded once).
+ * ws: rt_resize_aa_ws_bytes(C, ch, OW) bytes, 16-byte aligned (the pass along x). Two kernels on `stream`.
+ * Rejected on the host: null in / out / ws, a size < 1, a window not inside the image, ws too small or unaligned (RT_E_BADARG);
+ * C not 1 or 3, cw > RT_RESIZE_AA_MAX_SCALE·OW or ch > RT_RESIZE_AA_MAX_SCALE·OH, ch or OH > 65535 (RT_E_SHAPE). */
+int64_t rt_resize_aa_ws_bytes(int32_t C, int32_t ch, int32_t OW);
+int rt_resize_aa(const void* in, int32_t in_u8, int32_t C, int32_t H, int32_t W, int32_t x0, int32_t y0, int32_t cw, int32_t ch, float* out,
+                 int32_t OH, int32_t OW, float mul, float add, void* ws, int64_t ws_bytes, void* stream);
+/* Separable Gaussian blur of one f32 plane [H][W] (the mask's feather): radius R = ceil(3·sigma), weights exp(−k²/(2·sigma²)) in
+ * fp32 normalised to sum 1, replicated borders, rows then columns. An output farther than R (Chebyshev) from every non-zero input
+ * is exactly 0, and one whose inputs within R are all 1 is exactly 1 (the taps are added from the outermost pair inwards and the
+ * centre weight is 1 minus the fp32 sum of the others in that order). ws: H·W·4 bytes (the row pass); out must not be in.
+ * Rejected on the host: null pointers, H / W < 1, sigma <= 0 or NaN, ws too small, out == in (RT_E_BADARG); 3·sigma >
+ * RT_BLUR_MAX_RADIUS, H > 65535 (RT_E_SHAPE). */
+int rt_gaussian_blur_f32(const float* in, float* out, int32_t H, int32_t W, float sigma, void* ws, int64_t ws_bytes, void* stream);
+/* out uint8 [H][W][C] = photo uint8 [H][W][C] outside the rectangle (x0, y0, cw, ch); inside it, with gen f32 [C][ch][cw] in the
+ * decoder's range and alpha f32 [ch][cw]: g = clamp(gen/2 + 0.5, 0, 1)·255 (rt_image_out's expression), v = (1 − a)·src + a·g with
+ * every product and sum rounded once, out = rint(v) (half to even), clamped. alpha = 0 is the photo's byte, alpha = 1 the byte
+ * rt_image_out writes for gen. Any W and any rectangle: 16-byte loads and stores where photo and out are 16-byte aligned, byte
+ * accesses otherwise and for the last (H·W·C) % 16 bytes, in one launch. out must not overlap photo.
+ * Rejected on the host: null pointers, a size < 1, a rectangle not inside the photo (RT_E_BADARG); C not 1 or 3 (RT_E_SHAPE). */
+int rt_composite_u8(const uint8_t* photo, uint8_t* out, int32_t H, int32_t W, int32_t C, int32_t x0, int32_t y0, int32_t cw, int32_t ch,
+                    const float* gen, const float* alpha, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

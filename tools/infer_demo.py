@@ -19,6 +19,10 @@ encoders, which sit outside the hot path. With real checkpoints on disk use `Flu
                                               # inpainting (FluxControlNetRepaintPipeline): the last strength·steps steps from the noised
                                               # photo, the photo put back outside the lines' boxes after every step; no second tower, no CFG
                                               # doubling; combines with the flags above
+    python tools/infer_demo.py --source-image photo.jpg --photo-crop 32 [--mask-blur 4]   # the photo flow (FluxControlNetPhotoPipeline): the
+                                              # photo stays at ITS size; the lines are laid out and their hints rendered at that size, the
+                                              # region around them (+ 32 pixels) is cut out and resampled to --size on the device, repainted,
+                                              # resampled back and blended into the untouched photo under a mask feathered with sigma 4
     python tools/infer_demo.py --inpaint      # infer_inpaint.py's flow (infer_inpaint.py:48-155): second 68-channel tower, masked
                                               # background image, position mask = bbox+-5, true CFG with negative embeddings
 """
@@ -50,6 +54,9 @@ ap.add_argument("--negative-prompt", default=None, help="negative prompt of the 
 ap.add_argument("--true-cfg-scale", type=float, default=1.0)
 ap.add_argument("--source-image", default=None, help="photo to render the text into (the repaint pipeline's image=; the mask is the union of the lines' boxes)")
 ap.add_argument("--strength", type=float, default=0.6, help="share of the schedule a repaint runs")
+ap.add_argument("--photo-crop", type=int, default=None, help="with --source-image: keep the photo at its size and repaint only the region around "
+                "the text, this many pixels of padding around the lines' boxes (the photo pipeline's padding_mask_crop=)")
+ap.add_argument("--mask-blur", type=float, default=4.0, help="sigma of the feather under which the photo flow blends the result into the photo")
 a = ap.parse_args()
 dev, bf16 = torch.device("cuda:0"), torch.bfloat16
 ct, cc = flux_dev_transformer_config(), reptext_controlnet_config()
@@ -58,7 +65,11 @@ if a.depth_scale != 1.0:
     cc["num_layers"] = max(1, int(cc["num_layers"] * a.depth_scale))
 controlnet = FluxControlNetModel(**cc, device=dev, dtype=bf16).random_init_(seed=1)
 pipeline_class = FluxControlNetPipeline
-if a.source_image:
+if a.photo_crop is not None and not a.source_image:
+    ap.error("--photo-crop needs --source-image")
+if a.source_image and a.photo_crop is not None:
+    from pipeline_flux_controlnet_photo import FluxControlNetPhotoPipeline as pipeline_class          # the same components
+elif a.source_image:
     from pipeline_flux_controlnet_repaint import FluxControlNetRepaintPipeline as pipeline_class      # the same components
 
 pipe = pipeline_class(FlowMatchEulerDiscreteScheduler(), AutoencoderKL(**flux_vae_config(), device=dev, dtype=bf16).random_init_(seed=2),
@@ -66,12 +77,19 @@ pipe = pipeline_class(FlowMatchEulerDiscreteScheduler(), AutoencoderKL(**flux_va
 pipe.set_progress_bar_config(disable=True)
 
 width = height = a.size
-font = ImageFont.truetype("DejaVuSans.ttf", max(a.size * 80 // 1024, 12))      # infer.py:39-41 uses Arial Unicode, 80 px
+layout_w, layout_h = width, height              # the size at which the lines are laid out and their hints rendered
+if a.photo_crop is not None:                    # the photo flow: at the photo's own size; --size stays the working size
+    from PIL import Image
+
+    layout_w, layout_h = Image.open(a.source_image).size
+side = min(layout_w, layout_h)
+font = ImageFont.truetype("DejaVuSans.ttf", max(side * 80 // 1024, 12))        # infer.py:39-41 uses Arial Unicode, 80 px
 text_list = ["مرحبا", "RepText"]
-text_position_list = [(a.size * 370 // 1024, a.size * 200 // 1024), (a.size * 370 // 1024, a.size * 330 // 1024)]
+line_gap = side * 330 // 1024 - side * 200 // 1024                              # the second line follows the font's size, not the photo's height
+text_position_list = [(layout_w * 370 // 1024, layout_h * 200 // 1024), (layout_w * 370 // 1024, layout_h * 200 // 1024 + line_gap)]
 text_color_list = [(255, 255, 255), (255, 255, 255)]
 control_image_list, control_position_list, control_mask_list, control_glyph_all = hints.build_text_hints(
-    text_list, text_position_list, text_color_list, font, width, height)
+    text_list, text_position_list, text_color_list, font, layout_w, layout_h)
 
 g = torch.Generator().manual_seed(1)
 prompt_embeds = torch.randn(1, 512, 4096, generator=g).to(dev, bf16)
@@ -144,6 +162,8 @@ if a.source_image:
     from PIL import Image
 
     ip_kwargs.update(image=Image.open(a.source_image).convert("RGB"), strength=a.strength)     # mask_image=None: the union of control_mask
+    if a.photo_crop is not None:
+        ip_kwargs.update(padding_mask_crop=a.photo_crop, mask_blur=a.mask_blur)
 
 for it in range(2):
     torch.cuda.synchronize(); t0 = time.perf_counter()
