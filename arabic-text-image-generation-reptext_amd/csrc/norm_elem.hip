@@ -351,10 +351,14 @@ __device__ __forceinline__ float repaint_blend(float r, float src, float noise, 
 //   v2 = w != 0 ? v + w·(v − h) : v;   r = x + ds·v2;   h = v
 // w is a kernel scalar, so the branch is uniform: with w = 0 (the first step of a run) h is written and never read — it may be
 // uninitialised memory — and r is the text of the form without MULTI, the same bits.
-template <bool CFG, bool REPAINT, bool MULTI>
+// PROJ (projected guidance, rt_projected_step_f32): u carries the guidance difference d (fp32, from rt_guidance_reduce_f32), t the
+// positive prediction p, s is s − 1, and k (the norm clamp) and e = (η − 1)·α are the sample's two scalars:
+//   v = p + (s − 1)·(k·d + e·p)
+// With d = 0 (u == p) k = 1 and e = 0, so v = p + (s − 1)·0 = p: the plain step on p, the same bits.
+template <bool CFG, bool REPAINT, bool MULTI, bool PROJ = false>
 __device__ __forceinline__ float master_step_element(float x, float u, float t, float src, float noise, float m, float s, float ds,
-                                                     float sn, float w, float& h) {
-  const float v = CFG ? u + s * (t - u) : u;
+                                                     float sn, float w, float& h, float k = 1.0f, float e = 0.0f) {
+  const float v = PROJ ? t + s * (k * u + e * t) : CFG ? u + s * (t - u) : u;
   float v2 = v;
   if (MULTI) {
     if (w != 0.0f) v2 = v + w * (v - h);
@@ -368,31 +372,40 @@ __device__ __forceinline__ float master_step_element(float x, float u, float t, 
 // the up to three left over, or all of them — the host sets n4 = 0 where a pointer is not aligned or a group could straddle the
 // mask's period (n_mask < n and no multiple of 4). m = mask[i % n_mask]; t is read only under CFG, src / noise / mask only under
 // REPAINT, hist only under MULTI (read where w != 0, always written), in the groups and by the tail rules of x.
-template <bool CFG, bool REPAINT, bool MULTI>
-__global__ void master_step_f32_kernel(float* __restrict__ x, const bf16_t* __restrict__ u, const bf16_t* __restrict__ t,
-                                       bf16_t* __restrict__ xb, const float* __restrict__ src, const float* __restrict__ noise,
-                                       const float* __restrict__ mask, float* __restrict__ hist, float s, float ds, float sn, float w,
-                                       int64_t n, int64_t n_mask, int64_t n4) {
-  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+// The one text of both kernels below. Under PROJ the pointers are those of one sample (n = n_s), d is its guidance difference (u is
+// not read), mbase its first element's flat index for the mask's rule, and tid / nthr count over the x dimension of the grid.
+template <bool CFG, bool REPAINT, bool MULTI, bool PROJ>
+__device__ __forceinline__ void master_step_body(float* __restrict__ x, const bf16_t* __restrict__ u, const bf16_t* __restrict__ t,
+                                                 bf16_t* __restrict__ xb, const float* __restrict__ src, const float* __restrict__ noise,
+                                                 const float* __restrict__ mask, float* __restrict__ hist, float s, float ds, float sn,
+                                                 float w, int64_t n, int64_t n_mask, int64_t n4, int64_t tid, int64_t nthr,
+                                                 const float* __restrict__ d, int64_t mbase, float k, float e) {
   for (int64_t g = tid; g < n4; g += nthr) {
     const f32x4 xv = reinterpret_cast<const f32x4*>(x)[g];
-    const u32x2 uv = reinterpret_cast<const u32x2*>(u)[g];
-    u32x2 tv = uv;
-    if (CFG) tv = reinterpret_cast<const u32x2*>(t)[g];
+    u32x2 uv, tv;
+    f32x4 dv = xv;
+    if (PROJ) {
+      dv = reinterpret_cast<const f32x4*>(d)[g];
+      uv = tv = reinterpret_cast<const u32x2*>(t)[g];
+    } else {
+      uv = reinterpret_cast<const u32x2*>(u)[g];
+      tv = uv;
+      if (CFG) tv = reinterpret_cast<const u32x2*>(t)[g];
+    }
     f32x4 sv = xv, nv = xv, mv = xv, hv = xv;      // like tv: placeholders that the helper ignores without REPAINT / MULTI
     if (REPAINT) {
       sv = reinterpret_cast<const f32x4*>(src)[g];
       nv = reinterpret_cast<const f32x4*>(noise)[g];
-      mv = *reinterpret_cast<const f32x4*>(mask + (g * 4) % n_mask);
+      mv = *reinterpret_cast<const f32x4*>(mask + (PROJ ? (mbase + g * 4) % n_mask : (g * 4) % n_mask));
     }
     if (MULTI && w != 0.0f) hv = reinterpret_cast<const f32x4*>(hist)[g];
     f32x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float a = (j & 1) ? bf16hi(uv[j >> 1]) : bf16lo(uv[j >> 1]);
+      const float a = PROJ ? dv[j] : (j & 1) ? bf16hi(uv[j >> 1]) : bf16lo(uv[j >> 1]);
       const float b = (j & 1) ? bf16hi(tv[j >> 1]) : bf16lo(tv[j >> 1]);
       float h = hv[j];
-      o[j] = master_step_element<CFG, REPAINT, MULTI>(xv[j], a, b, sv[j], nv[j], mv[j], s, ds, sn, w, h);
+      o[j] = master_step_element<CFG, REPAINT, MULTI, PROJ>(xv[j], a, b, sv[j], nv[j], mv[j], s, ds, sn, w, h, k, e);
       hv[j] = h;
     }
     reinterpret_cast<f32x4*>(x)[g] = o;
@@ -400,15 +413,106 @@ __global__ void master_step_f32_kernel(float* __restrict__ x, const bf16_t* __re
     if (MULTI) reinterpret_cast<f32x4*>(hist)[g] = hv;
   }
   for (int64_t i = n4 * 4 + tid; i < n; i += nthr) {
-    const float a = bf16_to_f32(u[i]), b = CFG ? bf16_to_f32(t[i]) : a;
+    float a, b;
+    if (PROJ) { a = d[i]; b = bf16_to_f32(t[i]); }
+    else { a = bf16_to_f32(u[i]); b = CFG ? bf16_to_f32(t[i]) : a; }
     float sv = 0.0f, nv = 0.0f, mv = 0.0f, h = 0.0f;
-    if (REPAINT) { sv = src[i]; nv = noise[i]; mv = mask[i % n_mask]; }
+    if (REPAINT) { sv = src[i]; nv = noise[i]; mv = mask[PROJ ? (mbase + i) % n_mask : i % n_mask]; }
     if (MULTI && w != 0.0f) h = hist[i];
-    const float o = master_step_element<CFG, REPAINT, MULTI>(x[i], a, b, sv, nv, mv, s, ds, sn, w, h);
+    const float o = master_step_element<CFG, REPAINT, MULTI, PROJ>(x[i], a, b, sv, nv, mv, s, ds, sn, w, h, k, e);
     x[i] = o;
     if (xb) xb[i] = f32_to_bf16(o);
     if (MULTI) hist[i] = h;
   }
+}
+
+template <bool CFG, bool REPAINT, bool MULTI>
+__global__ void master_step_f32_kernel(float* __restrict__ x, const bf16_t* __restrict__ u, const bf16_t* __restrict__ t,
+                                       bf16_t* __restrict__ xb, const float* __restrict__ src, const float* __restrict__ noise,
+                                       const float* __restrict__ mask, float* __restrict__ hist, float s, float ds, float sn, float w,
+                                       int64_t n, int64_t n_mask, int64_t n4) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  master_step_body<CFG, REPAINT, MULTI, false>(x, u, t, xb, src, noise, mask, hist, s, ds, sn, w, n, n_mask, n4, tid, nthr, nullptr, 0,
+                                               1.0f, 0.0f);
+}
+
+// ---- projected guidance: per-sample sums, then the master step with the projected velocity (reptext_hip.h) --------------------------
+// One term of the three sums and the difference itself. Contraction off: every product and sum is rounded once, so the 16-byte and
+// the one-element path of the kernel below cannot differ by what the compiler fuses in either.
+__device__ __forceinline__ float guidance_term(float p, float u, float r, float beta, float& a, float& b, float& c) {
+#pragma clang fp contract(off)
+  float d = p - u;
+  if (beta != 0.0f) d = d + beta * r;
+  a += d * d;
+  b += d * p;
+  c += p * p;
+  return d;
+}
+
+// grid (chunks, B), 256 threads: thread th takes the groups of four th, th + 256, th + 512, th + 768 of its chunk of RT_GUIDE_CHUNK
+// elements, in that order and the four elements of a group in theirs, whether it loads them as a group (VEC) or one by one.
+template <bool VEC>
+__global__ __launch_bounds__(256) void guidance_reduce_kernel(const bf16_t* __restrict__ u, const bf16_t* __restrict__ t,
+                                                              float* __restrict__ diff, float beta, float* __restrict__ partials,
+                                                              int64_t n_s) {
+  static_assert(RT_GUIDE_CHUNK == 4 * 4 * 256, "four groups of four per thread");
+  const int64_t base = (int64_t)blockIdx.y * n_s;
+  u += base; t += base; diff += base;
+  float a = 0.0f, b = 0.0f, c = 0.0f;
+#pragma unroll
+  for (int it = 0; it < 4; ++it) {
+    const int64_t o = (int64_t)blockIdx.x * RT_GUIDE_CHUNK + (it * 256 + (int)threadIdx.x) * 4;
+    if (VEC) {
+      if (o < n_s) {              // n_s % 4 == 0: a group is inside the sample or outside it
+        const u32x2 uv = *reinterpret_cast<const u32x2*>(u + o), tv = *reinterpret_cast<const u32x2*>(t + o);
+        f32x4 rv = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (beta != 0.0f) rv = *reinterpret_cast<const f32x4*>(diff + o);
+        f32x4 dv;
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          dv[j] = guidance_term((j & 1) ? bf16hi(tv[j >> 1]) : bf16lo(tv[j >> 1]), (j & 1) ? bf16hi(uv[j >> 1]) : bf16lo(uv[j >> 1]),
+                                rv[j], beta, a, b, c);
+        *reinterpret_cast<f32x4*>(diff + o) = dv;
+      }
+    } else {
+      for (int j = 0; j < 4; ++j)
+        if (o + j < n_s) {
+          const float r = beta != 0.0f ? diff[o + j] : 0.0f;
+          diff[o + j] = guidance_term(bf16_to_f32(t[o + j]), bf16_to_f32(u[o + j]), r, beta, a, b, c);
+        }
+    }
+  }
+  a = wave_sum(a); b = wave_sum(b); c = wave_sum(c);
+  __shared__ float red[4][3];
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { red[wave][0] = a; red[wave][1] = b; red[wave][2] = c; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float* out = partials + ((int64_t)blockIdx.y * gridDim.x + blockIdx.x) * 3;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) out[q] = ((red[0][q] + red[1][q]) + red[2][q]) + red[3][q];
+  }
+}
+
+// grid (x, B). Prologue, the same in every workgroup of a sample: its partials added in index order in double, k and e formed in
+// double and rounded to float once. Then the one step body on the sample's pointers.
+template <bool REPAINT, bool MULTI>
+__global__ void projected_step_f32_kernel(float* __restrict__ x, const bf16_t* __restrict__ t, bf16_t* __restrict__ xb,
+                                          const float* __restrict__ diff, const float* __restrict__ partials, int nparts, float s1,
+                                          float eta, float tau, const float* __restrict__ src, const float* __restrict__ noise,
+                                          const float* __restrict__ mask, float* __restrict__ hist, float ds, float sn, float w,
+                                          int64_t n_s, int64_t n_mask, int64_t n4) {
+  const float* part = partials + (int64_t)blockIdx.y * nparts * 3;
+  double a = 0.0, b = 0.0, c = 0.0;
+  for (int j = 0; j < nparts; ++j) { a += (double)part[3 * j]; b += (double)part[3 * j + 1]; c += (double)part[3 * j + 2]; }
+  const double kd = (tau > 0.0f && a > (double)tau * (double)tau) ? (double)tau / sqrt(a) : 1.0;
+  const double alpha = c > 0.0 ? kd * b / c : 0.0;
+  const float k = (float)kd, e = (float)(((double)eta - 1.0) * alpha);
+  const int64_t base = (int64_t)blockIdx.y * n_s;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  master_step_body<false, REPAINT, MULTI, true>(x + base, nullptr, t + base, xb ? xb + base : nullptr, REPAINT ? src + base : nullptr,
+                                                REPAINT ? noise + base : nullptr, mask, MULTI ? hist + base : nullptr, s1, ds, sn, w,
+                                                n_s, n_mask, n4, tid, nthr, diff + base, base, k, e);
 }
 
 __global__ void cfg_mix_kernel(const bf16_t* __restrict__ u, const bf16_t* __restrict__ t, bf16_t* __restrict__ o,
@@ -774,6 +878,43 @@ int rt_multistep_step_f32(float* x, const void* v, const void* v_text, void* x_b
   if (!x || !v || !hist || n < 1 || n_mask < 1 || (mask && (!src || !noise))) return RT_E_BADARG;
   if (n % n_mask) return RT_E_SHAPE;
   return launch_master_step_f32(x, v, v_text, x_bf16, src, noise, mask, hist, s, dsigma, sigma_next, w, n, n_mask, stream);
+}
+
+int64_t rt_guidance_ws_bytes(int32_t B, int64_t n_s) {
+  if (B < 1 || n_s < 1) return 0;
+  return (int64_t)B * ((n_s + RT_GUIDE_CHUNK - 1) / RT_GUIDE_CHUNK) * 3 * (int64_t)sizeof(float);
+}
+
+int rt_guidance_reduce_f32(const void* v_uncond, const void* v_text, float* diff, float beta, float* partials, int32_t B, int64_t n_s,
+                           void* stream) {
+  if (!v_uncond || !v_text || !diff || !partials || B < 1 || n_s < 1) return RT_E_BADARG;
+  const int64_t chunks = (n_s + RT_GUIDE_CHUNK - 1) / RT_GUIDE_CHUNK;
+  if (B > 65535 || chunks > 0x7fffffff) return RT_E_SHAPE;
+  const bool vec = n_s % 4 == 0 && RT_ALIGNED(v_uncond, 8) && RT_ALIGNED(v_text, 8) && RT_ALIGNED(diff, 16);
+  hipLaunchKernelGGL(vec ? guidance_reduce_kernel<true> : guidance_reduce_kernel<false>, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0,
+                     (hipStream_t)stream, (const bf16_t*)v_uncond, (const bf16_t*)v_text, diff, beta, partials, n_s);
+  return rt_hip_status();
+}
+
+int rt_projected_step_f32(float* x, const void* v_uncond, const void* v_text, void* x_bf16, const float* diff, const float* partials,
+                          float s_minus_1, float eta, float tau, float* hist, float w, const float* src, const float* noise,
+                          const float* mask, float dsigma, float sigma_next, int32_t B, int64_t n_s, int64_t n_mask, void* stream) {
+  if (!x || !v_uncond || !v_text || !diff || !partials || B < 1 || n_s < 1 || n_mask < 1 || (mask && (!src || !noise))) return RT_E_BADARG;
+  const int64_t chunks = (n_s + RT_GUIDE_CHUNK - 1) / RT_GUIDE_CHUNK;
+  if (B > 65535 || chunks > 0x7fffffff || ((int64_t)B * n_s) % n_mask) return RT_E_SHAPE;
+  // every sample's pointers are aligned when the first one's are and n_s % 4 == 0; a mask's period is then a multiple of 4 too, or
+  // it is the whole of [B][n_s]
+  const bool vec = n_s % 4 == 0 && RT_ALIGNED(x, 16) && RT_ALIGNED(v_text, 8) && RT_ALIGNED(diff, 16) && (!x_bf16 || RT_ALIGNED(x_bf16, 8)) &&
+                   (!mask || ((n_mask % 4 == 0 || n_mask == (int64_t)B * n_s) && RT_ALIGNED(src, 16) && RT_ALIGNED(noise, 16) &&
+                              RT_ALIGNED(mask, 16))) &&
+                   (!hist || RT_ALIGNED(hist, 16));
+  const int64_t n4 = vec ? n_s / 4 : 0;
+  const auto kernel = mask ? (hist ? projected_step_f32_kernel<true, true> : projected_step_f32_kernel<true, false>)
+                           : (hist ? projected_step_f32_kernel<false, true> : projected_step_f32_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(grid_for(n4 > 0 ? n4 : n_s, 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream, x,
+                     (const bf16_t*)v_text, (bf16_t*)x_bf16, diff, partials, (int)chunks, s_minus_1, eta, tau, src, noise, mask, hist, dsigma,
+                     sigma_next, w, n_s, n_mask, n4);
+  return rt_hip_status();
 }
 
 int rt_cfg_mix(const void* v_uncond, const void* v_text, void* out, float s, int64_t n, void* stream) {

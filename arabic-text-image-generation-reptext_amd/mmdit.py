@@ -320,8 +320,9 @@ class ModulationTable:
     def _widths(doubles, singles, out_lin):
         return [w for pl in doubles for w in (pl.ada_img.w, pl.ada_txt.w)] + [pl.ada.w for pl in singles] + ([out_lin.weight.data] if out_lin is not None else [])
 
-    def step(self, i: int) -> StepMods:
-        r = slice(i * self.B, (i + 1) * self.B)
+    def step(self, i: int, rows: Optional[slice] = None) -> StepMods:
+        """The rows of step i, or with ``rows`` a slice of them (the positive half of a true-CFG table is the second half). Views."""
+        r = slice(i * self.B, (i + 1) * self.B) if rows is None else slice(i * self.B + rows.start, i * self.B + rows.stop)
         return StepMods([(a[r], b[r]) for a, b in self.double], [s[r] for s in self.single], None if self.out is None else self.out[r])
 
 

@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import torch
 
@@ -744,6 +744,46 @@ def multistep_step_f32_(x32: torch.Tensor, v: torch.Tensor, hist32: torch.Tensor
     blend under ``mask`` and the bf16 copy as in the three steps above. ``w`` = 0: hist32 is written and not read (it may be
     uninitialised) and x32 gets the bits of the step above that the other arguments select."""
     return _master_step_f32("multistep_step_f32_", x32, v, v_text, s, dsigma, x_bf16, sigma_next, src32, noise32, mask, hist32, w)
+
+
+def guidance_partials_shape(B: int, n_s: int) -> Tuple[int, int, int]:
+    """Shape of the fp32 workspace of the projected step for a state of B samples of n_s elements (rt_guidance_ws_bytes(B, n_s) bytes)."""
+    return int(B), -(-int(n_s) // native.RT_GUIDE_CHUNK), 3
+
+
+def projected_step_f32_(x32: torch.Tensor, v_uncond: torch.Tensor, v_text: torch.Tensor, diff32: torch.Tensor, partials: torch.Tensor, s: float,
+                        eta: float, norm_threshold: float, beta: float, dsigma: float, x_bf16: Optional[torch.Tensor] = None, *,
+                        hist32: Optional[torch.Tensor] = None, w: float = 0.0, sigma_next: float = 0.0, src32: Optional[torch.Tensor] = None,
+                        noise32: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The fp32 master step with projected guidance (guidance.py), two launches: rt_guidance_reduce_f32 — diff32 = (v_text − v_uncond)
+    + beta·diff32 in fp32 and, per sample and chunk, the partial sums of (d², d·p, p²) in a fixed order — then the step with
+    vel = p + (s − 1)·(k·d + e·p) in the mixed velocity's place — the multistep part (``hist32``, ``w``), the blend under ``mask`` and
+    the bf16 copy as in the other steps. ``diff32`` (fp32, x32's shape) and ``partials`` are the caller's; ``beta`` is the momentum, 0
+    for the first guided step of a run: diff32 is then written and not read, it may be uninitialised. x32's leading dimension is the
+    batch: the sums are per sample."""
+    name = "projected_step_f32_"
+    if x32.dim() < 2 or x32.numel() < 1:
+        raise ValueError(f"{name}: the state needs a leading batch dimension and at least one element, got shape {tuple(x32.shape)}")
+    if mask is not None and (src32 is None or noise32 is None):
+        raise ValueError(f"{name}: a mask needs src32 and noise32")
+    like = [v_uncond, v_text, diff32] + [t for t in (src32, noise32, hist32) if t is not None]
+    if not all(t.is_contiguous() for t in [x32, partials, *like] + ([] if mask is None else [mask])) or not all(t.shape == x32.shape for t in like):
+        raise ValueError(f"{name}: contiguous tensors of equal shape")
+    B, n_s = x32.shape[0], x32.numel() // x32.shape[0]
+    if tuple(partials.shape) != guidance_partials_shape(B, n_s):
+        raise ValueError(f"{name}: partials must be {guidance_partials_shape(B, n_s)} (guidance_partials_shape), got {tuple(partials.shape)}")
+    if x_bf16 is not None and (x_bf16.shape != x32.shape or not x_bf16.is_contiguous()):
+        raise ValueError("x_bf16 must match x32")
+    if mask is not None and mask.shape != x32.shape and tuple(mask.shape) != (1,) + tuple(x32.shape[1:]):
+        raise ValueError(f"{name}: mask {tuple(mask.shape)} is neither x32's shape {tuple(x32.shape)} nor that of one sample")
+    x, xb = _dev(x32, "x32", F32), _opt(x_bf16, "x_bf16", BF16)
+    pu, pt, pd, pp = _dev(v_uncond, "v_uncond", BF16), _dev(v_text, "v_text", BF16), _dev(diff32, "diff32", F32), _dev(partials, "partials", F32)
+    rest = (_opt(hist32, "hist32", F32), float(w), _opt(src32 if mask is not None else None, "src32", F32),
+            _opt(noise32 if mask is not None else None, "noise32", F32), _opt(mask, "mask", F32))
+    native.call("rt_guidance_reduce_f32", pu, pt, pd, float(beta), pp, B, n_s, _stream())
+    native.call("rt_projected_step_f32", x, pu, pt, xb, pd, pp, float(s) - 1.0, float(eta), float(norm_threshold), *rest, float(dsigma),
+                float(sigma_next), B, n_s, x32.numel() if mask is None else mask.numel(), _stream())
+    return x32
 
 
 def cfg_mix(v_uncond: torch.Tensor, v_text: torch.Tensor, s: float) -> torch.Tensor:

@@ -28,6 +28,7 @@ import torch.nn.functional as F
 from . import ops
 from .controlnet import FluxControlNetModel, FluxMultiControlNetModel, active_row_window
 from .image_processor import PipelineImageInput, VaeImageProcessor
+from .guidance import Guidance, ProjectedStep, loop_guidance
 from .scheduler import FlowMatchEulerDiscreteScheduler, FlowMatchMultistepScheduler, calculate_shift
 from .transformer import FluxTransformer2DModel
 from .utils import randn_tensor
@@ -222,6 +223,9 @@ class LoopExtras:
     extra_towers: Tuple = ()
     velocity: Optional[Callable] = None          # (i, noise_pred) -> what the scheduler steps with in its place (the inpaint flow's CFG)
     repaint: Optional[Repaint] = None            # the step also blends the re-noised source back in (pipeline_repaint.py)
+    # under true CFG, a guider that changes the call (guidance.Guidance: the guider and the steps it guides): projected guidance at
+    # those steps, and the steps outside them run on the positive half alone, at the latents' batch B; None: every step is the CFG step
+    guidance: Optional[Guidance] = None
     quiet: bool = False                          # no progress bar (a capture)
 
 
@@ -254,6 +258,9 @@ class FluxControlNetPipeline:
         # a second, unmasked ControlNet with its own step window beside the text-line tower (Union-Pro-2.0: canny / depth / pose); set
         # by from_pretrained(controlnet_union=) or assigned, fed by __call__(control_image_union=...) — base pipeline only
         self.controlnet_union: Optional[FluxControlNetModel] = None
+        # what a true-CFG call adds to the plain mix at every step: a guidance interval and projected guidance (guidance.TrueCFGGuider);
+        # assigned, read by a call with a negative prompt — not a component, not saved
+        self.guider = None
 
     # ------------------------------------------------------------------ component plumbing
     @property
@@ -959,7 +966,8 @@ class FluxControlNetPipeline:
         masks = [self._doubled_under_cfg(m, total, cfg, mask=True) for m in self._region_masks(control_mask, latents.device, prompt_embeds.dtype)]
         active = union_active_steps(len(timesteps), float(ext.control_guidance_start_union), float(ext.control_guidance_end_union)) if with_union else ()
         union = UnionTower(self.controlnet_union, union_hint, float(ext.controlnet_conditioning_scale_union), active) if active else None
-        extras = LoopExtras(ip_embeds=ip_embeds, union=union, cfg_scale=float(ext.true_cfg_scale) if cfg else None, repaint=repaint)
+        extras = LoopExtras(ip_embeds=ip_embeds, union=union, cfg_scale=float(ext.true_cfg_scale) if cfg else None, repaint=repaint,
+                            guidance=loop_guidance(self.guider, cfg, len(timesteps)))
 
         self._apply_lora_scale()
         latents = self._denoise(latents, prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids, timesteps, hints, masks,
@@ -1068,7 +1076,7 @@ class FluxControlNetPipeline:
         win = active_row_window(masks, latents.shape[1]) if masks and len(masks) == len(hints) else None
         extras = replace(extras or LoopExtras(), tower_window=win)
         # under true CFG (cfg_scale) prompt_embeds / pooled / hints hold [negative, positive]
-        ipe, union, cfg_scale, repaint = extras.ip_embeds, extras.union, extras.cfg_scale, extras.repaint
+        ipe, union, cfg_scale, repaint, guidance = extras.ip_embeds, extras.union, extras.cfg_scale, extras.repaint, extras.guidance
 
         def eager(callback=None):
             return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
@@ -1107,6 +1115,11 @@ class FluxControlNetPipeline:
             # source, noise and mask are three more static inputs; the sigmas the blend re-noises to are in the key already
             key += (("repaint", sig(repaint.src32), sig(repaint.noise32), sig(repaint.mask)),)
             ins.update(repaint_src=repaint.src32, repaint_noise=repaint.noise32, repaint_mask=repaint.mask)
+        if guidance is not None:
+            # which steps are guided and the guider's three numbers are host scalars baked into the capture; the guidance difference
+            # and the partial sums are allocated inside the capture, in the graph's pool, like the fp32 state
+            g = guidance.guider
+            key += (("guidance", guidance.steps, float(g.eta), float(g.norm_threshold), float(g.momentum)),)
         solver_order = getattr(self.scheduler, "solver_order", 1)
         if solver_order > 1:
             # the multistep weights are kernel scalars of every step, fixed by the sigmas and the timesteps that are in the key already;
@@ -1280,6 +1293,29 @@ class FluxControlNetPipeline:
         latents = latents.to(torch.bfloat16).contiguous().clone()
         # a multistep scheduler's velocity of the step before, fp32 like the state and owned here; its first step does not read it
         hist = dict(history=torch.empty_like(lat32)) if getattr(self.scheduler, "solver_order", 1) > 1 else {}
+        # A guider (true CFG only). At its steps the loop is the CFG loop, with the projected step where the guider asks for it: the
+        # guidance difference of the step before and the partial sums are fp32 buffers owned here, beside the state. At the other steps
+        # there is no negative half to evaluate: the models run on the positive half at batch B, through views of what the call prepared
+        # at 2B (``cat([negative, positive])``: the positive half is the contiguous slice [B:] of every conditioning tensor).
+        gd = extras.guidance
+        guided_at = None if gd is None else frozenset(gd.steps)
+        proj = None
+        if gd is not None and gd.guider.projected and gd.steps:
+            proj = ProjectedStep(gd.guider.eta, gd.guider.norm_threshold, gd.guider.momentum, torch.empty_like(lat32),
+                                 torch.empty(ops.guidance_partials_shape(B, lat32[0].numel()), device=device, dtype=torch.float32))
+        Bc = prompt_embeds.shape[0]
+        pos_rows = slice(Bc - B, Bc)
+
+        def positive_half(pe, st):
+            """(prompt, pooled, transformer's static embeddings, towers, sample buffers, single buffers, image prompt) of the positive half."""
+            pos = lambda t: t if t is None or t.shape[0] != Bc else t[Bc - B:]
+            tws = [replace(tw, hint=pos(tw.hint), rowscale=tw.rowscale if tw.rowscale is None or tw.rowscale.dim() == 1 else pos(tw.rowscale),
+                           static=replace(tw.static, ctx=pos(tw.static.ctx), hint=pos(tw.static.hint))) for tw in towers]
+            ip = ip_prep and replace(ip_prep, kv=[(pos(k), pos(v)) for k, v in ip_prep.kv], tok=pos(ip_prep.tok))
+            lead = lambda bufs: None if bufs is None else [b[:B] for b in bufs]
+            return pos(pe), pos(pooled), replace(st, ctx=pos(st.ctx), hint=pos(st.hint)), tws, lead(sample_buf), lead(single_buf), ip
+
+        half = positive_half(prompt_embeds, static_t) if gd is not None and len(gd.steps) < len(tvals) else None
         # Tower ∥ transformer: within a step the tower's chain of kernels and the transformer's are independent except that
         # transformer block i consumes tower sample i // 4 (A.3). The tower therefore runs on a side stream into preallocated
         # sample buffers and the transformer waits, block by block, on the event of the sample it needs. At batch 1 most
@@ -1302,6 +1338,11 @@ class FluxControlNetPipeline:
                 if self.interrupt:
                     continue
                 timestep = torch.full((B,), self._model_timestep(t), device=device, dtype=torch.float32)      # PIPE:1025,1048 (Q4)
+                # the conditioning this step sees: everything (under true CFG at 2B), or the positive half outside a guider's interval
+                guided = guided_at is None or i in guided_at
+                everything = (prompt_embeds, pooled, static_t, towers, sample_buf, single_buf, ip_prep)
+                c_pe, c_pooled, c_static, c_towers, c_samples, c_singles, c_ip = everything if guided else half
+                rows = None if guided else pos_rows        # of the modulation tables, which hold 2B rows per step
                 merged = merged_single = events = None
                 if steps[i]:
                     if overlap:
@@ -1316,13 +1357,14 @@ class FluxControlNetPipeline:
                             dirty = False
                         done_d = done_s = 0       # leading buffers already written in this step: the zero-linear epilogues add to those
                         for n, (k, pos) in enumerate(steps[i]):
-                            tw = towers[k]
+                            tw = c_towers[k]
                             bs, ss = tw.model(
                                 hidden_states=latents, controlnet_cond=tw.hint, controlnet_mode=control_mode, conditioning_scale=tw.scale,
-                                timestep=timestep, guidance=guidance, pooled_projections=pooled, encoder_hidden_states=prompt_embeds,
+                                timestep=timestep, guidance=guidance, pooled_projections=c_pooled, encoder_hidden_states=c_pe,
                                 txt_ids=text_ids, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs, return_dict=False,
-                                _rowscale=tw.rowscale, _accumulate_into=sample_buf, _accumulate_single_into=single_buf, _overwrite=(done_d, done_s),
-                                _sample_events=events if n == len(steps[i]) - 1 else None, _mods=tw.table.step(pos), _static=tw.static,
+                                _rowscale=tw.rowscale, _accumulate_into=c_samples, _accumulate_single_into=c_singles, _overwrite=(done_d, done_s),
+                                _sample_events=events if n == len(steps[i]) - 1 else None,
+                                _mods=tw.table.step(pos) if rows is None else tw.table.step(pos, rows), _static=tw.static,
                                 _ws_tag="tower" if overlap else "", _blocks_needed=blocks_needed, _window=window if tw.masked else None)
                             done_d = max(done_d, sum(b is not None for b in bs or ()))
                             done_s = max(done_s, sum(b is not None for b in ss or ()))
@@ -1330,20 +1372,25 @@ class FluxControlNetPipeline:
                             for ev in events[done_d:need_d]:   # the transformer waits on these; a shallower union tower alone left them
                                 ev.record(torch.cuda.current_stream())
                     # buffers no tower of this step wrote are not injected (None), the block-to-sample map keeps the first tower's depth
-                    merged = [b if j < done_d else None for j, b in enumerate(sample_buf)] or None
-                    merged_single = [b if j < done_s else None for j, b in enumerate(single_buf)] or None
+                    merged = [b if j < done_d else None for j, b in enumerate(c_samples)] or None
+                    merged_single = [b if j < done_s else None for j, b in enumerate(c_singles)] or None
                 noise_pred = self.transformer(
-                    hidden_states=latents, timestep=timestep, guidance=guidance, pooled_projections=pooled,
-                    encoder_hidden_states=prompt_embeds, controlnet_block_samples=merged, controlnet_single_block_samples=merged_single,
+                    hidden_states=latents, timestep=timestep, guidance=guidance, pooled_projections=c_pooled,
+                    encoder_hidden_states=c_pe, controlnet_block_samples=merged, controlnet_single_block_samples=merged_single,
                     txt_ids=text_ids, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs, return_dict=False,
-                    _mods=tab_t.step(i), _sample_events=events, _static=static_t, _ip=ip_prep)[0]
+                    _mods=tab_t.step(i) if rows is None else tab_t.step(i, rows), _sample_events=events, _static=c_static, _ip=c_ip)[0]
                 if events is not None:
                     torch.cuda.current_stream().wait_stream(side)     # the tower has finished reading `latents` (its last sample is unused, Q5)
                 if extras.velocity is not None:
                     noise_pred = extras.velocity(i, noise_pred)
-                cfg = extras.cfg_scale is not None             # then noise_pred is [negative, positive], B each
+                cfg = extras.cfg_scale is not None and guided  # then noise_pred is [negative, positive], B each
+                pj = {}
+                if cfg and proj is not None:
+                    pj = dict(projected=proj)                  # this step's guidance difference goes where the one before is read from
                 self.scheduler.step_master_(noise_pred[:B] if cfg else noise_pred, lat32, latents, v_text=noise_pred[B:] if cfg else None,
-                                            s=extras.cfg_scale, repaint=extras.repaint, **hist)
+                                            s=extras.cfg_scale if cfg else None, repaint=extras.repaint, **hist, **pj)
+                if pj:
+                    proj.first = False
                 if callback is not None:
                     env = {"latents": latents, "prompt_embeds": prompt_embeds}
                     out = callback(self, i, timesteps[i], {k: env[k] for k in callback_inputs})
@@ -1352,9 +1399,12 @@ class FluxControlNetPipeline:
                         lat32 = latents.to(torch.float32)
                         if hist:
                             self.scheduler.reset_history()       # the velocity before belongs to the replaced state: first order next
+                        if proj is not None:
+                            proj.first = True                    # and so does the guidance difference: no momentum next
                     if "prompt_embeds" in out:                       # the loop-invariant embeddings are no longer valid
                         prompt_embeds = out.pop("prompt_embeds")
                         static_t = prepare_static(prompt_embeds)
+                        half = half and positive_half(prompt_embeds, static_t)
                 if i == len(tvals) - 1 or ((i + 1) > num_warmup and (i + 1) % self.scheduler.order == 0):
                     bar.update()
         self._master_latents = lat32          # fp32 state of the loop; `latents` is its bf16 copy

@@ -106,6 +106,9 @@ class FluxControlNetPipeline(_BasePipeline):
                  controlnet_conditioning_scale_inpaint: Union[float, List[float]] = 1.0,
                  negative_prompt_embeds: Optional[torch.FloatTensor] = None,
                  negative_pooled_prompt_embeds: Optional[torch.FloatTensor] = None):
+        if self.guider is not None:
+            # this flow keeps the reference's own CFG (LoopExtras.velocity, the zero-velocity first step): no interval, no projection
+            raise ValueError("the inpaint pipeline does not support pipe.guider (a guidance interval or projected guidance); set it to None")
         height = height or self.default_sample_size * self.vae_scale_factor
         width = width or self.default_sample_size * self.vae_scale_factor
         self.check_inputs(prompt, prompt_2, height, width, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds,

@@ -463,6 +463,31 @@ int rt_repaint_euler_step_f32(float* x, const void* v, const void* v_text /* nul
 int rt_multistep_step_f32(float* x, const void* v, const void* v_text /* nullable */, void* x_bf16 /* nullable */, float* hist, float w,
                           const float* src /* nullable */, const float* noise /* nullable */, const float* mask /* nullable */,
                           float s, float dsigma, float sigma_next, int64_t n, int64_t n_mask, void* stream);
+/* Projected guidance (APG, as diffusers' guider is recalled; parity unpinned) in the same step: one more form of the velocity, which
+ * needs three sums per SAMPLE over its n_s elements. With p = v_text, u = v_uncond (bf16, widened), all in fp32:
+ *   d = (p − u) + beta·diff_old           beta = 0 on the first guided step of a run: diff is then written and never read
+ *   a = Σ d²,  b = Σ d·p,  c = Σ p²
+ *   k = tau > 0 and a > tau² ? tau/√a : 1;   alpha = c > 0 ? k·b/c : 0;   e = (eta − 1)·alpha
+ *   vel = p + s_minus_1·(k·d + e·p)        then vel2, r, hist, the blend and x_bf16 as in rt_multistep_step_f32
+ * Two launches, no atomics. rt_guidance_reduce_f32 writes d to diff (fp32 [B][n_s]) and, per chunk of RT_GUIDE_CHUNK elements of a
+ * sample, one (a, b, c) triple to partials (fp32 [B][ceil(n_s / RT_GUIDE_CHUNK)][3], rt_guidance_ws_bytes(B, n_s) bytes; 0 for sizes
+ * < 1). Where an element is added is a function of its index inside the sample alone: thread (i / 4) % 256 of chunk i / 4096 takes it
+ * as its (4·((i % 4096) / 1024) + i % 4)-th term, a wave adds its lanes in a fixed xor butterfly, one thread adds the four waves. So
+ * the sums have the same bits with 8- and 16-byte loads (n_s % 4 == 0, v_* 8-byte and diff 16-byte aligned) and one element at a
+ * time, and do not depend on B or on the other samples. rt_projected_step_f32 adds a sample's partials in index order in double,
+ * forms k and e in double, rounds each to float once (every workgroup of a sample: the same bits) and steps. v_uncond is not read by
+ * it (d is in diff); it is in the list so that the pair takes one set of arguments. hist / src / noise / mask are optional as above;
+ * m = mask[i % n_mask] over the flat index i of [B][n_s]. 16-byte groups are taken only when n_s % 4 == 0, so none straddles a sample.
+ * NULL v_uncond / v_text / diff / partials (/ x), B < 1, n_s < 1, n_mask < 1, a mask without src and noise: RT_E_BADARG;
+ * B > 65535, (B·n_s) % n_mask != 0: RT_E_SHAPE. Added without an ABI bump: nothing existing changed. */
+#define RT_GUIDE_CHUNK 4096
+int64_t rt_guidance_ws_bytes(int32_t B, int64_t n_s);
+int rt_guidance_reduce_f32(const void* v_uncond, const void* v_text, float* diff, float beta, float* partials, int32_t B, int64_t n_s,
+                           void* stream);
+int rt_projected_step_f32(float* x, const void* v_uncond, const void* v_text, void* x_bf16 /* nullable */, const float* diff,
+                          const float* partials, float s_minus_1, float eta, float tau, float* hist /* nullable */, float w,
+                          const float* src /* nullable */, const float* noise /* nullable */, const float* mask /* nullable */,
+                          float dsigma, float sigma_next, int32_t B, int64_t n_s, int64_t n_mask, void* stream);
 
 /* _pack_latents / _unpack_latents (PIPE:550-570): [B][C][2h][2w] <-> [B][h*w][4C], channel order (c,dy,dx).
  * unpack also applies z/scaling + shift (PIPE:1137) and writes NHWC bf16 [B][H2][W2][C]. */

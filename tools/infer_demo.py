@@ -15,6 +15,10 @@ encoders, which sit outside the hot path. With real checkpoints on disk use `Flu
     python tools/infer_demo.py --negative-prompt "blurry letters, extra text" --true-cfg-scale 3.5   # true CFG in the text-to-image flow:
                                               # internal batch 2, [negative, positive]; without text encoders the negative embeddings are
                                               # random tensors seeded by the text (with checkpoints: negative_prompt= goes through encode_prompt)
+    python tools/infer_demo.py --negative-prompt "blurry letters" --true-cfg-scale 3.5 --guidance-interval 0 0.5 --apg-eta 0 --apg-norm-threshold 15 \
+                               --apg-momentum -0.5   # a guider on the true-CFG call (pipe.guider): the negative half is evaluated on the first
+                                              # half of the steps only (the others run at batch 1), and at those steps the guidance is projected
+                                              # (APG); the four flags have an effect only with --negative-prompt
     python tools/infer_demo.py --source-image photo.jpg [--strength 0.6]   # repaint: the two lines are rendered INTO the photo by latent-blend
                                               # inpainting (FluxControlNetRepaintPipeline): the last strength·steps steps from the noised
                                               # photo, the photo put back outside the lines' boxes after every step; no second tower, no CFG
@@ -52,6 +56,11 @@ ap.add_argument("--union-scale", type=float, default=0.7)
 ap.add_argument("--union-end", type=float, default=0.8)
 ap.add_argument("--negative-prompt", default=None, help="negative prompt of the text-to-image flow (true CFG; needs --true-cfg-scale > 1)")
 ap.add_argument("--true-cfg-scale", type=float, default=1.0)
+ap.add_argument("--guidance-interval", type=float, nargs=2, default=(0.0, 1.0), metavar=("START", "STOP"),
+                help="with --negative-prompt: true CFG on this share of the steps that run only")
+ap.add_argument("--apg-eta", type=float, default=1.0, help="projected guidance: weight of the difference's component parallel to the positive prediction")
+ap.add_argument("--apg-norm-threshold", type=float, default=0.0, help="projected guidance: clamp of the difference's per-sample norm (0: none)")
+ap.add_argument("--apg-momentum", type=float, default=0.0, help="projected guidance: beta of the running difference (APG's usual value: -0.5)")
 ap.add_argument("--source-image", default=None, help="photo to render the text into (the repaint pipeline's image=; the mask is the union of the lines' boxes)")
 ap.add_argument("--strength", type=float, default=0.6, help="share of the schedule a repaint runs")
 ap.add_argument("--photo-crop", type=int, default=None, help="with --source-image: keep the photo at its size and repaint only the region around "
@@ -155,6 +164,11 @@ if a.negative_prompt is not None:
     gn = torch.Generator().manual_seed(zlib.crc32(a.negative_prompt.encode("utf-8")))     # no text encoders here: embeddings named by the text
     ip_kwargs.update(negative_prompt_embeds=torch.randn(1, 512, 4096, generator=gn).to(dev, bf16),
                      negative_pooled_prompt_embeds=torch.randn(1, 768, generator=gn).to(dev, bf16), true_cfg_scale=a.true_cfg_scale)
+    from reptext_amd.guidance import TrueCFGGuider
+
+    # a plain attribute of the pipeline; the default values are the plain CFG call
+    pipe.guider = TrueCFGGuider(start=a.guidance_interval[0], stop=a.guidance_interval[1], eta=a.apg_eta, norm_threshold=a.apg_norm_threshold,
+                                momentum=a.apg_momentum)
 elif a.true_cfg_scale != 1.0:
     ip_kwargs.update(true_cfg_scale=a.true_cfg_scale)                               # logs one line: no negative prompt, CFG stays off
 
