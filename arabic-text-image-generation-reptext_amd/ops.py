@@ -687,6 +687,21 @@ def euler_step_(x: torch.Tensor, v: torch.Tensor, dsigma: float) -> torch.Tensor
     return x
 
 
+def _check_master_step(name: str, x32: torch.Tensor, like, x_bf16: Optional[torch.Tensor], src32: Optional[torch.Tensor],
+                       noise32: Optional[torch.Tensor], mask: Optional[torch.Tensor], contiguous=()) -> None:
+    """The argument checks of every fp32 master step (``name``, for the messages): what is given of ``like``, src32 and noise32 has
+    x32's shape and is contiguous, as are ``contiguous`` and the mask, which has x32's shape or that of one sample; x_bf16 matches x32."""
+    if mask is not None and (src32 is None or noise32 is None):
+        raise ValueError(f"{name}: a mask needs src32 and noise32")
+    like = [t for t in (*like, src32, noise32) if t is not None]
+    if not all(t.is_contiguous() for t in [x32, *contiguous, *like] + ([] if mask is None else [mask])) or not all(t.shape == x32.shape for t in like):
+        raise ValueError(f"{name}: contiguous tensors of equal shape")
+    if x_bf16 is not None and (x_bf16.shape != x32.shape or not x_bf16.is_contiguous()):
+        raise ValueError("x_bf16 must match x32")
+    if mask is not None and mask.shape != x32.shape and not (x32.dim() > 1 and tuple(mask.shape) == (1,) + tuple(x32.shape[1:])):
+        raise ValueError(f"{name}: mask {tuple(mask.shape)} is neither x32's shape {tuple(x32.shape)} nor that of one sample")
+
+
 def _master_step_f32(name: str, x32: torch.Tensor, v: torch.Tensor, v_text: Optional[torch.Tensor], s: float, dsigma: float,
                      x_bf16: Optional[torch.Tensor], sigma_next: float = 0.0, src32: Optional[torch.Tensor] = None,
                      noise32: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None,
@@ -694,15 +709,7 @@ def _master_step_f32(name: str, x32: torch.Tensor, v: torch.Tensor, v_text: Opti
     """The body of euler_step_f32_ / cfg_euler_step_f32_ / repaint_euler_step_f32_ / multistep_step_f32_ (``name``, for the messages):
     the checks, and the entry that what is given selects. One fp32 master step x32 += dsigma·vel, vel = v or v + s·(v_text − v); with a
     mask, the blend; with ``hist`` (the fp32 velocity of the step before, replaced by this step's), vel + w·(vel − hist) in vel's place."""
-    if hist is not None and mask is not None and (src32 is None or noise32 is None):
-        raise ValueError(f"{name}: a mask needs src32 and noise32")
-    like = [t for t in (v, v_text, src32, noise32, hist) if t is not None]
-    if not all(t.is_contiguous() for t in [x32, *like] + ([] if mask is None else [mask])) or not all(t.shape == x32.shape for t in like):
-        raise ValueError(f"{name}: contiguous tensors of equal shape")
-    if x_bf16 is not None and (x_bf16.shape != x32.shape or not x_bf16.is_contiguous()):
-        raise ValueError("x_bf16 must match x32")
-    if mask is not None and mask.shape != x32.shape and not (x32.dim() > 1 and tuple(mask.shape) == (1,) + tuple(x32.shape[1:])):
-        raise ValueError(f"{name}: mask {tuple(mask.shape)} is neither x32's shape {tuple(x32.shape)} nor that of one sample")
+    _check_master_step(name, x32, (v, v_text, hist), x_bf16, src32, noise32, mask)
     x, xb, n = _dev(x32, "x32", F32), _opt(x_bf16, "x_bf16", BF16), x32.numel()
     if hist is not None:
         native.call("rt_multistep_step_f32", x, _dev(v, "v", BF16), _opt(v_text, "v_text", BF16), xb, _dev(hist, "hist", F32), float(w),
@@ -764,18 +771,10 @@ def projected_step_f32_(x32: torch.Tensor, v_uncond: torch.Tensor, v_text: torch
     name = "projected_step_f32_"
     if x32.dim() < 2 or x32.numel() < 1:
         raise ValueError(f"{name}: the state needs a leading batch dimension and at least one element, got shape {tuple(x32.shape)}")
-    if mask is not None and (src32 is None or noise32 is None):
-        raise ValueError(f"{name}: a mask needs src32 and noise32")
-    like = [v_uncond, v_text, diff32] + [t for t in (src32, noise32, hist32) if t is not None]
-    if not all(t.is_contiguous() for t in [x32, partials, *like] + ([] if mask is None else [mask])) or not all(t.shape == x32.shape for t in like):
-        raise ValueError(f"{name}: contiguous tensors of equal shape")
+    _check_master_step(name, x32, (v_uncond, v_text, diff32, hist32), x_bf16, src32, noise32, mask, contiguous=(partials,))
     B, n_s = x32.shape[0], x32.numel() // x32.shape[0]
     if tuple(partials.shape) != guidance_partials_shape(B, n_s):
         raise ValueError(f"{name}: partials must be {guidance_partials_shape(B, n_s)} (guidance_partials_shape), got {tuple(partials.shape)}")
-    if x_bf16 is not None and (x_bf16.shape != x32.shape or not x_bf16.is_contiguous()):
-        raise ValueError("x_bf16 must match x32")
-    if mask is not None and mask.shape != x32.shape and tuple(mask.shape) != (1,) + tuple(x32.shape[1:]):
-        raise ValueError(f"{name}: mask {tuple(mask.shape)} is neither x32's shape {tuple(x32.shape)} nor that of one sample")
     x, xb = _dev(x32, "x32", F32), _opt(x_bf16, "x_bf16", BF16)
     pu, pt, pd, pp = _dev(v_uncond, "v_uncond", BF16), _dev(v_text, "v_text", BF16), _dev(diff32, "diff32", F32), _dev(partials, "partials", F32)
     rest = (_opt(hist32, "hist32", F32), float(w), _opt(src32 if mask is not None else None, "src32", F32),

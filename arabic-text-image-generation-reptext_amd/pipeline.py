@@ -1292,7 +1292,7 @@ class FluxControlNetPipeline:
         lat32 = latents.to(torch.float32).contiguous()
         latents = latents.to(torch.bfloat16).contiguous().clone()
         # a multistep scheduler's velocity of the step before, fp32 like the state and owned here; its first step does not read it
-        hist = dict(history=torch.empty_like(lat32)) if getattr(self.scheduler, "solver_order", 1) > 1 else {}
+        hist = torch.empty_like(lat32) if getattr(self.scheduler, "solver_order", 1) > 1 else None
         # A guider (true CFG only). At its steps the loop is the CFG loop, with the projected step where the guider asks for it: the
         # guidance difference of the step before and the partial sums are fp32 buffers owned here, beside the state. At the other steps
         # there is no negative half to evaluate: the models run on the positive half at batch B, through views of what the call prepared
@@ -1384,20 +1384,18 @@ class FluxControlNetPipeline:
                 if extras.velocity is not None:
                     noise_pred = extras.velocity(i, noise_pred)
                 cfg = extras.cfg_scale is not None and guided  # then noise_pred is [negative, positive], B each
-                pj = {}
-                if cfg and proj is not None:
-                    pj = dict(projected=proj)                  # this step's guidance difference goes where the one before is read from
+                pj = proj if cfg else None                     # this step's guidance difference goes where the one before is read from
                 self.scheduler.step_master_(noise_pred[:B] if cfg else noise_pred, lat32, latents, v_text=noise_pred[B:] if cfg else None,
-                                            s=extras.cfg_scale if cfg else None, repaint=extras.repaint, **hist, **pj)
-                if pj:
-                    proj.first = False
+                                            s=extras.cfg_scale if cfg else None, repaint=extras.repaint, history=hist, projected=pj)
+                if pj is not None:
+                    pj.first = False
                 if callback is not None:
                     env = {"latents": latents, "prompt_embeds": prompt_embeds}
                     out = callback(self, i, timesteps[i], {k: env[k] for k in callback_inputs})
                     if "latents" in out:
                         latents = out.pop("latents").to(torch.bfloat16).contiguous()
                         lat32 = latents.to(torch.float32)
-                        if hist:
+                        if hist is not None:
                             self.scheduler.reset_history()       # the velocity before belongs to the replaced state: first order next
                         if proj is not None:
                             proj.first = True                    # and so does the guidance difference: no momentum next

@@ -102,32 +102,40 @@ class FlowMatchEulerDiscreteScheduler:
         self._step_index = i + 1
         return self.sigmas[i], self.sigmas[i + 1]
 
+    def _advance_weight(self):
+        """``_advance`` plus the multistep weight of the step about to be taken: 0, the Euler rule."""
+        return (*self._advance(), 0.0)
+
+    def _history(self, history: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """The history the step uses: the Euler rule has none (returns None) and refuses one."""
+        if history is not None:
+            raise TypeError("step_master_: history= belongs to the multistep scheduler, the Euler scheduler keeps no velocity")
+
     def step_master_(self, v: torch.Tensor, sample32: torch.Tensor, sample_bf16: Optional[torch.Tensor] = None, *,
-                     v_text: Optional[torch.Tensor] = None, s: Optional[float] = None, repaint=None, projected=None) -> None:
-        """In-place Euler step on an fp32 master copy of the latents (used by this repo's pipelines between steps; ``step`` keeps
+                     v_text: Optional[torch.Tensor] = None, s: Optional[float] = None, repaint=None,
+                     history: Optional[torch.Tensor] = None, projected=None) -> None:
+        """In-place step on an fp32 master copy of the latents (used by this repo's pipelines between steps; ``step`` keeps
         the diffusers contract of returning the model dtype), one kernel. Advances the step index exactly like ``step``.
         ``v_text``: true CFG, the velocity is ``v + s·(v_text − v)`` (``v`` the unconditional half), mixed in fp32 inside the kernel and
         not rounded to bf16 before the state takes it. ``repaint`` (a record with ``src32``, ``noise32``, ``mask``): where ``mask`` is 0
         the state becomes the source re-noised to the NEXT sigma, ``scale_noise(src32, sigmas[i + 1], noise32)`` — the source itself
         after the last step. ``projected`` (a ``guidance.ProjectedStep``; needs ``v_text`` and ``s``): projected guidance in the mix's
-        place, two kernels; its ``diff`` receives this step's guidance difference and is read unless ``projected.first``."""
-        sigma, sigma_next = self._advance()
-        if projected is not None:
-            return self._projected_step(v, v_text, s, projected, sample32, sample_bf16, sigma, sigma_next, repaint)
-        v_text = None if v_text is None else v_text.contiguous()
+        place, two kernels; its ``diff`` receives this step's guidance difference and is read unless ``projected.first`` (no momentum
+        on the first guided step of a run); ``s − 1`` is formed from the scale in double inside the op. ``history`` (the multistep
+        scheduler's; fp32, the state's shape) is read unless it is empty — it may then be uninitialised memory — and receives this
+        step's velocity, under true CFG the mixed or projected one in fp32; the blend of a repaint comes after."""
+        history = self._history(history)
+        sigma, sigma_next, w = self._advance_weight()
         rp = {} if repaint is None else dict(sigma_next=float(sigma_next), src32=repaint.src32, noise32=repaint.noise32, mask=repaint.mask)
-        ops._master_step_f32("step_master_", sample32, v.contiguous(), v_text, float(s or 0.0), float(sigma_next - sigma), sample_bf16, **rp)
-
-    @staticmethod
-    def _projected_step(v, v_text, s, projected, sample32, sample_bf16, sigma, sigma_next, repaint, history=None, w: float = 0.0) -> None:
-        """The projected form of ``step_master_`` for both schedulers: ``s − 1`` is formed from the scale in double inside the op, the
-        momentum is 0 on the first guided step of a run."""
-        if v_text is None or s is None:
+        if projected is None:
+            ops._master_step_f32("step_master_", sample32, v.contiguous(), None if v_text is None else v_text.contiguous(), float(s or 0.0),
+                                 float(sigma_next - sigma), sample_bf16, hist=history, w=w, **rp)
+        elif v_text is None or s is None:
             raise ValueError("step_master_: projected= needs v_text= and s= (true CFG)")
-        rp = {} if repaint is None else dict(sigma_next=float(sigma_next), src32=repaint.src32, noise32=repaint.noise32, mask=repaint.mask)
-        ops.projected_step_f32_(sample32, v.contiguous(), v_text.contiguous(), projected.diff, projected.partials, float(s), float(projected.eta),
-                                float(projected.norm_threshold), 0.0 if projected.first else float(projected.momentum),
-                                float(sigma_next - sigma), sample_bf16, hist32=history, w=float(w), **rp)
+        else:
+            ops.projected_step_f32_(sample32, v.contiguous(), v_text.contiguous(), projected.diff, projected.partials, float(s),
+                                    float(projected.eta), float(projected.norm_threshold), 0.0 if projected.first else float(projected.momentum),
+                                    float(sigma_next - sigma), sample_bf16, hist32=history, w=float(w), **rp)
 
     def scale_noise(self, sample: torch.Tensor, sigma_or_timestep, noise: torch.Tensor) -> torch.Tensor:
         """``sigma·noise + (1 − sigma)·sample``: the forward process of flow matching (diffusers' rule, recalled). A value of at most 1 is
@@ -214,30 +222,20 @@ class FlowMatchMultistepScheduler(FlowMatchEulerDiscreteScheduler):
         self.reset_history()
 
     def _advance_weight(self):
-        """``_advance`` plus the weight of the step about to be taken; the history then counts as holding its velocity."""
+        """``_advance`` plus the weight of the step about to be taken; at order 2 the history then counts as holding its velocity."""
+        if self.solver_order == 1:
+            return super()._advance_weight()
         sigma, sigma_next = self._advance()
         i = self._step_index - 1
         w = _multistep_weight(self.sigmas, i) if self._history_len > 0 and i > 0 else 0.0
         self._history_len = 1
         return sigma, sigma_next, w
 
-    def step_master_(self, v: torch.Tensor, sample32: torch.Tensor, sample_bf16: Optional[torch.Tensor] = None, *,
-                     v_text: Optional[torch.Tensor] = None, s: Optional[float] = None, repaint=None,
-                     history: Optional[torch.Tensor] = None, projected=None) -> None:
-        """``FlowMatchEulerDiscreteScheduler.step_master_`` with the multistep rule, one kernel: ``history`` (fp32, the state's shape)
-        is read unless it is empty — it may then be uninitialised memory — and receives this step's velocity, under true CFG the mixed
-        one in fp32 (with ``projected``, the projected one). The blend of a repaint comes after, as it does there."""
-        if self.solver_order == 1:
-            return super().step_master_(v, sample32, sample_bf16, v_text=v_text, s=s, repaint=repaint, projected=projected)
-        if history is None:
+    def _history(self, history: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+        """Order 2 needs the caller's history; order 1 is the Euler rule and leaves one unused."""
+        if self.solver_order > 1 and history is None:
             raise ValueError("step_master_: the multistep scheduler needs history=, an fp32 tensor of the state's shape")
-        sigma, sigma_next, w = self._advance_weight()
-        if projected is not None:
-            return self._projected_step(v, v_text, s, projected, sample32, sample_bf16, sigma, sigma_next, repaint, history, w)
-        v_text = None if v_text is None else v_text.contiguous()
-        rp = {} if repaint is None else dict(src32=repaint.src32, noise32=repaint.noise32, mask=repaint.mask)
-        ops.multistep_step_f32_(sample32, v.contiguous(), history, w, float(sigma_next - sigma), sample_bf16, v_text=v_text,
-                                s=float(s or 0.0), sigma_next=float(sigma_next) if repaint is not None else 0.0, **rp)
+        return history if self.solver_order > 1 else None
 
     def step(self, model_output: torch.Tensor, timestep: Union[float, torch.Tensor], sample: torch.Tensor,
              return_dict: bool = True, **unused):

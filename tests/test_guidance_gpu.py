@@ -1,5 +1,5 @@
 """A guider on a true-CFG call (``pipe.guider``, reptext_amd/guidance.py) on the GPU: parity of the loop with the CPU oracle's
-(tests/guidance_reference.py) for a guidance interval, projected guidance and both under the multistep scheduler; off means off; an
+(tests/loop_reference.py) for a guidance interval, projected guidance and both under the multistep scheduler; off means off; an
 empty interval is the plain call; eager = captured = replay; batch invariance and the loop's toggles; one call each with a repaint,
 the union tower, an image prompt and the fp8 modes; the refusal of the inpaint pipeline and the momentum after a callback.
 256x256 (N = 256, T = 64) with the reduced models of test_vae_pipeline_gpu.py, 4 steps, s = 2.0."""
@@ -15,8 +15,7 @@ from test_true_cfg_gpu import BOXES, graph_keys, negatives, random_pipe, token_m
 from test_vae_pipeline_gpu import SMALL_CN, SMALL_T, rel_l2  # noqa: E402
 
 import ip_adapter_reference as ipr  # noqa: E402
-from cfg_reference import denoise_loop_cfg  # noqa: E402
-from guidance_reference import denoise_loop_guided  # noqa: E402
+from loop_reference import denoise_loop_reference  # noqa: E402
 
 H = W = 256
 N, T, E = 256, 64, 64
@@ -59,12 +58,13 @@ def parity_setup():
     box = (60, 140, 80, 200)
     sig = orc.flow_sigmas(STEPS, orc.calculate_shift(N, 256, 4096, 0.5, 1.15))
     ids = orc.latent_image_ids(32, 32)
-    args = (tp, SMALL_T, cp, SMALL_CN, lat0, pe, pooled, npe, npooled, [hint], [token_mask(box)], sig, ids, torch.zeros(T, 3), 3.5, 2.0)
-    info = {}
-    denoise_loop_guided(*args[:11], sig[:2], *args[12:], guider(eta=0.0), info=info)          # one step: its d is the plain CFG difference
-    plain_cfg = denoise_loop_cfg(*args)
-    plain = orc.denoise_loop(tp, SMALL_T, cp, SMALL_CN, lat0, pe, pooled, [hint], [token_mask(box)], sig, ids, torch.zeros(T, 3), 3.5)
-    _SHARED.update(tp=tp, cp=cp, args=args, box=box, norm_d0=float(info["norm_d"][0]), plain_cfg=plain_cfg, plain=plain,
+    args = (tp, SMALL_T, cp, SMALL_CN, lat0, pe, pooled, [hint], [token_mask(box)], sig, ids, torch.zeros(T, 3), 3.5)
+    neg = dict(prompt_embeds=npe, pooled=npooled, scale=2.0)
+    info = {}                                                       # one step: its d is the plain CFG difference
+    denoise_loop_reference(*args[:9], sig[:2], *args[10:], negative=neg, guider=guider(eta=0.0), info=info)
+    plain_cfg = denoise_loop_reference(*args, negative=neg)
+    plain = orc.denoise_loop(*args)
+    _SHARED.update(tp=tp, cp=cp, args=args, neg=neg, box=box, norm_d0=float(info["norm_d"][0]), plain_cfg=plain_cfg, plain=plain,
                    inputs=dict(pe=pe, pooled=pooled, npe=npe, npooled=npooled, hint=hint, lat0=lat0))
     return _SHARED
 
@@ -87,9 +87,9 @@ def test_guided_loop_matches_the_oracle_loop(gpu, case):
     gd = {"interval": guider(stop=0.5), "projected": guider(eta=0.0, momentum=-0.5, norm_threshold=tau),
           "both_multistep": guider(stop=0.5, eta=0.0, momentum=-0.5, norm_threshold=tau)}[case]
     order = 2 if case == "both_multistep" else 1
-    ref = denoise_loop_guided(*S["args"], gd, order=order)
+    ref = denoise_loop_reference(*S["args"], negative=S["neg"], guider=gd, order=order)
     with orc.stored_as(torch.bfloat16):
-        ref16 = denoise_loop_guided(*S["args"], gd, order=order)
+        ref16 = denoise_loop_reference(*S["args"], negative=S["neg"], guider=gd, order=order)
     floor = rel_l2(ref16, ref)
     felt_cfg, felt_plain = rel_l2(S["plain_cfg"], ref), rel_l2(S["plain"], ref)
     print(f"guided [{case}] floor {floor:.3e}; the plain-CFG loop lies {felt_cfg / floor:.0f} floors away, the plain loop {felt_plain / floor:.0f}")

@@ -1,6 +1,6 @@
 """The host side of a guider on a true-CFG call (reptext_amd/guidance.py): the interval's known answers, the refusals, the two
 properties, the three entries in the header and their refusals without a device, the rule on hand-made vectors in fp64, the reference
-loop's two identities (tests/guidance_reference.py) and what ``_generate`` hands to the loop. No kernel runs here."""
+loop's two identities (tests/loop_reference.py) and what ``_generate`` hands to the loop. No kernel runs here."""
 import ctypes as C
 import math
 
@@ -9,8 +9,7 @@ import torch
 
 from oracle import flux_oracle as orc
 
-from cfg_reference import denoise_loop_cfg
-from guidance_reference import denoise_loop_guided, projected_velocity
+from loop_reference import denoise_loop_reference, projected_velocity
 
 BF16 = torch.bfloat16
 SMALL_T = dict(patch_size=1, in_channels=64, num_layers=2, num_single_layers=2, attention_head_dim=128, num_attention_heads=4,
@@ -230,14 +229,15 @@ def test_the_reference_loop_reduces_to_the_cfg_loop_and_to_the_plain_loop():
     rm = (torch.arange(N) % 3 == 0).float().reshape(1, N, 1)
     sig = orc.flow_sigmas(2, orc.calculate_shift(N, 256, 4096, 0.5, 1.15))
     ids = orc.latent_image_ids(16, 16)
-    args = (tp, SMALL_T, cp, SMALL_CN, lat0, pe, pooled, npe, npooled, [hint], [rm], sig, ids, torch.zeros(T, 3), 3.5, 2.0)
+    args = (tp, SMALL_T, cp, SMALL_CN, lat0, pe, pooled, [hint], [rm], sig, ids, torch.zeros(T, 3), 3.5)
+    kw = dict(conditioning_step=1, negative=dict(prompt_embeds=npe, pooled=npooled, scale=2.0))
     with orc.stored_as(BF16):
-        cfg = denoise_loop_cfg(*args, conditioning_step=1)
-        same = denoise_loop_guided(*args, TrueCFGGuider(), conditioning_step=1)
-        plain = orc.denoise_loop(tp, SMALL_T, cp, SMALL_CN, lat0, pe, pooled, [hint], [rm], sig, ids, torch.zeros(T, 3), 3.5, conditioning_step=1)
-        empty = denoise_loop_guided(*args, TrueCFGGuider(stop=0.0, eta=0.0, momentum=-0.5), conditioning_step=1)
+        cfg = denoise_loop_reference(*args, **kw)
+        same = denoise_loop_reference(*args, **kw, guider=TrueCFGGuider())
+        plain = orc.denoise_loop(*args, conditioning_step=1)
+        empty = denoise_loop_reference(*args, **kw, guider=TrueCFGGuider(stop=0.0, eta=0.0, momentum=-0.5))
         info = {}
-        half = denoise_loop_guided(*args, TrueCFGGuider(stop=0.5, eta=0.0), conditioning_step=1, info=info)
+        half = denoise_loop_reference(*args, **kw, guider=TrueCFGGuider(stop=0.5, eta=0.0), info=info)
     assert torch.equal(same, cfg) and torch.equal(empty, plain)
     assert not torch.equal(cfg, plain) and not torch.equal(half, cfg) and not torch.equal(half, plain)
     assert len(info["norm_d"]) == 1 and float(info["norm_d"][0]) > 0

@@ -1,5 +1,5 @@
 """The second-order multistep scheduler (reptext_amd.scheduler.FlowMatchMultistepScheduler) in the pipelines on the GPU: parity of the
-loop with the CPU oracle's (tests/multistep_reference.py) — plain, under true CFG and in a repaint — and the bitwise properties of the
+loop with the CPU oracle's (tests/loop_reference.py) — plain, under true CFG and in a repaint — and the bitwise properties of the
 call: eager = captured = replay, the Euler call's graph key and result untouched by multistep calls around it, ``solver_order=1`` is
 the Euler call, batch invariance, the loop's toggles, and a callback that hands the latents back makes the next step first order.
 256x256 (N = 256, T = 64) with the reduced models of test_vae_pipeline_gpu.py, 4 steps, like test_repaint_gpu.py."""
@@ -17,9 +17,7 @@ from test_true_cfg_gpu import graph_keys, negatives, random_pipe, token_mask, tw
 from test_true_cfg_host import assert_no_call_state  # noqa: E402
 from test_vae_pipeline_gpu import SMALL_CN, SMALL_T, rel_l2  # noqa: E402
 
-from cfg_reference import denoise_loop_cfg  # noqa: E402
-from multistep_reference import denoise_loop_multistep  # noqa: E402
-from repaint_reference import denoise_loop_repaint  # noqa: E402
+from loop_reference import denoise_loop_reference  # noqa: E402
 
 BF16 = torch.bfloat16
 
@@ -42,9 +40,8 @@ def solver_entries(key):
 def test_multistep_matches_the_oracle_loop(gpu, case):
     """4 steps, one masked text line: GPU error at the bf16-storage oracle's own floor; under true CFG at s = 2; and in a repaint at
     strength 0.75 (3 steps run, from sigma_1, the first of them first order). The condition on the inputs — asserted on the oracle alone
-    — is that the Euler loop lies at least 10 floors away. The Euler loop is the existing reference of each case (orc.denoise_loop,
-    tests/cfg_reference.py, tests/repaint_reference.py), and the multistep reference at order 1 is held to it bit for bit: the two
-    references differ in the rule alone."""
+    — is that the Euler loop lies at least 10 floors away. The Euler loop is the same reference at ``order=1`` (every weight 0), so the
+    two differ in the rule alone; without extensions it is held bit for bit to orc.denoise_loop."""
     from reptext_amd.controlnet import FluxControlNetModel
     from reptext_amd.pipeline import FluxControlNetPipeline
     from reptext_amd.pipeline_repaint import FluxControlNetRepaintPipeline, repaint_t_start
@@ -74,25 +71,21 @@ def test_multistep_matches_the_oracle_loop(gpu, case):
     ids = (orc.latent_image_ids(32, 32), torch.zeros(T, 3))
     args = (tp, SMALL_T, cp, SMALL_CN, noise, pe, pooled, [hint], [rm], sig, *ids, 3.5)
     rkw = dict(conditioning_scale=1.0, conditioning_step=30)
-    if case == "plain":
-        euler = orc.denoise_loop(*args, **rkw)
-    elif case == "cfg":
+    if case == "cfg":
         call.update(negative_prompt_embeds=b16(npe), negative_pooled_prompt_embeds=b16(npooled), true_cfg_scale=2.0)
         rkw["negative"] = dict(prompt_embeds=npe, pooled=npooled, scale=2.0)
-        euler = denoise_loop_cfg(tp, SMALL_T, cp, SMALL_CN, noise, pe, pooled, npe, npooled, [hint], [rm], sig, *ids, 3.5, 2.0,
-                                 conditioning_scale=1.0, conditioning_step=30)
-    else:
+    elif case == "repaint":
         call.update(image=src.to(gpu), mask_image=box_image(BOX), strength=0.75)
         mask = pipe._pack_mask(box_image(BOX), H, W, "cpu")
         t_start = repaint_t_start(4, 0.75)
         assert t_start == 1 and 0 < int(mask.sum()) < mask.numel()
         rkw["repaint"] = dict(src=src, noise=noise, mask=mask, t_start=t_start)
-        euler = denoise_loop_repaint(tp, SMALL_T, cp, SMALL_CN, src, noise, mask, pe, pooled, [hint], [rm], sig, t_start, *ids, 3.5,
-                                     conditioning_scale=1.0, conditioning_step=30)
-    ref = denoise_loop_multistep(*args, **rkw)
+    ref = denoise_loop_reference(*args, **rkw, order=2)
     with orc.stored_as(BF16):
-        ref16 = denoise_loop_multistep(*args, **rkw)
-    assert torch.equal(denoise_loop_multistep(*args, **rkw, order=1), euler)
+        ref16 = denoise_loop_reference(*args, **rkw, order=2)
+    euler = denoise_loop_reference(*args, **rkw, order=1)
+    if case == "plain":
+        assert torch.equal(euler, orc.denoise_loop(*args, **rkw))
     floor, felt = rel_l2(ref16, ref), rel_l2(euler, ref)
     out = pipe(**call).images.float().cpu()
     assert pipe.scheduler._step_index == 4 and pipe.scheduler._history_len == 1 and len(pipe.scheduler.sigmas) == len(sig)

@@ -30,7 +30,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-import multistep_reference as msr  # noqa: E402
+import loop_reference as lref  # noqa: E402
 from test_true_cfg_host import assert_no_call_state  # noqa: E402
 from test_union_tower_host import call_kwargs, make_pipe  # noqa: E402
 
@@ -60,13 +60,13 @@ def test_weights_on_the_flux_grid_and_with_a_begin_index():
     assert len(s) == 5 and all(abs(a - b) <= 2.0 ** -24 for a, b in zip(s, exact))
     w = multistep_weights(sc.sigmas)
     want = [0.0] + [(s[i + 1] - s[i]) / (2.0 * (s[i] - s[i - 1])) for i in (1, 2, 3)]
-    assert w == want == msr.weights(sc.sigmas)
+    assert w == want == lref.weights(sc.sigmas)
     # against the closed form: each dσ carries two table roundings of 2^-24 against a difference of at least 0.16
     for i in (1, 2, 3):
         assert abs(w[i] - (exact[i + 1] - exact[i]) / (2.0 * (exact[i] - exact[i - 1]))) < 1e-5
     assert all(0.3 < x < 1.1 for x in w[1:]) and len({round(x, 3) for x in w[1:]}) == 3          # a non-uniform grid: three weights
     # begin = 1: the run starts at step 1, which is first order; step 0 does not run
-    assert multistep_weights(sc.sigmas, begin=1) == [0.0, 0.0] + want[2:] == msr.weights(sc.sigmas, 1)
+    assert multistep_weights(sc.sigmas, begin=1) == [0.0, 0.0] + want[2:] == lref.weights(sc.sigmas, 1)
     assert multistep_weights(sc.sigmas, begin=3) == [0.0] * 4
 
 
@@ -74,7 +74,7 @@ def test_order_one_is_all_zero_and_other_orders_are_refused():
     from reptext_amd.scheduler import FlowMatchMultistepScheduler, multistep_weights
 
     sig = [1.0, 0.7, 0.3, 0.0]
-    assert multistep_weights(sig, order=1) == [0.0] * 3 == msr.weights(sig, order=1)
+    assert multistep_weights(sig, order=1) == [0.0] * 3 == lref.weights(sig, order=1)
     for order in (0, 3, 4):
         with pytest.raises(ValueError, match="order"):
             multistep_weights(sig, order=order)
@@ -111,11 +111,11 @@ def flux_grid(n, mu=1.15):
 def toy_errors():
     """(AB2, Euler): RMS error over 4096 start points drawn from N(0, 1) at 14, 28 and 56 steps against the 4096-step AB2 run."""
     x0 = torch.randn(4096, generator=torch.Generator().manual_seed(0), dtype=torch.float64)
-    exact = msr.integrate(toy_velocity, x0, flux_grid(4096))
+    exact = lref.integrate(toy_velocity, x0, flux_grid(4096))
     assert bool(torch.isfinite(exact).all()) and float(exact.std()) > 0.5
     rms = lambda x: float((x - exact).pow(2).mean().sqrt())
-    ab2 = {n: rms(msr.integrate(toy_velocity, x0, flux_grid(n))) for n in (14, 28, 56)}
-    euler = {n: rms(msr.integrate(toy_velocity, x0, flux_grid(n), order=1)) for n in (14, 28, 56)}
+    ab2 = {n: rms(lref.integrate(toy_velocity, x0, flux_grid(n))) for n in (14, 28, 56)}
+    euler = {n: rms(lref.integrate(toy_velocity, x0, flux_grid(n), order=1)) for n in (14, 28, 56)}
     print(f"[multistep toy] AB2 {ab2}, ratios {ab2[14] / ab2[28]:.2f} {ab2[28] / ab2[56]:.2f}; Euler {euler}, ratios "
           f"{euler[14] / euler[28]:.2f} {euler[28] / euler[56]:.2f}")
     return ab2, euler
@@ -140,14 +140,14 @@ def test_the_scheduler_walks_the_rule_of_the_reference(monkeypatch):
 
     seen = []
 
-    def op(x32, v, hist32, w, dsigma, x_bf16=None, **kw):
-        assert kw.get("mask") is None and kw.get("v_text") is None
+    def op(name, x32, v, v_text, s, dsigma, x_bf16=None, *, hist, w, **kw):
+        assert kw.get("mask") is None and v_text is None
         vel = v.float()
-        x32 += dsigma * (vel + w * (vel - hist32) if w != 0.0 else vel)
-        hist32.copy_(vel)
+        x32 += dsigma * (vel + w * (vel - hist) if w != 0.0 else vel)
+        hist.copy_(vel)
         seen.append(w)
 
-    monkeypatch.setattr(ops, "multistep_step_f32_", op)
+    monkeypatch.setattr(ops, "_master_step_f32", op)                # the one body every step of ``step_master_`` goes through
     sc = FlowMatchMultistepScheduler()
     sc.set_timesteps(sigmas=[1.0, 0.75, 0.5, 0.25], mu=0.5)
     x = torch.randn(2, 16, generator=torch.Generator().manual_seed(1))
@@ -157,8 +157,8 @@ def test_the_scheduler_walks_the_rule_of_the_reference(monkeypatch):
     for i in range(4):
         sc.step_master_(field(state, float(sc.sigmas[i])), state, history=hist)
         assert sc.step_index == i + 1
-    assert seen == msr.weights(sc.sigmas) and bool(torch.isfinite(state).all())
-    want = msr.integrate(field, x.double(), sc.sigmas)
+    assert seen == lref.weights(sc.sigmas) and bool(torch.isfinite(state).all())
+    want = lref.integrate(field, x.double(), sc.sigmas)
     assert float((state.double() - want).abs().max()) < 1e-5
     # step_master_ without a history is refused; reset_history, set_begin_index and set_timesteps make the next step first order
     with pytest.raises(ValueError, match="history"):
@@ -171,7 +171,7 @@ def test_the_scheduler_walks_the_rule_of_the_reference(monkeypatch):
         seen.clear()
         sc.step_master_(x.to(BF16), state, history=hist)
         sc.step_master_(x.to(BF16), state, history=hist)
-        assert seen == [0.0, msr.weights(sc.sigmas)[3]]
+        assert seen == [0.0, lref.weights(sc.sigmas)[3]]
 
 
 # ------------------------------------------------------------------------------------------------------------------ 3. config, loader, saver

@@ -4,7 +4,7 @@ n_s elements, p = v_text and u = v_uncond (bf16, widened), r the guidance differ
     d = (p − u) + β·r;   a = Σ d², b = Σ d·p, c = Σ p²;   k = τ > 0 and a > τ² ? τ/√a : 1;   e = (η − 1)·(c > 0 ? k·b/c : 0)
     v = p + (s − 1)·(k·d + e·p);   vel2 = w != 0 ? v + w·(v − h) : v;   r' = x + dσ·vel2;   o = mask ? (1 − m)·keep + m·r' : r'
 
-against fp64 (tests/guidance_reference.py: ``projected_velocity``) on the values the kernels read. With U = 2^-24 and γ(R) = R·U/(1 − R·U):
+against fp64 (tests/loop_reference.py: ``projected_velocity``) on the values the kernels read. With U = 2^-24 and γ(R) = R·U/(1 − R·U):
 
 The sums. d takes R_d roundings, 1 without momentum and 3 with it (p − u, β·r, their sum), each relative to a partial result below
 D = |p − u| + |β·r|. A term d², d·p, p² takes one more for the product, after the 2·R_d, R_d, 0 it inherits from d. A term then goes
@@ -38,7 +38,7 @@ import torch
 
 pytestmark = pytest.mark.gpu
 
-from guidance_reference import projected_velocity  # noqa: E402
+from loop_reference import projected_velocity  # noqa: E402
 
 BF16, F32 = torch.bfloat16, torch.float32
 U = 2.0 ** -24

@@ -1,4 +1,4 @@
-"""The repaint pipeline (reptext_amd/pipeline_repaint.py) on the GPU: parity of the loop with the CPU oracle's (tests/repaint_reference.py)
+"""The repaint pipeline (reptext_amd/pipeline_repaint.py) on the GPU: parity of the loop with the CPU oracle's (tests/loop_reference.py)
 alone, under true CFG and with the union tower; the bitwise properties of the call — the background ends as the source, strength 1 under
 a mask of ones is the base call, eager = captured = replay, the base call's graph key is untouched, batch invariance, the loop's toggles —
 and one call through the small VAE with PIL inputs. 256x256 (N = 256, T = 64) with the reduced models of test_vae_pipeline_gpu.py, 4
@@ -16,7 +16,7 @@ from test_true_cfg_gpu import BOXES, SMALL_UN, graph_keys, mask_images, negative
 from test_true_cfg_host import assert_no_call_state  # noqa: E402
 from test_vae_pipeline_gpu import SMALL_CN, SMALL_T, rel_l2, vae_pair  # noqa: E402,F401
 
-from repaint_reference import denoise_loop_repaint  # noqa: E402
+from loop_reference import denoise_loop_reference  # noqa: E402
 
 H = W = 256
 N, T = 256, 64
@@ -61,14 +61,18 @@ def base_call(pipe, kw):
 
 
 # ------------------------------------------------------------------------------------------------------------------ 1. parity
-@pytest.mark.parametrize("case", ["plain", "cfg", "union"])
+@pytest.mark.parametrize("case", ["plain", "cfg", "union", "everything"])
 def test_repaint_matches_the_oracle_loop(gpu, case):
     """One masked text line, a box mask, strength 0.75 of 4 steps (3 run, from sigma_1): GPU error at the bf16-storage oracle's own floor.
     The same under true CFG at s = 2 and with the union tower on [0.3, 1.0] of the steps that run (text tower for 2 of them). The
-    condition on the inputs — asserted on the oracle alone — is that the loop WITHOUT the blend lies at least 10 floors away."""
+    condition on the inputs — asserted on the oracle alone — is that the loop WITHOUT the blend lies at least 10 floors away.
+    ``everything``: every loop extension in one call — true CFG, the union tower, the multistep scheduler and a guider that projects
+    on [0, 0.67] (guided at steps 0 and 1 of the 3, its clamp at half the ‖d‖ the reference shows at step 0: active) — and the
+    reference also lies at least 10 floors from itself with the guider, the second order or the union tower left out."""
     from reptext_amd.controlnet import FluxControlNetModel
+    from reptext_amd.guidance import TrueCFGGuider
     from reptext_amd.pipeline_repaint import FluxControlNetRepaintPipeline, repaint_t_start
-    from reptext_amd.scheduler import FlowMatchEulerDiscreteScheduler
+    from reptext_amd.scheduler import FlowMatchEulerDiscreteScheduler, FlowMatchMultistepScheduler
     from reptext_amd.transformer import FluxTransformer2DModel
 
     tp = orc.init_mmdit_params(SMALL_T, seed=811)
@@ -76,7 +80,8 @@ def test_repaint_matches_the_oracle_loop(gpu, case):
     tr = FluxTransformer2DModel(**SMALL_T, device=gpu, dtype=BF16)
     cn = FluxControlNetModel(**SMALL_CN, device=gpu, dtype=BF16)
     tr.load_state_dict(tp); cn.load_state_dict(cp)
-    pipe = FluxControlNetRepaintPipeline(FlowMatchEulerDiscreteScheduler(), None, None, None, None, None, tr, cn)
+    sched = FlowMatchMultistepScheduler() if case == "everything" else FlowMatchEulerDiscreteScheduler()
+    pipe = FluxControlNetRepaintPipeline(sched, None, None, None, None, None, tr, cn)
     pipe.set_progress_bar_config(disable=True)
     g = torch.Generator().manual_seed(813)
     r = lambda *s: torch.randn(*s, generator=g).to(BF16).float()
@@ -87,15 +92,15 @@ def test_repaint_matches_the_oracle_loop(gpu, case):
     uhint = r(1, N, 64)
     rm = token_mask(BOX)
     b16 = lambda t: t.to(gpu, BF16)
-    cn_steps = 2 if case == "union" else 30
+    cn_steps = 2 if case in ("union", "everything") else 30
     call = dict(prompt_embeds=b16(pe), pooled_prompt_embeds=b16(pooled), height=H, width=W, num_inference_steps=4, guidance_scale=3.5,
                 control_image=[b16(hint)], control_mask=[box_image(BOX)], controlnet_conditioning_scale=1.0, controlnet_conditioning_step=cn_steps,
                 latents=b16(noise), image=src.to(gpu), mask_image=box_image(BOX), strength=0.75, output_type="latent")
     rkw = dict(conditioning_scale=1.0, conditioning_step=cn_steps)
-    if case == "cfg":
+    if case in ("cfg", "everything"):
         call.update(negative_prompt_embeds=b16(npe), negative_pooled_prompt_embeds=b16(npooled), true_cfg_scale=2.0)
         rkw["negative"] = dict(prompt_embeds=npe, pooled=npooled, scale=2.0)
-    if case == "union":
+    if case in ("union", "everything"):
         up = orc.init_mmdit_params(SMALL_UN, seed=814, controlnet=True)
         un = FluxControlNetModel(**SMALL_UN, device=gpu, dtype=BF16)
         un.load_state_dict(up)
@@ -107,12 +112,24 @@ def test_repaint_matches_the_oracle_loop(gpu, case):
     assert 0 < int(mask.sum()) < mask.numel() and set(mask.unique().tolist()) == {0.0, 1.0}
     t_start = repaint_t_start(4, 0.75)
     sig = orc.flow_sigmas(4, orc.calculate_shift(N, 256, 4096, 0.5, 1.15))
-    args = (tp, SMALL_T, cp, SMALL_CN, src, noise, mask, pe, pooled, [hint], [rm], sig, t_start, orc.latent_image_ids(32, 32), torch.zeros(T, 3), 3.5)
-    ref = denoise_loop_repaint(*args, **rkw)
+    args = (tp, SMALL_T, cp, SMALL_CN, noise, pe, pooled, [hint], [rm], sig, orc.latent_image_ids(32, 32), torch.zeros(T, 3), 3.5)
+    rkw["repaint"] = dict(src=src, noise=noise, mask=mask, t_start=t_start)
+    if case == "everything":
+        info = {}                                                   # one step: its d is the plain CFG difference
+        denoise_loop_reference(*args[:9], sig[: t_start + 2], *args[10:], **rkw, guider=TrueCFGGuider(eta=0.0), info=info)
+        pipe.guider = TrueCFGGuider(stop=0.67, eta=0.0, momentum=-0.5, norm_threshold=0.5 * float(info["norm_d"][0]))
+        rkw.update(order=2, guider=pipe.guider)
+    ref = denoise_loop_reference(*args, **rkw)
     with orc.stored_as(BF16):
-        ref16 = denoise_loop_repaint(*args, **rkw)
-    unblended = denoise_loop_repaint(*args, **rkw, blend=False)
+        ref16 = denoise_loop_reference(*args, **rkw)
+    unblended = denoise_loop_reference(*args, **{**rkw, "repaint": dict(rkw["repaint"], blend=False)})
     floor, felt = rel_l2(ref16, ref), rel_l2(unblended, ref)
+    if case == "everything":
+        away = {what: rel_l2(denoise_loop_reference(*args, **{**rkw, **without}), ref) / floor
+                for what, without in (("guider", dict(guider=None)), ("second order", dict(order=1)), ("union tower", dict(union=None)))}
+        print(f"repaint [{case}] floor {floor:.3e}; the reference without the blend lies {felt / floor:.0f} floors away, without the "
+              + ", ".join(f"{what} {d:.0f}" for what, d in away.items()))
+        assert min(away.values()) >= 10
     out = pipe(**call).images.float().cpu()
     assert pipe.scheduler._step_index == 4 and len(pipe.scheduler.sigmas) == len(sig)
     err, err16 = rel_l2(out, ref), rel_l2(out, ref16)

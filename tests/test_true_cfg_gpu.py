@@ -1,4 +1,4 @@
-"""Negative prompts (true CFG) in the text-to-image pipeline on the GPU: parity with the CPU oracle's loop (tests/cfg_reference.py),
+"""Negative prompts (true CFG) in the text-to-image pipeline on the GPU: parity with the CPU oracle's loop (tests/loop_reference.py),
 alone, with the union tower and with both IP-Adapter forms, and the bitwise properties of the call — off means off, equal halves
 collapse to the plain call, eager = captured, batch invariance, the loop's toggles, the fp8 modes — plus batch > 1 under true CFG in
 the inpaint pipeline. 256x256 (N = 256, T = 64) with the reduced models of test_vae_pipeline_gpu.py, 3-4 steps."""
@@ -15,7 +15,7 @@ from test_vae_pipeline_gpu import SMALL_CN, SMALL_T, rel_l2  # noqa: E402
 
 import instantx_reference as ixr  # noqa: E402
 import ip_adapter_reference as ipr  # noqa: E402
-from cfg_reference import denoise_loop_cfg  # noqa: E402
+from loop_reference import denoise_loop_reference  # noqa: E402
 
 SMALL_UN = dict(SMALL_T, num_layers=2, num_single_layers=0)
 BOXES = ((48, 96, 30, 200), (100, 150, 60, 240))        # two text lines inside image rows 48..144 of 256: the row window is active
@@ -108,7 +108,7 @@ def test_true_cfg_matches_the_oracle_loop(gpu, case):
                 true_cfg_scale=2.0, height=H, width=W, num_inference_steps=3, guidance_scale=3.5, control_image=[b16(hint)],
                 control_mask=[Image.fromarray(mask_np)], controlnet_conditioning_scale=1.0, controlnet_conditioning_step=cn_steps,
                 latents=b16(lat0), output_type="latent")
-    rkw = dict(conditioning_scale=1.0, conditioning_step=cn_steps)
+    rkw = dict(conditioning_scale=1.0, conditioning_step=cn_steps, negative=dict(prompt_embeds=npe, pooled=npooled, scale=2.0))
     if case == "union":
         up = orc.init_mmdit_params(SMALL_UN, seed=714, controlnet=True)
         un = FluxControlNetModel(**SMALL_UN, device=gpu, dtype=torch.bfloat16)
@@ -130,10 +130,10 @@ def test_true_cfg_matches_the_oracle_loop(gpu, case):
     if case.startswith("ip_"):
         call.update(ip_adapter_image_embeds=b16(emb), negative_ip_adapter_image_embeds=[b16(nemb)[:, None]])
     sig = orc.flow_sigmas(3, orc.calculate_shift(N, 256, 4096, 0.5, 1.15))
-    args = (tp, SMALL_T, cp, SMALL_CN, lat0, pe, pooled, npe, npooled, [hint], [rm], sig, orc.latent_image_ids(32, 32), torch.zeros(T, 3), 3.5, 2.0)
-    ref = denoise_loop_cfg(*args, **rkw)
+    args = (tp, SMALL_T, cp, SMALL_CN, lat0, pe, pooled, [hint], [rm], sig, orc.latent_image_ids(32, 32), torch.zeros(T, 3), 3.5)
+    ref = denoise_loop_reference(*args, **rkw)
     with orc.stored_as(torch.bfloat16):
-        ref16 = denoise_loop_cfg(*args, **rkw)
+        ref16 = denoise_loop_reference(*args, **rkw)
     out = pipe(**call).images.float().cpu()
     assert pipe._tower_window_used is not None
     err, err16, floor = rel_l2(out, ref), rel_l2(out, ref16), rel_l2(ref16, ref)

@@ -1,5 +1,5 @@
 """The second ControlNet of the base pipeline (pipe.controlnet_union + control_image_union=...) on the GPU: parity with the CPU
-oracle's loop (tests/union_reference.py), and the bitwise properties of its schedule — zero tower, empty interval, side stream,
+oracle's loop (tests/loop_reference.py), and the bitwise properties of its schedule — zero tower, empty interval, side stream,
 row window, captured graph, batch, image path. 256x256 (N = 256, T = 64) with the reduced models of test_vae_pipeline_gpu.py."""
 import numpy as np
 import pytest
@@ -11,7 +11,7 @@ from oracle import flux_oracle as orc  # noqa: E402
 from oracle import vae_oracle as vorc  # noqa: E402
 from test_models_gpu import assert_at_dtype_floor  # noqa: E402
 from test_vae_pipeline_gpu import SMALL_CN, SMALL_T, VAE_SMALL, rel_l2  # noqa: E402
-from union_reference import denoise_loop_union  # noqa: E402
+from loop_reference import denoise_loop_reference  # noqa: E402
 
 SMALL_UN = dict(SMALL_T, num_layers=2, num_single_layers=0)
 BOXES = ((48, 96, 30, 200), (100, 150, 60, 240))        # two text lines inside image rows 48..144 of 256: the row window is active
@@ -90,11 +90,11 @@ def test_union_tower_matches_the_oracle_loop(vae, gpu, case):
     lines = case != "no_text_line_256"
     hints, rms = ([hint], [rm]) if lines else ([], [])
     sig = orc.flow_sigmas(3, orc.calculate_shift(N, 256, 4096, 0.5, 1.15))
-    args = (tp, SMALL_T, cp, SMALL_CN, up, UN, lat0, pe, pooled, hints, rms, uhint, sig, orc.latent_image_ids(h2, w2), torch.zeros(T, 3), 3.5)
-    kw = dict(conditioning_scale=1.0, conditioning_step=2, union_scale=0.7, union_start=0.3, union_end=1.0)
-    ref = denoise_loop_union(*args, **kw)
+    args = (tp, SMALL_T, cp, SMALL_CN, lat0, pe, pooled, hints, rms, sig, orc.latent_image_ids(h2, w2), torch.zeros(T, 3), 3.5)
+    kw = dict(conditioning_scale=1.0, conditioning_step=2, union=dict(params=up, cfg=UN, cond=uhint, scale=0.7, start=0.3, end=1.0))
+    ref = denoise_loop_reference(*args, **kw)
     with orc.stored_as(torch.bfloat16):
-        ref16 = denoise_loop_union(*args, **kw)
+        ref16 = denoise_loop_reference(*args, **kw)
     b16 = lambda t: t.to(gpu, torch.bfloat16)
     from PIL import Image
 
