@@ -17,7 +17,16 @@
 // Reference math: torch.nn.functional.linear as reached from controlnet_flux.py:277,280,292,386,391 and the
 // diffusers blocks; epilogue terms documented in include/reptext_hip.h.
 #include "rt_common.h"
+#include <cstdlib>
 #include <type_traits>
+
+// Diagnostic hooks, empty in the library: tools/gemm_stamps compiles this file with them defined to take s_memtime stamps at the end
+// of the K loop and behind the last store of a tile's epilogue (kind: 0 general bf16, 1 general f32, 2 rope, 3 / 4 straight-line bf16
+// plain / GELU; + 8 on a general bf16 tile whose columns all take GELU).
+#ifndef RT_GEMM_STAMP_KLOOP_END
+#define RT_GEMM_STAMP_KLOOP_END()
+#define RT_GEMM_STAMP_STORES_ISSUED(kind)
+#endif
 
 namespace {
 
@@ -51,6 +60,7 @@ struct GroupDev {
   rt_gemm_group g;
   int tiles_m, tiles_n, tile_begin;
   int wide_store;      // bf16 output rows are 16-byte addressable in 8-column steps (C 16-B aligned, ldc/strideC/N % 8 == 0)
+  int fast_bf16;       // interior tiles may take epilogue_fast: bf16 operands and output, wide_store, no term but bias and GELU, alpha == 1
 };
 struct Launch {
   GroupDev grp[RT_GEMM_MAX_GROUPS];
@@ -242,6 +252,59 @@ __device__ __forceinline__ void epilogue_tile(const rt_gemm_group& g, int bidx, 
   }
 }
 
+// Straight-line epilogue of an INTERIOR 256x256 tile of a bf16 problem whose only terms are the bias and GELU (GroupDev::fast_bf16).
+// epilogue_tile is the definition; this is its arithmetic per element for that case — acc + bias, GELU, one rounding to bf16 — so the
+// same bits (rt_gemm_epilogue_variant(0) sends every tile to epilogue_tile). gemm_tile decides once per tile, in scalar code, that the
+// whole tile lies inside M x N and on one side of gelu_from; nothing here is decided per element: no bounds, no clamps, no term tests.
+// C is addressed as a scalar per-tile base (+ 16 i rows) plus ONE 32-bit byte offset per lane and an immediate per fragment pair (the
+// host checks that 256 rows of ldc stay inside 32 bits); each fragment pair is packed once and leaves through v_permlane16_swap as 16
+// bytes per lane — epilogue_tile's wide store. Per fragment about 6 (GELU: 35) instructions instead of 50 (80); measured per wave with
+// tools/gemm_stamps at 4608x21504x3072: 7.5 -> 3.8 us from the end of the K loop to the last store (GELU 10.3 -> 4.7 us).
+// The f32 kind (gate, f32 residual, add2, rowscale) was built the same way and is not here: its tiles are bound by the 512 KiB each
+// moves, not by issue (profiles/gemm_epilogue_ab.json: the last wave of a workgroup ends at 15.3 instead of 15.8 us, launches -0.4 to
+// -0.8 %, inside the run-to-run spread).
+// lrow / lcol: the lane's first row and column inside the tile.
+template <bool GELU, int NI, int NJ>
+__device__ __forceinline__ void epilogue_fast(const rt_gemm_group& g, int bidx, int m0, int n0, int lrow, int lcol, f32x4 (&acc)[NI][NJ]) {
+  static_assert(NJ % 2 == 0, "fragment columns leave in pairs");
+  f32x4 bias4[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) bias4[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (g.bias) {
+    const char* bb = reinterpret_cast<const char*>(reinterpret_cast<const bf16_t*>(g.bias) + n0);
+    const uint32_t bo = (uint32_t)lcol * 2;
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      const u32x2 b = *reinterpret_cast<const u32x2*>(bb + bo + 32 * j);
+      bias4[j] = f32x4{bf16lo(b[0]), bf16hi(b[0]), bf16lo(b[1]), bf16hi(b[1])};
+    }
+  }
+  char* cb = reinterpret_cast<char*>(reinterpret_cast<bf16_t*>(g.C) + (int64_t)bidx * g.strideC + (int64_t)m0 * g.ldc + n0);
+  const uint32_t ldcb = (uint32_t)g.ldc * 2;
+  const int c = lcol >> 2 & 3;                         // this lane's 16-lane group: after the swap it owns 8 columns of fragment jp + (c & 1)
+  const uint32_t co = (uint32_t)lrow * ldcb + (uint32_t)((lcol - 4 * c) + 16 * (c & 1) + 8 * (c >> 1)) * 2;
+#pragma unroll
+  for (int i = 0; i < NI; ++i) {
+    u32x2 packed[NJ];
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      f32x4 v = acc[i][j] + bias4[j];
+      if constexpr (GELU) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = gelu_tanh_f(v[e]);
+      }
+      packed[j] = u32x2{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3])};
+    }
+    char* crow = cb + (uint32_t)(16 * i) * ldcb;
+#pragma unroll
+    for (int jp = 0; jp < NJ; jp += 2) {
+      const auto x = __builtin_amdgcn_permlane16_swap(packed[jp][0], packed[jp + 1][0], false, false);
+      const auto y = __builtin_amdgcn_permlane16_swap(packed[jp][1], packed[jp + 1][1], false, false);
+      *reinterpret_cast<u32x4*>(crow + co + 32 * jp) = u32x4{x[0], y[0], x[1], y[1]};
+    }
+  }
+}
+
 // q/k RMSNorm + RoPE of one 256x256 tile through the LDS ring, which is idle after the K loop (rt_gemm_group::rope_*; ROPE
 // instantiation only, tiles whose columns are q or k). Nothing is kept beside the accumulators: after the first phase they are dead.
 //   1. barrier (every wave is past its last fragment read), then each lane stores pack_bf16x2(acc + bias) — the value epilogue_tile
@@ -363,7 +426,7 @@ typedef __attribute__((ext_vector_type(8))) int i32x8;
 //              dropped in the epilogue (0.4-3 % of the rows). Everything else — tile, LDS image, ping-pong schedule, counted waits —
 //              is the GEMM's; the K order of an output element is that of csrc/vae.hip's conv_nhwc_kernel (bit-identical results).
 template <bool FP8, class G_, bool MX = false, bool CONV = false, bool ROPE = false>
-__device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int m0, int n0, bool wide_store, char* smem) {
+__device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int m0, int n0, bool wide_store, bool fast_bf16, char* smem) {
   using T = G_;
   static_assert(!MX || FP8, "block scales belong to the e4m3 form");
   static_assert(!CONV || !FP8, "the convolution form is bf16");
@@ -586,6 +649,7 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
     RT_BAR(); RT_MFMA(1, 0); RT_BAR();
   }
   if (wm == 0) RT_BAR();                       // balance the stagger barrier
+  RT_GEMM_STAMP_KLOOP_END();
 #undef RT_READ_A
 #undef RT_READ_B
 #undef RT_READ_S
@@ -597,6 +661,19 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
     static_assert(!FP8 && !CONV && T::BM == 256 && T::BN == 256, "the fused q/k step belongs to the bf16 256x256 tile");
     if (g.rope_cos && ((n0 >= g.rope_q0 && n0 < g.rope_q0 + g.rope_w) || (n0 >= g.rope_k0 && n0 < g.rope_k0 + g.rope_w))) {
       rope_epilogue<T::NI, T::NJ>(g, bidx, m0, n0, wm * T::WMR + l15, wn * T::WNC + 4 * (lane >> 4), acc, smem);
+      RT_GEMM_STAMP_STORES_ISSUED(2);
+      return;
+    }
+  }
+  if constexpr (!FP8 && !CONV && T::BM == 256 && T::BN == 256) {
+    // Tile-uniform, in scalar code: an interior tile of a bias / GELU-only bf16 group that lies on one side of gelu_from takes the
+    // straight-line epilogue; every other tile takes epilogue_tile. (rows_per_batch plays no part: such a group has no gate or rowscale.)
+    const bool gelu_all = g.gelu_from <= n0, gelu_none = g.gelu_from >= n0 + T::BN;
+    if (fast_bf16 && m0 + T::BM <= g.M && n0 + T::BN <= g.N && (gelu_all || gelu_none)) {
+      const int lrow = wm * T::WMR + l15, lcol = wn * T::WNC + 4 * (lane >> 4);
+      if (gelu_all) epilogue_fast<true, T::NI, T::NJ>(g, bidx, m0, n0, lrow, lcol, acc);
+      else epilogue_fast<false, T::NI, T::NJ>(g, bidx, m0, n0, lrow, lcol, acc);
+      RT_GEMM_STAMP_STORES_ISSUED(gelu_all ? 4 : 3);
       return;
     }
   }
@@ -604,6 +681,7 @@ __device__ __forceinline__ void gemm_tile(const rt_gemm_group& g, int bidx, int 
   const int ncol = n0 + wn * T::WNC + 4 * (lane >> 4);
   if (g.out_f32) epilogue_tile<true, FP8, T::NI, T::NJ, CONV>(g, bidx, mrow, ncol, acc);
   else epilogue_tile<false, FP8, T::NI, T::NJ, CONV>(g, bidx, mrow, ncol, acc, wide_store);
+  RT_GEMM_STAMP_STORES_ISSUED(g.out_f32 ? 1 : g.gelu_from <= n0 ? 8 : 0);
 }
 
 // XCD-aware placement (speed only, never correctness): workgroups are dealt round-robin over the 8 XCDs, so blocks b and b+8
@@ -650,7 +728,7 @@ __global__ __launch_bounds__(THREADS, 2) void gemm_pp_kernel(const Launch L) {
   t -= bidx * tiles_per_batch;
   int tm, tn;
   panel_walk(t, G.tiles_m, G.tiles_n, tm, tn);
-  gemm_tile<FP8, G_, MX, CONV, ROPE>(G.g, bidx, tm * G_::BM, tn * G_::BN, G.wide_store != 0, smem);
+  gemm_tile<FP8, G_, MX, CONV, ROPE>(G.g, bidx, tm * G_::BM, tn * G_::BN, G.wide_store != 0, G.fast_bf16 != 0, smem);
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------
@@ -662,7 +740,22 @@ int set_lds(K kern, int bytes) {
   return e == hipSuccess ? 0 : (int)e;
 }
 
+int g_epilogue_variant = -1;   // 1 (default, env RT_GEMM_EPILOGUE) = interior tiles of bias / GELU-only bf16 groups take epilogue_fast; 0 = epilogue_tile everywhere
+int epilogue_variant_now() {
+  if (g_epilogue_variant < 0) {
+    const char* e = getenv("RT_GEMM_EPILOGUE");
+    g_epilogue_variant = e ? (atoi(e) != 0) : 1;
+  }
+  return g_epilogue_variant;
+}
+
 }  // namespace
+
+extern "C" int rt_gemm_epilogue_variant(int32_t mode) {
+  const int prev = epilogue_variant_now();
+  if (mode >= 0) g_epilogue_variant = mode != 0;
+  return prev;
+}
 
 static int launch_gemm(const rt_gemm_group* groups, int32_t ngroups, void* stream, bool fp8) {
   if (!groups || ngroups < 1 || ngroups > RT_GEMM_MAX_GROUPS) return RT_E_BADARG;
@@ -730,6 +823,9 @@ static int launch_gemm(const rt_gemm_group* groups, int32_t ngroups, void* strea
     L.grp[i].tiles_m = (g.M + Geo256::BM - 1) / Geo256::BM;
     L.grp[i].tiles_n = (g.N + Geo256::BN - 1) / Geo256::BN;
     L.grp[i].wide_store = (!g.out_f32 && RT_ALIGNED(g.C, 16) && g.ldc % 8 == 0 && g.strideC % 8 == 0 && g.N % 8 == 0) ? 1 : 0;
+    // ldc: 256 rows of a tile stay inside a 32-bit byte offset
+    L.grp[i].fast_bf16 = (!fp8 && g.conv_ks == 0 && epilogue_variant_now() != 0 && L.grp[i].wide_store && g.ldc < ((int64_t)1 << 22) && !g.gate && !g.res &&
+                          !g.add2 && !g.rowscale && g.alpha == 1.0f) ? 1 : 0;
     L.grp[i].tile_begin = total;
     total += L.grp[i].tiles_m * L.grp[i].tiles_n * g.batch;
   }

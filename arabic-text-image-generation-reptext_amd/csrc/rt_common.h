@@ -52,8 +52,11 @@ __device__ __forceinline__ bf16_t f32_to_bf16(float f) {
   __bf16 h = (__bf16)f;
   return *reinterpret_cast<bf16_t*>(&h);
 }
+// two floats -> one dword of two bf16 (lo in the low half): the two-element vector convert is ONE v_cvt_pk_bf16_f32 v, lo, hi; two
+// scalar casts joined by shift and or were two of them plus a shift and a v_or_b32_sdwa. Same instruction, same bits (NaN included).
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
-  return (uint32_t)f32_to_bf16(lo) | ((uint32_t)f32_to_bf16(hi) << 16);
+  typedef __attribute__((ext_vector_type(2))) float f32x2;
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2{lo, hi}, bf16x2));
 }
 __device__ __forceinline__ float bf16lo(uint32_t u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf16hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }

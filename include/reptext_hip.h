@@ -131,6 +131,13 @@ typedef struct rt_gemm_group {
 
 int rt_gemm_bf16(const rt_gemm_group* groups /* host */, int32_t ngroups, void* stream);
 
+/* Which epilogue serves rt_gemm_bf16's interior 256x256 tiles (speed only: both give the same bits). 1 (default, env
+ * RT_GEMM_EPILOGUE) = a tile that lies wholly inside M x N and on one side of gelu_from takes a straight-line epilogue when its
+ * group writes bf16 C in 16-byte steps (C 16-byte aligned, ldc / strideC / N % 8 == 0) and has no term but the bias and GELU
+ * (no gate / res / add2 / rowscale, alpha == 1); 0 = the general epilogue everywhere. mode < 0 only queries; returns the previous
+ * mode. Read when a launch is enqueued. Added without an ABI bump: nothing existing changed. */
+int rt_gemm_epilogue_variant(int32_t mode);
+
 /* Skinny linear for the adaLN tables (ABI 12; csrc/gemm_skinny.hip): M <= 32 activation rows given as the two-term bf16 split
  * hi + lo of an fp32 vector (rt_silu_split_bf16), up to two problems that share them:
  *   C[m][n] = lo[m]·W[n] + (hi[m]·W[n] + bias[n])        C f32 [M][ldc], W bf16 [N][ldw], bias bf16 [N] or NULL

@@ -1,5 +1,5 @@
 """Kernel micro-benchmarks at the C2 shapes (1024², S=4608, d=3072). Run on the GPU box:
-    python tools/bench_kernels.py [gemm|shapes|fp8|attn|attn8|elem|passes|all]
+    python tools/bench_kernels.py [gemm|shapes|epilogue|fp8|attn|attn8|elem|passes|all]
 Prints TFLOP/s from torch.cuda.Event timing on the current stream (same stream the kernels are enqueued on)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -68,6 +68,60 @@ def bench_gemm_shapes():
     for name, fl, run in launches:
         t = min(timeit(run, iters=10, warm=2) for _ in range(3))
         print(f"{name:42s} {t*1e6:7.1f} us {fl/t/1e12:7.1f} TF/s", flush=True)
+
+
+def bench_gemm_epilogue(rounds=10):
+    """rt_gemm_bf16 on the bf16 loop's launches with rt_gemm_epilogue_variant 0 (general epilogue everywhere) and 1 (straight-line
+    epilogue on interior tiles) alternating in one process: median and minimum over `rounds` rounds of 10 calls and the number of rounds
+    in which variant 1 was the faster of the pair, one JSON line each. `python tools/bench_kernels.py epilogue [rounds]`."""
+    import json
+    import statistics
+    from reptext_amd import native
+    lib = native.load()
+    T, Ni, d, H = 512, 4096, 3072, 24
+    S = T + Ni
+    P = ops.LinearProblem
+    bf = lambda *s: (torch.randn(*s, device=dev) * 0.02).to(torch.bfloat16)
+    x = torch.randn(S, 5 * d, device=dev).to(torch.bfloat16)
+    x32 = torch.randn(S, d, device=dev)
+    gate = torch.randn(1, d, device=dev)
+    inject = torch.randn(S, d, device=dev).to(torch.bfloat16)
+    wn = [(1 + 0.1 * torch.randn(128, device=dev)).to(torch.bfloat16) for _ in range(2)]
+    cos, sin = torch.randn(S, 128, device=dev), torch.randn(S, 128, device=dev)
+    launches = []
+    w7, b7, o7 = bf(7 * d, d), bf(7 * d), torch.empty(S, 7 * d, device=dev, dtype=torch.bfloat16)
+    launches.append(("single fused 4608x21504x3072 bf16 plain+gelu", 2 * S * 7 * d * d, lambda: ops.linear(x[:, :d], w7, o7, bias=b7, gelu_from=3 * d)))
+    rope = ops.QKRope(2 * d, 0, d, wn[0], wn[1], cos, sin)
+    launches.append(("single fused 4608x21504x3072 rope+plain+gelu", 2 * S * 7 * d * d, lambda: ops.linear(x[:, :d], w7, o7, bias=b7, gelu_from=3 * d, rope=rope)))
+    w5, b5 = bf(d, 5 * d), bf(d)
+    launches.append(("single out 4608x3072x15360 f32 gate+res", 2 * S * d * 5 * d, lambda: ops.linear(x, w5, x32, bias=b5, gate=gate, res=x32)))
+    for name, N, K, kind in (("qkv", 3 * d, d, "plain"), ("ff1", 4 * d, d, "gelu"), ("ff2", d, 4 * d, "f32+add2"), ("out", d, d, "f32")):
+        wi, wt, bi, bt = bf(N, K), bf(N, K), bf(N), bf(N)
+        o = x32 if kind.startswith("f32") else torch.empty(S, N, device=dev, dtype=torch.bfloat16)
+
+        def run(wi=wi, wt=wt, bi=bi, bt=bt, o=o, K=K, kind=kind):
+            if kind.startswith("f32"):
+                ops.linear_grouped([P(x[T:, :K], wi, o[T:], bias=bi, gate=gate, res=o[T:], add2=inject[T:] if kind == "f32+add2" else None),
+                                    P(x[:T, :K], wt, o[:T], bias=bt, gate=gate, res=o[:T])])
+            else:
+                gf = 0 if kind == "gelu" else None
+                ops.linear_grouped([P(x[T:, :K], wi, o[T:], bias=bi, gelu_from=gf), P(x[:T, :K], wt, o[:T], bias=bt, gelu_from=gf)])
+
+        launches.append((f"double {name} (4096+512)x{N}x{K} {kind}", 2 * S * N * K, run))
+    prev = lib.rt_gemm_epilogue_variant(-1)
+    try:
+        for name, fl, run in launches:
+            res = {0: [], 1: []}
+            for _ in range(rounds):
+                for var in (0, 1):
+                    lib.rt_gemm_epilogue_variant(var)
+                    res[var].append(timeit(run, iters=10, warm=2) * 1e6)
+            m0, m1 = statistics.median(res[0]), statistics.median(res[1])
+            print(json.dumps({"launch": name, "rounds": rounds, "general_us": {"median": round(m0, 1), "min": round(min(res[0]), 1)},
+                              "fast_us": {"median": round(m1, 1), "min": round(min(res[1]), 1)}, "median_change_pct": round(100 * (m1 / m0 - 1), 2),
+                              "rounds_fast_faster": sum(f < g for g, f in zip(res[0], res[1])), "fast_tflops": round(fl / m1 / 1e6, 1)}), flush=True)
+    finally:
+        lib.rt_gemm_epilogue_variant(prev)
 
 
 def bench_gemm_fp8():
@@ -226,6 +280,8 @@ if __name__ == "__main__":
         bench_gemm()
     if what in ("shapes", "all"):
         bench_gemm_shapes()
+    if what in ("epilogue", "all"):
+        bench_gemm_epilogue(int(sys.argv[2]) if len(sys.argv) > 2 else 10)
     if what in ("fp8", "all"):
         bench_gemm_fp8()
     if what in ("attn", "all"):
