@@ -30,6 +30,10 @@
 // runs. A workgroup that covers only part of an item writes its unnormalised (m, l, Oᵀ) to a workspace record; the last
 // one to finish an item combines its records in run order.
 //
+// rt_attention_fwd_grouped is the same kernel instantiated with GROUPED = true (region-masked attention for per-line prompts): keys in
+// tile-aligned groups, one visibility word per query row, hidden lanes' scores set to -inf under a wave-uniform branch. Everything it adds
+// stands under `if constexpr (GROUPED)`; the dense instantiation is the code it was.
+//
 // LDS image of a K or V tile: 64 rows × 256 B; 16-B chunk c of row r lives at 256·r + 16·(c ^ f(r)),
 // f(r) = ((r&3)<<2) | ((r>>2)&3): conflict-free for the row reads (K) and the transposed reads (V).
 // LDS-DMA writes lane-linear, so the XOR is applied to each lane's source address.
@@ -53,10 +57,27 @@ __host__ __device__ inline int group_slots(const SplitGeom& G, int xcd) {
   return c.nfull + (c.rem ? G.spx : 0);
 }
 
+// rt_attention_fwd_grouped: the keys fall into n contiguous groups whose ends are multiples of BKV (the last is S), so a key tile lies
+// in ONE group; a query row sees a tile iff the group's bit is set in its word of row_vis. By value in the kernel arguments: the group
+// of a tile is found with scalar loads and compares, nothing per lane but the bit test.
+constexpr int MAX_GROUPS = 32;
+struct KeyGroups {
+  int32_t end[MAX_GROUPS];
+  int32_t n;
+  const uint32_t* row_vis;   // [B][S], batch stride stride_vis_b (0: one table)
+  int64_t stride_vis_b;
+};
+struct NoGroups {};
+// Running maximum a grouped row starts with: finite, so that a hidden score (-inf) gives exp2(-inf - M0) = 0 and not exp2(NaN), and
+// so far below any score that the first visible one rescales the (all-zero) state by exp2(M0 - m) = 0.
+constexpr float GROUPED_M0 = -1.0e30f;
+
+template <bool GROUPED>
 __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V, bf16_t* O,
     int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob, float scale_log2, const SplitGeom G,
-    const int row_lo, const int row_hi, int* counters, char* records) {
+    const int row_lo, const int row_hi, int* counters, char* records,
+    const std::conditional_t<GROUPED, KeyGroups, NoGroups> KG) {
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE_B];   // [slot][K|V]
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -183,7 +204,15 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) o_acc[i][r] = 0.f;
-    float m_run = -INFINITY, l_run = 0.f;     // running max (log2 domain, may lag the true max by <= RESCALE_THR) and row sum
+    float m_run = GROUPED ? GROUPED_M0 : -INFINITY, l_run = 0.f;     // running max (log2 domain, may lag the true max by <= RESCALE_THR) and row sum
+    // grouped: this lane's row's visibility word (the row clamped as the Q load is), and the group the run's tiles are in: tiles
+    // below tile index gend_t belong to group gid (scalars; advanced at the head of a tile)
+    [[maybe_unused]] uint32_t vis = 0;
+    [[maybe_unused]] int gid = 0, gend_t = 0;
+    if constexpr (GROUPED) {
+      vis = KG.row_vis[b * KG.stride_vis_b + min(q0 + wave * 32 + l31, S - 1)];
+      gend_t = (KG.end[0] + BKV - 1) / BKV;
+    }
 
     // ---- softmax pieces (all per lane; the row's other keys live in lane ^ 32)
     // row max of one 32-key half (this lane's 16 keys)
@@ -265,6 +294,22 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
         for (int r = 0; r < 16; ++r)
           if (t * BKV + 32 * h + (r & 3) + 8 * (r >> 2) + 4 * hh >= S) s[r] = -INFINITY;
       };
+      // grouped: lanes whose row does not see this tile's group drop all its scores (wave-uniform branch, as for the ragged tile)
+      [[maybe_unused]] bool hidden = false;
+      if constexpr (GROUPED) {
+        while (t >= gend_t && gid + 1 < KG.n) {
+          ++gid;
+          gend_t = (KG.end[gid] + BKV - 1) / BKV;
+        }
+        hidden = ((vis >> gid) & 1u) == 0;
+      }
+      auto hide_half = [&](f32x16& s) {
+        if (hidden) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[r] = -INFINITY;
+        }
+      };
+      [[maybe_unused]] const bool any_hidden = GROUPED && __any(hidden);
       rt_dma_barrier();                          // tile t landed (every wave's vmcnt(0), then the barrier); the other slot is free
       f32x16 s0, s1;
 #pragma unroll
@@ -295,6 +340,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
 #pragma unroll
       for (int ks = 3; ks < 8; ++ks) kB[ks] = kread(1, ks);
       if (RT_RARE(ragged)) mask_half(s0, 0);
+      if constexpr (GROUPED) { if (any_hidden) hide_half(s0); }
       float mx0 = half_max(s0);
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
@@ -324,6 +370,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
       for (int dt = 0; dt < 4; ++dt) vB[dt] = vread(0, 1, dt);
       numer8(s0, 1, p01);
       if (RT_RARE(ragged)) mask_half(s1, 1);
+      if constexpr (GROUPED) { if (any_hidden) hide_half(s1); }
       float mx1 = half_max(s1);
       RT_WEAVE(4, 2, 9)
       RT_PIN(p01); RT_PIN(l_run); RT_PIN(mx1);
@@ -391,7 +438,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
           return records + split_rec_index(G, b, xcd, j, split_seg_of(G, parts, j)) * (int64_t)REC_B + wave * REC_WAVE_B;
         };
         // pass 1: common max; pass 2: weighted sum in run order
-        float M = -INFINITY;
+        float M = -INFINITY;   // grouped: every record's m is finite (a run that saw nothing: GROUPED_M0, l = 0, O = 0 — weight 0 or, if no run saw anything, 1)
         for (int j = parts.j_first; j <= parts.j_last; ++j) {
           const char* rj = rec_of(__builtin_amdgcn_readfirstlane(j));
           M = fmaxf(M, *reinterpret_cast<const float*>(rj + 16384 + lane * 8));
@@ -422,7 +469,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
 
     // ---- epilogue: O[q][d] = Oᵀ / l ; lane holds q = l31, d = 32dt + (r&3) + 8(r>>2) + 4hh
     const float l_tot = l_run + __shfl_xor(l_run, 32);
-    const float inv = 1.0f / l_tot;
+    const float inv = (GROUPED && !(l_tot > 0.f)) ? 0.f : 1.0f / l_tot;   // grouped: a row that sees no key gets zeros
     const bool wide = (ldo % 8 == 0) && (stride_ob % 8 == 0) && ((reinterpret_cast<uintptr_t>(O) & 15) == 0);
     if (wide) {
       rt_store_o_rows(O + b * stride_ob + (int64_t)min(qrow, S - 1) * ldo + head * DH, qrow < S, hh, o_acc, inv);
@@ -480,11 +527,10 @@ extern "C" int rt_attention_fwd(const void* q, const void* k, const void* v, voi
   return rt_attention_fwd_rows(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, 0, S, ws, ws_bytes, stream);
 }
 
-// The full launch, cut exactly as rt_attention_fwd cuts it (same kernel, grid, key split and workspace), in which only the items that
-// hold a query row of [row_lo, row_hi) do any work: those rows get the bits rt_attention_fwd gives them, at the cost of their items.
-extern "C" int rt_attention_fwd_rows(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b,
-                                     int64_t ldo, int64_t stride_ob, int32_t B, int32_t S, int32_t H, float scale,
-                                     int32_t row_lo, int32_t row_hi, void* ws, int64_t ws_bytes, void* stream) {
+namespace {
+
+int check_common(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob, int32_t B,
+                 int32_t S, int32_t H, int32_t row_lo, int32_t row_hi) {
   if (!q || !k || !v || !o || B < 1 || S < 1 || H < 1 || row_lo < 0 || row_hi > S || row_lo >= row_hi) return RT_E_BADARG;
   if (!RT_ALIGNED(q, 16) || !RT_ALIGNED(k, 16) || !RT_ALIGNED(v, 16) || !RT_ALIGNED(o, 8) || ld % 8 || stride_b % 8 ||
       ldo % 4 || stride_ob % 4)
@@ -492,11 +538,13 @@ extern "C" int rt_attention_fwd_rows(const void* q, const void* k, const void* v
   if (ld < (int64_t)H * DH || ldo < (int64_t)H * DH) return RT_E_SHAPE;
   if ((int64_t)(S + BKV) * ld * 2 >= (int64_t)1 << 31) return RT_E_SHAPE;      // per-tile byte offsets are 32-bit
   if (!split_fits_32bit(make_geom(S, H, true))) return RT_E_SHAPE;
-  {
-    int taken = 0;
-    const int st = rt_attention_v3_try(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, row_lo, row_hi, ws, ws_bytes, stream, &taken);
-    if (taken || st != RT_OK) return st;
-  }
+  return RT_OK;
+}
+
+// The launch of attention_fwd_kernel<GROUPED>: one grid, key split and workspace for both instantiations.
+template <bool GROUPED, class KG>
+int launch(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob, int32_t B,
+           int32_t S, int32_t H, float scale, int32_t row_lo, int32_t row_hi, void* ws, int64_t ws_bytes, void* stream, const KG& kg) {
   const int64_t need = rt_attention_ws_bytes(B, S, H);
   const bool split = ws != nullptr && need > 0;
   if (split && (ws_bytes < need || !RT_ALIGNED(ws, 256))) return RT_E_BADARG;
@@ -504,9 +552,48 @@ extern "C" int rt_attention_fwd_rows(const void* q, const void* k, const void* v
   int wmax = 0;
   for (int x = 0; x < 8; ++x) wmax = group_slots(G, x) > wmax ? group_slots(G, x) : wmax;
   const dim3 grid(8 * wmax, B);
-  hipLaunchKernelGGL(attention_fwd_kernel, grid, dim3(ATT_THREADS), 0, (hipStream_t)stream, (const bf16_t*)q,
+  hipLaunchKernelGGL(attention_fwd_kernel<GROUPED>, grid, dim3(ATT_THREADS), 0, (hipStream_t)stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ld, stride_b, ldo, stride_ob,
                      scale * 1.4426950408889634f, G, row_lo, row_hi, split ? (int*)ws : nullptr,
-                     split ? (char*)ws + split_cnt_bytes(B, S, H) : nullptr);
+                     split ? (char*)ws + split_cnt_bytes(B, S, H) : nullptr, kg);
   return rt_hip_status();
+}
+
+}  // namespace
+
+// The full launch, cut exactly as rt_attention_fwd cuts it (same kernel, grid, key split and workspace), in which only the items that
+// hold a query row of [row_lo, row_hi) do any work: those rows get the bits rt_attention_fwd gives them, at the cost of their items.
+extern "C" int rt_attention_fwd_rows(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b,
+                                     int64_t ldo, int64_t stride_ob, int32_t B, int32_t S, int32_t H, float scale,
+                                     int32_t row_lo, int32_t row_hi, void* ws, int64_t ws_bytes, void* stream) {
+  if (const int st = check_common(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, row_lo, row_hi)) return st;
+  {
+    int taken = 0;
+    const int st = rt_attention_v3_try(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, row_lo, row_hi, ws, ws_bytes, stream, &taken);
+    if (taken || st != RT_OK) return st;
+  }
+  return launch<false>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, row_lo, row_hi, ws, ws_bytes, stream, NoGroups{});
+}
+
+// Region-masked joint attention: always attention_fwd_kernel<true> — the grid, XCD placement, key split and workspace of the dense
+// launch of (B, S, H); never attention_v3, whatever rt_attention_variant says. No tile is skipped: a hidden tile costs what a visible one does.
+extern "C" int rt_attention_fwd_grouped(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b,
+                                        int64_t ldo, int64_t stride_ob, int32_t B, int32_t S, int32_t H, float scale,
+                                        const int32_t* group_end, int32_t n_groups, const uint32_t* row_vis, int64_t stride_vis_b,
+                                        void* ws, int64_t ws_bytes, void* stream) {
+  if (const int st = check_common(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, 0, S)) return st;
+  if (!(scale > 0.f) || !group_end || !row_vis || n_groups < 1 || n_groups > MAX_GROUPS || stride_vis_b < 0) return RT_E_BADARG;
+  if (!RT_ALIGNED(row_vis, 4)) return RT_E_ALIGN;
+  KeyGroups kg = {};
+  int32_t prev = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    const int32_t e = group_end[g];
+    if (e <= prev || e > S || (g + 1 < n_groups && e % BKV) || (g + 1 == n_groups && e != S)) return RT_E_BADARG;
+    kg.end[g] = prev = e;
+  }
+  for (int g = n_groups; g < MAX_GROUPS; ++g) kg.end[g] = S;
+  kg.n = n_groups;
+  kg.row_vis = row_vis;
+  kg.stride_vis_b = stride_vis_b;
+  return launch<true>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, 0, S, ws, ws_bytes, stream, kg);
 }

@@ -31,7 +31,7 @@ class HeaderParseError(ValueError):
 
 
 _SCALARS = {"int": C.c_int, "int32_t": C.c_int32, "int64_t": C.c_int64, "float": C.c_float}
-_POINTEES = set(_SCALARS) | {"void", "uint8_t"}
+_POINTEES = set(_SCALARS) | {"void", "uint8_t", "uint32_t"}
 _DECL = re.compile(r"(?:const\s+)?(\w+)\s*(\*?)\s*((?:\w+\s*,\s*)*\w+)?")
 _STATEMENT = re.compile(r"\s*(?:typedef\s+struct\s+\w*\s*\{([^{}]*)\}\s*(\w+)|((?:const\s+)?\w+\s*\*?)\s*(rt_\w+)\s*\(([^()]*)\))\s*;")
 _DEFINE = re.compile(r"#\s*define\s+(\w+)\s*(.*)")

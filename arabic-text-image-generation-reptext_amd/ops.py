@@ -511,16 +511,56 @@ def drop_attention_workspaces(keys) -> None:
         _ATTN_WS.pop(k, None)
 
 
+@dataclass(frozen=True)
+class KeyGroups:
+    """Key groups of a region-masked attention call (rt_attention_fwd_grouped). ``ends``: ascending key indices, group g = keys
+    [ends[g-1], ends[g]); at most 32, the last equals S, all others are multiples of 64. ``row_vis``: int32 or uint32 [B or 1, S] on the
+    device; query row i of entry b attends the keys of group g iff bit g of row_vis[b, i] is set ([1, S]: one table for the batch)."""
+    ends: tuple
+    row_vis: torch.Tensor
+
+    def check(self, B: int, S: int) -> Tuple[int, int]:
+        """Validate against a [B, S, .] call; returns (row_vis pointer, its batch stride in words)."""
+        ends = tuple(int(e) for e in self.ends)
+        if not 1 <= len(ends) <= 32:
+            raise ValueError(f"groups: need 1..32 key groups, got {len(ends)}")
+        if any(b <= a for a, b in zip((0,) + ends, ends)):
+            raise ValueError(f"groups: ends must be positive and ascending, got {ends}")
+        if any(e % 64 for e in ends[:-1]):
+            raise ValueError(f"groups: every end but the last must be a multiple of 64, got {ends}")
+        if ends[-1] != S:
+            raise ValueError(f"groups: the last end must be S = {S}, got {ends[-1]}")
+        rv = self.row_vis
+        if not isinstance(rv, torch.Tensor) or rv.dtype not in (torch.int32, torch.uint32):
+            raise TypeError("groups.row_vis must be an int32 or uint32 tensor")
+        if rv.dim() != 2 or rv.shape[1] != S or rv.shape[0] not in (1, B) or rv.stride(1) != 1:
+            raise ValueError(f"groups.row_vis: need [{B} or 1, {S}] with unit inner stride, got {tuple(rv.shape)} / {rv.stride()}")
+        return _dev(rv, "groups.row_vis"), (0 if rv.shape[0] == 1 else rv.stride(0))
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, scale: Optional[float] = None,
-              split: bool = True, rows: Optional[tuple] = None) -> torch.Tensor:
+              split: bool = True, rows: Optional[tuple] = None, groups: Optional[KeyGroups] = None) -> torch.Tensor:
     """q,k,v [B,S,H*128] views (common strides) of one buffer; out [B,S,H*128] view (may alias q). ``split=False`` runs every
     128-row block as one full-length workgroup (no key-split tail; A/B and tests). ``rows`` = (r0, r1): only the items of the launch that
     hold a query row of [r0, r1) do any work (rt_attention_fwd_rows): those rows of out get the bits the whole launch gives them, the
-    other rows of the touched items are written too, the rest of out is left as it is."""
+    other rows of the touched items are written too, the rest of out is left as it is. ``groups`` (a KeyGroups; not together with
+    ``rows``): region-masked attention, rt_attention_fwd_grouped — hidden keys must still hold finite values."""
     (B, S, _, ld, sb), _, _, (_, _, _, ldo, sob) = [_rows3(t, name, width=H * 128) for name, t in (("q", q), ("k", k), ("v", v), ("out", out))]
     if not (q.stride() == k.stride() == v.stride()) or k.shape != q.shape or v.shape != q.shape or out.shape != q.shape:
         raise ValueError("q,k,v must share shape and strides")
     sc = (128 ** -0.5) if scale is None else float(scale)
+    if groups is not None:
+        if rows is not None:
+            raise ValueError("attention: rows= and groups= cannot be combined")
+        if not sc > 0:
+            raise ValueError("attention: groups= needs scale > 0")
+        vis, svb = groups.check(B, S)
+        ends = (C.c_int32 * len(groups.ends))(*[int(e) for e in groups.ends])
+        ws = _attention_workspace(B, S, H, q.device) if split else None
+        native.call("rt_attention_fwd_grouped", _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(out, "out", BF16), ld, sb,
+                    ldo, sob, B, S, H, sc, C.cast(ends, C.c_void_p), len(groups.ends), vis, svb,
+                    None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), _stream())
+        return out
     ws = _attention_workspace(B, S, H, q.device) if split else None
     r0, r1 = (0, S) if rows is None else (int(rows[0]), int(rows[1]))
     native.call("rt_attention_fwd_rows", _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(out, "out", BF16), ld, sb,

@@ -174,6 +174,19 @@ class CallExtensions:
     negative_ip_adapter_image_embeds: Any = None
 
 
+LINE_PROMPT_ARGUMENTS = ("control_prompt", "control_prompt_embeds", "control_prompt_max_sequence_length")
+MAX_LINE_PROMPTS = 30                   # groups: the base prompt, one per line prompt, the image tokens — at most 32 (rt_attention_fwd_grouped)
+
+
+@dataclass
+class LineCallExtensions(CallExtensions):
+    """``CallExtensions`` of a call that names a per-line prompt (``LINE_PROMPT_ARGUMENTS``): the record with its three keywords behind
+    the thirteen. ``accepts_call_extensions`` builds it only for such a call; every other call carries the plain record it always did."""
+    control_prompt: Any = None                          # one entry per text line, parallel to control_image: a string or None
+    control_prompt_embeds: Any = None                   # the same as T5 embeddings: one [B, L, joint_attention_dim] tensor or None per line
+    control_prompt_max_sequence_length: int = 128       # L: a multiple of 64, at most 512
+
+
 def accepts_call_extensions(*names):
     """``__call__`` keeps the reference's parameter list (PIPE:751-781, which ``inspect.signature`` still reports). The fields of
     ``CallExtensions`` in ``names`` are keyword-only extensions of it, taken off here and left on the pipeline, as passed, as
@@ -182,7 +195,9 @@ def accepts_call_extensions(*names):
     def decorate(call):
         @functools.wraps(call)
         def wrapper(self, *args, **kwargs):
-            self._call_extensions = CallExtensions(**{k: kwargs.pop(k) for k in names if k in kwargs})
+            taken = {k: kwargs.pop(k) for k in names if k in kwargs}
+            record = LineCallExtensions if any(k in LINE_PROMPT_ARGUMENTS for k in taken) else CallExtensions
+            self._call_extensions = record(**taken)
             try:
                 return call(self, *args, **kwargs)
             finally:
@@ -210,6 +225,84 @@ class Repaint:
 
 
 @dataclass(frozen=True)
+class LinePrompts:
+    """Per-line prompts of a call: the transformer's text stream is ``cat([prompt_embeds, embeds], dim=1)`` and its joint
+    attention runs with the key groups ``ends`` and the row table ``row_vis`` (``line_prompt_groups``). The towers see the base prompt."""
+    embeds: torch.Tensor      # [Bc, R·L, joint_attention_dim]: the R line prompts' T5 embeddings, one after another
+    ends: Tuple[int, ...]     # key-group ends over the T0 + R·L + N joint rows
+    row_vis: torch.Tensor     # int32 [Bc, T0 + R·L + N]: bit g set = the row sees group g
+
+    def groups(self, rows: Optional[slice] = None) -> "ops.KeyGroups":
+        return ops.KeyGroups(self.ends, self.row_vis if rows is None else self.row_vis[rows])
+
+
+def line_prompt_groups(T0: int, L: int, masks, N: int, has_prompt=None, batch: int = 1, cfg: bool = False):
+    """The visibility contract of per-line prompts, from host values alone -> (ends, row_vis int32 [batch · (2 if cfg else 1), S]), or
+    None when no line has a prompt. ``masks``: one per text line, the regional mask after the pipeline's ÷16 bilinear resize, as [N],
+    [1, N, 1] or [batch, N, 1] values; ``has_prompt``: which lines have a prompt (default: all).
+    Groups: 0 = the base prompt's T0 tokens; r = 1..R the L tokens of the r-th line THAT HAS A PROMPT; R + 1 = the N image tokens.
+    Base text rows see {0, R+1}; line r's text rows see {r, R+1}; image token n sees {0, R+1} and every r whose line's mask is > 0 at n
+    (the rule ``active_row_window`` uses for a non-zero row; overlapping boxes OR their bits). Under true CFG the conditioning batch
+    is [negative, positive]: the negative half's image rows see {0, R+1} only."""
+    has_prompt = [True] * len(masks) if has_prompt is None else [bool(h) for h in has_prompt]
+    if len(has_prompt) != len(masks):
+        raise ValueError(f"line prompts: {len(has_prompt)} entries for {len(masks)} regional masks")
+    lines = [i for i, h in enumerate(has_prompt) if h]
+    R = len(lines)
+    if R == 0:
+        return None
+    if R > MAX_LINE_PROMPTS:
+        raise ValueError(f"at most {MAX_LINE_PROMPTS} line prompts are supported, got {R}")
+    if T0 < 64 or T0 % 64 or L < 64 or L % 64:
+        raise ValueError(f"line prompts: the base prompt's length ({T0}) and control_prompt_max_sequence_length ({L}) must be multiples of 64 "
+                         "(a 64-key attention tile lies in one group)")
+    T = T0 + R * L
+    S = T + N
+    ends = (T0,) + tuple(T0 + r * L for r in range(1, R + 1)) + (S,)
+    img = 1 << (R + 1)
+    vis = np.full((batch * (2 if cfg else 1), S), 1 | img, dtype=np.uint32)
+    for r, line in enumerate(lines, start=1):
+        vis[:, T0 + (r - 1) * L : T0 + r * L] = (1 << r) | img
+        on = torch.as_tensor(masks[line]).detach().to("cpu", torch.float32).reshape(-1, N).numpy() > 0      # [1 or batch, N]
+        if on.shape[0] not in (1, batch):
+            raise ValueError(f"line prompts: regional mask {line} has {on.shape[0]} entries for a batch of {batch}")
+        vis[-batch:, T:] |= np.where(on, np.uint32(1 << r), np.uint32(0))
+    return ends, torch.from_numpy(vis.view(np.int32))
+
+
+def line_prompt_arguments(ext, n_lines: int, control_mask, fp8_attention: bool = False) -> Optional[list]:
+    """Check the per-line prompt keywords of a call -> one entry per text line (a string, a [B, L, D] tensor or None), or None when
+    the call names none."""
+    prompts, embeds = getattr(ext, "control_prompt", None), getattr(ext, "control_prompt_embeds", None)
+    if prompts is None and embeds is None:
+        return None
+    if prompts is not None and embeds is not None:
+        raise ValueError("pass control_prompt or control_prompt_embeds, not both")
+    entries = prompts if prompts is not None else embeds
+    name = "control_prompt" if prompts is not None else "control_prompt_embeds"
+    if not isinstance(entries, (list, tuple)) or len(entries) != n_lines:
+        raise ValueError(f"{name} must be a list with one entry per text line (control_image has {n_lines}), a {'string' if prompts is not None else 'tensor'} or None each")
+    L = ext.control_prompt_max_sequence_length
+    if not isinstance(L, int) or L < 64 or L % 64 or L > 512:
+        raise ValueError(f"control_prompt_max_sequence_length must be a multiple of 64 and at most 512, got {L}")
+    for e in entries:
+        if e is not None and not isinstance(e, str if prompts is not None else torch.Tensor):
+            raise ValueError(f"{name}: an entry is a {'string' if prompts is not None else 'tensor'} or None, got {type(e).__name__}")
+        if isinstance(e, torch.Tensor) and (e.dim() != 3 or e.shape[1] != L):
+            raise ValueError(f"control_prompt_embeds: an entry is [B, {L}, joint_attention_dim] (control_prompt_max_sequence_length rows), got {tuple(e.shape)}")
+    if sum(e is not None for e in entries) > MAX_LINE_PROMPTS:
+        raise ValueError(f"at most {MAX_LINE_PROMPTS} line prompts are supported, got {sum(e is not None for e in entries)}")
+    if all(e is None for e in entries):
+        return None
+    if control_mask is None or len(control_mask) != n_lines:
+        raise ValueError(f"{name} needs control_mask: a line's prompt is visible to the image tokens inside that line's regional mask")
+    if fp8_attention:
+        raise ValueError(f"{name} cannot be combined with enable_fp8_attention: the e4m3 attention kernel takes no mask "
+                         "(the e4m3 linear levels with bf16 attention are fine)")
+    return list(entries)
+
+
+@dataclass(frozen=True)
 class LoopExtras:
     """What a call adds to the plain loop of ``_denoise_eager``. ``_denoise`` takes the first three and ``repaint`` (static inputs and key
     of the captured graph) and sets ``tower_window`` itself."""
@@ -226,6 +319,7 @@ class LoopExtras:
     # under true CFG, a guider that changes the call (guidance.Guidance: the guider and the steps it guides): projected guidance at
     # those steps, and the steps outside them run on the positive half alone, at the latents' batch B; None: every step is the CFG step
     guidance: Optional[Guidance] = None
+    line_prompts: Optional[LinePrompts] = None   # per-line prompts: a longer text stream and key groups for the transformer alone
     quiet: bool = False                          # no progress bar (a capture)
 
 
@@ -893,7 +987,7 @@ class FluxControlNetPipeline:
         return Image.new("RGB", (size, size), (0, 0, 0))
 
     # ------------------------------------------------------------------ the call
-    @accepts_call_extensions(*CallExtensions.__dataclass_fields__)
+    @accepts_call_extensions(*LineCallExtensions.__dataclass_fields__)
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 28,
@@ -935,6 +1029,8 @@ class FluxControlNetPipeline:
         ext = self._call_extensions
         with_union = self._check_union_inputs(ext.control_image_union, height, width, total)
         cfg = self._check_true_cfg_inputs(ext, prompt_embeds, pooled_prompt_embeds, batch_size, joint_attention_kwargs)
+        line_entries = line_prompt_arguments(ext, len(control_image) if control_image is not None else 0, control_mask,
+                                             bool(getattr(self.transformer, "_fp8_attention", False)))
         ip_embeds, self._joint_attention_kwargs = self._resolve_ip_embeds(ext.ip_adapter_image, ext.ip_adapter_image_embeds, joint_attention_kwargs,
                                                                           batch_size, num_images_per_prompt, device)
         if cfg and ip_embeds is not None:
@@ -963,17 +1059,41 @@ class FluxControlNetPipeline:
         timesteps, num_inference_steps = self._schedule(height, width, num_inference_steps, timesteps, device)
         timesteps, num_inference_steps = self._cut_schedule(start, timesteps, num_inference_steps)
         latents, latent_image_ids, repaint = self._start_state(start, control_glyph, total, height, width, prompt_embeds.dtype, device, generator, latents)
-        masks = [self._doubled_under_cfg(m, total, cfg, mask=True) for m in self._region_masks(control_mask, latents.device, prompt_embeds.dtype)]
+        region = self._region_masks(control_mask, latents.device, prompt_embeds.dtype)
+        masks = [self._doubled_under_cfg(m, total, cfg, mask=True) for m in region]
+        line_prompts = self._line_prompts(line_entries, ext, region, prompt_embeds, latents.shape[1], total, num_images_per_prompt, cfg, device)
         active = union_active_steps(len(timesteps), float(ext.control_guidance_start_union), float(ext.control_guidance_end_union)) if with_union else ()
         union = UnionTower(self.controlnet_union, union_hint, float(ext.controlnet_conditioning_scale_union), active) if active else None
         extras = LoopExtras(ip_embeds=ip_embeds, union=union, cfg_scale=float(ext.true_cfg_scale) if cfg else None, repaint=repaint,
-                            guidance=loop_guidance(self.guider, cfg, len(timesteps)))
+                            guidance=loop_guidance(self.guider, cfg, len(timesteps)), line_prompts=line_prompts)
 
         self._apply_lora_scale()
         latents = self._denoise(latents, prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids, timesteps, hints, masks,
                                 guidance_scale, controlnet_conditioning_scale, controlnet_conditioning_step, control_mode,
                                 callback_on_step_end, callback_on_step_end_tensor_inputs, num_inference_steps, extras)
         return self._finish(latents, height, width, output_type, return_dict)
+
+    def _line_prompts(self, entries, ext, region, prompt_embeds, N, total, num_images_per_prompt, cfg, device) -> Optional[LinePrompts]:
+        """The call's per-line prompts as the loop takes them (None: the call has none). T5 only: the pooled CLIP vector stays the base
+        prompt's. Under true CFG the line embeddings serve both halves; the negative half's image rows do not see them."""
+        if entries is None:
+            return None
+        L, Bc, T0 = ext.control_prompt_max_sequence_length, prompt_embeds.shape[0], prompt_embeds.shape[1]
+        table = line_prompt_groups(T0, L, region, N, [e is not None for e in entries], batch=total, cfg=cfg)
+        embeds = []
+        for e in entries:
+            if isinstance(e, str):
+                self._require_text_stack()
+                e = self._get_t5_prompt_embeds([e] * (total // num_images_per_prompt), num_images_per_prompt, L, device)
+            elif e is not None:
+                if e.shape[0] not in (1, total // num_images_per_prompt) or e.shape[2] != prompt_embeds.shape[2]:
+                    raise ValueError(f"control_prompt_embeds: an entry is [B or 1, {L}, {prompt_embeds.shape[2]}] with B the prompt's batch, got {tuple(e.shape)}")
+                e = e.expand(total // num_images_per_prompt, -1, -1).repeat_interleave(num_images_per_prompt, dim=0)
+            if e is not None:
+                e = e.to(device=device, dtype=prompt_embeds.dtype)
+                embeds.append(torch.cat([e, e]) if cfg else e)
+        assert all(e.shape[0] == Bc for e in embeds)
+        return LinePrompts(torch.cat(embeds, dim=1).contiguous(), table[0], table[1].to(device))
 
     # ------------------------------------------------------------------ stages of the call (shared with pipeline_inpaint.py)
     @staticmethod
@@ -1077,6 +1197,7 @@ class FluxControlNetPipeline:
         extras = replace(extras or LoopExtras(), tower_window=win)
         # under true CFG (cfg_scale) prompt_embeds / pooled / hints hold [negative, positive]
         ipe, union, cfg_scale, repaint, guidance = extras.ip_embeds, extras.union, extras.cfg_scale, extras.repaint, extras.guidance
+        lp = extras.line_prompts
 
         def eager(callback=None):
             return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
@@ -1120,6 +1241,10 @@ class FluxControlNetPipeline:
             # and the partial sums are allocated inside the capture, in the graph's pool, like the fp32 state
             g = guidance.guider
             key += (("guidance", guidance.steps, float(g.eta), float(g.norm_threshold), float(g.momentum)),)
+        if lp is not None:
+            # the line embeddings and the row table are two more static inputs; the group ends are kernel arguments baked into the capture
+            key += (("line_prompts", lp.ends, sig(lp.row_vis), sig(lp.embeds)),)
+            ins.update(line_embeds=lp.embeds, line_row_vis=lp.row_vis)
         solver_order = getattr(self.scheduler, "solver_order", 1)
         if solver_order > 1:
             # the multistep weights are kernel scalars of every step, fixed by the sigmas and the timesteps that are in the key already;
@@ -1156,7 +1281,8 @@ class FluxControlNetPipeline:
                 with torch.cuda.graph(graph, capture_error_mode="thread_local"):
                     captured = replace(extras, quiet=True, ip_embeds=static.get("ip_embeds"),
                                        union=union and replace(union, hint=static["union_hint"]),
-                                       repaint=repaint and Repaint(static["repaint_src"], static["repaint_noise"], static["repaint_mask"]))
+                                       repaint=repaint and Repaint(static["repaint_src"], static["repaint_noise"], static["repaint_mask"]),
+                                       line_prompts=lp and replace(lp, embeds=static["line_embeds"], row_vis=static["line_row_vis"]))
                     out = self._denoise_eager(static["latents"], static["prompt_embeds"], static["pooled"], static["text_ids"], static["image_ids"],
                                               tvals, static["hints"], static["masks"], guidance_scale, cn_scale, cn_steps, control_mode, None,
                                               callback_inputs, num_inference_steps, timesteps, extras=captured)
@@ -1246,8 +1372,15 @@ class FluxControlNetPipeline:
         # Loop-invariant work, once per image instead of once per step (the prompt and the hint latents do not change inside the
         # loop): context_embedder(prompt) of every model, controlnet_x_embedder(hint) per tower. A callback that replaces
         # prompt_embeds invalidates them (recomputed below).
+        # Per-line prompts: the transformer alone reads cat([base prompt, line prompts]) with text ids of that length (zeros, like the
+        # base prompt's) and the key groups; every tower, and a callback, sees the base prompt.
+        lp = extras.line_prompts
+        joint_text = lambda pe: pe if lp is None else torch.cat([pe, lp.embeds.to(pe.dtype)], dim=1)
+        text_ids_t = text_ids if lp is None else torch.zeros(prompt_embeds.shape[1] + lp.embeds.shape[1], 3, device=text_ids.device, dtype=text_ids.dtype)
+        prompt_t = joint_text(prompt_embeds)
+
         def prepare_static(pe):
-            static_t = self.transformer.prepare_static(pe)
+            static_t = self.transformer.prepare_static(joint_text(pe))
             for tw in towers:
                 tw.static = tw.model.prepare_static(pe, tw.hint)
             return static_t
@@ -1307,13 +1440,15 @@ class FluxControlNetPipeline:
         pos_rows = slice(Bc - B, Bc)
 
         def positive_half(pe, st):
-            """(prompt, pooled, transformer's static embeddings, towers, sample buffers, single buffers, image prompt) of the positive half."""
+            """(prompt, pooled, transformer's static embeddings, towers, sample buffers, single buffers, image prompt, the transformer's
+            text stream, its key groups) of the positive half."""
             pos = lambda t: t if t is None or t.shape[0] != Bc else t[Bc - B:]
             tws = [replace(tw, hint=pos(tw.hint), rowscale=tw.rowscale if tw.rowscale is None or tw.rowscale.dim() == 1 else pos(tw.rowscale),
                            static=replace(tw.static, ctx=pos(tw.static.ctx), hint=pos(tw.static.hint))) for tw in towers]
             ip = ip_prep and replace(ip_prep, kv=[(pos(k), pos(v)) for k, v in ip_prep.kv], tok=pos(ip_prep.tok))
             lead = lambda bufs: None if bufs is None else [b[:B] for b in bufs]
-            return pos(pe), pos(pooled), replace(st, ctx=pos(st.ctx), hint=pos(st.hint)), tws, lead(sample_buf), lead(single_buf), ip
+            return (pos(pe), pos(pooled), replace(st, ctx=pos(st.ctx), hint=pos(st.hint)), tws, lead(sample_buf), lead(single_buf), ip,
+                    pos(joint_text(pe)), lp and lp.groups(slice(Bc - B, Bc)))
 
         half = positive_half(prompt_embeds, static_t) if gd is not None and len(gd.steps) < len(tvals) else None
         # Tower ∥ transformer: within a step the tower's chain of kernels and the transformer's are independent except that
@@ -1340,8 +1475,8 @@ class FluxControlNetPipeline:
                 timestep = torch.full((B,), self._model_timestep(t), device=device, dtype=torch.float32)      # PIPE:1025,1048 (Q4)
                 # the conditioning this step sees: everything (under true CFG at 2B), or the positive half outside a guider's interval
                 guided = guided_at is None or i in guided_at
-                everything = (prompt_embeds, pooled, static_t, towers, sample_buf, single_buf, ip_prep)
-                c_pe, c_pooled, c_static, c_towers, c_samples, c_singles, c_ip = everything if guided else half
+                everything = (prompt_embeds, pooled, static_t, towers, sample_buf, single_buf, ip_prep, prompt_t, lp and lp.groups())
+                c_pe, c_pooled, c_static, c_towers, c_samples, c_singles, c_ip, c_pe_t, c_groups = everything if guided else half
                 rows = None if guided else pos_rows        # of the modulation tables, which hold 2B rows per step
                 merged = merged_single = events = None
                 if steps[i]:
@@ -1376,9 +1511,10 @@ class FluxControlNetPipeline:
                     merged_single = [b if j < done_s else None for j, b in enumerate(c_singles)] or None
                 noise_pred = self.transformer(
                     hidden_states=latents, timestep=timestep, guidance=guidance, pooled_projections=c_pooled,
-                    encoder_hidden_states=c_pe, controlnet_block_samples=merged, controlnet_single_block_samples=merged_single,
-                    txt_ids=text_ids, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs, return_dict=False,
-                    _mods=tab_t.step(i) if rows is None else tab_t.step(i, rows), _sample_events=events, _static=c_static, _ip=c_ip)[0]
+                    encoder_hidden_states=c_pe_t, controlnet_block_samples=merged, controlnet_single_block_samples=merged_single,
+                    txt_ids=text_ids_t, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs, return_dict=False,
+                    _mods=tab_t.step(i) if rows is None else tab_t.step(i, rows), _sample_events=events, _static=c_static, _ip=c_ip,
+                    **({} if c_groups is None else dict(_groups=c_groups)))[0]
                 if events is not None:
                     torch.cuda.current_stream().wait_stream(side)     # the tower has finished reading `latents` (its last sample is unused, Q5)
                 if extras.velocity is not None:
@@ -1401,7 +1537,7 @@ class FluxControlNetPipeline:
                             proj.first = True                    # and so does the guidance difference: no momentum next
                     if "prompt_embeds" in out:                       # the loop-invariant embeddings are no longer valid
                         prompt_embeds = out.pop("prompt_embeds")
-                        static_t = prepare_static(prompt_embeds)
+                        static_t, prompt_t = prepare_static(prompt_embeds), joint_text(prompt_embeds)
                         half = half and positive_half(prompt_embeds, static_t)
                 if i == len(tvals) - 1 or ((i + 1) > num_warmup and (i + 1) % self.scheduler.order == 0):
                     bar.update()

@@ -360,13 +360,15 @@ class FluxTransformer2DModel(_MMDiTBase):
                 joint_attention_kwargs: Optional[Dict[str, Any]] = None, controlnet_block_samples=None,
                 controlnet_single_block_samples=None, return_dict: bool = True, controlnet_blocks_repeat: bool = False,
                 _mods: Optional["mmdit.StepMods"] = None, _sample_events: Optional[Sequence["torch.cuda.Event"]] = None,
-                _static: Optional[StaticEmbeds] = None, _ip: Optional["ip_adapter.PreparedIP"] = None):
+                _static: Optional[StaticEmbeds] = None, _ip: Optional["ip_adapter.PreparedIP"] = None,
+                _groups: Optional["ops.KeyGroups"] = None):
         """``joint_attention_kwargs["ip_adapter_image_embeds"]`` (as in diffusers): the image prompt of a loaded IP-Adapter, projected
         and applied in every double block — in every block, single ones included, for an InstantX adapter (ip_adapter.py); ``_ip`` (optional) = the same already prepared (``_ip_adapter.prepare``), so
         that a loop does not redo the projection per step.
         ``_sample_events[k]`` (optional): event another stream records when controlnet_block_samples[k] is complete; the
         current stream waits for it right before the first block that consumes that sample. ``_static`` (optional): this
-        model's loop-invariant embeddings (prepare_static) — the text rows are copied instead of recomputed."""
+        model's loop-invariant embeddings (prepare_static) — the text rows are copied instead of recomputed. ``_groups`` (optional): an
+        ops.KeyGroups over the T + N joint rows, handed to the joint attention of every block (per-line prompts, pipeline.line_prompt_groups)."""
         doubles, singles = self._ensure_plans()
         joint_attention_kwargs = dict(joint_attention_kwargs or {})          # a copy: the image prompt is popped below, as diffusers does
         ip_embeds = joint_attention_kwargs.pop("ip_adapter_image_embeds", None)
@@ -397,6 +399,7 @@ class FluxTransformer2DModel(_MMDiTBase):
                 raise ValueError("ip_adapter_image_embeds were passed but no IP-Adapter is loaded (load_ip_adapter)")
             _ip = self._ip_adapter.prepare(ip_embeds) if self._ip_adapter.active else None
         waited = set()
+        gkw = {} if _groups is None else dict(groups=_groups)               # a call without key groups calls the blocks as it always did
         for i, pl in enumerate(doubles):
             inj = None
             if controlnet_block_samples is not None:
@@ -408,7 +411,7 @@ class FluxTransformer2DModel(_MMDiTBase):
                     waited.add(k)
             ip = None if _ip is None or _ip.scales[i] == 0.0 else (*_ip.kv[i], _ip.scales[i])
             mmdit.run_double(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.double[i], ip=ip,
-                             ip_inside=_ip is not None and _ip.inside)
+                             ip_inside=_ip is not None and _ip.inside, **gkw)
         for i, pl in enumerate(singles):
             inj = None
             if controlnet_single_block_samples is not None:
@@ -416,7 +419,7 @@ class FluxTransformer2DModel(_MMDiTBase):
             ip = None
             if _ip is not None and _ip.inside and _ip.scales[nl + i] != 0.0:
                 ip = (*_ip.kv[nl + i], _ip.scales[nl + i])
-            mmdit.run_single(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.single[i], ip=ip)
+            mmdit.run_single(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.single[i], ip=ip, **gkw)
         # AdaLayerNormContinuous: chunk order (scale, shift)  — A.3
         if _mods is not None:
             m = _mods.out

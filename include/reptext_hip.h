@@ -266,6 +266,22 @@ int rt_attention_fwd_rows(const void* q, const void* k, const void* v, void* o,
                           int32_t B, int32_t S, int32_t H, float scale, int32_t row_lo, int32_t row_hi,
                           void* ws, int64_t ws_bytes, void* stream);
 
+/* Region-masked joint attention (per-line prompts): rt_attention_fwd in which the keys fall into n_groups <= 32 contiguous groups
+ * and every query row carries a 32-bit set of the groups it sees. group_end: HOST array of n_groups ascending key indices, group g =
+ * keys [group_end[g-1], group_end[g]); the last is S, all others are multiples of 64 (a 64-key tile then lies in one group; the ends
+ * travel by value in the kernel arguments). row_vis: DEVICE [B][S] words, batch stride stride_vis_b elements (0: one table for the
+ * batch); row i of entry b attends key j iff bit g(j) of row_vis[b][i] is set. A row that sees no key gets zeros, never NaN.
+ * HIDDEN KEYS AND VALUES MUST STILL BE FINITE: no tile is skipped, a hidden key's value row meets a zero numerator on the MFMA
+ * (0 x NaN = NaN). scale > 0 is required (RT_E_BADARG): a hidden score is -inf times it. Always csrc/attention.hip's kernel (its
+ * grouped instantiation) with the grid, key split, workspace (rt_attention_ws_bytes) and batch invariance of the dense launch of
+ * (B, S, H); never attention_v3, rt_attention_variant does not affect it. With every bit set the output has the bits of that kernel's
+ * dense launch. Added without an ABI bump: nothing existing changed. */
+int rt_attention_fwd_grouped(const void* q, const void* k, const void* v, void* o,
+                             int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob,
+                             int32_t B, int32_t S, int32_t H, float scale,
+                             const int32_t* group_end, int32_t n_groups, const uint32_t* row_vis, int64_t stride_vis_b,
+                             void* ws, int64_t ws_bytes, void* stream);
+
 /* Which kernel serves rt_attention_fwd (speed only; both are tested against the same references): 1 (default, env RT_ATTN_V3) =
  * shapes with S % 256 == 0 and S >= 1536 run csrc/attention_v3.hip — one wave per SIMD, 64 query rows per wave, O / Q / row sums
  * in asm-owned accumulator registers, hand-placed MFMA gaps (S = 4608: 247 vs 264 us) —, everything else csrc/attention.hip;

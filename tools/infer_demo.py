@@ -61,6 +61,8 @@ ap.add_argument("--guidance-interval", type=float, nargs=2, default=(0.0, 1.0), 
 ap.add_argument("--apg-eta", type=float, default=1.0, help="projected guidance: weight of the difference's component parallel to the positive prediction")
 ap.add_argument("--apg-norm-threshold", type=float, default=0.0, help="projected guidance: clamp of the difference's per-sample norm (0: none)")
 ap.add_argument("--apg-momentum", type=float, default=0.0, help="projected guidance: beta of the running difference (APG's usual value: -0.5)")
+ap.add_argument("--line-prompt", action="append", default=None, metavar="TEXT",
+                help="a prompt of its own for a text line (control_prompt=): repeatable, one per text line in order; an empty string leaves a line without one")
 ap.add_argument("--source-image", default=None, help="photo to render the text into (the repaint pipeline's image=; the mask is the union of the lines' boxes)")
 ap.add_argument("--strength", type=float, default=0.6, help="share of the schedule a repaint runs")
 ap.add_argument("--photo-crop", type=int, default=None, help="with --source-image: keep the photo at its size and repaint only the region around "
@@ -171,6 +173,15 @@ if a.negative_prompt is not None:
                                 momentum=a.apg_momentum)
 elif a.true_cfg_scale != 1.0:
     ip_kwargs.update(true_cfg_scale=a.true_cfg_scale)                               # logs one line: no negative prompt, CFG stays off
+
+if a.line_prompt:
+    import zlib
+
+    if len(a.line_prompt) != len(text_list):
+        sys.exit(f"--line-prompt: give one per text line ({len(text_list)}), got {len(a.line_prompt)}")
+    named = lambda text: torch.randn(1, 128, 4096, generator=torch.Generator().manual_seed(zlib.crc32(text.encode("utf-8")))).to(dev, bf16)
+    # no text encoders here: embeddings named by the text (control_prompt=[...] takes the strings themselves where a T5 is loaded)
+    ip_kwargs.update(control_prompt_embeds=[named(t) if t else None for t in a.line_prompt], control_prompt_max_sequence_length=128)
 
 if a.source_image:
     from PIL import Image
