@@ -2,6 +2,10 @@
 // rt_ip_attention_gated — the same body with an optional fp32 column gate multiplied into ip_scale · acc before the write or
 // accumulate (GATED instantiations; the ungated ones are the code rt_ip_attention has always run): the InstantX form, whose term of a
 // double block goes through the adaLN gate_msa straight onto the residual rows, and whose single blocks query with all S rows.
+// rt_ip_attention_rows — the same body with an fp32 weight per query row (ROWS instantiations; the others are the code they were):
+// a regional image prompt. The weight joins ip_scale in fp32; a row of weight 0 is selected out, not multiplied (accumulate: its
+// output is neither read nor written; write: +0; its q row never reaches an output), a 16-row tile of such rows reads no q and runs
+// no MFMA, and a workgroup of such rows does not stage K / Vᵀ.
 //
 // Rectangular attention of many query rows (N image tokens) against a handful of image-prompt keys (1 <= n_ip <= 128), one pass,
 // no online softmax. Bound by memory: q is read once and o written once; K and V of a head (<= 64 KiB) are staged in LDS once per
@@ -37,9 +41,13 @@ struct IpArgs {
   int64_t ldq, stride_qb, ldkv, stride_kvb, ldo, stride_ob;
   int32_t N, n_ip, o_f32, accumulate;
   float sm_scale_log2, ip_scale, eps;
+  // ROWS only, last so that the other instantiations read their arguments where they always have
+  const float* row_w;          // [B or 1][N] fp32 weight per query row, batch stride stride_wb (0: one table)
+  int64_t stride_wb;
 };
 
-template <int KB, int TILES, bool GATED>   // key blocks of 32; 16-row tiles per wave; an fp32 gate per output column
+// key blocks of 32; 16-row tiles per wave; an fp32 gate per output column; an fp32 weight per query row (rt_ip_attention_rows)
+template <int KB, int TILES, bool GATED, bool ROWS>
 __global__ __launch_bounds__(256) void ip_attention_kernel(const IpArgs a) {
   // Vᵀ row stride (elements): NP + 8 puts the 16 rows x 2 lane groups of a half-wave's 8-byte reads on 64 distinct banks
   constexpr int NP = KB * 32, VLD = NP + 8;
@@ -48,6 +56,48 @@ __global__ __launch_bounds__(256) void ip_attention_kernel(const IpArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int h = blockIdx.x, b = blockIdx.z;        // heads fastest: the workgroups in flight together read neighbouring segments of the same rows
   const int r = lane & 15, g = lane >> 4;
+
+  // ROWS: lane (r, g) holds the weight of row r of the wave's tile g (g < TILES; rows beyond N count as zero). The ballot is the
+  // wave's tile mask, bits 16·it .. +15 = the rows of tile `it` that are worth something: wave-uniform, so every skip below is a
+  // scalar branch. A workgroup without one such row leaves before K / Vᵀ are staged: the decision comes out of the barrier itself, so
+  // all four waves take it together and none waits at the barrier below for a wave that has left.
+  float wlane = 0.f;
+  unsigned long long wmask = ~0ull;
+  auto zero_row = [&](int row) {                  // write mode: a row worth nothing is +0, whatever its q row holds
+    if (a.o_f32) {
+      f32x4* p = reinterpret_cast<f32x4*>((float*)a.o + (int64_t)b * a.stride_ob + (int64_t)row * a.ldo + h * 128 + 8 * g);
+#pragma unroll
+      for (int c = 0; c < 8; ++c) p[8 * (c >> 1) + (c & 1)] = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+      u32x4* p = reinterpret_cast<u32x4*>((bf16_t*)a.o + (int64_t)b * a.stride_ob + (int64_t)row * a.ldo + h * 128 + 8 * g);
+#pragma unroll
+      for (int cp = 0; cp < 4; ++cp) p[4 * cp] = u32x4{0u, 0u, 0u, 0u};
+    }
+  };
+  if constexpr (ROWS) {
+    const int wrow = blockIdx.y * (64 * TILES) + g * 64 + wave * 16 + r;
+    if (g < TILES && wrow < a.N) wlane = a.row_w[(int64_t)b * a.stride_wb + wrow];
+    wmask = __ballot(wlane != 0.f);
+    if (!__syncthreads_or(wmask != 0ull)) {       // workgroup-uniform
+      if (!a.accumulate && g < TILES && wrow < a.N) {
+        // the 4 lanes (r, 0..3) of a row write its 128 columns; here lane (r, g) owns row r of tile g, so it writes all four parts
+#pragma unroll 1
+        for (int gg = 0; gg < 4; ++gg) {
+          if (a.o_f32) {
+            f32x4* p = reinterpret_cast<f32x4*>((float*)a.o + (int64_t)b * a.stride_ob + (int64_t)wrow * a.ldo + h * 128 + 32 * gg);
+#pragma unroll
+            for (int c = 0; c < 8; ++c) p[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+          } else {
+            u32x4* p = reinterpret_cast<u32x4*>((bf16_t*)a.o + (int64_t)b * a.stride_ob + (int64_t)wrow * a.ldo + h * 128 + 32 * gg);
+#pragma unroll
+            for (int c = 0; c < 4; ++c) p[c] = u32x4{0u, 0u, 0u, 0u};
+          }
+        }
+      }
+      return;
+    }
+  }
+  auto tile_on = [&](int it) { return !ROWS || ((wmask >> (16 * it)) & 0xffffull) != 0ull; };
 
   // ---- stage K (row-major) and Vᵀ (key-contiguous) of this (batch, head); rows >= n_ip are zero
   {
@@ -104,7 +154,7 @@ __global__ __launch_bounds__(256) void ip_attention_kernel(const IpArgs a) {
   // batch entry) instead of held in 32 more registers
   const float* grow = GATED ? a.gate + (int64_t)b * a.stride_gb + h * 128 + 8 * g : nullptr;
   u32x4 qnext[4];
-  load_q(0, qnext);
+  if (tile_on(0)) load_q(0, qnext);
   __syncthreads();                                // K / Vᵀ staged (the q loads above are already in flight)
 
 #pragma unroll 1
@@ -113,10 +163,15 @@ __global__ __launch_bounds__(256) void ip_attention_kernel(const IpArgs a) {
     if (row0 >= a.N) break;                       // wave-uniform; no barrier below
     const int row = row0 + r;
     const bool valid = row < a.N;
+    if (!tile_on(it)) {                           // wave-uniform: no q, no RMSNorm, no MFMA; write mode leaves the zeros
+      if (it + 1 < TILES && tile_on(it + 1)) load_q(it + 1, qnext);       // the next tile still finds its rows in flight
+      if (!a.accumulate && valid) zero_row(row);
+      continue;
+    }
     u32x4 qraw[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) qraw[s] = qnext[s];
-    if (it + 1 < TILES) load_q(it + 1, qnext);
+    if (it + 1 < TILES && tile_on(it + 1)) load_q(it + 1, qnext);   // a tile worth nothing is not read
 
     // RMSNorm over the 128 columns of the row: 32 in this lane, the rest in lanes l ^ 16, l ^ 32, l ^ 48
     float qf[4][8], ss = 0.f;
@@ -172,7 +227,9 @@ __global__ __launch_bounds__(256) void ip_attention_kernel(const IpArgs a) {
       }
     sum += __shfl_xor(sum, 16);
     sum += __shfl_xor(sum, 32);
-    const float inv = a.ip_scale / sum;
+    // ROWS: the row's weight joins ip_scale in fp32, before the gate and any rounding (w = 1 keeps the bits of the unweighted launch)
+    const float wr = ROWS ? __shfl(wlane, 16 * it + r) : 1.0f;
+    const float inv = (ROWS ? a.ip_scale * wr : a.ip_scale) / sum;
 
     // Oᵀ tiles: ot[c][e] = o[row r][d = 32(c >> 1) + 8g + 4(c & 1) + e]
     f32x4 ot[8];
@@ -189,6 +246,10 @@ __global__ __launch_bounds__(256) void ip_attention_kernel(const IpArgs a) {
       }
     }
     if (!valid) continue;
+    if (ROWS && wr == 0.f) {                      // select, not multiply: accumulate leaves the row's bytes alone, write stores +0
+      if (!a.accumulate) zero_row(row);
+      continue;
+    }
     if (a.o_f32) {
       float* orow = (float*)a.o + (int64_t)b * a.stride_ob + (int64_t)row * a.ldo + h * 128 + 8 * g;
 #pragma unroll
@@ -232,24 +293,23 @@ __global__ __launch_bounds__(256) void ip_attention_kernel(const IpArgs a) {
   }
 }
 
-template <bool GATED>
+template <bool GATED, bool ROWS>
 void launch_ip(const IpArgs& a, int B, int H, hipStream_t st) {
   const int kb = (a.n_ip + 31) / 32, rows_per_wg = kb == 4 ? 256 : 128;
   const dim3 grid(H, (a.N + rows_per_wg - 1) / rows_per_wg, B), block(256);
   switch (kb) {
-    case 1: hipLaunchKernelGGL((ip_attention_kernel<1, 2, GATED>), grid, block, 0, st, a); break;
-    case 2: hipLaunchKernelGGL((ip_attention_kernel<2, 2, GATED>), grid, block, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((ip_attention_kernel<3, 2, GATED>), grid, block, 0, st, a); break;
-    default: hipLaunchKernelGGL((ip_attention_kernel<4, 4, GATED>), grid, block, 0, st, a); break;
+    case 1: hipLaunchKernelGGL((ip_attention_kernel<1, 2, GATED, ROWS>), grid, block, 0, st, a); break;
+    case 2: hipLaunchKernelGGL((ip_attention_kernel<2, 2, GATED, ROWS>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((ip_attention_kernel<3, 2, GATED, ROWS>), grid, block, 0, st, a); break;
+    default: hipLaunchKernelGGL((ip_attention_kernel<4, 4, GATED, ROWS>), grid, block, 0, st, a); break;
   }
 }
 
-}  // namespace
-
-extern "C" int rt_ip_attention_gated(const void* q, int64_t ldq, int64_t stride_qb, const void* wq, const void* k, const void* v,
-                                     int64_t ldkv, int64_t stride_kvb, const float* gate, int64_t stride_gb, void* o, int64_t ldo,
-                                     int64_t stride_ob, int32_t o_f32, int32_t accumulate, int32_t B, int32_t N, int32_t H, int32_t n_ip,
-                                     float sm_scale, float ip_scale, float eps, void* stream) {
+// the one host body: row_w == nullptr is rt_ip_attention_gated (the instantiations without ROWS)
+int ip_run(const void* q, int64_t ldq, int64_t stride_qb, const void* wq, const void* k, const void* v, int64_t ldkv, int64_t stride_kvb,
+           const float* gate, int64_t stride_gb, const float* row_w, int64_t stride_wb, void* o, int64_t ldo, int64_t stride_ob,
+           int32_t o_f32, int32_t accumulate, int32_t B, int32_t N, int32_t H, int32_t n_ip, float sm_scale, float ip_scale, float eps,
+           void* stream) {
   if (!q || !wq || !k || !v || !o || B < 1 || N < 1 || H < 1 || n_ip < 1) return RT_E_BADARG;
   if (!(sm_scale > 0.0f)) return RT_E_BADARG;     // the row maximum is taken before the scale is applied
   if (n_ip > 128 || (N + 127) / 128 > 65535 || B > 65535) return RT_E_SHAPE;
@@ -267,6 +327,8 @@ extern "C" int rt_ip_attention_gated(const void* q, int64_t ldq, int64_t stride_
   a.o = o;
   a.gate = gate;
   a.stride_gb = gate ? stride_gb : 0;
+  a.row_w = row_w;
+  a.stride_wb = row_w ? stride_wb : 0;
   a.ldq = ldq;
   a.stride_qb = stride_qb;
   a.ldkv = ldkv;
@@ -280,9 +342,34 @@ extern "C" int rt_ip_attention_gated(const void* q, int64_t ldq, int64_t stride_
   a.sm_scale_log2 = sm_scale * 1.4426950408889634f;
   a.ip_scale = ip_scale;
   a.eps = eps;
-  if (gate) launch_ip<true>(a, B, H, (hipStream_t)stream);
-  else launch_ip<false>(a, B, H, (hipStream_t)stream);
+  if (row_w) {
+    if (gate) launch_ip<true, true>(a, B, H, (hipStream_t)stream);
+    else launch_ip<false, true>(a, B, H, (hipStream_t)stream);
+  } else {
+    if (gate) launch_ip<true, false>(a, B, H, (hipStream_t)stream);
+    else launch_ip<false, false>(a, B, H, (hipStream_t)stream);
+  }
   return rt_hip_status();
+}
+
+}  // namespace
+
+extern "C" int rt_ip_attention_gated(const void* q, int64_t ldq, int64_t stride_qb, const void* wq, const void* k, const void* v,
+                                     int64_t ldkv, int64_t stride_kvb, const float* gate, int64_t stride_gb, void* o, int64_t ldo,
+                                     int64_t stride_ob, int32_t o_f32, int32_t accumulate, int32_t B, int32_t N, int32_t H, int32_t n_ip,
+                                     float sm_scale, float ip_scale, float eps, void* stream) {
+  return ip_run(q, ldq, stride_qb, wq, k, v, ldkv, stride_kvb, gate, stride_gb, nullptr, 0, o, ldo, stride_ob, o_f32, accumulate, B, N, H,
+                n_ip, sm_scale, ip_scale, eps, stream);
+}
+
+extern "C" int rt_ip_attention_rows(const void* q, int64_t ldq, int64_t stride_qb, const void* wq, const void* k, const void* v,
+                                    int64_t ldkv, int64_t stride_kvb, const float* gate, int64_t stride_gb, const float* row_w,
+                                    int64_t stride_wb, void* o, int64_t ldo, int64_t stride_ob, int32_t o_f32, int32_t accumulate,
+                                    int32_t B, int32_t N, int32_t H, int32_t n_ip, float sm_scale, float ip_scale, float eps, void* stream) {
+  if (!row_w || stride_wb < 0) return RT_E_BADARG;     // no weights: rt_ip_attention_gated
+  if (!RT_ALIGNED(row_w, 4)) return RT_E_ALIGN;
+  return ip_run(q, ldq, stride_qb, wq, k, v, ldkv, stride_kvb, gate, stride_gb, row_w, stride_wb, o, ldo, stride_ob, o_f32, accumulate, B, N,
+                H, n_ip, sm_scale, ip_scale, eps, stream);
 }
 
 extern "C" int rt_ip_attention(const void* q, int64_t ldq, int64_t stride_qb, const void* wq, const void* k, const void* v,

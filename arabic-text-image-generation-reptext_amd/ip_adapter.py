@@ -280,6 +280,41 @@ class PreparedIP:
     inside: bool = False
     num_double: int = 0
     tok: Optional[torch.Tensor] = None   # InstantX form: the image tokens [B or 1, n, C] K/V were made from
+    # a regional term (``regional_ip_weights``): fp32 weight per query row of a double block [B or 1, N] and of a single block
+    # [B or 1, T + N]; None = every row at full strength, the launch without a table
+    rows_img: Optional[torch.Tensor] = None
+    rows_joint: Optional[torch.Tensor] = None
+
+    def block_terms(self, j: int, single: bool = False) -> list:
+        """This term as block j takes it in a list of terms: [(K, V, scale, row weights)], empty where its scale is zero."""
+        if self.scales[j] == 0.0:
+            return []
+        return [(*self.kv[j], self.scales[j], self.rows_joint if single else self.rows_img)]
+
+
+def regional_ip_weights(mask, scale: float = 1.0, *, N: int, batch: int = 1, cfg: bool = False, line: bool = False):
+    """The one rule for the row weights of a regional image prompt, from host values alone -> (image rows [R, N] fp32, text rows [R]
+    fp32), or (None, None) for the call's own image prompt without a mask (the unweighted launch).
+    ``mask``: the term's region after the pipeline's ÷16 bilinear resize (fractional at the edges), as [N], [1, N, 1] or [batch, N, 1]
+    values. ``scale``: the term's scalar (1.0 for the call's own prompt, ``control_ip_adapter_scale`` for a text line), folded into the
+    weights. Image row n weighs scale · m[n]; the T text rows of an InstantX single block all weigh scale · mean_n m[n] (a full mask: the
+    unmasked call; an empty one: nothing; a small box: its share of the area). R = 1 or ``batch`` as the mask is; under true CFG
+    (``cfg``) the conditioning batch is [negative, positive] and R = 2 · batch: the call's own prompt (``line`` False) carries its mask
+    in both halves, a text line's term weighs 0 everywhere in the negative half, which does not see the lines."""
+    if mask is None:
+        if line:
+            raise ValueError("a text line's image prompt needs the line's regional mask")
+        return None, None
+    m = torch.as_tensor(mask).detach().to("cpu", torch.float32).reshape(-1, N)
+    if m.shape[0] not in (1, batch):
+        raise ValueError(f"regional image prompt: the mask has {m.shape[0]} entries for a batch of {batch}")
+    img = m * float(scale)
+    txt = m.mean(dim=1) * float(scale)
+    if cfg:
+        img, txt = img.expand(batch, N), txt.expand(batch)
+        img = torch.cat([torch.zeros_like(img) if line else img, img])
+        txt = torch.cat([torch.zeros_like(txt) if line else txt, txt])
+    return img.contiguous(), txt.contiguous()
 
 
 class IPAdapter:
@@ -334,6 +369,35 @@ class IPAdapter:
     @property
     def active(self) -> bool:
         return any(s != 0.0 for s in self.scales)
+
+    def prepare_terms(self, embeds: Sequence, weights: Optional[Sequence] = None, T: int = 0) -> List[PreparedIP]:
+        """``prepare`` for several image prompts through this one adapter (regional terms): the embeddings [B_t or 1, E] are concatenated
+        along the batch and projected ONCE (still three or six launches, M = the sum of their batches), and every term gets its rows of
+        that one buffer as views. ``weights``: per term (image rows [R, N], text rows [R]) as ``regional_ip_weights`` returns them, or
+        (None, None); ``T``: the text rows of a single block's query, which the InstantX form prepends to the image rows."""
+        es = [normalize_embeds(e) for e in embeds]
+        if not es:
+            return []
+        weights = [(None, None)] * len(es) if weights is None else list(weights)
+        if len(weights) != len(es):
+            raise ValueError(f"prepare_terms: {len(weights)} weight entries for {len(es)} image prompts")
+        for e in es:
+            if e.shape[1] != self.E:
+                raise ValueError(f"ip_adapter_image_embeds: width {e.shape[1]} != the adapter's image embedding width {self.E}")
+        dev = self.proj_w.device
+        whole = self.prepare(es[0] if len(es) == 1 else torch.cat([e.to(device=dev, dtype=torch.bfloat16) for e in es], dim=0))
+        out, o = [], 0
+        for e, (img, txt) in zip(es, weights):
+            rows = slice(o, o + e.shape[0])
+            o += e.shape[0]
+            ri = rj = None
+            if img is not None:
+                ri = img.to(device=dev, dtype=torch.float32).contiguous()
+                if whole.inside:
+                    rj = torch.cat([txt.to(device=dev, dtype=torch.float32)[:, None].expand(-1, T), ri], dim=1).contiguous()
+            out.append(PreparedIP([(k[rows], v[rows]) for k, v in whole.kv], list(whole.scales), whole.buf, whole.inside, whole.num_double,
+                                  None if whole.tok is None else whole.tok[rows], ri, rj))
+        return out
 
     def prepare(self, embeds) -> PreparedIP:
         """Steps 1-2 for one call: three launches (projection GEMM, LayerNorm, stacked K/V GEMM); six for the InstantX form (two

@@ -410,6 +410,15 @@ def _double_front(pl: DoublePlan, ws: Workspace, temb, cos, sin, mods: Optional[
     return mi, mt, fused
 
 
+def _ip_terms(ip) -> list:
+    """``ip`` of a block as a list of (K, V, scale, row weights): a plain (K, V, scale) tuple is one term without weights."""
+    if ip is None:
+        return []
+    if isinstance(ip[0], torch.Tensor):
+        return [(ip[0], ip[1], ip[2], None)]
+    return [tuple(t) + (None,) * (4 - len(t)) for t in ip]
+
+
 def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: int, inject: Optional[torch.Tensor] = None,
                mods: Optional[tuple] = None, ip: Optional[tuple] = None, ip_inside: bool = False,
                window: Optional[tuple] = None, groups: Optional["ops.KeyGroups"] = None) -> None:
@@ -427,8 +436,12 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
     out / LayerNorm / ff1 / ff2 on the window's rows only, and nothing of the text stream after the QKV projection. The other rows of
     ws.x are left as they were before the block. bf16 projections and attention without ``ip`` / ``inject`` only. ``groups`` (an
     ops.KeyGroups over the S joint rows): the region-masked joint attention of per-line prompts, bf16 attention only; nothing else of the
-    block changes."""
+    block changes. ``ip`` may also be a sequence of (K, V, scale, row_weights) terms, regional image prompts (ip_adapter.py): the
+    first takes the slot the single term takes, each further one accumulates into the same place with one more rounding, in order;
+    ``row_weights`` (fp32 [B or 1, N], or None) is the per-row weight of ops.ip_attention_gated."""
     T, d = ws.T, ws.d
+    terms = _ip_terms(ip)
+    ip = terms or None
     if groups is not None and (pl.fp8_attention or window is not None):
         raise ValueError("run_double: key groups need the bf16 attention kernel and the whole block (no e4m3 attention, no window)")
     if window is not None:
@@ -440,12 +453,14 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
     mi, mt, fused_rope = _double_front(pl, ws, temb, cos, sin, mods, rope=ip is None and not pl.fp8_attention)
     q, k, v = ws.qkv[..., :d], ws.qkv[..., d : 2 * d], ws.qkv[..., 2 * d :]
     if ip is not None and ip_inside:
-        ops.ip_attention_gated(q[:, T:], pl.nq_img, ip[0], ip[1], x_i, H, ip_scale=ip[2], gate=_ch(mi, 2, d), accumulate=True)
+        for K, V, s, w in terms:
+            ops.ip_attention_gated(q[:, T:], pl.nq_img, K, V, x_i, H, ip_scale=s, gate=_ch(mi, 2, d), accumulate=True, row_weights=w)
         ip = None
     if ip is not None:
         # the raw image query is only here: qk_rmsnorm_rope works in place and the attention output overwrites q
         ip_out = ws.ip_buffer()
-        ops.ip_attention(q[:, T:], pl.nq_img, ip[0], ip[1], ip_out, H, ip_scale=ip[2])
+        for j, (K, V, s, w) in enumerate(terms):
+            ops.ip_attention(q[:, T:], pl.nq_img, K, V, ip_out, H, ip_scale=s, accumulate=j > 0, row_weights=w)
         if inject is None:
             inject, ip = ip_out, None                # no ControlNet sample: the term rides the add2 slot of the ff2 epilogue
     attn_mx = pl.fp8_attention and pl.level == "mx"           # the attention kernel is the producer of the out-projections' operand
@@ -502,8 +517,11 @@ def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
     proj_out. The raw q only exists between the fused GEMM and norm + RoPE and attention overwrites it, so the term waits in a bf16
     [B,S,d] buffer and one strided add puts it over q's columns after attention. Wherever the attention output would skip bf16 (the
     "mx" level with e4m3 attention) such a block takes the bf16-output attention call and the quantise pass instead. With ``ip=None``
-    the launch sequence is unchanged. ``groups``: as in run_double."""
+    the launch sequence is unchanged. ``groups``: as in run_double. ``ip`` may also be a sequence of (K, V, scale, row_weights)
+    terms as in run_double, with ``row_weights`` over all S rows: the first writes the buffer, the others accumulate into it."""
     T, d = ws.T, ws.d
+    terms = _ip_terms(ip)
+    ip = terms or None
     if groups is not None and pl.fp8_attention:
         raise ValueError("run_single: key groups need the bf16 attention kernel (the e4m3 attention has no mask)")
     if mods is not None:
@@ -519,7 +537,8 @@ def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
     q = big[..., 2 * d : 3 * d]
     if ip is not None:
         ip_out = ws.ip_buffer_joint()
-        ops.ip_attention_gated(q, pl.nq, ip[0], ip[1], ip_out, H, ip_scale=ip[2])
+        for j, (K, V, s, w) in enumerate(terms):
+            ops.ip_attention_gated(q, pl.nq, K, V, ip_out, H, ip_scale=s, accumulate=j > 0, row_weights=w)
     attn_mx = pl.fp8_attention and pl.level == "mx" and ip is None
     if pl.fp8_attention:
         qk8, vt8 = ws.fp8_attn_buffers(H)

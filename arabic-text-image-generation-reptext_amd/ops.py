@@ -569,20 +569,25 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
 
 
 def ip_attention(q: torch.Tensor, wq: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, ip_scale: float = 1.0,
-                 accumulate: bool = False, scale: Optional[float] = None, eps: float = 1e-6) -> torch.Tensor:
+                 accumulate: bool = False, scale: Optional[float] = None, eps: float = 1e-6,
+                 row_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out (+)= ip_scale · softmax(bf16(rmsnorm(q)·wq) Kᵀ · scale) V (rt_ip_attention): the IP-Adapter term of a double block.
     q [B,N,H·128] bf16 view of the RAW query projection (unit inner stride, e.g. columns :d of the fused q|k|v buffer; not modified);
     wq bf16 [128] (norm_q.weight); k, v [B or 1, n, H·128] bf16 views sharing strides, 1 <= n <= 128 (batch 1: one image prompt for
     every batch entry); out [B,N,H·128] bf16 or f32 view. The launch is ip_attention_gated's without a gate, to which the C entry
     rt_ip_attention itself forwards."""
-    return ip_attention_gated(q, wq, k, v, out, H, ip_scale, None, accumulate, scale, eps)
+    return ip_attention_gated(q, wq, k, v, out, H, ip_scale, None, accumulate, scale, eps, row_weights)
 
 
 def ip_attention_gated(q: torch.Tensor, wq: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, ip_scale: float = 1.0,
-                       gate: Optional[torch.Tensor] = None, accumulate: bool = False, scale: Optional[float] = None, eps: float = 1e-6) -> torch.Tensor:
+                       gate: Optional[torch.Tensor] = None, accumulate: bool = False, scale: Optional[float] = None, eps: float = 1e-6,
+                       row_weights: Optional[torch.Tensor] = None) -> torch.Tensor:
     """out (+)= gate[b] · ip_scale · softmax(bf16(rmsnorm(q)·wq) Kᵀ · scale) V (rt_ip_attention_gated): ip_attention with an optional
     fp32 column gate [B, H·128] (a view with unit inner stride and any batch stride, e.g. the gate_msa chunk of the modulation table).
-    q may be any [B,rows,H·128] view (a single block: columns 2d:3d of the fused [k|v|q|mlp] buffer, all S rows); k as given."""
+    q may be any [B,rows,H·128] view (a single block: columns 2d:3d of the fused [k|v|q|mlp] buffer, all S rows); k as given.
+    row_weights: fp32 [B or 1, rows] with unit inner stride, a weight per query row multiplied into ip_scale (rt_ip_attention_rows: a
+    row of weight 0 is left alone when accumulating and written as +0 otherwise, and tiles of such rows cost nothing); None is the
+    launch without weights."""
     d = H * 128
     (B, N, _, ldq, sqb), (Bk, n, _, ldkv, skvb), _, (_, _, _, ldo, sob) = [_rows3(t, name, width=d) for name, t in (("q", q), ("k", k), ("v", v), ("out", out))]
     if out.shape != q.shape or out.dtype not in (BF16, F32):
@@ -596,6 +601,15 @@ def ip_attention_gated(q: torch.Tensor, wq: torch.Tensor, k: torch.Tensor, v: to
     if gate is not None and (gate.dim() != 2 or gate.shape != (B, d) or gate.stride(1) != 1):
         raise ValueError(f"gate must be a [B,{d}] view with unit inner stride")
     sc = (128 ** -0.5) if scale is None else float(scale)
+    if row_weights is not None:
+        if row_weights.dim() != 2 or row_weights.shape[0] not in (1, B) or row_weights.shape[1] != N or row_weights.stride(1) != 1:
+            raise ValueError(f"row_weights must be a [B or 1,{N}] view with unit inner stride")
+        swb = row_weights.stride(0) if row_weights.shape[0] == B and B > 1 else 0
+        native.call("rt_ip_attention_rows", _dev(q, "q", BF16), ldq, sqb, _dev(wq, "wq", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), ldkv,
+                    skvb if Bk == B and B > 1 else 0, _opt(gate, "gate", F32), 0 if gate is None else gate.stride(0),
+                    _dev(row_weights, "row_weights", F32), swb, _dev(out, "out"), ldo, sob, int(out.dtype == F32), int(accumulate), B, N, H, n, sc,
+                    float(ip_scale), float(eps), _stream())
+        return out
     native.call("rt_ip_attention_gated", _dev(q, "q", BF16), ldq, sqb, _dev(wq, "wq", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), ldkv,
                 skvb if Bk == B and B > 1 else 0, _opt(gate, "gate", F32), 0 if gate is None else gate.stride(0),
                 _dev(out, "out"), ldo, sob, int(out.dtype == F32), int(accumulate), B, N, H, n, sc, float(ip_scale), float(eps), _stream())

@@ -187,6 +187,19 @@ class LineCallExtensions(CallExtensions):
     control_prompt_max_sequence_length: int = 128       # L: a multiple of 64, at most 512
 
 
+REGIONAL_IP_ARGUMENTS = ("ip_adapter_mask", "control_ip_adapter_image", "control_ip_adapter_image_embeds", "control_ip_adapter_scale")
+
+
+@dataclass
+class RegionalIPCallExtensions(LineCallExtensions):
+    """``LineCallExtensions`` of a call that names a regional image prompt (``REGIONAL_IP_ARGUMENTS``), so that a call may name both
+    families. ``accepts_call_extensions`` builds it only for such a call."""
+    ip_adapter_mask: Any = None                         # the region of ip_adapter_image[_embeds]: one mask, in a control_mask entry's forms
+    control_ip_adapter_image: Any = None                # one entry per text line, parallel to control_image: an image or None
+    control_ip_adapter_image_embeds: Any = None         # the same as embeddings: [B,1,E], [B,E] or [1,E], or None, per line
+    control_ip_adapter_scale: Any = 1.0                 # a float, or one per text line
+
+
 def accepts_call_extensions(*names):
     """``__call__`` keeps the reference's parameter list (PIPE:751-781, which ``inspect.signature`` still reports). The fields of
     ``CallExtensions`` in ``names`` are keyword-only extensions of it, taken off here and left on the pipeline, as passed, as
@@ -197,6 +210,8 @@ def accepts_call_extensions(*names):
         def wrapper(self, *args, **kwargs):
             taken = {k: kwargs.pop(k) for k in names if k in kwargs}
             record = LineCallExtensions if any(k in LINE_PROMPT_ARGUMENTS for k in taken) else CallExtensions
+            if any(k in REGIONAL_IP_ARGUMENTS for k in taken):
+                record = RegionalIPCallExtensions
             self._call_extensions = record(**taken)
             try:
                 return call(self, *args, **kwargs)
@@ -303,6 +318,87 @@ def line_prompt_arguments(ext, n_lines: int, control_mask, fp8_attention: bool =
 
 
 @dataclass(frozen=True)
+class RegionalIP:
+    """The image prompts of a call that has a regional one, as ordered terms through the one loaded adapter: the call's
+    own prompt first, if given, then the text lines' in order. Each later term adds with one more rounding: the order is the contract of
+    the bits. Weights as ``ip_adapter.regional_ip_weights`` makes them; (None, None) = the call's own prompt without a mask."""
+    embeds: Tuple[torch.Tensor, ...]                    # per term [Bc or 1, E] bf16
+    img_w: Tuple[Optional[torch.Tensor], ...]           # per term fp32 [Bc or 1, N], or None
+    txt_w: Tuple[Optional[torch.Tensor], ...]           # per term fp32 [Bc or 1] (the text rows of an InstantX single block), or None
+
+    def signature(self, sig) -> tuple:
+        return ("regional_ip", len(self.embeds), tuple(w is not None for w in self.img_w), tuple(sig(e) for e in self.embeds),
+                tuple(None if w is None else sig(w) for w in self.img_w))
+
+    def tensors(self) -> Dict[str, torch.Tensor]:
+        """The static inputs of a captured loop, by name."""
+        out = {f"rip_embeds{i}": e for i, e in enumerate(self.embeds)}
+        out.update({f"rip_img_w{i}": w for i, w in enumerate(self.img_w) if w is not None})
+        out.update({f"rip_txt_w{i}": w for i, w in enumerate(self.txt_w) if w is not None})
+        return out
+
+    def rebound(self, static: Dict[str, torch.Tensor]) -> "RegionalIP":
+        n = range(len(self.embeds))
+        return RegionalIP(tuple(static[f"rip_embeds{i}"] for i in n), tuple(static.get(f"rip_img_w{i}") for i in n),
+                          tuple(static.get(f"rip_txt_w{i}") for i in n))
+
+
+def regional_ip_arguments(ext, n_lines: int, control_mask, adapter, positive_ip: bool, has_encoder: bool):
+    """Check the regional image prompt keywords of a call (``REGIONAL_IP_ARGUMENTS``) -> None when the call names none, else
+    (one entry per text line: an image, an embedding [B or 1, E] or None; one scale per line; the call's ``ip_adapter_mask`` or None)."""
+    mask = getattr(ext, "ip_adapter_mask", None)
+    images, embeds = getattr(ext, "control_ip_adapter_image", None), getattr(ext, "control_ip_adapter_image_embeds", None)
+    if mask is None and images is None and embeds is None:
+        return None
+    if images is not None and embeds is not None:
+        raise ValueError("pass control_ip_adapter_image or control_ip_adapter_image_embeds, not both")
+    if adapter is None:
+        raise ValueError("ip_adapter_mask / control_ip_adapter_image / control_ip_adapter_image_embeds were passed but no IP-Adapter is "
+                         "loaded (load_ip_adapter)")
+    if mask is not None and not positive_ip:
+        raise ValueError("`ip_adapter_mask` was passed without an image prompt (ip_adapter_image / ip_adapter_image_embeds)")
+    entries = images if images is not None else embeds
+    name = "control_ip_adapter_image" if images is not None else "control_ip_adapter_image_embeds"
+    if entries is None:
+        return [None] * n_lines, [1.0] * n_lines, mask
+    if not isinstance(entries, (list, tuple)) or len(entries) != n_lines:
+        raise ValueError(f"{name} must be a list with one entry per text line (control_image has {n_lines}), "
+                         f"{'an image' if images is not None else 'a tensor'} or None each")
+    out = []
+    for e in entries:
+        if e is None:
+            out.append(None)
+        elif images is not None:
+            import PIL.Image
+
+            if not isinstance(e, (PIL.Image.Image, np.ndarray, torch.Tensor)):
+                raise ValueError(f"{name}: an entry is an image (PIL, array or pixel tensor) or None, got {type(e).__name__}")
+            out.append(e)
+        else:
+            if not isinstance(e, torch.Tensor) or e.dim() not in (2, 3) or (e.dim() == 3 and e.shape[1] != 1):
+                raise ValueError(f"{name}: an entry is a [B,1,E], [B,E] or [1,E] tensor or None, got "
+                                 f"{tuple(e.shape) if isinstance(e, torch.Tensor) else type(e).__name__}")
+            e = e[:, 0] if e.dim() == 3 else e
+            if e.shape[1] != adapter.E:
+                raise ValueError(f"{name}: width {e.shape[1]} != the adapter's image embedding width {adapter.E}")
+            out.append(e)
+    scale = getattr(ext, "control_ip_adapter_scale", 1.0)
+    if isinstance(scale, (int, float)):
+        scales = [float(scale)] * n_lines
+    elif isinstance(scale, (list, tuple)) and len(scale) == n_lines and all(isinstance(x, (int, float)) for x in scale):
+        scales = [float(x) for x in scale]
+    else:
+        raise ValueError(f"control_ip_adapter_scale must be a float or one float per text line ({n_lines})")
+    if any(e is not None for e in out):
+        if control_mask is None or len(control_mask) != n_lines:
+            raise ValueError(f"{name} needs control_mask: a line's image prompt is confined to that line's regional mask")
+        if images is not None and not has_encoder:
+            raise NotImplementedError(f"{name} needs an image encoder, which this pipeline does not have: encode the image yourself and "
+                                      "pass control_ip_adapter_image_embeds")
+    return out, scales, mask
+
+
+@dataclass(frozen=True)
 class LoopExtras:
     """What a call adds to the plain loop of ``_denoise_eager``. ``_denoise`` takes the first three and ``repaint`` (static inputs and key
     of the captured graph) and sets ``tower_window`` itself."""
@@ -320,6 +416,7 @@ class LoopExtras:
     # those steps, and the steps outside them run on the positive half alone, at the latents' batch B; None: every step is the CFG step
     guidance: Optional[Guidance] = None
     line_prompts: Optional[LinePrompts] = None   # per-line prompts: a longer text stream and key groups for the transformer alone
+    regional_ip: Optional[RegionalIP] = None     # regional image prompts; it then holds the call's own prompt too, and ip_embeds is None
     quiet: bool = False                          # no progress bar (a capture)
 
 
@@ -987,7 +1084,7 @@ class FluxControlNetPipeline:
         return Image.new("RGB", (size, size), (0, 0, 0))
 
     # ------------------------------------------------------------------ the call
-    @accepts_call_extensions(*LineCallExtensions.__dataclass_fields__)
+    @accepts_call_extensions(*RegionalIPCallExtensions.__dataclass_fields__)
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 28,
@@ -1031,6 +1128,10 @@ class FluxControlNetPipeline:
         cfg = self._check_true_cfg_inputs(ext, prompt_embeds, pooled_prompt_embeds, batch_size, joint_attention_kwargs)
         line_entries = line_prompt_arguments(ext, len(control_image) if control_image is not None else 0, control_mask,
                                              bool(getattr(self.transformer, "_fp8_attention", False)))
+        positive_ip = (ext.ip_adapter_image is not None or ext.ip_adapter_image_embeds is not None
+                       or "ip_adapter_image_embeds" in (joint_attention_kwargs or {}))
+        regional_args = regional_ip_arguments(ext, len(control_image) if control_image is not None else 0, control_mask,
+                                              getattr(self.transformer, "_ip_adapter", None), positive_ip, self.image_encoder is not None)
         ip_embeds, self._joint_attention_kwargs = self._resolve_ip_embeds(ext.ip_adapter_image, ext.ip_adapter_image_embeds, joint_attention_kwargs,
                                                                           batch_size, num_images_per_prompt, device)
         if cfg and ip_embeds is not None:
@@ -1064,14 +1165,53 @@ class FluxControlNetPipeline:
         line_prompts = self._line_prompts(line_entries, ext, region, prompt_embeds, latents.shape[1], total, num_images_per_prompt, cfg, device)
         active = union_active_steps(len(timesteps), float(ext.control_guidance_start_union), float(ext.control_guidance_end_union)) if with_union else ()
         union = UnionTower(self.controlnet_union, union_hint, float(ext.controlnet_conditioning_scale_union), active) if active else None
-        extras = LoopExtras(ip_embeds=ip_embeds, union=union, cfg_scale=float(ext.true_cfg_scale) if cfg else None, repaint=repaint,
-                            guidance=loop_guidance(self.guider, cfg, len(timesteps)), line_prompts=line_prompts)
+        regional = self._regional_ip(regional_args, ip_embeds, region, latents.shape[1], total, num_images_per_prompt, cfg, device,
+                                     prompt_embeds.dtype)
+        extras = LoopExtras(ip_embeds=ip_embeds if regional is None else None, union=union, cfg_scale=float(ext.true_cfg_scale) if cfg else None,
+                            repaint=repaint, guidance=loop_guidance(self.guider, cfg, len(timesteps)), line_prompts=line_prompts,
+                            regional_ip=regional)
 
         self._apply_lora_scale()
         latents = self._denoise(latents, prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids, timesteps, hints, masks,
                                 guidance_scale, controlnet_conditioning_scale, controlnet_conditioning_step, control_mode,
                                 callback_on_step_end, callback_on_step_end_tensor_inputs, num_inference_steps, extras)
         return self._finish(latents, height, width, output_type, return_dict)
+
+    def _regional_ip(self, args, ip_embeds, region, N, total, num_images_per_prompt, cfg, device, dtype) -> Optional[RegionalIP]:
+        """The call's image prompts as ordered, weighted terms (None: no table and no line term, the loop takes ``ip_embeds`` as it always
+        did). ``args``: what ``regional_ip_arguments`` returned; ``ip_embeds``: the call's own prompt as the loop would take it (under true
+        CFG [negative, positive]); ``region``: the text lines' resized masks. The weights are ``ip_adapter.regional_ip_weights``'s."""
+        from . import ip_adapter as _ipa
+
+        if args is None or not self.transformer._ip_adapter.active:
+            return None
+        entries, scales, mask = args
+        embeds, img_w, txt_w = [], [], []
+        if ip_embeds is not None:
+            m = None if mask is None else self._region_masks([mask], device, dtype)[0]
+            if m is not None and m.shape[1] != N:
+                raise ValueError(f"ip_adapter_mask: {m.shape[1]} tokens after the resize, the image has {N}")
+            w = _ipa.regional_ip_weights(m, 1.0, N=N, batch=total, cfg=cfg)
+            embeds.append(ip_embeds), img_w.append(w[0]), txt_w.append(w[1])
+        lines = [i for i, e in enumerate(entries) if e is not None]
+        images = [entries[i] for i in lines if not (isinstance(entries[i], torch.Tensor) and entries[i].dim() == 2)]
+        if images:      # every line's image in one encoder batch
+            if all(isinstance(im, torch.Tensor) for im in images):
+                images = torch.cat([im if im.dim() == 4 else im[None] for im in images])
+            encoded = iter(self.encode_image(images, device).split(1))
+        for i in lines:
+            e = entries[i] if isinstance(entries[i], torch.Tensor) and entries[i].dim() == 2 else next(encoded)
+            if e.shape[0] == total // num_images_per_prompt and num_images_per_prompt != 1:
+                e = e.repeat_interleave(num_images_per_prompt, dim=0)
+            if e.shape[0] not in (1, total):
+                raise ValueError(f"a text line's image prompt has batch {e.shape[0]}, neither 1 nor the number of images {total}")
+            e = e.to(device=device, dtype=torch.bfloat16)
+            w = _ipa.regional_ip_weights(region[i], scales[i], N=N, batch=total, cfg=cfg, line=True)
+            embeds.append((torch.cat([e, e]) if cfg and e.shape[0] != 1 else e).contiguous()), img_w.append(w[0]), txt_w.append(w[1])
+        if not lines and (not embeds or img_w[0] is None):
+            return None
+        dev = lambda t: None if t is None else t.to(device)
+        return RegionalIP(tuple(embeds), tuple(dev(w) for w in img_w), tuple(dev(w) for w in txt_w))
 
     def _line_prompts(self, entries, ext, region, prompt_embeds, N, total, num_images_per_prompt, cfg, device) -> Optional[LinePrompts]:
         """The call's per-line prompts as the loop takes them (None: the call has none). T5 only: the pooled CLIP vector stays the base
@@ -1197,7 +1337,7 @@ class FluxControlNetPipeline:
         extras = replace(extras or LoopExtras(), tower_window=win)
         # under true CFG (cfg_scale) prompt_embeds / pooled / hints hold [negative, positive]
         ipe, union, cfg_scale, repaint, guidance = extras.ip_embeds, extras.union, extras.cfg_scale, extras.repaint, extras.guidance
-        lp = extras.line_prompts
+        lp, rip = extras.line_prompts, extras.regional_ip
 
         def eager(callback=None):
             return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
@@ -1245,6 +1385,12 @@ class FluxControlNetPipeline:
             # the line embeddings and the row table are two more static inputs; the group ends are kernel arguments baked into the capture
             key += (("line_prompts", lp.ends, sig(lp.row_vis), sig(lp.embeds)),)
             ins.update(line_embeds=lp.embeds, line_row_vis=lp.row_vis)
+        if rip is not None:
+            # the terms' embeddings and weight tables are static inputs: which tiles a launch skips is decided by the kernel from its
+            # table, so new mask values or images replay the same graph; the per-block scales are kernel scalars as above
+            adapter = self.transformer._ip_adapter
+            key += (rip.signature(sig), adapter.version, tuple(adapter.scales))
+            ins.update(rip.tensors())
         solver_order = getattr(self.scheduler, "solver_order", 1)
         if solver_order > 1:
             # the multistep weights are kernel scalars of every step, fixed by the sigmas and the timesteps that are in the key already;
@@ -1265,7 +1411,7 @@ class FluxControlNetPipeline:
         if ent == "seen":                                    # second call: capture
             static = {name: [t.clone() for t in v] if isinstance(v, list) else v.clone() for name, v in ins.items()}
             keep = [m._ensure_plans() for m in (self.transformer, self.controlnet) if m is not None] + [getattr(self.controlnet, "_cx_pad", None)]
-            keep.append(getattr(self.transformer, "_ip_adapter", None) if ipe is not None else None)     # its weights are read by the graph
+            keep.append(getattr(self.transformer, "_ip_adapter", None) if ipe is not None or rip is not None else None)     # its weights are read by the graph
             if union is not None:
                 keep += [union.model._ensure_plans(), getattr(union.model, "_cx_pad", None)]
             graph = torch.cuda.CUDAGraph()
@@ -1282,7 +1428,8 @@ class FluxControlNetPipeline:
                     captured = replace(extras, quiet=True, ip_embeds=static.get("ip_embeds"),
                                        union=union and replace(union, hint=static["union_hint"]),
                                        repaint=repaint and Repaint(static["repaint_src"], static["repaint_noise"], static["repaint_mask"]),
-                                       line_prompts=lp and replace(lp, embeds=static["line_embeds"], row_vis=static["line_row_vis"]))
+                                       line_prompts=lp and replace(lp, embeds=static["line_embeds"], row_vis=static["line_row_vis"]),
+                                       regional_ip=rip and rip.rebound(static))
                     out = self._denoise_eager(static["latents"], static["prompt_embeds"], static["pooled"], static["text_ids"], static["image_ids"],
                                               tvals, static["hints"], static["masks"], guidance_scale, cn_scale, cn_steps, control_mode, None,
                                               callback_inputs, num_inference_steps, timesteps, extras=captured)
@@ -1388,6 +1535,9 @@ class FluxControlNetPipeline:
         static_t = prepare_static(prompt_embeds)
         # the image prompt's tokens and every block's K/V of them: loop-invariant too (ip_adapter.py steps 1-2)
         ip_prep = self.transformer._ip_adapter.prepare(extras.ip_embeds) if extras.ip_embeds is not None else None
+        rip = extras.regional_ip
+        if rip is not None:        # regional terms: one projection for all of them, a list of views (the text rows are the transformer's)
+            ip_prep = self.transformer._ip_adapter.prepare_terms(rip.embeds, list(zip(rip.img_w, rip.txt_w)), T=prompt_t.shape[1])
         # Which tower samples does the transformer read? Block i takes sample i // ceil(n_blocks / n_samples) (A.3): with 6
         # samples against 19 double blocks the sixth is never consumed (Q5), so its block and zero-linear are not evaluated.
         # A tower of another depth adds into the first tower's buffers (it must not be deeper: there is one buffer per block
@@ -1445,7 +1595,8 @@ class FluxControlNetPipeline:
             pos = lambda t: t if t is None or t.shape[0] != Bc else t[Bc - B:]
             tws = [replace(tw, hint=pos(tw.hint), rowscale=tw.rowscale if tw.rowscale is None or tw.rowscale.dim() == 1 else pos(tw.rowscale),
                            static=replace(tw.static, ctx=pos(tw.static.ctx), hint=pos(tw.static.hint))) for tw in towers]
-            ip = ip_prep and replace(ip_prep, kv=[(pos(k), pos(v)) for k, v in ip_prep.kv], tok=pos(ip_prep.tok))
+            ip_pos = lambda p: replace(p, kv=[(pos(k), pos(v)) for k, v in p.kv], tok=pos(p.tok), rows_img=pos(p.rows_img), rows_joint=pos(p.rows_joint))
+            ip = ip_prep and ([ip_pos(p) for p in ip_prep] if isinstance(ip_prep, list) else ip_pos(ip_prep))
             lead = lambda bufs: None if bufs is None else [b[:B] for b in bufs]
             return (pos(pe), pos(pooled), replace(st, ctx=pos(st.ctx), hint=pos(st.hint)), tws, lead(sample_buf), lead(single_buf), ip,
                     pos(joint_text(pe)), lp and lp.groups(slice(Bc - B, Bc)))

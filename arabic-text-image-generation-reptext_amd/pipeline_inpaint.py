@@ -21,7 +21,7 @@ import torch.nn.functional as F
 from . import ops
 from .image_processor import PipelineImageInput, VaeImageProcessor
 from .pipeline import FluxControlNetPipeline as _BasePipeline
-from .pipeline import LINE_PROMPT_ARGUMENTS, LoopExtras, accepts_call_extensions
+from .pipeline import LINE_PROMPT_ARGUMENTS, REGIONAL_IP_ARGUMENTS, LoopExtras, accepts_call_extensions
 
 DEFAULT_NEGATIVE_PROMPT = "bad quality, worst quality, text, signature, watermark, extra words"     # INP:416
 
@@ -84,7 +84,7 @@ class FluxControlNetPipeline(_BasePipeline):
         return packed, height, width
 
     # ------------------------------------------------------------------ INP:846-1313
-    @accepts_call_extensions("ip_adapter_image", "ip_adapter_image_embeds", *LINE_PROMPT_ARGUMENTS)      # taken only to be refused by name below
+    @accepts_call_extensions("ip_adapter_image", "ip_adapter_image_embeds", *LINE_PROMPT_ARGUMENTS, *REGIONAL_IP_ARGUMENTS)      # taken only to be refused by name below
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  true_guidance_scale: float = 3.5, negative_prompt: Optional[Union[str, List[str]]] = None,
@@ -117,6 +117,9 @@ class FluxControlNetPipeline(_BasePipeline):
         if ext.ip_adapter_image is not None or ext.ip_adapter_image_embeds is not None or "ip_adapter_image_embeds" in (joint_attention_kwargs or {}):
             # the conditioning batch is 2B under true CFG: the unconditional half would need a negative image prompt
             raise ValueError("the inpaint pipeline does not support IP-Adapter image prompts (ip_adapter_image / ip_adapter_image_embeds)")
+        if any(getattr(ext, k, None) is not None for k in REGIONAL_IP_ARGUMENTS[:3]):
+            raise ValueError("the inpaint pipeline does not support IP-Adapter image prompts (ip_adapter_mask / control_ip_adapter_image / "
+                             "control_ip_adapter_image_embeds)")
         if getattr(ext, "control_prompt", None) is not None or getattr(ext, "control_prompt_embeds", None) is not None:
             # the flow's own CFG doubles the batch inside the loop: the row table of the unconditional half is not built for it
             raise ValueError("the inpaint pipeline does not support per-line prompts (control_prompt / control_prompt_embeds)")

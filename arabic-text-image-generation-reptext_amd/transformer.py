@@ -364,7 +364,8 @@ class FluxTransformer2DModel(_MMDiTBase):
                 _groups: Optional["ops.KeyGroups"] = None):
         """``joint_attention_kwargs["ip_adapter_image_embeds"]`` (as in diffusers): the image prompt of a loaded IP-Adapter, projected
         and applied in every double block — in every block, single ones included, for an InstantX adapter (ip_adapter.py); ``_ip`` (optional) = the same already prepared (``_ip_adapter.prepare``), so
-        that a loop does not redo the projection per step.
+        that a loop does not redo the projection per step, or a list of them (``_ip_adapter.prepare_terms``): regional image prompts, of which
+        block j gets, in order, those whose scale on block j is not zero (they share the adapter's per-block scales).
         ``_sample_events[k]`` (optional): event another stream records when controlnet_block_samples[k] is complete; the
         current stream waits for it right before the first block that consumes that sample. ``_static`` (optional): this
         model's loop-invariant embeddings (prepare_static) — the text rows are copied instead of recomputed. ``_groups`` (optional): an
@@ -398,6 +399,9 @@ class FluxTransformer2DModel(_MMDiTBase):
             if getattr(self, "_ip_adapter", None) is None:
                 raise ValueError("ip_adapter_image_embeds were passed but no IP-Adapter is loaded (load_ip_adapter)")
             _ip = self._ip_adapter.prepare(ip_embeds) if self._ip_adapter.active else None
+        ip_list = _ip if isinstance(_ip, (list, tuple)) else None          # regional terms; a single PreparedIP takes the lines it always took
+        if ip_list is not None:
+            _ip = ip_list[0] if ip_list else None
         waited = set()
         gkw = {} if _groups is None else dict(groups=_groups)               # a call without key groups calls the blocks as it always did
         for i, pl in enumerate(doubles):
@@ -410,6 +414,8 @@ class FluxTransformer2DModel(_MMDiTBase):
                     torch.cuda.current_stream().wait_event(_sample_events[k])
                     waited.add(k)
             ip = None if _ip is None or _ip.scales[i] == 0.0 else (*_ip.kv[i], _ip.scales[i])
+            if ip_list is not None:
+                ip = [t for p in ip_list for t in p.block_terms(i)] or None
             mmdit.run_double(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.double[i], ip=ip,
                              ip_inside=_ip is not None and _ip.inside, **gkw)
         for i, pl in enumerate(singles):
@@ -419,6 +425,8 @@ class FluxTransformer2DModel(_MMDiTBase):
             ip = None
             if _ip is not None and _ip.inside and _ip.scales[nl + i] != 0.0:
                 ip = (*_ip.kv[nl + i], _ip.scales[nl + i])
+            if ip_list is not None and _ip is not None and _ip.inside:
+                ip = [t for p in ip_list for t in p.block_terms(nl + i, single=True)] or None
             mmdit.run_single(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.single[i], ip=ip, **gkw)
         # AdaLayerNormContinuous: chunk order (scale, shift)  — A.3
         if _mods is not None:

@@ -361,6 +361,21 @@ int rt_ip_attention_gated(const void* q, int64_t ldq, int64_t stride_qb, const v
                           const float* gate, int64_t stride_gb,
                           void* o, int64_t ldo, int64_t stride_ob, int32_t o_f32, int32_t accumulate,
                           int32_t B, int32_t N, int32_t H, int32_t n_ip, float sm_scale, float ip_scale, float eps, void* stream);
+/* rt_ip_attention_gated with an fp32 weight per query row (a regional image prompt):
+ *   o[b][r] (+)= gate[b] * ( (ip_scale * row_w[b][r]) * softmax(...) * V )
+ * row_w: fp32 [B|1][N], batch stride stride_wb (elements; 0 = one table for the batch). Any finite value: fractional, above 1 or
+ * negative. The weight is multiplied into ip_scale in fp32 before the gate and before any rounding, so a table of 1.0f gives the bits
+ * of rt_ip_attention_gated. A row of weight 0 is selected out, not multiplied: with accumulate its output elements are neither read
+ * nor written, without it they are written as +0, and nothing of its q row (NaN or Inf included) reaches any output. A 16-row tile
+ * whose rows are all 0 loads no q and runs no RMSNorm and no MFMA; a workgroup (128 rows, 256 for n_ip > 96) whose rows are all 0
+ * does not stage K / V either: the launch costs what its non-zero rows cost. gate stays optional (NULL).
+ * Rejected on the host as rt_ip_attention_gated, and: row_w NULL (use rt_ip_attention_gated) or stride_wb < 0 (RT_E_BADARG); row_w
+ * not 4-byte aligned (RT_E_ALIGN). */
+int rt_ip_attention_rows(const void* q, int64_t ldq, int64_t stride_qb, const void* wq,
+                         const void* k, const void* v, int64_t ldkv, int64_t stride_kvb,
+                         const float* gate, int64_t stride_gb, const float* row_w, int64_t stride_wb,
+                         void* o, int64_t ldo, int64_t stride_ob, int32_t o_f32, int32_t accumulate,
+                         int32_t B, int32_t N, int32_t H, int32_t n_ip, float sm_scale, float ip_scale, float eps, void* stream);
 /* y[i] = bf16( 0.5 x[i] (1 + erf(x[i] / sqrt 2)) ): the exact GELU of the InstantX image projection (rt_gemm_group's epilogue has the
  * tanh form only). x fp32, y bf16, n elements; once per call, outside the loop. Null pointers or n < 1: RT_E_BADARG. */
 int rt_gelu_erf_bf16(const float* x, void* y, int64_t n, void* stream);

@@ -10,6 +10,8 @@ encoders, which sit outside the hot path. With real checkpoints on disk use `Flu
     python tools/infer_demo.py --ip-image photo.jpg   # adds an image prompt: CLIP ViT-L/14 vision encoder + a 4-token IP-Adapter, random weights
     python tools/infer_demo.py --ip-image photo.jpg --ip-layout instantx   # the InstantX layout instead: SigLIP-so400m encoder (1152-wide
                                               # pooler_output) + a 128-token adapter with a term in all 19 + 38 blocks, random weights
+    python tools/infer_demo.py --ip-image style.jpg --ip-mask region.png --line-ip-image brass.jpg --line-ip-image ""   # regional image prompts:
+                                              # the style reference confined to a region, a material photo for the first text line only
     python tools/infer_demo.py --union-image photo.jpg [--union-scale 0.7 --union-end 0.8]   # a second ControlNet (Union-Pro-2.0 shape,
                                               # random weights) steered by the device Canny of the photo, beside the RepText tower
     python tools/infer_demo.py --negative-prompt "blurry letters, extra text" --true-cfg-scale 3.5   # true CFG in the text-to-image flow:
@@ -51,6 +53,11 @@ ap.add_argument("--out", default="gpurun_out/result.jpg")
 ap.add_argument("--inpaint", action="store_true")
 ap.add_argument("--ip-image", default=None, help="image prompt for the text-to-image flow (ip_adapter_image=)")
 ap.add_argument("--ip-layout", choices=("xlabs", "instantx"), default="xlabs", help="adapter + encoder pair behind --ip-image")
+ap.add_argument("--ip-mask", default=None, metavar="FILE", help="region of --ip-image: a grey image, white = full strength (ip_adapter_mask=)")
+ap.add_argument("--line-ip-image", action="append", default=None, metavar="FILE",
+                help="an image prompt of its own for a text line, confined to the line's box (control_ip_adapter_image=): repeatable, one per "
+                     "text line in order; an empty string leaves a line without one")
+ap.add_argument("--line-ip-scale", type=float, default=1.0, help="strength of the --line-ip-image prompts (control_ip_adapter_scale=)")
 ap.add_argument("--union-image", default=None, help="photo whose Canny edges steer the second ControlNet (control_image_union=)")
 ap.add_argument("--union-scale", type=float, default=0.7)
 ap.add_argument("--union-end", type=float, default=0.8)
@@ -137,7 +144,9 @@ if a.inpaint:
     sys.exit(0)
 
 ip_kwargs = {}
-if a.ip_image:
+if a.ip_mask and not a.ip_image:
+    sys.exit("--ip-mask is the region of --ip-image: give both")
+if a.ip_image or a.line_ip_image:
     from PIL import Image
     from reptext_amd.image_encoder import CLIPVisionModelWithProjection, SiglipVisionModel
     from tools.bench_ip_adapter import adapter_sd, adapter_sd_instantx
@@ -149,7 +158,14 @@ if a.ip_image:
         pipe.image_encoder = CLIPVisionModelWithProjection(device=dev, dtype=bf16).random_init_(seed=4)  # ViT-L/14 shape, 768-wide embeds
         pipe.load_ip_adapter(adapter_sd(pipe.transformer, 4, dev, seed=5))
     pipe.set_ip_adapter_scale(0.7)
-    ip_kwargs = dict(ip_adapter_image=Image.open(a.ip_image))
+    if a.ip_image:
+        ip_kwargs = dict(ip_adapter_image=Image.open(a.ip_image))
+    if a.ip_mask:
+        ip_kwargs.update(ip_adapter_mask=Image.open(a.ip_mask).convert("L").resize((a.size, a.size)))
+    if a.line_ip_image:
+        if len(a.line_ip_image) != len(text_list):
+            sys.exit(f"--line-ip-image: give one per text line ({len(text_list)}), got {len(a.line_ip_image)}")
+        ip_kwargs.update(control_ip_adapter_image=[Image.open(f) if f else None for f in a.line_ip_image], control_ip_adapter_scale=a.line_ip_scale)
 
 if a.union_image:
     import numpy as np
