@@ -69,11 +69,11 @@ def make_qkv(Bn, S, Hn, seed, late_key_rows=()):
     return qkv
 
 
-def reference(qkv, Hn):
+def reference(qkv, Hn, scale=None):
     Bn, S, _ = qkv.shape
     d = Hn * DH
     q, k, v = (qkv[..., i * d : (i + 1) * d].float().reshape(Bn, S, Hn, DH) for i in range(3))
-    ref, pv = attention_ref(q, k, v)
+    ref, pv = attention_ref(q, k, v, scale)
     return ref, pv, float(v.abs().max())
 
 
@@ -100,18 +100,20 @@ def guards_intact(obuf, S, d):
     return same_bits(obuf[m], torch.full_like(obuf[m], SENT))
 
 
-def check_attention(what, got, ref, pv, vmax):
-    """The per-element bound; prints the part of the error the slack has to carry before it asserts."""
+def check_attention(what, got, ref, pv, vmax, slack_of=attn_slack):
+    """The per-element bound; prints the part of the error the slack has to carry before it asserts. slack_of: the attn_slack of the
+    file that asks (test_attention_v3_edges_gpu.py keeps a MEASURED_EXCESS of its own)."""
     got, ref, pv = got.double().cpu(), ref.double(), pv.double()
     base = 2.0 ** -8 * ref.abs() + 2.0 ** -8 * pv
-    slack = attn_slack(vmax)
+    slack = slack_of(vmax)
     excess = float(((got - ref).abs() - base).max())
     print(f"[attention] {what}: excess over 2^-8|ref| + 2^-8 sum p|v| {max(excess, 0.0):.3e} (slack {slack:.3e})")
     return check_bound(what, got, ref, base + slack)
 
 
-def run_guarded(ops, qkv, Hn, device, what, ref=None, ldo=None, split=True, check_entries=True):
-    """Out of place on guarded buffers, twice; bound, guards, inputs untouched; in place over q; every entry alone. Returns the output."""
+def run_guarded(ops, qkv, Hn, device, what, ref=None, ldo=None, split=True, check_entries=True, scale=None, slack_of=attn_slack):
+    """Out of place on guarded buffers, twice; bound, guards, inputs untouched; in place over q; every entry alone. Returns the output.
+    scale: the softmax scale of every launch and of the reference (None: the kernels' default, 128^-0.5)."""
     Bn, S, _ = qkv.shape
     d = Hn * DH
     buf, q, k, v = fused_buffer(qkv, device)
@@ -119,18 +121,18 @@ def run_guarded(ops, qkv, Hn, device, what, ref=None, ldo=None, split=True, chec
 
     def run():
         obuf, o = new_o(Bn, S, d, device, ldo)
-        ops.attention(q, k, v, o, Hn, split=split)
+        ops.attention(q, k, v, o, Hn, scale=scale, split=split)
         torch.cuda.synchronize()
         return obuf
 
     obuf = twice(run)
     got = obuf[:, :S, :d]
-    r, pv, vmax = reference(qkv, Hn) if ref is None else ref
-    check_attention(what, got, r, pv, vmax)
+    r, pv, vmax = reference(qkv, Hn, scale) if ref is None else ref
+    check_attention(what, got, r, pv, vmax, slack_of)
     assert guards_intact(obuf, S, d), f"{what}: wrote outside [:S, :H*128] of the output"
     assert same_bits(buf, before), f"{what}: the kernel wrote to its inputs"
     # in place over q: the same bits, and nothing else of the fused buffer changes
-    ops.attention(q, k, v, q, Hn, split=split)
+    ops.attention(q, k, v, q, Hn, scale=scale, split=split)
     torch.cuda.synchronize()
     assert same_bits(q, got), f"{what}: in place over q differs"
     expect = before.clone()
@@ -140,7 +142,7 @@ def run_guarded(ops, qkv, Hn, device, what, ref=None, ldo=None, split=True, chec
         for b in range(Bn):                                        # entry b of the batched launch = the batch-1 launch of that entry
             _, q1, k1, v1 = fused_buffer(qkv[b : b + 1], device)
             o1buf, o1 = new_o(1, S, d, device, ldo)
-            ops.attention(q1, k1, v1, o1, Hn, split=split)
+            ops.attention(q1, k1, v1, o1, Hn, scale=scale, split=split)
             torch.cuda.synchronize()
             assert same_bits(o1buf[0], obuf[b]), f"{what}: entry {b} differs from its batch-1 launch"
     return got

@@ -264,7 +264,8 @@ def test_attention_v3_variant(ops, gpu, B, S, H):
     """csrc/attention_v3.hip (one wave per SIMD, 64 query rows per wave, O and Q in asm-owned accumulator registers, speculative
     numerators with a deferred decision) on the shapes it takes (S % 256 == 0): against the fp32 oracle, against attention.hip on
     the same buffers, with a key that spikes LATE for one query row in each 32-row block position (the rescale path must fire
-    in both query blocks of a wave, in either key half), bitwise repeatable, in place over q."""
+    in both query blocks of a wave; the three keys sit at positions 58, 44 and 33 of their tiles, so all in the SECOND 32-key half:
+    every position of a tile, both halves, is tests/test_attention_v3_edges_gpu.py's), bitwise repeatable, in place over q."""
     from reptext_amd import native
 
     lib = native.load()
@@ -273,7 +274,7 @@ def test_attention_v3_variant(ops, gpu, B, S, H):
     qkv = bf16r(torch.randn(B, S, 3 * d, generator=g))
     qkv[..., :d] *= 2.0
     q, k, v = (qkv[..., i * d : (i + 1) * d].reshape(B, S, H, 128) for i in range(3))
-    # spikes: query rows 5 (block a of wave 0) and 40 (block b), 200 (wave 3): keys late in the sequence, first / second half of a tile
+    # spikes: query rows 5 (block a of wave 0) and 40 (block b), 200 (wave 3): keys late in the sequence, all in the second half of their tile
     for qrow, krow in ((5, S - 70), (40, S - 20), (200, S // 2 + 33)):
         k[0, krow, 0] = q[0, qrow, 0] * 3.0
     qkv = torch.cat([q.reshape(B, S, d), k.reshape(B, S, d), v.reshape(B, S, d)], dim=-1)
