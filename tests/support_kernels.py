@@ -3,6 +3,8 @@ share: the fp64 references of the GEMM epilogue, of the convolution and of atten
 not write), the bf16 error bound, ulp distances and the run-twice check. Further down, for test_token_passes_gpu.py and
 test_e4m3_producers_gpu.py: batched guarded views, the fp64 references and fp32-evaluation bounds of LayerNorm + modulation and of q/k
 RMSNorm + RoPE, the e4m3 grid (ulp_e4m3, finite bytes), the row-quantisation rule and the documented key order of the e4m3 V^T.
+Next to attention_ref, for test_ip_attention_edges_gpu.py: the fp64 reference of the IP-Adapter term (ip_attention_ref64) with the
+bf16 rounding of the normalised query done in fp64 (bf16_round64).
 A plain helper module, not a test file."""
 import torch
 
@@ -240,6 +242,41 @@ def attention_ref(q, k, v, scale=None):
             p = torch.softmax(q[b, :, h] @ k[b, :, h].t() * sc, dim=-1)
             ref[b, :, h], pv[b, :, h] = p @ v[b, :, h], p @ v[b, :, h].abs()
     return ref.reshape(B, S, H * Dh), pv.reshape(B, S, H * Dh)
+
+
+def bf16_round64(x):
+    """The bf16 value nearest to each element of the fp64 tensor x (ties to even; the normal range is assumed), as fp64, and the
+    distance of x to the nearest point halfway between two bf16 values, relative to |x| (inf where x is 0)."""
+    m, e = torch.frexp(x.double())                 # x = m 2^e, |m| in [0.5, 1): m 2^8 has its 8 significant bits in front of the point
+    y = m * 256.0
+    margin = ((y - torch.floor(y)) - 0.5).abs() / y.abs()
+    margin = torch.where(y == 0, torch.full_like(y, float("inf")), margin)
+    return torch.ldexp(torch.round(y), e - 8), margin
+
+
+def ip_qhat64(q, wq, eps):
+    """fp64 q rsqrt(mean_128(q^2) + eps) wq of q [B, N, H, 128], before any rounding."""
+    qd = q.double()
+    return qd * torch.rsqrt((qd * qd).mean(-1, keepdim=True) + eps) * wq.double()
+
+
+def ip_attention_ref64(q, wq, k, v, c, sm_scale, eps):
+    """fp64 rt_ip_attention / _gated / _rows of CPU tensors holding exactly the values the kernel reads: q [B, N, H, 128] raw, wq [128],
+    k / v [B or 1, n, H, 128], c [B, N, H * 128] (or what broadcasts to it) = ip_scale * row weight * gate, absent factors 1.
+        qh = bf16(q rsqrt(mean(q^2) + eps) wq)        rounded HERE as the kernel rounds its first product's operand
+        p  = softmax(qh k^T sm_scale),   term = c p v
+    Returns (term, pv, E_s): pv = |c| sum_j p_j |v_j| [B, N, H * 128], what the bf16 rounding of P is relative to, and E_s [B, N, H] =
+    136 x 2^-24 sm_scale max_j sum_d |qh_d k_jd|: the fp32 error of a 128-term score summed in any order (128), the subtraction of the
+    maximum and the product with the scale (8 more)."""
+    B, N, H, Dh = q.shape
+    qh, _ = bf16_round64(ip_qhat64(q, wq, eps))
+    kd, vd = k.double().expand(B, -1, -1, -1), v.double().expand(B, -1, -1, -1)
+    p = torch.softmax(torch.einsum("bqhd,bkhd->bhqk", qh, kd) * sm_scale, dim=-1)
+    o = torch.einsum("bhqk,bkhd->bqhd", p, vd).reshape(B, N, H * Dh)
+    oa = torch.einsum("bhqk,bkhd->bqhd", p, vd.abs()).reshape(B, N, H * Dh)
+    c = c.double()
+    e_s = 136 * U24 * sm_scale * torch.einsum("bqhd,bkhd->bhqk", qh.abs(), kd.abs()).amax(-1).permute(0, 2, 1)
+    return c * o, c.abs() * oa, e_s.contiguous()
 
 
 # ------------------------------------------------------------------------------------------------ token passes and e4m3 producers
