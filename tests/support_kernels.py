@@ -1,6 +1,6 @@
-"""What the tests of tests/test_support_kernels_gpu.py, test_gemm_epilogue_gpu.py, test_attention_edges_gpu.py and test_vae_kernels_gpu.py
-share: the fp64 references of the GEMM epilogue, of the convolution and of attention, the per-element bound check, guarded buffers (NaN where a kernel must not read, a sentinel where it must
-not write), the bf16 error bound, ulp distances and the run-twice check. Further down, for test_token_passes_gpu.py and
+"""What the tests of tests/test_support_kernels_gpu.py, test_gemm_epilogue_gpu.py, test_attention_edges_gpu.py,
+test_small_head_attention_edges_gpu.py and test_vae_kernels_gpu.py share: the fp64 references of the GEMM epilogue, of the convolution
+and of attention, the per-element bound check, guarded buffers (NaN where a kernel must not read, a sentinel where it must not write), the bf16 error bound, ulp distances and the run-twice check. Further down, for test_token_passes_gpu.py and
 test_e4m3_producers_gpu.py: batched guarded views, the fp64 references and fp32-evaluation bounds of LayerNorm + modulation and of q/k
 RMSNorm + RoPE, the e4m3 grid (ulp_e4m3, finite bytes), the row-quantisation rule and the documented key order of the e4m3 V^T.
 Next to attention_ref, for test_ip_attention_edges_gpu.py: the fp64 reference of the IP-Adapter term (ip_attention_ref64) with the
@@ -230,18 +230,21 @@ def conv_ref(x, w, bias, res, stride, up):
 
 
 def attention_ref(q, k, v, scale=None):
-    """fp64 softmax(q k^T scale) v of CPU tensors [B, S, H, Dh] holding exactly the values the kernel reads. Returns (ref, pv) as
-    [B, S, H * Dh]: the value and sum_j p_j |v_j| with p the fp64 softmax row — what the bf16 rounding of P (the second product's
-    operand) and of the normaliser is relative to."""
+    """fp64 softmax(q k^T scale) v of CPU tensors holding exactly the values the kernel reads: q [B or 1, Sq, H, Dh] (a leading 1 is
+    one set of queries shared by the batch), k and v [B, Sk, H, Dh]. Returns (ref, pv) as [B, Sq, H * Dh]: the value and
+    sum_j p_j |v_j| with p the fp64 softmax row — what the bf16 rounding of P (the second product's operand) and of the normaliser
+    is relative to."""
     q, k, v = q.double(), k.double(), v.double()
-    B, S, H, Dh = q.shape
+    Bq, Sq, H, Dh = q.shape
+    B, Sk = k.shape[:2]
+    assert Bq in (1, B) and k.shape == v.shape == (B, Sk, H, Dh), (q.shape, k.shape, v.shape)
     sc = Dh ** -0.5 if scale is None else float(scale)
-    ref, pv = torch.empty(B, S, H, Dh, dtype=F64), torch.empty(B, S, H, Dh, dtype=F64)
+    ref, pv = torch.empty(B, Sq, H, Dh, dtype=F64), torch.empty(B, Sq, H, Dh, dtype=F64)
     for b in range(B):
-        for h in range(H):                     # one [S, S] matrix at a time
-            p = torch.softmax(q[b, :, h] @ k[b, :, h].t() * sc, dim=-1)
+        for h in range(H):                     # one [Sq, Sk] matrix at a time
+            p = torch.softmax(q[b if Bq == B else 0, :, h] @ k[b, :, h].t() * sc, dim=-1)
             ref[b, :, h], pv[b, :, h] = p @ v[b, :, h], p @ v[b, :, h].abs()
-    return ref.reshape(B, S, H * Dh), pv.reshape(B, S, H * Dh)
+    return ref.reshape(B, Sq, H * Dh), pv.reshape(B, Sq, H * Dh)
 
 
 def bf16_round64(x):
