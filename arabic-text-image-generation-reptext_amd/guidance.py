@@ -68,6 +68,9 @@ class Guidance:
     guider: TrueCFGGuider
     steps: Tuple[int, ...]
 
+    def signature(self) -> tuple:            # of a captured loop: host scalars only; its buffers are allocated inside the capture
+        return (("guidance", self.steps) + tuple(float(getattr(self.guider, n)) for n in ("eta", "norm_threshold", "momentum")),)
+
 
 @dataclass
 class ProjectedStep:

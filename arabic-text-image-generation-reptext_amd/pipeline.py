@@ -18,7 +18,7 @@ import functools
 import inspect
 import json
 import os
-from dataclasses import dataclass, replace
+from dataclasses import dataclass, fields, make_dataclass, replace
 from typing import Any, Callable, Dict, List, Optional, Tuple, Union
 
 import numpy as np
@@ -151,6 +151,10 @@ class _Tower:
     static: Any = None
 
 
+# ``pipe._sample_cache``: the tower sample buffers of one shape and the row window outside which ``double`` reads zero (None: no promise)
+_SampleCache = make_dataclass("_SampleCache", ["key", "double", "single", ("window", Any, None)])
+
+
 TRUE_CFG_ARGUMENTS = ("negative_prompt", "negative_prompt_2", "true_cfg_scale", "negative_prompt_embeds", "negative_pooled_prompt_embeds",
                       "negative_ip_adapter_image", "negative_ip_adapter_image_embeds")
 
@@ -221,34 +225,54 @@ def accepts_call_extensions(*names):
     return decorate
 
 
+class _StaticFields:          # a ``LoopExtras`` record whose ``STATIC`` names the static inputs of a captured loop that its tensor fields are
+    def tensors(self) -> Dict[str, torch.Tensor]:
+        return {name: getattr(self, field) for name, field in self.STATIC.items()}
+
+    def rebound(self, static: Dict[str, torch.Tensor]):
+        return replace(self, **{field: static[name] for name, field in self.STATIC.items()})
+
+
 @dataclass(frozen=True)
-class UnionTower:
+class UnionTower(_StaticFields):
     """The base flow's second ControlNet in one call: unmasked, evaluated at ``active_steps`` (``union_active_steps``) only."""
     model: FluxControlNetModel
     hint: torch.Tensor
     scale: float
     active_steps: Tuple[int, ...]
+    STATIC = {"union_hint": "hint"}
+
+    def signature(self, sig, ident) -> tuple:
+        return ("union", ident(self.model), sig(self.hint), self.scale, self.active_steps)
 
 
 @dataclass(frozen=True)
-class Repaint:
+class Repaint(_StaticFields):
     """Latent-blend repaint: after every step the state becomes ``src32`` re-noised with ``noise32`` to the next sigma where ``mask`` is
     0 and stays the step's result where it is 1 (``scheduler.step_master_(repaint=)``). fp32; under true CFG at the latents' batch B."""
     src32: torch.Tensor       # [B, N, 64] packed source latents
     noise32: torch.Tensor     # [B, N, 64] the noise the start state was mixed with
     mask: torch.Tensor        # [1 or B, N, 64]; fractional values blend
+    STATIC = {"repaint_src": "src32", "repaint_noise": "noise32", "repaint_mask": "mask"}
+
+    def signature(self, sig) -> tuple:
+        return (("repaint", sig(self.src32), sig(self.noise32), sig(self.mask)),)
 
 
 @dataclass(frozen=True)
-class LinePrompts:
+class LinePrompts(_StaticFields):
     """Per-line prompts of a call: the transformer's text stream is ``cat([prompt_embeds, embeds], dim=1)`` and its joint
     attention runs with the key groups ``ends`` and the row table ``row_vis`` (``line_prompt_groups``). The towers see the base prompt."""
     embeds: torch.Tensor      # [Bc, R·L, joint_attention_dim]: the R line prompts' T5 embeddings, one after another
     ends: Tuple[int, ...]     # key-group ends over the T0 + R·L + N joint rows
     row_vis: torch.Tensor     # int32 [Bc, T0 + R·L + N]: bit g set = the row sees group g
+    STATIC = {"line_embeds": "embeds", "line_row_vis": "row_vis"}
 
     def groups(self, rows: Optional[slice] = None) -> "ops.KeyGroups":
         return ops.KeyGroups(self.ends, self.row_vis if rows is None else self.row_vis[rows])
+
+    def signature(self, sig) -> tuple:
+        return (("line_prompts", self.ends, sig(self.row_vis), sig(self.embeds)),)
 
 
 def line_prompt_groups(T0: int, L: int, masks, N: int, has_prompt=None, batch: int = 1, cfg: bool = False):
@@ -400,8 +424,8 @@ def regional_ip_arguments(ext, n_lines: int, control_mask, adapter, positive_ip:
 
 @dataclass(frozen=True)
 class LoopExtras:
-    """What a call adds to the plain loop of ``_denoise_eager``. ``_denoise`` takes the first three and ``repaint`` (static inputs and key
-    of the captured graph) and sets ``tower_window`` itself."""
+    """What a call adds to the plain loop of ``_denoise_eager``. ``_denoise`` sets ``tower_window`` itself; what the fields add to a captured
+    graph (key, static inputs, the capture's own extras) their records say: ``signature``, ``tensors()``, ``rebound(static)``, walked below."""
     ip_embeds: Optional[torch.Tensor] = None     # the image prompt, [total or 1, E] ([2·total, E] under true CFG); None: nothing to add
     union: Optional[UnionTower] = None           # it keeps the side stream and the text towers' row window
     # true CFG of the base flow: the conditioning batch is [negative, positive] (2B against the latents' B) and the step mixes its halves in
@@ -418,6 +442,30 @@ class LoopExtras:
     line_prompts: Optional[LinePrompts] = None   # per-line prompts: a longer text stream and key groups for the transformer alone
     regional_ip: Optional[RegionalIP] = None     # regional image prompts; it then holds the call's own prompt too, and ip_embeds is None
     quiet: bool = False                          # no progress bar (a capture)
+
+    def signature(self, sig, ident, adapter) -> tuple:
+        """The extensions' part of a captured graph's key, one row per field in field order; an absent field adds nothing."""
+        ip = adapter is not None and (adapter.version, tuple(adapter.scales))      # of either kind of image prompt: kernel scalars
+        return ((() if self.ip_embeds is None else (sig(self.ip_embeds),) + ip)
+                + (() if self.union is None else self.union.signature(sig, ident))
+                + (() if self.cfg_scale is None else (("cfg", self.cfg_scale),))
+                + (() if self.repaint is None else self.repaint.signature(sig))
+                + (() if self.guidance is None else self.guidance.signature())
+                + (() if self.line_prompts is None else self.line_prompts.signature(sig))
+                + (() if self.regional_ip is None else (self.regional_ip.signature(sig),) + ip))
+
+    def tensors(self) -> Dict[str, torch.Tensor]:          # the static inputs the fields add, in the order they are cloned and refreshed
+        records = [getattr(self, f.name) for f in fields(self)]      # one with static inputs of its own is known by its ``tensors`` method
+        own = {} if self.ip_embeds is None else {"ip_embeds": self.ip_embeds}
+        return dict(own, **{name: t for r in records if hasattr(r, "tensors") for name, t in r.tensors().items()})
+
+    def rebound(self, static: Dict[str, torch.Tensor]) -> "LoopExtras":          # what a capture runs with: the graph's own clones, no progress bar
+        own = {f.name: getattr(self, f.name).rebound(static) for f in fields(self) if hasattr(getattr(self, f.name), "tensors")}
+        return replace(self, quiet=True, ip_embeds=static.get("ip_embeds"), **own)
+
+    def kept(self, transformer) -> list:     # what a captured graph reads besides its static inputs and the pipeline's own models
+        union = [] if self.union is None else [self.union.model._ensure_plans(), getattr(self.union.model, "_cx_pad", None)]
+        return [getattr(transformer, "_ip_adapter", None) if self.ip_embeds is not None or self.regional_ip is not None else None] + union
 
 
 def do_true_cfg(true_cfg_scale, negative_prompt=None, negative_prompt_embeds=None, negative_pooled_prompt_embeds=None) -> bool:
@@ -1330,143 +1378,94 @@ class FluxControlNetPipeline:
     def _denoise(self, latents, prompt_embeds, pooled, text_ids, image_ids, timesteps, hints, masks, guidance_scale,
                  cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, extras: Optional[LoopExtras] = None):
         """Eager loop, or the replay of its captured hipGraph when this exact call signature has been seen before (GRAPH_CAPTURE).
-        ``extras``: the image prompt, the union tower, the CFG scale and the repaint record of the call (None: a plain loop)."""
+        ``extras``: what the call adds to the plain loop (None: nothing); under true CFG prompt_embeds / pooled / hints hold [negative, positive]."""
         tvals = timesteps.to(torch.float32).cpu().tolist()                 # host copies: no per-step device sync
         # the rows the regional masks leave non-zero: read here, never inside the loop or a capture; part of the call signature below
         win = active_row_window(masks, latents.shape[1]) if masks and len(masks) == len(hints) else None
         extras = replace(extras or LoopExtras(), tower_window=win)
-        # under true CFG (cfg_scale) prompt_embeds / pooled / hints hold [negative, positive]
-        ipe, union, cfg_scale, repaint, guidance = extras.ip_embeds, extras.union, extras.cfg_scale, extras.repaint, extras.guidance
-        lp, rip = extras.line_prompts, extras.regional_ip
+        base = dict(latents=latents, prompt_embeds=prompt_embeds, pooled=pooled, text_ids=text_ids, image_ids=image_ids, hints=hints, masks=masks)
 
-        def eager(callback=None):
-            return self._denoise_eager(latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale, cn_scale,
-                                       cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps, extras=extras)
+        def loop(named, extras, callback=None):              # the eager loop on ``base``, or on a graph's clones under the same names
+            lat, pe, pool, tids, iids, hs, ms = (named[name] for name in base)
+            return self._denoise_eager(lat, pe, pool, tids, iids, tvals, hs, ms, guidance_scale, cn_scale, cn_steps, control_mode,
+                                       callback, callback_inputs, num_inference_steps, timesteps, extras=extras)
 
-        use_graph = (GRAPH_CAPTURE and getattr(self, "capture_graphs", True) and callback is None and latents.is_cuda
-                     and not self.interrupt and isinstance(self.controlnet, (FluxControlNetModel, type(None)))
-                     and (control_mode is None) and self._graph_safe_kwargs())
-        if not use_graph:
-            return eager(callback)
-        from . import mmdit as _mm
-        _mm.reference_bf16_scalars(self.reference_bf16_scalars)      # the module switch follows THIS pipeline before the key is built
-        sig = lambda t: (tuple(t.shape), str(t.dtype), tuple(t.stride()))
-        ident = lambda m: (id(m), id(m._ensure_plans()), id(getattr(m, "_cx_pad", None)), bool(getattr(m, "_fp8_linears", False)),
-                           bool(getattr(m, "_fp8_attention", False)))
-        models = tuple(ident(m) for m in (self.transformer, self.controlnet) if m is not None)
-        key = (sig(latents), sig(prompt_embeds), sig(pooled), sig(text_ids), sig(image_ids), tuple(sig(h) for h in hints), tuple(sig(m) for m in masks),
-               tuple(tvals), tuple(self.scheduler.sigmas.tolist()), float(guidance_scale), repr(cn_scale), int(cn_steps), int(num_inference_steps),
-               str(latents.device), models, bool(self.reference_bf16_scalars), bool(_mm.RESIDUAL_F32), bool(OVERLAP_TOWER), bool(_mm.FUSED_QK_ROPE),
-               win, bool(TOWER_WINDOW))
-        # the graph's static inputs by name, in the order they are cloned and refreshed; hints and masks are lists of tensors
-        ins = dict(latents=latents, prompt_embeds=prompt_embeds, pooled=pooled, text_ids=text_ids, image_ids=image_ids, hints=list(hints), masks=list(masks))
-        if ipe is not None:
-            # the embeds are one more static input of the graph; the per-block scales are kernel scalars baked into the capture
-            adapter = self.transformer._ip_adapter
-            key += (sig(ipe), adapter.version, tuple(adapter.scales))
-            ins["ip_embeds"] = ipe
-        if union is not None:
-            # the union hint is one more static input; the tower's scale and its active steps are baked into the capture
-            key += ("union", ident(union.model), sig(union.hint), union.scale, union.active_steps)
-            ins["union_hint"] = union.hint
-        if cfg_scale is not None:
-            # the scale is a kernel scalar of every step (rt_cfg_euler_step_f32); the static inputs' shapes already carry the batch 2B
-            key += (("cfg", cfg_scale),)
-        if repaint is not None:
-            # source, noise and mask are three more static inputs; the sigmas the blend re-noises to are in the key already
-            key += (("repaint", sig(repaint.src32), sig(repaint.noise32), sig(repaint.mask)),)
-            ins.update(repaint_src=repaint.src32, repaint_noise=repaint.noise32, repaint_mask=repaint.mask)
-        if guidance is not None:
-            # which steps are guided and the guider's three numbers are host scalars baked into the capture; the guidance difference
-            # and the partial sums are allocated inside the capture, in the graph's pool, like the fp32 state
-            g = guidance.guider
-            key += (("guidance", guidance.steps, float(g.eta), float(g.norm_threshold), float(g.momentum)),)
-        if lp is not None:
-            # the line embeddings and the row table are two more static inputs; the group ends are kernel arguments baked into the capture
-            key += (("line_prompts", lp.ends, sig(lp.row_vis), sig(lp.embeds)),)
-            ins.update(line_embeds=lp.embeds, line_row_vis=lp.row_vis)
-        if rip is not None:
-            # the terms' embeddings and weight tables are static inputs: which tiles a launch skips is decided by the kernel from its
-            # table, so new mask values or images replay the same graph; the per-block scales are kernel scalars as above
-            adapter = self.transformer._ip_adapter
-            key += (rip.signature(sig), adapter.version, tuple(adapter.scales))
-            ins.update(rip.tensors())
-        solver_order = getattr(self.scheduler, "solver_order", 1)
-        if solver_order > 1:
-            # the multistep weights are kernel scalars of every step, fixed by the sigmas and the timesteps that are in the key already;
-            # the velocity history is allocated inside the capture, in the graph's pool, like the fp32 state
-            key += (("solver", solver_order),)
-        # host state of a multistep scheduler (whether its history holds a velocity): a capture must not move it, a replay leaves it full
-        history_len = self.scheduler._history_len if solver_order > 1 else None
+        if not (GRAPH_CAPTURE and getattr(self, "capture_graphs", True) and callback is None and latents.is_cuda
+                and not self.interrupt and isinstance(self.controlnet, (FluxControlNetModel, type(None)))
+                and (control_mode is None) and self._graph_safe_kwargs()):         # no graph for this call
+            return loop(base, extras, callback)
+        key, ins = self._graph_signature(base, extras, tvals, guidance_scale, cn_scale, cn_steps, num_inference_steps)
         cache = self.__dict__.setdefault("_graph_cache", {})
         ent = cache.get(key)
         if ent is None:                                      # first sight of this signature: eager (and warm), remember it
             if len(cache) >= GRAPH_CACHE_MAX:
                 cache.pop(next(iter(cache)))
             cache[key] = "seen"
-            return eager()
-        if ent == "failed":
-            return eager()
-        tensors = lambda named: [t for v in named.values() for t in (v if isinstance(v, list) else [v])]
-        if ent == "seen":                                    # second call: capture
-            static = {name: [t.clone() for t in v] if isinstance(v, list) else v.clone() for name, v in ins.items()}
-            keep = [m._ensure_plans() for m in (self.transformer, self.controlnet) if m is not None] + [getattr(self.controlnet, "_cx_pad", None)]
-            keep.append(getattr(self.transformer, "_ip_adapter", None) if ipe is not None or rip is not None else None)     # its weights are read by the graph
-            if union is not None:
-                keep += [union.model._ensure_plans(), getattr(union.model, "_cx_pad", None)]
-            graph = torch.cuda.CUDAGraph()
-            step_index = self.scheduler._step_index
-            # The graph bakes in the device pointers of every buffer the loop touches. Buffers that live in caches which may evict or
-            # replace them later (activation workspaces, attention key-split workspaces, tower sample buffers, rope tables) are
-            # recorded while the capture runs and OWNED by the graph's entry: a replay can never write into memory that was handed
-            # back to the allocator (tests: test_graphs_of_two_shapes_keep_their_buffers).
-            attn_keys = set(ops._ATTN_WS)
-            _mm.CAPTURE_KEEP, ops.CAPTURE_KEEP = keep, keep
-            try:
-                # thread-local capture mode: calls made by OTHER threads (RCCL's watchdog polling its events) do not invalidate the capture
-                with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-                    captured = replace(extras, quiet=True, ip_embeds=static.get("ip_embeds"),
-                                       union=union and replace(union, hint=static["union_hint"]),
-                                       repaint=repaint and Repaint(static["repaint_src"], static["repaint_noise"], static["repaint_mask"]),
-                                       line_prompts=lp and replace(lp, embeds=static["line_embeds"], row_vis=static["line_row_vis"]),
-                                       regional_ip=rip and rip.rebound(static))
-                    out = self._denoise_eager(static["latents"], static["prompt_embeds"], static["pooled"], static["text_ids"], static["image_ids"],
-                                              tvals, static["hints"], static["masks"], guidance_scale, cn_scale, cn_steps, control_mode, None,
-                                              callback_inputs, num_inference_steps, timesteps, extras=captured)
-                    out32 = self._master_latents
-            except Exception as e:                           # capture is an optimisation, never a requirement
-                import sys
-                print(f"[reptext_amd] hipGraph capture of the denoise loop failed ({type(e).__name__}: {e}); staying eager", file=sys.stderr, flush=True)
-                cache[key] = "failed"
-                _mm.CAPTURE_KEEP = ops.CAPTURE_KEEP = None
-                ops.drop_attention_workspaces(set(ops._ATTN_WS) - attn_keys)     # their zero fill was recorded, never executed
-                if getattr(self, "_sample_cache", None) is not None:
-                    self._sample_cache[3][0] = None                              # and so was a zero fill of the sample buffers
-                torch.cuda.synchronize()
-                self.scheduler._step_index = step_index
-                if history_len is not None:
-                    self.scheduler._history_len = history_len
-                return eager()
+        elif ent == "seen":                                  # second call: capture
+            ent = cache[key] = self._capture_loop(ins, extras, loop)
+        if not isinstance(ent, dict):                        # "seen" just now, or "failed" (now or earlier)
+            return loop(base, extras)
+        return self._replay_loop(ent, ins, len(tvals), num_inference_steps)
+
+    def _graph_signature(self, base, extras, tvals, guidance_scale, cn_scale, cn_steps, num_inference_steps):     # -> (key, static inputs by name)
+        from . import mmdit as _mm
+        _mm.reference_bf16_scalars(self.reference_bf16_scalars)      # the module switch follows THIS pipeline before the key is built
+        sig = lambda t: (tuple(t.shape), str(t.dtype), tuple(t.stride()))
+        ident = lambda m: (id(m), id(m._ensure_plans()), id(getattr(m, "_cx_pad", None)), bool(getattr(m, "_fp8_linears", False)),
+                           bool(getattr(m, "_fp8_attention", False)))
+        models = tuple(ident(m) for m in (self.transformer, self.controlnet) if m is not None)
+        *single, hints, masks = base.values()
+        key = (*(sig(t) for t in single), tuple(sig(h) for h in hints), tuple(sig(m) for m in masks),
+               tuple(tvals), tuple(self.scheduler.sigmas.tolist()), float(guidance_scale), repr(cn_scale), int(cn_steps), int(num_inference_steps),
+               str(base["latents"].device), models, bool(self.reference_bf16_scalars), bool(_mm.RESIDUAL_F32), bool(OVERLAP_TOWER), bool(_mm.FUSED_QK_ROPE),
+               extras.tower_window, bool(TOWER_WINDOW))
+        key += extras.signature(sig, ident, getattr(self.transformer, "_ip_adapter", None))
+        if getattr(self.scheduler, "solver_order", 1) > 1:       # its weights are kernel scalars fixed by the sigmas and timesteps in the key
+            key += (("solver", self.scheduler.solver_order),)
+        return key, dict(base, hints=list(hints), masks=list(masks), **extras.tensors())
+
+    def _capture_loop(self, ins, extras, loop):          # on clones of ``ins`` -> the graph's cache entry, or "failed": an optimisation, never a requirement
+        from . import mmdit as _mm
+        static = {name: [t.clone() for t in v] if isinstance(v, list) else v.clone() for name, v in ins.items()}
+        keep = [m._ensure_plans() for m in (self.transformer, self.controlnet) if m is not None] + [getattr(self.controlnet, "_cx_pad", None)]
+        keep += extras.kept(self.transformer)
+        graph = torch.cuda.CUDAGraph()
+        host = {n: getattr(self.scheduler, n) for n in ("_step_index", "_history_len") if hasattr(self.scheduler, n)}      # a capture must not move it
+        # The graph bakes in device pointers. Buffers from caches that may evict them later (workspaces, attention scratch, sample
+        # buffers, rope tables) are recorded during the capture and OWNED by its entry (test_graphs_of_two_shapes_keep_their_buffers).
+        attn_keys = set(ops._ATTN_WS)
+        _mm.CAPTURE_KEEP = ops.CAPTURE_KEEP = keep
+        try:
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):     # calls of OTHER threads (RCCL's watchdog) do not invalidate it
+                out = loop(static, extras.rebound(static))
+        except Exception as e:
+            import sys
+            print(f"[reptext_amd] hipGraph capture of the denoise loop failed ({type(e).__name__}: {e}); staying eager", file=sys.stderr, flush=True)
+            ops.drop_attention_workspaces(set(ops._ATTN_WS) - attn_keys)     # their zero fill was recorded, never executed
+            self._zero_samples_for(getattr(self, "_sample_cache", None), None)      # and so was a zero fill of the sample buffers: no promise
+            torch.cuda.synchronize()
+            return "failed"
+        finally:
             _mm.CAPTURE_KEEP = ops.CAPTURE_KEEP = None
-            keep.append(getattr(self, "_sample_cache", None))
-            keep.extend(dict(m._rope_cache) for m in (self.transformer, self.controlnet, union and union.model)
-                        if m is not None and hasattr(m, "_rope_cache"))
-            self.scheduler._step_index = step_index
-            if history_len is not None:
-                self.scheduler._history_len = history_len
-            # the sample buffers the capture wrote into and the window its zero-linears were restricted to (None: every row)
-            ent = cache[key] = {"graph": graph, "static": static, "out": out, "out32": out32, "keep": keep,
-                                "samples": getattr(self, "_sample_cache", None), "window": self._sample_promise}
+            for name, value in host.items():
+                setattr(self.scheduler, name, value)
+        samples = getattr(self, "_sample_cache", None)       # what the capture wrote into; "window": the rows its zero-linears were restricted to
+        keep.append(samples)
+        keep.extend(dict(m._rope_cache) for m in (self.transformer, self.controlnet, extras.union and extras.union.model)
+                    if m is not None and hasattr(m, "_rope_cache"))
+        return {"graph": graph, "static": static, "out": out, "out32": self._master_latents, "keep": keep, "samples": samples, "window": self._sample_promise}
+
+    def _replay_loop(self, ent, ins, n_steps, num_inference_steps):      # refresh the entry's static inputs from ``ins`` and replay its graph
+        tensors = lambda named: [t for v in named.values() for t in (v if isinstance(v, list) else [v])]
         for dst, src in zip(tensors(ent["static"]), tensors(ins)):
             if dst.data_ptr() != src.data_ptr():
                 dst.copy_(src)
         self._zero_samples_for(ent["samples"], ent["window"])       # another call may have left rows outside this window non-zero
         ent["graph"].replay()
-        # what the eager loop's step() calls leave behind: they start at the begin index, if one is set
         first = self.scheduler._step_index if self.scheduler._step_index is not None else (self.scheduler._begin_index or 0)
-        self.scheduler._step_index = first + len(tvals)
-        if history_len is not None and len(tvals) > 0:
-            self.scheduler._history_len = 1                 # the history (the graph's own) holds the last step's velocity
+        self.scheduler._step_index = first + n_steps       # what the eager loop's step() calls leave: they start at the begin index, if one is set
+        if getattr(self.scheduler, "solver_order", 1) > 1 and n_steps > 0:
+            self.scheduler._history_len = 1                                    # the history (the graph's own) holds the last step's velocity
         self._master_latents = ent["out32"].clone()
         with self.progress_bar(total=num_inference_steps) as bar:
             bar.update(num_inference_steps)
@@ -1474,17 +1473,15 @@ class FluxControlNetPipeline:
 
     @staticmethod
     def _zero_samples_for(cache, window) -> None:
-        """The tower sample buffers of ``cache`` (a ``_sample_cache`` tuple) must read zero outside ``window``, whose rows alone the
-        zero-linears will write. They are zeroed once, when the window is set or changes, not per step; the tuple's last element
-        remembers the window they are valid for (None: no promise — the full path overwrites every row, and a call with a union tower,
-        which writes every row at its steps, zeroes inside its own step sequence instead)."""
+        """The tower sample buffers of ``cache`` (a ``_SampleCache``) must read zero outside ``window``, whose rows alone the zero-linears
+        will write. They are zeroed once, when ``cache.window`` changes, not per step (None: no promise — the full path overwrites every
+        row, and a call with a union tower, which writes every row at its steps, zeroes inside its own step sequence instead)."""
         if cache is None:
             return
-        state = cache[3]
-        if window is not None and state[0] != window:
-            for buf in cache[1]:
+        if window is not None and cache.window != window:
+            for buf in cache.double:
                 buf.zero_()
-        state[0] = window
+        cache.window = window
 
     def _denoise_eager(self, latents, prompt_embeds, pooled, text_ids, image_ids, tvals, hints, masks, guidance_scale,
                        cn_scale, cn_steps, control_mode, callback, callback_inputs, num_inference_steps, timesteps,
@@ -1554,10 +1551,10 @@ class FluxControlNetPipeline:
             # sample buffers: allocated once per shape, written by the zero-linear epilogues every step (no per-step allocation)
             Bc, N_, d_ = prompt_embeds.shape[0], latents.shape[1], cnet.inner_dim
             key = (Bc, N_, d_, n_cd, n_cs, str(device))
-            if getattr(self, "_sample_cache", None) is None or self._sample_cache[0] != key:
+            if getattr(self, "_sample_cache", None) is None or self._sample_cache.key != key:
                 mk = lambda n: [torch.empty(Bc, N_, d_, device=device, dtype=torch.bfloat16) for _ in range(n)]
-                self._sample_cache = (key, mk(n_cd), mk(n_cs), [None])
-            sample_buf, single_buf = self._sample_cache[1], self._sample_cache[2]
+                self._sample_cache = _SampleCache(key, mk(n_cd), mk(n_cs))
+            sample_buf, single_buf = self._sample_cache.double, self._sample_cache.single
         # Zero-linears and the last block of the masked towers on the masked rows only (controlnet.forward: _window). The extra towers
         # are unmasked and ADD to every row of the buffers, step after step, so with them every row must be overwritten first: full path.
         use_window = (TOWER_WINDOW and any(tw.masked for tw in towers) and not extra_towers and blocks_needed is not None

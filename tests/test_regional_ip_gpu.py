@@ -326,3 +326,69 @@ def test_capture_and_replay_are_the_eager_bits(gpu, layout):
     for _ in range(2):
         assert torch.equal(run(pipe, plain_kw, graphs=True), want_plain)
     assert_no_call_state(pipe)
+
+
+def test_a_call_with_every_loop_extension_is_captured_and_replayed_bit_for_bit(gpu):
+    """Every field of ``LoopExtras`` that reaches the captured graph in ONE call of the repaint pipeline at B = 1: two masked text lines
+    with a prompt (L = 64) and an image prompt each, the call's own image prompt under ``ip_adapter_mask``, the union tower on the first
+    two of the three steps that run (4 grid steps, strength 0.75), true CFG with negative embeds, a projected guider that ends before the
+    last step, source and mask as packed latents, the second-order scheduler. Eager = seen = captured = replayed; then new VALUES for
+    every static input (same shapes, the text lines keep their image rows) replay the same graph without a call of the eager loop, and the
+    scheduler's host state after a replay is what the eager call leaves."""
+    from reptext_amd.controlnet import FluxControlNetModel
+    from reptext_amd.guidance import TrueCFGGuider
+    from reptext_amd.pipeline_repaint import FluxControlNetRepaintPipeline
+    from reptext_amd.scheduler import FlowMatchMultistepScheduler
+    from reptext_amd.transformer import FluxTransformer2DModel
+
+    tp, cp, ipp = params("instantx")
+    tr = FluxTransformer2DModel(**SMALL_T, device=gpu, dtype=torch.bfloat16)
+    cn = FluxControlNetModel(**SMALL_CN, device=gpu, dtype=torch.bfloat16)
+    tr.load_state_dict(tp)
+    cn.load_state_dict(cp)
+    pipe = FluxControlNetRepaintPipeline(FlowMatchMultistepScheduler(), None, None, None, None, None, tr, cn)      # fresh: its cache holds this key alone
+    pipe.controlnet_union = FluxControlNetModel(**dict(SMALL_T, num_layers=2, num_single_layers=0), device=gpu, dtype=torch.bfloat16).random_init_(915)
+    pipe.set_progress_bar_config(disable=True)
+    pipe.load_ip_adapter(ipp)
+    pipe.set_ip_adapter_scale(SCALES["instantx"])
+    guider = TrueCFGGuider(stop=0.67, eta=0.0, norm_threshold=2.0, momentum=-0.5)          # guided at steps 0 and 1 of the 3
+    g = torch.Generator().manual_seed(916)
+    r = lambda *s: torch.randn(*s, generator=g).to(gpu, torch.bfloat16)
+
+    def drawn(boxes, global_box):
+        """The arguments that become static inputs, drawn anew: every one of them but the latents comes from here."""
+        return dict(control_mask=mask_images(boxes), ip_adapter_mask=mask_images([global_box])[0], control_image_union=r(1, N, 64),
+                    image=r(1, N, 64).float() * 0.5 + 0.123, mask_image=(torch.rand(1, N, 64, generator=g) > 0.4).to(gpu, torch.float32),
+                    controlnet_conditioning_scale_union=0.7, control_guidance_end_union=0.67, num_inference_steps=4, strength=0.75)
+
+    kw = call("gml", cfg=True, prompts=True, **drawn(BOXES, GLOBAL_BOX))
+    eager = run(pipe, kw, guider=guider)
+    host = (pipe.scheduler._step_index, pipe.scheduler._history_len)
+    assert host == (4, 1) and graph_keys(pipe) == []                           # begin index 1 + 3 steps; the history holds a velocity
+    for _ in range(3):                                                          # seen, captured, replayed
+        assert torch.equal(run(pipe, kw, guider=guider, graphs=True), eager)
+        assert (pipe.scheduler._step_index, pipe.scheduler._history_len) == host
+    keys = graph_keys(pipe)
+    assert len(keys) == 1 and isinstance(pipe._graph_cache[keys[0]], dict)
+    tags = [e[0] for e in keys[0] if isinstance(e, tuple) and e and isinstance(e[0], str)]
+    assert tags == ["cfg", "repaint", "guidance", "line_prompts", "regional_ip", "solver"] and "union" in keys[0]
+    static = set(pipe._graph_cache[keys[0]]["static"])
+    assert {"union_hint", "repaint_src", "repaint_noise", "repaint_mask", "line_embeds", "line_row_vis", "rip_embeds2", "rip_img_w0"} <= static
+    assert "ip_embeds" not in static                                            # the call's own image prompt is the regional record's first term
+    # new values for every static input
+    other = dict(kw, **drawn(((48, 112, 60, 220), (96, 160, 20, 150)), (100, 256, 0, 256)), prompt_embeds=r(1, T, 256), pooled_prompt_embeds=r(1, 64),
+                 negative_prompt_embeds=r(1, T, 256), negative_pooled_prompt_embeds=r(1, 64), control_image=[r(1, N, 128), r(1, N, 128)],
+                 latents=r(1, N, 64), ip_adapter_image_embeds=r(1, E), negative_ip_adapter_image_embeds=r(1, E),
+                 control_ip_adapter_image_embeds=[r(1, E), r(1, 1, E)], control_prompt_embeds=[r(1, L, 256), r(1, L, 256)])
+    eager2 = run(pipe, other, guider=guider)
+    calls = []
+    orig = pipe._denoise_eager
+    pipe._denoise_eager = lambda *a, **k: (calls.append(1), orig(*a, **k))[1]
+    try:
+        assert torch.equal(run(pipe, other, guider=guider, graphs=True), eager2) and not torch.equal(eager2, eager)
+    finally:
+        pipe._denoise_eager = orig
+    assert not calls and graph_keys(pipe) == keys
+    assert (pipe.scheduler._step_index, pipe.scheduler._history_len) == host
+    assert torch.equal(run(pipe, kw, guider=guider, graphs=True), eager)        # and the first values again
+    assert_no_call_state(pipe)
