@@ -34,6 +34,12 @@
 // tile-aligned groups, one visibility word per query row, hidden lanes' scores set to -inf under a wave-uniform branch. Everything it adds
 // stands under `if constexpr (GROUPED)`; the dense instantiation is the code it was.
 //
+// rt_attention_fwd_keyed is the third instantiation (KEYED: region isolation for per-line prompts): every KEY carries a class id byte and a
+// row sees key j iff bit class[j] of its word is set. Per tile a lane holds the class of key 64t + lane (loaded one tile ahead); the
+// distinct classes of the tile are walked with readlane / ballot (wave-uniform, one turn per class present) into a 64-bit visibility
+// mask per row. A tile of one class takes the grouped code's hide branch; only a tile of several classes pays a bit test per score.
+// Everything it adds stands under `if constexpr (KEYED)`.
+//
 // LDS image of a K or V tile: 64 rows × 256 B; 16-B chunk c of row r lives at 256·r + 16·(c ^ f(r)),
 // f(r) = ((r&3)<<2) | ((r>>2)&3): conflict-free for the row reads (K) and the transposed reads (V).
 // LDS-DMA writes lane-linear, so the XOR is applied to each lane's source address.
@@ -68,16 +74,28 @@ struct KeyGroups {
   int64_t stride_vis_b;
 };
 struct NoGroups {};
+// rt_attention_fwd_keyed: a class id (0..31) per key, read a byte at a time: no alignment or padding is asked of the table.
+struct KeyClasses {
+  const uint32_t* row_vis;   // [B][S], batch stride stride_vis_b (0: one table)
+  int64_t stride_vis_b;
+  const uint8_t* key_class;  // [B][S], batch stride stride_class_b (0: one table)
+  int64_t stride_class_b;
+};
+enum { DENSE_MODE = 0, GROUPED_MODE = 1, KEYED_MODE = 2 };
+template <int MODE> struct MaskArg { using type = NoGroups; };
+template <> struct MaskArg<GROUPED_MODE> { using type = KeyGroups; };
+template <> struct MaskArg<KEYED_MODE> { using type = KeyClasses; };
 // Running maximum a grouped row starts with: finite, so that a hidden score (-inf) gives exp2(-inf - M0) = 0 and not exp2(NaN), and
 // so far below any score that the first visible one rescales the (all-zero) state by exp2(M0 - m) = 0.
 constexpr float GROUPED_M0 = -1.0e30f;
 
-template <bool GROUPED>
+template <int MODE>
 __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
     const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V, bf16_t* O,
     int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob, float scale_log2, const SplitGeom G,
     const int row_lo, const int row_hi, int* counters, char* records,
-    const std::conditional_t<GROUPED, KeyGroups, NoGroups> KG) {
+    const typename MaskArg<MODE>::type KG) {
+  constexpr bool GROUPED = MODE == GROUPED_MODE, KEYED = MODE == KEYED_MODE, MASKED = MODE != DENSE_MODE;
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE_B];   // [slot][K|V]
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -204,7 +222,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int r = 0; r < 16; ++r) o_acc[i][r] = 0.f;
-    float m_run = GROUPED ? GROUPED_M0 : -INFINITY, l_run = 0.f;     // running max (log2 domain, may lag the true max by <= RESCALE_THR) and row sum
+    float m_run = MASKED ? GROUPED_M0 : -INFINITY, l_run = 0.f;     // running max (log2 domain, may lag the true max by <= RESCALE_THR) and row sum
     // grouped: this lane's row's visibility word (the row clamped as the Q load is), and the group the run's tiles are in: tiles
     // below tile index gend_t belong to group gid (scalars; advanced at the head of a tile)
     [[maybe_unused]] uint32_t vis = 0;
@@ -212,6 +230,16 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
     if constexpr (GROUPED) {
       vis = KG.row_vis[b * KG.stride_vis_b + min(q0 + wave * 32 + l31, S - 1)];
       gend_t = (KG.end[0] + BKV - 1) / BKV;
+    }
+    // keyed: the class of key 64t + lane of the tile to come (clamped to the table: keys >= S are masked as in every mode; only the low
+    // 5 bits of a byte count, whatever the table holds), loaded a tile ahead: behind tile t's DMA barrier, so that the load has the whole
+    // tile to land and the next tile's barrier covers its wait
+    [[maybe_unused]] const uint8_t* kcls = nullptr;
+    [[maybe_unused]] uint32_t cls_next = 0;
+    if constexpr (KEYED) {
+      vis = KG.row_vis[b * KG.stride_vis_b + min(q0 + wave * 32 + l31, S - 1)];
+      kcls = KG.key_class + b * KG.stride_class_b;
+      cls_next = kcls[min(tb * BKV + lane, S - 1)] & 31u;
     }
 
     // ---- softmax pieces (all per lane; the row's other keys live in lane ^ 32)
@@ -309,8 +337,43 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
           for (int r = 0; r < 16; ++r) s[r] = -INFINITY;
         }
       };
-      [[maybe_unused]] const bool any_hidden = GROUPED && __any(hidden);
+      [[maybe_unused]] bool any_hidden = GROUPED && __any(hidden);
+      // keyed: vlo / vhi = this row's visibility of keys 0..31 / 32..63 of the tile, shifted so that bit 8(r>>2) + (r&3) is score r's
+      [[maybe_unused]] uint32_t vlo = 0, vhi = 0;
+      [[maybe_unused]] bool mixed = false;
+      [[maybe_unused]] uint32_t cls = 0;
       rt_dma_barrier();                          // tile t landed (every wave's vmcnt(0), then the barrier); the other slot is free
+      if constexpr (KEYED) {
+        cls = cls_next;
+        cls_next = kcls[min((t + 1) * BKV + lane, S - 1)] & 31u;
+        // every lane's class is below 32 and equals the class it supplies: each turn clears at least the supplying lane, 32 turns at most
+        uint64_t rem = __ballot(true);           // the active lanes: the walk ends when each has met its class
+        int nclass = 0;
+        do {
+          const uint32_t c = __builtin_amdgcn_readlane(cls, __builtin_ctzll(rem));
+          const uint64_t m = __ballot(cls == c);
+          rem &= ~m;
+          if ((vis >> c) & 1u) {
+            vlo |= (uint32_t)m;
+            vhi |= (uint32_t)(m >> 32);
+          }
+          ++nclass;
+        } while (rem);
+        mixed = nclass > 1;
+        hidden = (vlo & vhi) != 0xffffffffu;     // some key of the tile is hidden from this row
+        any_hidden = __any(hidden);
+        vlo >>= 4 * hh;
+        vhi >>= 4 * hh;
+      }
+      auto hide_keys = [&](f32x16& s, uint32_t vm) {   // keyed: one class -> the grouped code's whole-tile hide; several -> a bit per score
+        if (RT_RARE(mixed)) {
+#pragma unroll
+          for (int r = 0; r < 16; ++r)
+            if (!(vm & (1u << (8 * (r >> 2) + (r & 3))))) s[r] = -INFINITY;
+        } else {
+          hide_half(s);
+        }
+      };
       f32x16 s0, s1;
 #pragma unroll
       for (int r = 0; r < 16; ++r) { s0[r] = 0.f; s1[r] = 0.f; }
@@ -341,6 +404,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
       for (int ks = 3; ks < 8; ++ks) kB[ks] = kread(1, ks);
       if (RT_RARE(ragged)) mask_half(s0, 0);
       if constexpr (GROUPED) { if (any_hidden) hide_half(s0); }
+      if constexpr (KEYED) { if (any_hidden) hide_keys(s0, vlo); }
       float mx0 = half_max(s0);
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
@@ -371,6 +435,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
       numer8(s0, 1, p01);
       if (RT_RARE(ragged)) mask_half(s1, 1);
       if constexpr (GROUPED) { if (any_hidden) hide_half(s1); }
+      if constexpr (KEYED) { if (any_hidden) hide_keys(s1, vhi); }
       float mx1 = half_max(s1);
       RT_WEAVE(4, 2, 9)
       RT_PIN(p01); RT_PIN(l_run); RT_PIN(mx1);
@@ -469,7 +534,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
 
     // ---- epilogue: O[q][d] = Oᵀ / l ; lane holds q = l31, d = 32dt + (r&3) + 8(r>>2) + 4hh
     const float l_tot = l_run + __shfl_xor(l_run, 32);
-    const float inv = (GROUPED && !(l_tot > 0.f)) ? 0.f : 1.0f / l_tot;   // grouped: a row that sees no key gets zeros
+    const float inv = (MASKED && !(l_tot > 0.f)) ? 0.f : 1.0f / l_tot;   // grouped: a row that sees no key gets zeros
     const bool wide = (ldo % 8 == 0) && (stride_ob % 8 == 0) && ((reinterpret_cast<uintptr_t>(O) & 15) == 0);
     if (wide) {
       rt_store_o_rows(O + b * stride_ob + (int64_t)min(qrow, S - 1) * ldo + head * DH, qrow < S, hh, o_acc, inv);
@@ -541,8 +606,8 @@ int check_common(const void* q, const void* k, const void* v, void* o, int64_t l
   return RT_OK;
 }
 
-// The launch of attention_fwd_kernel<GROUPED>: one grid, key split and workspace for both instantiations.
-template <bool GROUPED, class KG>
+// The launch of attention_fwd_kernel<MODE>: one grid, key split and workspace for every instantiation.
+template <int MODE, class KG>
 int launch(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob, int32_t B,
            int32_t S, int32_t H, float scale, int32_t row_lo, int32_t row_hi, void* ws, int64_t ws_bytes, void* stream, const KG& kg) {
   const int64_t need = rt_attention_ws_bytes(B, S, H);
@@ -552,7 +617,7 @@ int launch(const void* q, const void* k, const void* v, void* o, int64_t ld, int
   int wmax = 0;
   for (int x = 0; x < 8; ++x) wmax = group_slots(G, x) > wmax ? group_slots(G, x) : wmax;
   const dim3 grid(8 * wmax, B);
-  hipLaunchKernelGGL(attention_fwd_kernel<GROUPED>, grid, dim3(ATT_THREADS), 0, (hipStream_t)stream, (const bf16_t*)q,
+  hipLaunchKernelGGL(attention_fwd_kernel<MODE>, grid, dim3(ATT_THREADS), 0, (hipStream_t)stream, (const bf16_t*)q,
                      (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, ld, stride_b, ldo, stride_ob,
                      scale * 1.4426950408889634f, G, row_lo, row_hi, split ? (int*)ws : nullptr,
                      split ? (char*)ws + split_cnt_bytes(B, S, H) : nullptr, kg);
@@ -572,7 +637,7 @@ extern "C" int rt_attention_fwd_rows(const void* q, const void* k, const void* v
     const int st = rt_attention_v3_try(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, row_lo, row_hi, ws, ws_bytes, stream, &taken);
     if (taken || st != RT_OK) return st;
   }
-  return launch<false>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, row_lo, row_hi, ws, ws_bytes, stream, NoGroups{});
+  return launch<DENSE_MODE>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, row_lo, row_hi, ws, ws_bytes, stream, NoGroups{});
 }
 
 // Region-masked joint attention: always attention_fwd_kernel<true> — the grid, XCD placement, key split and workspace of the dense
@@ -595,5 +660,18 @@ extern "C" int rt_attention_fwd_grouped(const void* q, const void* k, const void
   kg.n = n_groups;
   kg.row_vis = row_vis;
   kg.stride_vis_b = stride_vis_b;
-  return launch<true>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, 0, S, ws, ws_bytes, stream, kg);
+  return launch<GROUPED_MODE>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, 0, S, ws, ws_bytes, stream, kg);
+}
+
+// Joint attention with a class id per key (region isolation of per-line prompts): the grouped launch with visibility decided per key
+// instead of per 64-key tile. Same kernel source, grid, XCD placement, key split and workspace; never attention_v3.
+extern "C" int rt_attention_fwd_keyed(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b, int64_t ldo,
+                                      int64_t stride_ob, int32_t B, int32_t S, int32_t H, float scale, const uint32_t* row_vis,
+                                      int64_t stride_vis_b, const uint8_t* key_class, int64_t stride_class_b, void* ws, int64_t ws_bytes,
+                                      void* stream) {
+  if (const int st = check_common(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, 0, S)) return st;
+  if (!(scale > 0.f) || !row_vis || !key_class || stride_vis_b < 0 || stride_class_b < 0) return RT_E_BADARG;
+  if (!RT_ALIGNED(row_vis, 4)) return RT_E_ALIGN;
+  const KeyClasses kc = {row_vis, stride_vis_b, key_class, stride_class_b};
+  return launch<KEYED_MODE>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, 0, S, ws, ws_bytes, stream, kc);
 }

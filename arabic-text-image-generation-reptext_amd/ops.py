@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Optional, Sequence, Tuple
+from typing import Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -538,13 +538,50 @@ class KeyGroups:
         return _dev(rv, "groups.row_vis"), (0 if rv.shape[0] == 1 else rv.stride(0))
 
 
+@dataclass(frozen=True)
+class KeyClasses:
+    """Key classes of a per-key masked attention call (rt_attention_fwd_keyed). ``key_class``: uint8 [B or 1, S], the class id 0..31 of
+    every key; ``row_vis``: int32 or uint32 [B or 1, S]; query row i of entry b attends key j iff bit key_class[b, j] of row_vis[b, i] is
+    set. Dtypes, ranks and unit inner strides are checked here, once; so are the class ids (< 32) when the record is built from host
+    tensors — ``to(device)`` then gives the record the launch takes. A record built from device tensors (a captured loop's own
+    clones) is not read back. The entry reads the byte table a byte at a time: nothing is padded or re-laid."""
+    row_vis: torch.Tensor
+    key_class: torch.Tensor
+
+    def __post_init__(self):
+        rv, kc = self.row_vis, self.key_class
+        if not isinstance(rv, torch.Tensor) or rv.dtype not in (torch.int32, torch.uint32):
+            raise TypeError("groups.row_vis must be an int32 or uint32 tensor")
+        if not isinstance(kc, torch.Tensor) or kc.dtype != torch.uint8:
+            raise TypeError("groups.key_class must be a uint8 tensor")
+        if rv.dim() != 2 or kc.dim() != 2 or rv.shape[1] != kc.shape[1] or rv.stride(1) != 1 or kc.stride(1) != 1:
+            raise ValueError(f"groups: row_vis and key_class must be [B or 1, S] with unit inner stride, got {tuple(rv.shape)} / {rv.stride()} "
+                             f"and {tuple(kc.shape)} / {kc.stride()}")
+        if kc.device.type == "cpu" and kc.numel() and int(kc.max()) > 31:
+            raise ValueError(f"groups.key_class: class ids must be below 32, got {int(kc.max())}")
+
+    def to(self, device) -> "KeyClasses":
+        return KeyClasses(self.row_vis.to(device), self.key_class.to(device))
+
+    def check(self, B: int, S: int) -> Tuple[int, int, int, int]:
+        """Validate against a [B, S, .] call; returns (row_vis pointer, its batch stride in words, key_class pointer, its batch stride
+        in bytes)."""
+        rv, kc = self.row_vis, self.key_class
+        for name, t in (("row_vis", rv), ("key_class", kc)):
+            if t.shape[1] != S or t.shape[0] not in (1, B):
+                raise ValueError(f"groups.{name}: need [{B} or 1, {S}], got {tuple(t.shape)}")
+        return (_dev(rv, "groups.row_vis"), (0 if rv.shape[0] == 1 else rv.stride(0)),
+                _dev(kc, "groups.key_class"), (0 if kc.shape[0] == 1 else kc.stride(0)))
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, scale: Optional[float] = None,
-              split: bool = True, rows: Optional[tuple] = None, groups: Optional[KeyGroups] = None) -> torch.Tensor:
+              split: bool = True, rows: Optional[tuple] = None, groups: Optional[Union[KeyGroups, KeyClasses]] = None) -> torch.Tensor:
     """q,k,v [B,S,H*128] views (common strides) of one buffer; out [B,S,H*128] view (may alias q). ``split=False`` runs every
     128-row block as one full-length workgroup (no key-split tail; A/B and tests). ``rows`` = (r0, r1): only the items of the launch that
     hold a query row of [r0, r1) do any work (rt_attention_fwd_rows): those rows of out get the bits the whole launch gives them, the
     other rows of the touched items are written too, the rest of out is left as it is. ``groups`` (a KeyGroups; not together with
-    ``rows``): region-masked attention, rt_attention_fwd_grouped — hidden keys must still hold finite values."""
+    ``rows``): region-masked attention, rt_attention_fwd_grouped — hidden keys must still hold finite values; a KeyClasses in its
+    place: visibility per key, rt_attention_fwd_keyed."""
     (B, S, _, ld, sb), _, _, (_, _, _, ldo, sob) = [_rows3(t, name, width=H * 128) for name, t in (("q", q), ("k", k), ("v", v), ("out", out))]
     if not (q.stride() == k.stride() == v.stride()) or k.shape != q.shape or v.shape != q.shape or out.shape != q.shape:
         raise ValueError("q,k,v must share shape and strides")
@@ -554,6 +591,13 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
             raise ValueError("attention: rows= and groups= cannot be combined")
         if not sc > 0:
             raise ValueError("attention: groups= needs scale > 0")
+        if isinstance(groups, KeyClasses):
+            vis, svb, cls, scb = groups.check(B, S)
+            ws = _attention_workspace(B, S, H, q.device) if split else None
+            native.call("rt_attention_fwd_keyed", _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(out, "out", BF16), ld,
+                        sb, ldo, sob, B, S, H, sc, vis, svb, cls, scb, None if ws is None else ws.data_ptr(),
+                        0 if ws is None else ws.numel(), _stream())
+            return out
         vis, svb = groups.check(B, S)
         ends = (C.c_int32 * len(groups.ends))(*[int(e) for e in groups.ends])
         ws = _attention_workspace(B, S, H, q.device) if split else None

@@ -204,6 +204,17 @@ class RegionalIPCallExtensions(LineCallExtensions):
     control_ip_adapter_scale: Any = 1.0                 # a float, or one per text line
 
 
+ISOLATION_ARGUMENTS = ("control_prompt_isolation",)
+MAX_KEY_CLASSES = 32                    # rt_attention_fwd_keyed: a class id selects a bit of a row's 32-bit word
+
+
+@dataclass
+class IsolationCallExtensions(RegionalIPCallExtensions):
+    """``RegionalIPCallExtensions`` of a call that names ``control_prompt_isolation`` (``ISOLATION_ARGUMENTS``).
+    ``accepts_call_extensions`` builds it only for such a call."""
+    control_prompt_isolation: bool = False              # per-line prompts under the per-key rule of ``line_prompt_classes``
+
+
 def accepts_call_extensions(*names):
     """``__call__`` keeps the reference's parameter list (PIPE:751-781, which ``inspect.signature`` still reports). The fields of
     ``CallExtensions`` in ``names`` are keyword-only extensions of it, taken off here and left on the pipeline, as passed, as
@@ -216,6 +227,8 @@ def accepts_call_extensions(*names):
             record = LineCallExtensions if any(k in LINE_PROMPT_ARGUMENTS for k in taken) else CallExtensions
             if any(k in REGIONAL_IP_ARGUMENTS for k in taken):
                 record = RegionalIPCallExtensions
+            if any(k in ISOLATION_ARGUMENTS for k in taken):
+                record = IsolationCallExtensions
             self._call_extensions = record(**taken)
             try:
                 return call(self, *args, **kwargs)
@@ -307,6 +320,86 @@ def line_prompt_groups(T0: int, L: int, masks, N: int, has_prompt=None, batch: i
             raise ValueError(f"line prompts: regional mask {line} has {on.shape[0]} entries for a batch of {batch}")
         vis[-batch:, T:] |= np.where(on, np.uint32(1 << r), np.uint32(0))
     return ends, torch.from_numpy(vis.view(np.int32))
+
+
+@dataclass(frozen=True)
+class IsolatedLinePrompts(LinePrompts):
+    """``LinePrompts`` of a call with ``control_prompt_isolation=True``: the joint attention runs per key (``ops.KeyClasses``) under the
+    tables of ``line_prompt_classes``; ``row_vis`` is that rule's. ``ends`` stays what ``line_prompt_groups`` gives (the text layout)."""
+    key_class: torch.Tensor             # uint8 [Bc, T0 + R·L + N]: the class of every key
+    STATIC = dict(LinePrompts.STATIC, line_key_class="key_class")
+
+    def groups(self, rows: Optional[slice] = None) -> "ops.KeyClasses":
+        return ops.KeyClasses(self.row_vis, self.key_class) if rows is None else ops.KeyClasses(self.row_vis[rows], self.key_class[rows])
+
+    def signature(self, sig) -> tuple:
+        return LinePrompts.signature(self, sig) + (("line_isolation", sig(self.key_class)),)
+
+
+def line_prompt_classes(T0: int, L: int, masks, N: int, has_prompt=None, batch: int = 1, cfg: bool = False):
+    """The visibility contract of per-line prompts with region isolation, from host values alone -> (row_vis int32 [Bc, S], key_class
+    uint8 [Bc, S]), Bc = batch · (2 if cfg else 1), or None when no line has a prompt. Arguments as ``line_prompt_groups``; membership
+    of an image token in line r's box is its rule (the resized mask is > 0).
+    Key classes: 0 = the base prompt's T0 tokens; r = 1..R the L tokens of the r-th line that has a prompt; then one class per distinct
+    MEMBERSHIP SET of the image tokens: R + 1 = in no box (the background; it exists whether or not a token is in it), then the sets
+    that occur anywhere in the batch, ascending by their bit mask (bit r - 1 = in box r) — "in box r only", and one class per overlap
+    that occurs. More than 32 classes in all raise ``ValueError``.
+    Rows: base text rows see 0 and every image class; line r's text rows see r and the image classes whose set contains r (the line's own
+    box); an image row in no box sees 0 and every image class; an image row inside boxes M sees 0, every r in M, the background and every
+    image class whose set intersects M — not the image keys that lie only in other lines' boxes. Under true CFG the conditioning batch
+    is [negative, positive] and the key classes of the negative half are the positive half's; its image rows see 0 and every image class.
+    Every row sees at least one key (asserted)."""
+    has_prompt = [True] * len(masks) if has_prompt is None else [bool(h) for h in has_prompt]
+    if len(has_prompt) != len(masks):
+        raise ValueError(f"line prompts: {len(has_prompt)} entries for {len(masks)} regional masks")
+    lines = [i for i, h in enumerate(has_prompt) if h]
+    R = len(lines)
+    if R == 0:
+        return None
+    if R + 2 > MAX_KEY_CLASSES:
+        raise ValueError(f"line prompt isolation: {R} line prompts need more than {MAX_KEY_CLASSES} key classes")
+    if T0 < 1 or L < 1 or N < 1:
+        raise ValueError(f"line prompts: need at least one base, line and image token, got {T0}, {L}, {N}")
+    T = T0 + R * L
+    S = T + N
+    member = np.zeros((batch, N), dtype=np.int64)                    # bit r - 1: the token lies in box r
+    for r, line in enumerate(lines, start=1):
+        on = torch.as_tensor(masks[line]).detach().to("cpu", torch.float32).reshape(-1, N).numpy() > 0      # [1 or batch, N]
+        if on.shape[0] not in (1, batch):
+            raise ValueError(f"line prompts: regional mask {line} has {on.shape[0]} entries for a batch of {batch}")
+        member |= np.where(on, np.int64(1 << (r - 1)), np.int64(0))
+    sets = [0] + sorted(int(m) for m in np.unique(member) if m != 0)
+    if 1 + R + len(sets) > MAX_KEY_CLASSES:
+        raise ValueError(f"line prompt isolation: the base prompt, {R} line prompts and {len(sets)} kinds of image token (the background, the "
+                         f"boxes and their overlaps) need {1 + R + len(sets)} key classes, at most {MAX_KEY_CLASSES} are supported")
+    cls_of = {m: R + 1 + i for i, m in enumerate(sets)}
+    img_all = sum(1 << c for c in cls_of.values())
+    key_class = np.zeros((batch, S), dtype=np.uint8)
+    row_vis = np.full((batch * (2 if cfg else 1), S), 1 | img_all, dtype=np.uint32)
+    for r in range(1, R + 1):
+        key_class[:, T0 + (r - 1) * L : T0 + r * L] = r
+        row_vis[:, T0 + (r - 1) * L : T0 + r * L] = (1 << r) | sum(1 << c for m, c in cls_of.items() if (m >> (r - 1)) & 1)
+    word_of = {m: (1 | img_all) if m == 0 else (1 | (m << 1) | (1 << cls_of[0]) | sum(1 << c for m2, c in cls_of.items() if m2 & m)) for m in sets}
+    key_class[:, T:] = np.vectorize(cls_of.get, otypes=[np.uint8])(member)
+    row_vis[-batch:, T:] = np.vectorize(word_of.get, otypes=[np.uint32])(member)
+    if cfg:
+        key_class = np.concatenate([key_class, key_class])
+    present = np.zeros(key_class.shape[0], dtype=np.uint32)
+    for c in range(MAX_KEY_CLASSES):
+        present |= np.where((key_class == c).any(axis=1), np.uint32(1 << c), np.uint32(0))
+    assert ((row_vis & present[:, None]) != 0).all(), "line_prompt_classes: a row sees no key"
+    return torch.from_numpy(row_vis.view(np.int32)), torch.from_numpy(key_class)
+
+
+def line_isolation_argument(ext, line_entries) -> bool:
+    """Check ``control_prompt_isolation`` of a call (``ISOLATION_ARGUMENTS``) -> whether its line prompts run under ``line_prompt_classes``."""
+    on = getattr(ext, "control_prompt_isolation", False)
+    if not isinstance(on, bool):
+        raise ValueError(f"control_prompt_isolation must be a bool, got {type(on).__name__}")
+    if on and line_entries is None:
+        raise ValueError("control_prompt_isolation=True needs a per-line prompt (control_prompt / control_prompt_embeds): without one there "
+                         "is nothing to isolate")
+    return on
 
 
 def line_prompt_arguments(ext, n_lines: int, control_mask, fp8_attention: bool = False) -> Optional[list]:
@@ -1132,7 +1225,7 @@ class FluxControlNetPipeline:
         return Image.new("RGB", (size, size), (0, 0, 0))
 
     # ------------------------------------------------------------------ the call
-    @accepts_call_extensions(*RegionalIPCallExtensions.__dataclass_fields__)
+    @accepts_call_extensions(*IsolationCallExtensions.__dataclass_fields__)
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 28,
@@ -1176,6 +1269,7 @@ class FluxControlNetPipeline:
         cfg = self._check_true_cfg_inputs(ext, prompt_embeds, pooled_prompt_embeds, batch_size, joint_attention_kwargs)
         line_entries = line_prompt_arguments(ext, len(control_image) if control_image is not None else 0, control_mask,
                                              bool(getattr(self.transformer, "_fp8_attention", False)))
+        isolation = line_isolation_argument(ext, line_entries)
         positive_ip = (ext.ip_adapter_image is not None or ext.ip_adapter_image_embeds is not None
                        or "ip_adapter_image_embeds" in (joint_attention_kwargs or {}))
         regional_args = regional_ip_arguments(ext, len(control_image) if control_image is not None else 0, control_mask,
@@ -1210,7 +1304,8 @@ class FluxControlNetPipeline:
         latents, latent_image_ids, repaint = self._start_state(start, control_glyph, total, height, width, prompt_embeds.dtype, device, generator, latents)
         region = self._region_masks(control_mask, latents.device, prompt_embeds.dtype)
         masks = [self._doubled_under_cfg(m, total, cfg, mask=True) for m in region]
-        line_prompts = self._line_prompts(line_entries, ext, region, prompt_embeds, latents.shape[1], total, num_images_per_prompt, cfg, device)
+        line_prompts = self._line_prompts(line_entries, ext, region, prompt_embeds, latents.shape[1], total, num_images_per_prompt, cfg, device,
+                                          isolation)
         active = union_active_steps(len(timesteps), float(ext.control_guidance_start_union), float(ext.control_guidance_end_union)) if with_union else ()
         union = UnionTower(self.controlnet_union, union_hint, float(ext.controlnet_conditioning_scale_union), active) if active else None
         regional = self._regional_ip(regional_args, ip_embeds, region, latents.shape[1], total, num_images_per_prompt, cfg, device,
@@ -1261,13 +1356,16 @@ class FluxControlNetPipeline:
         dev = lambda t: None if t is None else t.to(device)
         return RegionalIP(tuple(embeds), tuple(dev(w) for w in img_w), tuple(dev(w) for w in txt_w))
 
-    def _line_prompts(self, entries, ext, region, prompt_embeds, N, total, num_images_per_prompt, cfg, device) -> Optional[LinePrompts]:
+    def _line_prompts(self, entries, ext, region, prompt_embeds, N, total, num_images_per_prompt, cfg, device,
+                      isolation: bool = False) -> Optional[LinePrompts]:
         """The call's per-line prompts as the loop takes them (None: the call has none). T5 only: the pooled CLIP vector stays the base
         prompt's. Under true CFG the line embeddings serve both halves; the negative half's image rows do not see them."""
         if entries is None:
             return None
         L, Bc, T0 = ext.control_prompt_max_sequence_length, prompt_embeds.shape[0], prompt_embeds.shape[1]
-        table = line_prompt_groups(T0, L, region, N, [e is not None for e in entries], batch=total, cfg=cfg)
+        has_prompt = [e is not None for e in entries]
+        # with isolation only the group ENDS (the text layout, and the rule's own refusals) are taken from it; the row table is line_prompt_classes'
+        ends, row_vis = line_prompt_groups(T0, L, region, N, has_prompt, batch=total, cfg=cfg)
         embeds = []
         for e in entries:
             if isinstance(e, str):
@@ -1281,7 +1379,10 @@ class FluxControlNetPipeline:
                 e = e.to(device=device, dtype=prompt_embeds.dtype)
                 embeds.append(torch.cat([e, e]) if cfg else e)
         assert all(e.shape[0] == Bc for e in embeds)
-        return LinePrompts(torch.cat(embeds, dim=1).contiguous(), table[0], table[1].to(device))
+        if isolation:
+            row_vis, key_class = line_prompt_classes(T0, L, region, N, has_prompt, batch=total, cfg=cfg)
+            return IsolatedLinePrompts(torch.cat(embeds, dim=1).contiguous(), ends, row_vis.to(device), key_class.to(device))
+        return LinePrompts(torch.cat(embeds, dim=1).contiguous(), ends, row_vis.to(device))
 
     # ------------------------------------------------------------------ stages of the call (shared with pipeline_inpaint.py)
     @staticmethod

@@ -21,7 +21,7 @@ import torch.nn.functional as F
 from . import ops
 from .image_processor import PipelineImageInput, VaeImageProcessor
 from .pipeline import FluxControlNetPipeline as _BasePipeline
-from .pipeline import LINE_PROMPT_ARGUMENTS, REGIONAL_IP_ARGUMENTS, LoopExtras, accepts_call_extensions
+from .pipeline import ISOLATION_ARGUMENTS, LINE_PROMPT_ARGUMENTS, REGIONAL_IP_ARGUMENTS, LoopExtras, accepts_call_extensions
 
 DEFAULT_NEGATIVE_PROMPT = "bad quality, worst quality, text, signature, watermark, extra words"     # INP:416
 
@@ -84,7 +84,8 @@ class FluxControlNetPipeline(_BasePipeline):
         return packed, height, width
 
     # ------------------------------------------------------------------ INP:846-1313
-    @accepts_call_extensions("ip_adapter_image", "ip_adapter_image_embeds", *LINE_PROMPT_ARGUMENTS, *REGIONAL_IP_ARGUMENTS)      # taken only to be refused by name below
+    @accepts_call_extensions("ip_adapter_image", "ip_adapter_image_embeds", *LINE_PROMPT_ARGUMENTS, *REGIONAL_IP_ARGUMENTS,
+                             *ISOLATION_ARGUMENTS)      # taken only to be refused by name below
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  true_guidance_scale: float = 3.5, negative_prompt: Optional[Union[str, List[str]]] = None,
@@ -123,6 +124,8 @@ class FluxControlNetPipeline(_BasePipeline):
         if getattr(ext, "control_prompt", None) is not None or getattr(ext, "control_prompt_embeds", None) is not None:
             # the flow's own CFG doubles the batch inside the loop: the row table of the unconditional half is not built for it
             raise ValueError("the inpaint pipeline does not support per-line prompts (control_prompt / control_prompt_embeds)")
+        if getattr(ext, "control_prompt_isolation", False):
+            raise ValueError("the inpaint pipeline does not support per-line prompts (control_prompt_isolation)")
         self._guidance_scale, self._joint_attention_kwargs, self._interrupt = guidance_scale, joint_attention_kwargs, False
         cfg = self.do_classifier_free_guidance                          # enabled by guidance_scale > 1, scaled by true_guidance_scale (Q8)
         device, dtype = self._execution_device, self.transformer.dtype

@@ -282,6 +282,21 @@ int rt_attention_fwd_grouped(const void* q, const void* k, const void* v, void* 
                              const int32_t* group_end, int32_t n_groups, const uint32_t* row_vis, int64_t stride_vis_b,
                              void* ws, int64_t ws_bytes, void* stream);
 
+/* Joint attention with a class id per KEY (region isolation of per-line prompts): rt_attention_fwd_grouped with visibility decided
+ * per key instead of per 64-key tile. key_class: DEVICE [B][S] bytes, values 0..31, batch stride stride_class_b bytes (0: one table
+ * for the batch); row_vis as above. Row i of entry b attends key j iff bit key_class[b][j] of row_vis[b][i] is set (only the low 5
+ * bits of a class byte are read). Keys >= S are masked whatever lies behind the table; a row that sees no key gets zeros. A class
+ * table that is constant on every 64-key tile is a group table: the output then has the bits of rt_attention_fwd_grouped.
+ * Alignment and padding: row_vis 4-byte aligned (RT_E_ALIGN). key_class is read a byte at a time, bytes [0, S) of each entry and no
+ * other: no alignment of base or stride and no padding is asked. RT_E_BADARG: a null table, scale <= 0, a negative stride.
+ * Otherwise rt_attention_fwd_grouped's contract: hidden keys and values must be finite, o may alias q, the grid, key split and
+ * workspace of the dense launch of (B, S, H), never attention_v3. Added without an ABI bump: nothing existing changed. */
+int rt_attention_fwd_keyed(const void* q, const void* k, const void* v, void* o,
+                           int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob,
+                           int32_t B, int32_t S, int32_t H, float scale,
+                           const uint32_t* row_vis, int64_t stride_vis_b, const uint8_t* key_class, int64_t stride_class_b,
+                           void* ws, int64_t ws_bytes, void* stream);
+
 /* Which kernel serves rt_attention_fwd (speed only; both are tested against the same references): 1 (default, env RT_ATTN_V3) =
  * shapes with S % 256 == 0 and S >= 1536 run csrc/attention_v3.hip — one wave per SIMD, 64 query rows per wave, O / Q / row sums
  * in asm-owned accumulator registers, hand-placed MFMA gaps (S = 4608: 247 vs 264 us) —, everything else csrc/attention.hip;

@@ -7,7 +7,11 @@ batch 1, random weights, captured loop):
     and of the call with two line prompts of 128 tokens, each from its captured graph, alternated in pairs (the pipeline keeps two graphs).
 By counting, the line prompts cost 4864² / 4608² = 1.11 x the attention FLOPs plus the loss of attention_v3 at this S, and the longer
 text stream in every GEMM of the text rows.
-Prints a table and one JSON line.  python tools/bench_line_prompts.py [--repeats 3] [--inference-steps 28] [--kernel-only]"""
+`--isolation` measures region isolation (control_prompt_isolation=True, rt_attention_fwd_keyed) instead: the kernel cases are the grouped
+launch with the real table, the keyed launch with the tables of line_prompt_classes for the same two boxes (16 of the 64 image-row
+tiles hold two classes), the keyed launch with a class per group (every tile of one class) and with every key of every tile of
+another class than its neighbour (every tile mixed); the pipeline pair is the call with line prompts without and with isolation.
+Prints a table and one JSON line.  python tools/bench_line_prompts.py [--repeats 3] [--inference-steps 28] [--kernel-only] [--isolation]"""
 import argparse
 import json
 import os
@@ -32,8 +36,8 @@ def two_boxes(dev, dtype):
     return out
 
 
-def kernel_bench(dev, rounds=3, iters=10):
-    from reptext_amd.pipeline import line_prompt_groups
+def kernel_bench(dev, rounds=3, iters=10, isolation=False):
+    from reptext_amd.pipeline import line_prompt_classes, line_prompt_groups
 
     S, d = T0 + R * L + N, H * 128
     qkv = torch.randn(1, S, 3 * d, device=dev).to(torch.bfloat16)
@@ -54,8 +58,16 @@ def kernel_bench(dev, rounds=3, iters=10):
 
     grouped = lambda table: (lambda g: lambda: ops.attention(q, k, v, out, H, groups=g))(ops.KeyGroups(ends, table.to(dev)))
     cases = {"grouped_all_bits": grouped(full), "grouped_real_table": grouped(real), "dense_variant0": dense(0), "dense_variant1": dense(1)}
+    if isolation:
+        boxes = [m.cpu() for m in two_boxes("cpu", torch.float32)]
+        keyed = lambda vis, cls: (lambda g: lambda: ops.attention(q, k, v, out, H, groups=g))(ops.KeyClasses(vis, cls).to(dev))
+        j = torch.arange(S)
+        per_group = torch.bucketize(j, torch.tensor(ends), right=True).to(torch.uint8)[None]
+        cases = {"grouped_real_table": grouped(real), "keyed_real_tables": keyed(*line_prompt_classes(T0, L, boxes, N)),
+                 "keyed_class_per_group": keyed(real, per_group), "keyed_every_tile_mixed": keyed(torch.full_like(real, 3), (j % 2).to(torch.uint8)[None])}
     for fn in cases.values():
-        fn()
+        for _ in range(iters if isolation else 1):                      # isolation: a window long enough for the clocks to settle
+            fn()
     torch.cuda.synchronize()
     res = {name: [] for name in cases}
     for _ in range(rounds):                                            # alternated: every round times each case once
@@ -79,11 +91,12 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--inference-steps", type=int, default=28)
     ap.add_argument("--kernel-only", action="store_true")
+    ap.add_argument("--isolation", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_line_prompts.py measures on an MI355X; no GPU is visible")
     dev = torch.device("cuda:0")
-    result = {"tool": "bench_line_prompts", "device": torch.cuda.get_device_name(0), "kernel": kernel_bench(dev)}
+    result = {"tool": "bench_line_prompts", "device": torch.cuda.get_device_name(0), "kernel": kernel_bench(dev, iters=200 if args.isolation else 10, isolation=args.isolation)}
     if args.kernel_only:
         print(json.dumps(result), flush=True)
         return
@@ -109,9 +122,10 @@ def main():
     base, long_prompt, lines = r(1, T0, 4096), r(1, T0 + R * L, 4096), [r(1, L, 4096) for _ in range(R)]
     modes = {"plain_T512": dict(prompt_embeds=base), "dense_T768": dict(prompt_embeds=long_prompt),
              "line_prompts": dict(prompt_embeds=base, control_prompt_embeds=lines, control_prompt_max_sequence_length=L)}
+    modes["line_isolation"] = dict(modes["line_prompts"], control_prompt_isolation=True)
     run = lambda m: pipe(**kw, **modes[m])
     result["pipeline"] = {"shape": "1024x1024, two text lines, batch 1", "steps": steps, "pairs": []}
-    for pair in (("plain_T512", "line_prompts"), ("dense_T768", "line_prompts")):
+    for pair in ((("line_prompts", "line_isolation"),) if args.isolation else (("plain_T512", "line_prompts"), ("dense_T768", "line_prompts"))):
         pipe.__dict__.get("_graph_cache", {}).clear()                   # the pipeline keeps two graphs: each pair has the cache to itself
         for m in pair:                                                  # eager, then capture
             run(m)
@@ -129,7 +143,7 @@ def main():
         graphs = len([v for v in pipe._graph_cache.values() if isinstance(v, dict)])
         result["pipeline"]["pairs"].append({"graphs": graphs, "ms_per_step": res})
         for m in pair:
-            print(f"  ms per denoising step, {m:13s}: " + "  ".join(f"{t:.3f}" for t in res[m]) + f"   ({graphs} captured graphs)", flush=True)
+            print(f"  ms per denoising step, {m:14s}: " + "  ".join(f"{t:.3f}" for t in res[m]) + f"   ({graphs} captured graphs)", flush=True)
     print(json.dumps(result), flush=True)
 
 
