@@ -40,6 +40,19 @@
 // mask per row. A tile of one class takes the grouped code's hide branch; only a tile of several classes pays a bit test per score.
 // Everything it adds stands under `if constexpr (KEYED)`.
 //
+// rt_attention_fwd_grouped_biased / rt_attention_fwd_keyed_biased are the fourth and fifth instantiation (BIASED: a strength per line
+// prompt): an fp32 bias per key CLASS (the group index / the class byte) is added to the logits of that class's keys. The kernel works
+// on RAW scores (scale_log2 is applied inside the exp2's fma), so a table entry is converted where it is read, once per class, to
+// raw-score units (bias / scale). It is read by a scalar load — grouped: when the group advances; keyed: in the class walk — and only
+// for a class whose bit is set in `nz`, the 32-bit set of the classes with a non-zero entry, taken once per workgroup: nothing is
+// held per lane. The bias is added BEFORE the half's row maximum is taken, so that the speculative numerators, decide, the deferred
+// rescale and the key-split records see an ordinary score: a record's m simply includes the bias, and the combine (which weighs
+// records by exp2(m_j - M) and knows nothing of how a score came about) needs no change — checked against attention_split.h.
+// A hidden or ragged score is -inf before the add and after it. A tile whose bias is 0 executes what its unbiased sibling executes.
+// A keyed tile of several classes of which one has a bias (never in the pipeline's use: biased classes are text tokens, which fill
+// whole tiles) loads, per lane, the class and the bias of key 64t + lane again and hands each score its own key's through v_readlane
+// (no LDS memory: the 64 KiB are taken), out of line. Everything it adds stands under `if constexpr (BIASED)`.
+//
 // LDS image of a K or V tile: 64 rows × 256 B; 16-B chunk c of row r lives at 256·r + 16·(c ^ f(r)),
 // f(r) = ((r&3)<<2) | ((r>>2)&3): conflict-free for the row reads (K) and the transposed reads (V).
 // LDS-DMA writes lane-linear, so the XOR is applied to each lane's source address.
@@ -81,10 +94,20 @@ struct KeyClasses {
   const uint8_t* key_class;  // [B][S], batch stride stride_class_b (0: one table)
   int64_t stride_class_b;
 };
-enum { DENSE_MODE = 0, GROUPED_MODE = 1, KEYED_MODE = 2 };
+// the biased entries: their sibling's record and the bias table, fp32 [B][MAX_GROUPS] in natural-log units, one entry per key class
+struct KeyBias {
+  const float* key_bias;     // batch stride stride_bias_b (0: one table)
+  int64_t stride_bias_b;
+};
+struct NoBias {};
+struct KeyGroupsBiased : KeyGroups, KeyBias {};
+struct KeyClassesBiased : KeyClasses, KeyBias {};
+enum { DENSE_MODE = 0, GROUPED_MODE = 1, KEYED_MODE = 2, GROUPED_BIASED_MODE = 3, KEYED_BIASED_MODE = 4 };
 template <int MODE> struct MaskArg { using type = NoGroups; };
 template <> struct MaskArg<GROUPED_MODE> { using type = KeyGroups; };
 template <> struct MaskArg<KEYED_MODE> { using type = KeyClasses; };
+template <> struct MaskArg<GROUPED_BIASED_MODE> { using type = KeyGroupsBiased; };
+template <> struct MaskArg<KEYED_BIASED_MODE> { using type = KeyClassesBiased; };
 // Running maximum a grouped row starts with: finite, so that a hidden score (-inf) gives exp2(-inf - M0) = 0 and not exp2(NaN), and
 // so far below any score that the first visible one rescales the (all-zero) state by exp2(M0 - m) = 0.
 constexpr float GROUPED_M0 = -1.0e30f;
@@ -95,7 +118,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
     int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob, float scale_log2, const SplitGeom G,
     const int row_lo, const int row_hi, int* counters, char* records,
     const typename MaskArg<MODE>::type KG) {
-  constexpr bool GROUPED = MODE == GROUPED_MODE, KEYED = MODE == KEYED_MODE, MASKED = MODE != DENSE_MODE;
+  constexpr bool GROUPED = MODE == GROUPED_MODE || MODE == GROUPED_BIASED_MODE, KEYED = MODE == KEYED_MODE || MODE == KEYED_BIASED_MODE;
+  constexpr bool MASKED = MODE != DENSE_MODE, BIASED = MODE == GROUPED_BIASED_MODE || MODE == KEYED_BIASED_MODE;
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE_B];   // [slot][K|V]
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -154,6 +178,20 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
       vp[1][dt] = (lds_cptr)smem + TILE_B + rl1 * 256 + (((dt * 4 + cl) ^ swz(rl1)) << 4) + 8 * (tp & 1);
     }
   }
+
+  // biased: the table is in natural-log units and a raw score is multiplied by scale_log2 = scale·log2(e) inside the exp2, so an entry
+  // times bias_mul = 1 / scale is a bias in raw-score units. nz: bit c set = class c's entry is not zero (scalar).
+  // Only nz lives across the tile loop; the table's address and bias_mul are formed again where a bias is read (rare).
+  [[maybe_unused]] uint32_t nz = 0;
+  [[maybe_unused]] auto bias_at = [&](uint32_t c) -> float {      // c wave-uniform: a scalar load
+    if constexpr (BIASED) return KG.key_bias[b * KG.stride_bias_b + c] * (1.4426950408889634f / scale_log2);
+    return 0.f;
+  };
+  if constexpr (BIASED) nz = (uint32_t)__ballot(lane < MAX_GROUPS && KG.key_bias[b * KG.stride_bias_b + (lane & (MAX_GROUPS - 1))] != 0.f);
+  // a tile's bias state in one scalar word: 0 = no key of the tile has a bias; MIXED_BIAS (a NaN pattern, no finite bias) = a keyed tile
+  // of several classes with a bias among them; else the bits of the tile's one bias
+  constexpr uint32_t MIXED_BIAS = 0x7fc00000u;
+  [[maybe_unused]] auto bias_word = [&](uint32_t c) -> uint32_t { return ((nz >> c) & 1u) ? __builtin_bit_cast(uint32_t, bias_at(c)) : 0u; };
 
   using S0 = std::integral_constant<int, 0>;
   using S1 = std::integral_constant<int, 1>;
@@ -231,6 +269,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
       vis = KG.row_vis[b * KG.stride_vis_b + min(q0 + wave * 32 + l31, S - 1)];
       gend_t = (KG.end[0] + BKV - 1) / BKV;
     }
+    [[maybe_unused]] uint32_t gbias = 0;      // biased grouped: the bias word of group gid (scalar; read when gid advances)
+    if constexpr (GROUPED && BIASED) gbias = bias_word(0);
     // keyed: the class of key 64t + lane of the tile to come (clamped to the table: keys >= S are masked as in every mode; only the low
     // 5 bits of a byte count, whatever the table holds), loaded a tile ahead: behind tile t's DMA barrier, so that the load has the whole
     // tile to land and the next tile's barrier covers its wait
@@ -328,6 +368,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
         while (t >= gend_t && gid + 1 < KG.n) {
           ++gid;
           gend_t = (KG.end[gid] + BKV - 1) / BKV;
+          if constexpr (BIASED) gbias = bias_word(gid);
         }
         hidden = ((vis >> gid) & 1u) == 0;
       }
@@ -342,6 +383,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
       [[maybe_unused]] uint32_t vlo = 0, vhi = 0;
       [[maybe_unused]] bool mixed = false;
       [[maybe_unused]] uint32_t cls = 0;
+      [[maybe_unused]] uint32_t tbias = 0;       // biased: the tile's bias word (wave-uniform)
+      if constexpr (GROUPED && BIASED) tbias = gbias;
       rt_dma_barrier();                          // tile t landed (every wave's vmcnt(0), then the barrier); the other slot is free
       if constexpr (KEYED) {
         cls = cls_next;
@@ -357,6 +400,9 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
             vlo |= (uint32_t)m;
             vhi |= (uint32_t)(m >> 32);
           }
+          if constexpr (BIASED) {
+            if (RT_RARE((nz >> c) & 1u)) tbias = __builtin_bit_cast(uint32_t, bias_at(c));      // the tile's, when this is its only class
+          }
           ++nclass;
         } while (rem);
         mixed = nclass > 1;
@@ -364,7 +410,28 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
         any_hidden = __any(hidden);
         vlo >>= 4 * hh;
         vhi >>= 4 * hh;
+        if constexpr (BIASED) { if (RT_RARE(mixed && tbias)) tbias = MIXED_BIAS; }
       }
+      // biased: every score gets the bias of its key's class, before the half's maximum is taken. One class: the scalar. Several (rare,
+      // out of line): lane l loads the class and the bias of key 64t + l (clamped as the class load is: a key >= S is -inf already);
+      // score r of half h is key 32h + (r&3) + 8(r>>2) + 4hh of the tile (mask_half's map) and takes the bias that the lane of that index holds.
+      [[maybe_unused]] auto add_bias = [&](f32x16& s, int h) {
+        if (RT_RARE(KEYED && tbias == MIXED_BIAS)) {
+          asm volatile("" ::: "memory");           // keep this rare block a real branch
+          float kbias = 0.f;
+          if constexpr (KEYED && BIASED)
+            kbias = KG.key_bias[b * KG.stride_bias_b + (kcls[min(t * BKV + lane, S - 1)] & 31u)] * (1.4426950408889634f / scale_log2);
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {           // two scalar reads per score register (lanes 0-31 / 32-63 hold different keys), no vector temporaries
+            const int k0 = 32 * h + (r & 3) + 8 * (r >> 2);
+            const int b0 = __builtin_amdgcn_readlane(__builtin_bit_cast(int, kbias), k0), b1 = __builtin_amdgcn_readlane(__builtin_bit_cast(int, kbias), k0 + 4);
+            s[r] += __builtin_bit_cast(float, hh ? b1 : b0);
+          }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 16; ++r) s[r] += __builtin_bit_cast(float, tbias);
+        }
+      };
       auto hide_keys = [&](f32x16& s, uint32_t vm) {   // keyed: one class -> the grouped code's whole-tile hide; several -> a bit per score
         if (RT_RARE(mixed)) {
 #pragma unroll
@@ -405,6 +472,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
       if (RT_RARE(ragged)) mask_half(s0, 0);
       if constexpr (GROUPED) { if (any_hidden) hide_half(s0); }
       if constexpr (KEYED) { if (any_hidden) hide_keys(s0, vlo); }
+      if constexpr (BIASED) { if (tbias) add_bias(s0, 0); }
       float mx0 = half_max(s0);
       __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
       __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
@@ -436,6 +504,7 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
       if (RT_RARE(ragged)) mask_half(s1, 1);
       if constexpr (GROUPED) { if (any_hidden) hide_half(s1); }
       if constexpr (KEYED) { if (any_hidden) hide_keys(s1, vhi); }
+      if constexpr (BIASED) { if (tbias) add_bias(s1, 1); }
       float mx1 = half_max(s1);
       RT_WEAVE(4, 2, 9)
       RT_PIN(p01); RT_PIN(l_run); RT_PIN(mx1);
@@ -624,6 +693,29 @@ int launch(const void* q, const void* k, const void* v, void* o, int64_t ld, int
   return rt_hip_status();
 }
 
+// The checks of rt_attention_fwd_grouped's own arguments, and its record by value.
+int make_key_groups(KeyGroups& kg, int32_t S, float scale, const int32_t* group_end, int32_t n_groups, const uint32_t* row_vis,
+                    int64_t stride_vis_b) {
+  if (!(scale > 0.f) || !group_end || !row_vis || n_groups < 1 || n_groups > MAX_GROUPS || stride_vis_b < 0) return RT_E_BADARG;
+  if (!RT_ALIGNED(row_vis, 4)) return RT_E_ALIGN;
+  int32_t prev = 0;
+  for (int g = 0; g < n_groups; ++g) {
+    const int32_t e = group_end[g];
+    if (e <= prev || e > S || (g + 1 < n_groups && e % BKV) || (g + 1 == n_groups && e != S)) return RT_E_BADARG;
+    kg.end[g] = prev = e;
+  }
+  for (int g = n_groups; g < MAX_GROUPS; ++g) kg.end[g] = S;
+  kg.n = n_groups;
+  kg.row_vis = row_vis;
+  kg.stride_vis_b = stride_vis_b;
+  return RT_OK;
+}
+
+int check_key_bias(const float* key_bias, int64_t stride_bias_b) {
+  if (!key_bias || stride_bias_b < 0) return RT_E_BADARG;
+  return RT_ALIGNED(key_bias, 4) ? RT_OK : RT_E_ALIGN;
+}
+
 }  // namespace
 
 // The full launch, cut exactly as rt_attention_fwd cuts it (same kernel, grid, key split and workspace), in which only the items that
@@ -647,20 +739,23 @@ extern "C" int rt_attention_fwd_grouped(const void* q, const void* k, const void
                                         const int32_t* group_end, int32_t n_groups, const uint32_t* row_vis, int64_t stride_vis_b,
                                         void* ws, int64_t ws_bytes, void* stream) {
   if (const int st = check_common(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, 0, S)) return st;
-  if (!(scale > 0.f) || !group_end || !row_vis || n_groups < 1 || n_groups > MAX_GROUPS || stride_vis_b < 0) return RT_E_BADARG;
-  if (!RT_ALIGNED(row_vis, 4)) return RT_E_ALIGN;
   KeyGroups kg = {};
-  int32_t prev = 0;
-  for (int g = 0; g < n_groups; ++g) {
-    const int32_t e = group_end[g];
-    if (e <= prev || e > S || (g + 1 < n_groups && e % BKV) || (g + 1 == n_groups && e != S)) return RT_E_BADARG;
-    kg.end[g] = prev = e;
-  }
-  for (int g = n_groups; g < MAX_GROUPS; ++g) kg.end[g] = S;
-  kg.n = n_groups;
-  kg.row_vis = row_vis;
-  kg.stride_vis_b = stride_vis_b;
+  if (const int st = make_key_groups(kg, S, scale, group_end, n_groups, row_vis, stride_vis_b)) return st;
   return launch<GROUPED_MODE>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, 0, S, ws, ws_bytes, stream, kg);
+}
+
+// rt_attention_fwd_grouped with a bias per key group: the same checks, grid, key split and workspace, the biased instantiation.
+extern "C" int rt_attention_fwd_grouped_biased(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b,
+                                               int64_t ldo, int64_t stride_ob, int32_t B, int32_t S, int32_t H, float scale,
+                                               const int32_t* group_end, int32_t n_groups, const uint32_t* row_vis, int64_t stride_vis_b,
+                                               void* ws, int64_t ws_bytes, void* stream, const float* key_bias, int64_t stride_bias_b) {
+  if (const int st = check_common(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, 0, S)) return st;
+  KeyGroupsBiased kg = {};
+  if (const int st = make_key_groups(kg, S, scale, group_end, n_groups, row_vis, stride_vis_b)) return st;
+  if (const int st = check_key_bias(key_bias, stride_bias_b)) return st;
+  kg.key_bias = key_bias;
+  kg.stride_bias_b = stride_bias_b;
+  return launch<GROUPED_BIASED_MODE>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, 0, S, ws, ws_bytes, stream, kg);
 }
 
 // Joint attention with a class id per key (region isolation of per-line prompts): the grouped launch with visibility decided per key
@@ -674,4 +769,19 @@ extern "C" int rt_attention_fwd_keyed(const void* q, const void* k, const void* 
   if (!RT_ALIGNED(row_vis, 4)) return RT_E_ALIGN;
   const KeyClasses kc = {row_vis, stride_vis_b, key_class, stride_class_b};
   return launch<KEYED_MODE>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, 0, S, ws, ws_bytes, stream, kc);
+}
+
+// rt_attention_fwd_keyed with a bias per key class: the same checks, grid, key split and workspace, the biased instantiation.
+extern "C" int rt_attention_fwd_keyed_biased(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b, int64_t ldo,
+                                             int64_t stride_ob, int32_t B, int32_t S, int32_t H, float scale, const uint32_t* row_vis,
+                                             int64_t stride_vis_b, const uint8_t* key_class, int64_t stride_class_b, void* ws,
+                                             int64_t ws_bytes, void* stream, const float* key_bias, int64_t stride_bias_b) {
+  if (const int st = check_common(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, 0, S)) return st;
+  if (!(scale > 0.f) || !row_vis || !key_class || stride_vis_b < 0 || stride_class_b < 0) return RT_E_BADARG;
+  if (!RT_ALIGNED(row_vis, 4)) return RT_E_ALIGN;
+  if (const int st = check_key_bias(key_bias, stride_bias_b)) return st;
+  KeyClassesBiased kc = {};
+  kc.row_vis = row_vis, kc.stride_vis_b = stride_vis_b, kc.key_class = key_class, kc.stride_class_b = stride_class_b;
+  kc.key_bias = key_bias, kc.stride_bias_b = stride_bias_b;
+  return launch<KEYED_BIASED_MODE>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, 0, S, ws, ws_bytes, stream, kc);
 }

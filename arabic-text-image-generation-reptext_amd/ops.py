@@ -574,18 +574,34 @@ class KeyClasses:
                 _dev(kc, "groups.key_class"), (0 if kc.shape[0] == 1 else kc.stride(0)))
 
 
+def _key_bias(kb, B: int, device) -> Tuple[int, int]:
+    """Validate ``attention``'s ``key_bias`` against a batch of B -> (pointer, batch stride in elements; 0: one table)."""
+    if not isinstance(kb, torch.Tensor) or kb.dtype != F32:
+        raise TypeError("attention: key_bias must be a float32 tensor")
+    if kb.dim() != 2 or kb.shape[1] != 32 or kb.shape[0] not in (1, B) or kb.stride(1) != 1:
+        raise ValueError(f"attention: key_bias: need [{B} or 1, 32] with unit inner stride, got {tuple(kb.shape)} / {kb.stride()}")
+    if kb.device != device:
+        raise RuntimeError(f"attention: key_bias is on {kb.device}, q on {device}")
+    return _dev(kb, "key_bias", F32), (0 if kb.shape[0] == 1 else kb.stride(0))
+
+
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, scale: Optional[float] = None,
-              split: bool = True, rows: Optional[tuple] = None, groups: Optional[Union[KeyGroups, KeyClasses]] = None) -> torch.Tensor:
+              split: bool = True, rows: Optional[tuple] = None, groups: Optional[Union[KeyGroups, KeyClasses]] = None,
+              key_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
     """q,k,v [B,S,H*128] views (common strides) of one buffer; out [B,S,H*128] view (may alias q). ``split=False`` runs every
     128-row block as one full-length workgroup (no key-split tail; A/B and tests). ``rows`` = (r0, r1): only the items of the launch that
     hold a query row of [r0, r1) do any work (rt_attention_fwd_rows): those rows of out get the bits the whole launch gives them, the
     other rows of the touched items are written too, the rest of out is left as it is. ``groups`` (a KeyGroups; not together with
     ``rows``): region-masked attention, rt_attention_fwd_grouped — hidden keys must still hold finite values; a KeyClasses in its
-    place: visibility per key, rt_attention_fwd_keyed."""
+    place: visibility per key, rt_attention_fwd_keyed. ``key_bias`` (only with ``groups``): float32 [B or 1, 32] on q's device, added
+    to the logits (natural-log units) of the keys of group / class c — the softmax weight of those keys times exp(key_bias[b, c]); finite
+    values; visibility is unchanged (rt_attention_fwd_grouped_biased / rt_attention_fwd_keyed_biased). None: the unbiased entries."""
     (B, S, _, ld, sb), _, _, (_, _, _, ldo, sob) = [_rows3(t, name, width=H * 128) for name, t in (("q", q), ("k", k), ("v", v), ("out", out))]
     if not (q.stride() == k.stride() == v.stride()) or k.shape != q.shape or v.shape != q.shape or out.shape != q.shape:
         raise ValueError("q,k,v must share shape and strides")
     sc = (128 ** -0.5) if scale is None else float(scale)
+    if key_bias is not None and groups is None:
+        raise ValueError("attention: key_bias= needs groups= (a bias per key group or class)")
     if groups is not None:
         if rows is not None:
             raise ValueError("attention: rows= and groups= cannot be combined")
@@ -593,14 +609,26 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
             raise ValueError("attention: groups= needs scale > 0")
         if isinstance(groups, KeyClasses):
             vis, svb, cls, scb = groups.check(B, S)
+            bias = None if key_bias is None else _key_bias(key_bias, B, q.device)
             ws = _attention_workspace(B, S, H, q.device) if split else None
+            if bias is not None:
+                native.call("rt_attention_fwd_keyed_biased", _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(out, "out", BF16),
+                            ld, sb, ldo, sob, B, S, H, sc, vis, svb, cls, scb, None if ws is None else ws.data_ptr(),
+                            0 if ws is None else ws.numel(), _stream(), *bias)
+                return out
             native.call("rt_attention_fwd_keyed", _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(out, "out", BF16), ld,
                         sb, ldo, sob, B, S, H, sc, vis, svb, cls, scb, None if ws is None else ws.data_ptr(),
                         0 if ws is None else ws.numel(), _stream())
             return out
         vis, svb = groups.check(B, S)
         ends = (C.c_int32 * len(groups.ends))(*[int(e) for e in groups.ends])
+        bias = None if key_bias is None else _key_bias(key_bias, B, q.device)
         ws = _attention_workspace(B, S, H, q.device) if split else None
+        if bias is not None:
+            native.call("rt_attention_fwd_grouped_biased", _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(out, "out", BF16),
+                        ld, sb, ldo, sob, B, S, H, sc, C.cast(ends, C.c_void_p), len(groups.ends), vis, svb,
+                        None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), _stream(), *bias)
+            return out
         native.call("rt_attention_fwd_grouped", _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(out, "out", BF16), ld, sb,
                     ldo, sob, B, S, H, sc, C.cast(ends, C.c_void_p), len(groups.ends), vis, svb,
                     None if ws is None else ws.data_ptr(), 0 if ws is None else ws.numel(), _stream())

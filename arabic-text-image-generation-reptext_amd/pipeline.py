@@ -17,6 +17,7 @@ import contextlib
 import functools
 import inspect
 import json
+import math
 import os
 from dataclasses import dataclass, fields, make_dataclass, replace
 from typing import Any, Callable, Dict, List, Optional, Tuple, Union
@@ -215,6 +216,17 @@ class IsolationCallExtensions(RegionalIPCallExtensions):
     control_prompt_isolation: bool = False              # per-line prompts under the per-key rule of ``line_prompt_classes``
 
 
+LINE_SCALE_ARGUMENTS = ("control_prompt_scale",)
+LINE_SCALE_RANGE = (1.0 / 64, 64.0)     # below it a line prompt is as good as hidden, above it the only text its box sees: a stated condition
+
+
+@dataclass
+class LineScaleCallExtensions(IsolationCallExtensions):
+    """``IsolationCallExtensions`` of a call that names ``control_prompt_scale`` (``LINE_SCALE_ARGUMENTS``).
+    ``accepts_call_extensions`` builds it only for such a call."""
+    control_prompt_scale: Any = None                    # a float for every line prompt, or one float or None per text line; None: 1.0
+
+
 def accepts_call_extensions(*names):
     """``__call__`` keeps the reference's parameter list (PIPE:751-781, which ``inspect.signature`` still reports). The fields of
     ``CallExtensions`` in ``names`` are keyword-only extensions of it, taken off here and left on the pipeline, as passed, as
@@ -229,6 +241,8 @@ def accepts_call_extensions(*names):
                 record = RegionalIPCallExtensions
             if any(k in ISOLATION_ARGUMENTS for k in taken):
                 record = IsolationCallExtensions
+            if any(k in LINE_SCALE_ARGUMENTS for k in taken):
+                record = LineScaleCallExtensions
             self._call_extensions = record(**taken)
             try:
                 return call(self, *args, **kwargs)
@@ -391,6 +405,64 @@ def line_prompt_classes(T0: int, L: int, masks, N: int, has_prompt=None, batch: 
     return torch.from_numpy(row_vis.view(np.int32)), torch.from_numpy(key_class)
 
 
+@dataclass(frozen=True)
+class LineScale(_StaticFields):
+    """The strengths of a call's per-line prompts (``control_prompt_scale``) as the joint attention takes them: ``key_bias``
+    = ``line_prompt_bias``'s table, ln w_r on key class r. With it the transformer's joint attention runs the biased launch of its rule
+    (grouped or keyed). A static input of a captured loop: other values replay the same graph."""
+    key_bias: torch.Tensor              # fp32 [1, 32]
+    STATIC = {"line_key_bias": "key_bias"}
+
+    def signature(self, sig) -> tuple:
+        return (("line_scale", sig(self.key_bias)),)
+
+
+def line_prompt_bias(scales, has_prompt) -> torch.Tensor:
+    """The rule of ``control_prompt_scale``, from host values alone -> fp32 [1, 32]: entry r = ln w_r for the r-th line THAT HAS A PROMPT
+    (r = 1..R, numbered as ``line_prompt_groups`` and ``line_prompt_classes`` both number them: classes 1..R are the line tokens under
+    either rule, so one table serves both), every other entry 0. ``scales``: one per text line, a float or None (= 1.0); ``has_prompt``:
+    which lines have a prompt. The softmax weight of line r's tokens is multiplied by w_r wherever they are visible; who sees them is the
+    row tables' matter alone. Under true CFG nothing more is needed: the negative half's image rows do not see the line classes."""
+    scales, has_prompt = list(scales), [bool(h) for h in has_prompt]
+    if len(scales) != len(has_prompt):
+        raise ValueError(f"line prompt scales: {len(scales)} entries for {len(has_prompt)} text lines")
+    lines = [i for i, h in enumerate(has_prompt) if h]
+    if len(lines) > MAX_LINE_PROMPTS:
+        raise ValueError(f"at most {MAX_LINE_PROMPTS} line prompts are supported, got {len(lines)}")
+    table = np.zeros((1, MAX_KEY_CLASSES), dtype=np.float32)
+    for r, line in enumerate(lines, start=1):
+        w = 1.0 if scales[line] is None else float(scales[line])
+        if not (math.isfinite(w) and LINE_SCALE_RANGE[0] <= w <= LINE_SCALE_RANGE[1]):
+            raise ValueError(f"line prompt scales: a scale lies in [1/64, 64], got {w}")
+        table[0, r] = np.float32(math.log(w))
+    return torch.from_numpy(table)
+
+
+def line_scale_argument(ext, line_entries, n_lines: int) -> Optional[list]:
+    """Check ``control_prompt_scale`` of a call (``LINE_SCALE_ARGUMENTS``) -> one float per text line, or None when the call does not name
+    it (``None`` names nothing). ``line_entries``: what ``line_prompt_arguments`` returned, whose refusals come first."""
+    scale = getattr(ext, "control_prompt_scale", None)
+    if scale is None:
+        return None
+    if line_entries is None:
+        raise ValueError("control_prompt_scale needs a per-line prompt (control_prompt / control_prompt_embeds): without one there is "
+                         "nothing to weigh")
+    number = lambda x: isinstance(x, (int, float)) and not isinstance(x, bool)
+    if number(scale):
+        scales = [float(scale) if e is not None else 1.0 for e in line_entries]
+    elif isinstance(scale, (list, tuple)) and len(scale) == n_lines and all(x is None or number(x) for x in scale):
+        scales = [1.0 if x is None else float(x) for x in scale]
+    else:
+        raise ValueError(f"control_prompt_scale must be a float or a list with a float or None per text line (control_image has {n_lines})")
+    for w, e in zip(scales, line_entries):
+        if not (math.isfinite(w) and LINE_SCALE_RANGE[0] <= w <= LINE_SCALE_RANGE[1]):
+            raise ValueError(f"control_prompt_scale: a scale is finite and lies in [1/64, 64] (below it the line prompt is as good as "
+                             f"hidden, above it the only text its box sees), got {w}")
+        if e is None and w != 1.0:
+            raise ValueError(f"control_prompt_scale: a text line without a prompt cannot have a scale ({w}); pass None or 1.0 for it")
+    return scales
+
+
 def line_isolation_argument(ext, line_entries) -> bool:
     """Check ``control_prompt_isolation`` of a call (``ISOLATION_ARGUMENTS``) -> whether its line prompts run under ``line_prompt_classes``."""
     on = getattr(ext, "control_prompt_isolation", False)
@@ -534,6 +606,7 @@ class LoopExtras:
     guidance: Optional[Guidance] = None
     line_prompts: Optional[LinePrompts] = None   # per-line prompts: a longer text stream and key groups for the transformer alone
     regional_ip: Optional[RegionalIP] = None     # regional image prompts; it then holds the call's own prompt too, and ip_embeds is None
+    line_scale: Optional[LineScale] = None       # control_prompt_scale: a bias per key class for the joint attention of line_prompts
     quiet: bool = False                          # no progress bar (a capture)
 
     def signature(self, sig, ident, adapter) -> tuple:
@@ -545,7 +618,8 @@ class LoopExtras:
                 + (() if self.repaint is None else self.repaint.signature(sig))
                 + (() if self.guidance is None else self.guidance.signature())
                 + (() if self.line_prompts is None else self.line_prompts.signature(sig))
-                + (() if self.regional_ip is None else (self.regional_ip.signature(sig),) + ip))
+                + (() if self.regional_ip is None else (self.regional_ip.signature(sig),) + ip)
+                + (() if self.line_scale is None else self.line_scale.signature(sig)))
 
     def tensors(self) -> Dict[str, torch.Tensor]:          # the static inputs the fields add, in the order they are cloned and refreshed
         records = [getattr(self, f.name) for f in fields(self)]      # one with static inputs of its own is known by its ``tensors`` method
@@ -1225,7 +1299,7 @@ class FluxControlNetPipeline:
         return Image.new("RGB", (size, size), (0, 0, 0))
 
     # ------------------------------------------------------------------ the call
-    @accepts_call_extensions(*IsolationCallExtensions.__dataclass_fields__)
+    @accepts_call_extensions(*LineScaleCallExtensions.__dataclass_fields__)
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 28,
@@ -1270,6 +1344,7 @@ class FluxControlNetPipeline:
         line_entries = line_prompt_arguments(ext, len(control_image) if control_image is not None else 0, control_mask,
                                              bool(getattr(self.transformer, "_fp8_attention", False)))
         isolation = line_isolation_argument(ext, line_entries)
+        line_scales = line_scale_argument(ext, line_entries, len(control_image) if control_image is not None else 0)
         positive_ip = (ext.ip_adapter_image is not None or ext.ip_adapter_image_embeds is not None
                        or "ip_adapter_image_embeds" in (joint_attention_kwargs or {}))
         regional_args = regional_ip_arguments(ext, len(control_image) if control_image is not None else 0, control_mask,
@@ -1312,7 +1387,9 @@ class FluxControlNetPipeline:
                                      prompt_embeds.dtype)
         extras = LoopExtras(ip_embeds=ip_embeds if regional is None else None, union=union, cfg_scale=float(ext.true_cfg_scale) if cfg else None,
                             repaint=repaint, guidance=loop_guidance(self.guider, cfg, len(timesteps)), line_prompts=line_prompts,
-                            regional_ip=regional)
+                            regional_ip=regional,
+                            line_scale=None if line_scales is None else LineScale(
+                                line_prompt_bias(line_scales, [e is not None for e in line_entries]).to(device)))
 
         self._apply_lora_scale()
         latents = self._denoise(latents, prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids, timesteps, hints, masks,
@@ -1623,6 +1700,8 @@ class FluxControlNetPipeline:
         joint_text = lambda pe: pe if lp is None else torch.cat([pe, lp.embeds.to(pe.dtype)], dim=1)
         text_ids_t = text_ids if lp is None else torch.zeros(prompt_embeds.shape[1] + lp.embeds.shape[1], 3, device=text_ids.device, dtype=text_ids.dtype)
         prompt_t = joint_text(prompt_embeds)
+        # control_prompt_scale: the bias table goes with the key groups, [1, 32] for every batch entry (a guider's positive half needs no view)
+        bias_kw = {} if extras.line_scale is None else dict(_key_bias=extras.line_scale.key_bias)
 
         def prepare_static(pe):
             static_t = self.transformer.prepare_static(joint_text(pe))
@@ -1763,7 +1842,7 @@ class FluxControlNetPipeline:
                     encoder_hidden_states=c_pe_t, controlnet_block_samples=merged, controlnet_single_block_samples=merged_single,
                     txt_ids=text_ids_t, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs, return_dict=False,
                     _mods=tab_t.step(i) if rows is None else tab_t.step(i, rows), _sample_events=events, _static=c_static, _ip=c_ip,
-                    **({} if c_groups is None else dict(_groups=c_groups)))[0]
+                    **({} if c_groups is None else dict(_groups=c_groups, **bias_kw)))[0]
                 if events is not None:
                     torch.cuda.current_stream().wait_stream(side)     # the tower has finished reading `latents` (its last sample is unused, Q5)
                 if extras.velocity is not None:

@@ -361,7 +361,7 @@ class FluxTransformer2DModel(_MMDiTBase):
                 controlnet_single_block_samples=None, return_dict: bool = True, controlnet_blocks_repeat: bool = False,
                 _mods: Optional["mmdit.StepMods"] = None, _sample_events: Optional[Sequence["torch.cuda.Event"]] = None,
                 _static: Optional[StaticEmbeds] = None, _ip: Optional["ip_adapter.PreparedIP"] = None,
-                _groups: Optional["ops.KeyGroups"] = None):
+                _groups: Optional["ops.KeyGroups"] = None, _key_bias: Optional[torch.Tensor] = None):
         """``joint_attention_kwargs["ip_adapter_image_embeds"]`` (as in diffusers): the image prompt of a loaded IP-Adapter, projected
         and applied in every double block — in every block, single ones included, for an InstantX adapter (ip_adapter.py); ``_ip`` (optional) = the same already prepared (``_ip_adapter.prepare``), so
         that a loop does not redo the projection per step, or a list of them (``_ip_adapter.prepare_terms``): regional image prompts, of which
@@ -369,7 +369,8 @@ class FluxTransformer2DModel(_MMDiTBase):
         ``_sample_events[k]`` (optional): event another stream records when controlnet_block_samples[k] is complete; the
         current stream waits for it right before the first block that consumes that sample. ``_static`` (optional): this
         model's loop-invariant embeddings (prepare_static) — the text rows are copied instead of recomputed. ``_groups`` (optional): an
-        ops.KeyGroups over the T + N joint rows, handed to the joint attention of every block (per-line prompts, pipeline.line_prompt_groups)."""
+        ops.KeyGroups over the T + N joint rows, handed to the joint attention of every block (per-line prompts, pipeline.line_prompt_groups); ``_key_bias``
+        (optional, with ``_groups``): fp32 [Bc or 1, 32], a bias per key group or class for the same launches (pipeline.line_prompt_bias)."""
         doubles, singles = self._ensure_plans()
         joint_attention_kwargs = dict(joint_attention_kwargs or {})          # a copy: the image prompt is popped below, as diffusers does
         ip_embeds = joint_attention_kwargs.pop("ip_adapter_image_embeds", None)
@@ -404,6 +405,8 @@ class FluxTransformer2DModel(_MMDiTBase):
             _ip = ip_list[0] if ip_list else None
         waited = set()
         gkw = {} if _groups is None else dict(groups=_groups)               # a call without key groups calls the blocks as it always did
+        if _key_bias is not None:
+            gkw["key_bias"] = _key_bias
         for i, pl in enumerate(doubles):
             inj = None
             if controlnet_block_samples is not None:

@@ -297,6 +297,26 @@ int rt_attention_fwd_keyed(const void* q, const void* k, const void* v, void* o,
                            const uint32_t* row_vis, int64_t stride_vis_b, const uint8_t* key_class, int64_t stride_class_b,
                            void* ws, int64_t ws_bytes, void* stream);
 
+/* rt_attention_fwd_grouped / rt_attention_fwd_keyed with an additive bias per key CLASS (a strength per line prompt): the logit of
+ * (row i, key j) is scale * q_i.k_j + key_bias[b][c(j)] in natural-log units, c(j) = key j's group index (grouped) or class byte
+ * (keyed); i.e. the softmax weight of every key of class c is multiplied by exp(key_bias[b][c]). key_bias: DEVICE fp32 [B][32],
+ * batch stride stride_bias_b elements (0: one table for the batch); all 32 entries of a row are read, whichever classes occur, and
+ * must be FINITE (an infinite or NaN bias is not a mask: visibility is row_vis's alone). Visibility is unchanged: a hidden key stays
+ * hidden whatever its bias, a row that sees no key gets zeros. A table of zeros gives the bits of the unbiased entry. The same
+ * constant on every class that occurs leaves the softmax what it was (up to rounding). RT_E_BADARG: a null table or a negative stride;
+ * RT_E_ALIGN: a table that is not 4-byte aligned; otherwise the sibling's contract, grid, key split and workspace (two further
+ * instantiations of csrc/attention.hip's kernel; never attention_v3). Added without an ABI bump: nothing existing changed. */
+int rt_attention_fwd_grouped_biased(const void* q, const void* k, const void* v, void* o,
+                                    int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob,
+                                    int32_t B, int32_t S, int32_t H, float scale,
+                                    const int32_t* group_end, int32_t n_groups, const uint32_t* row_vis, int64_t stride_vis_b,
+                                    void* ws, int64_t ws_bytes, void* stream, const float* key_bias, int64_t stride_bias_b);
+int rt_attention_fwd_keyed_biased(const void* q, const void* k, const void* v, void* o,
+                                  int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob,
+                                  int32_t B, int32_t S, int32_t H, float scale,
+                                  const uint32_t* row_vis, int64_t stride_vis_b, const uint8_t* key_class, int64_t stride_class_b,
+                                  void* ws, int64_t ws_bytes, void* stream, const float* key_bias, int64_t stride_bias_b);
+
 /* Which kernel serves rt_attention_fwd (speed only; both are tested against the same references): 1 (default, env RT_ATTN_V3) =
  * shapes with S % 256 == 0 and S >= 1536 run csrc/attention_v3.hip — one wave per SIMD, 64 query rows per wave, O / Q / row sums
  * in asm-owned accumulator registers, hand-placed MFMA gaps (S = 4608: 247 vs 264 us) —, everything else csrc/attention.hip;

@@ -11,7 +11,11 @@ text stream in every GEMM of the text rows.
 launch with the real table, the keyed launch with the tables of line_prompt_classes for the same two boxes (16 of the 64 image-row
 tiles hold two classes), the keyed launch with a class per group (every tile of one class) and with every key of every tile of
 another class than its neighbour (every tile mixed); the pipeline pair is the call with line prompts without and with isolation.
-Prints a table and one JSON line.  python tools/bench_line_prompts.py [--repeats 3] [--inference-steps 28] [--kernel-only] [--isolation]"""
+`--scale` measures a strength per line prompt (control_prompt_scale, rt_attention_fwd_grouped_biased / rt_attention_fwd_keyed_biased)
+instead: the kernel cases are the grouped and the keyed launch with the real tables, each without a bias and with the table of scales
+(2.0, 0.5) — 4 of the 76 key tiles carry a bias —; the pipeline pairs are the call with line prompts without and with the keyword, under
+the grouped rule and under isolation.
+Prints a table and one JSON line.  python tools/bench_line_prompts.py [--repeats 3] [--inference-steps 28] [--kernel-only] [--isolation | --scale]"""
 import argparse
 import json
 import os
@@ -36,8 +40,8 @@ def two_boxes(dev, dtype):
     return out
 
 
-def kernel_bench(dev, rounds=3, iters=10, isolation=False):
-    from reptext_amd.pipeline import line_prompt_classes, line_prompt_groups
+def kernel_bench(dev, rounds=3, iters=10, isolation=False, scale=False):
+    from reptext_amd.pipeline import line_prompt_bias, line_prompt_classes, line_prompt_groups
 
     S, d = T0 + R * L + N, H * 128
     qkv = torch.randn(1, S, 3 * d, device=dev).to(torch.bfloat16)
@@ -65,8 +69,15 @@ def kernel_bench(dev, rounds=3, iters=10, isolation=False):
         per_group = torch.bucketize(j, torch.tensor(ends), right=True).to(torch.uint8)[None]
         cases = {"grouped_real_table": grouped(real), "keyed_real_tables": keyed(*line_prompt_classes(T0, L, boxes, N)),
                  "keyed_class_per_group": keyed(real, per_group), "keyed_every_tile_mixed": keyed(torch.full_like(real, 3), (j % 2).to(torch.uint8)[None])}
+    if scale:
+        boxes = [m.cpu() for m in two_boxes("cpu", torch.float32)]
+        bias = line_prompt_bias([2.0, 0.5], [True, True]).to(dev)
+        kg, kc = ops.KeyGroups(ends, real.to(dev)), ops.KeyClasses(*line_prompt_classes(T0, L, boxes, N)).to(dev)
+        launch = lambda g, kb: lambda: ops.attention(q, k, v, out, H, groups=g, key_bias=kb)
+        cases = {"grouped_real_table": launch(kg, None), "grouped_biased": launch(kg, bias), "keyed_real_tables": launch(kc, None),
+                 "keyed_biased": launch(kc, bias)}
     for fn in cases.values():
-        for _ in range(iters if isolation else 1):                      # isolation: a window long enough for the clocks to settle
+        for _ in range(iters if isolation or scale else 1):                      # isolation: a window long enough for the clocks to settle
             fn()
     torch.cuda.synchronize()
     res = {name: [] for name in cases}
@@ -92,11 +103,14 @@ def main():
     ap.add_argument("--inference-steps", type=int, default=28)
     ap.add_argument("--kernel-only", action="store_true")
     ap.add_argument("--isolation", action="store_true")
+    ap.add_argument("--scale", action="store_true")
     args = ap.parse_args()
+    if args.isolation and args.scale:
+        raise SystemExit("--isolation and --scale are two measurements: give one")
     if not torch.cuda.is_available():
         raise SystemExit("bench_line_prompts.py measures on an MI355X; no GPU is visible")
     dev = torch.device("cuda:0")
-    result = {"tool": "bench_line_prompts", "device": torch.cuda.get_device_name(0), "kernel": kernel_bench(dev, iters=200 if args.isolation else 10, isolation=args.isolation)}
+    result = {"tool": "bench_line_prompts", "device": torch.cuda.get_device_name(0), "kernel": kernel_bench(dev, iters=200 if args.isolation or args.scale else 10, isolation=args.isolation, scale=args.scale)}
     if args.kernel_only:
         print(json.dumps(result), flush=True)
         return
@@ -123,9 +137,16 @@ def main():
     modes = {"plain_T512": dict(prompt_embeds=base), "dense_T768": dict(prompt_embeds=long_prompt),
              "line_prompts": dict(prompt_embeds=base, control_prompt_embeds=lines, control_prompt_max_sequence_length=L)}
     modes["line_isolation"] = dict(modes["line_prompts"], control_prompt_isolation=True)
+    modes["line_scale"] = dict(modes["line_prompts"], control_prompt_scale=[2.0, 0.5])
+    modes["line_isolation_scale"] = dict(modes["line_isolation"], control_prompt_scale=[2.0, 0.5])
     run = lambda m: pipe(**kw, **modes[m])
     result["pipeline"] = {"shape": "1024x1024, two text lines, batch 1", "steps": steps, "pairs": []}
-    for pair in ((("line_prompts", "line_isolation"),) if args.isolation else (("plain_T512", "line_prompts"), ("dense_T768", "line_prompts"))):
+    pairs = (("plain_T512", "line_prompts"), ("dense_T768", "line_prompts"))
+    if args.isolation:
+        pairs = (("line_prompts", "line_isolation"),)
+    if args.scale:
+        pairs = (("line_prompts", "line_scale"), ("line_isolation", "line_isolation_scale"))
+    for pair in pairs:
         pipe.__dict__.get("_graph_cache", {}).clear()                   # the pipeline keeps two graphs: each pair has the cache to itself
         for m in pair:                                                  # eager, then capture
             run(m)
@@ -143,7 +164,7 @@ def main():
         graphs = len([v for v in pipe._graph_cache.values() if isinstance(v, dict)])
         result["pipeline"]["pairs"].append({"graphs": graphs, "ms_per_step": res})
         for m in pair:
-            print(f"  ms per denoising step, {m:14s}: " + "  ".join(f"{t:.3f}" for t in res[m]) + f"   ({graphs} captured graphs)", flush=True)
+            print(f"  ms per denoising step, {m:20s}: " + "  ".join(f"{t:.3f}" for t in res[m]) + f"   ({graphs} captured graphs)", flush=True)
     print(json.dumps(result), flush=True)
 
 

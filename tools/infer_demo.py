@@ -70,6 +70,9 @@ ap.add_argument("--apg-norm-threshold", type=float, default=0.0, help="projected
 ap.add_argument("--apg-momentum", type=float, default=0.0, help="projected guidance: beta of the running difference (APG's usual value: -0.5)")
 ap.add_argument("--line-prompt", action="append", default=None, metavar="TEXT",
                 help="a prompt of its own for a text line (control_prompt=): repeatable, one per text line in order; an empty string leaves a line without one")
+ap.add_argument("--line-prompt-scale", action="append", default=None, type=float, metavar="W",
+                help="with --line-prompt: the strength of that line's prompt (control_prompt_scale), repeatable, parallel to --line-prompt; "
+                     "1 = as without it, in [1/64, 64]; a line whose --line-prompt is '' takes 1")
 ap.add_argument("--line-isolation", action="store_true",
                 help="with --line-prompt: region isolation (control_prompt_isolation=True) — a line's text reads only its own box and the boxes do not read each other")
 ap.add_argument("--source-image", default=None, help="photo to render the text into (the repaint pipeline's image=; the mask is the union of the lines' boxes)")
@@ -200,6 +203,10 @@ if a.line_prompt:
     named = lambda text: torch.randn(1, 128, 4096, generator=torch.Generator().manual_seed(zlib.crc32(text.encode("utf-8")))).to(dev, bf16)
     # no text encoders here: embeddings named by the text (control_prompt=[...] takes the strings themselves where a T5 is loaded)
     ip_kwargs.update(control_prompt_embeds=[named(t) if t else None for t in a.line_prompt], control_prompt_max_sequence_length=128)
+if a.line_prompt_scale:
+    if not a.line_prompt or len(a.line_prompt_scale) != len(a.line_prompt):
+        sys.exit(f"--line-prompt-scale: give one per --line-prompt ({len(a.line_prompt or [])}), got {len(a.line_prompt_scale)}")
+    ip_kwargs.update(control_prompt_scale=list(a.line_prompt_scale))
 if a.line_isolation:
     ip_kwargs.update(control_prompt_isolation=True)                                 # without --line-prompt the pipeline refuses it by name
 
