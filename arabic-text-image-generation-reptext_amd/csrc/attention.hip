@@ -53,6 +53,13 @@
 // whole tiles) loads, per lane, the class and the bias of key 64t + lane again and hands each score its own key's through v_readlane
 // (no LDS memory: the 64 KiB are taken), out of line. Everything it adds stands under `if constexpr (BIASED)`.
 //
+// rt_attention_fwd_keyed_self is the sixth instantiation (SELF: perturbed-attention guidance): the keyed rule, and every row also sees
+// the key of its own index. A wave's 32 query rows q0 + 32·wave .. +31 lie inside ONE key tile (q0 is a multiple of 128, a tile holds 64
+// keys), so only that tile differs, under a wave-uniform test: after the class walk each row ORs bit (row - 64t) into its 64-bit mask
+// (the row clamped as the word load is), and the tile takes the per-score path whenever a row hides part of it. Every other tile
+// executes what the keyed instantiation executes; a key-split run that sees nothing already weighs 0 in the combine. Everything it
+// adds stands under `if constexpr (SELF)`.
+//
 // LDS image of a K or V tile: 64 rows × 256 B; 16-B chunk c of row r lives at 256·r + 16·(c ^ f(r)),
 // f(r) = ((r&3)<<2) | ((r>>2)&3): conflict-free for the row reads (K) and the transposed reads (V).
 // LDS-DMA writes lane-linear, so the XOR is applied to each lane's source address.
@@ -102,12 +109,13 @@ struct KeyBias {
 struct NoBias {};
 struct KeyGroupsBiased : KeyGroups, KeyBias {};
 struct KeyClassesBiased : KeyClasses, KeyBias {};
-enum { DENSE_MODE = 0, GROUPED_MODE = 1, KEYED_MODE = 2, GROUPED_BIASED_MODE = 3, KEYED_BIASED_MODE = 4 };
+enum { DENSE_MODE = 0, GROUPED_MODE = 1, KEYED_MODE = 2, GROUPED_BIASED_MODE = 3, KEYED_BIASED_MODE = 4, KEYED_SELF_MODE = 5 };
 template <int MODE> struct MaskArg { using type = NoGroups; };
 template <> struct MaskArg<GROUPED_MODE> { using type = KeyGroups; };
 template <> struct MaskArg<KEYED_MODE> { using type = KeyClasses; };
 template <> struct MaskArg<GROUPED_BIASED_MODE> { using type = KeyGroupsBiased; };
 template <> struct MaskArg<KEYED_BIASED_MODE> { using type = KeyClassesBiased; };
+template <> struct MaskArg<KEYED_SELF_MODE> { using type = KeyClasses; };
 // Running maximum a grouped row starts with: finite, so that a hidden score (-inf) gives exp2(-inf - M0) = 0 and not exp2(NaN), and
 // so far below any score that the first visible one rescales the (all-zero) state by exp2(M0 - m) = 0.
 constexpr float GROUPED_M0 = -1.0e30f;
@@ -118,7 +126,8 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
     int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob, float scale_log2, const SplitGeom G,
     const int row_lo, const int row_hi, int* counters, char* records,
     const typename MaskArg<MODE>::type KG) {
-  constexpr bool GROUPED = MODE == GROUPED_MODE || MODE == GROUPED_BIASED_MODE, KEYED = MODE == KEYED_MODE || MODE == KEYED_BIASED_MODE;
+  constexpr bool SELF = MODE == KEYED_SELF_MODE;
+  constexpr bool GROUPED = MODE == GROUPED_MODE || MODE == GROUPED_BIASED_MODE, KEYED = MODE == KEYED_MODE || MODE == KEYED_BIASED_MODE || SELF;
   constexpr bool MASKED = MODE != DENSE_MODE, BIASED = MODE == GROUPED_BIASED_MODE || MODE == KEYED_BIASED_MODE;
   __shared__ __attribute__((aligned(16))) char smem[4 * TILE_B];   // [slot][K|V]
   const int tid = threadIdx.x;
@@ -406,6 +415,17 @@ __global__ __launch_bounds__(ATT_THREADS, 2) void attention_fwd_kernel(
           ++nclass;
         } while (rem);
         mixed = nclass > 1;
+        if constexpr (SELF) {
+          // the wave's rows q0 + 32·wave .. +31 are keys dq .. dq + 31 of the one tile with dq = 0 or 32 (wave-uniform): there a row sees
+          // its own key whatever its word says, and a row that hides the rest of a one-class tile needs the bit test per score
+          const int dq = q0 + wave * 32 - t * BKV;
+          if (dq == 0 || dq == 32) {
+            const int self = min(q0 + wave * 32 + l31, S - 1) - t * BKV;     // clamped as the word load is: a row >= S takes row S-1's key
+            if ((unsigned)self < 32u) vlo |= 1u << self;
+            else if ((unsigned)self < 64u) vhi |= 1u << (self - 32);
+            mixed = true;
+          }
+        }
         hidden = (vlo & vhi) != 0xffffffffu;     // some key of the tile is hidden from this row
         any_hidden = __any(hidden);
         vlo >>= 4 * hh;
@@ -769,6 +789,19 @@ extern "C" int rt_attention_fwd_keyed(const void* q, const void* k, const void* 
   if (!RT_ALIGNED(row_vis, 4)) return RT_E_ALIGN;
   const KeyClasses kc = {row_vis, stride_vis_b, key_class, stride_class_b};
   return launch<KEYED_MODE>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, 0, S, ws, ws_bytes, stream, kc);
+}
+
+// rt_attention_fwd_keyed with the self rule (perturbed-attention guidance): row i also sees key i. The same checks, grid, key split
+// and workspace, the self instantiation.
+extern "C" int rt_attention_fwd_keyed_self(const void* q, const void* k, const void* v, void* o, int64_t ld, int64_t stride_b, int64_t ldo,
+                                           int64_t stride_ob, int32_t B, int32_t S, int32_t H, float scale, const uint32_t* row_vis,
+                                           int64_t stride_vis_b, const uint8_t* key_class, int64_t stride_class_b, void* ws,
+                                           int64_t ws_bytes, void* stream) {
+  if (const int st = check_common(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, 0, S)) return st;
+  if (!(scale > 0.f) || !row_vis || !key_class || stride_vis_b < 0 || stride_class_b < 0) return RT_E_BADARG;
+  if (!RT_ALIGNED(row_vis, 4)) return RT_E_ALIGN;
+  const KeyClasses kc = {row_vis, stride_vis_b, key_class, stride_class_b};
+  return launch<KEYED_SELF_MODE>(q, k, v, o, ld, stride_b, ldo, stride_ob, B, S, H, scale, 0, S, ws, ws_bytes, stream, kc);
 }
 
 // rt_attention_fwd_keyed with a bias per key class: the same checks, grid, key split and workspace, the biased instantiation.

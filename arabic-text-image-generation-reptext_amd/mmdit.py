@@ -421,7 +421,8 @@ def _ip_terms(ip) -> list:
 
 def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: int, inject: Optional[torch.Tensor] = None,
                mods: Optional[tuple] = None, ip: Optional[tuple] = None, ip_inside: bool = False,
-               window: Optional[tuple] = None, groups: Optional["ops.KeyGroups"] = None, key_bias: Optional[torch.Tensor] = None) -> None:
+               window: Optional[tuple] = None, groups: Optional["ops.KeyGroups"] = None, key_bias: Optional[torch.Tensor] = None,
+               self_key: bool = False) -> None:
     """One FluxTransformerBlock on ws.x in place (A.1). ``inject`` [B,N,d] bf16 is added to the image rows after the
     block (A.3 ControlNet residual), fused into the last GEMM's epilogue. ``mods`` = precomputed (image, text) adaLN
     vectors for this step (ModulationTable); computed here from ``temb`` when absent. ``ip`` = (K, V, scale) of an IP-Adapter
@@ -439,12 +440,18 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
     block changes. ``ip`` may also be a sequence of (K, V, scale, row_weights) terms, regional image prompts (ip_adapter.py): the
     first takes the slot the single term takes, each further one accumulates into the same place with one more rounding, in order;
     ``row_weights`` (fp32 [B or 1, N], or None) is the per-row weight of ops.ip_attention_gated. ``key_bias`` (only with ``groups``):
-    ops.attention's bias per key group or class, the biased launch in place of the grouped or keyed one."""
+    ops.attention's bias per key group or class, the biased launch in place of the grouped or keyed one. ``self_key`` (only with
+    ``groups`` as an ops.KeyClasses): ops.attention's self rule, row i also sees key i (perturbed-attention guidance)."""
     T, d = ws.T, ws.d
     terms = _ip_terms(ip)
     ip = terms or None
     if key_bias is not None and groups is None:
         raise ValueError("run_double: key_bias needs key groups")
+    if self_key and groups is None:
+        raise ValueError("run_double: self_key needs key groups")
+    akw = dict(key_bias=key_bias) if key_bias is not None else {}
+    if self_key:
+        akw["self_key"] = True
     if groups is not None and (pl.fp8_attention or window is not None):
         raise ValueError("run_double: key groups need the bf16 attention kernel and the whole block (no e4m3 attention, no window)")
     if window is not None:
@@ -480,7 +487,7 @@ def run_double(pl: DoublePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
         # 4.-5. RMSNorm(q,k) + RoPE in place; 6. joint attention; output over q
         if not fused_rope:
             ops.qk_rmsnorm_rope(ws.qkv, 0, d, H, T, pl.nq_txt, pl.nk_txt, pl.nq_img, pl.nk_img, cos, sin)
-        ops.attention(q, k, v, q, H, groups=groups, **({} if key_bias is None else dict(key_bias=key_bias)))
+        ops.attention(q, k, v, q, H, groups=groups, **akw)
     # 7./8. x += gate_msa * out_proj(attn)
     _act_linear(ws, pl.level, q, ws.x, [(img, pl.out_img, dict(gate=_ch(mi, 2, d), res=x_i)),
                                         (txt, pl.out_txt, dict(gate=_ch(mt, 2, d), res=x_t))], fresh=0 if attn_mx else d)
@@ -515,19 +522,24 @@ def _run_double_window(pl: DoublePlan, ws: Workspace, temb, cos, sin, H: int, mo
 
 def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: int, inject: Optional[torch.Tensor] = None,
                mods: Optional[torch.Tensor] = None, ip: Optional[tuple] = None, groups: Optional["ops.KeyGroups"] = None,
-               key_bias: Optional[torch.Tensor] = None) -> None:
+               key_bias: Optional[torch.Tensor] = None, self_key: bool = False) -> None:
     """One FluxSingleTransformerBlock on ws.x in place (A.2). ``ip`` = (K, V, scale) of an InstantX IP-Adapter (ip_adapter.py):
     scale · softmax(q Kᵀ/√128) V from the query of ALL S rows after norm_q and before RoPE, added to the attention output before
     proj_out. The raw q only exists between the fused GEMM and norm + RoPE and attention overwrites it, so the term waits in a bf16
     [B,S,d] buffer and one strided add puts it over q's columns after attention. Wherever the attention output would skip bf16 (the
     "mx" level with e4m3 attention) such a block takes the bf16-output attention call and the quantise pass instead. With ``ip=None``
-    the launch sequence is unchanged. ``groups``, ``key_bias``: as in run_double. ``ip`` may also be a sequence of (K, V, scale, row_weights)
+    the launch sequence is unchanged. ``groups``, ``key_bias``, ``self_key``: as in run_double. ``ip`` may also be a sequence of (K, V, scale, row_weights)
     terms as in run_double, with ``row_weights`` over all S rows: the first writes the buffer, the others accumulate into it."""
     T, d = ws.T, ws.d
     terms = _ip_terms(ip)
     ip = terms or None
     if key_bias is not None and groups is None:
         raise ValueError("run_single: key_bias needs key groups")
+    if self_key and groups is None:
+        raise ValueError("run_single: self_key needs key groups")
+    akw = dict(key_bias=key_bias) if key_bias is not None else {}
+    if self_key:
+        akw["self_key"] = True
     if groups is not None and pl.fp8_attention:
         raise ValueError("run_single: key groups need the bf16 attention kernel (the e4m3 attention has no mask)")
     if mods is not None:
@@ -556,7 +568,7 @@ def run_single(pl: SinglePlan, ws: Workspace, temb: torch.Tensor, cos, sin, H: i
     else:
         if not fused_rope:
             ops.qk_rmsnorm_rope(big, 2 * d, 0, H, 0, None, None, pl.nq, pl.nk, cos, sin)
-        ops.attention(q, big[..., :d], big[..., d : 2 * d], q, H, groups=groups, **({} if key_bias is None else dict(key_bias=key_bias)))
+        ops.attention(q, big[..., :d], big[..., d : 2 * d], q, H, groups=groups, **akw)
     if ip is not None:
         ops.add_bf16_(q, ip_out)
     _act_linear(ws, pl.level, big[..., 2 * d :], ws.x, [(rows, pl.out, dict(gate=_ch(m, 2, d), res=ws.x))], fresh=0 if attn_mx else d)

@@ -587,7 +587,7 @@ def _key_bias(kb, B: int, device) -> Tuple[int, int]:
 
 def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tensor, H: int, scale: Optional[float] = None,
               split: bool = True, rows: Optional[tuple] = None, groups: Optional[Union[KeyGroups, KeyClasses]] = None,
-              key_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+              key_bias: Optional[torch.Tensor] = None, self_key: bool = False) -> torch.Tensor:
     """q,k,v [B,S,H*128] views (common strides) of one buffer; out [B,S,H*128] view (may alias q). ``split=False`` runs every
     128-row block as one full-length workgroup (no key-split tail; A/B and tests). ``rows`` = (r0, r1): only the items of the launch that
     hold a query row of [r0, r1) do any work (rt_attention_fwd_rows): those rows of out get the bits the whole launch gives them, the
@@ -595,13 +595,18 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
     ``rows``): region-masked attention, rt_attention_fwd_grouped — hidden keys must still hold finite values; a KeyClasses in its
     place: visibility per key, rt_attention_fwd_keyed. ``key_bias`` (only with ``groups``): float32 [B or 1, 32] on q's device, added
     to the logits (natural-log units) of the keys of group / class c — the softmax weight of those keys times exp(key_bias[b, c]); finite
-    values; visibility is unchanged (rt_attention_fwd_grouped_biased / rt_attention_fwd_keyed_biased). None: the unbiased entries."""
+    values; visibility is unchanged (rt_attention_fwd_grouped_biased / rt_attention_fwd_keyed_biased). None: the unbiased entries.
+    ``self_key=True`` (only with a KeyClasses, without ``rows`` and ``key_bias``): row i also sees key i whatever its word says,
+    rt_attention_fwd_keyed_self (perturbed-attention guidance)."""
     (B, S, _, ld, sb), _, _, (_, _, _, ldo, sob) = [_rows3(t, name, width=H * 128) for name, t in (("q", q), ("k", k), ("v", v), ("out", out))]
     if not (q.stride() == k.stride() == v.stride()) or k.shape != q.shape or v.shape != q.shape or out.shape != q.shape:
         raise ValueError("q,k,v must share shape and strides")
     sc = (128 ** -0.5) if scale is None else float(scale)
     if key_bias is not None and groups is None:
         raise ValueError("attention: key_bias= needs groups= (a bias per key group or class)")
+    if self_key and (not isinstance(groups, KeyClasses) or rows is not None or key_bias is not None):
+        raise ValueError("attention: self_key=True needs groups= as a KeyClasses (the self rule belongs to the per-key launch), "
+                         "without rows= and key_bias=")
     if groups is not None:
         if rows is not None:
             raise ValueError("attention: rows= and groups= cannot be combined")
@@ -616,7 +621,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, out: torch.Tens
                             ld, sb, ldo, sob, B, S, H, sc, vis, svb, cls, scb, None if ws is None else ws.data_ptr(),
                             0 if ws is None else ws.numel(), _stream(), *bias)
                 return out
-            native.call("rt_attention_fwd_keyed", _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(out, "out", BF16), ld,
+            native.call("rt_attention_fwd_keyed_self" if self_key else "rt_attention_fwd_keyed", _dev(q, "q", BF16), _dev(k, "k", BF16), _dev(v, "v", BF16), _dev(out, "out", BF16), ld,
                         sb, ldo, sob, B, S, H, sc, vis, svb, cls, scb, None if ws is None else ws.data_ptr(),
                         0 if ws is None else ws.numel(), _stream())
             return out

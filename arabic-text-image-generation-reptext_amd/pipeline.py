@@ -227,6 +227,17 @@ class LineScaleCallExtensions(IsolationCallExtensions):
     control_prompt_scale: Any = None                    # a float for every line prompt, or one float or None per text line; None: 1.0
 
 
+PAG_ARGUMENTS = ("pag_scale", "pag_applied_layers")
+
+
+@dataclass
+class PerturbedCallExtensions(LineScaleCallExtensions):
+    """``LineScaleCallExtensions`` of a call that names a keyword of perturbed-attention guidance (``PAG_ARGUMENTS``).
+    ``accepts_call_extensions`` builds it only for such a call."""
+    pag_scale: float = 0.0                              # PAG is on iff > 0: v = v_cond + pag_scale · (v_cond − v_perturbed)
+    pag_applied_layers: Any = None                      # the blocks whose attention is perturbed, by diffusers module name (``pag_layers``)
+
+
 def accepts_call_extensions(*names):
     """``__call__`` keeps the reference's parameter list (PIPE:751-781, which ``inspect.signature`` still reports). The fields of
     ``CallExtensions`` in ``names`` are keyword-only extensions of it, taken off here and left on the pipeline, as passed, as
@@ -243,6 +254,8 @@ def accepts_call_extensions(*names):
                 record = IsolationCallExtensions
             if any(k in LINE_SCALE_ARGUMENTS for k in taken):
                 record = LineScaleCallExtensions
+            if any(k in PAG_ARGUMENTS for k in taken):
+                record = PerturbedCallExtensions
             self._call_extensions = record(**taken)
             try:
                 return call(self, *args, **kwargs)
@@ -463,6 +476,90 @@ def line_scale_argument(ext, line_entries, n_lines: int) -> Optional[list]:
     return scales
 
 
+@dataclass(frozen=True)
+class Perturbed(_StaticFields):
+    """Perturbed-attention guidance of a call (``pag_scale``): at a guided step the conditioning batch is [perturbed,
+    positive], and the joint attention of the double blocks ``double_ids`` and the single blocks ``single_ids`` of the transformer runs
+    per key under the tables of ``perturbed_attention_tables`` with the self rule (``ops.attention(self_key=True)``). Every other block,
+    the towers, and a guider's unguided steps (the positive half alone, at batch B) run without tables. Two static inputs of a captured loop."""
+    row_vis: torch.Tensor               # int32 [2B, T + N]
+    key_class: torch.Tensor             # uint8 [1, T + N]
+    double_ids: frozenset
+    single_ids: frozenset
+    STATIC = {"pag_row_vis": "row_vis", "pag_key_class": "key_class"}
+
+    def groups(self) -> "ops.KeyClasses":
+        return ops.KeyClasses(self.row_vis, self.key_class)
+
+    def signature(self, sig) -> tuple:
+        layers = tuple([f"transformer_blocks.{i}" for i in sorted(self.double_ids)]
+                       + [f"single_transformer_blocks.{i}" for i in sorted(self.single_ids)])
+        return (("pag", layers, sig(self.row_vis), sig(self.key_class)),)
+
+
+def pag_layers(names, n_double: int, n_single: int) -> Tuple[frozenset, frozenset]:
+    """``pag_applied_layers`` -> (indices of the double blocks, indices of the single blocks). ``names``: a list of the models' diffusers
+    module names, ``"transformer_blocks.<i>"`` with i < ``n_double`` and ``"single_transformer_blocks.<i>"`` with i < ``n_single``.
+    Anything else, an index out of range, a duplicate and an empty list raise ``ValueError``. There is no default set: which blocks
+    are good ones can only be measured with a real checkpoint."""
+    if isinstance(names, str) or not isinstance(names, (list, tuple)):
+        raise ValueError("pag_applied_layers must be a list of block names such as 'transformer_blocks.8'")
+    if len(names) == 0:
+        raise ValueError("pag_applied_layers is empty: name at least one block (there is no default set)")
+    found = {"transformer_blocks": set(), "single_transformer_blocks": set()}
+    limit = {"transformer_blocks": int(n_double), "single_transformer_blocks": int(n_single)}
+    for name in names:
+        kind, dot, index = name.rpartition(".") if isinstance(name, str) else ("", "", "")
+        if kind not in found or not dot or not (index.isascii() and index.isdigit()) or str(int(index)) != index:
+            raise ValueError(f"pag_applied_layers: {name!r} is neither 'transformer_blocks.<i>' nor 'single_transformer_blocks.<i>'")
+        i = int(index)
+        if i >= limit[kind]:
+            raise ValueError(f"pag_applied_layers: {name!r} is out of range, the model has {limit[kind]} {kind}")
+        if i in found[kind]:
+            raise ValueError(f"pag_applied_layers: {name!r} is named twice")
+        found[kind].add(i)
+    return frozenset(found["transformer_blocks"]), frozenset(found["single_transformer_blocks"])
+
+
+def perturbed_attention_tables(T: int, N: int, batch: int = 1) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The visibility contract of perturbed-attention guidance, from host values alone -> (row_vis int32 [2·batch, T + N], key_class uint8
+    [1, T + N]) for the launch with the self rule (``ops.attention(self_key=True)``). Key classes: 0 = the T text keys, 1 = the N image
+    keys. Entries [0, batch) are the perturbed half: a text row sees both classes (0b11), an image row class 0 alone (0b01) — the text
+    keys, and its own key through the self rule. Entries [batch, 2·batch) are the positive half: every row 0b11. This is diffusers'
+    ``PAGJointAttnProcessor2_0`` (recalled) restated for text rows first."""
+    T, N, batch = int(T), int(N), int(batch)
+    if T < 0 or N < 0 or T + N < 1 or batch < 1:
+        raise ValueError(f"perturbed attention tables: need token counts >= 0 with a row in all and a batch >= 1, got T={T}, N={N}, batch={batch}")
+    key_class = np.zeros((1, T + N), dtype=np.uint8)
+    key_class[0, T:] = 1
+    row_vis = np.full((2 * batch, T + N), 0b11, dtype=np.uint32)
+    row_vis[:batch, T:] = 0b01
+    return torch.from_numpy(row_vis.view(np.int32)), torch.from_numpy(key_class)
+
+
+def pag_arguments(ext, transformer, cfg: bool) -> Optional[tuple]:
+    """Check ``pag_scale`` / ``pag_applied_layers`` of a call (``PAG_ARGUMENTS``), host values only -> (1 + pag_scale formed in double,
+    double block indices, single block indices), or None when PAG is off (``pag_scale`` 0: layers that are named are still checked).
+    ``cfg``: the call runs true CFG."""
+    scale, layers = getattr(ext, "pag_scale", 0.0), getattr(ext, "pag_applied_layers", None)
+    if isinstance(scale, bool) or not isinstance(scale, (int, float)) or not math.isfinite(scale) or scale < 0:
+        raise ValueError(f"pag_scale must be a finite number >= 0, got {scale!r}")
+    ids = None if layers is None else pag_layers(layers, len(transformer.transformer_blocks), len(transformer.single_transformer_blocks))
+    if not scale > 0:
+        return None
+    if ids is None:
+        raise ValueError("pag_scale > 0 needs pag_applied_layers: name the blocks whose attention is perturbed (there is no default set)")
+    if cfg:
+        raise ValueError("pag_scale cannot be combined with a negative prompt (true CFG): the three-way batch is not supported")
+    named = [k for k in LINE_PROMPT_ARGUMENTS[:2] + ("control_prompt_scale", "control_ip_adapter_image", "control_ip_adapter_image_embeds")
+             if getattr(ext, k, None) is not None] + (["control_prompt_isolation"] if getattr(ext, "control_prompt_isolation", False) else [])
+    if named:
+        raise ValueError(f"pag_scale cannot be combined with per-line prompts ({', '.join(named)}): one set of tables per attention launch")
+    if getattr(transformer, "_fp8_attention", False):
+        raise ValueError("pag_scale needs the bf16 attention kernel: the e4m3 attention (enable_fp8_attention) has no mask")
+    return 1.0 + float(scale), ids[0], ids[1]
+
+
 def line_isolation_argument(ext, line_entries) -> bool:
     """Check ``control_prompt_isolation`` of a call (``ISOLATION_ARGUMENTS``) -> whether its line prompts run under ``line_prompt_classes``."""
     on = getattr(ext, "control_prompt_isolation", False)
@@ -606,6 +703,9 @@ class LoopExtras:
     guidance: Optional[Guidance] = None
     line_prompts: Optional[LinePrompts] = None   # per-line prompts: a longer text stream and key groups for the transformer alone
     regional_ip: Optional[RegionalIP] = None     # regional image prompts; it then holds the call's own prompt too, and ip_embeds is None
+    # pag_scale: cfg_scale is 1 + pag_scale and the first half of the conditioning batch is the positive one under the perturbed tables
+    # (never together with line_prompts / line_scale; its key part is the last)
+    perturbed: Optional[Perturbed] = None
     line_scale: Optional[LineScale] = None       # control_prompt_scale: a bias per key class for the joint attention of line_prompts
     quiet: bool = False                          # no progress bar (a capture)
 
@@ -619,7 +719,8 @@ class LoopExtras:
                 + (() if self.guidance is None else self.guidance.signature())
                 + (() if self.line_prompts is None else self.line_prompts.signature(sig))
                 + (() if self.regional_ip is None else (self.regional_ip.signature(sig),) + ip)
-                + (() if self.line_scale is None else self.line_scale.signature(sig)))
+                + (() if self.line_scale is None else self.line_scale.signature(sig))
+                + (() if self.perturbed is None else self.perturbed.signature(sig)))
 
     def tensors(self) -> Dict[str, torch.Tensor]:          # the static inputs the fields add, in the order they are cloned and refreshed
         records = [getattr(self, f.name) for f in fields(self)]      # one with static inputs of its own is known by its ``tensors`` method
@@ -1299,7 +1400,7 @@ class FluxControlNetPipeline:
         return Image.new("RGB", (size, size), (0, 0, 0))
 
     # ------------------------------------------------------------------ the call
-    @accepts_call_extensions(*LineScaleCallExtensions.__dataclass_fields__)
+    @accepts_call_extensions(*PerturbedCallExtensions.__dataclass_fields__)
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 28,
@@ -1341,6 +1442,9 @@ class FluxControlNetPipeline:
         ext = self._call_extensions
         with_union = self._check_union_inputs(ext.control_image_union, height, width, total)
         cfg = self._check_true_cfg_inputs(ext, prompt_embeds, pooled_prompt_embeds, batch_size, joint_attention_kwargs)
+        # perturbed-attention guidance: prepared as a true-CFG call whose first half is the positive conditioning itself (``Perturbed``)
+        pag = pag_arguments(ext, self.transformer, cfg)
+        true_cfg, cfg = cfg, cfg or pag is not None
         line_entries = line_prompt_arguments(ext, len(control_image) if control_image is not None else 0, control_mask,
                                              bool(getattr(self.transformer, "_fp8_attention", False)))
         isolation = line_isolation_argument(ext, line_entries)
@@ -1354,7 +1458,7 @@ class FluxControlNetPipeline:
         if cfg and ip_embeds is not None:
             # [2·total, E], negative first like the prompt: rt_ip_attention takes K/V per entry of the conditioning batch
             pos = ip_embeds.expand(total, -1)
-            ip_embeds = torch.cat([self._negative_ip_embeds(ext, pos, total, device), pos], dim=0).contiguous()
+            ip_embeds = torch.cat([self._negative_ip_embeds(ext, pos, total, device) if true_cfg else pos, pos], dim=0).contiguous()
 
         prompt_embeds, pooled_prompt_embeds, text_ids = self.encode_prompt(
             prompt=prompt, prompt_2=prompt_2, prompt_embeds=prompt_embeds, pooled_prompt_embeds=pooled_prompt_embeds, device=device,
@@ -1365,7 +1469,7 @@ class FluxControlNetPipeline:
             # True CFG: the conditioning batch is cat([negative, positive]) (negative first, INP:1034-1035) against latents of batch B;
             # the models repeat the latents over it, and the step mixes the two halves of the velocity (LoopExtras.cfg_scale)
             npe, npooled = self._encode_negative_prompt(ext, prompt_embeds, pooled_prompt_embeds, batch_size, num_images_per_prompt,
-                                                        max_sequence_length, device)
+                                                        max_sequence_length, device) if true_cfg else (prompt_embeds, pooled_prompt_embeds)
             prompt_embeds = torch.cat([npe, prompt_embeds], dim=0)
             pooled_prompt_embeds = torch.cat([npooled, pooled_prompt_embeds], dim=0)
 
@@ -1385,11 +1489,17 @@ class FluxControlNetPipeline:
         union = UnionTower(self.controlnet_union, union_hint, float(ext.controlnet_conditioning_scale_union), active) if active else None
         regional = self._regional_ip(regional_args, ip_embeds, region, latents.shape[1], total, num_images_per_prompt, cfg, device,
                                      prompt_embeds.dtype)
-        extras = LoopExtras(ip_embeds=ip_embeds if regional is None else None, union=union, cfg_scale=float(ext.true_cfg_scale) if cfg else None,
+        perturbed = None
+        if pag is not None:
+            row_vis, key_class = perturbed_attention_tables(prompt_embeds.shape[1], latents.shape[1], total)
+            perturbed = Perturbed(row_vis.to(device), key_class.to(device), pag[1], pag[2])
+        cfg_scale = (float(ext.true_cfg_scale) if true_cfg else pag[0]) if cfg else None
+        extras = LoopExtras(ip_embeds=ip_embeds if regional is None else None, union=union, cfg_scale=cfg_scale,
                             repaint=repaint, guidance=loop_guidance(self.guider, cfg, len(timesteps)), line_prompts=line_prompts,
                             regional_ip=regional,
                             line_scale=None if line_scales is None else LineScale(
-                                line_prompt_bias(line_scales, [e is not None for e in line_entries]).to(device)))
+                                line_prompt_bias(line_scales, [e is not None for e in line_entries]).to(device)),
+                            perturbed=perturbed)
 
         self._apply_lora_scale()
         latents = self._denoise(latents, prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids, timesteps, hints, masks,
@@ -1702,6 +1812,8 @@ class FluxControlNetPipeline:
         prompt_t = joint_text(prompt_embeds)
         # control_prompt_scale: the bias table goes with the key groups, [1, 32] for every batch entry (a guider's positive half needs no view)
         bias_kw = {} if extras.line_scale is None else dict(_key_bias=extras.line_scale.key_bias)
+        # pag_scale: the tables go to the guided steps' forward at 2B; a guider's unguided step runs the positive half without any
+        pag_kw = {} if extras.perturbed is None else dict(_perturbed=extras.perturbed)
 
         def prepare_static(pe):
             static_t = self.transformer.prepare_static(joint_text(pe))
@@ -1842,7 +1954,7 @@ class FluxControlNetPipeline:
                     encoder_hidden_states=c_pe_t, controlnet_block_samples=merged, controlnet_single_block_samples=merged_single,
                     txt_ids=text_ids_t, img_ids=image_ids, joint_attention_kwargs=self.joint_attention_kwargs, return_dict=False,
                     _mods=tab_t.step(i) if rows is None else tab_t.step(i, rows), _sample_events=events, _static=c_static, _ip=c_ip,
-                    **({} if c_groups is None else dict(_groups=c_groups, **bias_kw)))[0]
+                    **({} if c_groups is None else dict(_groups=c_groups, **bias_kw)), **(pag_kw if guided else {}))[0]
                 if events is not None:
                     torch.cuda.current_stream().wait_stream(side)     # the tower has finished reading `latents` (its last sample is unused, Q5)
                 if extras.velocity is not None:

@@ -21,7 +21,8 @@ import torch.nn.functional as F
 from . import ops
 from .image_processor import PipelineImageInput, VaeImageProcessor
 from .pipeline import FluxControlNetPipeline as _BasePipeline
-from .pipeline import ISOLATION_ARGUMENTS, LINE_PROMPT_ARGUMENTS, LINE_SCALE_ARGUMENTS, REGIONAL_IP_ARGUMENTS, LoopExtras, accepts_call_extensions
+from .pipeline import (ISOLATION_ARGUMENTS, LINE_PROMPT_ARGUMENTS, LINE_SCALE_ARGUMENTS, PAG_ARGUMENTS, REGIONAL_IP_ARGUMENTS, LoopExtras,
+                       accepts_call_extensions)
 
 DEFAULT_NEGATIVE_PROMPT = "bad quality, worst quality, text, signature, watermark, extra words"     # INP:416
 
@@ -85,7 +86,7 @@ class FluxControlNetPipeline(_BasePipeline):
 
     # ------------------------------------------------------------------ INP:846-1313
     @accepts_call_extensions("ip_adapter_image", "ip_adapter_image_embeds", *LINE_PROMPT_ARGUMENTS, *REGIONAL_IP_ARGUMENTS,
-                             *ISOLATION_ARGUMENTS, *LINE_SCALE_ARGUMENTS)      # taken only to be refused by name below
+                             *ISOLATION_ARGUMENTS, *LINE_SCALE_ARGUMENTS, *PAG_ARGUMENTS)      # taken only to be refused by name below
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  true_guidance_scale: float = 3.5, negative_prompt: Optional[Union[str, List[str]]] = None,
@@ -128,6 +129,8 @@ class FluxControlNetPipeline(_BasePipeline):
             raise ValueError("the inpaint pipeline does not support per-line prompts (control_prompt_isolation)")
         if getattr(ext, "control_prompt_scale", None) is not None:
             raise ValueError("the inpaint pipeline does not support per-line prompts (control_prompt_scale)")
+        if getattr(ext, "pag_scale", 0.0) or getattr(ext, "pag_applied_layers", None) is not None:
+            raise ValueError("the inpaint pipeline does not support perturbed-attention guidance (pag_scale / pag_applied_layers)")
         self._guidance_scale, self._joint_attention_kwargs, self._interrupt = guidance_scale, joint_attention_kwargs, False
         cfg = self.do_classifier_free_guidance                          # enabled by guidance_scale > 1, scaled by true_guidance_scale (Q8)
         device, dtype = self._execution_device, self.transformer.dtype

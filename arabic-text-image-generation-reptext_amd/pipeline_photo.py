@@ -27,7 +27,7 @@ from PIL import Image
 
 from . import native, ops
 from .image_processor import PipelineImageInput
-from .pipeline import LineScaleCallExtensions, FluxPipelineOutput, accepts_call_extensions
+from .pipeline import PerturbedCallExtensions, FluxPipelineOutput, accepts_call_extensions
 from .pipeline_repaint import FluxControlNetRepaintPipeline, RepaintArguments
 
 MASK_THRESHOLD = 128            # a uint8 mask value counts as "repaint" from here on: x/255 >= 0.5
@@ -188,7 +188,7 @@ class FluxControlNetPhotoPipeline(FluxControlNetRepaintPipeline):
             raise ValueError(f"the region {cw}x{ch} and the working size {width}x{height} differ by more than a factor of {limit}")
         return photo, mask, region, cond
 
-    @accepts_call_extensions(*LineScaleCallExtensions.__dataclass_fields__)
+    @accepts_call_extensions(*PerturbedCallExtensions.__dataclass_fields__)
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 28,

@@ -24,7 +24,7 @@ from PIL import Image
 
 from . import ops
 from .image_processor import PipelineImageInput, VaeImageProcessor
-from .pipeline import LineScaleCallExtensions, FluxControlNetPipeline, Repaint, accepts_call_extensions
+from .pipeline import PerturbedCallExtensions, FluxControlNetPipeline, Repaint, accepts_call_extensions
 
 
 def repaint_t_start(num_inference_steps: int, strength: float) -> int:
@@ -149,7 +149,7 @@ class FluxControlNetRepaintPipeline(FluxControlNetPipeline):
         channels = self.transformer.config.in_channels // 4
         return self._pack_latents(m.repeat(1, channels, 1, 1), m.shape[0], channels, grid[0], grid[1]).contiguous()
 
-    @accepts_call_extensions(*LineScaleCallExtensions.__dataclass_fields__)
+    @accepts_call_extensions(*PerturbedCallExtensions.__dataclass_fields__)
     @torch.no_grad()
     def __call__(self, prompt: Union[str, List[str]] = None, prompt_2: Optional[Union[str, List[str]]] = None,
                  height: Optional[int] = None, width: Optional[int] = None, num_inference_steps: int = 28,

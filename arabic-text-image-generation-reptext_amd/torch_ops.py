@@ -83,9 +83,10 @@ def enable_dispatch(on: bool = True) -> None:
         ops.linear = linear
         # the registered op is the whole dense launch with the key split; a launch without it, for a range of rows or with key groups goes
         # straight to ctypes
-        ops.attention = lambda q, k, v, out, H, scale=None, split=True, rows=None, groups=None, key_bias=None: (
-            t.attention(q, k, v, out, H, 0.0 if scale is None else float(scale)) if split and rows is None and groups is None and key_bias is None
-            else _direct["attention"](q, k, v, out, H, scale, split=split, rows=rows, groups=groups, key_bias=key_bias)) or out
+        ops.attention = lambda q, k, v, out, H, scale=None, split=True, rows=None, groups=None, key_bias=None, self_key=False: (
+            t.attention(q, k, v, out, H, 0.0 if scale is None else float(scale))
+            if split and rows is None and groups is None and key_bias is None and not self_key
+            else _direct["attention"](q, k, v, out, H, scale, split=split, rows=rows, groups=groups, key_bias=key_bias, self_key=self_key)) or out
         ops.layernorm_modulate = lambda x, out, shift, scale, eps=1e-6: t.layernorm_modulate(x, out, shift, scale, eps) or out
         ops.qk_rmsnorm_rope = lambda buf, q_off, k_off, H, T, a, b, c, d, cos, sin, eps=1e-6: t.qk_rmsnorm_rope(buf, q_off, k_off, H, T, a, b, c, d, cos, sin, eps)
     else:

@@ -361,7 +361,7 @@ class FluxTransformer2DModel(_MMDiTBase):
                 controlnet_single_block_samples=None, return_dict: bool = True, controlnet_blocks_repeat: bool = False,
                 _mods: Optional["mmdit.StepMods"] = None, _sample_events: Optional[Sequence["torch.cuda.Event"]] = None,
                 _static: Optional[StaticEmbeds] = None, _ip: Optional["ip_adapter.PreparedIP"] = None,
-                _groups: Optional["ops.KeyGroups"] = None, _key_bias: Optional[torch.Tensor] = None):
+                _groups: Optional["ops.KeyGroups"] = None, _key_bias: Optional[torch.Tensor] = None, _perturbed=None):
         """``joint_attention_kwargs["ip_adapter_image_embeds"]`` (as in diffusers): the image prompt of a loaded IP-Adapter, projected
         and applied in every double block — in every block, single ones included, for an InstantX adapter (ip_adapter.py); ``_ip`` (optional) = the same already prepared (``_ip_adapter.prepare``), so
         that a loop does not redo the projection per step, or a list of them (``_ip_adapter.prepare_terms``): regional image prompts, of which
@@ -370,7 +370,10 @@ class FluxTransformer2DModel(_MMDiTBase):
         current stream waits for it right before the first block that consumes that sample. ``_static`` (optional): this
         model's loop-invariant embeddings (prepare_static) — the text rows are copied instead of recomputed. ``_groups`` (optional): an
         ops.KeyGroups over the T + N joint rows, handed to the joint attention of every block (per-line prompts, pipeline.line_prompt_groups); ``_key_bias``
-        (optional, with ``_groups``): fp32 [Bc or 1, 32], a bias per key group or class for the same launches (pipeline.line_prompt_bias)."""
+        (optional, with ``_groups``): fp32 [Bc or 1, 32], a bias per key group or class for the same launches (pipeline.line_prompt_bias).
+        ``_perturbed`` (optional, not with ``_groups``): a pipeline.Perturbed — perturbed-attention guidance: the double blocks in its
+        ``double_ids`` and the single blocks in its ``single_ids`` alone run their joint attention under its tables with the self rule
+        (ops.attention(self_key=True)); every other block is called as without it."""
         doubles, singles = self._ensure_plans()
         joint_attention_kwargs = dict(joint_attention_kwargs or {})          # a copy: the image prompt is popped below, as diffusers does
         ip_embeds = joint_attention_kwargs.pop("ip_adapter_image_embeds", None)
@@ -407,6 +410,12 @@ class FluxTransformer2DModel(_MMDiTBase):
         gkw = {} if _groups is None else dict(groups=_groups)               # a call without key groups calls the blocks as it always did
         if _key_bias is not None:
             gkw["key_bias"] = _key_bias
+        pkw, p_double, p_single = {}, frozenset(), frozenset()
+        if _perturbed is not None:
+            if _groups is not None:
+                raise ValueError("_perturbed and _groups cannot be combined (one set of tables per attention launch)")
+            pkw = dict(groups=_perturbed.groups(), self_key=True)
+            p_double, p_single = _perturbed.double_ids, _perturbed.single_ids
         for i, pl in enumerate(doubles):
             inj = None
             if controlnet_block_samples is not None:
@@ -420,7 +429,7 @@ class FluxTransformer2DModel(_MMDiTBase):
             if ip_list is not None:
                 ip = [t for p in ip_list for t in p.block_terms(i)] or None
             mmdit.run_double(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.double[i], ip=ip,
-                             ip_inside=_ip is not None and _ip.inside, **gkw)
+                             ip_inside=_ip is not None and _ip.inside, **(pkw if i in p_double else gkw))
         for i, pl in enumerate(singles):
             inj = None
             if controlnet_single_block_samples is not None:
@@ -430,7 +439,8 @@ class FluxTransformer2DModel(_MMDiTBase):
                 ip = (*_ip.kv[nl + i], _ip.scales[nl + i])
             if ip_list is not None and _ip is not None and _ip.inside:
                 ip = [t for p in ip_list for t in p.block_terms(nl + i, single=True)] or None
-            mmdit.run_single(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.single[i], ip=ip, **gkw)
+            mmdit.run_single(pl, ws, temb, cos, sin, H, inject=inj, mods=None if _mods is None else _mods.single[i], ip=ip,
+                             **(pkw if i in p_single else gkw))
         # AdaLayerNormContinuous: chunk order (scale, shift)  — A.3
         if _mods is not None:
             m = _mods.out

@@ -297,6 +297,17 @@ int rt_attention_fwd_keyed(const void* q, const void* k, const void* v, void* o,
                            const uint32_t* row_vis, int64_t stride_vis_b, const uint8_t* key_class, int64_t stride_class_b,
                            void* ws, int64_t ws_bytes, void* stream);
 
+/* rt_attention_fwd_keyed with a self rule (perturbed-attention guidance): row i of entry b sees key j iff bit key_class[b][j] of
+ * row_vis[b][i] is set OR j == i. The self rule holds for every row and costs nothing for a row that sees its own class anyway; with
+ * every word 0 each row sees its own key alone and the output is v. A row always sees a key, so no row gets zeros. Arguments,
+ * refusals, grid, key split and workspace are rt_attention_fwd_keyed's (one more instantiation of csrc/attention.hip's kernel; never
+ * attention_v3). Added without an ABI bump: nothing existing changed. */
+int rt_attention_fwd_keyed_self(const void* q, const void* k, const void* v, void* o,
+                                int64_t ld, int64_t stride_b, int64_t ldo, int64_t stride_ob,
+                                int32_t B, int32_t S, int32_t H, float scale,
+                                const uint32_t* row_vis, int64_t stride_vis_b, const uint8_t* key_class, int64_t stride_class_b,
+                                void* ws, int64_t ws_bytes, void* stream);
+
 /* rt_attention_fwd_grouped / rt_attention_fwd_keyed with an additive bias per key CLASS (a strength per line prompt): the logit of
  * (row i, key j) is scale * q_i.k_j + key_bias[b][c(j)] in natural-log units, c(j) = key j's group index (grouped) or class byte
  * (keyed); i.e. the softmax weight of every key of class c is multiplied by exp(key_bias[b][c]). key_bias: DEVICE fp32 [B][32],

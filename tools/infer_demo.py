@@ -21,6 +21,10 @@ encoders, which sit outside the hot path. With real checkpoints on disk use `Flu
                                --apg-momentum -0.5   # a guider on the true-CFG call (pipe.guider): the negative half is evaluated on the first
                                               # half of the steps only (the others run at batch 1), and at those steps the guidance is projected
                                               # (APG); the four flags have an effect only with --negative-prompt
+    python tools/infer_demo.py --pag-scale 3.0 --pag-layer transformer_blocks.8 [--pag-layer single_transformer_blocks.0]   # perturbed-attention
+                                              # guidance, which needs no negative prompt: internal batch 2, [perturbed, positive]; in the named
+                                              # blocks an image token of the first half reads the text and itself only; there is no default layer
+                                              # set; --guidance-interval and the --apg flags apply as they do to --negative-prompt
     python tools/infer_demo.py --source-image photo.jpg [--strength 0.6]   # repaint: the two lines are rendered INTO the photo by latent-blend
                                               # inpainting (FluxControlNetRepaintPipeline): the last strength·steps steps from the noised
                                               # photo, the photo put back outside the lines' boxes after every step; no second tower, no CFG
@@ -73,6 +77,9 @@ ap.add_argument("--line-prompt", action="append", default=None, metavar="TEXT",
 ap.add_argument("--line-prompt-scale", action="append", default=None, type=float, metavar="W",
                 help="with --line-prompt: the strength of that line's prompt (control_prompt_scale), repeatable, parallel to --line-prompt; "
                      "1 = as without it, in [1/64, 64]; a line whose --line-prompt is '' takes 1")
+ap.add_argument("--pag-scale", type=float, default=0.0, help="perturbed-attention guidance (pag_scale): on iff > 0, needs --pag-layer; not with --negative-prompt or --line-prompt")
+ap.add_argument("--pag-layer", action="append", default=None, metavar="NAME",
+                help="a block whose attention is perturbed (pag_applied_layers), repeatable: transformer_blocks.<i> or single_transformer_blocks.<i>")
 ap.add_argument("--line-isolation", action="store_true",
                 help="with --line-prompt: region isolation (control_prompt_isolation=True) — a line's text reads only its own box and the boxes do not read each other")
 ap.add_argument("--source-image", default=None, help="photo to render the text into (the repaint pipeline's image=; the mask is the union of the lines' boxes)")
@@ -209,6 +216,9 @@ if a.line_prompt_scale:
     ip_kwargs.update(control_prompt_scale=list(a.line_prompt_scale))
 if a.line_isolation:
     ip_kwargs.update(control_prompt_isolation=True)                                 # without --line-prompt the pipeline refuses it by name
+
+if a.pag_scale or a.pag_layer:
+    ip_kwargs.update(pag_scale=a.pag_scale, pag_applied_layers=a.pag_layer)         # the pipeline refuses a scale without layers by name
 
 if a.source_image:
     from PIL import Image
