@@ -2,6 +2,7 @@
 // timestep/RoPE tables, Euler step, latent pack/unpack, casts. All loads/stores are 8–16 B per lane,
 // statistics in fp32. Math per SURVEY.md Appendix A.1/A.2/A.5/A.6 and PIPE:550-570,1109.
 #include "rt_common.h"
+#include "philox.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -355,16 +356,37 @@ __device__ __forceinline__ float repaint_blend(float r, float src, float noise, 
 // positive prediction p, s is s − 1, and k (the norm clamp) and e = (η − 1)·α are the sample's two scalars:
 //   v = p + (s − 1)·(k·d + e·p)
 // With d = 0 (u == p) k = 1 and e = 0, so v = p + (s − 1)·0 = p: the plain step on p, the same bits.
-template <bool CFG, bool REPAINT, bool MULTI, bool PROJ = false>
+// STOCH (stochastic sampling, rt_stochastic_step_f32 / rt_projected_stochastic_step_f32): the predicted clean image re-noised to the
+// next sigma with a fresh standard normal z (philox.h), in the Euler rule's place:
+//   x0 = x − σ·v;   ê = x0 + v (only where η < 1);   n = η < 1 ? c·ê + η·z : z,  c = sqrt(1 − η²);   r = (1 − σn)·x0 + σn·n
+// σn = 0 (the last step) gives r = x0 and z is never drawn: the branch is uniform, sn is a kernel scalar. Contraction off, every
+// product and sum rounded once: the 16-byte and the one-element path cannot differ by what the compiler fuses in either.
+struct stoch_args {
+  float sigma = 0.0f, eta = 1.0f, c = 0.0f;
+  uint32_t step = 0;
+  int64_t seed = 0, sub = 0;
+};
+__device__ __forceinline__ float stochastic_rule(float x, float v, float z, float sigma, float sn, float eta, float c) {
+#pragma clang fp contract(off)
+  const float x0 = x - sigma * v;
+  if (sn == 0.0f) return x0;
+  float n = z;
+  if (eta < 1.0f) n = c * (x0 + v) + eta * z;
+  return (1.0f - sn) * x0 + sn * n;
+}
+
+template <bool CFG, bool REPAINT, bool MULTI, bool PROJ = false, bool STOCH = false>
 __device__ __forceinline__ float master_step_element(float x, float u, float t, float src, float noise, float m, float s, float ds,
-                                                     float sn, float w, float& h, float k = 1.0f, float e = 0.0f) {
+                                                     float sn, float w, float& h, float k = 1.0f, float e = 0.0f, float z = 0.0f,
+                                                     const stoch_args& st = stoch_args()) {
+  static_assert(!(STOCH && MULTI), "the history of a re-noised state is not a velocity of the same trajectory");
   const float v = PROJ ? t + s * (k * u + e * t) : CFG ? u + s * (t - u) : u;
   float v2 = v;
   if (MULTI) {
     if (w != 0.0f) v2 = v + w * (v - h);
     h = v;
   }
-  const float r = x + ds * v2;
+  const float r = STOCH ? stochastic_rule(x, v, z, st.sigma, sn, st.eta, st.c) : x + ds * v2;
   return REPAINT ? repaint_blend(r, src, noise, m, sn) : r;
 }
 
@@ -374,12 +396,15 @@ __device__ __forceinline__ float master_step_element(float x, float u, float t, 
 // REPAINT, hist only under MULTI (read where w != 0, always written), in the groups and by the tail rules of x.
 // The one text of both kernels below. Under PROJ the pointers are those of one sample (n = n_s), d is its guidance difference (u is
 // not read), mbase its first element's flat index for the mask's rule, and tid / nthr count over the x dimension of the grid.
-template <bool CFG, bool REPAINT, bool MULTI, bool PROJ>
+// Under STOCH the pointers are one sample's too (the index inside the sample is the Philox counter), and z is drawn per group — by
+// the tail per element, from the element's group — unless sn == 0.
+template <bool CFG, bool REPAINT, bool MULTI, bool PROJ, bool STOCH = false>
 __device__ __forceinline__ void master_step_body(float* __restrict__ x, const bf16_t* __restrict__ u, const bf16_t* __restrict__ t,
                                                  bf16_t* __restrict__ xb, const float* __restrict__ src, const float* __restrict__ noise,
                                                  const float* __restrict__ mask, float* __restrict__ hist, float s, float ds, float sn,
                                                  float w, int64_t n, int64_t n_mask, int64_t n4, int64_t tid, int64_t nthr,
-                                                 const float* __restrict__ d, int64_t mbase, float k, float e) {
+                                                 const float* __restrict__ d, int64_t mbase, float k, float e,
+                                                 const stoch_args& st = stoch_args()) {
   for (int64_t g = tid; g < n4; g += nthr) {
     const f32x4 xv = reinterpret_cast<const f32x4*>(x)[g];
     u32x2 uv, tv;
@@ -396,16 +421,18 @@ __device__ __forceinline__ void master_step_body(float* __restrict__ x, const bf
     if (REPAINT) {
       sv = reinterpret_cast<const f32x4*>(src)[g];
       nv = reinterpret_cast<const f32x4*>(noise)[g];
-      mv = *reinterpret_cast<const f32x4*>(mask + (PROJ ? (mbase + g * 4) % n_mask : (g * 4) % n_mask));
+      mv = *reinterpret_cast<const f32x4*>(mask + (PROJ || STOCH ? (mbase + g * 4) % n_mask : (g * 4) % n_mask));
     }
     if (MULTI && w != 0.0f) hv = reinterpret_cast<const f32x4*>(hist)[g];
+    float zv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (STOCH && sn != 0.0f) philox_normal4(philox_group(st.seed, st.sub, st.step, (uint64_t)g), zv);
     f32x4 o;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float a = PROJ ? dv[j] : (j & 1) ? bf16hi(uv[j >> 1]) : bf16lo(uv[j >> 1]);
       const float b = (j & 1) ? bf16hi(tv[j >> 1]) : bf16lo(tv[j >> 1]);
       float h = hv[j];
-      o[j] = master_step_element<CFG, REPAINT, MULTI, PROJ>(xv[j], a, b, sv[j], nv[j], mv[j], s, ds, sn, w, h, k, e);
+      o[j] = master_step_element<CFG, REPAINT, MULTI, PROJ, STOCH>(xv[j], a, b, sv[j], nv[j], mv[j], s, ds, sn, w, h, k, e, zv[j], st);
       hv[j] = h;
     }
     reinterpret_cast<f32x4*>(x)[g] = o;
@@ -417,9 +444,11 @@ __device__ __forceinline__ void master_step_body(float* __restrict__ x, const bf
     if (PROJ) { a = d[i]; b = bf16_to_f32(t[i]); }
     else { a = bf16_to_f32(u[i]); b = CFG ? bf16_to_f32(t[i]) : a; }
     float sv = 0.0f, nv = 0.0f, mv = 0.0f, h = 0.0f;
-    if (REPAINT) { sv = src[i]; nv = noise[i]; mv = mask[PROJ ? (mbase + i) % n_mask : i % n_mask]; }
+    if (REPAINT) { sv = src[i]; nv = noise[i]; mv = mask[PROJ || STOCH ? (mbase + i) % n_mask : i % n_mask]; }
     if (MULTI && w != 0.0f) h = hist[i];
-    const float o = master_step_element<CFG, REPAINT, MULTI, PROJ>(x[i], a, b, sv, nv, mv, s, ds, sn, w, h, k, e);
+    float z = 0.0f;
+    if (STOCH && sn != 0.0f) z = philox_normal_lane(philox_group(st.seed, st.sub, st.step, (uint64_t)(i >> 2)), (int)(i & 3));
+    const float o = master_step_element<CFG, REPAINT, MULTI, PROJ, STOCH>(x[i], a, b, sv, nv, mv, s, ds, sn, w, h, k, e, z, st);
     x[i] = o;
     if (xb) xb[i] = f32_to_bf16(o);
     if (MULTI) hist[i] = h;
@@ -434,6 +463,42 @@ __global__ void master_step_f32_kernel(float* __restrict__ x, const bf16_t* __re
   const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
   master_step_body<CFG, REPAINT, MULTI, false>(x, u, t, xb, src, noise, mask, hist, s, ds, sn, w, n, n_mask, n4, tid, nthr, nullptr, 0,
                                                1.0f, 0.0f);
+}
+
+// The stochastic forms: grid (x, B), the pointers of sample blockIdx.y, whose (seed, subsequence) is row blockIdx.y of rng — read
+// only where a z is drawn (sn != 0), so the last step never touches it.
+__device__ __forceinline__ stoch_args stoch_args_of(const int64_t* __restrict__ rng, float sigma, float sn, float eta, float c, uint32_t step) {
+  stoch_args st;
+  st.sigma = sigma; st.eta = eta; st.c = c; st.step = step;
+  if (sn != 0.0f) { st.seed = rng[2 * (int64_t)blockIdx.y]; st.sub = rng[2 * (int64_t)blockIdx.y + 1]; }
+  return st;
+}
+
+template <bool CFG, bool REPAINT>
+__global__ void stochastic_step_f32_kernel(float* __restrict__ x, const bf16_t* __restrict__ u, const bf16_t* __restrict__ t,
+                                           bf16_t* __restrict__ xb, const float* __restrict__ src, const float* __restrict__ noise,
+                                           const float* __restrict__ mask, const int64_t* __restrict__ rng, float s, float sigma, float sn,
+                                           float eta, float c, uint32_t step, int64_t n_s, int64_t n_mask, int64_t n4) {
+  const stoch_args st = stoch_args_of(rng, sigma, sn, eta, c, step);
+  const int64_t base = (int64_t)blockIdx.y * n_s;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  master_step_body<CFG, REPAINT, false, false, true>(x + base, u + base, CFG ? t + base : nullptr, xb ? xb + base : nullptr,
+                                                     REPAINT ? src + base : nullptr, REPAINT ? noise + base : nullptr, mask, nullptr, s, 0.0f,
+                                                     sn, 0.0f, n_s, n_mask, n4, tid, nthr, nullptr, base, 1.0f, 0.0f, st);
+}
+
+// out[b][i] = the z the stochastic step draws for element i of sample b at ``step``: the same two paths, the same bits
+__global__ void normal_fill_f32_kernel(float* __restrict__ out, const int64_t* __restrict__ rng, uint32_t step, int64_t n_s, int64_t n4) {
+  const int64_t seed = rng[2 * (int64_t)blockIdx.y], sub = rng[2 * (int64_t)blockIdx.y + 1];
+  out += (int64_t)blockIdx.y * n_s;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t g = tid; g < n4; g += nthr) {
+    float z[4];
+    philox_normal4(philox_group(seed, sub, step, (uint64_t)g), z);
+    reinterpret_cast<f32x4*>(out)[g] = f32x4{z[0], z[1], z[2], z[3]};
+  }
+  for (int64_t i = n4 * 4 + tid; i < n_s; i += nthr)
+    out[i] = philox_normal_lane(philox_group(seed, sub, step, (uint64_t)(i >> 2)), (int)(i & 3));
 }
 
 // ---- projected guidance: per-sample sums, then the master step with the projected velocity (reptext_hip.h) --------------------------
@@ -513,6 +578,27 @@ __global__ void projected_step_f32_kernel(float* __restrict__ x, const bf16_t* _
   master_step_body<false, REPAINT, MULTI, true>(x + base, nullptr, t + base, xb ? xb + base : nullptr, REPAINT ? src + base : nullptr,
                                                 REPAINT ? noise + base : nullptr, mask, MULTI ? hist + base : nullptr, s1, ds, sn, w,
                                                 n_s, n_mask, n4, tid, nthr, diff + base, base, k, e);
+}
+
+// The projected step's stochastic form: the same prologue, then the STOCH body (no history).
+template <bool REPAINT>
+__global__ void projected_stochastic_step_f32_kernel(float* __restrict__ x, const bf16_t* __restrict__ t, bf16_t* __restrict__ xb,
+                                                     const float* __restrict__ diff, const float* __restrict__ partials, int nparts, float s1,
+                                                     float eta_g, float tau, const float* __restrict__ src, const float* __restrict__ noise,
+                                                     const float* __restrict__ mask, const int64_t* __restrict__ rng, float sigma, float sn,
+                                                     float eta, float c, uint32_t step, int64_t n_s, int64_t n_mask, int64_t n4) {
+  const float* part = partials + (int64_t)blockIdx.y * nparts * 3;
+  double a = 0.0, b = 0.0, cc = 0.0;
+  for (int j = 0; j < nparts; ++j) { a += (double)part[3 * j]; b += (double)part[3 * j + 1]; cc += (double)part[3 * j + 2]; }
+  const double kd = (tau > 0.0f && a > (double)tau * (double)tau) ? (double)tau / sqrt(a) : 1.0;
+  const double alpha = cc > 0.0 ? kd * b / cc : 0.0;
+  const float k = (float)kd, e = (float)(((double)eta_g - 1.0) * alpha);
+  const stoch_args st = stoch_args_of(rng, sigma, sn, eta, c, step);
+  const int64_t base = (int64_t)blockIdx.y * n_s;
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nthr = (int64_t)gridDim.x * blockDim.x;
+  master_step_body<false, REPAINT, false, true, true>(x + base, nullptr, t + base, xb ? xb + base : nullptr, REPAINT ? src + base : nullptr,
+                                                      REPAINT ? noise + base : nullptr, mask, nullptr, s1, 0.0f, sn, 0.0f, n_s, n_mask, n4, tid,
+                                                      nthr, diff + base, base, k, e, st);
 }
 
 __global__ void cfg_mix_kernel(const bf16_t* __restrict__ u, const bf16_t* __restrict__ t, bf16_t* __restrict__ o,
@@ -914,6 +1000,54 @@ int rt_projected_step_f32(float* x, const void* v_uncond, const void* v_text, vo
   hipLaunchKernelGGL(kernel, dim3(grid_for(n4 > 0 ? n4 : n_s, 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream, x,
                      (const bf16_t*)v_text, (bf16_t*)x_bf16, diff, partials, (int)chunks, s_minus_1, eta, tau, src, noise, mask, hist, dsigma,
                      sigma_next, w, n_s, n_mask, n4);
+  return rt_hip_status();
+}
+
+// The 16-byte path of the stochastic forms: as above, and n_s % 4 == 0 — a group is one Philox call, so none may straddle two samples.
+static bool stochastic_vec(const float* x, const void* v, const void* v_text, const void* x_bf16, const float* src, const float* noise,
+                           const float* mask, int32_t B, int64_t n_s, int64_t n_mask) {
+  return n_s % 4 == 0 && RT_ALIGNED(x, 16) && (!v || RT_ALIGNED(v, 8)) && (!v_text || RT_ALIGNED(v_text, 8)) && (!x_bf16 || RT_ALIGNED(x_bf16, 8)) &&
+         (!mask || ((n_mask % 4 == 0 || n_mask == (int64_t)B * n_s) && RT_ALIGNED(src, 16) && RT_ALIGNED(noise, 16) && RT_ALIGNED(mask, 16)));
+}
+
+int rt_stochastic_step_f32(float* x, const void* v, const void* v_text, void* x_bf16, const float* src, const float* noise, const float* mask,
+                           const int64_t* rng, float s, float sigma, float sigma_next, float eta, float sqrt_1m_eta2, int32_t step, int32_t B,
+                           int64_t n_s, int64_t n_mask, void* stream) {
+  if (!x || !v || B < 1 || n_s < 1 || n_mask < 1 || (mask && (!src || !noise)) || (!rng && sigma_next != 0.0f)) return RT_E_BADARG;
+  if (!(eta > 0.0f && eta <= 1.0f) || step < 0) return RT_E_BADARG;
+  if (B > 65535 || ((int64_t)B * n_s) % n_mask) return RT_E_SHAPE;
+  const int64_t n4 = stochastic_vec(x, v, v_text, x_bf16, src, noise, mask, B, n_s, n_mask) ? n_s / 4 : 0;
+  const auto kernel = mask ? (v_text ? stochastic_step_f32_kernel<true, true> : stochastic_step_f32_kernel<false, true>)
+                           : (v_text ? stochastic_step_f32_kernel<true, false> : stochastic_step_f32_kernel<false, false>);
+  hipLaunchKernelGGL(kernel, dim3(grid_for(n4 > 0 ? n4 : n_s, 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)v,
+                     (const bf16_t*)v_text, (bf16_t*)x_bf16, src, noise, mask, rng, s, sigma, sigma_next, eta, sqrt_1m_eta2, (uint32_t)step, n_s, n_mask, n4);
+  return rt_hip_status();
+}
+
+int rt_projected_stochastic_step_f32(float* x, const void* v_uncond, const void* v_text, void* x_bf16, const float* diff, const float* partials,
+                                     float s_minus_1, float eta_guidance, float tau, const float* src, const float* noise, const float* mask,
+                                     const int64_t* rng, float sigma, float sigma_next, float eta, float sqrt_1m_eta2, int32_t step, int32_t B,
+                                     int64_t n_s, int64_t n_mask, void* stream) {
+  if (!x || !v_uncond || !v_text || !diff || !partials || B < 1 || n_s < 1 || n_mask < 1 || (mask && (!src || !noise)) ||
+      (!rng && sigma_next != 0.0f))
+    return RT_E_BADARG;
+  if (!(eta > 0.0f && eta <= 1.0f) || step < 0) return RT_E_BADARG;
+  const int64_t chunks = (n_s + RT_GUIDE_CHUNK - 1) / RT_GUIDE_CHUNK;
+  if (B > 65535 || chunks > 0x7fffffff || ((int64_t)B * n_s) % n_mask) return RT_E_SHAPE;
+  const int64_t n4 = stochastic_vec(x, nullptr, v_text, x_bf16, src, noise, mask, B, n_s, n_mask) && RT_ALIGNED(diff, 16) ? n_s / 4 : 0;
+  const auto kernel = mask ? projected_stochastic_step_f32_kernel<true> : projected_stochastic_step_f32_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3(grid_for(n4 > 0 ? n4 : n_s, 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream, x, (const bf16_t*)v_text,
+                     (bf16_t*)x_bf16, diff, partials, (int)chunks, s_minus_1, eta_guidance, tau, src, noise, mask, rng, sigma, sigma_next, eta,
+                     sqrt_1m_eta2, (uint32_t)step, n_s, n_mask, n4);
+  return rt_hip_status();
+}
+
+int rt_normal_fill_f32(float* out, const int64_t* rng, int32_t B, int64_t n_s, int32_t step, void* stream) {
+  if (!out || !rng || B < 1 || n_s < 1 || step < 0) return RT_E_BADARG;
+  if (B > 65535) return RT_E_SHAPE;
+  const int64_t n4 = n_s % 4 == 0 && RT_ALIGNED(out, 16) ? n_s / 4 : 0;
+  hipLaunchKernelGGL(normal_fill_f32_kernel, dim3(grid_for(n4 > 0 ? n4 : n_s, 256), (unsigned)B), dim3(256), 0, (hipStream_t)stream, out, rng,
+                     (uint32_t)step, n_s, n4);
   return rt_hip_status();
 }
 

@@ -836,13 +836,23 @@ def _check_master_step(name: str, x32: torch.Tensor, like, x_bf16: Optional[torc
 def _master_step_f32(name: str, x32: torch.Tensor, v: torch.Tensor, v_text: Optional[torch.Tensor], s: float, dsigma: float,
                      x_bf16: Optional[torch.Tensor], sigma_next: float = 0.0, src32: Optional[torch.Tensor] = None,
                      noise32: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, hist: Optional[torch.Tensor] = None,
-                     w: float = 0.0) -> torch.Tensor:
-    """The body of euler_step_f32_ / cfg_euler_step_f32_ / repaint_euler_step_f32_ / multistep_step_f32_ (``name``, for the messages):
-    the checks, and the entry that what is given selects. One fp32 master step x32 += dsigma·vel, vel = v or v + s·(v_text − v); with a
-    mask, the blend; with ``hist`` (the fp32 velocity of the step before, replaced by this step's), vel + w·(vel − hist) in vel's place."""
+                     w: float = 0.0, stochastic: Optional[StochasticArgs] = None) -> torch.Tensor:
+    """The body of euler_step_f32_ / cfg_euler_step_f32_ / repaint_euler_step_f32_ / multistep_step_f32_ / stochastic_step_f32_
+    (``name``, for the messages): the checks, and the entry that what is given selects. One fp32 master step x32 += dsigma·vel,
+    vel = v or v + s·(v_text − v); with a mask, the blend; with ``hist`` (the fp32 velocity of the step before, replaced by this
+    step's), vel + w·(vel − hist) in vel's place; with ``stochastic``, its rule in the Euler rule's place (``dsigma`` is then unused)."""
     _check_master_step(name, x32, (v, v_text, hist), x_bf16, src32, noise32, mask)
+    if stochastic is not None:
+        if hist is not None:
+            raise ValueError(f"{name}: the stochastic step keeps no history (solver order 1 only)")
+        B, n_s = _stochastic_batch(name, x32, stochastic, sigma_next)
     x, xb, n = _dev(x32, "x32", F32), _opt(x_bf16, "x_bf16", BF16), x32.numel()
-    if hist is not None:
+    if stochastic is not None:
+        native.call("rt_stochastic_step_f32", x, _dev(v, "v", BF16), _opt(v_text, "v_text", BF16), xb,
+                    _opt(src32 if mask is not None else None, "src32", F32), _opt(noise32 if mask is not None else None, "noise32", F32),
+                    _opt(mask, "mask", F32), _opt(stochastic.rng, "rng", torch.int64), float(s), *stochastic.scalars(sigma_next), B, n_s,
+                    n if mask is None else mask.numel(), _stream())
+    elif hist is not None:
         native.call("rt_multistep_step_f32", x, _dev(v, "v", BF16), _opt(v_text, "v_text", BF16), xb, _dev(hist, "hist", F32), float(w),
                     _opt(src32 if mask is not None else None, "src32", F32), _opt(noise32 if mask is not None else None, "noise32", F32),
                     _opt(mask, "mask", F32), float(s), float(dsigma), float(sigma_next), n, n if mask is None else mask.numel(), _stream())
@@ -854,6 +864,63 @@ def _master_step_f32(name: str, x32: torch.Tensor, v: torch.Tensor, v_text: Opti
     else:
         native.call("rt_euler_step_f32", x, _dev(v, "v", BF16), xb, float(dsigma), n, _stream())
     return x32
+
+
+@dataclass(frozen=True)
+class StochasticArgs:
+    """What the stochastic form of the master step takes besides the step's own arguments (rt_stochastic_step_f32): ``rng`` int64
+    [B, 2] on the state's device, (seed, subsequence) per sample — None is allowed where sigma_next is 0, the kernel then draws
+    nothing; ``sigma`` the step's sigma, ``eta`` in (0, 1] and ``sqrt_1m_eta2`` = sqrt(1 − eta²) formed by the caller in double,
+    ``step`` the absolute step index (the Philox counter's third word)."""
+    rng: Optional[torch.Tensor]
+    sigma: float
+    eta: float
+    sqrt_1m_eta2: float
+    step: int
+
+    def scalars(self, sigma_next: float) -> tuple:
+        return float(self.sigma), float(sigma_next), float(self.eta), float(self.sqrt_1m_eta2), int(self.step)
+
+
+def _stochastic_batch(name: str, x32: torch.Tensor, st: StochasticArgs, sigma_next: float) -> Tuple[int, int]:
+    """(B, n_s) of a state whose leading dimension is the batch, after the checks of ``st``."""
+    if x32.dim() < 2 or x32.numel() < 1:
+        raise ValueError(f"{name}: the stochastic step needs a leading batch dimension and at least one element, got shape {tuple(x32.shape)}")
+    if not 0.0 < float(st.eta) <= 1.0:
+        raise ValueError(f"{name}: eta must lie in (0, 1], got {st.eta}")
+    if int(st.step) < 0:
+        raise ValueError(f"{name}: step must not be negative, got {st.step}")
+    B = x32.shape[0]
+    if st.rng is None:
+        if float(sigma_next) != 0.0:
+            raise ValueError(f"{name}: rng is needed unless sigma_next is 0")
+    elif st.rng.dtype != torch.int64 or tuple(st.rng.shape) != (B, 2) or not st.rng.is_contiguous() or st.rng.device != x32.device:
+        raise ValueError(f"{name}: rng must be a contiguous int64 [{B}, 2] tensor on the state's device, got {tuple(st.rng.shape)} {st.rng.dtype}")
+    return B, x32.numel() // B
+
+
+def normal_fill_f32(rng: torch.Tensor, n_s: int, step: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """fp32 [B, n_s]: the standard normals the stochastic step draws at ``step`` for samples whose (seed, subsequence) are the rows of
+    ``rng`` (int64 [B, 2], on the GPU) — rt_normal_fill_f32, the same bits. ``out``: written in place (any shape of B·n_s elements)."""
+    if rng.dtype != torch.int64 or rng.dim() != 2 or rng.shape[1] != 2 or not rng.is_contiguous():
+        raise ValueError(f"normal_fill_f32: rng must be a contiguous int64 [B, 2] tensor, got {tuple(rng.shape)} {rng.dtype}")
+    B = rng.shape[0]
+    if out is None:
+        out = torch.empty(B, int(n_s), device=rng.device, dtype=F32)
+    elif out.dtype != F32 or out.numel() != B * int(n_s) or not out.is_contiguous() or out.device != rng.device:
+        raise ValueError("normal_fill_f32: out must be a contiguous fp32 tensor of B·n_s elements on rng's device")
+    native.call("rt_normal_fill_f32", _dev(out, "out", F32), _dev(rng, "rng", torch.int64), B, int(n_s), int(step), _stream())
+    return out
+
+
+def stochastic_step_f32_(x32: torch.Tensor, v: torch.Tensor, stochastic: StochasticArgs, sigma_next: float,
+                         x_bf16: Optional[torch.Tensor] = None, *, v_text: Optional[torch.Tensor] = None, s: float = 0.0,
+                         src32: Optional[torch.Tensor] = None, noise32: Optional[torch.Tensor] = None,
+                         mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The stochastic form of the fp32 master step: x0 = x32 − sigma·vel re-noised to sigma_next with noise drawn inside the kernel,
+    x32 = (1 − sigma_next)·x0 + sigma_next·n, n = z at eta = 1 and sqrt(1 − eta²)·(x0 + vel) + eta·z below; vel, the blend under
+    ``mask`` and the bf16 copy as in the steps above. x32's leading dimension is the batch."""
+    return _master_step_f32("stochastic_step_f32_", x32, v, v_text, s, 0.0, x_bf16, sigma_next, src32, noise32, mask, stochastic=stochastic)
 
 
 def euler_step_f32_(x32: torch.Tensor, v: torch.Tensor, dsigma: float, x_bf16: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -892,13 +959,15 @@ def guidance_partials_shape(B: int, n_s: int) -> Tuple[int, int, int]:
 def projected_step_f32_(x32: torch.Tensor, v_uncond: torch.Tensor, v_text: torch.Tensor, diff32: torch.Tensor, partials: torch.Tensor, s: float,
                         eta: float, norm_threshold: float, beta: float, dsigma: float, x_bf16: Optional[torch.Tensor] = None, *,
                         hist32: Optional[torch.Tensor] = None, w: float = 0.0, sigma_next: float = 0.0, src32: Optional[torch.Tensor] = None,
-                        noise32: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+                        noise32: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                        stochastic: Optional[StochasticArgs] = None) -> torch.Tensor:
     """The fp32 master step with projected guidance (guidance.py), two launches: rt_guidance_reduce_f32 — diff32 = (v_text − v_uncond)
     + beta·diff32 in fp32 and, per sample and chunk, the partial sums of (d², d·p, p²) in a fixed order — then the step with
     vel = p + (s − 1)·(k·d + e·p) in the mixed velocity's place — the multistep part (``hist32``, ``w``), the blend under ``mask`` and
     the bf16 copy as in the other steps. ``diff32`` (fp32, x32's shape) and ``partials`` are the caller's; ``beta`` is the momentum, 0
     for the first guided step of a run: diff32 is then written and not read, it may be uninitialised. x32's leading dimension is the
-    batch: the sums are per sample."""
+    batch: the sums are per sample. ``stochastic``: the stochastic rule in the Euler rule's place (rt_projected_stochastic_step_f32; no
+    history, ``dsigma`` unused)."""
     name = "projected_step_f32_"
     if x32.dim() < 2 or x32.numel() < 1:
         raise ValueError(f"{name}: the state needs a leading batch dimension and at least one element, got shape {tuple(x32.shape)}")
@@ -906,11 +975,20 @@ def projected_step_f32_(x32: torch.Tensor, v_uncond: torch.Tensor, v_text: torch
     B, n_s = x32.shape[0], x32.numel() // x32.shape[0]
     if tuple(partials.shape) != guidance_partials_shape(B, n_s):
         raise ValueError(f"{name}: partials must be {guidance_partials_shape(B, n_s)} (guidance_partials_shape), got {tuple(partials.shape)}")
+    if stochastic is not None:
+        if hist32 is not None:
+            raise ValueError(f"{name}: the stochastic step keeps no history (solver order 1 only)")
+        _stochastic_batch(name, x32, stochastic, sigma_next)
     x, xb = _dev(x32, "x32", F32), _opt(x_bf16, "x_bf16", BF16)
     pu, pt, pd, pp = _dev(v_uncond, "v_uncond", BF16), _dev(v_text, "v_text", BF16), _dev(diff32, "diff32", F32), _dev(partials, "partials", F32)
     rest = (_opt(hist32, "hist32", F32), float(w), _opt(src32 if mask is not None else None, "src32", F32),
             _opt(noise32 if mask is not None else None, "noise32", F32), _opt(mask, "mask", F32))
     native.call("rt_guidance_reduce_f32", pu, pt, pd, float(beta), pp, B, n_s, _stream())
+    if stochastic is not None:
+        native.call("rt_projected_stochastic_step_f32", x, pu, pt, xb, pd, pp, float(s) - 1.0, float(eta), float(norm_threshold), *rest[2:],
+                    _opt(stochastic.rng, "rng", torch.int64), *stochastic.scalars(sigma_next), B, n_s,
+                    x32.numel() if mask is None else mask.numel(), _stream())
+        return x32
     native.call("rt_projected_step_f32", x, pu, pt, xb, pd, pp, float(s) - 1.0, float(eta), float(norm_threshold), *rest, float(dsigma),
                 float(sigma_next), B, n_s, x32.numel() if mask is None else mask.numel(), _stream())
     return x32

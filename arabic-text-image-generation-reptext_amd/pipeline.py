@@ -30,7 +30,7 @@ from . import ops
 from .controlnet import FluxControlNetModel, FluxMultiControlNetModel, active_row_window
 from .image_processor import PipelineImageInput, VaeImageProcessor
 from .guidance import Guidance, ProjectedStep, loop_guidance
-from .scheduler import FlowMatchEulerDiscreteScheduler, FlowMatchMultistepScheduler, calculate_shift
+from .scheduler import STOCHASTIC_DEFAULTS, FlowMatchEulerDiscreteScheduler, FlowMatchMultistepScheduler, calculate_shift
 from .transformer import FluxTransformer2DModel
 from .utils import randn_tensor
 from .vae import AutoencoderKL
@@ -297,6 +297,31 @@ class Repaint(_StaticFields):
 
     def signature(self, sig) -> tuple:
         return (("repaint", sig(self.src32), sig(self.noise32), sig(self.mask)),)
+
+
+@dataclass(frozen=True)
+class StepNoise(_StaticFields):
+    """The noise streams of a call under stochastic sampling: ``rng`` int64 [B, 2], (seed, subsequence) per sample of the latents' batch
+    (``stochastic_rng``). A static input of a captured loop: another seed replays the same graph, which bakes the step index per node."""
+    rng: torch.Tensor
+    STATIC = {"step_noise_rng": "rng"}
+
+
+def stochastic_rng(generator, batch: int) -> torch.Tensor:
+    """int64 [batch, 2] on the CPU: (seed, subsequence) of every sample's noise stream (csrc/philox.h). A list of generators, one per
+    sample: ``(g_b.initial_seed(), 0)``, so sample b of a batch draws what a call of its own with ``g_b`` draws. One generator:
+    ``(initial_seed(), b)``. None: one draw from torch's default CPU generator is the seed, with subsequence b. A generator that is
+    given is read, never advanced. Seeds are taken modulo 2^64 into the int64's bits."""
+    wrap = lambda seed: ((int(seed) + (1 << 63)) % (1 << 64)) - (1 << 63)
+    batch = int(batch)
+    if isinstance(generator, (list, tuple)):
+        if len(generator) != batch:
+            raise ValueError(f"a list of {len(generator)} generators for a batch of {batch}")
+        rows = [(wrap(g.initial_seed()), 0) for g in generator]
+    else:
+        seed = int(torch.randint(0, (1 << 63) - 1, (1,), dtype=torch.int64)) if generator is None else wrap(generator.initial_seed())
+        rows = [(seed, b) for b in range(batch)]
+    return torch.tensor(rows, dtype=torch.int64).reshape(batch, 2)
 
 
 @dataclass(frozen=True)
@@ -706,7 +731,10 @@ class LoopExtras:
     # pag_scale: cfg_scale is 1 + pag_scale and the first half of the conditioning batch is the positive one under the perturbed tables
     # (never together with line_prompts / line_scale; its key part is the last)
     perturbed: Optional[Perturbed] = None
-    line_scale: Optional[LineScale] = None       # control_prompt_scale: a bias per key class for the joint attention of line_prompts
+    # stochastic sampling (the scheduler's switch): the noise streams of the call's samples for ``scheduler.step_master_(stochastic=)``;
+    # its key part, ("stochastic", eta), is appended by ``_graph_signature`` after everything else
+    step_noise: Optional[StepNoise] = None
+    line_scale: Optional[LineScale] = None      # control_prompt_scale: a bias per key class for the joint attention of line_prompts
     quiet: bool = False                          # no progress bar (a capture)
 
     def signature(self, sig, ident, adapter) -> tuple:
@@ -814,7 +842,7 @@ class FluxControlNetPipeline:
                 import sys
                 print(f"[reptext_amd] scheduler class {sched_name!r} is not available; using FlowMatchEulerDiscreteScheduler", file=sys.stderr, flush=True)
             sched_cls = FlowMatchEulerDiscreteScheduler
-        known = set(sched_cls().config.keys())
+        known = set(sched_cls().config.keys()) | set(STOCHASTIC_DEFAULTS)
         scheduler = kwargs.pop("scheduler", None) or sched_cls(**{k: v for k, v in sched_cfg.items() if k in known})
         transformer = kwargs.pop("transformer", None) or FluxTransformer2DModel.from_pretrained(root, torch_dtype=dt, subfolder="transformer")
         vae = kwargs.pop("vae", None) or AutoencoderKL.from_pretrained(root, torch_dtype=dt, subfolder="vae")
@@ -1494,12 +1522,15 @@ class FluxControlNetPipeline:
             row_vis, key_class = perturbed_attention_tables(prompt_embeds.shape[1], latents.shape[1], total)
             perturbed = Perturbed(row_vis.to(device), key_class.to(device), pag[1], pag[2])
         cfg_scale = (float(ext.true_cfg_scale) if true_cfg else pag[0]) if cfg else None
+        # stochastic sampling: the samples' noise streams, named by the call's generator after the start state has drawn from it (without
+        # the switch nothing is built and nothing is drawn)
+        step_noise = StepNoise(stochastic_rng(generator, latents.shape[0]).to(device)) if getattr(self.scheduler, "stochastic_sampling", False) else None
         extras = LoopExtras(ip_embeds=ip_embeds if regional is None else None, union=union, cfg_scale=cfg_scale,
                             repaint=repaint, guidance=loop_guidance(self.guider, cfg, len(timesteps)), line_prompts=line_prompts,
                             regional_ip=regional,
                             line_scale=None if line_scales is None else LineScale(
                                 line_prompt_bias(line_scales, [e is not None for e in line_entries]).to(device)),
-                            perturbed=perturbed)
+                            perturbed=perturbed, step_noise=step_noise)
 
         self._apply_lora_scale()
         latents = self._denoise(latents, prompt_embeds, pooled_prompt_embeds, text_ids, latent_image_ids, timesteps, hints, masks,
@@ -1710,6 +1741,8 @@ class FluxControlNetPipeline:
         key += extras.signature(sig, ident, getattr(self.transformer, "_ip_adapter", None))
         if getattr(self.scheduler, "solver_order", 1) > 1:       # its weights are kernel scalars fixed by the sigmas and timesteps in the key
             key += (("solver", self.scheduler.solver_order),)
+        if extras.step_noise is not None:       # eta is a kernel scalar, like the step index each node bakes; the seeds are a static input
+            key += (("stochastic", self.scheduler.stochastic_eta),)
         return key, dict(base, hints=list(hints), masks=list(masks), **extras.tensors())
 
     def _capture_loop(self, ins, extras, loop):          # on clones of ``ins`` -> the graph's cache entry, or "failed": an optimisation, never a requirement
@@ -1875,6 +1908,8 @@ class FluxControlNetPipeline:
         if gd is not None and gd.guider.projected and gd.steps:
             proj = ProjectedStep(gd.guider.eta, gd.guider.norm_threshold, gd.guider.momentum, torch.empty_like(lat32),
                                  torch.empty(ops.guidance_partials_shape(B, lat32[0].numel()), device=device, dtype=torch.float32))
+        # stochastic sampling: the scheduler's record of the call's noise streams; every step draws at its absolute step index
+        stoch = None if extras.step_noise is None else self.scheduler.stochastic_step(extras.step_noise.rng)
         Bc = prompt_embeds.shape[0]
         pos_rows = slice(Bc - B, Bc)
 
@@ -1962,7 +1997,8 @@ class FluxControlNetPipeline:
                 cfg = extras.cfg_scale is not None and guided  # then noise_pred is [negative, positive], B each
                 pj = proj if cfg else None                     # this step's guidance difference goes where the one before is read from
                 self.scheduler.step_master_(noise_pred[:B] if cfg else noise_pred, lat32, latents, v_text=noise_pred[B:] if cfg else None,
-                                            s=extras.cfg_scale if cfg else None, repaint=extras.repaint, history=hist, projected=pj)
+                                            s=extras.cfg_scale if cfg else None, repaint=extras.repaint, history=hist, projected=pj,
+                                            **({} if stoch is None else dict(stochastic=stoch)))
                 if pj is not None:
                     pj.first = False
                 if callback is not None:

@@ -131,6 +131,8 @@ class FluxControlNetPipeline(_BasePipeline):
             raise ValueError("the inpaint pipeline does not support per-line prompts (control_prompt_scale)")
         if getattr(ext, "pag_scale", 0.0) or getattr(ext, "pag_applied_layers", None) is not None:
             raise ValueError("the inpaint pipeline does not support perturbed-attention guidance (pag_scale / pag_applied_layers)")
+        if getattr(self.scheduler, "stochastic_sampling", False):
+            raise ValueError("the inpaint pipeline does not support stochastic sampling (the scheduler's stochastic_sampling)")
         self._guidance_scale, self._joint_attention_kwargs, self._interrupt = guidance_scale, joint_attention_kwargs, False
         cfg = self.do_classifier_free_guidance                          # enabled by guidance_scale > 1, scaled by true_guidance_scale (Q8)
         device, dtype = self._execution_device, self.transformer.dtype

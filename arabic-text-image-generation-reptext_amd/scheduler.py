@@ -10,6 +10,7 @@ one model evaluation per step as before, plus the velocity of the step before in
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from typing import List, Optional, Union
 
 import numpy as np
@@ -26,11 +27,32 @@ def calculate_shift(image_seq_len, base_seq_len: int = 256, max_seq_len: int = 4
     return image_seq_len * slope + (base_shift - slope * base_seq_len)
 
 
+# stochastic sampling: diffusers' switch and this package's eta, with their defaults; a config holds a key only where its value is
+# not the default, so a scheduler without the switch saves the file it always saved
+STOCHASTIC_DEFAULTS = {"stochastic_sampling": False, "stochastic_eta": 1.0}
+
+
+@dataclass(frozen=True)
+class StochasticStep:
+    """What ``step_master_(stochastic=)`` takes: ``rng`` int64 [B, 2] on the state's device, (seed, subsequence) per sample
+    (``pipeline.stochastic_rng``), and the two eta scalars (``FlowMatchEulerDiscreteScheduler.stochastic_step`` forms them)."""
+    rng: torch.Tensor
+    eta: float
+    sqrt_1m_eta2: float
+
+
 class FlowMatchEulerDiscreteScheduler:
     order = 1
 
     def __init__(self, **config):
+        stochastic = {k: config.pop(k, default) for k, default in STOCHASTIC_DEFAULTS.items()}
+        if not isinstance(stochastic["stochastic_sampling"], bool):
+            raise ValueError(f"stochastic_sampling must be a bool, got {stochastic['stochastic_sampling']!r}")
+        eta = stochastic["stochastic_eta"] = float(stochastic["stochastic_eta"])
+        if not 0.0 < eta <= 1.0:          # 0 is the Euler step, reached in the limit only: it draws nothing and is this scheduler without the switch
+            raise ValueError(f"stochastic_eta must lie in (0, 1], got {eta}")
         self.config = flux_scheduler_config(**config)
+        self.config.update({k: v for k, v in stochastic.items() if v != STOCHASTIC_DEFAULTS[k]})
         self.timesteps: Optional[torch.Tensor] = None
         self.sigmas: Optional[torch.Tensor] = None      # host fp32, n+1 entries (trailing 0)
         self._step_index: Optional[int] = None
@@ -44,6 +66,19 @@ class FlowMatchEulerDiscreteScheduler:
     @property
     def step_index(self):
         return self._step_index
+
+    @property
+    def stochastic_sampling(self) -> bool:
+        return bool(self.config.get("stochastic_sampling", False))
+
+    @property
+    def stochastic_eta(self) -> float:
+        return float(self.config.get("stochastic_eta", 1.0))
+
+    def stochastic_step(self, rng: torch.Tensor) -> StochasticStep:
+        """The ``stochastic=`` record of this scheduler's eta for a call's ``rng``; sqrt(1 − eta²) in double."""
+        eta = self.stochastic_eta
+        return StochasticStep(rng, eta, math.sqrt(max(0.0, 1.0 - eta * eta)))
 
     def set_begin_index(self, begin_index: int = 0):
         self._begin_index = begin_index
@@ -113,7 +148,7 @@ class FlowMatchEulerDiscreteScheduler:
 
     def step_master_(self, v: torch.Tensor, sample32: torch.Tensor, sample_bf16: Optional[torch.Tensor] = None, *,
                      v_text: Optional[torch.Tensor] = None, s: Optional[float] = None, repaint=None,
-                     history: Optional[torch.Tensor] = None, projected=None) -> None:
+                     history: Optional[torch.Tensor] = None, projected=None, stochastic: Optional[StochasticStep] = None) -> None:
         """In-place step on an fp32 master copy of the latents (used by this repo's pipelines between steps; ``step`` keeps
         the diffusers contract of returning the model dtype), one kernel. Advances the step index exactly like ``step``.
         ``v_text``: true CFG, the velocity is ``v + s·(v_text − v)`` (``v`` the unconditional half), mixed in fp32 inside the kernel and
@@ -123,10 +158,21 @@ class FlowMatchEulerDiscreteScheduler:
         place, two kernels; its ``diff`` receives this step's guidance difference and is read unless ``projected.first`` (no momentum
         on the first guided step of a run); ``s − 1`` is formed from the scale in double inside the op. ``history`` (the multistep
         scheduler's; fp32, the state's shape) is read unless it is empty — it may then be uninitialised memory — and receives this
-        step's velocity, under true CFG the mixed or projected one in fp32; the blend of a repaint comes after."""
+        step's velocity, under true CFG the mixed or projected one in fp32; the blend of a repaint comes after. ``stochastic`` (a
+        ``StochasticStep``; a scheduler with ``stochastic_sampling`` needs it, any other takes the rule from it all the same): the
+        predicted clean image ``x − σ·v`` re-noised to the next sigma in the Euler rule's place, with fresh noise drawn inside the kernel
+        from (``rng``, the absolute step index); after the last step it is the clean image itself. ``sample32``'s leading dimension is
+        then the batch."""
         history = self._history(history)
+        if stochastic is None and self.stochastic_sampling:
+            raise ValueError("step_master_: a scheduler with stochastic_sampling needs stochastic= (scheduler.stochastic_step(rng))")
+        if stochastic is not None and history is not None:
+            raise ValueError("step_master_: stochastic= and history= exclude each other (stochastic sampling is first order)")
         sigma, sigma_next, w = self._advance_weight()
         rp = {} if repaint is None else dict(sigma_next=float(sigma_next), src32=repaint.src32, noise32=repaint.noise32, mask=repaint.mask)
+        if stochastic is not None:
+            rp = dict(rp, sigma_next=float(sigma_next), stochastic=ops.StochasticArgs(
+                stochastic.rng, float(sigma), stochastic.eta, stochastic.sqrt_1m_eta2, self._step_index - 1))
         if projected is None:
             ops._master_step_f32("step_master_", sample32, v.contiguous(), None if v_text is None else v_text.contiguous(), float(s or 0.0),
                                  float(sigma_next - sigma), sample_bf16, hist=history, w=w, **rp)
@@ -150,7 +196,22 @@ class FlowMatchEulerDiscreteScheduler:
         return sigma * noise + (1.0 - sigma) * sample
 
     def step(self, model_output: torch.Tensor, timestep: Union[float, torch.Tensor], sample: torch.Tensor,
-             return_dict: bool = True, **unused):
+             return_dict: bool = True, generator=None, **unused):
+        """The diffusers contract: the sample comes and goes in the model dtype. With ``stochastic_sampling`` the step is the op of
+        ``step_master_`` on an fp32 temporary, and ``generator`` (one, a list per sample, or None: ``pipeline.stochastic_rng``) names the
+        noise streams; the sample's leading dimension is the batch."""
+        if self.stochastic_sampling:
+            from .pipeline import stochastic_rng
+
+            sigma, sigma_next = self._advance()
+            x32 = sample.to(torch.float32).contiguous().clone()
+            if x32.dim() < 2:
+                x32 = x32[None]
+            st = self.stochastic_step(stochastic_rng(generator, x32.shape[0]).to(x32.device))
+            ops.stochastic_step_f32_(x32, model_output.contiguous().view(x32.shape), ops.StochasticArgs(
+                st.rng, float(sigma), st.eta, st.sqrt_1m_eta2, self._step_index - 1), float(sigma_next))
+            prev = x32.view(sample.shape).to(model_output.dtype)
+            return (prev,) if not return_dict else Config(prev_sample=prev)
         sigma, sigma_next = self._advance()
         prev = sample.to(model_output.dtype).clone()
         ops.euler_step_(prev, model_output.contiguous(), float(sigma_next - sigma))
@@ -192,6 +253,9 @@ class FlowMatchMultistepScheduler(FlowMatchEulerDiscreteScheduler):
         if solver_order not in (1, 2):
             raise ValueError(f"solver_order {solver_order} is not supported (1 or 2)")
         super().__init__(**config)
+        if solver_order > 1 and self.stochastic_sampling:
+            raise ValueError("stochastic_sampling needs solver_order=1: the velocity of the step before belongs to a state that the "
+                             "fresh noise has replaced, it is no history of the same trajectory")
         self.config["solver_order"] = solver_order
         self._history_len = 0                       # velocities the history holds: 0 or 1
         self._step_history: Optional[torch.Tensor] = None       # the history of ``step`` (the diffusers contract), fp32
@@ -199,7 +263,7 @@ class FlowMatchMultistepScheduler(FlowMatchEulerDiscreteScheduler):
     @classmethod
     def from_config(cls, config):
         """From a saved config of this class or of the Euler class; keys of other schedulers are ignored, as the loader ignores them."""
-        known = set(flux_scheduler_config().keys()) | {"solver_order"}
+        known = set(flux_scheduler_config().keys()) | {"solver_order"} | set(STOCHASTIC_DEFAULTS)
         return cls(**{k: v for k, v in dict(config).items() if k in known})
 
     @property
@@ -240,7 +304,7 @@ class FlowMatchMultistepScheduler(FlowMatchEulerDiscreteScheduler):
     def step(self, model_output: torch.Tensor, timestep: Union[float, torch.Tensor], sample: torch.Tensor,
              return_dict: bool = True, **unused):
         if self.solver_order == 1:
-            return super().step(model_output, timestep, sample, return_dict=return_dict)
+            return super().step(model_output, timestep, sample, return_dict=return_dict, **unused)
         hist = self._step_history if self._history_len > 0 else None
         if hist is None or hist.shape != sample.shape or hist.device != sample.device:
             self._history_len = 0

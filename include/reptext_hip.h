@@ -572,6 +572,38 @@ int rt_projected_step_f32(float* x, const void* v_uncond, const void* v_text, vo
                           const float* partials, float s_minus_1, float eta, float tau, float* hist /* nullable */, float w,
                           const float* src /* nullable */, const float* noise /* nullable */, const float* mask /* nullable */,
                           float dsigma, float sigma_next, int32_t B, int64_t n_s, int64_t n_mask, void* stream);
+/* Stochastic sampling (the scheduler's stochastic_sampling switch; diffusers' rule at eta = 1, recalled, parity unpinned): one more form
+ * of the same step. vel is the velocity the step already has (plain, the mix, or the projected form); per element, every product and
+ * sum rounded once:
+ *   x0 = x − sigma·vel
+ *   e  = x0 + vel                                             only where eta < 1: the noise the state holds at sigma
+ *   n  = eta < 1 ? sqrt_1m_eta2·e + eta·z : z                 z: a fresh standard normal
+ *   r  = (1 − sigma_next)·x0 + sigma_next·n                   then the blend and x_bf16 as above
+ * sigma_next = 0 (the last step) gives r = x0: no z is drawn and rng is not read (it may be NULL). eta lies in (0, 1];
+ * sqrt_1m_eta2 = sqrt(1 − eta²) comes from the host, formed in double.
+ * z is drawn inside the kernel from Philox4x32-10 (csrc/philox.h): one call per group of four consecutive elements of a sample,
+ *   counter = (g low, g high, step, subsequence)   g = (index inside the sample) / 4
+ *   key     = (seed low, seed high ^ 0x53544F43)
+ *   u = ((w >> 8) + 0.5)·2^-24;  z0 = r·cos θ, z1 = r·sin θ with r = sqrt(−2 ln u(w0)), θ = 2π·u(w1);  z2, z3 from w2, w3
+ * with (seed, subsequence) = rng[b][0..1] (int64 [B][2], device memory) of the element's sample b. z depends on (seed, subsequence,
+ * step, index inside the sample) alone: not on B, on the other samples, or on which path of the kernel takes the element (16-byte
+ * groups only when n_s % 4 == 0 and the pointers are aligned; the one-element path runs Philox for the element's group and picks its
+ * lane). There is no noise tensor and no generator state: step is a kernel scalar, the scheduler's absolute step index.
+ * rt_normal_fill_f32 writes that z to out (fp32 [B][n_s]), the same bits.
+ * The mask's rule is m = mask[i % n_mask] over the flat index i of [B][n_s], as in rt_projected_step_f32.
+ * NULL x / v (v_uncond, v_text, diff, partials) / out, NULL rng with sigma_next != 0, B < 1, n_s < 1, n_mask < 1, a mask without src
+ * and noise, eta outside (0, 1], step < 0: RT_E_BADARG; B > 65535, (B·n_s) % n_mask != 0: RT_E_SHAPE.
+ * Added without an ABI bump: nothing existing changed. */
+int rt_stochastic_step_f32(float* x, const void* v, const void* v_text /* nullable */, void* x_bf16 /* nullable */,
+                           const float* src /* nullable */, const float* noise /* nullable */, const float* mask /* nullable */,
+                           const int64_t* rng, float s, float sigma, float sigma_next, float eta, float sqrt_1m_eta2, int32_t step,
+                           int32_t B, int64_t n_s, int64_t n_mask, void* stream);
+int rt_projected_stochastic_step_f32(float* x, const void* v_uncond, const void* v_text, void* x_bf16 /* nullable */, const float* diff,
+                                     const float* partials, float s_minus_1, float eta_guidance, float tau,
+                                     const float* src /* nullable */, const float* noise /* nullable */, const float* mask /* nullable */,
+                                     const int64_t* rng, float sigma, float sigma_next, float eta, float sqrt_1m_eta2, int32_t step,
+                                     int32_t B, int64_t n_s, int64_t n_mask, void* stream);
+int rt_normal_fill_f32(float* out, const int64_t* rng, int32_t B, int64_t n_s, int32_t step, void* stream);
 
 /* _pack_latents / _unpack_latents (PIPE:550-570): [B][C][2h][2w] <-> [B][h*w][4C], channel order (c,dy,dx).
  * unpack also applies z/scaling + shift (PIPE:1137) and writes NHWC bf16 [B][H2][W2][C]. */

@@ -87,7 +87,12 @@ ap.add_argument("--strength", type=float, default=0.6, help="share of the schedu
 ap.add_argument("--photo-crop", type=int, default=None, help="with --source-image: keep the photo at its size and repaint only the region around "
                 "the text, this many pixels of padding around the lines' boxes (the photo pipeline's padding_mask_crop=)")
 ap.add_argument("--mask-blur", type=float, default=4.0, help="sigma of the feather under which the photo flow blends the result into the photo")
+ap.add_argument("--stochastic", action="store_true", help="stochastic sampling (the scheduler's stochastic_sampling): every step re-noises the "
+                "predicted clean image to the next sigma, with noise drawn inside the step kernel from the generator's seed; not with --inpaint")
+ap.add_argument("--stochastic-eta", type=float, default=1.0, metavar="E", help="with --stochastic: the share of fresh noise, in (0, 1] (stochastic_eta)")
 a = ap.parse_args()
+if a.stochastic and a.inpaint:
+    ap.error("--stochastic: the inpaint pipeline does not support stochastic sampling")
 dev, bf16 = torch.device("cuda:0"), torch.bfloat16
 ct, cc = flux_dev_transformer_config(), reptext_controlnet_config()
 if a.depth_scale != 1.0:
@@ -102,7 +107,8 @@ if a.source_image and a.photo_crop is not None:
 elif a.source_image:
     from pipeline_flux_controlnet_repaint import FluxControlNetRepaintPipeline as pipeline_class      # the same components
 
-pipe = pipeline_class(FlowMatchEulerDiscreteScheduler(), AutoencoderKL(**flux_vae_config(), device=dev, dtype=bf16).random_init_(seed=2),
+scheduler_config = dict(stochastic_sampling=True, stochastic_eta=a.stochastic_eta) if a.stochastic else {}
+pipe = pipeline_class(FlowMatchEulerDiscreteScheduler(**scheduler_config), AutoencoderKL(**flux_vae_config(), device=dev, dtype=bf16).random_init_(seed=2),
                               None, None, None, None, FluxTransformer2DModel(**ct, device=dev, dtype=bf16).random_init_(seed=0), controlnet)
 pipe.set_progress_bar_config(disable=True)
 
